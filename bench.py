@@ -2,10 +2,18 @@
 """
 bench.py -- throughput of the hot path (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config fbank16k|mfcc40_libri|onthefly] [--cuts C]
-                    [--no-cpu-baseline] [--no-host-fed] [--no-parity]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config fbank16k|mfcc40_libri|onthefly] [--cuts C] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-host-fed] [--no-parity]]
 
 A "step" is ONE pass of the feature-extraction path over one batch of synthetic cuts that is already resident in HBM.
+
+A plain run does only what the headline figure needs: set-up, warm-up, exactly K timed steps, the outputs (--dump-outputs) and the
+line.  Everything else the line can carry -- `parity`, `extra` (the other BASELINE configs among them) and `cpu_baseline` below --
+runs only with --full; the --no-* switches narrow a --full run.
+
+--dump-outputs DIR writes what the LAST timed step computed as DIR/<name>.npy (features float32, frame counts of ragged outputs
+float64): a fixed, seeded sample of DUMP_CUTS cuts (rank 0's), the same for the same arguments from run to run and from build to
+build, so that two builds can be compared output by output.
 
   --config fbank16k (default) BASELINE.json configs[1]: C (default 10 000) cuts x 10 s @ 16 kHz float32 -> C x (1000, 80) float32 log-mel,
                               one launch.  All cuts hold distinct random data (6.4 GB of input per GPU, far beyond the 256 MiB Infinity Cache).
@@ -61,6 +69,8 @@ HBM_PEAK = 8.0e12  # B/s, MI355X spec (MI355X_MICROARCH.md)
 NUM_SIMDS = 256 * 4
 MAX_CLOCK = 2.4e9
 PARITY_CUTS = 64
+DUMP_CUTS = 48  # cuts per --dump-outputs sample: <= 64 MB in all even for the longest cuts a config draws (30 s at speed 0.9)
+DUMP_LIMIT = 64 << 20
 LOG_EPSILON = -23.025850929940457  # lhotse/utils.py:50-51
 
 
@@ -251,6 +261,32 @@ def fbank16k_parity_indices(cuts: int, rank: int):
     return np.sort(rs.choice(cuts, size=min(PARITY_CUTS, cuts), replace=False))
 
 
+def dump_indices(cuts: int):
+    """The cuts of the last timed step that --dump-outputs writes: a fixed, seeded sample."""
+    import numpy as np
+
+    return np.sort(np.random.RandomState(2718).choice(cuts, size=min(DUMP_CUTS, cuts), replace=False))
+
+
+def read_stored(manifest: str, idx):
+    """(len(idx), frames, bins): the cuts `idx` of a stored pass, read back through its gzip JSONL manifest and the archive reader(s)
+    the manifest names."""
+    import gzip
+
+    import numpy as np
+
+    from lhotse_amd import storage as S
+
+    with gzip.open(manifest, "rt") as f:
+        feats = [json.loads(ln)["features"] for ln in f]
+    readers, got = {}, []
+    for j in idx:
+        d = feats[int(j)]
+        reader = readers.get(d["storage_path"]) or readers.setdefault(d["storage_path"], S.HipArchiveReader(d["storage_path"]))
+        got.append(reader.read(d["storage_key"]))
+    return np.stack(got)
+
+
 class Fbank16k:
     """BASELINE configs[1]."""
 
@@ -346,6 +382,11 @@ class Fbank16k:
             stats.append(compare(got, want, truth, alt32=n32.extract(x)))
         return fold(stats)
 
+    def outputs(self):
+        """(cuts, 1000, 80) log-mel features of the sampled cuts."""
+        idx = self.torch.from_numpy(dump_indices(self.C)).to(self.out.device)
+        return {"fbank": self.out.view(self.C, FRAMES_PER_CUT, NUM_MELS).index_select(0, idx).cpu().numpy()}
+
     def extra(self, args):
         return {} if args.no_host_fed else {"host_fed_cuts_per_s": host_fed(self.ex)}
 
@@ -438,6 +479,12 @@ class Mfcc40Libri:
             assert got.shape == want.shape, (got.shape, want.shape)
             stats.append(compare(got, want, truth, log_mel=False))  # cepstra: no linear-domain reading
         return fold(stats)
+
+    def outputs(self):
+        """The sampled cuts' MFCC rows one after the other, and each cut's number of rows."""
+        idx = dump_indices(self.C)
+        rows = self.torch.cat([self.torch.arange(int(self.rows[i]), int(self.rows[i + 1])) for i in idx]).to(self.out.device)
+        return {"mfcc": self.out.index_select(0, rows).cpu().numpy(), "mfcc_num_frames": self.frames[idx].astype(self.np.float64)}
 
     def extra(self, args):
         return {}
@@ -602,6 +649,24 @@ class OnTheFly:
             assert bool((f[row, int(fl[i]) :] == LOG_EPSILON).all()), "padding rows of the collated batch"
             stats.append(compare(got, want, truth))
         return fold(stats)
+
+    def outputs(self):
+        """The sampled cuts' feature rows (their padding rows left out) one after the other, and each cut's number of rows."""
+        np = self.np
+        first = np.cumsum([0] + [len(bt["lens"]) for bt in self.batches])
+        parts, frames = [], []
+        for g in dump_indices(self.units):
+            b = int(np.searchsorted(first, g, side="right")) - 1
+            i = int(g - first[b])
+            f, fl = self.feats[b][:2]
+            if isinstance(f, list):  # --prefetch K: the mini-batch of cut i, and the cut's row in that mini-batch's tensor
+                j = int(np.searchsorted(self.batches[b]["first"], i, side="right")) - 1
+                f, row = f[j], i - int(self.batches[b]["first"][j])
+            else:
+                row = i
+            parts.append(f[row, : int(fl[i])])
+            frames.append(int(fl[i]))
+        return {"fbank": self.torch.cat(parts).cpu().numpy(), "fbank_num_frames": np.asarray(frames, dtype=np.float64)}
 
     def _rate(self, seconds: float = 1.0):
         """(cuts/s, host microseconds per mini-batch) of the current route.  The host figure is the wall time of enqueueing a burst of
@@ -909,6 +974,10 @@ class BulkSave:
             stats.append(compare(got, o32.extract(x), o64.extract(x)))
         return fold(stats)
 
+    def outputs(self):
+        """The sampled cuts as the last timed pass stored them."""
+        return {"fbank": read_stored(os.path.join(self.last_root, "cuts.jsonl.gz"), dump_indices(self.units))}
+
     def extra(self, args):
         """The other entry forms / storages and round 4's per-cut route, a few passes each, with the stage split of every variant."""
         out = {}
@@ -1038,6 +1107,10 @@ class Plumbing:
             x = P.read_wav(self.cuts[int(j)].path)[0]
             stats.append(compare(P.read_back(self.last, int(j)), o32.extract(x), o64.extract(x)))
         return fold(stats)
+
+    def outputs(self):
+        """The sampled cuts as the last timed pass stored them."""
+        return {"fbank": read_stored(self.last["manifest"], dump_indices(self.units))}
 
     def _fresh(self, *flags, repeat=None):
         """One leg in a FRESH process (tools/plumbing.py main): the GPU is first touched at the first batch, after the loader's workers were
@@ -1207,6 +1280,11 @@ class SelfTestStub:
         want = (truth + 1e-6 * rs.randn(50, 80)).astype(np.float32)
         got = (want + np.float32(1e-6) * rs.randn(50, 80).astype(np.float32)).astype(np.float32)
         return fold([compare(got, want, truth)])
+
+    def outputs(self):
+        import numpy as np
+
+        return {"selftest": np.arange(self.units, dtype=np.float32) + self.rank}
 
     def extra(self, args):
         return {"host_fed_cuts_per_s": {"batch_60": 100.0 * (self.rank + 1), "what": "self-test"}}
@@ -1451,6 +1529,20 @@ def timed_region(w, steps: int, warmup: int, dev, dist, cdev, world: int):
         dist.all_reduce(s, op=dist.ReduceOp.SUM)
         units_total, audio_total = float(s[0]), float(s[1])
     return {"elapsed": elapsed, "launch_ms": launch_ms, "rank_launch_ms": rank_launch_ms, "units_total": units_total, "audio_total": audio_total}
+
+
+def dump_outputs(w, out_dir: str) -> None:
+    """--dump-outputs: the workload's sample of what its last timed step computed, one float32 / float64 DIR/<name>.npy per array."""
+    import numpy as np
+
+    arrays = {name: np.ascontiguousarray(a) for name, a in w.outputs().items()}
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes, over the {DUMP_LIMIT}-byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 PARITY_MAX_KEYS = ["rel_l2_max", "max_abs_max", "oracle_f32_vs_f64_rel_l2_max", "oracle_f32_vs_f64_max_abs", "hip_vs_f64_max_abs",
@@ -1735,7 +1827,13 @@ def main():
     ap.add_argument("--cpu-procs", type=int, default=0, help="host processes of the CPU baseline (default: best of a sweep over cores/8, cores/4, cores/2)")
     ap.add_argument("--input", default="uniform", choices=["uniform", "zeros", "sine"], help="fbank16k: synthetic input (the metric is defined on `uniform`; the others exist to expose power/DVFS effects)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default; falls back to gloo if it cannot be initialised) or gloo (self-test of the N>1 path on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also the in-run parity leg, the other BASELINE configs, the PCIe-inclusive and after-idle legs (`extra`) "
+                    "and the CPU baseline; the --no-* switches narrow a --full run.  Default: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write a fixed, seeded sample of what the last timed step computed "
+                    f"(rank 0's: {DUMP_CUTS} cuts, <= 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_host_fed = args.no_parity = args.no_extra = args.no_other_configs = True
     if not args.steps:
         args.steps = {"fbank16k": 250, "mfcc40_libri": 200, "onthefly": 60, "bulk_save": 5, "plumbing": 3}[args.config]
 
@@ -1776,6 +1874,8 @@ def main():
 
     tr = timed_region(w, args.steps, args.warmup, dev, dist, cdev, world)
     elapsed, launch_ms = tr["elapsed"], tr["launch_ms"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)
 
     # ---- parity in the same run, on every rank, on the timed output buffer
     parity = None

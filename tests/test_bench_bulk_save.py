@@ -44,6 +44,12 @@ def test_bulk_save_workload_writes_what_the_extractor_computes(monkeypatch, stri
     par = w.parity(0)
     # stored == what the (numpy-oracle-backed) plan computed; ref32 of the parity leg is the torch restatement since round 5: rounding apart
     assert par["n"] == 8 and par["rel_l2_max"] < 1e-5
+    # --dump-outputs: the seeded sample of cuts as the last timed pass stored them
+    dump = w.outputs()["fbank"]
+    flat = [i for _, idx, _ in w.batches for i in idx]
+    assert dump.shape == (48, 100, 80) and dump.dtype == np.float32
+    for k, j in list(enumerate(bench.dump_indices(120)))[:3]:
+        assert np.array_equal(dump[k], w.ex.extract(w.pool32[flat[j]].numpy(), 16000))
     # round 4's per-cut Python route writes the same lines (storage fields apart: its archive is one file)
     st4 = {}
     root4 = w._one_pass("float32", "hip_archive", st4, "per_cut")

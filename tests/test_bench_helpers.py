@@ -4,6 +4,9 @@ import json
 import os
 import types
 
+import numpy as np
+import pytest
+
 import bench
 
 
@@ -45,3 +48,16 @@ def test_committed_traffic_json_serves_all_three_baseline_kernels_while_the_sour
         c = bench.load_profile_constants("fft512c_kernel<13> whatever", name)
         assert c.get("stale") or 1.0 <= c["hbm_bytes_per_algorithmic_byte"] < 1.5
     assert bench.load_profile_constants("some_other_kernel", "onthefly") == {}
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit_and_refuses_others(tmp_path):
+    w = types.SimpleNamespace(outputs=lambda: {"feats": np.ones((2, 3), np.float32), "num_frames": np.arange(4, dtype=np.float64)})
+    bench.dump_outputs(w, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == ["feats.npy", "num_frames.npy"]
+    assert np.load(tmp_path / "d" / "feats.npy").dtype == np.float32 and np.load(tmp_path / "d" / "num_frames.npy").tolist() == [0, 1, 2, 3]
+    for bad in ({"h": np.ones(4, np.float16)}, {"big": np.zeros(bench.DUMP_LIMIT // 4 + 1, np.float32)}):
+        with pytest.raises(AssertionError):
+            bench.dump_outputs(types.SimpleNamespace(outputs=lambda: bad), str(tmp_path / "bad"))
+    assert not (tmp_path / "bad").exists()
+    assert list(bench.dump_indices(10)) == list(range(10)) and np.array_equal(bench.dump_indices(10000), bench.dump_indices(10000))
+    assert len(bench.dump_indices(10000)) == bench.DUMP_CUTS

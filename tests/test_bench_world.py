@@ -9,18 +9,19 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(world: int, steps: int = 4, warmup: int = 2):
+def _run(world: int, steps: int = 4, warmup: int = 2, *flags):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     env = dict(os.environ, BENCH_SELFTEST_STUB="1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup)]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), *flags]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -32,7 +33,7 @@ def _run(world: int, steps: int = 4, warmup: int = 2):
 @pytest.mark.parametrize("world", [8, 2])
 def test_one_json_line_from_eight_ranks(world):
     steps, warmup = 4, 2
-    r = _run(world, steps, warmup)
+    r = _run(world, steps, warmup, "--full")
     cfg = r["config"]
     assert r["n_gpus"] == world and r["steps"] == steps and r["warmup"] == warmup and r["higher_is_better"] is True and r["scaling"] == "weak"
     assert "SELFTEST" in cfg and cfg["world_size"] == world and cfg["dist_backend"].startswith("gloo")
@@ -53,3 +54,12 @@ def test_one_json_line_from_eight_ranks(world):
     par = r["parity"]
     assert par["n"] == world and par["pass"] is True and par["statement_version"].startswith("r6")
     assert r["roofline"]["bound"] == "hbm" and "cpu_baseline" not in r
+
+
+def test_the_plain_line_of_two_ranks_carries_the_headline_only_and_dumps_rank_0s_outputs(tmp_path):
+    """Without --full: the contract's timed steps and the line, no parity leg, no `extra`; --dump-outputs writes rank 0's outputs."""
+    r = _run(2, 3, 1, "--dump-outputs", str(tmp_path))
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["n_gpus"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["parity"] is None and "extra" not in r and "cpu_baseline" not in r
+    assert os.listdir(tmp_path) == ["selftest.npy"]
+    assert np.load(tmp_path / "selftest.npy").tolist() == list(range(10))

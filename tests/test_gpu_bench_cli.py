@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,11 +13,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*flags, env=None):
+def _bench(*flags, env=None, full=True):
     e = dict(os.environ)
     e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     e.update(env or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-host-fed", *flags], capture_output=True, text=True,
+    extra = ["--full", "--no-cpu-baseline", "--no-host-fed"] if full else []
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *extra, *flags], capture_output=True, text=True,
                        env=e, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -89,3 +91,32 @@ def test_the_default_line_carries_the_other_baseline_configs_and_both_regimes():
     assert len(ramp) == 10 and all(x > 0 for x in ramp)
     assert 0.7 * res["value"] < res["extra"]["contract_only"]["value"] < 1.05 * res["value"]
     assert res["parity"]["pass_rel_l2"] and res["parity"]["pass_linear"]
+
+
+PLAIN = {"fbank16k": ("400", {"fbank": (48, 1000, 80)}), "mfcc40_libri": ("100", {"mfcc": (None, 40), "mfcc_num_frames": (48,)}),
+         "onthefly": ("6", {"fbank": (None, 80), "fbank_num_frames": (48,)}), "bulk_save": ("1", {"fbank": (48, 1000, 80)}),
+         "plumbing": ("1", {"fbank": (48, 1000, 80)})}
+
+
+@pytest.mark.parametrize("config", sorted(PLAIN))
+def test_a_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_every_time(config, tmp_path):
+    """The plain form (no --full): the headline figure only -- no parity leg, no `extra`, no CPU baseline -- exactly --steps timed
+    steps, and --dump-outputs writes the same seeded sample of the last timed step's outputs from run to run (checked on the
+    headline config and on the multi-stream one)."""
+    cuts, shapes = PLAIN[config]
+    runs = []
+    for k in range(2 if config in ("fbank16k", "onthefly") else 1):
+        res, err = _bench("--config", config, "--cuts", cuts, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / f"run{k}"), full=False)
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0, err[-1500:]
+        assert res["parity"] is None and "extra" not in res and "cpu_baseline" not in res
+        assert res["metric"].startswith("cuts/sec") and res["unit"] == "cuts/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        runs.append({p.stem: np.load(p) for p in (tmp_path / f"run{k}").iterdir()})
+    assert set(runs[0]) == set(shapes) and sum(a.nbytes for a in runs[0].values()) <= 64 << 20
+    for name, shape in shapes.items():
+        a = runs[0][name]
+        assert a.dtype in (np.float32, np.float64) and len(a.shape) == len(shape) and all(s is None or s == n for s, n in zip(shape, a.shape)), (name, a.shape)
+        assert np.isfinite(a).all() and all(np.array_equal(a, r[name]) for r in runs[1:]), name
+    feats = runs[0]["mfcc" if config == "mfcc40_libri" else "fbank"]
+    assert float(feats.std()) > 0.1
+    if config in ("mfcc40_libri", "onthefly"):
+        assert feats.shape[0] == int(runs[0][("mfcc" if config == "mfcc40_libri" else "fbank") + "_num_frames"].sum())

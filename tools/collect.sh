@@ -4,7 +4,7 @@
 #   tools/collect.sh <outdir under gpurun_out> <section> [<section> ...]        e.g.  gpurun -- 'tools/collect.sh r6_final bench stats suite smoke'
 #
 # sections (each writes its files under gpurun_out/<outdir>/; copy what is to be judged into profiles/ with the round's prefix):
-#   bench        the driver's form of the bench line (`--steps 20 --warmup 5`, every BASELINE config in it) + the default-steps form
+#   bench        the bench line with everything in it (`--full --steps 20 --warmup 5`, every BASELINE config) + the default-steps form
 #   stats        rocprofv3 --kernel-trace --stats of the headline command -> kernel_stats.txt (tools/rocprof_summary.py)
 #   pmc          SQ counters of the three BASELINE kernels in separate --pmc passes (tools/pmc_any.sh) -> pmc_<config>/summary.txt
 #   traffic      FETCH_SIZE / WRITE_SIZE passes of the three BASELINE kernels -> traffic_<config>/summary.txt (tools/make_traffic_json.py)
@@ -29,14 +29,14 @@ for section in "$@"; do
   echo "== $section"
   case $section in
     bench)
-      timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "rc=$?"
-      timeout 600 python bench.py --no-cpu-baseline --no-extra > "$OUT/bench_default_steps.json" 2> /dev/null
+      timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "rc=$?"
+      timeout 600 python bench.py --full --no-cpu-baseline --no-extra > "$OUT/bench_default_steps.json" 2> /dev/null
       tail -c 300 "$OUT/bench.json"; echo ;;
     stats)
       prof_env
       # (BENCH_NO_PLUMBING: under rocprofv3's preloaded tool a multiprocessing fork server cannot restore its signal handlers, its workers die
       #  and the server itself never exits -- rocprofv3 then waits for it for ever; the kernels of the line are what is profiled here)
-      BENCH_NO_PLUMBING=1 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-fed > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err"
+      BENCH_NO_PLUMBING=1 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-fed > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err"
       summarise "$OUT/prof" "$OUT/kernel_stats.txt"; head -12 "$OUT/kernel_stats.txt" ;;
     pmc)
       for cfg in fbank16k mfcc40_libri onthefly; do
@@ -61,15 +61,15 @@ for section in "$@"; do
       cp profiles/traffic.json "$OUT/traffic.json" ;;
     configs)
       for cfg in mfcc40_libri onthefly bulk_save plumbing; do
-        timeout 900 python bench.py --config $cfg > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"; echo "$cfg rc=$?"
+        timeout 900 python bench.py --full --config $cfg > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"; echo "$cfg rc=$?"
       done
-      timeout 900 python bench.py --total-cuts 100000 --steps 10 --no-cpu-baseline --no-extra > "$OUT/bench_total100k.json" 2> "$OUT/bench_total100k.err" ;;
+      timeout 900 python bench.py --full --total-cuts 100000 --steps 10 --no-cpu-baseline --no-extra > "$OUT/bench_total100k.json" 2> "$OUT/bench_total100k.err" ;;
     stripes)
       for n in 1 8 16 32; do
-        timeout 600 python bench.py --config bulk_save --stripes $n --no-cpu-baseline > "$OUT/bench_bulk_save_stripes$n.json" 2> /dev/null; echo "stripes $n rc=$?"
+        timeout 600 python bench.py --full --config bulk_save --stripes $n --no-cpu-baseline > "$OUT/bench_bulk_save_stripes$n.json" 2> /dev/null; echo "stripes $n rc=$?"
       done ;;
     n2)
-      HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --gpus 2 --dist-backend gloo --steps 5 --cuts 2000 --no-cpu-baseline > "$OUT/bench_2ranks_gloo.json" 2> "$OUT/bench_2ranks_gloo.err"
+      HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --steps 5 --cuts 2000 --no-cpu-baseline > "$OUT/bench_2ranks_gloo.json" 2> "$OUT/bench_2ranks_gloo.err"
       echo "rc=$?"; tail -c 400 "$OUT/bench_2ranks_gloo.json"; echo ;;
     rates)
       prof_env

@@ -10,7 +10,7 @@ VAR=$PWD/lhotse_amd/_lib/var_mfcc_tws.so
 for rep in 1 2 3; do
   for which in product variant; do
     if [ $which = variant ]; then export HIPFEAT_LIB=$VAR; else unset HIPFEAT_LIB; fi
-    python bench.py --config mfcc40_libri --steps 100 --no-cpu-baseline --no-extra > "$OUT/${which}_$rep.json" 2> "$OUT/${which}_$rep.err"
+    python bench.py --full --config mfcc40_libri --steps 100 --no-cpu-baseline --no-extra > "$OUT/${which}_$rep.json" 2> "$OUT/${which}_$rep.err"
     python - "$OUT/${which}_$rep.json" $which $rep <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
