@@ -93,6 +93,21 @@ struct StagingSlot {
   bool busy = false;
 };
 
+// The kernel family a plan runs.  hipfeat_plan_create tries the families in a fixed order; the first setup that accepts the
+// configuration claims the plan, the generic kernel takes the rest.
+enum class Route {
+  Generic,   // generic_kernel (kernel_generic.hpp): any configuration
+  Fft512b,   // fft512 "b": 16-frame tiles (fbank / mfcc / spectrogram)
+  Fft256b,   // fft256 "b": 32-frame tiles
+  Wave,      // wave-per-frame kernel: power-of-two fft 512 .. 2048 without a specialised kernel
+  Whisper2,  // whisper: 16 x 25 mixed-radix FFT + banded mel GEMM, normalisation in a separate pass
+  Fft512c,   // fft512 wave-autonomous fbank / mfcc
+  Fft1024c,  // fft1024 wave-autonomous fbank
+  Whisper3,  // whisper wave-autonomous with the normalisation fused
+  Fft2048c,  // fft2048 wave-autonomous fbank
+  Fft256c,   // fft256 wave-autonomous fbank
+};
+
 struct hipfeat_plan {
   hipfeat_config cfg{};
   int device = 0;
@@ -102,6 +117,12 @@ struct hipfeat_plan {
   int npad_left = 0;
   std::string kernel_name = "generic";
   int blocks_per_cu = 0;  // hipOccupancyMaxActiveBlocksPerMultiprocessor for the selected kernel
+  // the launch, recorded by the setup that claims the plan: one workgroup per layout workgroup
+  Route route = Route::Generic;
+  const void* fn = nullptr;       // kernel instance
+  const void* fn_flat = nullptr;  // fft512c: the FLAT instance of ragged batches (nullptr: none)
+  int block = 0;                  // threads per workgroup
+  size_t lds = 0;                 // dynamic LDS bytes
   // device constants
   float* d_window = nullptr;
   float2* d_tw = nullptr;
@@ -112,44 +133,34 @@ struct hipfeat_plan {
   // generic kernel geometry
   int fpb = 8;
   int span = 0, off_z = 0, off_p = 0, off_tw = 0, off_stat = 0, off_mel = 0;
-  size_t lds_bytes = 0;
-  // fft512 fast path
-  int variant = 0;  // 0 generic, 2 fft512 "b" (16-frame tiles), 4 fft256, 5 wave-per-frame, 6 whisper, 7 fft512 "c" (wave-autonomous fbank), 8 fft1024 "c", 9 whisper wave-autonomous + fused normalisation, 10 fft2048 "c", 11 fft256 "c"
+  // fft512 / fft256 "b" kernels
   float* d_mel_a4 = nullptr;
   float* d_dct_consts = nullptr;
-  bool fast_mfcc = false;
-  int fast_out = 0;  // kernel b output stage: 0 fbank, 1 mfcc, 2 (log-)spectrogram
   int lm_stride = 0, dct_groups = 0, dct_floats = 0;
-  int nrows = 0;    // template instance: pass-1 rows that can be non-zero
   int tiles_per_block = 4;
   int xs_floats = 0;
-  size_t fast_lds_bytes = 0;
   int const_floats = 0;
   float* d_lds_consts = nullptr;
   float* d_mel_a = nullptr;
   WaveWork* d_work = nullptr;
-  // fft512 wave-autonomous fbank kernel (variant 7)
+  // wave-autonomous kernels (fft512c, fft256c, fft1024c, fft2048c, whisper3)
   float* d_c_shared = nullptr;  // LDS image: FFT constants | 4x4-block filterbank weights | lane tables
-  int c_shared_floats = 0, c_wtab_off = 0, c_ltab_off = 0, c_xs_floats = 0, c_rounds = 0, c_mode = 0;
+  int c_shared_floats = 0, c_wtab_off = 0, c_ltab_off = 0, c_xs_floats = 0, c_rounds = 0;
   // wave-autonomous kernels: frames per workgroup = fpb_unit (frames of one round of all waves) x rounds, rounds chosen per LAYOUT between 2
   // and c_rounds_max: long launches take many rounds per workgroup (the constant tables and the first, un-overlapped span are paid once per
   // workgroup: 16 instead of 8 rounds is + 4 % on the bench workload), short ones few (enough workgroups to fill the chip)
   int fpb_unit = 0, c_rounds_max = 0;
-  // fft1024 wave-autonomous fbank kernel (variant 8; shares d_c_shared / c_* with variant 7)
+  // fft1024c / fft2048c / whisper3: accumulator sets of the filterbank schedule
   int w_nsets = 0, w_steps[kWMaxSets] = {}, w_step0[kWMaxSets] = {};
-  int w_waves = kWWaves;  // fft1024c: waves per workgroup (12 for the fixed-schedule instances)
-  int w_fixed = 0;  // fft1024c / fft2048c: instance with a compile-time mel schedule (fft1024c_fixed_id)
-  // fft2048 wave-autonomous fbank kernel (variant 10; shares d_c_shared / c_* / w_* with variants 7 and 8)
+  // fft2048c
   float* d_x_twp = nullptr;  // [32][32] v2 W_1024^(q k1)
   int x_waves = 0, x_tws_off = 0, x_tw32_off = 0;
-  bool x_odd = false;
-  // wave-per-frame kernel (variant 5)
+  // wave-per-frame kernel
   float* d_mel_t = nullptr;  // filterbank blob (descriptors + compact weights)
   int mel_maxband = 0;
   int wave_blob_floats = 0;
   bool wave_dct_in_lds = false;
-  size_t wave_lds_bytes = 0;
-  // whisper FFT fast path (variant 6)
+  // whisper2 (whisper3 reads its d_wh2_cs)
   float* d_wh2_cs = nullptr;
   float* d_wh2_tw = nullptr;
   float* d_wh2_mel = nullptr;
@@ -181,7 +192,7 @@ struct hipfeat_layout {
   std::vector<int32_t> block_cut;  // ragged batches: owner of every workgroup (uploaded behind the descriptors; uniform_bpc = -1)
   bool flat = false;               // ragged batch laid out by frame quads (fft512c FLAT instances): first_block = a cut's first quad
   int64_t total_quads = 0;
-  // Whisper (variant 9): per-cut normalisation scratch behind the descriptors, kNormSlots copies handed out round-robin so that
+  // Whisper3: per-cut normalisation scratch behind the descriptors, kNormSlots copies handed out round-robin so that
   // launches of one layout that overlap on different streams do not share one (each copy re-arms itself at the end of its launch)
   // copy k: [total_blocks][2] float workgroup statistics, then [batch] uint32 completion counters (armed = 0)
   unsigned char* d_norm = nullptr;
@@ -304,6 +315,20 @@ static hipError_t ensure_dynamic_lds(const void* fn, size_t bytes) {
   return e;
 }
 
+// The setup that accepts a configuration claims the plan with the instance it runs: the instance's dynamic-LDS limit is raised, its
+// occupancy read (blocks_per_cu, part of the kernel name) and the launch recorded for launch().
+static hipfeat_status claim(hipfeat_plan* p, Route route, const void* fn, int block, size_t lds) {
+  hipError_t e = ensure_dynamic_lds(fn, lds);
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, block, lds) == hipSuccess) p->blocks_per_cu = nb;
+  p->route = route;
+  p->fn = fn;
+  p->block = block;
+  p->lds = lds;
+  return HIPFEAT_OK;
+}
+
 // Mel work split of the fast kernels: band of every 16-mel tile in 8-bin groups, assigned to the 4 waves, and the MFMA
 // A operands in lane order.  Returns false when the filterbank does not fit the static schedule (-> generic kernel).
 static bool build_mel_schedule(const float* h_mel, int M, int K, int prow_stride, int ntiles, WaveWork (&work)[4], std::vector<float>& mel_a) {
@@ -389,38 +414,26 @@ static const void* fft512c_entry() {
   return reinterpret_cast<const void*>(&fft512c_kernel<NROWS, NFULL, MODE, FLAT>);
 }
 
-// (rows, frame length, mode) -> kernel instance; `launch` == false only returns the entry point
 // the (rows, frame length) that have a FLAT instance (ragged batches by frame quads, kernel_fft512c.hpp): the 25 ms @ 16 kHz default
 static bool fft512c_has_flat(int nrows, int N) { return nrows == 13 && N >= 384; }
 
+// (rows, frame length, mode) -> kernel instance
 template <int MODE>
-static const void* fft512c_pick(int nrows, int N, bool launch, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Fft512cParams* fp, bool flat = false) {
+static const void* fft512c_pick(int nrows, int N, bool flat) {
+  if (flat && fft512c_has_flat(nrows, N)) return fft512c_entry<13, 12, MODE, true>();
+  if (nrows == 10) return fft512c_entry<10, 0, MODE>();
   // 25 ms at 16 kHz (N = 400: 12 full rows of 32 samples + a partial one) gets the instance without length masks on the full rows
-#define HF_C_CASE(R, F)                                                                                   \
-  {                                                                                                       \
-    if (launch) hipLaunchKernelGGL((fft512c_kernel<R, F, MODE>), grid, block, lds, stream, *fp);          \
-    return fft512c_entry<R, F, MODE>();                                                                   \
-  }
-  if (flat && fft512c_has_flat(nrows, N)) {
-    if (launch) hipLaunchKernelGGL((fft512c_kernel<13, 12, MODE, true>), grid, block, lds, stream, *fp);
-    return fft512c_entry<13, 12, MODE, true>();
-  }
-  if (nrows == 10) HF_C_CASE(10, 0)
-  if (nrows == 13 && N >= 384) HF_C_CASE(13, 12)
-  if (nrows == 13) HF_C_CASE(13, 0)
-  HF_C_CASE(16, 0)
-#undef HF_C_CASE
+  if (nrows == 13 && N >= 384) return fft512c_entry<13, 12, MODE>();
+  if (nrows == 13) return fft512c_entry<13, 0, MODE>();
+  return fft512c_entry<16, 0, MODE>();
 }
-static const void* fft512c_dispatch(int mode, int nrows, int N, bool launch, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Fft512cParams* fp,
-                                    bool flat = false) {
-  return mode == 0 ? fft512c_pick<0>(nrows, N, launch, grid, block, lds, stream, fp, flat)
-                   : (mode == 1 ? fft512c_pick<1>(nrows, N, launch, grid, block, lds, stream, fp, flat)
-                                : (mode == 2 ? fft512c_pick<2>(nrows, N, launch, grid, block, lds, stream, fp, flat)
-                                             : fft512c_pick<3>(nrows, N, launch, grid, block, lds, stream, fp, flat)));
+static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat) {
+  return mode == 0 ? fft512c_pick<0>(nrows, N, flat)
+                   : (mode == 1 ? fft512c_pick<1>(nrows, N, flat) : (mode == 2 ? fft512c_pick<2>(nrows, N, flat) : fft512c_pick<3>(nrows, N, flat)));
 }
 
-// Returns HIPFEAT_OK with p->variant == 7 when the configuration takes the wave-autonomous kernel, HIPFEAT_OK with the
-// variant untouched when it does not (the caller then sets up kernel "b").
+// Claims the plan (Route::Fft512c) when the configuration takes the wave-autonomous kernel, leaves it unclaimed when it does
+// not (the caller then sets up kernel "b").
 static hipfeat_status setup_fft512c(hipfeat_plan* p, const float* h_window, const float* h_mel, int nrows, const float* h_dct, const float* h_lifter) {
   const hipfeat_config& c = p->cfg;
   const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
@@ -478,9 +491,6 @@ static hipfeat_status setup_fft512c(hipfeat_plan* p, const float* h_window, cons
   p->c_xs_floats = (3 * shift + 32 * nrows + 3) & ~3;
   const size_t lds = ((size_t)p->c_shared_floats + (size_t)kCWaves * (p->c_xs_floats + kCRegion)) * sizeof(float);
   if (lds > 80 * 1024 || (p->c_xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
-  const void* fn = fft512c_dispatch(mode, nrows, N, false, dim3(), dim3(), 0, nullptr, nullptr);
-  hipError_t e = ensure_dynamic_lds(fn, lds);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(fft512c) failed: %s", hipGetErrorName(e));
   hipfeat_status st;
   if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
   if (mfcc) {  // DCT operands in matrix-core lane order: [chunk of 4 filters][lane = cepstral coefficient][filter in the chunk], then the lifter
@@ -492,21 +502,21 @@ static hipfeat_status setup_fft512c(hipfeat_plan* p, const float* h_window, cons
     for (int cc = 0; cc < 64; ++cc) dt[(size_t)dch * 256 + cc] = (c.apply_lifter && h_lifter && cc < C) ? h_lifter[cc] : 1.0f;
     if ((st = upload(&p->d_dct_consts, dt.data(), dt.size())) != HIPFEAT_OK) return st;
   }
-  p->c_mode = mode;
-  p->nrows = nrows;
   p->c_rounds = 8;  // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
   p->fpb = kCWaves * p->c_rounds * 4;
   p->fpb_unit = kCWaves * 4;
   p->c_rounds_max = 16;
-  p->fast_lds_bytes = lds;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * kCWaves, lds) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Fft512c, fft512c_dispatch(mode, nrows, N, false), 64 * kCWaves, lds)) != HIPFEAT_OK) return st;
+  if (fft512c_has_flat(nrows, N)) {  // the same launch shape, chosen per layout (build_descs)
+    p->fn_flat = fft512c_dispatch(mode, nrows, N, true);
+    hipError_t e = ensure_dynamic_lds(p->fn_flat, lds);
+    if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
+  }
   int total_steps = 0;
   for (int s2 = 0; s2 < sch.nsets; ++s2) total_steps += sch.steps[s2];
   char nm[128];
   snprintf(nm, sizeof(nm), "fft512c_kernel<%d> %s lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, mfcc ? "mfcc" : "fbank", lds, p->blocks_per_cu, sch.nsets, total_steps);
   p->kernel_name = nm;
-  p->variant = 7;
   return HIPFEAT_OK;
 }
 
@@ -530,7 +540,7 @@ static hipfeat_status setup_fft512(hipfeat_plan* p, const float* h_window, const
     const char* var = route_env("HIPFEAT_FFT512_VARIANT");
     if (!(var && var[0] == 'b')) {  // HIPFEAT_FFT512_VARIANT=b: the 16-frame-tile kernel for these too (tests compare the two)
       hipfeat_status stc = setup_fft512c(p, h_window, h_mel, nrows, h_dct, h_lifter);
-      if (stc != HIPFEAT_OK || p->variant == 7) return stc;
+      if (stc != HIPFEAT_OK || p->route == Route::Fft512c) return stc;
     }
   }
   WaveWork work[4];
@@ -564,13 +574,13 @@ static hipfeat_status setup_fft512(hipfeat_plan* p, const float* h_window, const
   if ((st = upload(&p->d_lds_consts, lc.data(), lc.size())) != HIPFEAT_OK) return st;
   if ((st = upload(&p->d_mel_a, mel_a.data(), mel_a.size())) != HIPFEAT_OK) return st;
   if ((st = upload(&p->d_work, work, 4)) != HIPFEAT_OK) return st;
-  p->nrows = nrows;
   // 16 tiles (256 frames) per workgroup: the constant-table load and the first, un-overlapped span
   // fetch are paid once per workgroup (measured on MI355X: 4 -> 1.98 M, 8 -> 2.11 M, 16 -> 2.16 M cuts/s)
   p->tiles_per_block = 16;
   const int const_floats = (int)lc.size();
   p->const_floats = const_floats;
   const void* fn;
+  size_t lds;
   {
     // weights as 16-byte vectors: [wave][step / 4][lane][step % 4]
     std::vector<float> mel_a4(mel_a.size());
@@ -588,10 +598,8 @@ static hipfeat_status setup_fft512(hipfeat_plan* p, const float* h_window, const
       p->dct_floats = (int)da.size();
       if ((st = upload(&p->d_dct_consts, da.data(), da.size())) != HIPFEAT_OK) return st;
       lds_floats += (size_t)kTileFrames * p->lm_stride + da.size();
-      p->fast_mfcc = true;
     }
-    p->fast_lds_bytes = lds_floats * sizeof(float);
-    p->fast_out = mfcc ? 1 : (spec ? 2 : 0);
+    lds = lds_floats * sizeof(float);
     if (mfcc)
       fn = nrows == 10 ? fft512b_entry<10, 1>() : (nrows == 13 ? fft512b_entry<13, 1>() : fft512b_entry<16, 1>());
     else if (spec)
@@ -599,17 +607,13 @@ static hipfeat_status setup_fft512(hipfeat_plan* p, const float* h_window, const
     else
       fn = nrows == 10 ? fft512b_entry<10, 0>() : (nrows == 13 ? fft512b_entry<13, 0>() : fft512b_entry<16, 0>());
   }
-  if (p->fast_lds_bytes > 160 * 1024) return HIPFEAT_OK;
-  hipError_t e = ensure_dynamic_lds(fn, p->fast_lds_bytes);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(fft512) failed: %s", hipGetErrorName(e));
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, p->fast_lds_bytes) == hipSuccess) p->blocks_per_cu = nb;
+  if (lds > 160 * 1024) return HIPFEAT_OK;
+  if ((st = claim(p, Route::Fft512b, fn, 256, lds)) != HIPFEAT_OK) return st;
   char nm[96];
   // same spelling as the device symbol rocprofv3 reports (modulo the space after the comma)
-  snprintf(nm, sizeof(nm), "fft512b_kernel<%d,%d> %s lds=%zuB blocks/CU=%d", nrows, p->fast_out,
-           mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"), p->fast_lds_bytes, p->blocks_per_cu);
+  snprintf(nm, sizeof(nm), "fft512b_kernel<%d,%d> %s lds=%zuB blocks/CU=%d", nrows, mfcc ? 1 : (spec ? 2 : 0),
+           mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"), lds, p->blocks_per_cu);
   p->kernel_name = nm;
-  p->variant = 2;
   p->fpb = kTileFrames * p->tiles_per_block;
   return HIPFEAT_OK;
 }
@@ -637,7 +641,7 @@ static hipfeat_status setup_fft1024c(hipfeat_plan* p, const float* h_window, con
   const hipfeat_config& c = p->cfg;
   const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;  // centred frames, |X| or |X|^2, log10 (librosa_fbank.py:66-137)
-  if (p->variant != 0 || (c.kind != HIPFEAT_FBANK && !librosa) || c.fft_length != 1024 || (shift & 1) || N < 32 * 17 || c.use_energy ||
+  if ((c.kind != HIPFEAT_FBANK && !librosa) || c.fft_length != 1024 || (shift & 1) || N < 32 * 17 || c.use_energy ||
       (c.use_fft_mag && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_AUTONOMOUS"))
     return HIPFEAT_OK;
   const int need = (N + 31) / 32;
@@ -703,9 +707,6 @@ static hipfeat_status setup_fft1024c(hipfeat_plan* p, const float* h_window, con
                    : fixed == 3 ? fft1024c_entry<20, 24, 24, 8>()
                    : fixed == 4 ? fft1024c_entry<32, 16, 16, 8, true>()
                    : nrows == 20 ? fft1024c_entry<20>() : (nrows == 26 ? fft1024c_entry<26>() : fft1024c_entry<32>());
-  hipError_t e = ensure_dynamic_lds(fn, lds);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(fft1024c) failed: %s", hipGetErrorName(e));
-  p->w_fixed = fixed;
   hipfeat_status st;
   if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
   p->w_nsets = sch.nsets;
@@ -715,19 +716,14 @@ static hipfeat_status setup_fft1024c(hipfeat_plan* p, const float* h_window, con
     p->w_step0[s2] = s2 < sch.nsets ? sch.step0[s2] : 0;
     total_steps += p->w_steps[s2];
   }
-  p->nrows = nrows;
   p->c_rounds = 8;
   p->fpb = waves * p->c_rounds * 4;
   p->fpb_unit = waves * 4;
-  p->w_waves = waves;
   p->c_rounds_max = 32;
-  p->fast_lds_bytes = lds;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * waves, lds) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Fft1024c, fn, 64 * waves, lds)) != HIPFEAT_OK) return st;
   char nm[160];
   snprintf(nm, sizeof(nm), "fft1024c_kernel<%d> fbank%s waves=%d lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, fixed ? " fixed-schedule" : "", waves, lds, p->blocks_per_cu, sch.nsets, total_steps);
   p->kernel_name = nm;
-  p->variant = 8;
   return HIPFEAT_OK;
 }
 
@@ -795,24 +791,18 @@ static hipfeat_status setup_fft256c(hipfeat_plan* p, const float* h_window, cons
   if (lds > 80 * 1024 || (p->c_xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
   // 25 ms at 8 kHz (N = 200: 12 full rows of 16 samples + a partial one) gets the instance without length masks on the full rows
   const void* fn = nrows == 13 ? (N >= 192 ? fft256c_entry<13, 12>() : fft256c_entry<13, 0>()) : fft256c_entry<16, 0>();
-  hipError_t e = ensure_dynamic_lds(fn, lds);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(fft256c) failed: %s", hipGetErrorName(e));
   hipfeat_status st;
   if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
-  p->nrows = nrows;
   p->c_rounds = 4;  // 8 waves x 4 rounds x 8 frames = 256 frames per workgroup
   p->fpb = kDWaves * p->c_rounds * 8;
   p->fpb_unit = kDWaves * 8;
   p->c_rounds_max = 16;
-  p->fast_lds_bytes = lds;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * kDWaves, lds) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Fft256c, fn, 64 * kDWaves, lds)) != HIPFEAT_OK) return st;
   int total_steps = 0;
   for (int s2 = 0; s2 < sch.nsets; ++s2) total_steps += sch.steps[s2];
   char nm[128];
   snprintf(nm, sizeof(nm), "fft256c_kernel<%d> fbank lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, lds, p->blocks_per_cu, sch.nsets, total_steps);
   p->kernel_name = nm;
-  p->variant = 11;
   return HIPFEAT_OK;
 }
 
@@ -833,7 +823,7 @@ static hipfeat_status setup_fft256(hipfeat_plan* p, const float* h_window, const
     const char* var = route_env("HIPFEAT_FFT256_VARIANT");
     if (!(var && var[0] == 'b') && !route_env("HIPFEAT_NO_WAVE_AUTONOMOUS")) {  // HIPFEAT_FFT256_VARIANT=b: the 32-frame-tile kernel (tests compare the two)
       hipfeat_status stc = setup_fft256c(p, h_window, h_mel, nrows);
-      if (stc != HIPFEAT_OK || p->variant == 11) return stc;
+      if (stc != HIPFEAT_OK || p->route == Route::Fft256c) return stc;
     }
   }
   WaveWork work[4];
@@ -878,7 +868,6 @@ static hipfeat_status setup_fft256(hipfeat_plan* p, const float* h_window, const
       for (int lane = 0; lane < 64; ++lane)
         mel_a4[(((size_t)w * kBMelVec + s4 / 4) * 64 + lane) * 4 + (s4 & 3)] = mel_a[((size_t)w * kMelARegs + s4) * 64 + lane];
   if ((st = upload(&p->d_mel_a4, mel_a4.data(), mel_a4.size())) != HIPFEAT_OK) return st;
-  p->nrows = nrows;
   p->tiles_per_block = 16;  // 512 frames per workgroup (measured: 8 -> 3.84 M, 16 -> 3.99 M, 32 -> 3.93 M cuts/s at 8 kHz fbank-80)
   p->const_floats = const_floats;
   p->xs_floats = ((k256TileFrames - 1) * shift + 16 * nrows + 255) & ~255;  // whole 1 KiB LDS-DMA chunks
@@ -890,24 +879,18 @@ static hipfeat_status setup_fft256(hipfeat_plan* p, const float* h_window, const
     p->dct_floats = (int)da.size();
     if ((st = upload(&p->d_dct_consts, da.data(), da.size())) != HIPFEAT_OK) return st;
     lds_floats += (size_t)k256TileFrames * p->lm_stride + da.size();
-    p->fast_mfcc = true;
   }
-  p->fast_lds_bytes = lds_floats * sizeof(float);
-  p->fast_out = mfcc ? 1 : (spec ? 2 : 0);
-  if (p->fast_lds_bytes > 64 * 1024) return HIPFEAT_OK;  // keep at least two workgroups per CU; otherwise the generic kernel
+  const size_t lds = lds_floats * sizeof(float);
+  if (lds > 64 * 1024) return HIPFEAT_OK;  // keep at least two workgroups per CU; otherwise the generic kernel
   const void* fn;
   if (mfcc) fn = nrows == 13 ? fft256_entry<13, 1>() : fft256_entry<16, 1>();
   else if (spec) fn = nrows == 13 ? fft256_entry<13, 2>() : fft256_entry<16, 2>();
   else fn = nrows == 13 ? fft256_entry<13, 0>() : fft256_entry<16, 0>();
-  hipError_t e = ensure_dynamic_lds(fn, p->fast_lds_bytes);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(fft256) failed: %s", hipGetErrorName(e));
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, p->fast_lds_bytes) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Fft256b, fn, 256, lds)) != HIPFEAT_OK) return st;
   char nm[112];
-  snprintf(nm, sizeof(nm), "fft256_kernel<%d,%d> %s lds=%zuB blocks/CU=%d", nrows, p->fast_out, mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"),
-           p->fast_lds_bytes, p->blocks_per_cu);
+  snprintf(nm, sizeof(nm), "fft256_kernel<%d,%d> %s lds=%zuB blocks/CU=%d", nrows, mfcc ? 1 : (spec ? 2 : 0), mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"),
+           lds, p->blocks_per_cu);
   p->kernel_name = nm;
-  p->variant = 4;
   p->fpb = k256TileFrames * p->tiles_per_block;
   return HIPFEAT_OK;
 }
@@ -923,7 +906,7 @@ static const void* wave_entry() {
 static hipfeat_status setup_wave(hipfeat_plan* p, const float* h_mel) {
   const hipfeat_config& c = p->cfg;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
-  if (p->variant != 0 || !p->pow2 || (c.kind > HIPFEAT_MFCC && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_KERNEL"))
+  if (!p->pow2 || (c.kind > HIPFEAT_MFCC && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_KERNEL"))
     return HIPFEAT_OK;
   const int H = p->H;
   // H = 128 (fft 256) stays on the radix-2 kernel: measured 0.92 M vs 0.72 M cuts/s there; H = 256: 0.46 vs 0.48 M
@@ -970,17 +953,13 @@ static hipfeat_status setup_wave(hipfeat_plan* p, const float* h_mel) {
   p->wave_dct_in_lds = c.kind == HIPFEAT_MFCC && (size_t)M * c.num_ceps <= 2560;
   auto up4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
   // twiddles W_2H^k + 4 padded wave buffers + window + twiddles W_H^m + filterbank blob (+ DCT matrix)
-  p->wave_lds_bytes = ((size_t)2 * H + 4 * ((size_t)144 * (H / 64) + 8) + up4((size_t)c.frame_length) + (size_t)2 * H + up4((size_t)p->wave_blob_floats) +
-                       (p->wave_dct_in_lds ? (size_t)M * c.num_ceps : 0)) * sizeof(float);
+  const size_t lds = ((size_t)2 * H + 4 * ((size_t)144 * (H / 64) + 8) + up4((size_t)c.frame_length) + (size_t)2 * H + up4((size_t)p->wave_blob_floats) +
+                      (p->wave_dct_in_lds ? (size_t)M * c.num_ceps : 0)) * sizeof(float);
   const void* fn = H == 256 ? wave_entry<4>() : (H == 512 ? wave_entry<8>() : wave_entry<16>());
-  hipError_t e = ensure_dynamic_lds(fn, p->wave_lds_bytes);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(wave) failed: %s", hipGetErrorName(e));
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, p->wave_lds_bytes) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Wave, fn, 256, lds)) != HIPFEAT_OK) return st;
   char nm[96];
-  snprintf(nm, sizeof(nm), "wave_kernel<%d> fft=%d lds=%zuB blocks/CU=%d", H / 64, c.fft_length, p->wave_lds_bytes, p->blocks_per_cu);
+  snprintf(nm, sizeof(nm), "wave_kernel<%d> fft=%d lds=%zuB blocks/CU=%d", H / 64, c.fft_length, lds, p->blocks_per_cu);
   p->kernel_name = nm;
-  p->variant = 5;
   p->fpb = 32;  // 4 waves x 8 frames (the tables copied to LDS per workgroup are ~12 KB)
   return HIPFEAT_OK;
 }
@@ -988,7 +967,10 @@ static hipfeat_status setup_wave(hipfeat_plan* p, const float* h_mel) {
 // --------------------------------------------------------------------------------------
 // whisper FFT fast path: 400 = 16 x 25 mixed-radix FFT on the vector ALUs + banded mel GEMM (kernel_whisper2.hpp)
 // --------------------------------------------------------------------------------------
-static hipfeat_status setup_whisper2(hipfeat_plan* p, const float* h_mel) {
+static hipfeat_status setup_whisper3(hipfeat_plan* p, const float* h_window, const float* h_mel);
+
+// whisper2, or whisper3 (which reads whisper2's DFT-25 table) when the filterbank schedule and the LDS budget allow
+static hipfeat_status setup_whisper(hipfeat_plan* p, const float* h_window, const float* h_mel) {
   const hipfeat_config& c = p->cfg;
   if (c.kind != HIPFEAT_WHISPER || c.frame_length != kW2N || c.frame_shift != kW2Shift || c.num_filters > 16 * kW2MaxMelTiles ||
       route_env("HIPFEAT_FORCE_GENERIC"))
@@ -1058,10 +1040,12 @@ static hipfeat_status setup_whisper2(hipfeat_plan* p, const float* h_mel) {
       if (mt >= 0) e[1] = p->wh2_k0[mt], e[2] = p->wh2_steps[mt], e[3] = p->wh2_off[mt];
     }
   if ((st = upload(&p->d_wh2_sched, sched.data(), sched.size())) != HIPFEAT_OK) return st;
-  p->variant = 6;
+  const char* v = route_env("HIPFEAT_WHISPER_VARIANT");
+  if (!(v && v[0] == '2')) {  // HIPFEAT_WHISPER_VARIANT=2: whisper2 (tests compare the two)
+    if ((st = setup_whisper3(p, h_window, h_mel)) != HIPFEAT_OK || p->route == Route::Whisper3) return st;
+  }
   p->fpb = 16 * kW2TilesPerBlock;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&whisper2_kernel), 256, 0) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Whisper2, reinterpret_cast<const void*>(&whisper2_kernel), 256, 0)) != HIPFEAT_OK) return st;
   char buf[160];
   snprintf(buf, sizeof(buf), "whisper_kernel2 fft400=16x25 mel_chunks=%d+%d+%d+%d blocks/CU=%d", load[0], load[1], load[2], load[3], p->blocks_per_cu);
   p->kernel_name = buf;
@@ -1078,7 +1062,7 @@ static hipfeat_status setup_fft2048c(hipfeat_plan* p, const float* h_window, con
   const hipfeat_config& c = p->cfg;
   const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;  // centred frames, |X| or |X|^2, log10 (librosa_fbank.py:66-137)
-  if (p->variant != 0 || (c.kind != HIPFEAT_FBANK && !librosa) || c.fft_length != 2048 || N <= 1024 || c.use_energy ||
+  if ((c.kind != HIPFEAT_FBANK && !librosa) || c.fft_length != 2048 || N <= 1024 || c.use_energy ||
       (c.use_fft_mag && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_AUTONOMOUS"))
     return HIPFEAT_OK;
   const bool odd = (shift & 1) != 0;
@@ -1155,9 +1139,6 @@ static hipfeat_status setup_fft2048c(hipfeat_plan* p, const float* h_window, con
                                 : (w12 ? fft2048c_entry<19, false, 52, 28, 16, true>() : fft2048c_entry<19, false, 52, 28, 16>()))
                    : odd ? (nrows == 18 ? fft2048c_entry<18, true>() : fft2048c_entry<32, true>())
                          : (nrows == 19 ? fft2048c_entry<19, false>() : fft2048c_entry<32, false>());
-  p->w_fixed = fixed ? 1 : 0;
-  hipError_t e = ensure_dynamic_lds(fn, lds);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(fft2048c) failed: %s", hipGetErrorName(e));
   std::vector<float> twp((size_t)32 * 32 * 2);
   for (int k1 = 0; k1 < 32; ++k1)
     for (int q = 0; q < 32; ++q) {
@@ -1175,24 +1156,19 @@ static hipfeat_status setup_fft2048c(hipfeat_plan* p, const float* h_window, con
     p->w_step0[s2] = s2 < sch.nsets ? sch.step0[s2] : 0;
     total_steps += p->w_steps[s2];
   }
-  p->nrows = nrows;
-  p->x_odd = odd;
   p->x_waves = waves;
   p->c_rounds = 8;
   p->fpb = waves * p->c_rounds * 2;
   p->fpb_unit = waves * 2;
   p->c_rounds_max = 64;
-  p->fast_lds_bytes = lds;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * waves, lds) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Fft2048c, fn, 64 * waves, lds)) != HIPFEAT_OK) return st;
   char nm[160];
   snprintf(nm, sizeof(nm), "fft2048c_kernel<%d,%d> fbank%s waves=%d lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, (int)odd, fixed ? " fixed-schedule" : "", waves, lds, p->blocks_per_cu, sch.nsets, total_steps);
   p->kernel_name = nm;
-  p->variant = 10;
   return HIPFEAT_OK;
 }
 
-// whisper, wave-autonomous with the normalisation fused (kernel_whisper3.hpp): shares the DFT-25 coefficient table of setup_whisper2
+// whisper, wave-autonomous with the normalisation fused (kernel_whisper3.hpp): shares the DFT-25 coefficient table of setup_whisper
 template <int NSETS>
 static const void* whisper3_entry() {
   return reinterpret_cast<const void*>(&whisper3_kernel<NSETS>);
@@ -1200,9 +1176,6 @@ static const void* whisper3_entry() {
 
 static hipfeat_status setup_whisper3(hipfeat_plan* p, const float* h_window, const float* h_mel) {
   const hipfeat_config& c = p->cfg;
-  if (p->variant != 6) return HIPFEAT_OK;  // setup_whisper2 decides whether this is the Whisper fast-path configuration
-  const char* v = route_env("HIPFEAT_WHISPER_VARIANT");
-  if (v && v[0] == '2') return HIPFEAT_OK;
   const int M = c.num_filters;
   Mel4Schedule sch;
   if (!build_mel4_schedule(h_mel, M, 201, kW3PRowStride, kW3MaxSets, kW3Steps, sch)) return HIPFEAT_OK;
@@ -1235,8 +1208,6 @@ static hipfeat_status setup_whisper3(hipfeat_plan* p, const float* h_window, con
   const size_t lds = (img.size() + (size_t)kW3Waves * (kW3Span + kW3Region) + kW3Tail) * sizeof(float);
   if (lds > 80 * 1024) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
   const void* fn = nsets == 2 ? whisper3_entry<2>() : whisper3_entry<3>();
-  hipError_t e = ensure_dynamic_lds(fn, lds);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(whisper3) failed: %s", hipGetErrorName(e));
   hipfeat_status st;
   if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
   p->c_shared_floats = (int)img.size();
@@ -1245,15 +1216,12 @@ static hipfeat_status setup_whisper3(hipfeat_plan* p, const float* h_window, con
   p->fpb = kW3Waves * p->c_rounds * 4;
   p->fpb_unit = kW3Waves * 4;
   p->c_rounds_max = 16;
-  p->fast_lds_bytes = lds;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * kW3Waves, lds) == hipSuccess) p->blocks_per_cu = nb;
+  if ((st = claim(p, Route::Whisper3, fn, 64 * kW3Waves, lds)) != HIPFEAT_OK) return st;
   int total_steps = 0;
   for (int s2 = 0; s2 < sch.nsets; ++s2) total_steps += sch.steps[s2];
   char nm[160];
   snprintf(nm, sizeof(nm), "whisper3_kernel<%d> fft400=16x25 fused-norm lds=%zuB blocks/CU=%d mel4=%dx%d", nsets, lds, p->blocks_per_cu, sch.nsets, total_steps);
   p->kernel_name = nm;
-  p->variant = 9;
   return HIPFEAT_OK;
 }
 
@@ -1369,8 +1337,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     p->off_stat = p->off_tw + (p->pow2 ? al(2 * std::max(p->H, 1)) : 0);
     p->off_mel = p->off_stat + al(2 * fpb);
     const int end = p->off_mel + al(fpb * std::max(M, 1));
-    p->lds_bytes = (size_t)end * sizeof(float);
-    return p->lds_bytes;
+    p->lds = (size_t)end * sizeof(float);
+    return p->lds;
   };
   {
     size_t cap = 21 * 1024;
@@ -1381,22 +1349,23 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     if (carve(pick) > 160 * 1024) p->fpb = 0;
   }
   if (p->fpb < 1) return bail(fail(HIPFEAT_ERR_UNSUPPORTED, "configuration does not fit in LDS"));
-  hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&generic_kernel), p->lds_bytes);
-  if (e != hipSuccess) return bail(fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", p->lds_bytes, hipGetErrorName(e)));
+  // the generic kernel's launch: it stays unless a specialised kernel claims the plan
+  p->fn = reinterpret_cast<const void*>(&generic_kernel);
+  p->block = 256;
+  hipError_t e = ensure_dynamic_lds(p->fn, p->lds);
+  if (e != hipSuccess) return bail(fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", p->lds, hipGetErrorName(e)));
 
-  st = setup_fft512(p, h_window, h_mel, h_dct, h_lifter);
-  if (st != HIPFEAT_OK) return bail(st);
-  st = setup_whisper2(p, h_mel);
-  if (st != HIPFEAT_OK) return bail(st);
-  st = setup_whisper3(p, h_window, h_mel);
-  if (st != HIPFEAT_OK) return bail(st);
-  st = setup_fft256(p, h_window, h_mel, h_dct, h_lifter);
-  if (st != HIPFEAT_OK) return bail(st);
-  st = setup_fft1024c(p, h_window, h_mel);
-  if (st != HIPFEAT_OK) return bail(st);
-  st = setup_fft2048c(p, h_window, h_mel);
-  if (st != HIPFEAT_OK) return bail(st);
-  st = setup_wave(p, h_mel);
+  // the specialised kernels, in order of preference: the first setup that claims the plan ends the search
+  auto unclaimed = [&](hipfeat_status s) {
+    st = s;
+    return st == HIPFEAT_OK && p->route == Route::Generic;
+  };
+  if (unclaimed(setup_fft512(p, h_window, h_mel, h_dct, h_lifter)) &&
+      unclaimed(setup_whisper(p, h_window, h_mel)) &&
+      unclaimed(setup_fft256(p, h_window, h_mel, h_dct, h_lifter)) &&
+      unclaimed(setup_fft1024c(p, h_window, h_mel)) &&
+      unclaimed(setup_fft2048c(p, h_window, h_mel)))
+    st = setup_wave(p, h_mel);
   if (st != HIPFEAT_OK) return bail(st);
 
   *out = p;
@@ -1504,7 +1473,7 @@ static hipfeat_status build_descs(const hipfeat_plan* plan, int64_t batch, const
   bool ragged = false;
   for (int64_t b = 1; b < batch && !ragged; ++b) ragged = lay->num_frames[(size_t)b] != lay->num_frames[0];
   static const bool no_flat = route_env("HIPFEAT_NO_FLAT") != nullptr;
-  lay->flat = ragged && !no_flat && plan->variant == 7 && fft512c_has_flat(plan->nrows, c.frame_length);
+  lay->flat = ragged && !no_flat && plan->fn_flat;
   lay->total_quads = 0;
   lay->block_cut.clear();
   if (lay->flat) {
@@ -1591,7 +1560,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_layout_create(const hipfeat_plan* 
   // (ragged batches: the workgroup -> cut map directly behind the descriptors, common.hpp::block_cut_map)
   const size_t map_bytes = (lay->block_cut.size() * sizeof(int32_t) + 15) & ~(size_t)15;
   const size_t desc_bytes = std::max<size_t>(descs.size(), 1) * sizeof(CutDesc) + map_bytes;
-  const size_t norm_bytes = plan->variant == 9 ? (size_t)kNormSlots * norm_slot_bytes(lay) : 0;
+  const size_t norm_bytes = plan->route == Route::Whisper3 ? (size_t)kNormSlots * norm_slot_bytes(lay) : 0;
   std::vector<unsigned char> blob(desc_bytes + norm_bytes, 0);  // zeros = armed counters
   if (!descs.empty()) std::memcpy(blob.data(), descs.data(), descs.size() * sizeof(CutDesc));
   if (map_bytes) std::memcpy(blob.data() + descs.size() * sizeof(CutDesc), lay->block_cut.data(), lay->block_cut.size() * sizeof(int32_t));
@@ -1635,6 +1604,39 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_layout_num_frames(const hipfeat_la
 // --------------------------------------------------------------------------------------
 // launch
 // --------------------------------------------------------------------------------------
+// Fields of the wave-autonomous families (fft512c / fft256c, fft1024c, fft2048c, whisper3): the batch, one LDS constants image and
+// workgroups of `rounds` rounds of frames.
+template <typename P>
+static void fill_wave_autonomous(P& p, const hipfeat_plan* plan, const hipfeat_layout* lay, const float* d_wave, float* d_out) {
+  p.wave = d_wave;
+  p.out = d_out;
+  p.cuts = lay->d_cuts;
+  p.shared_consts = plan->d_c_shared;
+  p.shared_floats = plan->c_shared_floats;
+  p.wtab_off = plan->c_wtab_off;
+  p.ltab_off = plan->c_ltab_off;
+  p.out_stride = lay->out_row_stride;
+  p.num_cuts = (int32_t)lay->batch;
+  p.uniform_bpc = lay->uniform_bpc;
+  p.frames_per_block = lay->fpb;
+  p.rounds = lay->fpb / plan->fpb_unit;
+  p.M = plan->cfg.num_filters;
+  p.mel_floor = plan->cfg.mel_floor;
+}
+
+// Frame geometry of the wave-autonomous FFT kernels (fft512c / fft256c plans have neither magnitudes nor centred framing: their
+// flags come down to F_REMOVE_DC).
+template <typename P>
+static void fill_frames(P& p, const hipfeat_plan* plan) {
+  const hipfeat_config& c = plan->cfg;
+  p.N = c.frame_length;
+  p.shift = c.frame_shift;
+  p.npad_left = plan->npad_left;
+  p.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LIBROSA_FBANK ? (F_CENTER | F_LOG10) : 0);
+  p.preemph = c.preemph_coeff;
+  p.xs_floats = plan->c_xs_floats;
+}
+
 static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay, const float* d_wave, float* d_out,
                              hipStream_t stream) {
   if (lay->total_blocks == 0) return HIPFEAT_OK;
@@ -1642,353 +1644,180 @@ static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay
   if ((plan->fpb_unit > 0 ? (lay->fpb_unit != plan->fpb_unit || lay->fpb % plan->fpb_unit != 0) : lay->fpb != plan->fpb) || lay->device != plan->device)
     return fail(HIPFEAT_ERR_INVALID, "layout was created for a different plan");
   const hipfeat_config& c = plan->cfg;
-  if (plan->variant == 5) {
-    WaveParams wp{};
-    wp.wave = d_wave;
-    wp.out = d_out;
-    wp.cuts = lay->d_cuts;
-    wp.window = plan->d_window;
-    wp.tw = plan->d_tw;
-    wp.mel_blob = plan->d_mel_t;
-    wp.mel_blob_floats = plan->wave_blob_floats;
-    wp.dct_in_lds = plan->wave_dct_in_lds ? 1 : 0;
-    wp.dct = plan->d_dct;
-    wp.lifter = plan->d_lifter;
-    wp.out_stride = lay->out_row_stride;
-    wp.num_cuts = (int32_t)lay->batch;
-    wp.uniform_bpc = lay->uniform_bpc;
-    wp.frames_per_wave = plan->fpb / 4;
-    wp.N = c.frame_length;
-    wp.shift = c.frame_shift;
-    wp.H = plan->H;
-    wp.K = plan->K;
-    wp.M = c.num_filters;
-    wp.C = c.num_ceps;
-    const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
-    wp.kind = librosa ? (int)HIPFEAT_FBANK : c.kind;
-    wp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) |
-               (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0) | (librosa ? (F_CENTER | F_LOG10) : 0);
-    wp.npad_left = plan->npad_left;
-    wp.preemph = c.preemph_coeff;
-    wp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
-    wp.mel_floor = c.mel_floor;
-    wp.log_offset = c.log_offset;
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(256);
-    set_lds_poison(plan->wave_lds_bytes);
-    switch (plan->H >> 6) {
-      case 4: hipLaunchKernelGGL(wave_kernel<4>, grid, block, plan->wave_lds_bytes, stream, wp); break;
-      case 8: hipLaunchKernelGGL(wave_kernel<8>, grid, block, plan->wave_lds_bytes, stream, wp); break;
-      default: hipLaunchKernelGGL(wave_kernel<16>, grid, block, plan->wave_lds_bytes, stream, wp); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 9) {
-    Whisper3Params wp{};
-    wp.wave = d_wave;
-    wp.out = d_out;
-    wp.cuts = lay->d_cuts;
-    wp.shared_consts = plan->d_c_shared;
-    wp.cs = plan->d_wh2_cs;
-    wp.out_stride = lay->out_row_stride;
-    wp.num_cuts = (int32_t)lay->batch;
-    wp.uniform_bpc = lay->uniform_bpc;
-    wp.total_blocks = (int32_t)lay->total_blocks;
-    wp.frames_per_block = lay->fpb;
-    wp.rounds = lay->fpb / plan->fpb_unit;
-    wp.M = c.num_filters;
-    wp.mel_floor = c.mel_floor;
-    wp.shared_floats = plan->c_shared_floats;
-    wp.wtab_off = plan->c_wtab_off;
-    wp.ltab_off = plan->c_ltab_off;
-    if (lay->d_norm) {
-      unsigned char* slot = lay->d_norm + (size_t)(lay->norm_next.fetch_add(1u) % (unsigned)lay->norm_slots) * norm_slot_bytes(lay);
-      wp.wg_stat = reinterpret_cast<float*>(slot);
-      wp.cut_done = reinterpret_cast<uint32_t*>(slot + 2 * (size_t)lay->total_blocks * sizeof(float));
-    }
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(64 * kW3Waves);
-    set_lds_poison(plan->fast_lds_bytes);
-    if (plan->w_nsets == 2) hipLaunchKernelGGL(whisper3_kernel<2>, grid, block, plan->fast_lds_bytes, stream, wp);
-    else hipLaunchKernelGGL(whisper3_kernel<3>, grid, block, plan->fast_lds_bytes, stream, wp);
-    HIP_TRY(hipGetLastError());
-    if (!wp.wg_stat) {  // no scratch behind this layout: finish with the separate pass
-      hipLaunchKernelGGL(whisper_norm_kernel, dim3((unsigned)lay->batch), dim3(1024), 0, stream, lay->d_cuts, d_out, lay->out_row_stride,
-                         (int32_t)c.num_filters, (int32_t)c.frame_shift);
-      HIP_TRY(hipGetLastError());
-    }
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 6) {
-    Whisper2Params wp{};
-    wp.wave = d_wave;
-    wp.out = d_out;
-    wp.cuts = lay->d_cuts;
-    wp.window = plan->d_window;
-    wp.cs = plan->d_wh2_cs;
-    wp.tw = plan->d_wh2_tw;
-    wp.mel_a = plan->d_wh2_mel;
-    wp.out_stride = lay->out_row_stride;
-    wp.num_cuts = (int32_t)lay->batch;
-    wp.uniform_bpc = lay->uniform_bpc;
-    wp.M = c.num_filters;
-    wp.mel_floor = c.mel_floor;
-    wp.sched = plan->d_wh2_sched;
-    DeviceGuard g(plan->device);
-    hipLaunchKernelGGL(whisper2_kernel, dim3((unsigned)lay->total_blocks), dim3(256), 0, stream, wp);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(whisper_norm_kernel, dim3((unsigned)lay->batch), dim3(1024), 0, stream, lay->d_cuts, d_out, lay->out_row_stride,
-                       (int32_t)c.num_filters, (int32_t)c.frame_shift);
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 11) {
-    Fft512cParams fp{};
-    fp.wave = d_wave;
-    fp.out = d_out;
-    fp.cuts = lay->d_cuts;
-    fp.shared_consts = plan->d_c_shared;
-    fp.out_stride = lay->out_row_stride;
-    fp.num_cuts = (int32_t)lay->batch;
-    fp.uniform_bpc = lay->uniform_bpc;
-    fp.frames_per_block = lay->fpb;
-    fp.rounds = lay->fpb / plan->fpb_unit;
-    fp.N = c.frame_length;
-    fp.shift = c.frame_shift;
-    fp.npad_left = plan->npad_left;
-    fp.M = c.num_filters;
-    fp.flags = c.remove_dc_offset ? F_REMOVE_DC : 0;
-    fp.preemph = c.preemph_coeff;
-    fp.mel_floor = c.mel_floor;
-    fp.shared_floats = plan->c_shared_floats;
-    fp.wtab_off = plan->c_wtab_off;
-    fp.ltab_off = plan->c_ltab_off;
-    fp.xs_floats = plan->c_xs_floats;
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(64 * kDWaves);
-    set_lds_poison(plan->fast_lds_bytes);
-    if (plan->nrows == 13 && c.frame_length >= 192) hipLaunchKernelGGL((fft256c_kernel<13, 12>), grid, block, plan->fast_lds_bytes, stream, fp);
-    else if (plan->nrows == 13) hipLaunchKernelGGL((fft256c_kernel<13, 0>), grid, block, plan->fast_lds_bytes, stream, fp);
-    else hipLaunchKernelGGL((fft256c_kernel<16, 0>), grid, block, plan->fast_lds_bytes, stream, fp);
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 10) {
-    Fft2048cParams fp{};
-    fp.wave = d_wave;
-    fp.out = d_out;
-    fp.cuts = lay->d_cuts;
-    fp.shared_consts = plan->d_c_shared;
-    fp.twp = plan->d_x_twp;
-    fp.out_stride = lay->out_row_stride;
-    fp.num_cuts = (int32_t)lay->batch;
-    fp.uniform_bpc = lay->uniform_bpc;
-    fp.frames_per_block = lay->fpb;
-    fp.rounds = lay->fpb / plan->fpb_unit;
-    fp.waves = plan->x_waves;
-    fp.N = c.frame_length;
-    fp.shift = c.frame_shift;
-    fp.npad_left = plan->npad_left;
-    fp.M = c.num_filters;
-    fp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LIBROSA_FBANK ? (F_CENTER | F_LOG10) : 0);
-    fp.preemph = c.preemph_coeff;
-    fp.mel_floor = c.mel_floor;
-    fp.shared_floats = plan->c_shared_floats;
-    fp.tws_off = plan->x_tws_off;
-    fp.tw32_off = plan->x_tw32_off;
-    fp.wtab_off = plan->c_wtab_off;
-    fp.ltab_off = plan->c_ltab_off;
-    fp.xs_floats = plan->c_xs_floats;
-    fp.nsets = plan->w_nsets;
-    for (int s2 = 0; s2 < kXMaxSets; ++s2) fp.steps[s2] = plan->w_steps[s2], fp.step0[s2] = plan->w_step0[s2];
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(64 * plan->x_waves);
-    set_lds_poison(plan->fast_lds_bytes);
-    if (plan->x_odd) {
-      if (plan->w_fixed && plan->x_waves == kXWavesFixed) hipLaunchKernelGGL((fft2048c_kernel<18, true, 52, 28, 16, true>), grid, block, plan->fast_lds_bytes, stream, fp);
-      else if (plan->w_fixed) hipLaunchKernelGGL((fft2048c_kernel<18, true, 52, 28, 16>), grid, block, plan->fast_lds_bytes, stream, fp);
-      else if (plan->nrows == 18) hipLaunchKernelGGL((fft2048c_kernel<18, true>), grid, block, plan->fast_lds_bytes, stream, fp);
-      else hipLaunchKernelGGL((fft2048c_kernel<32, true>), grid, block, plan->fast_lds_bytes, stream, fp);
-    } else {
-      if (plan->w_fixed && plan->x_waves == kXWavesFixed) hipLaunchKernelGGL((fft2048c_kernel<19, false, 52, 28, 16, true>), grid, block, plan->fast_lds_bytes, stream, fp);
-      else if (plan->w_fixed) hipLaunchKernelGGL((fft2048c_kernel<19, false, 52, 28, 16>), grid, block, plan->fast_lds_bytes, stream, fp);
-      else if (plan->nrows == 19) hipLaunchKernelGGL((fft2048c_kernel<19, false>), grid, block, plan->fast_lds_bytes, stream, fp);
-      else hipLaunchKernelGGL((fft2048c_kernel<32, false>), grid, block, plan->fast_lds_bytes, stream, fp);
-    }
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 8) {
-    Fft1024cParams fp{};
-    fp.wave = d_wave;
-    fp.out = d_out;
-    fp.cuts = lay->d_cuts;
-    fp.shared_consts = plan->d_c_shared;
-    fp.out_stride = lay->out_row_stride;
-    fp.num_cuts = (int32_t)lay->batch;
-    fp.uniform_bpc = lay->uniform_bpc;
-    fp.frames_per_block = lay->fpb;
-    fp.rounds = lay->fpb / plan->fpb_unit;
-    fp.N = c.frame_length;
-    fp.shift = c.frame_shift;
-    fp.npad_left = plan->npad_left;
-    fp.M = c.num_filters;
-    fp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LIBROSA_FBANK ? (F_CENTER | F_LOG10) : 0);
-    fp.preemph = c.preemph_coeff;
-    fp.mel_floor = c.mel_floor;
-    fp.shared_floats = plan->c_shared_floats;
-    fp.wtab_off = plan->c_wtab_off;
-    fp.ltab_off = plan->c_ltab_off;
-    fp.xs_floats = plan->c_xs_floats;
-    fp.nsets = plan->w_nsets;
-    for (int s2 = 0; s2 < kWMaxSets; ++s2) fp.steps[s2] = plan->w_steps[s2], fp.step0[s2] = plan->w_step0[s2];
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(64 * plan->w_waves);
-    set_lds_poison(plan->fast_lds_bytes);
-    if (plan->w_fixed == 1) hipLaunchKernelGGL((fft1024c_kernel<20, 24, 16, 8>), grid, block, plan->fast_lds_bytes, stream, fp);
-    else if (plan->w_fixed == 2) hipLaunchKernelGGL((fft1024c_kernel<26, 24, 16, 8>), grid, block, plan->fast_lds_bytes, stream, fp);
-    else if (plan->w_fixed == 3) hipLaunchKernelGGL((fft1024c_kernel<20, 24, 24, 8>), grid, block, plan->fast_lds_bytes, stream, fp);
-    else if (plan->w_fixed == 4) hipLaunchKernelGGL((fft1024c_kernel<32, 16, 16, 8, true>), grid, block, plan->fast_lds_bytes, stream, fp);
-    else if (plan->nrows == 20) hipLaunchKernelGGL(fft1024c_kernel<20>, grid, block, plan->fast_lds_bytes, stream, fp);
-    else if (plan->nrows == 26) hipLaunchKernelGGL(fft1024c_kernel<26>, grid, block, plan->fast_lds_bytes, stream, fp);
-    else hipLaunchKernelGGL(fft1024c_kernel<32>, grid, block, plan->fast_lds_bytes, stream, fp);
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 7) {
-    Fft512cParams fp{};
-    fp.wave = d_wave;
-    fp.out = d_out;
-    fp.cuts = lay->d_cuts;
-    fp.shared_consts = plan->d_c_shared;
-    fp.out_stride = lay->out_row_stride;
-    fp.num_cuts = (int32_t)lay->batch;
-    fp.uniform_bpc = lay->uniform_bpc;
-    fp.frames_per_block = lay->fpb;
-    fp.rounds = lay->fpb / plan->fpb_unit;
-    fp.N = c.frame_length;
-    fp.shift = c.frame_shift;
-    fp.npad_left = plan->npad_left;
-    fp.M = c.num_filters;
-    fp.flags = c.remove_dc_offset ? F_REMOVE_DC : 0;
-    fp.preemph = c.preemph_coeff;
-    fp.mel_floor = c.mel_floor;
-    fp.shared_floats = plan->c_shared_floats;
-    fp.wtab_off = plan->c_wtab_off;
-    fp.ltab_off = plan->c_ltab_off;
-    fp.xs_floats = plan->c_xs_floats;
-    fp.dct_tab = plan->d_dct_consts;
-    fp.C = c.num_ceps;
-    fp.total_quads = (int32_t)lay->total_quads;
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(64 * kCWaves);
-    set_lds_poison(plan->fast_lds_bytes);
-    fft512c_dispatch(plan->c_mode, plan->nrows, c.frame_length, true, grid, block, plan->fast_lds_bytes, stream, &fp, lay->flat);
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  if (plan->variant == 2 || plan->variant == 4) {
-    Fft512Params fp{};
-    fp.wave = d_wave;
-    fp.out = d_out;
-    fp.cuts = lay->d_cuts;
-    fp.lds_consts = plan->d_lds_consts;
-    fp.mel_a = plan->d_mel_a4;
-    fp.work = plan->d_work;
-    fp.out_stride = lay->out_row_stride;
-    fp.num_cuts = (int32_t)lay->batch;
-    fp.uniform_bpc = lay->uniform_bpc;
-    fp.tiles_per_block = plan->tiles_per_block;
-    fp.N = c.frame_length;
-    fp.shift = c.frame_shift;
-    fp.npad_left = plan->npad_left;
-    fp.M = c.num_filters;
-    fp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LOG_SPECTROGRAM ? F_LOG_SPEC : 0);
-    fp.log_offset = c.log_offset;
-    fp.preemph = c.preemph_coeff;
-    fp.mel_floor = c.mel_floor;
-    fp.xs_floats = plan->xs_floats;
-    fp.const_floats = plan->const_floats;
-    fp.dct_consts = plan->d_dct_consts;
-    fp.C = c.num_ceps;
-    fp.lm_stride = plan->lm_stride;
-    fp.dct_groups = plan->dct_groups;
-    fp.dct_floats = plan->dct_floats;
-    DeviceGuard g(plan->device);
-    const dim3 grid((unsigned)lay->total_blocks), block(256);
-    set_lds_poison(plan->fast_lds_bytes);
-    if (plan->variant == 4) {
-#define HF_LAUNCH_256(NR, OUT) hipLaunchKernelGGL((fft256_kernel<NR, OUT>), grid, block, plan->fast_lds_bytes, stream, fp)
-      if (plan->nrows == 13) {
-        if (plan->fast_out == 1) HF_LAUNCH_256(13, 1);
-        else if (plan->fast_out == 2) HF_LAUNCH_256(13, 2);
-        else HF_LAUNCH_256(13, 0);
-      } else {
-        if (plan->fast_out == 1) HF_LAUNCH_256(16, 1);
-        else if (plan->fast_out == 2) HF_LAUNCH_256(16, 2);
-        else HF_LAUNCH_256(16, 0);
-      }
-#undef HF_LAUNCH_256
-    } else if (plan->variant == 2) {
-#define HF_LAUNCH_B(NR, OUT) hipLaunchKernelGGL((fft512b_kernel<NR, OUT>), grid, block, plan->fast_lds_bytes, stream, fp)
-#define HF_LAUNCH_NR(OUT)                      \
-  do {                                         \
-    if (plan->nrows == 10) HF_LAUNCH_B(10, OUT);      \
-    else if (plan->nrows == 13) HF_LAUNCH_B(13, OUT); \
-    else HF_LAUNCH_B(16, OUT);                        \
-  } while (0)
-      if (plan->fast_out == 1) HF_LAUNCH_NR(1);
-      else if (plan->fast_out == 2) HF_LAUNCH_NR(2);
-      else HF_LAUNCH_NR(0);
-#undef HF_LAUNCH_NR
-#undef HF_LAUNCH_B
-    }
-    HIP_TRY(hipGetLastError());
-    return HIPFEAT_OK;
-  }
-  GenericParams gp{};
-  gp.wave = d_wave;
-  gp.out = d_out;
-  gp.cuts = lay->d_cuts;
-  gp.window = plan->d_window;
-  gp.tw = plan->d_tw;
-  gp.mel = plan->d_mel;
-  gp.mel_range = plan->d_mel_range;
-  gp.dct = plan->d_dct;
-  gp.lifter = plan->d_lifter;
-  gp.out_stride = lay->out_row_stride;
-  gp.num_cuts = (int32_t)lay->batch;
-  gp.uniform_bpc = lay->uniform_bpc;
-  gp.N = c.frame_length;
-  gp.shift = c.frame_shift;
-  gp.fft = c.fft_length;
-  gp.H = plan->H;
-  gp.log2H = plan->log2H;
-  gp.K = plan->K;
-  gp.M = c.num_filters;
-  gp.C = c.num_ceps;
   const bool whisper = c.kind == HIPFEAT_WHISPER, librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
-  gp.kind = (whisper || librosa) ? (int)HIPFEAT_FBANK : c.kind;  // same epilogue with log10; the post-pass below finishes it
-  gp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) |
-             (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0) | (plan->pow2 ? F_POW2 : 0) | ((whisper || librosa) ? (F_CENTER | F_LOG10) : 0);
-  gp.fpb = plan->fpb;
-  gp.npad_left = plan->npad_left;
-  gp.preemph = c.preemph_coeff;
-  gp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
-  gp.mel_floor = c.mel_floor;
-  gp.log_offset = c.log_offset;
-  gp.span = plan->span;
-  gp.off_z = plan->off_z;
-  gp.off_p = plan->off_p;
-  gp.off_tw = plan->off_tw;
-  gp.off_stat = plan->off_stat;
-  gp.off_mel = plan->off_mel;
+  // the kernel's one argument: the Params struct of the plan's family
+  GenericParams gp{};
+  WaveParams wp{};
+  Whisper2Params w2{};
+  Whisper3Params w3{};
+  Fft512Params bp{};
+  Fft512cParams cp{};
+  Fft1024cParams kp{};
+  Fft2048cParams xp{};
+  void* arg = nullptr;
+  switch (plan->route) {
+    case Route::Generic:
+      gp.wave = d_wave;
+      gp.out = d_out;
+      gp.cuts = lay->d_cuts;
+      gp.window = plan->d_window;
+      gp.tw = plan->d_tw;
+      gp.mel = plan->d_mel;
+      gp.mel_range = plan->d_mel_range;
+      gp.dct = plan->d_dct;
+      gp.lifter = plan->d_lifter;
+      gp.out_stride = lay->out_row_stride;
+      gp.num_cuts = (int32_t)lay->batch;
+      gp.uniform_bpc = lay->uniform_bpc;
+      gp.N = c.frame_length;
+      gp.shift = c.frame_shift;
+      gp.fft = c.fft_length;
+      gp.H = plan->H;
+      gp.log2H = plan->log2H;
+      gp.K = plan->K;
+      gp.M = c.num_filters;
+      gp.C = c.num_ceps;
+      gp.kind = (whisper || librosa) ? (int)HIPFEAT_FBANK : c.kind;  // same epilogue with log10; Whisper: the post-pass below finishes it
+      gp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) |
+                 (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0) | (plan->pow2 ? F_POW2 : 0) | ((whisper || librosa) ? (F_CENTER | F_LOG10) : 0);
+      gp.fpb = plan->fpb;
+      gp.npad_left = plan->npad_left;
+      gp.preemph = c.preemph_coeff;
+      gp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
+      gp.mel_floor = c.mel_floor;
+      gp.log_offset = c.log_offset;
+      gp.span = plan->span;
+      gp.off_z = plan->off_z;
+      gp.off_p = plan->off_p;
+      gp.off_tw = plan->off_tw;
+      gp.off_stat = plan->off_stat;
+      gp.off_mel = plan->off_mel;
+      arg = &gp;
+      break;
+    case Route::Wave:
+      wp.wave = d_wave;
+      wp.out = d_out;
+      wp.cuts = lay->d_cuts;
+      wp.window = plan->d_window;
+      wp.tw = plan->d_tw;
+      wp.mel_blob = plan->d_mel_t;
+      wp.mel_blob_floats = plan->wave_blob_floats;
+      wp.dct_in_lds = plan->wave_dct_in_lds ? 1 : 0;
+      wp.dct = plan->d_dct;
+      wp.lifter = plan->d_lifter;
+      wp.out_stride = lay->out_row_stride;
+      wp.num_cuts = (int32_t)lay->batch;
+      wp.uniform_bpc = lay->uniform_bpc;
+      wp.frames_per_wave = plan->fpb / 4;
+      wp.N = c.frame_length;
+      wp.shift = c.frame_shift;
+      wp.H = plan->H;
+      wp.K = plan->K;
+      wp.M = c.num_filters;
+      wp.C = c.num_ceps;
+      wp.kind = librosa ? (int)HIPFEAT_FBANK : c.kind;
+      wp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) |
+                 (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0) | (librosa ? (F_CENTER | F_LOG10) : 0);
+      wp.npad_left = plan->npad_left;
+      wp.preemph = c.preemph_coeff;
+      wp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
+      wp.mel_floor = c.mel_floor;
+      wp.log_offset = c.log_offset;
+      arg = &wp;
+      break;
+    case Route::Whisper2:
+      w2.wave = d_wave;
+      w2.out = d_out;
+      w2.cuts = lay->d_cuts;
+      w2.window = plan->d_window;
+      w2.cs = plan->d_wh2_cs;
+      w2.tw = plan->d_wh2_tw;
+      w2.mel_a = plan->d_wh2_mel;
+      w2.out_stride = lay->out_row_stride;
+      w2.num_cuts = (int32_t)lay->batch;
+      w2.uniform_bpc = lay->uniform_bpc;
+      w2.M = c.num_filters;
+      w2.mel_floor = c.mel_floor;
+      w2.sched = plan->d_wh2_sched;
+      arg = &w2;
+      break;
+    case Route::Whisper3:
+      fill_wave_autonomous(w3, plan, lay, d_wave, d_out);
+      w3.cs = plan->d_wh2_cs;
+      w3.total_blocks = (int32_t)lay->total_blocks;
+      if (lay->d_norm) {
+        unsigned char* slot = lay->d_norm + (size_t)(lay->norm_next.fetch_add(1u) % (unsigned)lay->norm_slots) * norm_slot_bytes(lay);
+        w3.wg_stat = reinterpret_cast<float*>(slot);
+        w3.cut_done = reinterpret_cast<uint32_t*>(slot + 2 * (size_t)lay->total_blocks * sizeof(float));
+      }
+      arg = &w3;
+      break;
+    case Route::Fft512c:
+      cp.dct_tab = plan->d_dct_consts;
+      cp.C = c.num_ceps;
+      cp.total_quads = (int32_t)lay->total_quads;
+      [[fallthrough]];
+    case Route::Fft256c:
+      fill_wave_autonomous(cp, plan, lay, d_wave, d_out);
+      fill_frames(cp, plan);
+      arg = &cp;
+      break;
+    case Route::Fft1024c:
+      fill_wave_autonomous(kp, plan, lay, d_wave, d_out);
+      fill_frames(kp, plan);
+      kp.nsets = plan->w_nsets;
+      for (int s2 = 0; s2 < kWMaxSets; ++s2) kp.steps[s2] = plan->w_steps[s2], kp.step0[s2] = plan->w_step0[s2];
+      arg = &kp;
+      break;
+    case Route::Fft2048c:
+      fill_wave_autonomous(xp, plan, lay, d_wave, d_out);
+      fill_frames(xp, plan);
+      xp.twp = plan->d_x_twp;
+      xp.waves = plan->x_waves;
+      xp.tws_off = plan->x_tws_off;
+      xp.tw32_off = plan->x_tw32_off;
+      xp.nsets = plan->w_nsets;
+      for (int s2 = 0; s2 < kXMaxSets; ++s2) xp.steps[s2] = plan->w_steps[s2], xp.step0[s2] = plan->w_step0[s2];
+      arg = &xp;
+      break;
+    case Route::Fft512b:
+    case Route::Fft256b:
+      bp.wave = d_wave;
+      bp.out = d_out;
+      bp.cuts = lay->d_cuts;
+      bp.lds_consts = plan->d_lds_consts;
+      bp.mel_a = plan->d_mel_a4;
+      bp.work = plan->d_work;
+      bp.out_stride = lay->out_row_stride;
+      bp.num_cuts = (int32_t)lay->batch;
+      bp.uniform_bpc = lay->uniform_bpc;
+      bp.tiles_per_block = plan->tiles_per_block;
+      bp.N = c.frame_length;
+      bp.shift = c.frame_shift;
+      bp.npad_left = plan->npad_left;
+      bp.M = c.num_filters;
+      bp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LOG_SPECTROGRAM ? F_LOG_SPEC : 0);
+      bp.log_offset = c.log_offset;
+      bp.preemph = c.preemph_coeff;
+      bp.mel_floor = c.mel_floor;
+      bp.xs_floats = plan->xs_floats;
+      bp.const_floats = plan->const_floats;
+      bp.dct_consts = plan->d_dct_consts;
+      bp.C = c.num_ceps;
+      bp.lm_stride = plan->lm_stride;
+      bp.dct_groups = plan->dct_groups;
+      bp.dct_floats = plan->dct_floats;
+      arg = &bp;
+      break;
+  }
+  const void* fn = lay->flat && plan->fn_flat ? plan->fn_flat : plan->fn;
+  void* args[] = {arg};
   DeviceGuard g(plan->device);
-  set_lds_poison(plan->lds_bytes);
-  hipLaunchKernelGGL(generic_kernel, dim3((unsigned)lay->total_blocks), dim3(256), plan->lds_bytes, stream, gp);
+  set_lds_poison(plan->lds);
+  (void)hipLaunchKernel(fn, dim3((unsigned)lay->total_blocks), dim3(plan->block), args, plan->lds, stream);
   HIP_TRY(hipGetLastError());
-  if (whisper) {
+  // Whisper: the normalisation pass over every cut, unless whisper3 fused it (then the layout carries the scratch)
+  if (whisper && !(plan->route == Route::Whisper3 && lay->d_norm)) {
     hipLaunchKernelGGL(whisper_norm_kernel, dim3((unsigned)lay->batch), dim3(1024), 0, stream, lay->d_cuts, d_out, lay->out_row_stride,
                        (int32_t)c.num_filters, (int32_t)c.frame_shift);
     HIP_TRY(hipGetLastError());
@@ -2106,7 +1935,7 @@ static hipfeat_status extract_transient(const hipfeat_plan* plan, const float* d
   // Whisper with the fused normalisation: one armed scratch entry per cut travels behind the descriptors (fresh for every call)
   const size_t map_bytes = (lay.block_cut.size() * sizeof(int32_t) + 15) & ~(size_t)15;  // ragged: workgroup -> cut map behind the descriptors
   const size_t desc_bytes = descs.size() * sizeof(CutDesc) + map_bytes;
-  const size_t bytes = desc_bytes + (plan->variant == 9 ? norm_slot_bytes(&lay) : 0);
+  const size_t bytes = desc_bytes + (plan->route == Route::Whisper3 ? norm_slot_bytes(&lay) : 0);
   std::lock_guard<std::mutex> lk(plan->mu);
   StagingSlot& s = plan->slots[plan->next_slot];
   plan->next_slot = (plan->next_slot + 1) % 4;
@@ -2647,7 +2476,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_minibatch_plan(hipfeat_speed_bank*
                                                              int64_t* h_info) {
   if (!bank || !plan || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   if (batch <= 0 || !h_offsets || !h_num_samples || batch > 65535) return fail(HIPFEAT_ERR_INVALID, "bad batch arguments (1 ... 65535 cuts)");
-  if (plan->variant == 9 || plan->cfg.kind == HIPFEAT_WHISPER || plan->cfg.kind == HIPFEAT_LIBROSA_FBANK)
+  if (plan->route == Route::Whisper3 || plan->cfg.kind == HIPFEAT_WHISPER || plan->cfg.kind == HIPFEAT_LIBROSA_FBANK)
     return fail(HIPFEAT_ERR_UNSUPPORTED, "the mini-batch launch pair serves the Kaldi-style plans (spectrogram / fbank / mfcc)");
   if (num_groups < 0 || (num_groups > 0 && !h_group_sizes)) return fail(HIPFEAT_ERR_INVALID, "bad group arguments");
   std::lock_guard<std::mutex> lk(bank->mu);
