@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HIPFEAT_ABI_VERSION 5
+#define HIPFEAT_ABI_VERSION 6
 
 #if defined(HIPFEAT_BUILD)
 #define HIPFEAT_API __attribute__((visibility("default")))
@@ -299,6 +299,44 @@ HIPFEAT_API hipfeat_status hipfeat_minibatch_plan(hipfeat_speed_bank* bank, cons
                                                   int64_t* h_group_rows, int64_t* h_info);
 HIPFEAT_API hipfeat_status hipfeat_minibatch_run(hipfeat_speed_bank* bank, int64_t ticket, float* d_arena, int64_t arena_floats, float* d_out,
                                                  int64_t rows_per_cut, float pad_value, void* stream);
+
+/* ---- ABI v6: the tracks of MixedCuts mixed on the device (noise at an SNR, padding) ------------------------------ */
+/*
+ * CutMix / CutSet.mix / CutSet.pad turn a cut into a MixedCut whose samples come out of MixedCut.load_audio (lhotse/cut/mixed.py:1312-1409):
+ * every audible track is loaded, audio_energy = mean(x^2) is taken per track (lhotse/audio/mixer.py:175-176), every SNR becomes a gain
+ * against the reference track's energy, and AudioMixer adds gain * audio at the tracks' offsets in track order (mixer.py:104-119, 138-172).
+ * Here the tracks of a whole mini-batch lie in ONE device arena (unperturbed tracks as packed, speed-perturbed ones where hipfeat_resample
+ * put them) and two stream-ordered launches -- sums of squares per track, then gains + the scaled sum -- write the mixed cuts behind
+ * them; no value visits the host in between, so hipfeat_extract* over the returned offsets / lengths can follow on the same stream.
+ *   E_t = mean(x_t^2) in float64;  g_t = 1 when the track has no SNR, the cut no reference track, E_ref <= 0 or E_t <= 0, or when it is
+ *   the first track and the reference itself; else g_t = (float)sqrt(E_ref * 10^(-snr_t / 10) / E_t);
+ *   out[i] = ((0 + g_0 * x_0[i - o_0]) + g_1 * x_1[i - o_1]) + ... over the tracks that cover i, float32, product rounded before the add;
+ *   samples no track covers are 0; the cut has max_t(o_t + n_t) samples, cut down to h_max_samples[c] when that is >= 0 and smaller
+ *   (mixed.py:1381-1385).  Results are bit-identical from run to run and do not depend on the other cuts of the batch.
+ *
+ * hipfeat_mixer_create / _destroy: the object that owns the workspace (partial sums, staged tables) on `device`; calls are serialised
+ * inside, up to 16 plans may be outstanding, destroy waits for the work it enqueued.
+ * hipfeat_mix_plan (host only): the tracks of cut c are [h_track_first[c], h_track_first[c + 1]) in the four track tables
+ * (h_track_first[0] = 0; 1 ... 256 tracks per cut): h_src_offset = arena offset of the track's samples, -1 = a padding track (PaddingCut: no
+ * source, it only lengthens the cut); h_src_len = its samples; h_dst_offset = its first sample inside the cut
+ * (compute_num_samples(track.offset)); h_snr_db = its SNR in dB, NaN = none (h_snr_db may be NULL: none at all).  h_ref_track[c] = the
+ * SNR reference track (_get_snr_reference_track, mixed.py:1909-1918) as an index WITHIN the cut, -1 = none (may be NULL).  Every source must
+ * end at or before tail_start: the mixed cuts are written from there on, each on a 16-byte boundary, at h_out_offsets[c] with
+ * h_out_num_samples[c] samples.  h_info[4] = {ticket, floats the arena must hold, energy work items, mix work items}.
+ * A bad table (negative offset, a source that reaches into the tail, a reference index outside the cut or on a padding track, an empty
+ * cut, a 17th plan while 16 are planned and not yet run) returns HIPFEAT_ERR_INVALID, more than 256 tracks in a cut HIPFEAT_ERR_UNSUPPORTED,
+ * and plans nothing.
+ * hipfeat_mix_run enqueues the two launches of a planned mix on `stream` (a ticket runs once); an unknown ticket or an arena smaller
+ * than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.
+ */
+typedef struct hipfeat_mixer hipfeat_mixer;
+HIPFEAT_API hipfeat_status hipfeat_mixer_create(int32_t device, hipfeat_mixer** mixer);
+HIPFEAT_API hipfeat_status hipfeat_mixer_destroy(hipfeat_mixer* mixer);
+HIPFEAT_API hipfeat_status hipfeat_mix_plan(hipfeat_mixer* mixer, int64_t num_cuts, const int64_t* h_track_first, const int64_t* h_src_offset,
+                                            const int64_t* h_src_len, const int64_t* h_dst_offset, const double* h_snr_db,
+                                            const int32_t* h_ref_track, const int64_t* h_max_samples, int64_t tail_start,
+                                            int64_t* h_out_offsets, int64_t* h_out_num_samples, int64_t* h_info);
+HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

@@ -15,7 +15,7 @@ from .extractors import (  # noqa: F401
     HipSpectrogramConfig,
 )
 
-from .augmentation import HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler  # noqa: F401,E402
+from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
 
 from .kaldifeat import (  # noqa: F401,E402
     HipKaldifeatFbank,
@@ -65,6 +65,9 @@ __all__ = [
     "HipKaldifeatMelOptions",
     "HipSpeed",
     "HipSpeedBank",
+    "HipMixer",
+    "mix_in_arena",
+    "mixed_tail_floats",
     "HipResample",
     "HipResampleTensor",
     "get_or_create_resampler",

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # name -> (return C type, [argument C types]) ; mirrors include/hipfeat.h one to one.
 _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
@@ -75,6 +75,14 @@ _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
          "int64_t", "const int64_t*", "int64_t*", "int64_t*", "int64_t*", "int64_t*", "int64_t*"],
     ),
     "hipfeat_minibatch_run": ("int", ["hipfeat_speed_bank*", "int64_t", "float*", "int64_t", "float*", "int64_t", "float", "void*"]),
+    "hipfeat_mixer_create": ("int", ["int32_t", "hipfeat_mixer**"]),
+    "hipfeat_mixer_destroy": ("int", ["hipfeat_mixer*"]),
+    "hipfeat_mix_plan": (
+        "int",
+        ["hipfeat_mixer*", "int64_t", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "const double*", "const int32_t*",
+         "const int64_t*", "int64_t", "int64_t*", "int64_t*", "int64_t*"],
+    ),
+    "hipfeat_mix_run": ("int", ["hipfeat_mixer*", "int64_t", "float*", "int64_t", "void*"]),
     "hipfeat_archive_open": ("int", ["const char* const*", "int32_t", "int32_t", "hipfeat_archive**"]),
     "hipfeat_archive_append": ("int", ["hipfeat_archive*", "const void*", "int64_t", "const int64_t*", "int32_t", "int32_t", "int32_t*", "int64_t*"]),
     "hipfeat_archive_size": ("int64_t", ["const hipfeat_archive*", "int32_t"]),

@@ -243,6 +243,33 @@ def perturbed_tail_floats(lengths: np.ndarray, factors: Sequence[float], samplin
     return total
 
 
+def perturbed_layout(offsets: np.ndarray, lengths: np.ndarray, factors: Sequence[float], sampling_rate: int,
+                     tail_start: int) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Where ``perturb_speed_in_arena`` puts every cut and how long it comes out -- host arithmetic only, THE placement rule: cuts with
+    factor 1 stay, the others go behind ``tail_start`` factor by factor in ascending order, every resampled cut on a 16-byte boundary,
+    ``ceil(new * n / orig)`` samples in float32 (resample.py:309) with orig : new = round(sr * f) : sr reduced by their gcd
+    (resample.py:219-222).  -> (offsets, lengths, first free float behind the resampled cuts, 16-byte aligned)."""
+    from math import gcd
+
+    offsets, lengths = _lib.i64(offsets).copy(), _lib.i64(lengths).copy()
+    fac = np.asarray(factors, dtype=np.float64)
+    assert len(fac) == len(lengths)
+    tail = (int(tail_start) + 3) & ~3
+    for f in sorted(set(fac.tolist())):
+        if f == 1.0:
+            continue
+        idx = np.nonzero(fac == f)[0]
+        src, dst = round(sampling_rate * f), int(sampling_rate)
+        g = gcd(src, dst)
+        out_lens = np.ceil(((dst // g) * lengths[idx] / (src // g)).astype(np.float32)).astype(np.int64)
+        out_offs = np.zeros(len(idx), dtype=np.int64)
+        np.cumsum(((out_lens + 3) & ~3)[:-1], out=out_offs[1:])
+        out_offs += tail
+        offsets[idx], lengths[idx] = out_offs, out_lens
+        tail = (int(out_offs[-1] + out_lens[-1]) + 3) & ~3
+    return offsets, lengths, tail
+
+
 def perturb_speed_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np.ndarray, factors: Sequence[float], sampling_rate: int,
                            tail_start: int) -> Tuple[np.ndarray, np.ndarray]:
     """Mixed-factor speed perturbation of a device-resident packed mini-batch (``PerturbSpeed`` picks one factor per cut,
@@ -253,29 +280,24 @@ def perturb_speed_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np
     distinct factor -- into the tail.  Returns the per-cut (offsets, lengths) of the perturbed batch inside the same arena, i.e. exactly
     what ``hipfeat_extract*`` takes next: no copy of the unperturbed cuts, no host round trip, no second buffer."""
     assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
-    offsets, lengths = _lib.i64(offsets).copy(), _lib.i64(lengths).copy()
+    in_offsets, in_lengths = _lib.i64(offsets), _lib.i64(lengths)
     fac = np.asarray(factors, dtype=np.float64)
-    assert len(fac) == len(lengths)
-    tail = (int(tail_start) + 3) & ~3
+    offsets, lengths, _ = perturbed_layout(in_offsets, in_lengths, factors, sampling_rate, tail_start)
+    last = int((offsets + lengths)[fac != 1.0].max(initial=0))
+    if last > arena.numel():
+        raise ValueError(f"arena too small: {arena.numel()} floats, the perturbed cuts need {last} (see perturbed_tail_floats)")
     dev = arena.device
     for f in sorted(set(fac.tolist())):
         if f == 1.0:
             continue
         idx = np.nonzero(fac == f)[0]
         r = get_or_create_resampler(round(sampling_rate * f), sampling_rate, dev)
-        out_lens = r.output_lengths(lengths[idx])
-        out_offs = np.zeros(len(idx), dtype=np.int64)
-        np.cumsum(((out_lens + 3) & ~3)[:-1], out=out_offs[1:])
-        out_offs += tail
-        end = int(out_offs[-1] + out_lens[-1])
-        if end > arena.numel():
-            raise ValueError(f"arena too small: {arena.numel()} floats, the perturbed cuts need {end} (see perturbed_tail_floats)")
-        in_offs, in_lens = np.ascontiguousarray(offsets[idx]), np.ascontiguousarray(lengths[idx])  # (named: they must outlive the call)
+        in_offs, in_lens = np.ascontiguousarray(in_offsets[idx]), np.ascontiguousarray(in_lengths[idx])  # (named: they must outlive the call)
+        out_offs = np.ascontiguousarray(offsets[idx])
+        assert np.array_equal(r.output_lengths(in_lens), lengths[idx])  # the library's own length rule
         with torch.cuda.device(dev):
             r.lib.check("hipfeat_resample", r.handle, arena.data_ptr(), _lib.addr(in_offs), _lib.addr(in_lens), int(len(idx)), arena.data_ptr(),
                         _lib.addr(out_offs), int(torch.cuda.current_stream(dev).cuda_stream))
-        offsets[idx], lengths[idx] = out_offs, out_lens
-        tail = (end + 3) & ~3
     return offsets, lengths
 
 
@@ -382,3 +404,118 @@ class HipSpeedBank:
             self.close()
         except Exception:
             pass
+
+
+# ---- mixing the tracks of MixedCuts (CutMix / CutSet.mix / .pad) in the same arena --------------------------------------------
+def _mix_tables(track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples):
+    """The host tables of ``hipfeat_mix_plan`` as C-contiguous arrays (``snrs``: None / NaN = no SNR)."""
+    first = np.ascontiguousarray(track_first, dtype=np.int64)
+    n = int(first[-1]) if len(first) else 0
+    snr = np.full(n, np.nan, dtype=np.float64) if snrs is None else np.ascontiguousarray([np.nan if s is None else float(s) for s in snrs], dtype=np.float64)
+    ref = np.full(len(first) - 1, -1, dtype=np.int32) if ref_tracks is None else np.ascontiguousarray(ref_tracks, dtype=np.int32)
+    cap = np.full(len(first) - 1, -1, dtype=np.int64) if max_samples is None else np.ascontiguousarray(max_samples, dtype=np.int64)
+    tabs = (first, np.ascontiguousarray(src_offsets, dtype=np.int64), np.ascontiguousarray(src_lens, dtype=np.int64),
+            np.ascontiguousarray(dst_offsets, dtype=np.int64), snr, ref, cap)
+    if not (len(tabs[1]) == len(tabs[2]) == len(tabs[3]) == len(snr) == n and len(ref) == len(cap) == len(first) - 1):
+        raise ValueError("mix tables: the track tables hold track_first[-1] entries, the cut tables len(track_first) - 1")
+    return tabs
+
+
+def mixed_num_samples(track_first, src_lens, dst_offsets, max_samples=None) -> np.ndarray:
+    """Samples of every mixed cut: ``max_t(offset_t + n_t)`` (``AudioMixer.num_samples_total``, lhotse/audio/mixer.py:77-82), cut down
+    to ``max_samples`` where that is >= 0 and smaller (lhotse/cut/mixed.py:1381-1385)."""
+    first = _lib.i64(track_first)
+    end = _lib.i64(src_lens) + _lib.i64(dst_offsets)
+    out = np.array([int(end[a:b].max(initial=0)) for a, b in zip(first[:-1], first[1:])], dtype=np.int64)
+    if max_samples is not None:
+        cap = _lib.i64(max_samples)
+        out = np.where(cap >= 0, np.minimum(out, cap), out)
+    return out
+
+
+def mixed_tail_floats(track_first, src_lens, dst_offsets, max_samples=None) -> int:
+    """Floats the mixed cuts of a mini-batch need behind ``tail_start`` (every mixed cut starts on a 16-byte boundary)."""
+    return int(((mixed_num_samples(track_first, src_lens, dst_offsets, max_samples) + 3) & ~3).sum()) + 3
+
+
+class HipMixer:
+    """The device half of ``MixedCut.load_audio`` (lhotse/cut/mixed.py:1312-1409) for a packed mini-batch: ``hipfeat_mixer``
+    (include/hipfeat.h) owns the workspace of the two launches -- track energies, then gains + the scaled sum in track order.  Energies
+    and gains never visit the host, so the feature launch can follow on the same stream.  One mixer per device (``get_or_create_mixer``);
+    it may be shared by threads."""
+
+    def __init__(self, device: Union[str, torch.device, None] = None):
+        self.lib = _lib.load()
+        self.handle = 0
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.HipFeatError(1, f"HipMixer runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        out = np.zeros(1, dtype=np.uint64)
+        self.lib.check("hipfeat_mixer_create", int(self.device.index), _lib.addr(out))
+        self.handle = int(out[0])
+        self._lock = threading.Lock()
+
+    def plan(self, track_first, src_offsets, src_lens, dst_offsets, snrs=None, ref_tracks=None, max_samples=None, tail_start: int = 0):
+        """Host only -> (ticket, out_offsets, out_lengths, info = [ticket, arena floats needed, energy items, mix items])."""
+        first, so, sl, do, snr, ref, cap = _mix_tables(track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples)
+        n = len(first) - 1
+        out_offs, out_lens, info = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_mix_plan", self.handle, n, _lib.addr(first), _lib.addr(so), _lib.addr(sl), _lib.addr(do), _lib.addr(snr), _lib.addr(ref),
+                           _lib.addr(cap), int(tail_start), _lib.addr(out_offs), _lib.addr(out_lens), _lib.addr(info))
+        return int(info[0]), out_offs, out_lens, info
+
+    def run(self, ticket: int, arena: torch.Tensor, stream: Optional[int] = None) -> None:
+        assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
+        with torch.cuda.device(self.device):
+            self.lib.check("hipfeat_mix_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
+
+    def close(self):
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_mixer_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_mixers: Dict[int, HipMixer] = {}
+
+
+def get_or_create_mixer(device: Union[str, torch.device, None] = None) -> HipMixer:
+    dev = torch.device("cuda" if device is None else device)
+    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    with _cache_lock:
+        m = _mixers.get(int(index))
+        if m is None:
+            m = _mixers[int(index)] = HipMixer(torch.device(dev.type, index))
+        return m
+
+
+def mix_in_arena(arena: torch.Tensor, track_first, src_offsets, src_lens, dst_offsets, snrs=None, ref_tracks=None, max_samples=None,
+                 tail_start: int = 0, mixer: Optional[HipMixer] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Mix the tracks of a device-resident packed mini-batch of ``MixedCut``s (lhotse/cut/mixed.py:1312-1409, lhotse/audio/mixer.py:10-172);
+    the counterpart of ``perturb_speed_in_arena``, and what runs behind it when a track carries a pending ``Speed``.
+
+    ``arena`` is ONE float32 device buffer: all tracks in front of ``tail_start``, free space behind it (``mixed_tail_floats``).  The tracks
+    of cut ``c`` are ``[track_first[c], track_first[c + 1])`` of the track tables: ``src_offsets`` (arena offset, -1 = a padding track
+    without a source), ``src_lens``, ``dst_offsets`` (first sample inside the cut), ``snrs`` (dB; None / NaN = no SNR); ``ref_tracks[c]``
+    = the SNR reference track as an index within the cut (-1 = none), ``max_samples[c]`` = the cut's sample count when the mix comes
+    out a sample or two longer (-1 = no cap).  Returns the per-cut (offsets, lengths) of the mixed cuts inside the same arena, i.e.
+    what ``hipfeat_extract*`` takes next.  Two launches on the current stream, no device -> host copy, bit-identical from run to run."""
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    if mixer is None:
+        mixer = get_or_create_mixer(arena.device)
+    ticket, offs, lens, info = mixer.plan(track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples, tail_start)
+    if int(info[1]) > arena.numel():
+        raise ValueError(f"arena too small: {arena.numel()} floats, the mixed cuts need {int(info[1])} (see mixed_tail_floats)")
+    mixer.run(ticket, arena)
+    return offs, lens

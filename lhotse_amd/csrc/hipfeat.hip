@@ -25,6 +25,7 @@
 #include "mel4_schedule.hpp"
 #include "kernel_resample.hpp"
 #include "kernel_minibatch.hpp"
+#include "kernel_mix.hpp"
 #include "kernel_specaug.hpp"
 #include "kernel_whisper2.hpp"
 #include "kernel_whisper3.hpp"
@@ -2690,6 +2691,222 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_minibatch_run(hipfeat_speed_bank* 
   hipError_t e2 = hipEventRecord(s.ev, st);
   s.busy = (e2 == hipSuccess);
   return rc;
+}
+
+// --------------------------------------------------------------------------------------
+// MixedCut tracks mixed on the device: energies, gains and the scaled sum in two launches (kernel_mix.hpp)
+// --------------------------------------------------------------------------------------
+constexpr int kMixSlots = 16;
+
+struct MixSlot {
+  int64_t ticket = -1;
+  bool planned = false;
+  std::vector<MixCut> cuts;
+  std::vector<MixTrack> tracks;
+  int64_t energy_items = 0, mix_items = 0, arena_need = 0;
+  void* h = nullptr;  // pinned staging (tables that do not fit the kernel arguments)
+  void* d = nullptr;  // device: the staged tables, then the partial sums of squares
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool busy = false;
+};
+
+struct hipfeat_mixer {
+  int device = 0;
+  bool allow_inline = true;
+  std::mutex mu;
+  MixSlot slots[kMixSlots];
+  int64_t next_ticket = 0;
+};
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_mixer_create(int32_t device, hipfeat_mixer** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "mixer pointer is NULL");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  hipfeat_mixer* m = new (std::nothrow) hipfeat_mixer();
+  if (!m) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  m->device = device;
+  m->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
+  *out = m;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_mixer_destroy(hipfeat_mixer* m) {
+  if (!m) return HIPFEAT_OK;
+  DeviceGuard g(m->device);
+  for (auto& s : m->slots) {
+    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    if (s.ev) (void)hipEventDestroy(s.ev);
+  }
+  delete m;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_plan(hipfeat_mixer* mixer, int64_t num_cuts, const int64_t* h_track_first, const int64_t* h_src_offset,
+                                                       const int64_t* h_src_len, const int64_t* h_dst_offset, const double* h_snr_db,
+                                                       const int32_t* h_ref_track, const int64_t* h_max_samples, int64_t tail_start,
+                                                       int64_t* h_out_offsets, int64_t* h_out_num_samples, int64_t* h_info) {
+  if (!mixer || !h_track_first || !h_src_offset || !h_src_len || !h_dst_offset || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (num_cuts <= 0 || num_cuts > 65535) return fail(HIPFEAT_ERR_INVALID, "bad batch arguments (1 ... 65535 cuts)");
+  if (tail_start < 0) return fail(HIPFEAT_ERR_INVALID, "tail_start %lld is negative", (long long)tail_start);
+  if (h_track_first[0] != 0) return fail(HIPFEAT_ERR_INVALID, "h_track_first[0] must be 0");
+  constexpr int64_t kMaxLen = INT32_MAX / 2;
+  std::lock_guard<std::mutex> lk(mixer->mu);
+  // (validated into locals first: a refused table leaves the outstanding plans as they were)
+  std::vector<MixCut> cuts((size_t)num_cuts);
+  std::vector<MixTrack> tracks;
+  int64_t tail = (tail_start + 3) & ~(int64_t)3, parts = 0, items = 0;
+  for (int64_t c = 0; c < num_cuts; ++c) {
+    const int64_t t0 = h_track_first[c], t1 = h_track_first[c + 1], nt = t1 - t0;
+    if (nt < 1 || t0 > INT32_MAX / 4) return fail(HIPFEAT_ERR_INVALID, "cut %lld: tracks [%lld, %lld): every cut has at least one track", (long long)c, (long long)t0, (long long)t1);
+    if (nt > kMixMaxTracks) return fail(HIPFEAT_ERR_UNSUPPORTED, "cut %lld has %lld tracks, the mix launch serves up to %d per cut", (long long)c, (long long)nt, kMixMaxTracks);
+    const int64_t ref = h_ref_track ? h_ref_track[c] : -1;
+    if (ref < -1 || ref >= nt) return fail(HIPFEAT_ERR_INVALID, "cut %lld: reference track %lld of %lld", (long long)c, (long long)ref, (long long)nt);
+    if (ref >= 0 && h_src_offset[t0 + ref] < 0) return fail(HIPFEAT_ERR_INVALID, "cut %lld: reference track %lld is a padding track", (long long)c, (long long)ref);
+    int64_t total = 0;
+    bool any_snr = false;
+    for (int64_t t = t0; t < t1; ++t) {
+      const int64_t so = h_src_offset[t], n = h_src_len[t], off = h_dst_offset[t];
+      const bool padding = so == -1;
+      if (so < -1 || off < 0) return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld: negative offset (source %lld, in the cut %lld)", (long long)c, (long long)(t - t0), (long long)so, (long long)off);
+      if (n < (padding ? 0 : 1) || n > kMaxLen || off + n > kMaxLen)
+        return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld: %lld samples at offset %lld out of range", (long long)c, (long long)(t - t0), (long long)n, (long long)off);
+      if (!padding && so + n > tail_start)  // the mixed cuts are written from tail_start on: output and source ranges would overlap
+        return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld (offset %lld, %lld samples) reaches into the arena's tail (tail_start %lld), where the mixed cuts are written",
+                    (long long)c, (long long)(t - t0), (long long)so, (long long)n, (long long)tail_start);
+      const double snr = h_snr_db ? h_snr_db[t] : NAN;
+      // no SNR, no reference, a padding track, or the first track being the reference itself (mixed.py:1346-1350): gain 1
+      const bool scaled = !std::isnan(snr) && ref >= 0 && !padding && !(t == t0 && ref == 0);
+      MixTrack tr{};
+      tr.src_off = so;
+      tr.src_len = (int32_t)n;
+      tr.dst_off = (int32_t)off;
+      tr.part_first = 0;
+      tr.part_count = scaled ? 1 : 0;  // (flag; counted below)
+      tr.ratio = scaled ? std::pow(10.0, -snr / 10.0) : -1.0;
+      if (scaled && !(tr.ratio >= 0.0 && std::isfinite(tr.ratio))) return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld: SNR %g dB out of range", (long long)c, (long long)(t - t0), snr);
+      any_snr |= scaled;
+      tracks.push_back(tr);
+      total = std::max(total, off + n);
+    }
+    if (any_snr) tracks[(size_t)(t0 + ref)].part_count = 1;
+    for (int64_t t = t0; t < t1; ++t) {
+      MixTrack& tr = tracks[(size_t)t];
+      tr.part_first = (int32_t)parts;
+      if (tr.part_count) tr.part_count = (tr.src_len + kMixEnergyBlock - 1) / kMixEnergyBlock;
+      parts += tr.part_count;
+    }
+    int64_t n_out = total;
+    if (h_max_samples && h_max_samples[c] >= 0) n_out = std::min(n_out, h_max_samples[c]);  // (mixed.py:1381-1385: a sample or two to truncate)
+    if (n_out < 1) return fail(HIPFEAT_ERR_INVALID, "cut %lld: the mix is empty", (long long)c);
+    MixCut& cd = cuts[(size_t)c];
+    cd.out_off = tail;
+    cd.out_len = (int32_t)n_out;
+    cd.item_first = (int32_t)items;
+    cd.track_first = (int32_t)t0;
+    cd.track_count = (int32_t)nt;
+    cd.ref_track = ref >= 0 ? (int32_t)(t0 + ref) : -1;
+    cd.pad = 0;
+    items += (n_out + kMixBlock - 1) / kMixBlock;
+    tail += (n_out + 3) & ~(int64_t)3;
+    if (items > INT32_MAX - (1 << 24) || parts > INT32_MAX - (1 << 24)) return fail(HIPFEAT_ERR_INVALID, "batch too large for one launch");
+  }
+  if (mixer->slots[mixer->next_ticket % kMixSlots].planned)  // (never drop a live plan: its ticket would fail at run)
+    return fail(HIPFEAT_ERR_INVALID, "%d planned mixes are outstanding: run ticket %lld first", kMixSlots, (long long)mixer->slots[mixer->next_ticket % kMixSlots].ticket);
+  const int64_t ticket = mixer->next_ticket++;
+  MixSlot& s = mixer->slots[ticket % kMixSlots];
+  s.ticket = ticket;
+  s.cuts.swap(cuts);
+  s.tracks.swap(tracks);
+  s.energy_items = parts;
+  s.mix_items = items;
+  s.arena_need = tail;
+  s.planned = true;
+  for (int64_t c = 0; c < num_cuts; ++c) {
+    if (h_out_offsets) h_out_offsets[c] = s.cuts[(size_t)c].out_off;
+    if (h_out_num_samples) h_out_num_samples[c] = s.cuts[(size_t)c].out_len;
+  }
+  h_info[0] = ticket;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.energy_items;
+  h_info[3] = s.mix_items;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
+  if (!mixer || !d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(mixer->mu);
+  MixSlot& s = mixer->slots[((ticket % kMixSlots) + kMixSlots) % kMixSlots];
+  if (s.ticket != ticket || !s.planned)
+    return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned mix (at most %d plans may be outstanding)", (long long)ticket, kMixSlots);
+  if (arena_floats < s.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the mixed cuts need %lld", (long long)arena_floats, (long long)s.arena_need);
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
+  s.planned = false;
+  DeviceGuard g(mixer->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cut_bytes = s.cuts.size() * sizeof(MixCut), trk_bytes = s.tracks.size() * sizeof(MixTrack), bytes = cut_bytes + trk_bytes;  // (multiples of 32)
+  const size_t part_bytes = (size_t)std::max<int64_t>(s.energy_items, 1) * sizeof(double);
+  const bool inl = mixer->allow_inline && bytes <= (size_t)kMbInlineBytes;
+  if (s.busy) {  // the launches that used this slot's device memory last time
+    HIP_TRY(hipEventSynchronize(s.ev));
+    s.busy = false;
+  }
+  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  const size_t dev_bytes = bytes + part_bytes;
+  if (s.cap < dev_bytes) {
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    s.h = s.d = nullptr;
+    s.cap = 0;
+    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
+    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&s.d, cap));
+    s.cap = cap;
+  }
+  MixInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
+  MixHeader& h = args.h;
+  h.arena = d_arena;
+  h.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(s.d) + bytes);
+  h.tables = nullptr;
+  h.num_cuts = (int32_t)s.cuts.size();
+  h.num_tracks = (int32_t)s.tracks.size();
+  h.energy_items = (int32_t)s.energy_items;
+  h.mix_items = (int32_t)s.mix_items;
+  h.table_bytes = (int32_t)bytes;
+  h.pad = 0;
+  auto fill_blob = [&](unsigned char* dst) {
+    std::memcpy(dst, s.cuts.data(), cut_bytes);
+    std::memcpy(dst + cut_bytes, s.tracks.data(), trk_bytes);
+  };
+  // a few workgroups per CU take the items round-robin (as hipfeat_minibatch_run)
+  auto grid_of = [](int64_t items) {
+    const int64_t per_wg = std::max<int64_t>(1, (items + 1791) / 1792);
+    return (unsigned)std::max<int64_t>(1, (items + per_wg - 1) / per_wg);
+  };
+  const size_t dyn = bytes <= (size_t)kMbLdsTableBytes ? bytes : 0;
+  hipError_t e1 = hipSuccess;
+  if (inl) {
+    fill_blob(args.blob);
+    if (s.energy_items > 0) hipLaunchKernelGGL(mix_energy_inline_kernel, dim3(grid_of(s.energy_items)), dim3(256), 0, st, args);
+    hipLaunchKernelGGL(mix_inline_kernel, dim3(grid_of(s.mix_items)), dim3(256), 0, st, args);
+    e1 = hipGetLastError();
+  } else {
+    fill_blob(static_cast<unsigned char*>(s.h));
+    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+    h.tables = static_cast<const unsigned char*>(s.d);
+    if (s.energy_items > 0) hipLaunchKernelGGL(mix_energy_kernel, dim3(grid_of(s.energy_items)), dim3(256), dyn, st, h);
+    hipLaunchKernelGGL(mix_kernel, dim3(grid_of(s.mix_items)), dim3(256), dyn, st, h);
+    e1 = hipGetLastError();
+  }
+  hipError_t e2 = hipEventRecord(s.ev, st);
+  s.busy = (e2 == hipSuccess);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "mix launch failed: %s", hipGetErrorName(e1));
+  return HIPFEAT_OK;
 }
 
 // ---- bulk save path: per-batch host work of the offline driver (host_bulk.hpp) -------------------------------------------------

@@ -702,11 +702,21 @@ class NativeHostPipeline:
 _SHARED_STAGING: Dict[int, "_HostStaging"] = {}
 
 
-def pack_to_device(items: Sequence[ArrayLike], device: torch.device, stage: Optional["_HostStaging"] = None) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+def pack_to_device(items: Sequence[ArrayLike], device: torch.device, stage: Optional["_HostStaging"] = None,
+                   headroom: int = 0) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
     """1-D float32 waveforms (host arrays / CPU tensors / tensors already on ``device``) -> one packed device buffer,
     element offsets and lengths.  Host items go through reusable pinned staging with multi-threaded copies and ONE H2D
-    transfer (a pageable ``.cuda()`` per cut is several times slower); every cut starts on a 16-byte boundary."""
+    transfer (a pageable ``.cuda()`` per cut is several times slower); every cut starts on a 16-byte boundary.
+    ``headroom`` > 0: the buffer is that many floats longer than the packed items (uninitialised space behind them: the arena of
+    a mini-batch that is resampled / mixed in place, allocated once)."""
     lens = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
+    if headroom and all(isinstance(x, torch.Tensor) and x.device == device for x in items):
+        offs = np.zeros(len(items), dtype=np.int64)
+        np.cumsum(lens[:-1], out=offs[1:])
+        total = int(lens.sum())
+        wave = torch.empty(total + int(headroom), dtype=torch.float32, device=device)
+        torch.cat([x.contiguous() for x in items], out=wave[:total])
+        return wave, offs, lens
     if all(isinstance(x, torch.Tensor) and x.device == device for x in items):
         if len(items) == 1:
             return items[0].contiguous(), np.zeros(1, dtype=np.int64), lens
@@ -726,7 +736,7 @@ def pack_to_device(items: Sequence[ArrayLike], device: torch.device, stage: Opti
             if isinstance(x, torch.Tensor):
                 x = x.detach().cpu().contiguous().numpy()
             pieces.append((int(o), np.ascontiguousarray(x)))
-        wave = torch.empty(total, dtype=torch.float32, device=device)
+        wave = torch.empty(total + int(headroom), dtype=torch.float32, device=device)
         hv = host.numpy()
         # pack and upload in a few runs of items: while the DMA engine moves run i out of the pinned buffer the host threads are already
         # copying run i+1 into it (the pack, not PCIe, is the slower of the two)
@@ -956,26 +966,30 @@ class _HipExtractor(FeatureExtractor):
 
         return self._pipe().run(plan, bounds, frames, upload), frames
 
-    def _pack(self, items: Sequence[ArrayLike]) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+    def _pack(self, items: Sequence[ArrayLike], headroom: int = 0) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
         """Concatenate 1-D waveforms into one device buffer (one H2D copy for host inputs).  Every
-        cut starts on a 16-byte boundary so that the kernels can use their 16-byte load path."""
+        cut starts on a 16-byte boundary so that the kernels can use their 16-byte load path.
+        ``headroom``: floats of free space behind the packed items (``pack_to_device``)."""
         dev = self.plan.device
         lens = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
         pcm = [_is_pcm16(x) for x in items]
         if any(pcm):
             if not all(pcm):
                 raise TypeError("a batch must be all float32 or all int16 PCM")
-            return self._pack_pcm16(items, lens)
+            wave, offs, lens = self._pack_pcm16(items, lens)
+            if headroom:  # (the conversion wrote a buffer of its own size: one copy, int16 input only)
+                wave = torch.cat([wave, torch.empty(int(headroom), dtype=wave.dtype, device=wave.device)])
+            return wave, offs, lens
         if dev.type != "cuda":  # only reachable with a stand-in plan (tests); no staging needed
             padded = (lens + 3) & ~3
             offs = np.zeros(len(items), dtype=np.int64)
             np.cumsum(padded[:-1], out=offs[1:])
             total = int(offs[-1] + lens[-1]) if len(items) else 0
-            host = torch.zeros(total, dtype=torch.float32)
+            host = torch.zeros(total + int(headroom), dtype=torch.float32)
             for x, o, n in zip(items, offs, lens):
                 host[o : o + n] = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
             return host, offs, lens
-        return pack_to_device(items, dev, self._stage())
+        return pack_to_device(items, dev, self._stage(), headroom)
 
     def _pack_pcm16(self, items: Sequence[ArrayLike], lens: np.ndarray) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
         """int16 PCM items -> one pinned int16 buffer -> H2D (half the bytes) -> float32 on the device."""

@@ -18,8 +18,21 @@ very segment of the original file ``load_audio`` would read, through the same ``
 ``AudioSource.load_audio`` calls -- and the batch is perturbed on the device, mixed factors and all, in the arena the
 feature launch reads from (``lhotse_amd.augmentation.perturb_speed_in_arena``).  Sample counts follow
 ``assert_and_maybe_fix_num_samples`` (truncate; the rare cut that would need reflect-padding takes the reference's own
-path), values agree with the CPU ``Speed`` to the resampler's 1e-5.  Every other cut (mixed cuts, other or several
-transforms, multi-channel) is loaded exactly as before.
+path), values agree with the CPU ``Speed`` to the resampler's 1e-5.  Every other cut (other or several transforms,
+multi-channel) is loaded exactly as before.
+
+Mixed cuts.  ``CutMix`` / ``CutSet.mix`` / ``.pad`` turn a cut into a ``MixedCut`` whose samples come out of
+``MixedCut.load_audio`` (lhotse/cut/mixed.py:1312-1409): every track is loaded (its ``Speed`` on the CPU), its energy is
+taken, a gain is computed from its SNR, and ``AudioMixer`` adds the scaled tracks at their offsets
+(lhotse/audio/mixer.py:10-172).  With ``gpu_mix`` (default: on unless ``wave_transforms`` are given, as for the speed) the
+tracks of an eligible mixed cut are loaded one by one, the way a mono cut is, and the batch is mixed on the device behind the
+resampler: energy launch, mix launch, then the unchanged feature launch over the mixed samples
+(``FusedMiniBatch.features_of_tracks``, ``lhotse_amd.augmentation.mix_in_arena``).  Unperturbed tracks come out within the
+reference's own float32 rounding of the exact mix (the energies are float64 here, float32 pairwise sums there; bit-equal when no
+gain is involved), perturbed ones within the resampler's 1e-5.  ``deferred_mix`` says which cuts qualify; everything else --
+multi-channel or nested tracks, other transforms, a ``MixedCut`` with transforms of its own, video, a mix that needs reflect-
+padding, a first track with an SNR against another reference track, a muted reference track -- takes ``cut.load_audio()``, and a
+mini-batch may combine device-mixed, plain, speed-only and fallback cuts freely.
 
 Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the class does not.
 """
@@ -54,6 +67,18 @@ def _perturb_in_arena(arena, offsets, lengths, factors, sampling_rate, tail_star
     return perturb_speed_in_arena(arena, offsets, lengths, factors, sampling_rate, tail_start)
 
 
+def _mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples, tail_start):
+    """(indirection for the CPU stand-in of the tests)"""
+    from .augmentation import mix_in_arena
+
+    return mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples, tail_start)
+
+
+def _is_plain(tracks) -> bool:
+    """One track with samples that starts at 0 and is not scaled: the cut IS that track (a MonoCut, speed-perturbed or not)."""
+    return len(tracks) == 1 and not isinstance(tracks[0][0], (int, np.integer)) and int(tracks[0][2]) == 0
+
+
 class FusedMiniBatch:
     """The device-facing half of ``HipOnTheFlyFeatures`` -- packing a (partly speed-perturbed) mini-batch into one arena, the launch pair
     of ``hipfeat_minibatch_*`` (or the per-factor route), the collated feature tensor -- WITHOUT any lhotse type in its interface:
@@ -76,6 +101,105 @@ class FusedMiniBatch:
             feats, feat_lens, _ = self._perturb_and_extract(audios, factors, wants, sampling_rate)
             return feats, feat_lens
         return self.extractor.extract_collated(audios, sampling_rate=sampling_rate, padding_value=LOG_EPSILON)
+
+    def features_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
+        """``features_of`` for a mini-batch in which some cuts are ``MixedCut``s (``CutMix``, ``CutSet.mix`` / ``.pad``), without a lhotse
+        type: every cut is a list of tracks ``(samples, factor, offset_samples, snr, is_reference[, num_samples])`` -- ``samples`` as read
+        from the file (in front of a pending ``Speed(factor)``; 1.0 = none) or, for a ``PaddingCut`` track, its sample COUNT as an int;
+        the track's first sample inside the cut; its SNR in dB or None; whether it is the cut's SNR reference track
+        (``_get_snr_reference_track``, lhotse/cut/mixed.py:1909-1918); optionally the samples the track must end up with after its
+        ``Speed`` (a sample or two are truncated, recording.py:1058-1060).  ``wants[c]`` = samples cut ``c`` must end up with
+        (``cut.num_samples``).  A cut of one unscaled track at offset 0 is a plain cut and is not copied.
+
+        Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> energy launch -> mix launch
+        (``lhotse_amd.augmentation.mix_in_arena``) -> the feature launch over the mixed offsets / lengths; one arena, one stream, no
+        device -> host copy in between.  Without a mixed cut this IS ``features_of``.
+        -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None."""
+        if len(cuts_tracks) != len(wants):
+            raise ValueError("features_of_tracks: one wanted sample count per cut")
+        if all(_is_plain(t) for t in cuts_tracks):
+            audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
+            audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
+            if any(f != 1.0 for f in factors):
+                return self._perturb_and_extract(audios, factors, wants, sampling_rate)
+            feats, feat_lens = self.extractor.extract_collated(audios, sampling_rate=sampling_rate, padding_value=LOG_EPSILON)
+            return feats, feat_lens, ([a.reshape(-1) for a in audios] if self.return_audio else None)
+        return self._mix_and_extract(cuts_tracks, wants, sampling_rate)
+
+    def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int):
+        """Pack every track, resample those with a pending factor into the tail, mix the mixed cuts behind them, extract."""
+        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout
+        from .extractors import _as_1d_float
+
+        ex = self.extractor
+        ex._check_sr(sr)
+        items, factors, caps = [], [], []  # the tracks that have a source, in cut / track order
+        for tracks in cuts_tracks:
+            for tr in tracks:
+                if isinstance(tr[0], (int, np.integer)):
+                    continue
+                a = tr[0]
+                items.append(_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures"))
+                factors.append(float(tr[1]))
+                caps.append(-1 if len(tr) < 6 or tr[5] is None else int(tr[5]))
+        caps = np.asarray(caps, dtype=np.int64)
+        cut_off, cut_len = np.zeros(len(cuts_tracks), dtype=np.int64), np.zeros(len(cuts_tracks), dtype=np.int64)
+
+        def tables(po, pl):
+            """The mix tables over the tracks at po / pl (a sample or two of a resampled track truncated); plain cuts -> cut_off / cut_len."""
+            pl = np.where(caps >= 0, np.minimum(pl, caps), pl)
+            first, so, sl, do, snrs, refs, cap, ids = [0], [], [], [], [], [], [], []
+            k = 0
+            for c, tracks in enumerate(cuts_tracks):
+                if _is_plain(tracks):
+                    cut_off[c], cut_len[c] = po[k], min(int(pl[k]), int(wants[c]))
+                    k += 1
+                    continue
+                ref = -1
+                for t, tr in enumerate(tracks):
+                    if isinstance(tr[0], (int, np.integer)):
+                        so.append(-1), sl.append(int(tr[0]))
+                    else:
+                        so.append(int(po[k])), sl.append(int(pl[k]))
+                        k += 1
+                    do.append(int(tr[2])), snrs.append(tr[3])
+                    if tr[4] and ref < 0:
+                        ref = t
+                first.append(len(so)), refs.append(ref), cap.append(int(wants[c])), ids.append(c)
+            return first, so, sl, do, snrs, refs, cap, ids
+
+        with torch.no_grad():
+            # sizes first, from the lengths alone (the sample counts of the resampled tracks are known on the host, resample.py:309), so
+            # that the tracks are packed straight into the ONE arena everything behind them is written to
+            lens0 = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
+            _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
+            first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
+            if mixed_ids:
+                short = mixed_num_samples(first, sl, do) < np.asarray(cap, dtype=np.int64)
+                if short.any():
+                    raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
+                                     "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
+            headroom = 3 + res_floats + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
+            arena, offs, lens = ex._pack(items, headroom=headroom)
+            front = int(offs[-1] + lens[-1])
+            if any(f != 1.0 for f in factors):
+                po, pl = _perturb_in_arena(arena, offs, lens, factors, sr, front)
+            else:
+                po, pl = offs, lens
+            first, so, sl, do, snrs, refs, cap, mixed_ids = tables(po, pl)
+            mix_start = ((front + 3) & ~3) + res_floats  # behind the resampled tracks (perturbed_layout's own end)
+            if not mixed_ids:  # (every cut turned out to be one plain track, e.g. a mixed cut whose other tracks are muted: nothing to mix)
+                mo = ml = np.zeros(0, dtype=np.int64)
+            else:
+                mo, ml = _mix_in_arena(arena, first, so, sl, do, snrs, refs, cap, mix_start)
+            cut_off[mixed_ids], cut_len[mixed_ids] = mo, ml
+            zero_pad = getattr(ex.config, "edge_rule", "reflect") == "batch_zero_pad"  # as extract_collated
+            padded = np.full(len(cut_len), int(cut_len.max()), dtype=np.int64) if zero_pad else None
+            feats, frames = ex.plan.run_collated(arena, cut_off, cut_len, padded, float(LOG_EPSILON))
+        audio = None
+        if self.return_audio:
+            audio = [arena[int(o) : int(o) + int(n)].cpu() for o, n in zip(cut_off, cut_len)]
+        return feats, torch.from_numpy(np.asarray(frames, dtype=np.int64)), audio
 
     def _speed_bank(self, factors, sr: int, device):
         """The bank of the factors met so far on this device (rebuilt when a new factor shows up); None if one of them is not among
@@ -182,9 +306,16 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         audio = rec._stack_audio_channels(per_source)
         return np.ascontiguousarray(audio.reshape(-1), dtype=np.float32)
 
-    def _read_one(cut, gpu_speed: bool, suppress_errors: bool) -> Optional[Tuple[torch.Tensor, float, int]]:
-        """(samples, factor still to be applied, samples the cut must end up with) or None when the read failed and errors are suppressed."""
+    def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
+        """(samples, factor still to be applied, samples the cut must end up with) or None when the read failed and errors are suppressed.
+        For a mixed cut the device will mix, ``samples`` is the list of its loaded tracks (``FusedMiniBatch.features_of_tracks``); a failed
+        track drops the cut."""
         with suppress_audio_loading_errors(enabled=suppress_errors):
+            tracks = deferred_mix(cut) if gpu_mix else None
+            if tracks is not None and (gpu_speed or all(t[1] in (None, 1.0) for t in tracks)):
+                res = _read_tracks(cut, tracks)
+                if res is not None:
+                    return res
             factor = deferred_speed_factor(cut) if gpu_speed else None
             if factor is not None and factor != 1.0:
                 raw = read_unperturbed(cut, factor)
@@ -201,13 +332,85 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             return torch.from_numpy(audio), 1.0, int(audio.shape[-1])
         return None
 
+    def _pending_speed(cut) -> Optional[float]:
+        """1.0 for a mono cut over an untransformed recording, the factor when exactly one ``Speed`` is pending, None otherwise."""
+        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
+            return None
+        if not cut.recording.transforms:
+            return 1.0
+        return deferred_speed_factor(cut)
+
+    def deferred_mix(cut) -> Optional[List[tuple]]:
+        """The tracks of a ``MixedCut`` the device can mix -- ``[(track cut, factor, offset_samples, snr, is_reference)]`` over its audible
+        tracks, ``factor`` = None for a ``PaddingCut`` track -- or None: load it the reference's way (``cut.load_audio()``).  Decided on
+        the host before anything is read.  Refused: anything but a ``MixedCut`` with audio and without video or ``transforms`` of its own;
+        a track that is not a ``PaddingCut`` or a mono cut whose recording carries no transform or exactly one ``Speed`` (multi-channel
+        cuts, nested mixed cuts, other or several transforms); tracks at another sampling rate; no determinable, a muted or a padding SNR
+        reference track; a first track with an SNR while the reference track is another one (the reference scales it through float64,
+        mixed.py:1346-1350); a mix that comes out shorter than ``cut.num_samples`` (reflect-
+        padded, mixed.py:1386-1387) or longer by lhotse's tolerance or more.  (A perturbed track that would need reflect-padding is found when
+        it is read, as for a mono cut: ``_read_tracks`` returns None and the cut is loaded the reference's way.)"""
+        if type(cut).__name__ != "MixedCut" or not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
+            return None
+        from lhotse.audio.utils import get_audio_duration_mismatch_tolerance
+        from lhotse.cut.mixed import _get_audible_tracks, _get_snr_reference_track  # the reference's own rules are the contract
+
+        try:
+            _, ref = _get_snr_reference_track(cut)
+        except ValueError:
+            return None
+        if ref.mute or all(t.mute for t in cut.tracks) or type(ref.cut).__name__ == "PaddingCut":  # (an explicit is_snr_reference on padding: E_ref = 0)
+            return None
+        tracks = _get_audible_tracks(cut)
+        sr = cut.sampling_rate
+        if tracks[0].snr is not None and tracks[0] is not ref:
+            return None
+        out, total = [], 0
+        for t in tracks:
+            c = t.cut
+            if c.sampling_rate != sr:
+                return None
+            if type(c).__name__ == "PaddingCut":
+                factor = None
+            else:
+                factor = _pending_speed(c)
+                if factor is None:
+                    return None
+            off = compute_num_samples(t.offset, sr)
+            total = max(total, off + compute_num_samples(c.duration, sr))
+            out.append((c, factor, off, t.snr, t is ref))
+        diff = total - cut.num_samples
+        if diff < 0 or diff >= max(1, compute_num_samples(get_audio_duration_mismatch_tolerance(), sampling_rate=sr)):
+            return None
+        return out
+
+    def _read_tracks(cut, tracks) -> Optional[Tuple[list, float, int]]:
+        """The tracks of an eligible mixed cut, each loaded the way a mono cut is (``load_audio`` / ``read_unperturbed``); None when a
+        perturbed track would need reflect-padding (the rule of ``_read_one``)."""
+        sr = cut.sampling_rate
+        loaded = []
+        for c, factor, off, snr, is_ref in tracks:
+            n = compute_num_samples(c.duration, sr)
+            if factor is None:
+                loaded.append((n, 1.0, off, snr, is_ref, n))
+            elif factor != 1.0:
+                raw = read_unperturbed(c, factor)
+                src, dst = round(sr * factor), sr
+                g = gcd(src, dst)
+                if int(np.ceil(np.float32((dst // g) * len(raw) / (src // g)))) < n:  # resample.py:309
+                    return None
+                loaded.append((raw, factor, off, snr, is_ref, n))
+            else:
+                loaded.append((np.ascontiguousarray(c.load_audio().reshape(-1), dtype=np.float32), 1.0, off, snr, is_ref, n))
+        return loaded, 1.0, int(cut.num_samples)
+
     class HipOnTheFlyFeatures(OnTheFlyFeatures, FusedMiniBatch):
         """Same constructor as ``OnTheFlyFeatures`` plus ``return_device`` (``None`` keeps the padded feature tensor on the
         extractor's GPU, ready for the training step; ``"cpu"`` hands back a host tensor like the reference does) and
-        ``gpu_speed_perturb`` (see the module docstring)."""
+        ``gpu_speed_perturb`` / ``gpu_mix`` (see the module docstring)."""
 
         def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
-                     gpu_speed_perturb: Optional[bool] = None, **kwargs) -> None:
+                     gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, **kwargs) -> None:
             if not hasattr(extractor, "extract_collated"):
                 raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
             super().__init__(extractor, *args, **kwargs)
@@ -218,20 +421,27 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             # wave_transforms is a contradiction and raises when a perturbed cut is met.
             self._gpu_speed_explicit = gpu_speed_perturb is not None
             self.gpu_speed_perturb = (not self.wave_transforms) if gpu_speed_perturb is None else bool(gpu_speed_perturb)
+            # the same for the tracks of mixed cuts: wave_transforms run on the MIXED samples, so with them the mix stays where the
+            # reference does it (MixedCut.load_audio); an explicit True together with wave_transforms raises when a mixed cut is met
+            self.gpu_mix = (not self.wave_transforms) if gpu_mix is None else bool(gpu_mix)
 
         def _read(self, cuts, pool, recording_field):
             """read_audio_from_cuts (lhotse/dataset/collation.py:541-600) with the Speed of eligible cuts left for the device."""
-            if recording_field is not None or not self.gpu_speed_perturb or not any(deferred_speed_factor(c) not in (None, 1.0) for c in cuts):
+            cuts = list(cuts)
+            on_device = recording_field is None and (
+                (self.gpu_speed_perturb and any(deferred_speed_factor(c) not in (None, 1.0) for c in cuts))
+                or (self.gpu_mix and any(type(c).__name__ == "MixedCut" for c in cuts)))
+            if not on_device:
                 audios, ok = read_audio_from_cuts(cuts, executor=pool, suppress_errors=self.fault_tolerant, recording_field=recording_field)
                 return audios, [1.0] * len(audios), [int(a.shape[-1]) for a in audios], ok
             from functools import partial
 
             from lhotse import CutSet
 
-            cuts = list(cuts)
             map_fn = map if pool is None else pool.map
             audios, factors, wants, ok = [], [], [], []
-            for cut, res in zip(cuts, map_fn(partial(_read_one, gpu_speed=True, suppress_errors=self.fault_tolerant), cuts)):
+            read = partial(_read_one, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix)
+            for cut, res in zip(cuts, map_fn(read, cuts)):
                 if res is None:
                     continue
                 audios.append(res[0]), factors.append(res[1]), wants.append(res[2]), ok.append(cut)
@@ -244,7 +454,12 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             helpers it uses."""
             pool = _get_executor(self.num_workers, executor_type=self._executor_type)
             audios, factors, wants, cuts = self._read(cuts, pool, recording_field)
+            mixed = any(isinstance(a, list) for a in audios)  # (the loaded tracks of the cuts the device mixes)
             for transform in self.wave_transforms:
+                if mixed:
+                    raise ValueError("gpu_mix=True was requested together with wave_transforms: the transforms run on the mixed samples, "
+                                     "before the device mixes the tracks; leave gpu_mix at its default (None: MixedCut.load_audio whenever "
+                                     "wave_transforms are given) or pass False")
                 if any(f != 1.0 for f in factors):
                     raise ValueError("gpu_speed_perturb=True was requested together with wave_transforms: the transforms run on the loaded "
                                      "samples, before the device applies the pending speed factors; leave gpu_speed_perturb at its default "
@@ -254,7 +469,10 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             assert len(rates) == 1, f"one launch per batch needs a single sampling rate, got {sorted(rates)}"
             sr = rates.pop()
             perturbed = None
-            if any(f != 1.0 for f in factors):  # (FusedMiniBatch.features_of, with the perturbed samples kept for `return_audio`)
+            if mixed:  # (FusedMiniBatch.features_of_tracks: a plain cut is a cut of one track)
+                tracks = [a if isinstance(a, list) else [(a, f, 0, None, True)] for a, f in zip(audios, factors)]
+                feats, feat_lens, perturbed = self._mix_and_extract(tracks, wants, sr)
+            elif any(f != 1.0 for f in factors):  # (FusedMiniBatch.features_of, with the perturbed samples kept for `return_audio`)
                 feats, feat_lens, perturbed = self._perturb_and_extract(audios, factors, wants, sr)
             else:
                 feats, feat_lens = self.extractor.extract_collated(audios, sampling_rate=sr, padding_value=LOG_EPSILON)
