@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
+#include "plan_tables.hpp"  // WaveWork
 
 namespace hipfeat {
 
@@ -17,10 +18,6 @@ constexpr int kPRowStride = 260;                      // dwords per power row (=
 constexpr int kMaxGroups0 = 20;                       // 8-bin MFMA groups of a wave's first / second mel tile
 constexpr int kMaxGroups1 = 4;
 constexpr int kMelARegs = 2 * (kMaxGroups0 + kMaxGroups1);
-
-struct WaveWork {  // mel work of one wave: up to two (tile, band) segments
-  int32_t tile0, bin0, ngroups0, tile1, bin1, ngroups1, pad0, pad1;
-};
 
 struct Fft512Params {
   const float* wave;

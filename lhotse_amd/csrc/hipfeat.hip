@@ -22,7 +22,7 @@
 #include "kernel_fft512c.hpp"
 #include "kernel_fft1024c.hpp"
 #include "kernel_fft2048c.hpp"
-#include "mel4_schedule.hpp"
+#include "plan_tables.hpp"
 #include "kernel_resample.hpp"
 #include "kernel_minibatch.hpp"
 #include "kernel_mix.hpp"
@@ -142,11 +142,11 @@ struct hipfeat_plan {
   int xs_floats = 0;
   int const_floats = 0;
   float* d_lds_consts = nullptr;
-  float* d_mel_a = nullptr;
+  float* d_mel_a = nullptr;  // fft512 "b": the operands before the reorder to d_mel_a4 (uploaded, read by no kernel)
   WaveWork* d_work = nullptr;
   // wave-autonomous kernels (fft512c, fft256c, fft1024c, fft2048c, whisper3)
   float* d_c_shared = nullptr;  // LDS image: FFT constants | 4x4-block filterbank weights | lane tables
-  int c_shared_floats = 0, c_wtab_off = 0, c_ltab_off = 0, c_xs_floats = 0, c_rounds = 0;
+  int c_shared_floats = 0, c_wtab_off = 0, c_ltab_off = 0, c_xs_floats = 0;
   // wave-autonomous kernels: frames per workgroup = fpb_unit (frames of one round of all waves) x rounds, rounds chosen per LAYOUT between 2
   // and c_rounds_max: long launches take many rounds per workgroup (the constant tables and the first, un-overlapped span are paid once per
   // workgroup: 16 instead of 8 rounds is + 4 % on the bench workload), short ones few (enough workgroups to fill the chip)
@@ -158,7 +158,6 @@ struct hipfeat_plan {
   int x_waves = 0, x_tws_off = 0, x_tw32_off = 0;
   // wave-per-frame kernel
   float* d_mel_t = nullptr;  // filterbank blob (descriptors + compact weights)
-  int mel_maxband = 0;
   int wave_blob_floats = 0;
   bool wave_dct_in_lds = false;
   // whisper2 (whisper3 reads its d_wh2_cs)
@@ -166,8 +165,6 @@ struct hipfeat_plan {
   float* d_wh2_tw = nullptr;
   float* d_wh2_mel = nullptr;
   int32_t* d_wh2_sched = nullptr;
-  int32_t wh2_k0[kW2MaxMelTiles] = {}, wh2_steps[kW2MaxMelTiles] = {}, wh2_off[kW2MaxMelTiles] = {};
-  int32_t wh2_wave_tiles[4][2] = {};
   // transient-layout staging ring (hipfeat_extract)
   mutable std::mutex mu;
   mutable StagingSlot slots[4];
@@ -285,11 +282,22 @@ static void plan_free(hipfeat_plan* p) {
 }
 
 // --------------------------------------------------------------------------------------
-// fft512 fast path: eligibility, constants, mel work split
+// specialised kernels.  Every setup_* checks that the configuration and the routing switches admit its kernel family, has the family's
+// constant tables built (plan_tables.hpp: pure host code, tested on the CPU), tests the LDS budget, picks the kernel instance, uploads
+// the tables and claims the plan.  A setup that leaves the plan unclaimed has changed nothing the next one reads.
 // --------------------------------------------------------------------------------------
-template <int NROWS, int OUT>
-static const void* fft512b_entry() {
-  return reinterpret_cast<const void*>(&fft512b_kernel<NROWS, OUT>);
+template <auto* F>
+static const void* entry() {
+  return reinterpret_cast<const void*>(F);
+}
+
+static std::string strf(const char* fmt, ...) {
+  char buf[192];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return buf;
 }
 
 // The dynamic-LDS limit of a kernel is a property of the FUNCTION, shared by every plan of the process: it is only ever
@@ -330,103 +338,72 @@ static hipfeat_status claim(hipfeat_plan* p, Route route, const void* fn, int bl
   return HIPFEAT_OK;
 }
 
-// Mel work split of the fast kernels: band of every 16-mel tile in 8-bin groups, assigned to the 4 waves, and the MFMA
-// A operands in lane order.  Returns false when the filterbank does not fit the static schedule (-> generic kernel).
-static bool build_mel_schedule(const float* h_mel, int M, int K, int prow_stride, int ntiles, WaveWork (&work)[4], std::vector<float>& mel_a) {
-  struct Seg { int tile, bin, ng; };
-  std::vector<Seg> segs;
-  for (int t = 0; t < ntiles; ++t) {
-    int lo = K, hi = 0;
-    for (int k = 0; k < K; ++k)
-      for (int j = 16 * t; j < std::min(M, 16 * t + 16); ++j)
-        if (h_mel[(size_t)k * M + j] != 0.0f) {
-          lo = std::min(lo, k);
-          hi = std::max(hi, k + 1);
-        }
-    if (hi == 0) lo = 0, hi = 1;
-    int lo2 = lo & ~1;
-    int ng = (hi - lo2 + 7) / 8;
-    if (lo2 + 8 * ng > prow_stride) lo2 = (prow_stride - 8 * ng) & ~1;  // keep reads inside the padded row
-    if (lo2 < 0 || ng > kMaxGroups0) return false;
-    segs.push_back({t, lo2, ng});
-  }
-  // the four widest tiles become the waves' first segment, the rest go to the least loaded waves
-  std::sort(segs.begin(), segs.end(), [](const Seg& a, const Seg& b) { return a.ng > b.ng; });
-  std::memset(work, 0, sizeof(work));
-  int load[4] = {0, 0, 0, 0};
-  bool has1[4] = {false, false, false, false};
-  for (size_t i = 0; i < segs.size(); ++i) {
-    const Seg& sg = segs[i];
-    if (i < 4) {
-      work[i].tile0 = sg.tile; work[i].bin0 = sg.bin; work[i].ngroups0 = sg.ng;
-      load[i] = sg.ng;
-      continue;
-    }
-    if (sg.ng > kMaxGroups1) return false;
-    int best = -1;
-    for (int w = 0; w < 4; ++w)
-      if (!has1[w] && (best < 0 || load[w] < load[best])) best = w;
-    if (best < 0) return false;
-    work[best].tile1 = sg.tile; work[best].bin1 = sg.bin; work[best].ngroups1 = sg.ng;
-    has1[best] = true;
-    load[best] += sg.ng;
-  }
-  // MFMA A operands: lane (i = lane & 15, kk = lane >> 4) of step (2*gi + r) holds
-  // W[bin + 8*gi + 2*kk + r][16*tile + i]; the second segment's steps start at 2*kMaxGroups0
-  mel_a.assign((size_t)4 * kMelARegs * 64, 0.0f);
-  for (int w = 0; w < 4; ++w)
-    for (int sgm = 0; sgm < 2; ++sgm) {
-      const int tile = sgm ? work[w].tile1 : work[w].tile0, bin = sgm ? work[w].bin1 : work[w].bin0;
-      const int ng = sgm ? work[w].ngroups1 : work[w].ngroups0;
-      for (int g2 = 0; g2 < ng; ++g2)
-        for (int r = 0; r < 2; ++r)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int i = lane & 15, kk = lane >> 4;
-            const int b = bin + 8 * g2 + 2 * kk + r, m = 16 * tile + i;
-            const int step = 2 * ((sgm ? kMaxGroups0 : 0) + g2) + r;
-            if (b < K && m < M) mel_a[((size_t)w * kMelARegs + step) * 64 + lane] = h_mel[(size_t)b * M + m];
-          }
-    }
-  return true;
+// Wave-autonomous families: uploads the LDS image, stores what launch() passes on, claims the plan for `fn` and names it `head` + the
+// common trailer.  A wave takes `frames` frames per round; a workgroup runs 2 .. rounds_max rounds, chosen per layout (build_descs).
+static hipfeat_status claim_wave_auto(hipfeat_plan* p, Route route, const void* fn, const WaveAutoTables& t, int frames, int rounds, int rounds_max,
+                                      const std::string& head) {
+  hipfeat_status st;
+  if ((st = upload(&p->d_c_shared, t.image.data(), t.image.size())) != HIPFEAT_OK) return st;
+  if (!t.dct.empty() && (st = upload(&p->d_dct_consts, t.dct.data(), t.dct.size())) != HIPFEAT_OK) return st;
+  if (!t.twp.empty() && (st = upload(&p->d_x_twp, t.twp.data(), t.twp.size())) != HIPFEAT_OK) return st;
+  p->c_shared_floats = t.shared_floats;
+  p->c_wtab_off = t.wtab_off;
+  p->c_ltab_off = t.ltab_off;
+  p->c_xs_floats = t.xs_floats;
+  p->x_tws_off = t.tws_off;
+  p->x_tw32_off = t.tw32_off;
+  p->w_nsets = t.w_nsets;
+  std::copy(t.w_steps, t.w_steps + 4, p->w_steps);
+  std::copy(t.w_step0, t.w_step0 + 4, p->w_step0);
+  p->fpb_unit = t.waves * frames;
+  p->fpb = p->fpb_unit * rounds;
+  p->c_rounds_max = rounds_max;
+  if ((st = claim(p, route, fn, 64 * t.waves, t.lds)) != HIPFEAT_OK) return st;
+  p->kernel_name = head + strf(" lds=%zuB blocks/CU=%d mel4=%dx%d", t.lds, p->blocks_per_cu, t.sch_nsets, t.sch_steps);
+  return HIPFEAT_OK;
 }
 
-// DCT^T as MFMA A operands + lifter (MFCC stage of the fast kernels): lane (i = lane & 15, kk = lane >> 4) of group g,
-// half r holds dct[mel = 8 g + 2 kk + r][ceps = 16 ct + i]  (Wav2MFCC._dct, layers.py:697-706)
-static std::vector<float> build_dct_operands(const hipfeat_config& c, const float* h_dct, const float* h_lifter, int dct_groups) {
-  const int M = c.num_filters, C = c.num_ceps, nct = (C + 15) / 16;
-  std::vector<float> da((size_t)nct * dct_groups * 64 * 2, 0.0f);
-  for (int ct = 0; ct < nct; ++ct)
-    for (int g2 = 0; g2 < dct_groups; ++g2)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int r = 0; r < 2; ++r) {
-          const int i = lane & 15, kk = lane >> 4, m = 8 * g2 + 2 * kk + r, cc = 16 * ct + i;
-          if (m < M && cc < C) da[(((size_t)ct * dct_groups + g2) * 64 + lane) * 2 + r] = h_dct[(size_t)m * C + cc];
-        }
-  for (int cc = 0; cc < 64; ++cc)  // lifter (layers.py:681-695), ones when cepstral_lifter == 0
-    da.push_back((c.apply_lifter && h_lifter && cc < C) ? h_lifter[cc] : 1.0f);
-  return da;
+// fft512 "b" / fft256 "b": uploads the tables, stores what launch() passes on, claims the plan for `fn`
+static hipfeat_status claim_tile(hipfeat_plan* p, Route route, const void* fn, const TileTables& t, int tile_frames, const char* kernel) {
+  const hipfeat_config& c = p->cfg;
+  const bool mfcc = c.kind == HIPFEAT_MFCC, spec = c.kind == HIPFEAT_SPECTROGRAM || c.kind == HIPFEAT_LOG_SPECTROGRAM;
+  hipfeat_status st;
+  if ((st = upload(&p->d_lds_consts, t.consts.data(), t.consts.size())) != HIPFEAT_OK) return st;
+  if (route == Route::Fft512b && (st = upload(&p->d_mel_a, t.mel_a.data(), t.mel_a.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(&p->d_work, t.work, 4)) != HIPFEAT_OK) return st;
+  if ((st = upload(&p->d_mel_a4, t.mel_a4.data(), t.mel_a4.size())) != HIPFEAT_OK) return st;
+  if (mfcc && (st = upload(&p->d_dct_consts, t.dct.data(), t.dct.size())) != HIPFEAT_OK) return st;
+  // 16 tiles per workgroup: the constant-table load and the first, un-overlapped span fetch are paid once per workgroup (measured on
+  // MI355X, cuts/s: fft512 4 -> 1.98 M, 8 -> 2.11 M, 16 -> 2.16 M; fft256 at 8 kHz fbank-80 8 -> 3.84 M, 16 -> 3.99 M, 32 -> 3.93 M)
+  p->tiles_per_block = 16;
+  p->fpb = tile_frames * p->tiles_per_block;
+  p->const_floats = (int)t.consts.size();
+  p->xs_floats = t.xs_floats;
+  p->lm_stride = t.lm_stride;
+  p->dct_groups = t.dct_groups;
+  p->dct_floats = (int)t.dct.size();
+  if ((st = claim(p, route, fn, 256, t.lds)) != HIPFEAT_OK) return st;
+  // same spelling as the device symbol rocprofv3 reports (modulo the space after the comma)
+  p->kernel_name = strf("%s<%d,%d> %s lds=%zuB blocks/CU=%d", kernel, t.nrows, mfcc ? 1 : (spec ? 2 : 0), mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"), t.lds,
+                        p->blocks_per_cu);
+  return HIPFEAT_OK;
 }
 
 // --------------------------------------------------------------------------------------
-// fft512 wave-autonomous fbank kernel (kernel_fft512c.hpp); its filterbank schedule is built in mel4_schedule.hpp
+// fft512: the wave-autonomous fbank / mfcc kernel (kernel_fft512c.hpp), else the 16-frame-tile kernel "b" (kernel_fft512b.hpp)
 // --------------------------------------------------------------------------------------
-template <int NROWS, int NFULL, int MODE, bool FLAT = false>
-static const void* fft512c_entry() {
-  return reinterpret_cast<const void*>(&fft512c_kernel<NROWS, NFULL, MODE, FLAT>);
-}
-
 // the (rows, frame length) that have a FLAT instance (ragged batches by frame quads, kernel_fft512c.hpp): the 25 ms @ 16 kHz default
 static bool fft512c_has_flat(int nrows, int N) { return nrows == 13 && N >= 384; }
 
 // (rows, frame length, mode) -> kernel instance
 template <int MODE>
 static const void* fft512c_pick(int nrows, int N, bool flat) {
-  if (flat && fft512c_has_flat(nrows, N)) return fft512c_entry<13, 12, MODE, true>();
-  if (nrows == 10) return fft512c_entry<10, 0, MODE>();
+  if (flat && fft512c_has_flat(nrows, N)) return entry<fft512c_kernel<13, 12, MODE, true>>();
+  if (nrows == 10) return entry<fft512c_kernel<10, 0, MODE>>();
   // 25 ms at 16 kHz (N = 400: 12 full rows of 32 samples + a partial one) gets the instance without length masks on the full rows
-  if (nrows == 13 && N >= 384) return fft512c_entry<13, 12, MODE>();
-  if (nrows == 13) return fft512c_entry<13, 0, MODE>();
-  return fft512c_entry<16, 0, MODE>();
+  if (nrows == 13 && N >= 384) return entry<fft512c_kernel<13, 12, MODE>>();
+  if (nrows == 13) return entry<fft512c_kernel<13, 0, MODE>>();
+  return entry<fft512c_kernel<16, 0, MODE>>();
 }
 static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat) {
   return mode == 0 ? fft512c_pick<0>(nrows, N, flat)
@@ -435,476 +412,131 @@ static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat) {
 
 // Claims the plan (Route::Fft512c) when the configuration takes the wave-autonomous kernel, leaves it unclaimed when it does
 // not (the caller then sets up kernel "b").
-static hipfeat_status setup_fft512c(hipfeat_plan* p, const float* h_window, const float* h_mel, int nrows, const float* h_dct, const float* h_lifter) {
-  const hipfeat_config& c = p->cfg;
-  const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
-  const bool mfcc = c.kind == HIPFEAT_MFCC;
-  if (mfcc && (M > 4 * kCDctChunks || c.num_ceps > 64 || !h_dct)) return HIPFEAT_OK;
-  // mode 0: 2 accumulator sets x 16 steps (many narrow filters); modes 1 / 2 (MFCC): 1 set x 32 steps (few, wide filters)
-  Mel4Schedule sch;
-  int mode = mfcc ? (M <= 4 * kCDctChunksSmall ? 3 : 2) : 0;  // MFCC: 3 = at most 24 filters (6 chunks of DCT operands + split-step twiddles in registers)
-  if (mfcc || !build_mel4_schedule(h_mel, M, p->K, kCPRowStride, kCMaxSets, kCMaxSteps, sch)) {
-    if (!build_mel4_schedule(h_mel, M, p->K, kCPRowStride, 1, 2 * kCMaxSteps, sch)) return HIPFEAT_OK;
-    if (!mfcc) mode = 1;
+static hipfeat_status setup_fft512c(hipfeat_plan* p, const PlanInputs& in, int nrows) {
+  const bool mfcc = p->cfg.kind == HIPFEAT_MFCC;
+  if (mfcc && (in.M > 4 * kCDctChunks || in.C > 64 || !in.dct)) return HIPFEAT_OK;
+  const WaveAutoTables t = build_fft512c_tables(in, nrows, {kCPRowStride, kCMaxSets, kCMaxSteps, kCWaves, kCRegion}, kCDctChunks, kCDctChunksSmall);
+  if (!t.fits || t.lds > 80 * 1024 || (t.xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
+  // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
+  hipfeat_status st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false), t, 4, 8, 16,
+                                      strf("fft512c_kernel<%d> %s", nrows, mfcc ? "mfcc" : "fbank"));
+  if (st == HIPFEAT_OK && fft512c_has_flat(nrows, in.N)) {  // the same launch shape, chosen per layout (build_descs)
+    p->fn_flat = fft512c_dispatch(t.mode, nrows, in.N, true);
+    hipError_t e = ensure_dynamic_lds(p->fn_flat, t.lds);
+    if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", t.lds, hipGetErrorName(e));
   }
-  const int tsets = mode == 0 ? kCMaxSets : 1, tsteps = mode == 0 ? kCMaxSteps : 2 * kCMaxSteps;
-  // LDS image: window/2 as (even, odd) sample pairs per (row n1, lane q); pass twiddles W_256^(q k1) per (row k1, lane q);
-  // split-step twiddles -i W_512^(q + 16 k2) per (row k2 < 8, lane q); then the filterbank tables
-  std::vector<float> img((size_t)(nrows * 16 + 256 + 128) * 2, 0.0f);
-  for (int n1 = 0; n1 < nrows; ++n1)
-    for (int q = 0; q < 16; ++q)
-      for (int e = 0; e < 2; ++e) {
-        const int i = 32 * n1 + 2 * q + e;
-        img[2 * (n1 * 16 + q) + e] = i < N ? 0.5f * h_window[i] : 0.0f;
-      }
-  float* twp = img.data() + 2 * nrows * 16;
-  float* tws = twp + 512;
-  for (int k1 = 0; k1 < 16; ++k1)
-    for (int q = 0; q < 16; ++q) {
-      const double a = -2.0 * M_PI * (double)(q * k1) / 256.0;
-      twp[2 * (k1 * 16 + q)] = (float)std::cos(a);
-      twp[2 * (k1 * 16 + q) + 1] = (float)std::sin(a);
-    }
-  for (int k2 = 0; k2 < 8; ++k2)
-    for (int q = 0; q < 16; ++q) {  // w = -i * W_512^k = (sin(a), -cos(a)) with a = -2 pi k / 512
-      const double a = -2.0 * M_PI * (double)(q + 16 * k2) / 512.0;
-      tws[2 * (k2 * 16 + q)] = (float)std::sin(a);
-      tws[2 * (k2 * 16 + q) + 1] = (float)(-std::cos(a));
-    }
-  // the kernel runs `tsets` sets of `tsteps` steps unconditionally: pad the tables (weights 0, no output column)
-  p->c_wtab_off = (int)img.size();
-  img.resize(img.size() + (size_t)tsets * tsteps * 64, 0.0f);
-  for (int s2 = 0; s2 < sch.nsets; ++s2)
-    std::memcpy(img.data() + p->c_wtab_off + (size_t)s2 * tsteps * 64, sch.wtab.data() + (size_t)sch.step0[s2] * 64, (size_t)sch.steps[s2] * 64 * sizeof(float));
-  p->c_ltab_off = (int)img.size();
-  img.resize(img.size() + (size_t)tsets * 256, 0.0f);
-  {
-    const int none = kMel4NoColumn;
-    for (int s2 = 0; s2 < tsets; ++s2)
-      for (int lane = 0; lane < 64; ++lane) {
-        float* lt = img.data() + p->c_ltab_off + ((size_t)s2 * 64 + lane) * 4;
-        if (s2 < sch.nsets) std::memcpy(lt, sch.ltab.data() + ((size_t)s2 * 64 + lane) * 4, 4 * sizeof(float));
-        else std::memcpy(lt + 1, &none, 4);
-      }
-  }
-  while (img.size() % 64) img.push_back(0.0f);
-  p->c_shared_floats = (int)img.size();
-  p->c_xs_floats = (3 * shift + 32 * nrows + 3) & ~3;
-  const size_t lds = ((size_t)p->c_shared_floats + (size_t)kCWaves * (p->c_xs_floats + kCRegion)) * sizeof(float);
-  if (lds > 80 * 1024 || (p->c_xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
-  hipfeat_status st;
-  if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
-  if (mfcc) {  // DCT operands in matrix-core lane order: [chunk of 4 filters][lane = cepstral coefficient][filter in the chunk], then the lifter
-    const int C = c.num_ceps;
-    const int dch = mode == 3 ? kCDctChunksSmall : kCDctChunks;
-    std::vector<float> dt((size_t)dch * 256 + 64, 0.0f);
-    for (int m = 0; m < M; ++m)
-      for (int cc = 0; cc < C; ++cc) dt[((size_t)(m / 4) * 64 + cc) * 4 + (m & 3)] = h_dct[(size_t)m * C + cc];
-    for (int cc = 0; cc < 64; ++cc) dt[(size_t)dch * 256 + cc] = (c.apply_lifter && h_lifter && cc < C) ? h_lifter[cc] : 1.0f;
-    if ((st = upload(&p->d_dct_consts, dt.data(), dt.size())) != HIPFEAT_OK) return st;
-  }
-  p->c_rounds = 8;  // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
-  p->fpb = kCWaves * p->c_rounds * 4;
-  p->fpb_unit = kCWaves * 4;
-  p->c_rounds_max = 16;
-  if ((st = claim(p, Route::Fft512c, fft512c_dispatch(mode, nrows, N, false), 64 * kCWaves, lds)) != HIPFEAT_OK) return st;
-  if (fft512c_has_flat(nrows, N)) {  // the same launch shape, chosen per layout (build_descs)
-    p->fn_flat = fft512c_dispatch(mode, nrows, N, true);
-    hipError_t e = ensure_dynamic_lds(p->fn_flat, lds);
-    if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
-  }
-  int total_steps = 0;
-  for (int s2 = 0; s2 < sch.nsets; ++s2) total_steps += sch.steps[s2];
-  char nm[128];
-  snprintf(nm, sizeof(nm), "fft512c_kernel<%d> %s lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, mfcc ? "mfcc" : "fbank", lds, p->blocks_per_cu, sch.nsets, total_steps);
-  p->kernel_name = nm;
-  return HIPFEAT_OK;
+  return st;
 }
 
-static hipfeat_status setup_fft512(hipfeat_plan* p, const float* h_window, const float* h_mel, const float* h_dct,
-                                   const float* h_lifter) {
+static hipfeat_status setup_fft512(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
   const char* force = route_env("HIPFEAT_FORCE_GENERIC");
   if (force && force[0] == '1') return HIPFEAT_OK;
-  const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
   const bool mfcc = c.kind == HIPFEAT_MFCC;
   const bool spec = c.kind == HIPFEAT_SPECTROGRAM || c.kind == HIPFEAT_LOG_SPECTROGRAM;
-  if (c.kind > HIPFEAT_MFCC || c.fft_length != 512 || (shift & 1) || N < 32 || c.use_energy || (!spec && c.use_fft_mag))
+  if (c.kind > HIPFEAT_MFCC || c.fft_length != 512 || (in.shift & 1) || in.N < 32 || c.use_energy || (!spec && c.use_fft_mag))
     return HIPFEAT_OK;
-  if (mfcc && (M > 8 * kMaxDctGroups || c.num_ceps > 64)) return HIPFEAT_OK;
-  const int need = (N + 31) / 32;
+  if (mfcc && (in.M > 8 * kMaxDctGroups || in.C > 64)) return HIPFEAT_OK;
+  const int need = (in.N + 31) / 32;
   const int nrows = need <= 10 ? 10 : (need <= 13 ? 13 : 16);
-  const int ntiles = spec ? 0 : (M + 15) / 16;
-  if (ntiles > 8) return HIPFEAT_OK;
+  if ((in.M + 15) / 16 > 8) return HIPFEAT_OK;  // at most 8 mel tiles of 16 filters
 
   if (!spec) {  // log-mel filterbank / MFCC: the wave-autonomous kernel, unless the schedule or the LDS budget says no
     const char* var = route_env("HIPFEAT_FFT512_VARIANT");
     if (!(var && var[0] == 'b')) {  // HIPFEAT_FFT512_VARIANT=b: the 16-frame-tile kernel for these too (tests compare the two)
-      hipfeat_status stc = setup_fft512c(p, h_window, h_mel, nrows, h_dct, h_lifter);
+      hipfeat_status stc = setup_fft512c(p, in, nrows);
       if (stc != HIPFEAT_OK || p->route == Route::Fft512c) return stc;
     }
   }
-  WaveWork work[4];
-  std::vector<float> mel_a;
-  if (!build_mel_schedule(h_mel, M, p->K, kPRowStride, ntiles, work, mel_a)) return HIPFEAT_OK;  // -> generic kernel
-  // LDS constant block: window/2 as (even, odd) sample pairs per (row n1, lane q); pass twiddles
-  // W_256^(q k1) per (row k1, lane q); split-step twiddles -i W_512^(q + 16 k2) per (row k2, lane q)
-  std::vector<float> wh(512, 0.0f);
-  for (int i = 0; i < N; ++i) wh[i] = 0.5f * h_window[i];
-  std::vector<float> lc((size_t)(nrows * 16 + 256 + 128) * 2, 0.0f);
-  for (int n1 = 0; n1 < nrows; ++n1)
-    for (int q = 0; q < 16; ++q) {
-      lc[2 * (n1 * 16 + q)] = wh[32 * n1 + 2 * q];
-      lc[2 * (n1 * 16 + q) + 1] = wh[32 * n1 + 2 * q + 1];
-    }
-  float* twp = lc.data() + 2 * nrows * 16;
-  float* tws = twp + 512;
-  for (int k1 = 0; k1 < 16; ++k1)
-    for (int q = 0; q < 16; ++q) {
-      const double a = -2.0 * M_PI * (double)(q * k1) / 256.0;
-      twp[2 * (k1 * 16 + q)] = (float)std::cos(a);
-      twp[2 * (k1 * 16 + q) + 1] = (float)std::sin(a);
-    }
-  for (int k2 = 0; k2 < 8; ++k2)
-    for (int q = 0; q < 16; ++q) {  // w = -i * W_512^k = (sin(a), -cos(a)) with a = -2 pi k / 512
-      const double a = -2.0 * M_PI * (double)(q + 16 * k2) / 512.0;
-      tws[2 * (k2 * 16 + q)] = (float)std::sin(a);
-      tws[2 * (k2 * 16 + q) + 1] = (float)(-std::cos(a));
-    }
-  hipfeat_status st;
-  if ((st = upload(&p->d_lds_consts, lc.data(), lc.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_mel_a, mel_a.data(), mel_a.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_work, work, 4)) != HIPFEAT_OK) return st;
-  // 16 tiles (256 frames) per workgroup: the constant-table load and the first, un-overlapped span
-  // fetch are paid once per workgroup (measured on MI355X: 4 -> 1.98 M, 8 -> 2.11 M, 16 -> 2.16 M cuts/s)
-  p->tiles_per_block = 16;
-  const int const_floats = (int)lc.size();
-  p->const_floats = const_floats;
+  const TileTables t = build_tile_tables(in, nrows, {16, kPRowStride, kMaxGroups0, kMaxGroups1, kTileFrames, kBWaveRegion, false});
+  if (!t.fits || t.lds > 160 * 1024) return HIPFEAT_OK;  // -> generic kernel
   const void* fn;
-  size_t lds;
-  {
-    // weights as 16-byte vectors: [wave][step / 4][lane][step % 4]
-    std::vector<float> mel_a4(mel_a.size());
-    for (int w = 0; w < 4; ++w)
-      for (int st = 0; st < kMelARegs; ++st)
-        for (int lane = 0; lane < 64; ++lane)
-          mel_a4[(((size_t)w * kBMelVec + st / 4) * 64 + lane) * 4 + (st & 3)] = mel_a[((size_t)w * kMelARegs + st) * 64 + lane];
-    if ((st = upload(&p->d_mel_a4, mel_a4.data(), mel_a4.size())) != HIPFEAT_OK) return st;
-    p->xs_floats = (15 * shift + 32 * nrows + 255) & ~255;  // whole 1 KiB LDS-DMA chunks
-    size_t lds_floats = (size_t)p->xs_floats + const_floats + 4 * kBWaveRegion;
-    if (mfcc) {
-      p->dct_groups = (M + 7) / 8;
-      p->lm_stride = ntiles <= 2 ? 36 : (ntiles <= 4 ? 68 : 132);  // 4 mod 32: conflict-free 8-byte reads of the log-mel tile; 36 keeps MFCC-13 at 4 workgroups/CU
-      std::vector<float> da = build_dct_operands(c, h_dct, h_lifter, p->dct_groups);
-      p->dct_floats = (int)da.size();
-      if ((st = upload(&p->d_dct_consts, da.data(), da.size())) != HIPFEAT_OK) return st;
-      lds_floats += (size_t)kTileFrames * p->lm_stride + da.size();
-    }
-    lds = lds_floats * sizeof(float);
-    if (mfcc)
-      fn = nrows == 10 ? fft512b_entry<10, 1>() : (nrows == 13 ? fft512b_entry<13, 1>() : fft512b_entry<16, 1>());
-    else if (spec)
-      fn = nrows == 10 ? fft512b_entry<10, 2>() : (nrows == 13 ? fft512b_entry<13, 2>() : fft512b_entry<16, 2>());
-    else
-      fn = nrows == 10 ? fft512b_entry<10, 0>() : (nrows == 13 ? fft512b_entry<13, 0>() : fft512b_entry<16, 0>());
-  }
-  if (lds > 160 * 1024) return HIPFEAT_OK;
-  if ((st = claim(p, Route::Fft512b, fn, 256, lds)) != HIPFEAT_OK) return st;
-  char nm[96];
-  // same spelling as the device symbol rocprofv3 reports (modulo the space after the comma)
-  snprintf(nm, sizeof(nm), "fft512b_kernel<%d,%d> %s lds=%zuB blocks/CU=%d", nrows, mfcc ? 1 : (spec ? 2 : 0),
-           mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"), lds, p->blocks_per_cu);
-  p->kernel_name = nm;
-  p->fpb = kTileFrames * p->tiles_per_block;
-  return HIPFEAT_OK;
+  if (mfcc)
+    fn = nrows == 10 ? entry<fft512b_kernel<10, 1>>() : (nrows == 13 ? entry<fft512b_kernel<13, 1>>() : entry<fft512b_kernel<16, 1>>());
+  else if (spec)
+    fn = nrows == 10 ? entry<fft512b_kernel<10, 2>>() : (nrows == 13 ? entry<fft512b_kernel<13, 2>>() : entry<fft512b_kernel<16, 2>>());
+  else
+    fn = nrows == 10 ? entry<fft512b_kernel<10, 0>>() : (nrows == 13 ? entry<fft512b_kernel<13, 0>>() : entry<fft512b_kernel<16, 0>>());
+  return claim_tile(p, Route::Fft512b, fn, t, kTileFrames, "fft512b_kernel");
 }
 
 // --------------------------------------------------------------------------------------
 // fft1024 wave-autonomous fbank kernel (kernel_fft1024c.hpp): 22.05 / 24 / 32 kHz Kaldi log-mel
 // --------------------------------------------------------------------------------------
-template <int NROWS, int S0 = 0, int S1 = 0, int S2 = 0, bool PLAIN = false>
-static const void* fft1024c_entry() {
-  return reinterpret_cast<const void*>(&fft1024c_kernel<NROWS, S0, S1, S2, PLAIN>);
-}
-// instances with the mel schedule as compile-time constants (kernel_fft1024c.hpp): 1 = <20, 24,16,8> (24 kHz), 2 = <26, 24,16,8> (32 kHz),
-// 3 = <20, 24,24,8> (22.05 kHz), 4 = <32, 16,16,8, PLAIN> (the librosa default: n_fft 1024 @ 22.05 kHz, 80 slaney filters, no DC removal,
-// no pre-emphasis); 0 = generic
-static int fft1024c_fixed_id(int nrows, int nsets, const int* steps, bool plain) {
-  if (nsets != 3 || route_env("HIPFEAT_NO_FIXED_SCHEDULE")) return 0;
-  if (nrows == 32) return plain && steps[0] == 16 && steps[1] == 16 && steps[2] == 8 ? 4 : 0;
-  if (nrows == 20 && steps[0] == 24 && steps[1] == 16 && steps[2] == 8) return 1;
-  if (nrows == 26 && steps[0] == 24 && steps[1] == 16 && steps[2] == 8) return 2;
-  if (nrows == 20 && steps[0] == 24 && steps[1] == 24 && steps[2] == 8) return 3;
-  return 0;
-}
-
-static hipfeat_status setup_fft1024c(hipfeat_plan* p, const float* h_window, const float* h_mel) {
+static hipfeat_status setup_fft1024c(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
-  const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
+  const int N = in.N, shift = in.shift;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;  // centred frames, |X| or |X|^2, log10 (librosa_fbank.py:66-137)
   if ((c.kind != HIPFEAT_FBANK && !librosa) || c.fft_length != 1024 || (shift & 1) || N < 32 * 17 || c.use_energy ||
       (c.use_fft_mag && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_AUTONOMOUS"))
     return HIPFEAT_OK;
   const int need = (N + 31) / 32;
   const int nrows = need <= 20 ? 20 : (need <= 26 ? 26 : 32);
-  Mel4Schedule sch;
-  if (!build_mel4_schedule(h_mel, M, p->K, kWPRowStride, kWMaxSets, kWMaxSteps, sch)) return HIPFEAT_OK;
-  std::vector<float> img((size_t)(nrows * 16 + 512 + kWSplitSteps * 16) * 2, 0.0f);
-  for (int n1 = 0; n1 < nrows; ++n1)
-    for (int q = 0; q < 16; ++q)
-      for (int e = 0; e < 2; ++e) {
-        const int i = 32 * n1 + 2 * q + e;
-        img[2 * (n1 * 16 + q) + e] = i < N ? 0.5f * h_window[i] : 0.0f;
-      }
-  float* twp = img.data() + 2 * nrows * 16;
-  float* tws = twp + 1024;
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int q = 0; q < 16; ++q) {
-      const double a = -2.0 * M_PI * (double)(q * k1) / 512.0;
-      twp[2 * (k1 * 16 + q)] = (float)std::cos(a);
-      twp[2 * (k1 * 16 + q) + 1] = (float)std::sin(a);
-    }
-  for (int st = 0; st < kWSplitSteps; ++st)
-    for (int q = 0; q < 16; ++q) {  // bin of the step's first operand: lanes >= 1: q + 32 s; lane 0: 32 s (s <= 8), 16 + 32 (s - 9) (s <= 15), 240
-      int k;
-      if (q != 0) k = st < 16 ? q + 32 * st : 0;
-      else k = st <= 8 ? 32 * st : (st <= 15 ? 16 + 32 * (st - 9) : 240);
-      const double a = -2.0 * M_PI * (double)k / 1024.0;  // w = -i * W_1024^k = (sin(a), -cos(a))
-      tws[2 * (st * 16 + q)] = (float)std::sin(a);
-      tws[2 * (st * 16 + q) + 1] = (float)(-std::cos(a));
-    }
-  // the kernel runs two accumulation chains per set over chunks of 4 steps: every set's steps are padded to a multiple of 8
-  // (zero weights; the power-row reads stay inside the wave's region)
-  p->c_wtab_off = (int)img.size();
-  {
-    int step0 = 0;
-    for (int s2 = 0; s2 < sch.nsets; ++s2) {
-      const int padded = (sch.steps[s2] + 7) & ~7;
-      const size_t at = img.size();
-      img.resize(at + (size_t)padded * 64, 0.0f);
-      std::memcpy(img.data() + at, sch.wtab.data() + (size_t)sch.step0[s2] * 64, (size_t)sch.steps[s2] * 64 * sizeof(float));
-      sch.steps[s2] = padded;
-      sch.step0[s2] = step0;
-      step0 += padded;
-    }
-  }
-  p->c_ltab_off = (int)img.size();
-  img.insert(img.end(), sch.ltab.begin(), sch.ltab.end());
-  while (img.size() % 64) img.push_back(0.0f);
-  p->c_shared_floats = (int)img.size();
-  p->c_xs_floats = (3 * shift + 32 * nrows + 3) & ~3;
-  // fixed-schedule instances: 12 waves per workgroup, the span buffer aliases the exchange / power region (kernel_fft1024c.hpp)
-  int fixed = fft1024c_fixed_id(nrows, sch.nsets, sch.steps, !c.remove_dc_offset && c.preemph_coeff == 0.0f);
-  if (fixed && p->c_xs_floats > kWRegion) fixed = 0;
-  if (fixed >= 1 && fixed <= 3 && (librosa || c.use_fft_mag)) fixed = 0;  // the Kaldi instances have |X|^2, ln and Kaldi's edges compiled in
-  // ... and the default frame geometry at 24 / 32 / 22.05 kHz with 80 filters (kernel_fft1024c.hpp)
-  if (fixed >= 1 && fixed <= 3 && !(M == 80 && !c.snip_edges && ((fixed == 1 && N == 600 && shift == 240) || (fixed == 2 && N == 800 && shift == 320) || (fixed == 3 && N == 551 && shift == 220))))
-    fixed = 0;
-  const int waves = fixed ? kWWavesFixed : kWWaves;
-  const size_t lds = ((size_t)p->c_shared_floats + (size_t)waves * (fixed ? kWRegion : p->c_xs_floats + kWRegion)) * sizeof(float);
-  if (lds > 160 * 1024 || (p->c_xs_floats >> 8) > 10) return HIPFEAT_OK;
-  const void* fn = fixed == 1 ? fft1024c_entry<20, 24, 16, 8>()
-                   : fixed == 2 ? fft1024c_entry<26, 24, 16, 8>()
-                   : fixed == 3 ? fft1024c_entry<20, 24, 24, 8>()
-                   : fixed == 4 ? fft1024c_entry<32, 16, 16, 8, true>()
-                   : nrows == 20 ? fft1024c_entry<20>() : (nrows == 26 ? fft1024c_entry<26>() : fft1024c_entry<32>());
-  hipfeat_status st;
-  if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
-  p->w_nsets = sch.nsets;
-  int total_steps = 0;
-  for (int s2 = 0; s2 < kWMaxSets; ++s2) {
-    p->w_steps[s2] = s2 < sch.nsets ? sch.steps[s2] : 0;
-    p->w_step0[s2] = s2 < sch.nsets ? sch.step0[s2] : 0;
-    total_steps += p->w_steps[s2];
-  }
-  p->c_rounds = 8;
-  p->fpb = waves * p->c_rounds * 4;
-  p->fpb_unit = waves * 4;
-  p->c_rounds_max = 32;
-  if ((st = claim(p, Route::Fft1024c, fn, 64 * waves, lds)) != HIPFEAT_OK) return st;
-  char nm[160];
-  snprintf(nm, sizeof(nm), "fft1024c_kernel<%d> fbank%s waves=%d lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, fixed ? " fixed-schedule" : "", waves, lds, p->blocks_per_cu, sch.nsets, total_steps);
-  p->kernel_name = nm;
-  return HIPFEAT_OK;
+  // The instance that has this configuration's mel schedule and frame geometry as compile-time constants (kernel_fft1024c.hpp), if the
+  // schedule turns out to be that one: 1 = <20, 24,16,8> (24 kHz), 2 = <26, 24,16,8> (32 kHz), 3 = <20, 24,24,8> (22.05 kHz): the Kaldi default
+  // with 80 filters (|X|^2, ln and Kaldi's edges compiled in); 4 = <32, 16,16,8, PLAIN> (the librosa default: n_fft 1024 @ 22.05 kHz, 80
+  // slaney filters, no DC removal, no pre-emphasis); 0 = none
+  static const int kFixedSteps[5][3] = {{0, 0, 0}, {24, 16, 8}, {24, 16, 8}, {24, 24, 8}, {16, 16, 8}};
+  int want = 0;
+  if (route_env("HIPFEAT_NO_FIXED_SCHEDULE")) want = 0;  // (routing switch: the generic instances)
+  else if (nrows == 32) want = !c.remove_dc_offset && c.preemph_coeff == 0.0f ? 4 : 0;
+  else if (!librosa && !c.use_fft_mag && in.M == 80 && !c.snip_edges)
+    want = N == 600 && shift == 240 ? 1 : (N == 800 && shift == 320 ? 2 : (N == 551 && shift == 220 ? 3 : 0));
+  // fixed-schedule instances: 12 waves per workgroup, the span buffer aliases the exchange / power region
+  const WaveAutoTables t = build_fft1024c_tables(in, nrows, {kWPRowStride, kWMaxSets, kWMaxSteps, kWWaves, kWRegion}, kWSplitSteps, kWWavesFixed, want ? kFixedSteps[want] : nullptr);
+  if (!t.fits || t.lds > 160 * 1024 || (t.xs_floats >> 8) > 10) return HIPFEAT_OK;
+  const int fixed = t.fixed ? want : 0;
+  const void* fn = fixed == 1 ? entry<fft1024c_kernel<20, 24, 16, 8>>()
+                   : fixed == 2 ? entry<fft1024c_kernel<26, 24, 16, 8>>()
+                   : fixed == 3 ? entry<fft1024c_kernel<20, 24, 24, 8>>()
+                   : fixed == 4 ? entry<fft1024c_kernel<32, 16, 16, 8, true>>()
+                   : nrows == 20 ? entry<fft1024c_kernel<20>>() : (nrows == 26 ? entry<fft1024c_kernel<26>>() : entry<fft1024c_kernel<32>>());
+  return claim_wave_auto(p, Route::Fft1024c, fn, t, 4, 8, 32, strf("fft1024c_kernel<%d> fbank%s waves=%d", nrows, fixed ? " fixed-schedule" : "", t.waves));
 }
 
 // --------------------------------------------------------------------------------------
-// fft256 fast path (kernel_fft256.hpp): 8 kHz 25/10 ms frames, or <= 16 ms frames at 16 kHz
+// fft256 (8 kHz 25/10 ms frames, or <= 16 ms frames at 16 kHz): the wave-autonomous log-mel kernel (kernel_fft256c.hpp), else the
+// 32-frame-tile kernel "b" (kernel_fft256.hpp)
 // --------------------------------------------------------------------------------------
-template <int NROWS, int OUT>
-static const void* fft256_entry() {
-  return reinterpret_cast<const void*>(&fft256_kernel<NROWS, OUT>);
-}
-
-// fft256 wave-autonomous log-mel kernel (kernel_fft256c.hpp); shares d_c_shared / c_* with the other wave-autonomous kernels
-template <int NROWS, int NFULL>
-static const void* fft256c_entry() {
-  return reinterpret_cast<const void*>(&fft256c_kernel<NROWS, NFULL>);
-}
-
-static hipfeat_status setup_fft256c(hipfeat_plan* p, const float* h_window, const float* h_mel, int nrows) {
-  const hipfeat_config& c = p->cfg;
-  const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
-  Mel4Schedule sch;
-  if (!build_mel4_schedule(h_mel, M, p->K, kDPRowStride, kDSets, kDSteps, sch)) return HIPFEAT_OK;
-  // LDS image: window/2 pairs per (row n1, lane q) | W_128^(q k1) per (row k1, lane q) | split-step twiddles -i W_256^(q + 8 j)
-  std::vector<float> img((size_t)(nrows * 8 + 128 + 64) * 2, 0.0f);
-  for (int n1 = 0; n1 < nrows; ++n1)
-    for (int q = 0; q < 8; ++q)
-      for (int e = 0; e < 2; ++e) {
-        const int i = 16 * n1 + 2 * q + e;
-        img[2 * (n1 * 8 + q) + e] = i < N ? 0.5f * h_window[i] : 0.0f;
-      }
-  float* twp = img.data() + 2 * nrows * 8;
-  float* tws = twp + 256;
-  for (int k1 = 0; k1 < 16; ++k1)
-    for (int q = 0; q < 8; ++q) {
-      const double a = -2.0 * M_PI * (double)(q * k1) / 128.0;
-      twp[2 * (k1 * 8 + q)] = (float)std::cos(a);
-      twp[2 * (k1 * 8 + q) + 1] = (float)std::sin(a);
-    }
-  for (int j = 0; j < 8; ++j)
-    for (int q = 0; q < 8; ++q) {  // w = -i * W_256^k = (sin(a), -cos(a)) with a = -2 pi k / 256
-      const double a = -2.0 * M_PI * (double)(q + 8 * j) / 256.0;
-      tws[2 * (j * 8 + q)] = (float)std::sin(a);
-      tws[2 * (j * 8 + q) + 1] = (float)(-std::cos(a));
-    }
-  // the kernel runs kDSets sets of kDSteps steps unconditionally: pad the tables (weights 0, no output column)
-  p->c_wtab_off = (int)img.size();
-  img.resize(img.size() + (size_t)kDSets * kDSteps * 64, 0.0f);
-  for (int s2 = 0; s2 < sch.nsets; ++s2)
-    std::memcpy(img.data() + p->c_wtab_off + (size_t)s2 * kDSteps * 64, sch.wtab.data() + (size_t)sch.step0[s2] * 64, (size_t)sch.steps[s2] * 64 * sizeof(float));
-  p->c_ltab_off = (int)img.size();
-  img.resize(img.size() + (size_t)kDSets * 256, 0.0f);
-  {
-    const int none = kMel4NoColumn;
-    for (int s2 = 0; s2 < kDSets; ++s2)
-      for (int lane = 0; lane < 64; ++lane) {
-        float* lt = img.data() + p->c_ltab_off + ((size_t)s2 * 64 + lane) * 4;
-        if (s2 < sch.nsets) std::memcpy(lt, sch.ltab.data() + ((size_t)s2 * 64 + lane) * 4, 4 * sizeof(float));
-        else std::memcpy(lt + 1, &none, 4);
-      }
-  }
-  while (img.size() % 64) img.push_back(0.0f);
-  p->c_shared_floats = (int)img.size();
-  p->c_xs_floats = (7 * shift + 16 * nrows + 3) & ~3;
-  const size_t lds = ((size_t)p->c_shared_floats + (size_t)kDWaves * (p->c_xs_floats + kDRegion)) * sizeof(float);
-  if (lds > 80 * 1024 || (p->c_xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
+static hipfeat_status setup_fft256c(hipfeat_plan* p, const PlanInputs& in, int nrows) {
+  const WaveAutoTables t = build_fft256c_tables(in, nrows, {kDPRowStride, kDSets, kDSteps, kDWaves, kDRegion});
+  if (!t.fits || t.lds > 80 * 1024 || (t.xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
   // 25 ms at 8 kHz (N = 200: 12 full rows of 16 samples + a partial one) gets the instance without length masks on the full rows
-  const void* fn = nrows == 13 ? (N >= 192 ? fft256c_entry<13, 12>() : fft256c_entry<13, 0>()) : fft256c_entry<16, 0>();
-  hipfeat_status st;
-  if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
-  p->c_rounds = 4;  // 8 waves x 4 rounds x 8 frames = 256 frames per workgroup
-  p->fpb = kDWaves * p->c_rounds * 8;
-  p->fpb_unit = kDWaves * 8;
-  p->c_rounds_max = 16;
-  if ((st = claim(p, Route::Fft256c, fn, 64 * kDWaves, lds)) != HIPFEAT_OK) return st;
-  int total_steps = 0;
-  for (int s2 = 0; s2 < sch.nsets; ++s2) total_steps += sch.steps[s2];
-  char nm[128];
-  snprintf(nm, sizeof(nm), "fft256c_kernel<%d> fbank lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, lds, p->blocks_per_cu, sch.nsets, total_steps);
-  p->kernel_name = nm;
-  return HIPFEAT_OK;
+  const void* fn = nrows == 13 ? (in.N >= 192 ? entry<fft256c_kernel<13, 12>>() : entry<fft256c_kernel<13, 0>>()) : entry<fft256c_kernel<16, 0>>();
+  // 8 waves x 4 rounds x 8 frames = 256 frames per workgroup
+  return claim_wave_auto(p, Route::Fft256c, fn, t, 8, 4, 16, strf("fft256c_kernel<%d> fbank", nrows));
 }
 
-static hipfeat_status setup_fft256(hipfeat_plan* p, const float* h_window, const float* h_mel, const float* h_dct, const float* h_lifter) {
+static hipfeat_status setup_fft256(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
-  const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
   const bool mfcc = c.kind == HIPFEAT_MFCC;
   const bool spec = c.kind == HIPFEAT_SPECTROGRAM || c.kind == HIPFEAT_LOG_SPECTROGRAM;
-  if (c.kind > HIPFEAT_MFCC || c.fft_length != 256 || (shift & 1) || N < 16 || c.use_energy || (!spec && c.use_fft_mag) ||
+  if (c.kind > HIPFEAT_MFCC || c.fft_length != 256 || (in.shift & 1) || in.N < 16 || c.use_energy || (!spec && c.use_fft_mag) ||
       route_env("HIPFEAT_FORCE_GENERIC"))
     return HIPFEAT_OK;
-  if (mfcc && (M > 8 * kMaxDctGroups || c.num_ceps > 64)) return HIPFEAT_OK;
-  const int need = (N + 15) / 16;
-  const int nrows = need <= 13 ? 13 : 16;
-  const int ntiles = spec ? 0 : (M + 15) / 16;
-  if (ntiles > 8) return HIPFEAT_OK;
+  if (mfcc && (in.M > 8 * kMaxDctGroups || in.C > 64)) return HIPFEAT_OK;
+  const int nrows = (in.N + 15) / 16 <= 13 ? 13 : 16;
+  if ((in.M + 15) / 16 > 8) return HIPFEAT_OK;  // at most 8 mel tiles of 16 filters
   if (!mfcc && !spec) {  // log-mel filterbank: the wave-autonomous kernel, unless the schedule or the LDS budget says no
     const char* var = route_env("HIPFEAT_FFT256_VARIANT");
     if (!(var && var[0] == 'b') && !route_env("HIPFEAT_NO_WAVE_AUTONOMOUS")) {  // HIPFEAT_FFT256_VARIANT=b: the 32-frame-tile kernel (tests compare the two)
-      hipfeat_status stc = setup_fft256c(p, h_window, h_mel, nrows);
+      hipfeat_status stc = setup_fft256c(p, in, nrows);
       if (stc != HIPFEAT_OK || p->route == Route::Fft256c) return stc;
     }
   }
-  WaveWork work[4];
-  std::vector<float> mel_a((size_t)4 * kMelARegs * 64, 0.0f);
-  std::memset(work, 0, sizeof(work));
-  if (!spec && !build_mel_schedule(h_mel, M, p->K, k256PRowStride, ntiles, work, mel_a)) return HIPFEAT_OK;
-  // LDS constants: window/2 pairs per (row n1, lane q) | W_128^(q k1) per (row k1, lane q) | split-step twiddles
-  // w = -i W_256^(q + 8 j) per (row j < 8, lane q) | (-w.y, w.x)
-  std::vector<float> wh(256, 0.0f);
-  for (int i = 0; i < N; ++i) wh[i] = 0.5f * h_window[i];
-  const int const_floats = (nrows * 8 + 128 + 64 + 64) * 2;
-  std::vector<float> lc((size_t)const_floats, 0.0f);
-  for (int n1 = 0; n1 < nrows; ++n1)
-    for (int q = 0; q < 8; ++q) {
-      lc[2 * (n1 * 8 + q)] = wh[16 * n1 + 2 * q];
-      lc[2 * (n1 * 8 + q) + 1] = wh[16 * n1 + 2 * q + 1];
-    }
-  float* twp = lc.data() + 2 * nrows * 8;
-  float* tws = twp + 256;
-  float* twsp = tws + 128;
-  for (int k1 = 0; k1 < 16; ++k1)
-    for (int q = 0; q < 8; ++q) {
-      const double a = -2.0 * M_PI * (double)(q * k1) / 128.0;
-      twp[2 * (k1 * 8 + q)] = (float)std::cos(a);
-      twp[2 * (k1 * 8 + q) + 1] = (float)std::sin(a);
-    }
-  for (int j = 0; j < 8; ++j)
-    for (int q = 0; q < 8; ++q) {  // w = -i * W_256^k = (sin(a), -cos(a)) with a = -2 pi k / 256
-      const double a = -2.0 * M_PI * (double)(q + 8 * j) / 256.0;
-      const float wx = (float)std::sin(a), wy = (float)(-std::cos(a));
-      tws[2 * (j * 8 + q)] = wx;
-      tws[2 * (j * 8 + q) + 1] = wy;
-      twsp[2 * (j * 8 + q)] = -wy;
-      twsp[2 * (j * 8 + q) + 1] = wx;
-    }
-  hipfeat_status st;
-  if ((st = upload(&p->d_lds_consts, lc.data(), lc.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_work, work, 4)) != HIPFEAT_OK) return st;
-  std::vector<float> mel_a4(mel_a.size());  // weights as 16-byte vectors: [wave][step / 4][lane][step % 4]
-  for (int w = 0; w < 4; ++w)
-    for (int s4 = 0; s4 < kMelARegs; ++s4)
-      for (int lane = 0; lane < 64; ++lane)
-        mel_a4[(((size_t)w * kBMelVec + s4 / 4) * 64 + lane) * 4 + (s4 & 3)] = mel_a[((size_t)w * kMelARegs + s4) * 64 + lane];
-  if ((st = upload(&p->d_mel_a4, mel_a4.data(), mel_a4.size())) != HIPFEAT_OK) return st;
-  p->tiles_per_block = 16;  // 512 frames per workgroup (measured: 8 -> 3.84 M, 16 -> 3.99 M, 32 -> 3.93 M cuts/s at 8 kHz fbank-80)
-  p->const_floats = const_floats;
-  p->xs_floats = ((k256TileFrames - 1) * shift + 16 * nrows + 255) & ~255;  // whole 1 KiB LDS-DMA chunks
-  size_t lds_floats = (size_t)p->xs_floats + const_floats + 4 * k256WaveRegion;
-  if (mfcc) {
-    p->dct_groups = (M + 7) / 8;
-    p->lm_stride = ntiles <= 2 ? 36 : (ntiles <= 4 ? 68 : 132);
-    std::vector<float> da = build_dct_operands(c, h_dct, h_lifter, p->dct_groups);
-    p->dct_floats = (int)da.size();
-    if ((st = upload(&p->d_dct_consts, da.data(), da.size())) != HIPFEAT_OK) return st;
-    lds_floats += (size_t)k256TileFrames * p->lm_stride + da.size();
-  }
-  const size_t lds = lds_floats * sizeof(float);
-  if (lds > 64 * 1024) return HIPFEAT_OK;  // keep at least two workgroups per CU; otherwise the generic kernel
+  const TileTables t = build_tile_tables(in, nrows, {8, k256PRowStride, kMaxGroups0, kMaxGroups1, k256TileFrames, k256WaveRegion, true});
+  if (!t.fits || t.lds > 64 * 1024) return HIPFEAT_OK;  // keep at least two workgroups per CU; otherwise the generic kernel
   const void* fn;
-  if (mfcc) fn = nrows == 13 ? fft256_entry<13, 1>() : fft256_entry<16, 1>();
-  else if (spec) fn = nrows == 13 ? fft256_entry<13, 2>() : fft256_entry<16, 2>();
-  else fn = nrows == 13 ? fft256_entry<13, 0>() : fft256_entry<16, 0>();
-  if ((st = claim(p, Route::Fft256b, fn, 256, lds)) != HIPFEAT_OK) return st;
-  char nm[112];
-  snprintf(nm, sizeof(nm), "fft256_kernel<%d,%d> %s lds=%zuB blocks/CU=%d", nrows, mfcc ? 1 : (spec ? 2 : 0), mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"),
-           lds, p->blocks_per_cu);
-  p->kernel_name = nm;
-  p->fpb = k256TileFrames * p->tiles_per_block;
-  return HIPFEAT_OK;
+  if (mfcc) fn = nrows == 13 ? entry<fft256_kernel<13, 1>>() : entry<fft256_kernel<16, 1>>();
+  else if (spec) fn = nrows == 13 ? entry<fft256_kernel<13, 2>>() : entry<fft256_kernel<16, 2>>();
+  else fn = nrows == 13 ? entry<fft256_kernel<13, 0>>() : entry<fft256_kernel<16, 0>>();
+  return claim_tile(p, Route::Fft256b, fn, t, k256TileFrames, "fft256_kernel");
 }
 
 // --------------------------------------------------------------------------------------
-// wave-per-frame kernel (kernel_wave.hpp): power-of-two fft 256 .. 2048 without a specialised kernel
+// wave-per-frame kernel (kernel_wave.hpp): power-of-two fft 512 .. 2048 without a specialised kernel
 // --------------------------------------------------------------------------------------
-template <int N1>
-static const void* wave_entry() {
-  return reinterpret_cast<const void*>(&wave_kernel<N1>);
-}
-
-static hipfeat_status setup_wave(hipfeat_plan* p, const float* h_mel) {
+static hipfeat_status setup_wave(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
   if (!p->pow2 || (c.kind > HIPFEAT_MFCC && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_KERNEL"))
@@ -912,156 +544,58 @@ static hipfeat_status setup_wave(hipfeat_plan* p, const float* h_mel) {
   const int H = p->H;
   // H = 128 (fft 256) stays on the radix-2 kernel: measured 0.92 M vs 0.72 M cuts/s there; H = 256: 0.46 vs 0.48 M
   if (!(H == 256 || H == 512 || H == 1024) || c.num_filters > 128) return HIPFEAT_OK;
-  const bool need_mel = c.kind == HIPFEAT_FBANK || c.kind == HIPFEAT_MFCC || librosa;
-  const int M = need_mel ? c.num_filters : 0;
+  const WaveTables t = build_wave_tables(in, H);
   hipfeat_status st;
-  if (need_mel) {
-    int maxband = 1;
-    std::vector<int2> rng(M);
-    for (int j = 0; j < M; ++j) {
-      int lo = p->K, hi = 0;
-      for (int k = 0; k < p->K; ++k)
-        if (h_mel[(size_t)k * M + j] != 0.0f) {
-          lo = std::min(lo, k);
-          hi = std::max(hi, k + 1);
-        }
-      if (hi == 0) lo = 0;
-      rng[j] = make_int2(lo, hi);
-      maxband = std::max(maxband, hi - lo);
-    }
-    // blob = [M] int4 {lo rounded down to a multiple of 4, offset of the filter's weights, number of float4 groups, 0} followed
-    // by the weights themselves, each filter zero-padded to whole float4 groups
-    std::vector<int32_t> desc((size_t)4 * M, 0);
-    std::vector<float> wts;
-    for (int j = 0; j < M; ++j) {
-      const int lo4 = rng[j].x & ~3;
-      const int groups = rng[j].y > rng[j].x ? (rng[j].y - lo4 + 3) / 4 : 0;
-      desc[(size_t)4 * j] = lo4;
-      desc[(size_t)4 * j + 1] = (int32_t)wts.size();
-      desc[(size_t)4 * j + 2] = groups;
-      for (int t = 0; t < 4 * groups; ++t) {
-        const int k = lo4 + t;
-        wts.push_back(k < p->K ? h_mel[(size_t)k * M + j] : 0.0f);
-      }
-    }
-    std::vector<float> blob((size_t)4 * M + wts.size());
-    std::memcpy(blob.data(), desc.data(), desc.size() * sizeof(int32_t));
-    std::memcpy(blob.data() + 4 * M, wts.data(), wts.size() * sizeof(float));
-    if ((st = upload(&p->d_mel_t, blob.data(), blob.size())) != HIPFEAT_OK) return st;
-    p->mel_maxband = maxband;
-    p->wave_blob_floats = (int)blob.size();
-  }
-  p->wave_dct_in_lds = c.kind == HIPFEAT_MFCC && (size_t)M * c.num_ceps <= 2560;
-  auto up4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-  // twiddles W_2H^k + 4 padded wave buffers + window + twiddles W_H^m + filterbank blob (+ DCT matrix)
-  const size_t lds = ((size_t)2 * H + 4 * ((size_t)144 * (H / 64) + 8) + up4((size_t)c.frame_length) + (size_t)2 * H + up4((size_t)p->wave_blob_floats) +
-                      (p->wave_dct_in_lds ? (size_t)M * c.num_ceps : 0)) * sizeof(float);
-  const void* fn = H == 256 ? wave_entry<4>() : (H == 512 ? wave_entry<8>() : wave_entry<16>());
-  if ((st = claim(p, Route::Wave, fn, 256, lds)) != HIPFEAT_OK) return st;
-  char nm[96];
-  snprintf(nm, sizeof(nm), "wave_kernel<%d> fft=%d lds=%zuB blocks/CU=%d", H / 64, c.fft_length, lds, p->blocks_per_cu);
-  p->kernel_name = nm;
+  if (in.M > 0 && (st = upload(&p->d_mel_t, t.blob.data(), t.blob.size())) != HIPFEAT_OK) return st;
+  p->wave_blob_floats = (int)t.blob.size();
+  p->wave_dct_in_lds = t.dct_in_lds;
+  const void* fn = H == 256 ? entry<wave_kernel<4>>() : (H == 512 ? entry<wave_kernel<8>>() : entry<wave_kernel<16>>());
+  if ((st = claim(p, Route::Wave, fn, 256, t.lds)) != HIPFEAT_OK) return st;
+  p->kernel_name = strf("wave_kernel<%d> fft=%d lds=%zuB blocks/CU=%d", H / 64, c.fft_length, t.lds, p->blocks_per_cu);
   p->fpb = 32;  // 4 waves x 8 frames (the tables copied to LDS per workgroup are ~12 KB)
   return HIPFEAT_OK;
 }
 
 // --------------------------------------------------------------------------------------
-// whisper FFT fast path: 400 = 16 x 25 mixed-radix FFT on the vector ALUs + banded mel GEMM (kernel_whisper2.hpp)
+// whisper: 400 = 16 x 25 mixed-radix FFT on the vector ALUs.  whisper3 (kernel_whisper3.hpp: wave-autonomous, the normalisation fused)
+// when the filterbank schedule and the LDS budget allow, else whisper2 (kernel_whisper2.hpp: banded mel GEMM, normalisation in a
+// separate pass); whisper3 reads whisper2's DFT-25 table
 // --------------------------------------------------------------------------------------
-static hipfeat_status setup_whisper3(hipfeat_plan* p, const float* h_window, const float* h_mel);
+static hipfeat_status setup_whisper3(hipfeat_plan* p, const PlanInputs& in) {
+  const WaveAutoTables t = build_whisper3_tables(in, {kW3PRowStride, kW3MaxSets, kW3Steps, kW3Waves, kW3Region}, kW3Span, kW3Tail);
+  if (!t.fits || t.lds > 80 * 1024) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
+  const void* fn = t.w_nsets == 2 ? entry<whisper3_kernel<2>>() : entry<whisper3_kernel<3>>();
+  // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
+  return claim_wave_auto(p, Route::Whisper3, fn, t, 4, 8, 16, strf("whisper3_kernel<%d> fft400=16x25 fused-norm", t.w_nsets));
+}
 
-// whisper2, or whisper3 (which reads whisper2's DFT-25 table) when the filterbank schedule and the LDS budget allow
-static hipfeat_status setup_whisper(hipfeat_plan* p, const float* h_window, const float* h_mel) {
+static hipfeat_status setup_whisper(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
   if (c.kind != HIPFEAT_WHISPER || c.frame_length != kW2N || c.frame_shift != kW2Shift || c.num_filters > 16 * kW2MaxMelTiles ||
       route_env("HIPFEAT_FORCE_GENERIC"))
     return HIPFEAT_OK;
-  const int M = c.num_filters, nmt = (M + 15) / 16;
-  std::vector<float> cs(288);
-  for (int j = 1; j <= 12; ++j)
-    for (int k = 1; k <= 12; ++k) {
-      const double th = 2.0 * M_PI * (double)((j * k) % 25) / 25.0;
-      cs[(size_t)(j - 1) * 24 + 2 * (k - 1)] = (float)std::cos(th);
-      cs[(size_t)(j - 1) * 24 + 2 * (k - 1) + 1] = (float)-std::sin(th);
-    }
-  std::vector<float> tw((size_t)13 * 16 * 2);
-  for (int k2 = 0; k2 < 13; ++k2)
-    for (int l = 0; l < 16; ++l) {
-      const double th = 2.0 * M_PI * (double)((l * k2) % 400) / 400.0;
-      tw[((size_t)k2 * 16 + l) * 2] = (float)std::cos(th);
-      tw[((size_t)k2 * 16 + l) * 2 + 1] = (float)-std::sin(th);
-    }
-  std::vector<float> mel;
-  for (int mt = 0; mt < nmt; ++mt) {
-    int lo = 201, hi = 0;
-    for (int bin = 0; bin <= 200; ++bin)
-      for (int i = 0; i < 16; ++i) {
-        const int m = 16 * mt + i;
-        if (m < M && h_mel[(size_t)bin * M + m] != 0.0f) {
-          lo = std::min(lo, bin);
-          hi = std::max(hi, bin + 1);
-        }
-      }
-    if (hi == 0) lo = 0;
-    const int k0 = lo & ~3, chunks = hi > lo ? (hi - k0 + 15) / 16 : 0;  // chunks of 4 k-steps (16 bins); zero weights pad the band
-    p->wh2_k0[mt] = k0;
-    p->wh2_steps[mt] = chunks;
-    p->wh2_off[mt] = (int32_t)(mel.size() / 256);
-    for (int ch = 0; ch < chunks; ++ch)
-      for (int l = 0; l < 64; ++l)
-        for (int r = 0; r < 4; ++r) {
-          const int bin = k0 + 16 * ch + 4 * r + (l >> 4), m = 16 * mt + (l & 15);
-          mel.push_back((bin <= 200 && m < M) ? h_mel[(size_t)bin * M + m] : 0.0f);
-        }
-  }
-  if (mel.empty()) mel.assign(256, 0.0f);
-  // deal the mel tiles to the four waves: longest first, always to the least loaded wave (at most two tiles each)
-  int load[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
-  for (int wv = 0; wv < 4; ++wv) p->wh2_wave_tiles[wv][0] = p->wh2_wave_tiles[wv][1] = -1;
-  std::vector<int> order(nmt);
-  for (int i = 0; i < nmt; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return p->wh2_steps[a] > p->wh2_steps[b]; });
-  for (int mt : order) {
-    int best = -1;
-    for (int wv = 0; wv < 4; ++wv)
-      if (cnt[wv] < 2 && (best < 0 || load[wv] < load[best])) best = wv;
-    p->wh2_wave_tiles[best][cnt[best]++] = mt;
-    load[best] += p->wh2_steps[mt];
-  }
+  const Whisper2Tables t = build_whisper2_tables(in);
   hipfeat_status st;
-  if ((st = upload(&p->d_wh2_cs, cs.data(), cs.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_wh2_tw, tw.data(), tw.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_wh2_mel, mel.data(), mel.size())) != HIPFEAT_OK) return st;
-  std::vector<int32_t> sched(32, 0);
-  for (int wv = 0; wv < 4; ++wv)
-    for (int sl = 0; sl < 2; ++sl) {
-      const int mt = p->wh2_wave_tiles[wv][sl];
-      int32_t* e = &sched[(size_t)(wv * 2 + sl) * 4];
-      e[0] = mt;
-      if (mt >= 0) e[1] = p->wh2_k0[mt], e[2] = p->wh2_steps[mt], e[3] = p->wh2_off[mt];
-    }
-  if ((st = upload(&p->d_wh2_sched, sched.data(), sched.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(&p->d_wh2_cs, t.cs.data(), t.cs.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(&p->d_wh2_tw, t.tw.data(), t.tw.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(&p->d_wh2_mel, t.mel.data(), t.mel.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(&p->d_wh2_sched, t.sched.data(), t.sched.size())) != HIPFEAT_OK) return st;
   const char* v = route_env("HIPFEAT_WHISPER_VARIANT");
   if (!(v && v[0] == '2')) {  // HIPFEAT_WHISPER_VARIANT=2: whisper2 (tests compare the two)
-    if ((st = setup_whisper3(p, h_window, h_mel)) != HIPFEAT_OK || p->route == Route::Whisper3) return st;
+    if ((st = setup_whisper3(p, in)) != HIPFEAT_OK || p->route == Route::Whisper3) return st;
   }
   p->fpb = 16 * kW2TilesPerBlock;
-  if ((st = claim(p, Route::Whisper2, reinterpret_cast<const void*>(&whisper2_kernel), 256, 0)) != HIPFEAT_OK) return st;
-  char buf[160];
-  snprintf(buf, sizeof(buf), "whisper_kernel2 fft400=16x25 mel_chunks=%d+%d+%d+%d blocks/CU=%d", load[0], load[1], load[2], load[3], p->blocks_per_cu);
-  p->kernel_name = buf;
+  if ((st = claim(p, Route::Whisper2, entry<whisper2_kernel>(), 256, 0)) != HIPFEAT_OK) return st;
+  p->kernel_name = strf("whisper_kernel2 fft400=16x25 mel_chunks=%d+%d+%d+%d blocks/CU=%d", t.load[0], t.load[1], t.load[2], t.load[3], p->blocks_per_cu);
   return HIPFEAT_OK;
 }
 
+// --------------------------------------------------------------------------------------
 // fft2048 wave-autonomous fbank kernel (kernel_fft2048c.hpp): 44.1 / 48 kHz Kaldi filterbanks, librosa-style log-mel with n_fft 2048
-template <int NROWS, bool ODD, int S0 = 0, int S1 = 0, int S2 = 0, bool W12 = false>
-static const void* fft2048c_entry() {
-  return reinterpret_cast<const void*>(&fft2048c_kernel<NROWS, ODD, S0, S1, S2, W12>);
-}
-
-static hipfeat_status setup_fft2048c(hipfeat_plan* p, const float* h_window, const float* h_mel) {
+// --------------------------------------------------------------------------------------
+static hipfeat_status setup_fft2048c(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
-  const int N = c.frame_length, shift = c.frame_shift, M = c.num_filters;
+  const int N = in.N, shift = in.shift;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;  // centred frames, |X| or |X|^2, log10 (librosa_fbank.py:66-137)
   if ((c.kind != HIPFEAT_FBANK && !librosa) || c.fft_length != 2048 || N <= 1024 || c.use_energy ||
       (c.use_fft_mag && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_AUTONOMOUS"))
@@ -1069,161 +603,25 @@ static hipfeat_status setup_fft2048c(hipfeat_plan* p, const float* h_window, con
   const bool odd = (shift & 1) != 0;
   const int need = (N + 63) / 64;
   const int nrows = odd ? (need <= 18 ? 18 : 32) : (need <= 19 ? 19 : 32);
-  Mel4Schedule sch;
-  if (!build_mel4_schedule(h_mel, M, p->K, kXPRowStride, kXMaxSets, kXMaxSteps, sch)) return HIPFEAT_OK;
-  // LDS image: window/2 as (even, odd) sample pairs per (row n1, lane q)
-  std::vector<float> img((size_t)nrows * 32 * 2, 0.0f);
-  for (int n1 = 0; n1 < nrows; ++n1)
-    for (int q = 0; q < 32; ++q)
-      for (int e = 0; e < 2; ++e) {
-        const int i = 64 * n1 + 2 * q + e;
-        img[2 * (n1 * 32 + q) + e] = i < N ? 0.5f * h_window[i] : 0.0f;
-      }
-  // split twiddles -i W_2048^k per (step, lane); k = bin of the step's first operand: lanes 1..16: l + 64 s, lanes 17..31:
-  // (64 - l) + 64 s; lane 0: 64 s (s <= 8), 32 + 64 (s - 9) (s <= 15), 480 (s = 16)
-  p->x_tws_off = (int)img.size();
-  img.resize(img.size() + (size_t)kXSplitSteps * 32 * 2, 0.0f);
-  for (int st = 0; st < kXSplitSteps; ++st)
-    for (int q = 0; q < 32; ++q) {
-      int k;
-      if (q != 0) k = st < 16 ? (q <= 16 ? q : 64 - q) + 64 * st : 0;
-      else k = st <= 8 ? 64 * st : (st <= 15 ? 32 + 64 * (st - 9) : 480);
-      const double a = -2.0 * M_PI * (double)k / 2048.0;  // w = -i * W_2048^k = (sin(a), -cos(a))
-      img[(size_t)p->x_tws_off + 2 * (st * 32 + q)] = (float)std::sin(a);
-      img[(size_t)p->x_tws_off + 2 * (st * 32 + q) + 1] = (float)(-std::cos(a));
-    }
-  // butterfly twiddles of pass 2: row 0 = ones (even outputs), row 1 = W_32^n (odd outputs)
-  p->x_tw32_off = (int)img.size();
-  img.resize(img.size() + 2 * 16 * 2, 0.0f);
-  for (int n = 0; n < 16; ++n) {
-    const double a = -2.0 * M_PI * (double)n / 32.0;
-    img[(size_t)p->x_tw32_off + 2 * n] = 1.0f;
-    img[(size_t)p->x_tw32_off + 2 * (16 + n)] = (float)std::cos(a);
-    img[(size_t)p->x_tw32_off + 2 * (16 + n) + 1] = (float)std::sin(a);
-  }
-  p->c_wtab_off = (int)img.size();
-  img.insert(img.end(), sch.wtab.begin(), sch.wtab.end());
-  // a wave carries TWO frames: rows 2 and 3 of every 4 x 4 block read the power rows of frames 0 and 1 again (their results are dropped)
-  for (size_t i = 0; i < sch.ltab.size(); i += 4) {
-    const int lane = (int)((i / 4) % 64);
-    if ((lane & 3) >= 2) {
-      int v;
-      std::memcpy(&v, &sch.ltab[i], 4);
-      v -= 2 * kXPRowStride;
-      std::memcpy(&sch.ltab[i], &v, 4);
-    }
-  }
-  p->c_ltab_off = (int)img.size();
-  img.insert(img.end(), sch.ltab.begin(), sch.ltab.end());
-  while (img.size() % 64) img.push_back(0.0f);
-  p->c_shared_floats = (int)img.size();
-  p->c_xs_floats = (shift + 64 * nrows + 3) & ~3;
-  if ((p->c_xs_floats >> 8) > 10) return HIPFEAT_OK;
-  // instance with the mel schedule as compile-time constants (kernel_fft2048c.hpp): the 80-filter Kaldi default at 44.1 / 48 kHz.  The 44.1 kHz one
-  // runs 12 waves per workgroup (3 waves/SIMD) without a span prefetch, the span buffer aliasing the exchange / power region (at 48 kHz that
-  // layout measured 3 % slower than 8 waves with the prefetch)
-  const bool fixed = sch.nsets == 3 && sch.steps[0] == 52 && sch.steps[1] == 28 && sch.steps[2] == 16 && sch.step0[1] == 52 && sch.step0[2] == 80 &&
-                     (odd ? nrows == 18 : nrows == 19) && !librosa && !c.use_fft_mag && M == 80 &&
-                     (odd ? (N == 1102 && shift == 441) : (N == 1200 && shift == 480)) && !c.snip_edges &&  // the geometry the instances have compiled in (kernel_fft2048c.hpp)
-                     !route_env("HIPFEAT_NO_FIXED_SCHEDULE");
+  // instance with the mel schedule and the frame geometry as compile-time constants (kernel_fft2048c.hpp): the 80-filter Kaldi default at
+  // 44.1 / 48 kHz, if the schedule turns out to be 52 + 28 + 16 steps.  The 44.1 kHz one runs 12 waves per workgroup (3 waves/SIMD) without a
+  // span prefetch, the span buffer aliasing the exchange / power region (at 48 kHz that layout measured 3 % slower than 8 waves with the prefetch)
+  static const int kFixedSteps[3] = {52, 28, 16};
+  const bool want = (odd ? nrows == 18 : nrows == 19) && !librosa && !c.use_fft_mag && in.M == 80 &&
+                    (odd ? (N == 1102 && shift == 441) : (N == 1200 && shift == 480)) && !c.snip_edges && !route_env("HIPFEAT_NO_FIXED_SCHEDULE");
   // (HIPFEAT_FFT2048_W12 = 1 / 0: routing switch, forces / forbids the 12-wave layout for either default -- same-call A/Bs)
   const char* w12_env = route_env("HIPFEAT_FFT2048_W12");
-  const bool w12_want = w12_env ? w12_env[0] == '1' : odd;
-  const bool w12 = fixed && w12_want && p->c_xs_floats <= kXRegion && ((size_t)p->c_shared_floats + (size_t)kXWavesFixed * kXRegion) * sizeof(float) <= 160 * 1024;
-  int waves = w12 ? kXWavesFixed : kXMaxWaves;
-  auto lds_of = [&](int wv) { return ((size_t)p->c_shared_floats + (size_t)wv * (w12 ? kXRegion : p->c_xs_floats + kXRegion)) * sizeof(float); };
-  while (waves > 0 && lds_of(waves) > 160 * 1024) --waves;
-  if (waves < 4) return HIPFEAT_OK;
-  if (fixed && waves != (w12 ? kXWavesFixed : kXMaxWaves)) return HIPFEAT_OK;  // (cannot happen for the default geometry: its LDS image fits)
-  const size_t lds = lds_of(waves);
-  const void* fn = fixed ? (odd ? (w12 ? fft2048c_entry<18, true, 52, 28, 16, true>() : fft2048c_entry<18, true, 52, 28, 16>())
-                                : (w12 ? fft2048c_entry<19, false, 52, 28, 16, true>() : fft2048c_entry<19, false, 52, 28, 16>()))
-                   : odd ? (nrows == 18 ? fft2048c_entry<18, true>() : fft2048c_entry<32, true>())
-                         : (nrows == 19 ? fft2048c_entry<19, false>() : fft2048c_entry<32, false>());
-  std::vector<float> twp((size_t)32 * 32 * 2);
-  for (int k1 = 0; k1 < 32; ++k1)
-    for (int q = 0; q < 32; ++q) {
-      const double a = -2.0 * M_PI * (double)(q * k1) / 1024.0;
-      twp[2 * ((size_t)k1 * 32 + q)] = (float)std::cos(a);
-      twp[2 * ((size_t)k1 * 32 + q) + 1] = (float)std::sin(a);
-    }
-  hipfeat_status st;
-  if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_x_twp, twp.data(), twp.size())) != HIPFEAT_OK) return st;
-  p->w_nsets = sch.nsets;
-  int total_steps = 0;
-  for (int s2 = 0; s2 < kXMaxSets; ++s2) {
-    p->w_steps[s2] = s2 < sch.nsets ? sch.steps[s2] : 0;
-    p->w_step0[s2] = s2 < sch.nsets ? sch.step0[s2] : 0;
-    total_steps += p->w_steps[s2];
-  }
-  p->x_waves = waves;
-  p->c_rounds = 8;
-  p->fpb = waves * p->c_rounds * 2;
-  p->fpb_unit = waves * 2;
-  p->c_rounds_max = 64;
-  if ((st = claim(p, Route::Fft2048c, fn, 64 * waves, lds)) != HIPFEAT_OK) return st;
-  char nm[160];
-  snprintf(nm, sizeof(nm), "fft2048c_kernel<%d,%d> fbank%s waves=%d lds=%zuB blocks/CU=%d mel4=%dx%d", nrows, (int)odd, fixed ? " fixed-schedule" : "", waves, lds, p->blocks_per_cu, sch.nsets, total_steps);
-  p->kernel_name = nm;
-  return HIPFEAT_OK;
-}
-
-// whisper, wave-autonomous with the normalisation fused (kernel_whisper3.hpp): shares the DFT-25 coefficient table of setup_whisper
-template <int NSETS>
-static const void* whisper3_entry() {
-  return reinterpret_cast<const void*>(&whisper3_kernel<NSETS>);
-}
-
-static hipfeat_status setup_whisper3(hipfeat_plan* p, const float* h_window, const float* h_mel) {
-  const hipfeat_config& c = p->cfg;
-  const int M = c.num_filters;
-  Mel4Schedule sch;
-  if (!build_mel4_schedule(h_mel, M, 201, kW3PRowStride, kW3MaxSets, kW3Steps, sch)) return HIPFEAT_OK;
-  const int nsets = sch.nsets <= 2 ? 2 : 3;
-  std::vector<float> img((size_t)kW3N + 13 * 16 * 2, 0.0f);
-  for (int i = 0; i < kW3N; ++i) img[(size_t)i] = h_window[i];
-  for (int k2 = 0; k2 < 13; ++k2)
-    for (int l = 0; l < 16; ++l) {
-      const double th = 2.0 * M_PI * (double)((l * k2) % 400) / 400.0;
-      img[(size_t)kW3N + ((size_t)k2 * 16 + l) * 2] = (float)std::cos(th);
-      img[(size_t)kW3N + ((size_t)k2 * 16 + l) * 2 + 1] = (float)-std::sin(th);
-    }
-  // the kernel runs `nsets` sets of kW3Steps steps unconditionally: pad the tables (weights 0, no output column)
-  p->c_wtab_off = (int)img.size();
-  img.resize(img.size() + (size_t)nsets * kW3Steps * 64, 0.0f);
-  for (int s2 = 0; s2 < sch.nsets; ++s2)
-    std::memcpy(img.data() + p->c_wtab_off + (size_t)s2 * kW3Steps * 64, sch.wtab.data() + (size_t)sch.step0[s2] * 64, (size_t)sch.steps[s2] * 64 * sizeof(float));
-  p->c_ltab_off = (int)img.size();
-  img.resize(img.size() + (size_t)nsets * 256, 0.0f);
-  {
-    const int none = kMel4NoColumn;
-    for (int s2 = 0; s2 < nsets; ++s2)
-      for (int lane = 0; lane < 64; ++lane) {
-        float* lt = img.data() + p->c_ltab_off + ((size_t)s2 * 64 + lane) * 4;
-        if (s2 < sch.nsets) std::memcpy(lt, sch.ltab.data() + ((size_t)s2 * 64 + lane) * 4, 4 * sizeof(float));
-        else std::memcpy(lt + 1, &none, 4);
-      }
-  }
-  while (img.size() % 64) img.push_back(0.0f);
-  const size_t lds = (img.size() + (size_t)kW3Waves * (kW3Span + kW3Region) + kW3Tail) * sizeof(float);
-  if (lds > 80 * 1024) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
-  const void* fn = nsets == 2 ? whisper3_entry<2>() : whisper3_entry<3>();
-  hipfeat_status st;
-  if ((st = upload(&p->d_c_shared, img.data(), img.size())) != HIPFEAT_OK) return st;
-  p->c_shared_floats = (int)img.size();
-  p->w_nsets = nsets;
-  p->c_rounds = 8;  // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
-  p->fpb = kW3Waves * p->c_rounds * 4;
-  p->fpb_unit = kW3Waves * 4;
-  p->c_rounds_max = 16;
-  if ((st = claim(p, Route::Whisper3, fn, 64 * kW3Waves, lds)) != HIPFEAT_OK) return st;
-  int total_steps = 0;
-  for (int s2 = 0; s2 < sch.nsets; ++s2) total_steps += sch.steps[s2];
-  char nm[160];
-  snprintf(nm, sizeof(nm), "whisper3_kernel<%d> fft400=16x25 fused-norm lds=%zuB blocks/CU=%d mel4=%dx%d", nsets, lds, p->blocks_per_cu, sch.nsets, total_steps);
-  p->kernel_name = nm;
-  return HIPFEAT_OK;
+  const WaveAutoTables t = build_fft2048c_tables(in, nrows, {kXPRowStride, kXMaxSets, kXMaxSteps, kXMaxWaves, kXRegion}, kXSplitSteps, kXWavesFixed,
+                                                 want ? kFixedSteps : nullptr, w12_env ? w12_env[0] == '1' : odd, 160 * 1024);
+  if (!t.fits || (t.xs_floats >> 8) > 10 || t.waves < 4) return HIPFEAT_OK;
+  if (t.fixed && t.waves != (t.w12 ? kXWavesFixed : kXMaxWaves)) return HIPFEAT_OK;  // (cannot happen for the default geometry: its LDS image fits)
+  const void* fn = t.fixed ? (odd ? (t.w12 ? entry<fft2048c_kernel<18, true, 52, 28, 16, true>>() : entry<fft2048c_kernel<18, true, 52, 28, 16>>())
+                                  : (t.w12 ? entry<fft2048c_kernel<19, false, 52, 28, 16, true>>() : entry<fft2048c_kernel<19, false, 52, 28, 16>>()))
+                   : odd ? (nrows == 18 ? entry<fft2048c_kernel<18, true>>() : entry<fft2048c_kernel<32, true>>())
+                         : (nrows == 19 ? entry<fft2048c_kernel<19, false>>() : entry<fft2048c_kernel<32, false>>());
+  p->x_waves = t.waves;
+  return claim_wave_auto(p, Route::Fft2048c, fn, t, 2, 8, 64,
+                         strf("fft2048c_kernel<%d,%d> fbank%s waves=%d", nrows, (int)odd, t.fixed ? " fixed-schedule" : "", t.waves));
 }
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* cfg, const float* h_window,
@@ -1305,17 +703,10 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
   if ((st = upload(&p->d_window, h_window, (size_t)N)) != HIPFEAT_OK) return bail(st);
   if (need_mel) {
     if ((st = upload(&p->d_mel, h_mel, (size_t)p->K * M)) != HIPFEAT_OK) return bail(st);
-    // band of each filter: [first non-zero bin, last non-zero bin + 1)
-    std::vector<int2> rng(M);
+    std::vector<int2> rng(M);  // band of each filter: [first non-zero bin, last non-zero bin + 1)
     for (int j = 0; j < M; ++j) {
-      int lo = p->K, hi = 0;
-      for (int k = 0; k < p->K; ++k)
-        if (h_mel[(size_t)k * M + j] != 0.0f) {
-          lo = std::min(lo, k);
-          hi = std::max(hi, k + 1);
-        }
-      if (hi == 0) lo = 0;
-      rng[j] = make_int2(lo, hi);
+      const MelBand b = mel_band(h_mel, M, p->K, j, j + 1);
+      rng[j] = make_int2(b.lo, b.hi);
     }
     if ((st = upload(&p->d_mel_range, rng.data(), rng.size())) != HIPFEAT_OK) return bail(st);
   }
@@ -1361,12 +752,12 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     st = s;
     return st == HIPFEAT_OK && p->route == Route::Generic;
   };
-  if (unclaimed(setup_fft512(p, h_window, h_mel, h_dct, h_lifter)) &&
-      unclaimed(setup_whisper(p, h_window, h_mel)) &&
-      unclaimed(setup_fft256(p, h_window, h_mel, h_dct, h_lifter)) &&
-      unclaimed(setup_fft1024c(p, h_window, h_mel)) &&
-      unclaimed(setup_fft2048c(p, h_window, h_mel)))
-    st = setup_wave(p, h_mel);
+  PlanInputs in;
+  in.N = N, in.shift = shift, in.K = p->K, in.M = M, in.C = C;
+  in.window = h_window, in.mel = h_mel, in.dct = h_dct, in.lifter = cfg->apply_lifter ? h_lifter : nullptr;
+  if (unclaimed(setup_fft512(p, in)) && unclaimed(setup_whisper(p, in)) && unclaimed(setup_fft256(p, in)) && unclaimed(setup_fft1024c(p, in)) &&
+      unclaimed(setup_fft2048c(p, in)))
+    st = setup_wave(p, in);
   if (st != HIPFEAT_OK) return bail(st);
 
   *out = p;

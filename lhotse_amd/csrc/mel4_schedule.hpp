@@ -31,19 +31,28 @@ struct Mel4Schedule {
   std::vector<float> ltab;      // [nsets][64 lanes][4]: power-row offset (int bits), output column (int bits, kMel4NoColumn = none), m4, m8
 };
 
+// Band of the filter columns [j0, j1) of h_mel ([K][M] row-major, bin x filter): [first non-zero bin, last non-zero bin + 1), {0, 0} when
+// they are all zero.
+struct MelBand { int lo, hi; };
+inline MelBand mel_band(const float* h_mel, int M, int K, int j0, int j1) {
+  MelBand b{K, 0};
+  for (int k = 0; k < K; ++k)
+    for (int j = j0; j < std::min(M, j1); ++j)
+      if (h_mel[(size_t)k * M + j] != 0.0f) {
+        b.lo = std::min(b.lo, k);
+        b.hi = std::max(b.hi, k + 1);
+      }
+  if (b.hi == 0) b.lo = 0;
+  return b;
+}
+
 // h_mel: [K][M] row-major filterbank (bin x filter).  prow_stride: floats between the power rows of consecutive frames.
 inline bool build_mel4_schedule(const float* h_mel, int M, int K, int prow_stride, int max_sets, int max_steps, Mel4Schedule& out) {
   const int ng = (M + 3) / 4;
   std::vector<int> lo(ng, 0), alen(ng, 4);  // 4-aligned band start, length from there to the last non-zero bin
   for (int g = 0; g < ng; ++g) {
-    int l = K, h = 0;
-    for (int k = 0; k < K; ++k)
-      for (int j = 4 * g; j < std::min(M, 4 * g + 4); ++j)
-        if (h_mel[(size_t)k * M + j] != 0.0f) {
-          l = std::min(l, k);
-          h = std::max(h, k + 1);
-        }
-    if (h > 0) lo[g] = l & ~3, alen[g] = h - (l & ~3);
+    const MelBand b = mel_band(h_mel, M, K, 4 * g, 4 * g + 4);
+    if (b.hi > 0) lo[g] = b.lo & ~3, alen[g] = b.hi - (b.lo & ~3);
   }
   // pstride: bins between the starts of consecutive pieces of a split group; shift: bins (multiple of 4) the first piece starts below lo
   struct Place { int set, row, pos, cnt, pstride, shift; };
