@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HIPFEAT_ABI_VERSION 6
+#define HIPFEAT_ABI_VERSION 7
 
 #if defined(HIPFEAT_BUILD)
 #define HIPFEAT_API __attribute__((visibility("default")))
@@ -337,6 +337,41 @@ HIPFEAT_API hipfeat_status hipfeat_mix_plan(hipfeat_mixer* mixer, int64_t num_cu
                                             const int32_t* h_ref_track, const int64_t* h_max_samples, int64_t tail_start,
                                             int64_t* h_out_offsets, int64_t* h_out_num_samples, int64_t* h_info);
 HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
+
+/* ---- ABI v7: cuts reverberated with a recorded room impulse response on the device ------------------------------ */
+/*
+ * ReverbWithImpulseResponse.__call__ (lhotse/augmentation/rir.py:78-153) scales the loaded RIR by 2^-15, convolves every output channel's
+ * input with it through three float32 FFTs of size next_fast_len(N + L - 1) (convolve1d, lhotse/augmentation/utils.py:49-75), keeps the N
+ * samples from argmax(rir) on ("shift output", rir.py:145-146) and, with normalize_output, scales them to the input's power (rir.py:148-151).
+ * Here the inputs AND the scaled RIRs of a whole mini-batch lie in ONE device arena and two stream-ordered launches -- a direct-form float32
+ * convolution that also writes float64 partial sums of squares, then the gain -- write the reverberated channels behind them; no value
+ * visits the host in between, so hipfeat_mix_run / hipfeat_extract* over the returned offsets can follow on the same stream.
+ * One (input channel, RIR channel) pair is an item:
+ *   hs = rir * 2^-15 (exact; done by the caller);  shift = first index of max(hs) (np.argmax: of the values, not the magnitudes);
+ *   y[n] = sum_k hs[k] * x[n + shift - k], 0 <= n < N, over the k with 0 <= n + shift - k < N; float32: runs of 16 consecutive taps
+ *   [16 s, 16 s + 16) accumulated with fmaf in ascending order, the 16 runs of the 256 taps [256 c, 256 c + 256) added in ascending order into
+ *   a partial sum, the partial sums added in ascending order of c (kernel_reverb.hpp has the order in full);
+ *   with the normalise flag: Sx = sum x^2, Sy = sum y^2 in float64; if Sy > 0: y *= (float)sqrt((Sx / N) / (Sy / N)), else y stays.
+ *   Results are bit-identical from run to run and do not depend on the other items of the batch.
+ *
+ * hipfeat_reverb_create / _destroy: the object that owns the workspace (partial sums, staged tables) on `device`; calls are serialised
+ * inside, up to 16 plans may be outstanding, destroy waits for the work it enqueued.
+ * hipfeat_reverb_plan (host only): per item h_src_offset / h_src_len = arena offset and samples N of the input channel, h_rir_offset /
+ * h_rir_len = arena offset and taps L of the SCALED impulse response, h_shift, h_normalize (may be NULL: none).  Every source and every
+ * impulse response must end at or before tail_start: the outputs are written from there on, each on a 16-byte boundary, N samples at
+ * h_out_offsets[i]; sources are never modified.  h_info[4] = {ticket, floats the arena must hold, convolution work items, partial sums}.
+ * A bad table (a negative offset, N < 1 or L < 1, a shift outside [0, L), a source or impulse response that reaches past tail_start, a
+ * 17th plan while 16 are planned and not yet run) returns HIPFEAT_ERR_INVALID and plans nothing.
+ * hipfeat_reverb_run enqueues the two launches of a planned reverberation on `stream` (a ticket runs once); an unknown ticket or an arena
+ * smaller than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.
+ */
+typedef struct hipfeat_reverb hipfeat_reverb;
+HIPFEAT_API hipfeat_status hipfeat_reverb_create(int32_t device, hipfeat_reverb** reverb);
+HIPFEAT_API hipfeat_status hipfeat_reverb_destroy(hipfeat_reverb* reverb);
+HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* reverb, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                               const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
+                                               const int32_t* h_normalize, int64_t tail_start, int64_t* h_out_offsets, int64_t* h_info);
+HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* reverb, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

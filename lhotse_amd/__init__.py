@@ -15,6 +15,7 @@ from .extractors import (  # noqa: F401
     HipSpectrogramConfig,
 )
 
+from .augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_arena, reverb_tail_floats  # noqa: F401,E402
 from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
 
 from .kaldifeat import (  # noqa: F401,E402
@@ -68,6 +69,10 @@ __all__ = [
     "HipMixer",
     "mix_in_arena",
     "mixed_tail_floats",
+    "HipReverb",
+    "HipReverbWithImpulseResponse",
+    "reverb_in_arena",
+    "reverb_tail_floats",
     "HipResample",
     "HipResampleTensor",
     "get_or_create_resampler",

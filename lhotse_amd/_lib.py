@@ -20,7 +20,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # name -> (return C type, [argument C types]) ; mirrors include/hipfeat.h one to one.
 _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
@@ -83,6 +83,14 @@ _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
          "const int64_t*", "int64_t", "int64_t*", "int64_t*", "int64_t*"],
     ),
     "hipfeat_mix_run": ("int", ["hipfeat_mixer*", "int64_t", "float*", "int64_t", "void*"]),
+    "hipfeat_reverb_create": ("int", ["int32_t", "hipfeat_reverb**"]),
+    "hipfeat_reverb_destroy": ("int", ["hipfeat_reverb*"]),
+    "hipfeat_reverb_plan": (
+        "int",
+        ["hipfeat_reverb*", "int64_t", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "const int32_t*",
+         "int64_t", "int64_t*", "int64_t*"],
+    ),
+    "hipfeat_reverb_run": ("int", ["hipfeat_reverb*", "int64_t", "float*", "int64_t", "void*"]),
     "hipfeat_archive_open": ("int", ["const char* const*", "int32_t", "int32_t", "hipfeat_archive**"]),
     "hipfeat_archive_append": ("int", ["hipfeat_archive*", "const void*", "int64_t", "const int64_t*", "int32_t", "int32_t", "int32_t*", "int64_t*"]),
     "hipfeat_archive_size": ("int64_t", ["const hipfeat_archive*", "int32_t"]),

@@ -519,3 +519,204 @@ def mix_in_arena(arena: torch.Tensor, track_first, src_offsets, src_lens, dst_of
         raise ValueError(f"arena too small: {arena.numel()} floats, the mixed cuts need {int(info[1])} (see mixed_tail_floats)")
     mixer.run(ticket, arena)
     return offs, lens
+
+
+# ---- reverberation with a recorded room impulse response in the same arena ------------------------------------------------------
+RIR_SCALING_FACTOR = 0.5 ** 15  # (lhotse/augmentation/rir.py:34)
+
+
+def reverb_tail_floats(src_lens) -> int:
+    """Floats the reverberated channels of a mini-batch need behind ``tail_start`` (every output starts on a 16-byte boundary)."""
+    return int(((_lib.i64(src_lens) + 3) & ~3).sum()) + 3
+
+
+def scaled_rir(rir: np.ndarray) -> Tuple[np.ndarray, int]:
+    """One channel of a loaded RIR -> (``hs = rir * 2^-15`` in float32 -- exact --, ``shift`` = first index of ``max(hs)``)
+    (lhotse/augmentation/rir.py:139, 145)."""
+    hs = np.ascontiguousarray(rir, dtype=np.float32).reshape(-1) * np.float32(RIR_SCALING_FACTOR)
+    return hs, int(np.argmax(hs))
+
+
+class HipReverb:
+    """The device half of ``ReverbWithImpulseResponse.__call__`` (lhotse/augmentation/rir.py:78-153) for a packed mini-batch:
+    ``hipfeat_reverb`` (include/hipfeat.h) owns the workspace of the two launches -- direct-form float32 convolution with float64 sums
+    of squares, then the power-preserving gain.  One object per device (``get_or_create_reverb``); it may be shared by threads."""
+
+    def __init__(self, device: Union[str, torch.device, None] = None):
+        self.lib = _lib.load()
+        self.handle = 0
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.HipFeatError(1, f"HipReverb runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        out = np.zeros(1, dtype=np.uint64)
+        self.lib.check("hipfeat_reverb_create", int(self.device.index), _lib.addr(out))
+        self.handle = int(out[0])
+        self._lock = threading.Lock()
+
+    def plan(self, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0):
+        """Host only -> (ticket, out_offsets, info = [ticket, arena floats needed, convolution work items, partial sums])."""
+        so, sl, ro, rl, sh = (_lib.i64(a) for a in (src_offsets, src_lens, rir_offsets, rir_lens, shifts))
+        n = len(so)
+        if np.ndim(normalize) == 0:
+            normalize = np.full(n, 0 if normalize is None else int(bool(normalize)))
+        nm = np.ascontiguousarray(normalize, dtype=np.int32)
+        if not (len(sl) == len(ro) == len(rl) == len(sh) == len(nm) == n):
+            raise ValueError("reverb tables: one entry per item in every table")
+        out_offs, info = np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_reverb_plan", self.handle, n, _lib.addr(so), _lib.addr(sl), _lib.addr(ro), _lib.addr(rl), _lib.addr(sh), _lib.addr(nm),
+                           int(tail_start), _lib.addr(out_offs), _lib.addr(info))
+        return int(info[0]), out_offs, info
+
+    def run(self, ticket: int, arena: torch.Tensor, stream: Optional[int] = None) -> None:
+        assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
+        with torch.cuda.device(self.device):
+            self.lib.check("hipfeat_reverb_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
+
+    def close(self):
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_reverb_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_reverbs: Dict[int, HipReverb] = {}
+
+
+def get_or_create_reverb(device: Union[str, torch.device, None] = None) -> HipReverb:
+    dev = torch.device("cuda" if device is None else device)
+    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    with _cache_lock:
+        r = _reverbs.get(int(index))
+        if r is None:
+            r = _reverbs[int(index)] = HipReverb(torch.device(dev.type, index))
+        return r
+
+
+def reverb_in_arena(arena: torch.Tensor, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0,
+                    reverb: Optional[HipReverb] = None) -> np.ndarray:
+    """Reverberate the channels of a device-resident packed mini-batch (``ReverbWithImpulseResponse.__call__``,
+    lhotse/augmentation/rir.py:78-153); the counterpart of ``perturb_speed_in_arena`` / ``mix_in_arena``, run between the two when a
+    track carries ``[Speed, Reverb]``.
+
+    ``arena`` is ONE float32 device buffer: all sources and all SCALED impulse responses (``scaled_rir``) in front of ``tail_start``, free
+    space behind it (``reverb_tail_floats``).  Item ``i`` convolves the ``src_lens[i]`` samples at ``src_offsets[i]`` with the
+    ``rir_lens[i]`` taps at ``rir_offsets[i]``, keeps the samples from ``shifts[i]`` on and, where ``normalize[i]``, scales them to the
+    input's power.  Returns the arena offsets of the outputs (``src_lens[i]`` samples each).  Two launches on the current stream, no
+    device -> host copy, bit-identical from run to run."""
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    if reverb is None:
+        reverb = get_or_create_reverb(arena.device)
+    ticket, offs, info = reverb.plan(src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start)
+    if int(info[1]) > arena.numel():
+        raise ValueError(f"arena too small: {arena.numel()} floats, the reverberated cuts need {int(info[1])} (see reverb_tail_floats)")
+    reverb.run(ticket, arena)
+    return offs
+
+
+def reverb_items(num_input_channels: int, num_rir_channels: int, rir_given: bool = True) -> List[Tuple[int, int]]:
+    """The reference's four mono / multi-channel cases (lhotse/augmentation/rir.py:90-135) as ``(input channel, rir channel)`` per
+    output channel; its assertions as ``ValueError``s with the same conditions."""
+    mono = num_input_channels == 1
+    if mono:
+        if not (rir_given or num_rir_channels == 1):
+            raise ValueError("For mono input, either provide an RIR explicitly or set rir_channels to [0].")
+    elif not (num_rir_channels == 1 or num_rir_channels == num_input_channels):
+        raise ValueError("For multi-channel input, we only support mono RIR or RIR with the same number of channels as the input.")
+    d_out = num_rir_channels if mono else num_input_channels
+    return [(0 if mono else d, 0 if num_rir_channels == 1 else d) for d in range(d_out)]
+
+
+def load_rir(rir, rir_channels: Sequence[int], early_only: bool) -> np.ndarray:
+    """The RIR samples ``(D_rir, L)`` the way the reference loads them (lhotse/augmentation/rir.py:116-122): its own calls are the
+    contract.  ``rir``: a lhotse ``Recording`` / ``Cut``, or -- without lhotse -- an array ``(C, L)`` of already loaded samples."""
+    if isinstance(rir, np.ndarray):
+        a = np.atleast_2d(rir)[list(rir_channels)]
+        return np.ascontiguousarray(a, dtype=np.float32)
+    cut = rir.to_cut() if type(rir).__name__ == "Recording" else rir
+    cut = cut.with_channels(list(rir_channels))
+    if early_only:
+        cut = cut.truncate(duration=0.05)
+    return np.ascontiguousarray(np.atleast_2d(cut.load_audio()), dtype=np.float32)
+
+
+@dataclass
+class HipReverbWithImpulseResponse(AudioTransform):
+    """Reverberation with a recorded room impulse response on the GPU; drop-in for ``lhotse.augmentation.ReverbWithImpulseResponse``
+    (rir.py:12-166) with ``rir`` given: same fields, same dict round trip, output of the input's length ("shift output").  The random
+    generator (``rir=None``) is not served: ``HipFeatError`` (UNSUPPORTED)."""
+
+    rir: Optional[Union[dict, object]] = None
+    normalize_output: bool = True
+    early_only: bool = False
+    rir_channels: List[int] = None  # type: ignore[assignment]
+    rir_generator: Optional[Union[dict, object]] = None
+    device: str = "cuda"
+
+    def __post_init__(self):
+        if self.rir_channels is None:
+            self.rir_channels = [0]
+        self.rir_channels = [int(c) for c in self.rir_channels]
+        if isinstance(self.rir, dict):
+            if not HAVE_LHOTSE:
+                raise ImportError("a serialised RIR manifest needs lhotse to be read back (lhotse.serialization.deserialize_item)")
+            from lhotse.serialization import deserialize_item  # type: ignore
+
+            rir = self.rir.copy()  # (rir.py:40-45: deserialisation is destructive)
+            if "recording" in self.rir:
+                rir["recording"] = rir["recording"].copy()
+            self.rir = deserialize_item(rir)
+        if self.rir is None:
+            raise _lib.HipFeatError(_lib.ERR_UNSUPPORTED, "HipReverbWithImpulseResponse needs a recorded impulse response (rir=...): the random "
+                                    "RIR generator of the reference (rir=None, rir_generator) is not served on the device")
+        if not isinstance(self.rir, np.ndarray) and not all(c < self.rir.num_channels for c in self.rir_channels):
+            raise ValueError("Invalid channel index in `rir_channels`")
+
+    def to_dict(self) -> dict:
+        rir = self.rir.to_dict() if hasattr(self.rir, "to_dict") else self.rir
+        gen = self.rir_generator if self.rir_generator is None or isinstance(self.rir_generator, dict) else self.rir_generator.to_dict()
+        return {"name": type(self).__name__,
+                "kwargs": {"rir": rir, "normalize_output": self.normalize_output, "early_only": self.early_only,
+                           "rir_channels": list(self.rir_channels), "rir_generator": gen, "device": self.device}}
+
+    def __call__(self, samples: Union[np.ndarray, torch.Tensor], sampling_rate: int) -> Union[np.ndarray, torch.Tensor]:
+        is_tensor = isinstance(samples, torch.Tensor)
+        x = samples if is_tensor else torch.from_numpy(np.ascontiguousarray(samples))
+        if x.ndim != 2:
+            raise ValueError(f"expected samples of shape (channels, num_samples), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"expected float32 samples, got {x.dtype}")
+        d_in, n = int(x.shape[0]), int(x.shape[1])
+        rir = load_rir(self.rir, self.rir_channels, self.early_only)
+        items = reverb_items(d_in, int(rir.shape[0]))
+        scaled = [scaled_rir(rir[c]) for c in range(rir.shape[0])]
+        dev = torch.device(self.device)
+        dev = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index) if dev.type == "cuda" else dev
+        # one arena: the input channels, the scaled RIRs, the outputs (every part on a 16-byte boundary)
+        n4, taps = (n + 3) & ~3, int(rir.shape[1])
+        l4 = (taps + 3) & ~3
+        front = d_in * n4 + len(scaled) * l4
+        host = np.zeros(front, dtype=np.float32)
+        for c, (hs, _) in enumerate(scaled):
+            host[d_in * n4 + c * l4 : d_in * n4 + c * l4 + taps] = hs
+        arena = torch.empty(front + reverb_tail_floats([n] * len(items)), dtype=torch.float32, device=dev)
+        arena[:front].copy_(torch.from_numpy(host))
+        arena[: d_in * n4].view(d_in, n4)[:, :n].copy_(x)
+        offs = reverb_in_arena(arena, [a * n4 for a, _ in items], [n] * len(items), [d_in * n4 + b * l4 for _, b in items], [taps] * len(items),
+                               [scaled[b][1] for _, b in items], [int(bool(self.normalize_output))] * len(items), front)
+        out = torch.stack([arena[int(o) : int(o) + n] for o in offs])
+        return out.to(samples.device) if is_tensor else out.cpu().numpy()
+
+    def reverse_timestamps(self, offset: Seconds, duration: Optional[Seconds], sampling_rate: Optional[int]) -> Tuple[Seconds, Optional[Seconds]]:
+        """The output is shifted to the input's length: timestamps are unchanged (rir.py:155-166)."""
+        return offset, duration

@@ -26,6 +26,7 @@
 #include "kernel_resample.hpp"
 #include "kernel_minibatch.hpp"
 #include "kernel_mix.hpp"
+#include "kernel_reverb.hpp"
 #include "kernel_specaug.hpp"
 #include "kernel_whisper2.hpp"
 #include "kernel_whisper3.hpp"
@@ -2297,6 +2298,174 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int6
   hipError_t e2 = hipEventRecord(s.ev, st);
   s.busy = (e2 == hipSuccess);
   if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "mix launch failed: %s", hipGetErrorName(e1));
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Reverberation with a recorded impulse response on the device: convolution + power normalisation in two launches (kernel_reverb.hpp)
+// --------------------------------------------------------------------------------------
+constexpr int kRvSlots = 16;
+
+struct RvSlot {
+  int64_t ticket = -1;
+  bool planned = false;
+  std::vector<RvItem> items;
+  int64_t work_items = 0, arena_need = 0;
+  void* h = nullptr;  // pinned staging (a table that does not fit the kernel arguments)
+  void* d = nullptr;  // device: the staged table, then the partial sums of squares
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool busy = false;
+};
+
+struct hipfeat_reverb {
+  int device = 0;
+  bool allow_inline = true;
+  std::mutex mu;
+  RvSlot slots[kRvSlots];
+  int64_t next_ticket = 0;
+};
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_create(int32_t device, hipfeat_reverb** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "reverb pointer is NULL");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  hipfeat_reverb* r = new (std::nothrow) hipfeat_reverb();
+  if (!r) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  r->device = device;
+  r->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
+  *out = r;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_destroy(hipfeat_reverb* r) {
+  if (!r) return HIPFEAT_OK;
+  DeviceGuard g(r->device);
+  for (auto& s : r->slots) {
+    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    if (s.ev) (void)hipEventDestroy(s.ev);
+  }
+  delete r;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* rv, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                          const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
+                                                          const int32_t* h_normalize, int64_t tail_start, int64_t* h_out_offsets, int64_t* h_info) {
+  if (!rv || !h_src_offset || !h_src_len || !h_rir_offset || !h_rir_len || !h_shift || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (num_items <= 0 || num_items > 65535) return fail(HIPFEAT_ERR_INVALID, "bad batch arguments (1 ... 65535 items)");
+  if (tail_start < 0) return fail(HIPFEAT_ERR_INVALID, "tail_start %lld is negative", (long long)tail_start);
+  constexpr int64_t kMaxLen = INT32_MAX / 2;
+  std::lock_guard<std::mutex> lk(rv->mu);
+  // (validated into a local first: a refused table leaves the outstanding plans as they were)
+  std::vector<RvItem> items((size_t)num_items);
+  int64_t tail = (tail_start + 3) & ~(int64_t)3, work = 0;
+  for (int64_t i = 0; i < num_items; ++i) {
+    const int64_t so = h_src_offset[i], n = h_src_len[i], ro = h_rir_offset[i], taps = h_rir_len[i], shift = h_shift[i];
+    if (so < 0 || ro < 0) return fail(HIPFEAT_ERR_INVALID, "item %lld: negative offset (source %lld, impulse response %lld)", (long long)i, (long long)so, (long long)ro);
+    if (n < 1 || n > kMaxLen || taps < 1 || taps > kMaxLen)
+      return fail(HIPFEAT_ERR_INVALID, "item %lld: %lld samples, %lld taps: both must be 1 ... %lld", (long long)i, (long long)n, (long long)taps, (long long)kMaxLen);
+    if (shift < 0 || shift >= taps) return fail(HIPFEAT_ERR_INVALID, "item %lld: shift %lld outside [0, %lld)", (long long)i, (long long)shift, (long long)taps);
+    if (so + n > tail_start || ro + taps > tail_start)  // the outputs are written from tail_start on: output and source ranges would overlap
+      return fail(HIPFEAT_ERR_INVALID, "item %lld (source %lld + %lld, impulse response %lld + %lld) reaches into the arena's tail (tail_start %lld), where the outputs are written",
+                  (long long)i, (long long)so, (long long)n, (long long)ro, (long long)taps, (long long)tail_start);
+    RvItem& it = items[(size_t)i];
+    it.src_off = so;
+    it.rir_off = ro;
+    it.out_off = tail;
+    it.n = (int32_t)n;
+    it.taps = (int32_t)taps;
+    it.shift = (int32_t)shift;
+    it.item_first = (int32_t)work;
+    it.normalize = (h_normalize && h_normalize[i]) ? 1 : 0;
+    it.pad = 0;
+    work += (n + kRvBlock - 1) / kRvBlock;
+    tail += (n + 3) & ~(int64_t)3;
+    if (work > INT32_MAX - (1 << 24)) return fail(HIPFEAT_ERR_INVALID, "batch too large for one launch");
+  }
+  if (rv->slots[rv->next_ticket % kRvSlots].planned)  // (never drop a live plan: its ticket would fail at run)
+    return fail(HIPFEAT_ERR_INVALID, "%d planned reverberations are outstanding: run ticket %lld first", kRvSlots, (long long)rv->slots[rv->next_ticket % kRvSlots].ticket);
+  const int64_t ticket = rv->next_ticket++;
+  RvSlot& s = rv->slots[ticket % kRvSlots];
+  s.ticket = ticket;
+  s.items.swap(items);
+  s.work_items = work;
+  s.arena_need = tail;
+  s.planned = true;
+  if (h_out_offsets)
+    for (int64_t i = 0; i < num_items; ++i) h_out_offsets[i] = s.items[(size_t)i].out_off;
+  h_info[0] = ticket;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.work_items;
+  h_info[3] = 2 * s.work_items;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
+  if (!rv || !d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(rv->mu);
+  RvSlot& s = rv->slots[((ticket % kRvSlots) + kRvSlots) % kRvSlots];
+  if (s.ticket != ticket || !s.planned)
+    return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned reverberation (at most %d plans may be outstanding)", (long long)ticket, kRvSlots);
+  if (arena_floats < s.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the reverberated cuts need %lld", (long long)arena_floats, (long long)s.arena_need);
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
+  s.planned = false;
+  DeviceGuard g(rv->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = s.items.size() * sizeof(RvItem);  // (a multiple of 16)
+  const size_t part_bytes = (size_t)s.work_items * 2 * sizeof(double);
+  const bool inl = rv->allow_inline && bytes <= (size_t)kMbInlineBytes;
+  if (s.busy) {  // the launches that used this slot's device memory last time
+    HIP_TRY(hipEventSynchronize(s.ev));
+    s.busy = false;
+  }
+  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  const size_t dev_bytes = bytes + part_bytes;
+  if (s.cap < dev_bytes) {
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    s.h = s.d = nullptr;
+    s.cap = 0;
+    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
+    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&s.d, cap));
+    s.cap = cap;
+  }
+  RvInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
+  RvHeader& h = args.h;
+  h.arena = d_arena;
+  h.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(s.d) + bytes);
+  h.tables = nullptr;
+  h.num_items = (int32_t)s.items.size();
+  h.work_items = (int32_t)s.work_items;
+  h.table_bytes = (int32_t)bytes;
+  h.pad = 0;
+  // a few workgroups per CU take the work items round-robin (as hipfeat_mix_run)
+  const int64_t per_wg = std::max<int64_t>(1, (s.work_items + 1791) / 1792);
+  const unsigned grid = (unsigned)std::max<int64_t>(1, (s.work_items + per_wg - 1) / per_wg);
+  const size_t dyn = bytes <= (size_t)kMbLdsTableBytes ? bytes : 0;
+  hipError_t e1 = hipSuccess;
+  if (inl) {
+    std::memcpy(args.blob, s.items.data(), bytes);
+    hipLaunchKernelGGL(reverb_conv_inline_kernel, dim3(grid), dim3(256), 0, st, args);
+    hipLaunchKernelGGL(reverb_gain_inline_kernel, dim3(grid), dim3(256), 0, st, args);
+    e1 = hipGetLastError();
+  } else {
+    std::memcpy(s.h, s.items.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+    h.tables = static_cast<const unsigned char*>(s.d);
+    hipLaunchKernelGGL(reverb_conv_kernel, dim3(grid), dim3(256), dyn, st, h);
+    hipLaunchKernelGGL(reverb_gain_kernel, dim3(grid), dim3(256), dyn, st, h);
+    e1 = hipGetLastError();
+  }
+  hipError_t e2 = hipEventRecord(s.ev, st);
+  s.busy = (e2 == hipSuccess);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "reverb launch failed: %s", hipGetErrorName(e1));
   return HIPFEAT_OK;
 }
 

@@ -34,6 +34,15 @@ multi-channel or nested tracks, other transforms, a ``MixedCut`` with transforms
 padding, a first track with an SNR against another reference track, a muted reference track -- takes ``cut.load_audio()``, and a
 mini-batch may combine device-mixed, plain, speed-only and fallback cuts freely.
 
+Reverberation.  ``ReverbWithImpulseResponse`` (lhotse/augmentation/rir.py:12-166; ``cut.reverb_rir``) appends itself to the recording's
+transforms and ``Recording.load_audio`` then convolves the loaded (and speed-perturbed) samples with the RIR through three full-length
+float32 FFTs on the CPU.  With ``gpu_reverb`` (default: on unless ``wave_transforms`` are given) a recording whose transforms are
+``[Reverb]`` or ``[Speed, Reverb]`` with a RECORDED RIR and one ``rir_channels`` entry is read in front of them, the RIR is loaded on the
+host with the reference's own calls, and the convolution runs on the device between the resampler and the mix
+(``lhotse_amd.augmentation.reverb_in_arena``: direct form, float32, within 2 x the reference's own distance from the exact float64
+convolution).  ``rir=None`` (the random generator), several ``rir_channels``, a reverb in front of a ``Speed`` and a ``MixedCut`` whose own
+``transforms`` hold the reverb (``mix_first``) keep the reference's path.
+
 Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the class does not.
 """
 from __future__ import annotations
@@ -74,9 +83,22 @@ def _mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, 
     return mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples, tail_start)
 
 
+def _reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start):
+    """(indirection for the CPU stand-in of the tests)"""
+    from .augmentation import reverb_in_arena
+
+    return reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start)
+
+
 def _is_plain(tracks) -> bool:
-    """One track with samples that starts at 0 and is not scaled: the cut IS that track (a MonoCut, speed-perturbed or not)."""
+    """One track with samples that starts at 0 and is not scaled: the cut IS that track (a MonoCut, speed-perturbed or not; when the
+    track carries a reverb, the cut is the reverb's output)."""
     return len(tracks) == 1 and not isinstance(tracks[0][0], (int, np.integer)) and int(tracks[0][2]) == 0
+
+
+def _reverb_of(track):
+    """The optional 7th element of a track: ``(rir_samples, normalize_output)`` or None."""
+    return track[6] if len(track) > 6 and track[6] is not None else None
 
 
 class FusedMiniBatch:
@@ -109,15 +131,20 @@ class FusedMiniBatch:
         the track's first sample inside the cut; its SNR in dB or None; whether it is the cut's SNR reference track
         (``_get_snr_reference_track``, lhotse/cut/mixed.py:1909-1918); optionally the samples the track must end up with after its
         ``Speed`` (a sample or two are truncated, recording.py:1058-1060).  ``wants[c]`` = samples cut ``c`` must end up with
-        (``cut.num_samples``).  A cut of one unscaled track at offset 0 is a plain cut and is not copied.
+        (``cut.num_samples``).  A cut of one unscaled track at offset 0 is a plain cut and is not copied.  An optional 7th element
+        ``(rir_samples, normalize_output)`` reverberates the track (``ReverbWithImpulseResponse`` with a recorded RIR behind the track's
+        ``Speed``, lhotse/augmentation/rir.py:78-153): ``rir_samples`` = the float32 RIR as the reference loads it (channel selected,
+        ``early_only`` applied).  The RIRs of the mini-batch are packed into the arena with the tracks, each distinct one once, scaled by
+        2^-15 on the host; the reverb sees the untruncated resampled track, the mix and the plain cuts read its output.
 
-        Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> energy launch -> mix launch
+        Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> convolution and gain launch of
+        the reverberated tracks (``lhotse_amd.augmentation.reverb_in_arena``) -> energy launch -> mix launch
         (``lhotse_amd.augmentation.mix_in_arena``) -> the feature launch over the mixed offsets / lengths; one arena, one stream, no
         device -> host copy in between.  Without a mixed cut this IS ``features_of``.
         -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None."""
         if len(cuts_tracks) != len(wants):
             raise ValueError("features_of_tracks: one wanted sample count per cut")
-        if all(_is_plain(t) for t in cuts_tracks):
+        if all(_is_plain(t) and _reverb_of(t[0]) is None for t in cuts_tracks):
             audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
             audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
             if any(f != 1.0 for f in factors):
@@ -127,26 +154,50 @@ class FusedMiniBatch:
         return self._mix_and_extract(cuts_tracks, wants, sampling_rate)
 
     def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int):
-        """Pack every track, resample those with a pending factor into the tail, mix the mixed cuts behind them, extract."""
-        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout
+        """Pack every track (and every distinct RIR), resample the tracks with a pending factor into the tail, reverberate those with a RIR
+        behind them, mix the mixed cuts behind that, extract."""
+        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout, scaled_rir
         from .extractors import _as_1d_float
 
         ex = self.extractor
         ex._check_sr(sr)
         items, factors, caps = [], [], []  # the tracks that have a source, in cut / track order
+        rirs, rir_of, rv_idx, rv_rir, rv_norm = [], {}, [], [], []  # distinct scaled RIRs (hs, shift); reverberated tracks -> their RIR
         for tracks in cuts_tracks:
             for tr in tracks:
                 if isinstance(tr[0], (int, np.integer)):
+                    if _reverb_of(tr) is not None:
+                        raise ValueError("a padding track cannot carry a reverb")
                     continue
                 a = tr[0]
+                rv = _reverb_of(tr)
+                if rv is not None:
+                    if id(rv[0]) not in rir_of:  # (the same array object, as the loader's RIR cache hands out: no look at its bytes)
+                        h = np.ascontiguousarray(rv[0], dtype=np.float32).reshape(-1)
+                        if h.size < 1:
+                            raise ValueError("an impulse response needs at least one tap")
+                        key = (h.size, h.tobytes())
+                        if key not in rir_of:
+                            rir_of[key] = len(rirs)
+                            rirs.append(scaled_rir(h))
+                        rir_of[id(rv[0])] = rir_of[key]
+                    rv_idx.append(len(items)), rv_rir.append(rir_of[id(rv[0])]), rv_norm.append(int(bool(rv[1])))
                 items.append(_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures"))
                 factors.append(float(tr[1]))
                 caps.append(-1 if len(tr) < 6 or tr[5] is None else int(tr[5]))
         caps = np.asarray(caps, dtype=np.int64)
+        num_tracks = len(items)
+        rir_items = [hs for hs, _ in rirs]  # the RIRs travel in the same pack, behind the tracks
+        if rir_items and all(isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in items):
+            rir_items = [torch.from_numpy(h).to(items[0].device) for h in rir_items]  # (device-resident tracks are packed on the device)
+        items += rir_items
+        factors += [1.0] * len(rirs)
+        rv_idx = np.asarray(rv_idx, dtype=np.int64)
         cut_off, cut_len = np.zeros(len(cuts_tracks), dtype=np.int64), np.zeros(len(cuts_tracks), dtype=np.int64)
 
         def tables(po, pl):
             """The mix tables over the tracks at po / pl (a sample or two of a resampled track truncated); plain cuts -> cut_off / cut_len."""
+            pl = np.asarray(pl)[: len(caps)]  # (the RIRs behind the tracks are not tracks)
             pl = np.where(caps >= 0, np.minimum(pl, caps), pl)
             first, so, sl, do, snrs, refs, cap, ids = [0], [], [], [], [], [], [], []
             k = 0
@@ -173,21 +224,30 @@ class FusedMiniBatch:
             # that the tracks are packed straight into the ONE arena everything behind them is written to
             lens0 = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
             _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
+            rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) resampled tracks
             first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
             if mixed_ids:
                 short = mixed_num_samples(first, sl, do) < np.asarray(cap, dtype=np.int64)
                 if short.any():
                     raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
                                      "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
-            headroom = 3 + res_floats + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
+            headroom = 3 + res_floats + rv_floats + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
             arena, offs, lens = ex._pack(items, headroom=headroom)
             front = int(offs[-1] + lens[-1])
             if any(f != 1.0 for f in factors):
                 po, pl = _perturb_in_arena(arena, offs, lens, factors, sr, front)
             else:
                 po, pl = offs, lens
-            first, so, sl, do, snrs, refs, cap, mixed_ids = tables(po, pl)
             mix_start = ((front + 3) & ~3) + res_floats  # behind the resampled tracks (perturbed_layout's own end)
+            if len(rv_idx):
+                # the reverb sees the whole resampled track and takes its powers over that length; the sample or two that
+                # assert_and_maybe_fix_num_samples removes come off afterwards (recording.py:1032-1070): `tables` applies the caps
+                ro = _reverb_in_arena(arena, po[rv_idx], pl[rv_idx], [int(po[num_tracks + r]) for r in rv_rir], [len(rirs[r][0]) for r in rv_rir],
+                                      [rirs[r][1] for r in rv_rir], rv_norm, mix_start)
+                po = np.array(po, dtype=np.int64)
+                po[rv_idx] = ro
+                mix_start += rv_floats
+            first, so, sl, do, snrs, refs, cap, mixed_ids = tables(po, pl)
             if not mixed_ids:  # (every cut turned out to be one plain track, e.g. a mixed cut whose other tracks are muted: nothing to mix)
                 mo = ml = np.zeros(0, dtype=np.int64)
             else:
@@ -284,6 +344,59 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         factor = t["kwargs"]["factor"] if isinstance(t, dict) else t.factor
         return float(factor)
 
+    def _transform_name(t) -> str:
+        return t.get("name") if isinstance(t, dict) else type(t).__name__
+
+    def pending_transforms(cut, gpu_reverb: bool = True) -> Optional[Tuple[float, Optional[dict]]]:
+        """THE rule of what the device takes over: a mono cut (no video) over a recording whose transform list is ``[]``, ``[Speed]``,
+        ``[ReverbWithImpulseResponse]`` or ``[Speed, ReverbWithImpulseResponse]`` -> ``(factor still to be applied, 1.0 = none; the
+        reverb's kwargs or None)``.  The reverb must have a recorded ``rir`` and exactly one entry in ``rir_channels``.  None = load it
+        the reference's way: anything else, among it ``rir=None`` (the random generator), several ``rir_channels``, a reverb in front
+        of a ``Speed``, and any reverb when ``gpu_reverb`` is off."""
+        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
+            return None
+        tf = list(cut.recording.transforms or [])
+        factor, reverb = 1.0, None
+        if tf and _transform_name(tf[0]) == "Speed":
+            t = tf.pop(0)
+            factor = float(t["kwargs"]["factor"] if isinstance(t, dict) else t.factor)
+        if tf and _transform_name(tf[0]) == "ReverbWithImpulseResponse" and gpu_reverb:
+            t = tf.pop(0)
+            kw = dict(t["kwargs"]) if isinstance(t, dict) else {k: getattr(t, k) for k in ("rir", "normalize_output", "early_only", "rir_channels")}
+            if kw.get("rir") is None or len(kw.get("rir_channels") or [0]) != 1:
+                return None
+            reverb = {"rir": kw["rir"], "normalize_output": bool(kw.get("normalize_output", True)), "early_only": bool(kw.get("early_only", False)),
+                      "rir_channels": [int(c) for c in (kw.get("rir_channels") or [0])]}
+        return None if tf else (factor, reverb)
+
+    def deferred_reverb(cut, gpu_reverb: bool = True) -> Optional[Tuple[float, dict]]:
+        """``(pending speed factor, the reverb's kwargs)`` of a mono cut whose recording ends in a reverb the device serves
+        (``pending_transforms``), else None."""
+        p = pending_transforms(cut, gpu_reverb)
+        return None if p is None or p[1] is None else p
+
+    _RIR_CACHE: dict = {}
+
+    def load_reverb_rir(spec: dict) -> np.ndarray:
+        """The float32 RIR ``(L,)`` of a reverb the way the reference loads it (lhotse/augmentation/rir.py:116-122): ``to_cut()``,
+        ``with_channels``, ``truncate(duration=0.05)`` for ``early_only``, ``load_audio()`` -- through the reference's own class, whose
+        ``__post_init__`` reads the manifest back.  Cached per (recording id, channel, early_only)."""
+        from lhotse.augmentation import ReverbWithImpulseResponse  # the reference's own class: its loading calls are the contract
+
+        from .augmentation import load_rir
+
+        rir = spec["rir"]
+        if isinstance(rir, dict):
+            rir = ReverbWithImpulseResponse(rir=rir, rir_channels=list(spec["rir_channels"])).rir
+        key = (getattr(rir, "id", None), getattr(getattr(rir, "recording", None), "id", None), getattr(rir, "start", None),
+               getattr(rir, "duration", None), spec["rir_channels"][0], spec["early_only"])
+        hit = _RIR_CACHE.get(key)
+        if hit is None:
+            if len(_RIR_CACHE) >= 4096:
+                _RIR_CACHE.clear()
+            hit = _RIR_CACHE[key] = load_rir(rir, spec["rir_channels"], spec["early_only"])[0]
+        return hit
+
     def read_unperturbed(cut, factor: float) -> np.ndarray:
         """The segment of the ORIGINAL audio that ``Recording.load_audio`` reads for this cut before it applies ``Speed(factor)``
         (lhotse/audio/recording.py:412-467): same backward pass over the timestamps, same per-source reads."""
@@ -306,16 +419,38 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         audio = rec._stack_audio_channels(per_source)
         return np.ascontiguousarray(audio.reshape(-1), dtype=np.float32)
 
-    def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
+    def _read_before_transforms(cut, factor: float) -> Optional[np.ndarray]:
+        """The samples in front of the cut's pending transforms: ``read_unperturbed`` in front of a ``Speed`` (None when the resampled
+        segment would need reflect-padding, the rule of ``_read_one``), the plain segment of the file otherwise."""
+        sr = cut.sampling_rate
+        if factor == 1.0:
+            from lhotse.utils import fastcopy
+
+            plain = fastcopy(cut, recording=fastcopy(cut.recording, transforms=None))
+            return np.ascontiguousarray(plain.load_audio().reshape(-1), dtype=np.float32)
+        raw = read_unperturbed(cut, factor)
+        src, dst = round(sr * factor), sr
+        g = gcd(src, dst)
+        if int(np.ceil(np.float32((dst // g) * len(raw) / (src // g)))) < compute_num_samples(cut.duration, sr):  # resample.py:309
+            return None
+        return raw
+
+    def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False, gpu_reverb: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
         """(samples, factor still to be applied, samples the cut must end up with) or None when the read failed and errors are suppressed.
-        For a mixed cut the device will mix, ``samples`` is the list of its loaded tracks (``FusedMiniBatch.features_of_tracks``); a failed
-        track drops the cut."""
+        For a mixed cut the device will mix, and for a cut the device will reverberate, ``samples`` is the list of its loaded tracks
+        (``FusedMiniBatch.features_of_tracks``); a failed track drops the cut."""
         with suppress_audio_loading_errors(enabled=suppress_errors):
-            tracks = deferred_mix(cut) if gpu_mix else None
+            tracks = deferred_mix(cut, gpu_reverb) if gpu_mix else None
             if tracks is not None and (gpu_speed or all(t[1] in (None, 1.0) for t in tracks)):
                 res = _read_tracks(cut, tracks)
                 if res is not None:
                     return res
+            rv = deferred_reverb(cut, gpu_reverb)
+            if rv is not None and (gpu_speed or rv[0] == 1.0):
+                raw = _read_before_transforms(cut, rv[0])
+                if raw is not None:
+                    want = compute_num_samples(cut.duration, cut.sampling_rate)
+                    return [(raw, rv[0], 0, None, True, want, (load_reverb_rir(rv[1]), rv[1]["normalize_output"]))], 1.0, want
             factor = deferred_speed_factor(cut) if gpu_speed else None
             if factor is not None and factor != 1.0:
                 raw = read_unperturbed(cut, factor)
@@ -332,20 +467,19 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             return torch.from_numpy(audio), 1.0, int(audio.shape[-1])
         return None
 
-    def _pending_speed(cut) -> Optional[float]:
-        """1.0 for a mono cut over an untransformed recording, the factor when exactly one ``Speed`` is pending, None otherwise."""
-        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
-            return None
-        if not cut.recording.transforms:
-            return 1.0
-        return deferred_speed_factor(cut)
+    def _pending_speed(cut, gpu_reverb: bool = True) -> Optional[float]:
+        """1.0 for a mono cut over a recording without a pending ``Speed``, the factor when one is pending in front of nothing else or
+        of a reverb the device serves, None otherwise (``pending_transforms``)."""
+        p = pending_transforms(cut, gpu_reverb)
+        return None if p is None else p[0]
 
-    def deferred_mix(cut) -> Optional[List[tuple]]:
+    def deferred_mix(cut, gpu_reverb: bool = True) -> Optional[List[tuple]]:
         """The tracks of a ``MixedCut`` the device can mix -- ``[(track cut, factor, offset_samples, snr, is_reference)]`` over its audible
         tracks, ``factor`` = None for a ``PaddingCut`` track -- or None: load it the reference's way (``cut.load_audio()``).  Decided on
         the host before anything is read.  Refused: anything but a ``MixedCut`` with audio and without video or ``transforms`` of its own;
-        a track that is not a ``PaddingCut`` or a mono cut whose recording carries no transform or exactly one ``Speed`` (multi-channel
-        cuts, nested mixed cuts, other or several transforms); tracks at another sampling rate; no determinable, a muted or a padding SNR
+        a track that is not a ``PaddingCut`` or a mono cut whose recording's transforms are ``[]``, ``[Speed]``, ``[Reverb]`` or
+        ``[Speed, Reverb]`` (``pending_transforms``: multi-channel cuts, nested mixed cuts, other transforms, a reverb the device does
+        not serve); tracks at another sampling rate; no determinable, a muted or a padding SNR
         reference track; a first track with an SNR while the reference track is another one (the reference scales it through float64,
         mixed.py:1346-1350); a mix that comes out shorter than ``cut.num_samples`` (reflect-
         padded, mixed.py:1386-1387) or longer by lhotse's tolerance or more.  (A perturbed track that would need reflect-padding is found when
@@ -373,12 +507,13 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             if type(c).__name__ == "PaddingCut":
                 factor = None
             else:
-                factor = _pending_speed(c)
+                factor = _pending_speed(c, gpu_reverb)
                 if factor is None:
                     return None
             off = compute_num_samples(t.offset, sr)
             total = max(total, off + compute_num_samples(c.duration, sr))
-            out.append((c, factor, off, t.snr, t is ref))
+            rv = None if factor is None else deferred_reverb(c, gpu_reverb)
+            out.append((c, factor, off, t.snr, t is ref) + (() if rv is None else (rv[1],)))  # (a 6th element: the track's reverb)
         diff = total - cut.num_samples
         if diff < 0 or diff >= max(1, compute_num_samples(get_audio_duration_mismatch_tolerance(), sampling_rate=sr)):
             return None
@@ -389,10 +524,16 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         perturbed track would need reflect-padding (the rule of ``_read_one``)."""
         sr = cut.sampling_rate
         loaded = []
-        for c, factor, off, snr, is_ref in tracks:
+        for tr in tracks:
+            c, factor, off, snr, is_ref = tr[:5]
             n = compute_num_samples(c.duration, sr)
             if factor is None:
                 loaded.append((n, 1.0, off, snr, is_ref, n))
+            elif len(tr) > 5:  # a reverb behind the (possibly pending) Speed
+                raw = _read_before_transforms(c, factor)
+                if raw is None:
+                    return None
+                loaded.append((raw, factor, off, snr, is_ref, n, (load_reverb_rir(tr[5]), tr[5]["normalize_output"])))
             elif factor != 1.0:
                 raw = read_unperturbed(c, factor)
                 src, dst = round(sr * factor), sr
@@ -407,10 +548,11 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
     class HipOnTheFlyFeatures(OnTheFlyFeatures, FusedMiniBatch):
         """Same constructor as ``OnTheFlyFeatures`` plus ``return_device`` (``None`` keeps the padded feature tensor on the
         extractor's GPU, ready for the training step; ``"cpu"`` hands back a host tensor like the reference does) and
-        ``gpu_speed_perturb`` / ``gpu_mix`` (see the module docstring)."""
+        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` (see the module docstring)."""
 
         def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
-                     gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, **kwargs) -> None:
+                     gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, gpu_reverb: Optional[bool] = None,
+                     **kwargs) -> None:
             if not hasattr(extractor, "extract_collated"):
                 raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
             super().__init__(extractor, *args, **kwargs)
@@ -424,13 +566,18 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             # the same for the tracks of mixed cuts: wave_transforms run on the MIXED samples, so with them the mix stays where the
             # reference does it (MixedCut.load_audio); an explicit True together with wave_transforms raises when a mixed cut is met
             self.gpu_mix = (not self.wave_transforms) if gpu_mix is None else bool(gpu_mix)
+            # and for a reverb with a recorded RIR at the end of a recording's transforms (ReverbWithImpulseResponse): None = on the
+            # device unless wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a
+            # cut is met
+            self.gpu_reverb = (not self.wave_transforms) if gpu_reverb is None else bool(gpu_reverb)
 
         def _read(self, cuts, pool, recording_field):
             """read_audio_from_cuts (lhotse/dataset/collation.py:541-600) with the Speed of eligible cuts left for the device."""
             cuts = list(cuts)
             on_device = recording_field is None and (
                 (self.gpu_speed_perturb and any(deferred_speed_factor(c) not in (None, 1.0) for c in cuts))
-                or (self.gpu_mix and any(type(c).__name__ == "MixedCut" for c in cuts)))
+                or (self.gpu_mix and any(type(c).__name__ == "MixedCut" for c in cuts))
+                or (self.gpu_reverb and any(deferred_reverb(c) is not None for c in cuts)))
             if not on_device:
                 audios, ok = read_audio_from_cuts(cuts, executor=pool, suppress_errors=self.fault_tolerant, recording_field=recording_field)
                 return audios, [1.0] * len(audios), [int(a.shape[-1]) for a in audios], ok
@@ -440,7 +587,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
 
             map_fn = map if pool is None else pool.map
             audios, factors, wants, ok = [], [], [], []
-            read = partial(_read_one, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix)
+            read = partial(_read_one, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix,
+                           gpu_reverb=self.gpu_reverb)
             for cut, res in zip(cuts, map_fn(read, cuts)):
                 if res is None:
                     continue
@@ -456,6 +604,10 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             audios, factors, wants, cuts = self._read(cuts, pool, recording_field)
             mixed = any(isinstance(a, list) for a in audios)  # (the loaded tracks of the cuts the device mixes)
             for transform in self.wave_transforms:
+                if any(isinstance(a, list) and any(len(t) > 6 for t in a) for a in audios):
+                    raise ValueError("gpu_reverb=True was requested together with wave_transforms: the transforms run on the reverberated "
+                                     "samples, before the device convolves them; leave gpu_reverb at its default (None: "
+                                     "Recording.load_audio whenever wave_transforms are given) or pass False")
                 if mixed:
                     raise ValueError("gpu_mix=True was requested together with wave_transforms: the transforms run on the mixed samples, "
                                      "before the device mixes the tracks; leave gpu_mix at its default (None: MixedCut.load_audio whenever "
