@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HIPFEAT_ABI_VERSION 7
+#define HIPFEAT_ABI_VERSION 8
 
 #if defined(HIPFEAT_BUILD)
 #define HIPFEAT_API __attribute__((visibility("default")))
@@ -251,6 +251,14 @@ typedef struct hipfeat_resampler hipfeat_resampler;
 HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq, int32_t new_freq, int32_t width, const float* h_kernel,
                                         int32_t device, hipfeat_resampler** resampler);
 HIPFEAT_API hipfeat_status hipfeat_resampler_destroy(hipfeat_resampler* resampler);
+/*
+ * ABI v8.  The kernel hipfeat_resample launches for this resampler, chosen once at creation: "resample_fast<9,10,7>" (a compile-time
+ * instance: the speed ratios and 1:2, 2:1, 3:1), "resample_mfma" (many phases and an odd hop, e.g. 441:160 = 44.1 -> 16 kHz: the
+ * strided convolution of lhotse/augmentation/resample.py:284-315 as a GEMM on the f32 matrix cores) or "resample_generic" (everything
+ * else, and everything under HIPFEAT_RESAMPLE_GENERIC=1).  All three sum a sample's taps in ascending order; their outputs are equal.
+ * The string lives as long as the resampler.
+ */
+HIPFEAT_API const char* hipfeat_resampler_kernel_name(const hipfeat_resampler* resampler);
 /* ceil(new * num_samples / orig), evaluated like the reference (in float32, resample.py:309). */
 HIPFEAT_API int64_t hipfeat_resampled_length(int64_t num_samples, int32_t orig_freq, int32_t new_freq);
 /* Batch of cuts: cut b = d_in[h_in_offsets[b] .. + h_num_samples[b]) -> d_out[h_out_offsets[b] .. + resampled_length). */

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # name -> (return C type, [argument C types]) ; mirrors include/hipfeat.h one to one.
 _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
@@ -62,6 +62,7 @@ _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
     "hipfeat_resampler_create": ("int", ["int32_t", "int32_t", "int32_t", "const float*", "int32_t", "hipfeat_resampler**"]),
     "hipfeat_resampler_destroy": ("int", ["hipfeat_resampler*"]),
+    "hipfeat_resampler_kernel_name": ("const char*", ["const hipfeat_resampler*"]),
     "hipfeat_resampled_length": ("int64_t", ["int64_t", "int32_t", "int32_t"]),
     "hipfeat_resample": (
         "int",

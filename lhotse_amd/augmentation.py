@@ -78,6 +78,8 @@ class HipResampleTensor:
         out = np.zeros(1, dtype=np.uint64)
         self.lib.check("hipfeat_resampler_create", self.orig, self.new, self.width, _lib.addr(self.kernel), int(self.device.index), _lib.addr(out))
         self.handle = int(out[0])
+        # "resample_fast<9,10,7>" | "resample_mfma" | "resample_generic": the kernel the library chose for this ratio
+        self.kernel_name = self.lib.string("hipfeat_resampler_kernel_name", self.handle)
 
     # ---- lengths -------------------------------------------------------------------------------------------
     def output_length(self, num_samples: int) -> int:
@@ -243,23 +245,20 @@ def perturbed_tail_floats(lengths: np.ndarray, factors: Sequence[float], samplin
     return total
 
 
-def perturbed_layout(offsets: np.ndarray, lengths: np.ndarray, factors: Sequence[float], sampling_rate: int,
-                     tail_start: int) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Where ``perturb_speed_in_arena`` puts every cut and how long it comes out -- host arithmetic only, THE placement rule: cuts with
-    factor 1 stay, the others go behind ``tail_start`` factor by factor in ascending order, every resampled cut on a 16-byte boundary,
-    ``ceil(new * n / orig)`` samples in float32 (resample.py:309) with orig : new = round(sr * f) : sr reduced by their gcd
-    (resample.py:219-222).  -> (offsets, lengths, first free float behind the resampled cuts, 16-byte aligned)."""
+def _grouped_layout(offsets, lengths, keys, ratio_of, tail_start):
+    """The placement rule behind ``resample_layout`` and ``perturbed_layout``: cuts whose key is None stay, the others go behind
+    ``tail_start`` group by group in ascending order of their keys, every resampled cut on a 16-byte boundary, ``ceil(new * n / orig)``
+    samples in float32 (resample.py:309) with orig : new = ``ratio_of(key)`` reduced by their gcd (resample.py:219-222).
+    -> (offsets, lengths, first free float behind the resampled cuts, 16-byte aligned, [(key, indices of its cuts)])."""
     from math import gcd
 
     offsets, lengths = _lib.i64(offsets).copy(), _lib.i64(lengths).copy()
-    fac = np.asarray(factors, dtype=np.float64)
-    assert len(fac) == len(lengths)
+    assert len(keys) == len(lengths)
     tail = (int(tail_start) + 3) & ~3
-    for f in sorted(set(fac.tolist())):
-        if f == 1.0:
-            continue
-        idx = np.nonzero(fac == f)[0]
-        src, dst = round(sampling_rate * f), int(sampling_rate)
+    groups = []
+    for key in sorted(set(k for k in keys if k is not None)):
+        idx = np.array([i for i, k in enumerate(keys) if k == key], dtype=np.int64)
+        src, dst = (int(v) for v in ratio_of(key))
         g = gcd(src, dst)
         out_lens = np.ceil(((dst // g) * lengths[idx] / (src // g)).astype(np.float32)).astype(np.int64)
         out_offs = np.zeros(len(idx), dtype=np.int64)
@@ -267,7 +266,75 @@ def perturbed_layout(offsets: np.ndarray, lengths: np.ndarray, factors: Sequence
         out_offs += tail
         offsets[idx], lengths[idx] = out_offs, out_lens
         tail = (int(out_offs[-1] + out_lens[-1]) + 3) & ~3
-    return offsets, lengths, tail
+        groups.append((key, idx))
+    return offsets, lengths, tail, groups
+
+
+def _resample_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups, ratio_of, what):
+    """One ``hipfeat_resample`` launch per group of ``_grouped_layout``, input and output in the same arena."""
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    last = max((int((offsets[idx] + lengths[idx]).max()) for _, idx in groups), default=0)
+    if last > arena.numel():
+        raise ValueError(f"arena too small: {arena.numel()} floats, the {what} cuts need {last} (see {what}_tail_floats)")
+    dev = arena.device
+    for key, idx in groups:
+        src, dst = (int(v) for v in ratio_of(key))
+        r = get_or_create_resampler(src, dst, dev)
+        in_offs, in_lens = np.ascontiguousarray(in_offsets[idx]), np.ascontiguousarray(in_lengths[idx])  # (named: they must outlive the call)
+        out_offs = np.ascontiguousarray(offsets[idx])
+        assert np.array_equal(r.output_lengths(in_lens), lengths[idx])  # the library's own length rule
+        with torch.cuda.device(dev):
+            r.lib.check("hipfeat_resample", r.handle, arena.data_ptr(), _lib.addr(in_offs), _lib.addr(in_lens), int(len(idx)), arena.data_ptr(),
+                        _lib.addr(out_offs), int(torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _ratio_keys(ratios) -> list:
+    return [None if r is None else (int(r[0]), int(r[1])) for r in ratios]
+
+
+def resampled_tail_floats(lengths: np.ndarray, ratios: Sequence[Optional[Tuple[int, int]]]) -> int:
+    """Floats the resampled cuts of ``resample_in_arena`` need behind ``tail_start`` (rounded up to 16 bytes)."""
+    return int(_grouped_layout(np.zeros(len(lengths), dtype=np.int64), lengths, _ratio_keys(ratios), lambda k: k, 0)[2])
+
+
+def resample_layout(offsets: np.ndarray, lengths: np.ndarray, ratios: Sequence[Optional[Tuple[int, int]]],
+                    tail_start: int) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Where ``resample_in_arena`` puts every cut and how long it comes out -- host arithmetic only.  ``ratios[i]`` = (source rate,
+    target rate) of cut i, or None for a cut that stays as it is.  Cuts go behind ``tail_start`` ratio by ratio in ascending order of
+    (source, target), every resampled cut on a 16-byte boundary, ``ceil(new * n / orig)`` samples in float32 (resample.py:309) with
+    orig : new the rates reduced by their gcd (resample.py:219-222).  ``perturbed_layout`` is this rule with the ratios of ``Speed``.
+    -> (offsets, lengths, first free float behind the resampled cuts, 16-byte aligned)."""
+    return _grouped_layout(offsets, lengths, _ratio_keys(ratios), lambda k: k, tail_start)[:3]
+
+
+def resample_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np.ndarray, ratios: Sequence[Optional[Tuple[int, int]]],
+                      tail_start: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Sampling-rate conversion of a device-resident packed mini-batch (``Resample``, lhotse/augmentation/torchaudio.py:86-139 with the
+    sinc backend): the generalisation of ``perturb_speed_in_arena`` from speed factors to any (source, target) rates per cut.
+
+    ``arena`` is ONE float32 device buffer: the cuts at ``offsets`` / ``lengths`` in its front part, free space from ``tail_start`` on
+    (``resampled_tail_floats`` says how much).  Cuts with ratio None stay where they are; the others are resampled -- one
+    ``hipfeat_resample`` launch per distinct ratio, in ascending order -- into the tail.  Returns the per-cut (offsets, lengths) inside
+    the same arena.  A second pass (a ``Speed`` behind the ``Resample``) takes these as its input with ``tail_start`` = the end
+    ``resample_layout`` reports."""
+    keys = _ratio_keys(ratios)
+    in_offsets, in_lengths = _lib.i64(offsets), _lib.i64(lengths)
+    offsets, lengths, _, groups = _grouped_layout(in_offsets, in_lengths, keys, lambda k: k, tail_start)
+    _resample_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups, lambda k: k, "resampled")
+    return offsets, lengths
+
+
+def _speed_keys(factors) -> list:
+    return [None if f == 1.0 else f for f in np.asarray(factors, dtype=np.float64).tolist()]
+
+
+def perturbed_layout(offsets: np.ndarray, lengths: np.ndarray, factors: Sequence[float], sampling_rate: int,
+                     tail_start: int) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Where ``perturb_speed_in_arena`` puts every cut and how long it comes out -- host arithmetic only, THE placement rule: cuts with
+    factor 1 stay, the others go behind ``tail_start`` factor by factor in ascending order, every resampled cut on a 16-byte boundary,
+    ``ceil(new * n / orig)`` samples in float32 (resample.py:309) with orig : new = round(sr * f) : sr reduced by their gcd
+    (resample.py:219-222).  -> (offsets, lengths, first free float behind the resampled cuts, 16-byte aligned)."""
+    return _grouped_layout(offsets, lengths, _speed_keys(factors), lambda f: (round(sampling_rate * f), int(sampling_rate)), tail_start)[:3]
 
 
 def perturb_speed_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np.ndarray, factors: Sequence[float], sampling_rate: int,
@@ -279,25 +346,10 @@ def perturb_speed_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np
     (``perturbed_tail_floats`` says how much).  Cuts with factor 1 stay where they are; the others are resampled -- one launch per
     distinct factor -- into the tail.  Returns the per-cut (offsets, lengths) of the perturbed batch inside the same arena, i.e. exactly
     what ``hipfeat_extract*`` takes next: no copy of the unperturbed cuts, no host round trip, no second buffer."""
-    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
     in_offsets, in_lengths = _lib.i64(offsets), _lib.i64(lengths)
-    fac = np.asarray(factors, dtype=np.float64)
-    offsets, lengths, _ = perturbed_layout(in_offsets, in_lengths, factors, sampling_rate, tail_start)
-    last = int((offsets + lengths)[fac != 1.0].max(initial=0))
-    if last > arena.numel():
-        raise ValueError(f"arena too small: {arena.numel()} floats, the perturbed cuts need {last} (see perturbed_tail_floats)")
-    dev = arena.device
-    for f in sorted(set(fac.tolist())):
-        if f == 1.0:
-            continue
-        idx = np.nonzero(fac == f)[0]
-        r = get_or_create_resampler(round(sampling_rate * f), sampling_rate, dev)
-        in_offs, in_lens = np.ascontiguousarray(in_offsets[idx]), np.ascontiguousarray(in_lengths[idx])  # (named: they must outlive the call)
-        out_offs = np.ascontiguousarray(offsets[idx])
-        assert np.array_equal(r.output_lengths(in_lens), lengths[idx])  # the library's own length rule
-        with torch.cuda.device(dev):
-            r.lib.check("hipfeat_resample", r.handle, arena.data_ptr(), _lib.addr(in_offs), _lib.addr(in_lens), int(len(idx)), arena.data_ptr(),
-                        _lib.addr(out_offs), int(torch.cuda.current_stream(dev).cuda_stream))
+    ratio_of = lambda f: (round(sampling_rate * f), int(sampling_rate))  # noqa: E731
+    offsets, lengths, _, groups = _grouped_layout(in_offsets, in_lengths, _speed_keys(factors), ratio_of, tail_start)
+    _resample_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups, ratio_of, "perturbed")
     return offsets, lengths
 
 

@@ -24,6 +24,7 @@
 #include "kernel_fft2048c.hpp"
 #include "plan_tables.hpp"
 #include "kernel_resample.hpp"
+#include "resample_tables.hpp"
 #include "kernel_minibatch.hpp"
 #include "kernel_mix.hpp"
 #include "kernel_reverb.hpp"
@@ -44,7 +45,7 @@ static thread_local char g_err[512] = "";
 
 // Environment switches, two classes:
 //   route_env  ROUTING switches choose among kernels / launch routes that ALL meet the parity bar (HIPFEAT_FORCE_GENERIC, *_VARIANT,
-//              HIPFEAT_NO_FIXED_SCHEDULE, HIPFEAT_NO_WAVE_*, HIPFEAT_NO_FLAT, HIPFEAT_RESAMPLE_GENERIC, HIPFEAT_MB_NO_INLINE): the GPU
+//              HIPFEAT_NO_FIXED_SCHEDULE, HIPFEAT_NO_WAVE_*, HIPFEAT_NO_FLAT, HIPFEAT_RESAMPLE_GENERIC / _MFMA, HIPFEAT_MB_NO_INLINE): the GPU
 //              suite uses them to compare the instances of ONE library against each other, bit for bit where the arithmetic is the same.
 //   exp_env    EXPERIMENT switches skip work or retune launch shapes (HIPFEAT_MB_SKIP = deliberately wrong results, HIPFEAT_MB_SLOTS,
 //              HIPFEAT_ROUNDS, HIPFEAT_ROUNDS_R3).  They exist only in builds with -DHIPFEAT_EXPERIMENTS (tools/variants.py); in the
@@ -1601,6 +1602,10 @@ struct hipfeat_resampler {
   float* d_kernel_t = nullptr;
   void (*fast)(const float*, float*, const ResCut*, const float*, int, unsigned, hipStream_t) = nullptr;
   int fast_outs = 0;
+  // matrix-core path (many-phase ratios): padded transposed bank [kwp][nwp] + geometry (resample_tables.hpp)
+  float* d_kernel_mfma = nullptr;
+  ResMfmaGeometry mfma;
+  char kernel_name[48] = "resample_generic";
   mutable std::mutex mu;
   mutable StagingSlot slots[4];
   mutable int next_slot = 0;
@@ -1617,6 +1622,7 @@ static bool pick_resample_fast(hipfeat_resampler* r) {
   if (r->orig != ORIG || r->nw != NEW || r->width != WIDTH) return false;
   r->fast = &launch_resample_fast<ORIG, NEW, WIDTH>;
   r->fast_outs = ResampleFast<ORIG, NEW, WIDTH>::OUTS;
+  std::snprintf(r->kernel_name, sizeof(r->kernel_name), "resample_fast<%d,%d,%d>", ORIG, NEW, WIDTH);
   return true;
 }
 
@@ -1649,7 +1655,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
     return st;
   }
   // speed 0.9 / 1.1 / 0.95 / 1.05 at any rate, and the 1:2, 2:1, 3:1 rate conversions
-  const bool fast = !route_env("HIPFEAT_RESAMPLE_GENERIC") &&
+  const bool generic_only = route_env("HIPFEAT_RESAMPLE_GENERIC");
+  const bool fast = !generic_only &&
                     (pick_resample_fast<9, 10, 7>(r) || pick_resample_fast<11, 10, 7>(r) || pick_resample_fast<19, 20, 7>(r) ||
                      pick_resample_fast<21, 20, 7>(r) || pick_resample_fast<1, 2, 7>(r) || pick_resample_fast<2, 1, 13>(r) ||
                      pick_resample_fast<3, 1, 19>(r));
@@ -1664,6 +1671,19 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
       delete r;
       return st;
     }
+  } else if (!generic_only && (res_mfma_routed(r->orig, r->nw, r->width) ||
+                               (route_env("HIPFEAT_RESAMPLE_MFMA") && r->nw >= kResMfmaTile && res_mfma_geometry(r->orig, r->nw, r->width).fits))) {
+    // many phases, odd hop: the matrix-core kernel (measured against the generic one by tools/bench_resample_rates.py, which sets
+    // HIPFEAT_RESAMPLE_MFMA=1 to time it on the ratios the rule leaves to the generic kernel as well)
+    r->mfma = res_mfma_geometry(r->orig, r->nw, r->width);
+    const std::vector<float> kt = res_mfma_bank(h_kernel, r->nw, r->kw, r->mfma.kwp, r->mfma.nwp);
+    st = upload(&r->d_kernel_mfma, kt.data(), kt.size());
+    if (st != HIPFEAT_OK) {
+      (void)hipFree(r->d_kernel);
+      delete r;
+      return st;
+    }
+    std::snprintf(r->kernel_name, sizeof(r->kernel_name), "resample_mfma");
   }
   r->kernel_in_lds = ((size_t)r->nw * r->kw <= 8192) ? 1 : 0;
   for (r->outs_per_block = 2048; r->outs_per_block >= 64; r->outs_per_block >>= 1) {
@@ -1685,6 +1705,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_destroy(hipfeat_resample
   DeviceGuard g(r->device);
   (void)hipFree(r->d_kernel);
   if (r->d_kernel_t) (void)hipFree(r->d_kernel_t);
+  if (r->d_kernel_mfma) (void)hipFree(r->d_kernel_mfma);
   for (auto& s : r->slots) {
     if (s.h) (void)hipHostFree(s.h);
     if (s.d) (void)hipFree(s.d);
@@ -1694,6 +1715,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_destroy(hipfeat_resample
   return HIPFEAT_OK;
 }
 
+extern "C" HIPFEAT_API const char* hipfeat_resampler_kernel_name(const hipfeat_resampler* r) { return r ? r->kernel_name : ""; }
+
 extern "C" HIPFEAT_API hipfeat_status hipfeat_resample(const hipfeat_resampler* r, const float* d_in, const int64_t* h_in_offsets,
                                                        const int64_t* h_num_samples, int64_t batch, float* d_out,
                                                        const int64_t* h_out_offsets, void* stream) {
@@ -1702,7 +1725,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resample(const hipfeat_resampler* 
     return fail(HIPFEAT_ERR_INVALID, "bad batch arguments");
   std::vector<ResCut> cuts((size_t)batch);
   int64_t blocks = 0;
-  const int64_t opb = r->fast ? r->fast_outs : r->outs_per_block;
+  const int64_t opb = r->fast ? r->fast_outs : r->d_kernel_mfma ? r->mfma.outs_per_block : r->outs_per_block;
   for (int64_t b = 0; b < batch; ++b) {
     const int64_t L = h_num_samples[b];
     if (L < 0 || L > INT32_MAX / 2) return fail(HIPFEAT_ERR_INVALID, "cut %lld: %lld samples out of range", (long long)b, (long long)L);
@@ -1737,6 +1760,32 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resample(const hipfeat_resampler* 
   HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
   if (r->fast) {
     r->fast(d_in, d_out, static_cast<const ResCut*>(s.d), r->d_kernel_t, (int)batch, (unsigned)blocks, (hipStream_t)stream);
+    hipError_t e1 = hipGetLastError();
+    hipError_t e2 = hipEventRecord(s.ev, (hipStream_t)stream);
+    s.busy = (e2 == hipSuccess);
+    if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "resample launch failed: %s", hipGetErrorName(e1));
+    return HIPFEAT_OK;
+  }
+  if (r->d_kernel_mfma) {
+    ResMfmaParams mp{};
+    mp.in = d_in;
+    mp.out = d_out;
+    mp.cuts = static_cast<const ResCut*>(s.d);
+    mp.kt = r->d_kernel_mfma;
+    mp.num_cuts = (int32_t)batch;
+    mp.orig = r->orig;
+    mp.nw = r->nw;
+    mp.width = r->width;
+    mp.kwp = r->mfma.kwp;
+    mp.nwp = r->mfma.nwp;
+    mp.span_floats = r->mfma.span_floats;
+    const dim3 grid((unsigned)blocks), wg(256);
+    if (r->mfma.hop_tiles == 4)
+      hipLaunchKernelGGL(resample_mfma_kernel<4>, grid, wg, r->mfma.lds_bytes, (hipStream_t)stream, mp);
+    else if (r->mfma.hop_tiles == 2)
+      hipLaunchKernelGGL(resample_mfma_kernel<2>, grid, wg, r->mfma.lds_bytes, (hipStream_t)stream, mp);
+    else
+      hipLaunchKernelGGL(resample_mfma_kernel<1>, grid, wg, r->mfma.lds_bytes, (hipStream_t)stream, mp);
     hipError_t e1 = hipGetLastError();
     hipError_t e2 = hipEventRecord(s.ev, (hipStream_t)stream);
     s.busy = (e2 == hipSuccess);

@@ -43,6 +43,15 @@ host with the reference's own calls, and the convolution runs on the device betw
 convolution).  ``rir=None`` (the random generator), several ``rir_channels``, a reverb in front of a ``Speed`` and a ``MixedCut`` whose own
 ``transforms`` hold the reverb (``mix_first``) keep the reference's path.
 
+Resampling.  ``cuts.resample(sr)`` puts a ``Resample(a -> sr)`` at the front of the recording's transforms (lhotse/audio/recording.py:905-935)
+and ``Recording.load_audio`` then runs the sinc resampler on the CPU (44.1 -> 16 kHz: 160 filters of 475 taps).  With ``gpu_resample``
+(default: on unless ``wave_transforms`` are given, and only where the reference itself runs its sinc resampler: torchaudio importable,
+backend ``default``) a mono recording whose transforms are ``[Resample]? [Speed]? [Reverb]?`` is read in front of ALL of them at the
+source rate (``read_before_chain``), and the chain runs on the device: the rate conversion first, one launch per distinct source rate
+(``lhotse_amd.augmentation.resample_in_arena``; the many-phase ratios on the matrix cores), then the ``Speed`` as a second pass over
+its output, then reverb and mix as before.  ``pending_chain`` says which cuts qualify; a ``Resample`` that is not first or not alone,
+the ``sox`` backend and a filter bank of more than 2^20 floats keep the reference's path.
+
 Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the class does not.
 """
 from __future__ import annotations
@@ -76,6 +85,13 @@ def _perturb_in_arena(arena, offsets, lengths, factors, sampling_rate, tail_star
     return perturb_speed_in_arena(arena, offsets, lengths, factors, sampling_rate, tail_start)
 
 
+def _resample_in_arena(arena, offsets, lengths, ratios, tail_start):
+    """(indirection for the CPU stand-in of the tests)"""
+    from .augmentation import resample_in_arena
+
+    return resample_in_arena(arena, offsets, lengths, ratios, tail_start)
+
+
 def _mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples, tail_start):
     """(indirection for the CPU stand-in of the tests)"""
     from .augmentation import mix_in_arena
@@ -99,6 +115,12 @@ def _is_plain(tracks) -> bool:
 def _reverb_of(track):
     """The optional 7th element of a track: ``(rir_samples, normalize_output)`` or None."""
     return track[6] if len(track) > 6 and track[6] is not None else None
+
+
+def _source_rate_of(track, sampling_rate: int) -> Optional[int]:
+    """The optional 8th element of a track: the rate its samples are at, when that is not the mini-batch's (a pending ``Resample``)."""
+    rate = track[7] if len(track) > 7 else None
+    return None if rate is None or int(rate) == int(sampling_rate) else int(rate)
 
 
 class FusedMiniBatch:
@@ -135,7 +157,12 @@ class FusedMiniBatch:
         ``(rir_samples, normalize_output)`` reverberates the track (``ReverbWithImpulseResponse`` with a recorded RIR behind the track's
         ``Speed``, lhotse/augmentation/rir.py:78-153): ``rir_samples`` = the float32 RIR as the reference loads it (channel selected,
         ``early_only`` applied).  The RIRs of the mini-batch are packed into the arena with the tracks, each distinct one once, scaled by
-        2^-15 on the host; the reverb sees the untruncated resampled track, the mix and the plain cuts read its output.
+        2^-15 on the host; the reverb sees the untruncated resampled track, the mix and the plain cuts read its output.  An optional 8th
+        element ``source_rate``: the samples are at that rate (a pending ``Resample(source_rate -> sampling_rate)`` in front of the
+        ``Speed``, lhotse/augmentation/torchaudio.py:86-139 with the sinc backend) and are resampled to ``sampling_rate`` first, one launch
+        per distinct rate (``lhotse_amd.augmentation.resample_in_arena``); the track's ``Speed`` then is a second pass over the first
+        pass's output, and only the final length is capped (recording.py:486-490).  A mini-batch without a ``source_rate`` takes exactly
+        the route it took before there was one.
 
         Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> convolution and gain launch of
         the reverberated tracks (``lhotse_amd.augmentation.reverb_in_arena``) -> energy launch -> mix launch
@@ -144,7 +171,7 @@ class FusedMiniBatch:
         -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None."""
         if len(cuts_tracks) != len(wants):
             raise ValueError("features_of_tracks: one wanted sample count per cut")
-        if all(_is_plain(t) and _reverb_of(t[0]) is None for t in cuts_tracks):
+        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None for t in cuts_tracks):
             audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
             audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
             if any(f != 1.0 for f in factors):
@@ -156,12 +183,12 @@ class FusedMiniBatch:
     def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int):
         """Pack every track (and every distinct RIR), resample the tracks with a pending factor into the tail, reverberate those with a RIR
         behind them, mix the mixed cuts behind that, extract."""
-        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout, scaled_rir
+        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout, resample_layout, scaled_rir
         from .extractors import _as_1d_float
 
         ex = self.extractor
         ex._check_sr(sr)
-        items, factors, caps = [], [], []  # the tracks that have a source, in cut / track order
+        items, factors, caps, ratios = [], [], [], []  # the tracks that have a source, in cut / track order; ratios: (source rate, sr) or None
         rirs, rir_of, rv_idx, rv_rir, rv_norm = [], {}, [], [], []  # distinct scaled RIRs (hs, shift); reverberated tracks -> their RIR
         for tracks in cuts_tracks:
             for tr in tracks:
@@ -184,6 +211,8 @@ class FusedMiniBatch:
                     rv_idx.append(len(items)), rv_rir.append(rir_of[id(rv[0])]), rv_norm.append(int(bool(rv[1])))
                 items.append(_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures"))
                 factors.append(float(tr[1]))
+                rate = _source_rate_of(tr, sr)
+                ratios.append(None if rate is None else (rate, int(sr)))
                 caps.append(-1 if len(tr) < 6 or tr[5] is None else int(tr[5]))
         caps = np.asarray(caps, dtype=np.int64)
         num_tracks = len(items)
@@ -192,6 +221,8 @@ class FusedMiniBatch:
             rir_items = [torch.from_numpy(h).to(items[0].device) for h in rir_items]  # (device-resident tracks are packed on the device)
         items += rir_items
         factors += [1.0] * len(rirs)
+        ratios += [None] * len(rirs)
+        two_pass = any(r is not None for r in ratios)
         rv_idx = np.asarray(rv_idx, dtype=np.int64)
         cut_off, cut_len = np.zeros(len(cuts_tracks), dtype=np.int64), np.zeros(len(cuts_tracks), dtype=np.int64)
 
@@ -223,6 +254,9 @@ class FusedMiniBatch:
             # sizes first, from the lengths alone (the sample counts of the resampled tracks are known on the host, resample.py:309), so
             # that the tracks are packed straight into the ONE arena everything behind them is written to
             lens0 = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
+            rs_floats = 0  # the first pass (source rate -> sr), in front of the pass of the speed factors: both count for the head-room
+            if two_pass:
+                _, lens0, rs_floats = resample_layout(np.zeros(len(items), dtype=np.int64), lens0, ratios, 0)  # (a multiple of 4)
             _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
             rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) resampled tracks
             first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
@@ -231,9 +265,12 @@ class FusedMiniBatch:
                 if short.any():
                     raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
                                      "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
-            headroom = 3 + res_floats + rv_floats + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
+            headroom = 3 + rs_floats + res_floats + rv_floats + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
             arena, offs, lens = ex._pack(items, headroom=headroom)
             front = int(offs[-1] + lens[-1])
+            if two_pass:  # the tracks at another rate come to sr behind the pack; the speed pass reads them there
+                offs, lens = _resample_in_arena(arena, offs, lens, ratios, front)
+                front = ((front + 3) & ~3) + rs_floats  # (resample_layout's own end)
             if any(f != 1.0 for f in factors):
                 po, pl = _perturb_in_arena(arena, offs, lens, factors, sr, front)
             else:
@@ -375,6 +412,95 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         p = pending_transforms(cut, gpu_reverb)
         return None if p is None or p[1] is None else p
 
+    MAX_RESAMPLE_BANK_FLOATS = 1 << 20  # the largest filter bank (new x (2 width + orig) floats, reduced rates) the device route takes
+
+    def _sinc_bank_floats(source_rate: int, target_rate: int) -> int:
+        """Floats of the reference's filter bank for source -> target (lhotse/augmentation/resample.py:219-236: rates reduced by their
+        gcd, lowpass_filter_width 6, rolloff 0.99), from the rates alone."""
+        from math import ceil
+
+        g = gcd(int(source_rate), int(target_rate))
+        orig, new = int(source_rate) // g, int(target_rate) // g
+        width = ceil(6 * orig / (min(orig, new) * 0.99))
+        return new * (2 * width + orig)
+
+    def pending_chain(cut, gpu_reverb: bool = True, gpu_resample: bool = True) -> Optional[Tuple[Optional[int], float, Optional[dict]]]:
+        """``pending_transforms`` with a ``Resample`` in front: a mono cut (no video) over a recording whose transform list is
+        ``[Resample(a -> sr)]? [Speed]? [ReverbWithImpulseResponse]?`` with ``sr == cut.sampling_rate`` and ``a != sr`` ->
+        ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None)``.  None = load it the reference's way:
+        whatever ``pending_transforms`` refuses behind the ``Resample``; a ``Resample`` that is not the first transform
+        (``[Speed, Resample]``) or not the only one (``LowpassUsingResampling`` adds two); one to another rate than the cut's; the
+        ``sox`` resampling backend (``LHOTSE_RESAMPLING_BACKEND=sox``: another filter); a reduced filter bank of more than 2^20 floats;
+        any ``Resample`` when ``gpu_resample`` is off."""
+        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
+            return None
+        tf = list(cut.recording.transforms or [])
+        if not tf or _transform_name(tf[0]) != "Resample":
+            p = pending_transforms(cut, gpu_reverb)
+            return None if p is None else (None, p[0], p[1])
+        if not gpu_resample:
+            return None
+        t = tf[0]
+        src = int(t["kwargs"]["source_sampling_rate"] if isinstance(t, dict) else t.source_sampling_rate)
+        dst = int(t["kwargs"]["target_sampling_rate"] if isinstance(t, dict) else t.target_sampling_rate)
+        if dst != int(cut.sampling_rate) or src == dst or src <= 0:
+            return None
+        from lhotse.audio.resampling_backend import get_current_resampling_backend  # the reference's own switch is the contract
+
+        if get_current_resampling_backend() != "default" or _sinc_bank_floats(src, dst) > MAX_RESAMPLE_BANK_FLOATS:
+            return None
+        from lhotse.utils import fastcopy
+
+        rest = pending_transforms(fastcopy(cut, recording=fastcopy(cut.recording, transforms=tf[1:])), gpu_reverb)
+        return None if rest is None else (src, rest[0], rest[1])
+
+    def chain_num_samples(num_samples: int, source_rate: Optional[int], factor: float, sampling_rate: int) -> int:
+        """Samples that come out of ``[Resample(source_rate -> sr)]? [Speed(factor)]?`` for ``num_samples`` going in: per stage
+        ``ceil(new * n / orig)`` in float32 with the rates reduced by their gcd (resample.py:219-222, :309)."""
+        n = int(num_samples)
+        for src, dst in ((source_rate, sampling_rate), (None if factor == 1.0 else round(sampling_rate * factor), sampling_rate)):
+            if src is not None and int(src) != int(dst):
+                g = gcd(int(src), int(dst))
+                n = int(np.ceil(np.float32((int(dst) // g) * n / (int(src) // g))))
+        return n
+
+    def read_before_chain(cut) -> np.ndarray:
+        """``read_unperturbed`` for the whole pending chain: the segment of the ORIGINAL audio that ``Recording.load_audio`` reads for this
+        cut before it applies the recording's transforms (lhotse/audio/recording.py:412-467) -- the backward pass over ALL of them with
+        the reference's own objects (recording.py:436-444), then the same per-source reads."""
+        from lhotse.augmentation import AudioTransform  # the reference's own classes: their reverse_timestamps are the contract
+
+        rec = cut.recording
+        offset, duration = cut.start, cut.duration
+        if duration is not None and isclose(duration, rec.duration, abs_tol=1e-3):
+            duration = None  # (recording.py:415-417)
+        transforms = [t if isinstance(t, AudioTransform) else AudioTransform.from_dict(t) for t in rec.transforms or []]
+        for t in reversed(transforms):
+            offset, duration = t.reverse_timestamps(offset=offset, duration=duration, sampling_rate=rec.sampling_rate)
+        per_source = []
+        for source in rec.sources:
+            if cut.channel not in source.channels:
+                continue
+            samples = source.load_audio(offset=offset, duration=duration, force_opus_sampling_rate=rec.sampling_rate)
+            drop = [i for i, cid in enumerate(source.channels) if cid != cut.channel]
+            if drop:
+                samples = np.delete(samples, drop, axis=0)
+            per_source.append(samples)
+        audio = rec._stack_audio_channels(per_source)
+        return np.ascontiguousarray(audio.reshape(-1), dtype=np.float32)
+
+    def _read_chain_track(cut, chain, offset: int = 0, snr=None, is_ref: bool = True) -> Optional[tuple]:
+        """The 8-element track of ``FusedMiniBatch.features_of_tracks`` for a cut with a pending ``Resample`` (``chain`` =
+        ``pending_chain(cut)``), or None when the chain's output would be shorter than the cut (it would need reflect-padding: the
+        rule of ``_read_one``)."""
+        source_rate, factor, rv = chain
+        sr = cut.sampling_rate
+        raw = read_before_chain(cut)
+        want = compute_num_samples(cut.duration, sr)
+        if chain_num_samples(len(raw), source_rate, factor, sr) < want:
+            return None
+        return (raw, factor, offset, snr, is_ref, want, None if rv is None else (load_reverb_rir(rv), rv["normalize_output"]), source_rate)
+
     _RIR_CACHE: dict = {}
 
     def load_reverb_rir(spec: dict) -> np.ndarray:
@@ -435,16 +561,22 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             return None
         return raw
 
-    def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False, gpu_reverb: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
+    def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False, gpu_reverb: bool = False,
+                  gpu_resample: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
         """(samples, factor still to be applied, samples the cut must end up with) or None when the read failed and errors are suppressed.
         For a mixed cut the device will mix, and for a cut the device will reverberate, ``samples`` is the list of its loaded tracks
         (``FusedMiniBatch.features_of_tracks``); a failed track drops the cut."""
         with suppress_audio_loading_errors(enabled=suppress_errors):
-            tracks = deferred_mix(cut, gpu_reverb) if gpu_mix else None
+            tracks = deferred_mix(cut, gpu_reverb, gpu_resample=gpu_resample) if gpu_mix else None
             if tracks is not None and (gpu_speed or all(t[1] in (None, 1.0) for t in tracks)):
                 res = _read_tracks(cut, tracks)
                 if res is not None:
                     return res
+            chain = pending_chain(cut, gpu_reverb) if gpu_resample else None
+            if chain is not None and chain[0] is not None and (gpu_speed or chain[1] == 1.0):  # a Resample in front: the cut is one track
+                track = _read_chain_track(cut, chain)
+                if track is not None:
+                    return [track], 1.0, track[5]
             rv = deferred_reverb(cut, gpu_reverb)
             if rv is not None and (gpu_speed or rv[0] == 1.0):
                 raw = _read_before_transforms(cut, rv[0])
@@ -467,13 +599,17 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             return torch.from_numpy(audio), 1.0, int(audio.shape[-1])
         return None
 
+    def _has_pending_resample(cut) -> bool:
+        tf = cut.recording.transforms if type(cut).__name__ == "MonoCut" and cut.has_recording else None
+        return bool(tf) and _transform_name(tf[0]) == "Resample"
+
     def _pending_speed(cut, gpu_reverb: bool = True) -> Optional[float]:
         """1.0 for a mono cut over a recording without a pending ``Speed``, the factor when one is pending in front of nothing else or
         of a reverb the device serves, None otherwise (``pending_transforms``)."""
         p = pending_transforms(cut, gpu_reverb)
         return None if p is None else p[0]
 
-    def deferred_mix(cut, gpu_reverb: bool = True) -> Optional[List[tuple]]:
+    def deferred_mix(cut, gpu_reverb: bool = True, gpu_resample: bool = False) -> Optional[List[tuple]]:
         """The tracks of a ``MixedCut`` the device can mix -- ``[(track cut, factor, offset_samples, snr, is_reference)]`` over its audible
         tracks, ``factor`` = None for a ``PaddingCut`` track -- or None: load it the reference's way (``cut.load_audio()``).  Decided on
         the host before anything is read.  Refused: anything but a ``MixedCut`` with audio and without video or ``transforms`` of its own;
@@ -482,7 +618,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         not serve); tracks at another sampling rate; no determinable, a muted or a padding SNR
         reference track; a first track with an SNR while the reference track is another one (the reference scales it through float64,
         mixed.py:1346-1350); a mix that comes out shorter than ``cut.num_samples`` (reflect-
-        padded, mixed.py:1386-1387) or longer by lhotse's tolerance or more.  (A perturbed track that would need reflect-padding is found when
+        padded, mixed.py:1386-1387) or longer by lhotse's tolerance or more.  With ``gpu_resample`` a track may also carry a ``Resample`` in
+        front (``pending_chain``); such a track comes with two more elements, its reverb or None and its source rate.  (A perturbed track that would need reflect-padding is found when
         it is read, as for a mono cut: ``_read_tracks`` returns None and the cut is loaded the reference's way.)"""
         if type(cut).__name__ != "MixedCut" or not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
             return None
@@ -506,12 +643,22 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 return None
             if type(c).__name__ == "PaddingCut":
                 factor = None
+                chain = None
+            elif gpu_resample and _has_pending_resample(c):
+                chain = pending_chain(c, gpu_reverb)
+                if chain is None:
+                    return None
+                factor = chain[1]
             else:
+                chain = None
                 factor = _pending_speed(c, gpu_reverb)
                 if factor is None:
                     return None
             off = compute_num_samples(t.offset, sr)
             total = max(total, off + compute_num_samples(c.duration, sr))
+            if chain is not None:
+                out.append((c, factor, off, t.snr, t is ref, chain[2], chain[0]))  # (the track's reverb or None, its source rate)
+                continue
             rv = None if factor is None else deferred_reverb(c, gpu_reverb)
             out.append((c, factor, off, t.snr, t is ref) + (() if rv is None else (rv[1],)))  # (a 6th element: the track's reverb)
         diff = total - cut.num_samples
@@ -529,6 +676,11 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             n = compute_num_samples(c.duration, sr)
             if factor is None:
                 loaded.append((n, 1.0, off, snr, is_ref, n))
+            elif len(tr) > 6:  # a Resample in front of the (possibly pending) Speed and reverb
+                track = _read_chain_track(c, (tr[6], factor, tr[5]), off, snr, is_ref)
+                if track is None:
+                    return None
+                loaded.append(track)
             elif len(tr) > 5:  # a reverb behind the (possibly pending) Speed
                 raw = _read_before_transforms(c, factor)
                 if raw is None:
@@ -545,14 +697,22 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 loaded.append((np.ascontiguousarray(c.load_audio().reshape(-1), dtype=np.float32), 1.0, off, snr, is_ref, n))
         return loaded, 1.0, int(cut.num_samples)
 
+    def _reference_resamples_with_sinc() -> bool:
+        """Whether lhotse's ``Resample.__call__`` would run ``ResampleTensor`` (the sinc resampler the device implements): torchaudio
+        importable and the resampling backend ``default`` (lhotse/augmentation/torchaudio.py:108-139)."""
+        import lhotse.augmentation.torchaudio as ref  # (looked up on the module: the very name Resample.__call__ consults)
+        from lhotse.audio.resampling_backend import get_current_resampling_backend
+
+        return bool(ref.is_torchaudio_available()) and get_current_resampling_backend() == "default"
+
     class HipOnTheFlyFeatures(OnTheFlyFeatures, FusedMiniBatch):
         """Same constructor as ``OnTheFlyFeatures`` plus ``return_device`` (``None`` keeps the padded feature tensor on the
         extractor's GPU, ready for the training step; ``"cpu"`` hands back a host tensor like the reference does) and
-        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` (see the module docstring)."""
+        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` (see the module docstring)."""
 
         def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
                      gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, gpu_reverb: Optional[bool] = None,
-                     **kwargs) -> None:
+                     gpu_resample: Optional[bool] = None, **kwargs) -> None:
             if not hasattr(extractor, "extract_collated"):
                 raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
             super().__init__(extractor, *args, **kwargs)
@@ -570,6 +730,12 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             # device unless wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a
             # cut is met
             self.gpu_reverb = (not self.wave_transforms) if gpu_reverb is None else bool(gpu_reverb)
+            # and for a Resample at the front of a recording's transforms (cuts.resample(sr)): None = on the device unless wave_transforms
+            # are given AND only where the reference itself would run its sinc resampler -- without torchaudio its Resample substitutes
+            # scipy.signal.resample_poly, another filter (lhotse/augmentation/torchaudio.py:124-139), which the device does not
+            # implement; False = always Recording.load_audio; True forces the device's sinc resampler, and raises together with
+            # wave_transforms when such a cut is met
+            self.gpu_resample = (not self.wave_transforms and _reference_resamples_with_sinc()) if gpu_resample is None else bool(gpu_resample)
 
         def _read(self, cuts, pool, recording_field):
             """read_audio_from_cuts (lhotse/dataset/collation.py:541-600) with the Speed of eligible cuts left for the device."""
@@ -577,7 +743,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             on_device = recording_field is None and (
                 (self.gpu_speed_perturb and any(deferred_speed_factor(c) not in (None, 1.0) for c in cuts))
                 or (self.gpu_mix and any(type(c).__name__ == "MixedCut" for c in cuts))
-                or (self.gpu_reverb and any(deferred_reverb(c) is not None for c in cuts)))
+                or (self.gpu_reverb and any(deferred_reverb(c) is not None for c in cuts))
+                or (self.gpu_resample and any(_has_pending_resample(c) for c in cuts)))
             if not on_device:
                 audios, ok = read_audio_from_cuts(cuts, executor=pool, suppress_errors=self.fault_tolerant, recording_field=recording_field)
                 return audios, [1.0] * len(audios), [int(a.shape[-1]) for a in audios], ok
@@ -588,7 +755,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             map_fn = map if pool is None else pool.map
             audios, factors, wants, ok = [], [], [], []
             read = partial(_read_one, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix,
-                           gpu_reverb=self.gpu_reverb)
+                           gpu_reverb=self.gpu_reverb, gpu_resample=self.gpu_resample)
             for cut, res in zip(cuts, map_fn(read, cuts)):
                 if res is None:
                     continue
@@ -604,7 +771,11 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             audios, factors, wants, cuts = self._read(cuts, pool, recording_field)
             mixed = any(isinstance(a, list) for a in audios)  # (the loaded tracks of the cuts the device mixes)
             for transform in self.wave_transforms:
-                if any(isinstance(a, list) and any(len(t) > 6 for t in a) for a in audios):
+                if any(isinstance(a, list) and any(len(t) > 7 and t[7] is not None for t in a) for a in audios):
+                    raise ValueError("gpu_resample=True was requested together with wave_transforms: the transforms run on the resampled "
+                                     "samples, before the device resamples them; leave gpu_resample at its default (None: "
+                                     "Recording.load_audio whenever wave_transforms are given) or pass False")
+                if any(isinstance(a, list) and any(_reverb_of(t) is not None for t in a) for a in audios):
                     raise ValueError("gpu_reverb=True was requested together with wave_transforms: the transforms run on the reverberated "
                                      "samples, before the device convolves them; leave gpu_reverb at its default (None: "
                                      "Recording.load_audio whenever wave_transforms are given) or pass False")

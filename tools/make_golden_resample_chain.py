@@ -1,0 +1,256 @@
+#!/usr/bin/env python3
+"""
+TEST INFRASTRUCTURE -- generates tests/golden/resample_chain.npz + resample_chain.json: what the REFERENCE returns for cuts whose
+recording starts with a ``Resample`` (``cuts.resample(16000)``) over source files at 44.1, 22.05 and 8 kHz (tests/_resample_chain.py:
+``oracle.driver_corpus.pcm16`` / ``write_wav`` at the file's own rate), together with the track tables of those cuts in plain numbers.
+
+Needs the real lhotse (authoring container only):
+
+    python tools/make_golden_resample_chain.py
+
+``lhotse.augmentation.torchaudio.is_torchaudio_available`` is set to ``lambda: True`` before anything is loaded: torchaudio is not
+installed in the authoring container, and without it the reference's ``Resample.__call__`` substitutes ``scipy.signal.resample_poly``
+for its own sinc resampler (lhotse/augmentation/torchaudio.py:124-139).  The branch taken here is ``ResampleTensor``, lhotse's own
+module (lhotse/augmentation/resample.py), which needs nothing of torchaudio -- the branch every installation with torchaudio takes.
+
+Groups (fixed seeds, cuts of at most 0.5 s):
+  1 resample                [Resample] at 441:160 (44.1 kHz), 441:320 (22.05 kHz) and 1:2 (8 kHz)
+  2 resample_speed          [Resample, Speed(0.9 | 1.1)]
+  3 resample_cutmix         CutMix of resampled speech with noise resampled from 8 kHz
+  4 resample_speed_reverb   [Resample, Speed, ReverbWithImpulseResponse] (apart from the others: the reverb kernels are a separate matter)
+  5 k2                      one K2SpeechRecognitionDataset(OnTheFlyFeatures(Fbank()), cut_transforms=[PerturbSpeed(p=2/3), CutMix(p=0.5)])
+                            batch over a cut set of mixed source rates (44.1, 22.05, 8 and 16 kHz)
+
+Per cut: the track table -- file id, first sample and sample count of the read (at the file's rate), source rate, factor, offset in
+samples, SNR, reference flag, samples the track ends up with[, the reverb] --, taken from the product's own classifier and reader
+(``pending_chain``, ``deferred_mix(gpu_resample=True)``, ``_read_tracks``) with the audio backend logging which samples of which file each
+track read; the wanted sample count; the reference's Fbank features.  Groups 1-3 also: ``load_audio()``; the exact float64 chain
+(``oracle.resample_ref.resample(..., dtype=np.float64)`` per stage, the float64 mix of tests/_resample_chain.py behind it) as its float32
+difference from ``load_audio()``; the reference's own max-abs distance from that chain.
+
+Asserted for every cut of group 4: the reference's Fbank over the numpy model of the whole chain (tests/_reverb_ref.py behind
+model_track) meets the feature bar (rel-L2 <= 1e-4, max abs <= 2e-3).  Asserted for every cut of groups 1-3 (another signal is to be picked if one fails): the float32 numpy model of the device's summation
+order (tests/_resample_chain.py::model_track, the mix of tests/_mix_ref.py behind it) stays within 2 x the reference's own distance +
+2^-24 of the float64 chain; a single stage also within 1e-5 of ``load_audio()``.
+"""
+from __future__ import annotations
+
+import json
+import os
+import random
+import sys
+import tempfile
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from oracle.driver_corpus import write_wav  # noqa: E402
+
+SR = 16000
+RIR = ("rir1201", 1201, 30, 9)  # name, taps, peak, seed
+
+
+def rir_pcm16(taps: int, peak: int, seed: int) -> np.ndarray:
+    rs = np.random.RandomState(seed)
+    h = rs.randn(taps) * np.exp(-5.0 * np.abs(np.arange(taps) - peak) / taps) * 0.12
+    h[peak] = 1.0
+    return np.round(h * 24000.0).astype(np.int16)
+
+
+def main():
+    torch.manual_seed(0)
+    torch.set_num_threads(1)
+    import _resample_chain as RC
+    import _reverb_ref as RV
+    from _dropin_support import import_lhotse, install_wave_backend
+    from _mix_ref import mix_tracks
+
+    import_lhotse()
+    import lhotse.augmentation.torchaudio as ref_ta
+
+    ref_ta.is_torchaudio_available = lambda: True  # the reference's sinc branch (see the docstring)
+    install_wave_backend()
+    from lhotse import CutSet, MonoCut, Recording, SupervisionSegment
+    from lhotse.audio import AudioSource
+    from lhotse.audio.backend import get_current_audio_backend
+    from lhotse.dataset import K2SpeechRecognitionDataset
+    from lhotse.dataset.cut_transforms import CutMix, PerturbSpeed
+    from lhotse.dataset.input_strategies import OnTheFlyFeatures
+    from lhotse.features.kaldi.extractors import Fbank
+
+    import lhotse_amd.input_strategies as IS
+
+    backend = get_current_audio_backend()
+    reads = []
+    inner = backend.read_audio
+
+    def logging_read(path_or_fd, offset=0.0, duration=None, force_opus_sampling_rate=None):
+        audio, sr = inner(path_or_fd, offset=offset, duration=duration, force_opus_sampling_rate=force_opus_sampling_rate)
+        if not Path(str(path_or_fd)).stem.startswith("rir"):
+            reads.append((Path(str(path_or_fd)).stem, int(round(offset * sr)), int(audio.shape[1])))
+        return audio, sr
+
+    backend.read_audio = logging_read
+
+    def cutset(files, ids, supervised=True):
+        cuts = []
+        for f in files:
+            if f["id"] not in ids:
+                continue
+            dur = f["n"] / f["rate"]
+            rec = Recording(id=f"rec-{f['id']}", sources=[AudioSource(type="file", channels=[0], source=f["path"])], sampling_rate=f["rate"],
+                            num_samples=f["n"], duration=dur)
+            sup = SupervisionSegment(id=f"sup-{f['id']}", recording_id=rec.id, start=0.0, duration=dur, channel=0, text=f"text of {f['id']}")
+            cuts.append(MonoCut(id=f["id"], start=0, duration=dur, channel=0, recording=rec, supervisions=[sup] if supervised else []))
+        return CutSet.from_cuts(sorted(cuts, key=lambda c: ids.index(c.id)))
+
+    def table_of(cut):
+        """-> rows of the track table through the product's classifier and reader; a mono cut is a cut of one track."""
+        if type(cut).__name__ == "MixedCut":
+            tracks = IS.deferred_mix(cut, gpu_resample=True)
+            assert tracks is not None, cut
+        else:
+            ch = IS.pending_chain(cut)
+            assert ch is not None, cut
+            tracks = [(cut, ch[1], 0, None, True, ch[2], ch[0])]
+        rows = []
+        for tr in tracks:
+            del reads[:]
+            res = IS._read_tracks(cut, [tr])
+            assert res is not None
+            t, = res[0]
+            x, factor, off, snr, is_ref, n = t[:6]
+            if isinstance(x, int):
+                assert not reads
+                rows.append({"file": None, "first": 0, "count": int(x), "source_rate": None, "factor": 1.0, "offset": int(off), "snr": None, "ref": False,
+                             "num_samples": int(n)})
+                continue
+            assert len(reads) == 1 and reads[0][2] == len(x), (reads, len(x))
+            rows.append({"file": reads[0][0], "first": reads[0][1], "count": len(x), "source_rate": None if len(t) < 8 else t[7], "factor": float(factor),
+                         "offset": int(off), "snr": None if snr is None else float(snr), "ref": bool(is_ref), "num_samples": int(n)})
+            if len(t) > 6 and t[6] is not None:
+                rows[-1]["reverb"] = {"rir": RIR[0], "early_only": False, "normalize": bool(t[6][1])}
+                assert np.array_equal(t[6][0], rir_loaded)  # the product loaded what the reference loads
+        return rows
+
+    arrays, meta = {}, {"sampling_rate": SR, "groups": {}}
+    fb = Fbank()
+    with tempfile.TemporaryDirectory() as td:
+        td = Path(td)
+        files = RC.write_sources(td / "wav")
+        paths = {f["id"]: f["path"] for f in files}
+        meta["files"] = [{k: v for k, v in f.items() if k != "path"} for f in files]
+        name, taps, peak, seed = RIR
+        arrays[f"rir/{name}"] = rir_pcm16(taps, peak, seed)
+        write_wav(td / "wav" / f"{name}.wav", arrays[f"rir/{name}"])
+        rir_rec = Recording(id=f"rec-{name}", sources=[AudioSource(type="file", channels=[0], source=str(td / "wav" / f"{name}.wav"))], sampling_rate=SR,
+                            num_samples=taps, duration=taps / SR)
+        rir_loaded = rir_rec.to_cut().with_channels([0]).load_audio()[0]
+
+        def record(group, cuts, audio=True):
+            out = []
+            for i, cut in enumerate(cuts):
+                assert cut.sampling_rate == SR
+                rows = table_of(cut)
+                want = int(cut.num_samples)
+                ref_audio = cut.load_audio()[0]
+                assert ref_audio.dtype == np.float32 and len(ref_audio) == want
+                key = f"{group}/{len(out)}"
+                entry = {"tracks": rows, "want": want, "audio": False}
+                arrays[f"{key}/feats"] = fb.extract(ref_audio, SR)
+                if len(rows) == 1 and rows[0].get("reverb"):
+                    # the float32 model of the whole chain (the untruncated resampled track through the reverb's numpy statement,
+                    # tests/_reverb_ref.py) must meet the feature bar under the reference's own Fbank: another signal is picked if not
+                    x_in = RC.model_track(RC.track_samples(rows[0], paths), rows[0]["source_rate"], rows[0]["factor"])
+                    hs, shift = RV.scale_and_shift(rir_loaded)
+                    model = RV.chunked32(x_in, hs, shift, rows[0]["reverb"]["normalize"])[:want]
+                    d = fb.extract(model, SR).astype(np.float64) - arrays[f"{key}/feats"]
+                    rel, mx = float(np.linalg.norm(d) / np.linalg.norm(arrays[f"{key}/feats"])), float(np.abs(d).max())
+                    print(f"{key}: N {want} features of the model: rel-L2 {rel:.3g} max abs {mx:.3g}")
+                    if not (rel <= 1e-4 and mx <= 2e-3):
+                        print(f"{key}: NOT A FIXTURE (the model of the chain misses the feature bar under the reference's own Fbank)")
+                        del arrays[f"{key}/feats"]
+                        continue
+                if audio:
+                    mt, ref = RC.chain_tracks(entry, paths, RC.model_track)
+                    et, _ = RC.chain_tracks(entry, paths, RC.exact_track)
+                    if len(rows) == 1:
+                        assert rows[0]["offset"] == 0
+                        model, truth = mt[0][0][:want], et[0][0][:want]
+                    else:
+                        model, truth = mix_tracks(mt, ref, want), RC.exact_mix(et, ref, want)
+                    assert len(model) == len(truth) == want
+                    ref_max = float(np.abs(ref_audio.astype(np.float64) - truth).max())
+                    m_max = float(np.abs(model.astype(np.float64) - truth).max())
+                    bar = 2.0 * ref_max + 2.0 ** -24
+                    print(f"{key}: N {want} reference {ref_max:.3g} model {m_max:.3g} bar {bar:.3g}; model vs load_audio {np.abs(model - ref_audio).max():.3g}")
+                    assert m_max <= bar, (group, i, "the device's order misses the bar: pick another signal")
+                    if len(rows) == 1 and len(RC.stages(rows[0]["source_rate"], rows[0]["factor"])) == 1:
+                        assert np.abs(model - ref_audio).max() <= 1e-5, (group, i)
+                    arrays[f"{key}/audio"] = ref_audio
+                    arrays[f"{key}/exact_minus_audio"] = (truth - ref_audio.astype(np.float64)).astype(np.float32)
+                    entry.update(audio=True, reference_max_abs=ref_max)
+                out.append(entry)
+            meta["groups"][group] = out
+
+        s44a, s44b, s22a, s22b, n8a, n8b, s16a = cutset(files, [f["id"] for f in files])
+        short = lambda c, off, dur: c.truncate(offset=off, duration=dur)  # noqa: E731
+        g1 = [s44a.resample(SR), short(s44b, 0.05, 0.3).resample(SR), s22a.resample(SR), short(s22b, 0.1, 0.35).resample(SR), short(n8a, 0.0, 0.5).resample(SR)]
+        record("resample", g1)
+        record("resample_speed", [s44a.resample(SR).perturb_speed(0.9), short(s44b, 0.05, 0.3).resample(SR).perturb_speed(1.1),
+                                  s22a.resample(SR).perturb_speed(1.1), short(n8a, 0.0, 0.5).resample(SR).perturb_speed(0.9)])
+        speech = CutSet.from_cuts([s44a.resample(SR), short(s22b, 0.1, 0.35).resample(SR), s16a])
+        noise = CutSet.from_cuts([fastcopy_unsup(c).resample(SR) for c in (n8a, n8b)])
+        record("resample_cutmix", list(CutMix(noise, snr=(10, 20), p=1.0, pad_to_longest=True, random_mix_offset=True, seed=7)(speech)))
+        # candidates: one whose float32 model misses the feature bar is not a fixture (record() says which and leaves it out)
+        record("resample_speed_reverb", [s44a.resample(SR).perturb_speed(1.1).reverb_rir(rir_rec), s44b.resample(SR).perturb_speed(0.9).reverb_rir(rir_rec),
+                                         short(s22b, 0.1, 0.35).resample(SR).perturb_speed(0.9).reverb_rir(rir_rec),
+                                         s22a.resample(SR).perturb_speed(1.1).reverb_rir(rir_rec), short(s44a, 0.1, 0.3).resample(SR).perturb_speed(0.9).reverb_rir(rir_rec),
+                                         short(n8a, 0.0, 0.5).resample(SR).reverb_rir(rir_rec)], audio=False)
+        kept = {(r["source_rate"], r["factor"]) for e in meta["groups"]["resample_speed_reverb"] for r in e["tracks"]}
+        assert {f for _, f in kept} >= {0.9, 1.0, 1.1} and len({a for a, _ in kept}) >= 2, kept
+
+        k2cuts = CutSet.from_cuts([c.resample(SR) for c in (s44a, s44b, s22a, s22b, n8a)] + [s16a])
+        tf = [PerturbSpeed(factors=[0.9, 1.1], p=2 / 3, randgen=random.Random(1)),
+              CutMix(noise, snr=(10, 20), p=0.5, pad_to_longest=False, random_mix_offset=True, seed=13)]
+        ds = K2SpeechRecognitionDataset(input_strategy=OnTheFlyFeatures(Fbank()), cut_transforms=tf, return_cuts=True)
+        batch = ds[k2cuts]
+        bc = batch["supervisions"]["cut"]
+        record("k2", bc, audio=False)
+
+        def kind(c):
+            if type(c).__name__ == "MixedCut":
+                return "mixed"
+            names = [IS._transform_name(t) for t in (c.recording.transforms or [])]
+            return "+".join(n.lower() for n in names) or "plain"
+
+        meta["k2_kinds"] = [kind(c) for c in bc]
+        assert {"mixed", "resample", "resample+speed"} <= set(meta["k2_kinds"]), meta["k2_kinds"]
+        nf = batch["supervisions"]["num_frames"].numpy()
+        inputs = batch["inputs"].numpy()
+        for i in range(len(bc)):
+            arrays[f"k2/{i}/feats"] = inputs[i, : int(nf[i])]  # (the batch's rows replace the per-cut matrix: zero-padded framing)
+        arrays["k2/num_frames"] = nf
+        arrays["k2/shape"] = np.array(inputs.shape, dtype=np.int32)
+
+    out_dir = os.path.join(ROOT, "tests", "golden")
+    np.savez_compressed(os.path.join(out_dir, "resample_chain.npz"), **arrays)
+    with open(os.path.join(out_dir, "resample_chain.json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+    print("resample_chain.npz", os.path.getsize(os.path.join(out_dir, "resample_chain.npz")), "bytes;", {g: len(v) for g, v in meta["groups"].items()},
+          "k2:", meta["k2_kinds"])
+
+
+def fastcopy_unsup(cut):
+    from lhotse.utils import fastcopy
+
+    return fastcopy(cut, supervisions=[])
+
+
+if __name__ == "__main__":
+    main()
