@@ -8,7 +8,8 @@ numpy statement of the reverberation rule of ABI v7 (include/hipfeat.h, lhotse_a
 three ways: ``exact`` (float64 throughout: the truth both implementations are judged against), ``chunked32`` (the device's order: float32
 partial sums of 256 consecutive taps -- each the ascending sum of its runs of 16 taps --, added in ascending order; ``chunk=None`` = one serial chain over all taps, the
 form the accuracy bar rejects) and ``fft32`` (float32 FFTs of a 2-3-5-smooth size >= N + L - 1: the arithmetic of the CPU path, in the role
-of the reference).  ``bars`` are the two audio bars of the suite.
+of the reference).  ``bars`` are the two audio bars of the suite.  ``integer_item`` / ``integer_expected``: items whose output under the rule
+is the same float32 array in every summation order -- the yardstick of the batches that are too large for ``chunked32``.
 """
 from __future__ import annotations
 
@@ -63,6 +64,50 @@ def chunked32(x, hs, shift, normalize=False, chunk=256, run=16):
         g = _gain64(x, y)
         if g is not None:
             y = y * np.float32(g)
+    return y
+
+
+# ---- integer-valued items: a yardstick without a tolerance for batches too large to model tap by tap -----------------------------------
+# x in {-15 ... 15}, rir in {-15 ... 15} with ONE tap of 16 (the unique maximum, so shift = its index): hs = rir * 2^-15, every product and
+# every partial sum of them is a multiple of 2^-15 below 15 * 16 * L * 2^-15 -- exact in float32 while 15 * 16 * L < 2^24, in ANY summation
+# order, fused or not.  Sx and Sy are sums of multiples of 2^-30 that stay below 2^53 such units: exact in float64 in any order.  What remains of
+# the rule is the gain, (float32) sqrt((Sx / N) / (Sy / N)) in correctly rounded float64 operations, and one rounded float32 multiply.
+INT_AMPLITUDE, INT_PEAK = 15, 16
+
+
+def assert_integer_exact(n, taps):
+    """The bounds the exactness argument rests on."""
+    bound = INT_AMPLITUDE * INT_PEAK * int(taps)  # >= |y| in units of 2^-15
+    assert bound < 2 ** 24, f"{taps} taps: partial sums of integer items would leave float32's exact range"
+    assert int(n) * bound * bound < 2 ** 53, f"{n} samples x {taps} taps: sum(y^2) would leave float64's exact range"
+
+
+def integer_item(rng, n, taps, shift, normalize):
+    """-> (x, hs, shift, normalize) as the GPU tests' ``_run`` takes items; ``rng``: a numpy Generator."""
+    assert_integer_exact(n, taps)
+    assert 0 <= shift < taps
+    x = rng.integers(-INT_AMPLITUDE, INT_AMPLITUDE + 1, size=n).astype(np.float32)
+    rir = rng.integers(-INT_AMPLITUDE, INT_AMPLITUDE + 1, size=taps).astype(np.float32)
+    rir[shift] = INT_PEAK
+    hs, found = scale_and_shift(rir)
+    assert found == shift
+    return x, hs, int(shift), bool(normalize)
+
+
+def integer_expected(x, hs, shift, normalize=False):
+    """The float32 output of an integer-valued item under the rule, bit for bit, whatever the summation order -> float32 (N,)"""
+    x, hs = np.asarray(x, np.float32).reshape(-1), np.asarray(hs, np.float32).reshape(-1)
+    assert_integer_exact(len(x), len(hs))
+    assert np.array_equal(x, np.rint(x)) and np.abs(x).max(initial=0) <= INT_AMPLITUDE
+    units = hs.astype(np.float64) * 2.0 ** 15
+    assert np.array_equal(units, np.rint(units)) and np.abs(units).max(initial=0) <= INT_PEAK
+    y64 = exact(x, hs, shift)  # sums of integers x 2^-15 below 2^53: exact
+    y = y64.astype(np.float32)
+    assert np.array_equal(y.astype(np.float64), y64)
+    if normalize:
+        g = _gain64(x, y64)  # Sx, Sy exact; /, /, /, sqrt correctly rounded, as on the device
+        if g is not None:
+            y = y * np.float32(g)  # one rounded float32 multiply
     return y
 
 

@@ -12,6 +12,7 @@ from lhotse_amd import augmentation as A
 
 pytestmark = pytest.mark.gpu
 LOG_EPSILON = -23.025850929940457
+LDS_TABLE_BYTES = 24576  # kMbLdsTableBytes (tests/test_mix_abi.py::test_launch_constants_the_gpu_shapes_sit_on fails when it moves)
 
 
 def _minibatch(seed, n, factors, lo=6000, hi=90000, extra_tail=0):
@@ -39,12 +40,21 @@ def _round3_route(ex, arena, offs, lens, fac, front, want=None, zero_pad=False):
 
 
 @pytest.mark.parametrize("tables", ["kernel-arguments", "staged"])
-@pytest.mark.parametrize("n,factors", [(23, [0.9, 1.0, 1.1]), (7, [1.0]), (5, [1.1]), (180, [0.9, 1.0, 1.1])])
+@pytest.mark.parametrize("n,factors", [(23, [0.9, 1.0, 1.1]), (7, [1.0]), (5, [1.1]), (180, [0.9, 1.0, 1.1]), (700, [0.9, 1.0, 1.1])])
 def test_two_launches_equal_the_per_factor_route_bit_for_bit(monkeypatch, tables, n, factors):
+    """23 / 7 / 5 cuts: tables in the kernel arguments (or staged and copied to LDS); 180 cuts: ~11 KB of tables, copied to LDS; 700 cuts of
+    50-125 ms: more than kMbLdsTableBytes = 24576 bytes of tables (lhotse_amd/csrc/kernel_minibatch.hpp:32), searched in HBM where they
+    were staged, whichever way a smaller batch would travel."""
     if tables == "staged":
         monkeypatch.setenv("HIPFEAT_MB_NO_INLINE", "1")  # read when the bank is created
     ex = LA.HipFbank()
-    arena, offs, lens, fac, front = _minibatch(100 + n, n, factors, hi=30000 if n > 100 else 90000)
+    lo, hi = (800, 2000) if n == 700 else (6000, 30000) if n > 100 else (6000, 90000)
+    arena, offs, lens, fac, front = _minibatch(100 + n, n, factors, lo=lo, hi=hi)
+    if n == 700:
+        # the blob of hipfeat_minibatch_run: ResCut (32 B) per perturbed cut | CutDesc (32 B) per cut | int32 fill_first[n + 1] | int32 rows[n]
+        table_bytes = (32 * int((fac != 1.0).sum()) + 32 * n + 4 * (n + 1) + 4 * n + 15) & ~15
+        print(f"{n} cuts: tables {table_bytes} B")
+        assert table_bytes > LDS_TABLE_BYTES
     want_feats, want_frames, want_waves = _round3_route(ex, arena, offs, lens, fac, front)
     bank = A.HipSpeedBank(factors, 16000, "cuda")
     before = arena[:front].clone()

@@ -16,7 +16,7 @@ from _mix_ref import mix_tracks
 
 import lhotse_amd as LA
 from lhotse_amd import _lib
-from lhotse_amd.augmentation import HipMixer, mix_in_arena, mixed_tail_floats
+from lhotse_amd.augmentation import HipMixer, get_or_create_mixer, mix_in_arena, mixed_tail_floats
 from lhotse_amd.compat import LOG_EPSILON
 from lhotse_amd.input_strategies import FusedMiniBatch
 
@@ -40,8 +40,9 @@ def _rel_l2(got, want):
     return float(np.linalg.norm(np.asarray(got, dtype=np.float64) - want) / np.linalg.norm(want))
 
 
-def _mix_on_device(cuts, wants=None):
-    """cuts: [(tracks as _mix_ref.mix_tracks takes them, reference index)] -> the mixed cuts (numpy) through mix_in_arena alone."""
+def _mix_on_device(cuts, wants=None, info=None):
+    """cuts: [(tracks as _mix_ref.mix_tracks takes them, reference index)] -> the mixed cuts (numpy) through mix_in_arena alone.
+    ``info``: a list that receives the plan's info block (the two calls mix_in_arena consists of are then made here)."""
     first, so, sl, do, snrs, refs, chunks, pos = [0], [], [], [], [], [], [], 0
     for tracks, ref in cuts:
         for x, o, snr in tracks:
@@ -55,9 +56,22 @@ def _mix_on_device(cuts, wants=None):
     front = pos
     arena = torch.full((((front + 3) & ~3) + mixed_tail_floats(first, sl, do, wants),), float("nan"), dtype=torch.float32, device="cuda:0")
     arena[:front] = torch.from_numpy(np.concatenate(chunks))
-    offs, lens = mix_in_arena(arena, first, so, sl, do, snrs, refs, wants, front)
+    if info is None:
+        offs, lens = mix_in_arena(arena, first, so, sl, do, snrs, refs, wants, front)
+    else:
+        mixer = get_or_create_mixer(arena.device)
+        ticket, offs, lens, block = mixer.plan(first, so, sl, do, snrs, refs, wants, front)
+        assert int(block[1]) <= arena.numel()
+        info.append(block.copy())
+        mixer.run(ticket, arena)
     host = arena.cpu().numpy()
     assert np.array_equal(host[:front], np.concatenate(chunks))  # the sources are untouched
+    used = np.zeros(len(host), dtype=bool)
+    used[:front] = True
+    for o, n in zip(offs.tolist(), lens.tolist()):
+        assert o % 4 == 0 and o >= front and not used[o : o + n].any()
+        used[o : o + n] = True
+    assert np.isnan(host[~used]).all()  # nothing else was written
     return [host[o : o + n].copy() for o, n in zip(offs.tolist(), lens.tolist())]
 
 
@@ -161,6 +175,39 @@ def _check_against_rule(cuts, wants, got):
         assert d <= bound, (d, bound)
 
 
+# Sizes the large shapes sit on (tests/test_mix_abi.py::test_launch_constants_the_gpu_shapes_sit_on fails when one of them moves):
+INLINE_BYTES = 3328      # kMbInlineBytes, lhotse_amd/csrc/kernel_minibatch.hpp:31: tables up to this size travel in the kernel arguments
+LDS_TABLE_BYTES = 24576  # kMbLdsTableBytes, kernel_minibatch.hpp:32: staged tables up to this size are copied to LDS, larger ones searched in HBM
+MAX_WORKGROUPS = 1792    # grid_of in hipfeat_mix_run, lhotse_amd/csrc/hipfeat.hip:2329: grid = ceil(items / ceil(items / 1792))
+DESCRIPTOR_BYTES = 32    # sizeof(MixCut) = sizeof(MixTrack), lhotse_amd/csrc/kernel_mix.hpp:51: one per cut and one per track
+MIX_BLOCK, ENERGY_BLOCK = 4096, 16384  # kMixBlock, kMixEnergyBlock (kernel_mix.hpp:30-31): samples per mix item / energy item
+
+
+def _route(table_bytes):
+    return "kernel arguments" if table_bytes <= INLINE_BYTES else "LDS copy" if table_bytes <= LDS_TABLE_BYTES else "HBM"
+
+
+def _work(cuts, info):
+    """info: what the plan that ran reported -> (its energy items, its mix items, the bytes of its tables)"""
+    mix_items = sum(-(-max(o + (x if np.isscalar(x) else len(x)) for x, o, _ in tracks) // MIX_BLOCK) for tracks, _ in cuts)
+    assert int(info[3]) == mix_items
+    return int(info[2]), mix_items, DESCRIPTOR_BYTES * (len(cuts) + sum(len(tracks) for tracks, _ in cuts))
+
+
+def _check_batch(cuts, wants, got, alone=6):
+    """The rule bar for every cut; the plain sum, bit for bit, where no track carries an SNR; `alone` spread-out cuts equal to the same
+    cut mixed on its own (its launch has one or a few work items: no workgroup takes a second one, the tables travel in the arguments)."""
+    _check_against_rule(cuts, wants, got)
+    plain = 0
+    for (tracks, ref), w, g in zip(cuts, wants, got):
+        if all(snr is None for _, _, snr in tracks):
+            assert np.array_equal(g, mix_tracks(tracks, -1, w))
+            plain += 1
+    for k in sorted({int(i) for i in np.linspace(0, len(cuts) - 1, alone)}):
+        assert np.array_equal(_mix_on_device([cuts[k]], [wants[k]])[0], got[k]), k
+    return plain
+
+
 def test_determinism_and_order_independence():
     rs = np.random.RandomState(5)
     cuts = [_random_cut(rs, n, [(m, o, s)]) for n, m, o, s in [(16000, 9000, 1201, 12.5), (40000, 40000, 0, 10.0), (5000, 777, 4223, 20.0), (20001, 20000, 1, 17.0)]]
@@ -183,10 +230,15 @@ def test_shapes_that_break_work_distribution():
     many = [_random_cut(rs, int(rs.randint(1600, 16000)), [(int(rs.randint(800, 1600)), int(rs.randint(0, 800)), float(rs.uniform(10, 20)))]) for _ in range(200)]
     got = _mix_on_device(many)
     _check_against_rule(many, [-1] * len(many), got)
-    # 600 cuts of 50-100 ms: 56 KB of tables, searched where they are staged (they do not fit the LDS copy)
-    tiny = [_random_cut(rs, int(rs.randint(800, 1600)), [(int(rs.randint(100, 800)), int(rs.randint(0, 100)), float(rs.uniform(10, 20)))]) for _ in range(600)]
-    got = _mix_on_device(tiny)
-    _check_against_rule(tiny, [-1] * len(tiny), got)
+    # 1900 cuts of 50-100 ms: 178 KB of tables, searched where they are staged (they do not fit the LDS copy); 3800 energy items and
+    # 1900 mix items, both more than the 1792 workgroups of a launch: the workgroups of both kernels take a second item
+    tiny = [_random_cut(rs, int(rs.randint(800, 1600)), [(int(rs.randint(100, 800)), int(rs.randint(0, 100)), float(rs.uniform(10, 20)))]) for _ in range(1900)]
+    info = []
+    got = _mix_on_device(tiny, info=info)
+    energy_items, mix_items, table_bytes = _work(tiny, info[0])
+    print(f"tiny: {energy_items} energy items, {mix_items} mix items, tables {table_bytes} B ({_route(table_bytes)})")
+    assert energy_items == 3800 and mix_items == 1900 and min(energy_items, mix_items) > MAX_WORKGROUPS and _route(table_bytes) == "HBM"
+    _check_batch(tiny, [-1] * len(tiny), got)
     # truncation by one sample; a padding track that only lengthens the cut
     cut = ([((rs.rand(8001).astype(np.float32) - 0.5), 0, None), ((rs.rand(4000).astype(np.float32) - 0.5), 333, 15.0)], 0)
     padded = ([(2000, 0, None), ((rs.rand(3000).astype(np.float32) - 0.5), 2000, None), (9000, 0, None)], 1)
@@ -194,6 +246,50 @@ def test_shapes_that_break_work_distribution():
     assert len(got[0]) == 8000 and len(got[1]) == 9000
     _check_against_rule([cut, padded], [8000, -1], got)
     assert np.all(got[1][:2000] == 0) and np.all(got[1][5000:] == 0) and np.array_equal(got[1][2000:5000], padded[0][1][0])
+
+
+def test_long_cuts_in_the_kernel_arguments_with_more_mix_items_than_workgroups():
+    """30 cuts of 17.5 s = 69 mix items each, 2070 in all: the workgroups of the mix launch take a second item while the tables still
+    travel in the kernel arguments -- 30 cuts + 30 speech tracks + 44 noise tracks (two for 14 of the cuts, one for the others) are the
+    104 descriptors that just fit."""
+    rs = np.random.RandomState(11)
+    n = 280000
+    cuts = []
+    for k in range(30):
+        noises = [(int(rs.randint(2000, 9000)), int(rs.randint(0, n - 9000)), float(rs.uniform(5, 20))) for _ in range(2 if k % 2 == 0 and k < 28 else 1)]
+        cuts.append(_random_cut(rs, n, noises))
+    info = []
+    got = _mix_on_device(cuts, info=info)
+    energy_items, mix_items, table_bytes = _work(cuts, info[0])
+    print(f"long: {energy_items} energy items, {mix_items} mix items, tables {table_bytes} B ({_route(table_bytes)})")
+    assert mix_items == 2070 > MAX_WORKGROUPS and table_bytes == INLINE_BYTES and _route(table_bytes) == "kernel arguments"
+    assert energy_items == 30 * -(-n // ENERGY_BLOCK) + 44
+    _check_batch(cuts, [-1] * len(cuts), got)
+
+
+@pytest.mark.parametrize("descriptors,mixed,single,padding", [(104, 34, 1, 0), (105, 34, 1, 1), (768, 254, 3, 0), (769, 254, 3, 1)])
+def test_table_routes_at_their_boundaries(descriptors, mixed, single, padding):
+    """104 | 105 descriptors (cuts + tracks, 32 bytes each): the last tables that fit the kernel arguments and the first that are staged;
+    768 | 769: the last that are searched in LDS and the first that are searched in HBM.  `mixed` cuts of a speech and a noise track at
+    an SNR (3 descriptors), `single` cuts of one track (2; the plain sum applies), and `padding` = 1: a padding track on one of them."""
+    rs = np.random.RandomState(descriptors)
+    cuts = [_random_cut(rs, int(rs.randint(800, 3000)), [(int(rs.randint(100, 800)), int(rs.randint(0, 100)), float(rs.uniform(10, 20)))]) for _ in range(mixed)]
+    for k in range(single):  # spread over the list; the first one takes the padding track, which lengthens it
+        x = (rs.rand(int(rs.randint(800, 3000))).astype(np.float32) - 0.5) * 0.6
+        tracks = [(x, 0, None)] + ([(len(x) + 500, 0, None)] if padding and k == 0 else [])
+        cuts.insert((k * len(cuts)) // single + k, (tracks, -1))
+    assert len(cuts) + sum(len(t) for t, _ in cuts) == descriptors
+    info = []
+    got = _mix_on_device(cuts, info=info)
+    energy_items, mix_items, table_bytes = _work(cuts, info[0])
+    print(f"{descriptors} descriptors: {energy_items} energy items, {mix_items} mix items, tables {table_bytes} B ({_route(table_bytes)})")
+    assert table_bytes == DESCRIPTOR_BYTES * descriptors
+    assert _route(table_bytes) == {104: "kernel arguments", 105: "LDS copy", 768: "LDS copy", 769: "HBM"}[descriptors]
+    assert energy_items == 2 * mixed and mix_items == len(cuts)
+    assert _check_batch(cuts, [-1] * len(cuts), got) == single
+    if padding:
+        k = next(i for i, (t, _) in enumerate(cuts) if len(t) == 2 and np.isscalar(t[1][0]))
+        assert len(got[k]) == len(cuts[k][0][0][0]) + 500 and np.all(got[k][-500:] == 0)
 
 
 def test_gains_follow_the_reference_track_and_the_snr():

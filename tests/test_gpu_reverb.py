@@ -13,7 +13,7 @@ import _reverb_ref as R
 
 import lhotse_amd as LA
 from lhotse_amd import _lib
-from lhotse_amd.augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_arena, reverb_tail_floats, scaled_rir
+from lhotse_amd.augmentation import HipReverb, HipReverbWithImpulseResponse, get_or_create_reverb, reverb_in_arena, reverb_tail_floats, scaled_rir
 from lhotse_amd.input_strategies import FusedMiniBatch
 
 pytestmark = pytest.mark.gpu
@@ -52,8 +52,9 @@ def _grid():
     return items
 
 
-def _run(items, reverb=None, fill=float("nan")):
-    """items: [(x, hs, shift, normalize)] -> the outputs (numpy) through reverb_in_arena alone; sources / RIRs must come back unchanged."""
+def _run(items, reverb=None, fill=float("nan"), info=None):
+    """items: [(x, hs, shift, normalize)] -> the outputs (numpy) through reverb_in_arena alone; sources / RIRs must come back unchanged.
+    ``info``: a list that receives the plan's info block (the two calls reverb_in_arena consists of are then made here)."""
     chunks, so, ro, pos = [], [], [], 0
     for x, hs, _, _ in items:
         so.append(pos), chunks.append(x)
@@ -64,8 +65,15 @@ def _run(items, reverb=None, fill=float("nan")):
     lens = [len(x) for x, _, _, _ in items]
     arena = torch.full((((pos + 3) & ~3) + reverb_tail_floats(lens),), fill, dtype=torch.float32, device="cuda:0")
     arena[:pos] = torch.from_numpy(front)
-    offs = reverb_in_arena(arena, so, lens, ro, [len(h) for _, h, _, _ in items], [s for _, _, s, _ in items], [int(f) for _, _, _, f in items], pos,
-                           reverb=reverb)
+    tables = (so, lens, ro, [len(h) for _, h, _, _ in items], [s for _, _, s, _ in items], [int(f) for _, _, _, f in items], pos)
+    if info is None:
+        offs = reverb_in_arena(arena, *tables, reverb=reverb)
+    else:
+        rv = reverb if reverb is not None else get_or_create_reverb(arena.device)
+        ticket, offs, block = rv.plan(*tables)
+        assert int(block[1]) <= arena.numel()
+        info.append(block.copy())
+        rv.run(ticket, arena)
     host = arena.cpu().numpy()
     assert np.array_equal(host[:pos], front)  # sources and impulse responses are untouched
     used = np.zeros(len(host), dtype=bool)
@@ -127,6 +135,81 @@ def test_runs_repeat_and_items_do_not_depend_on_their_neighbours(grid):
     assert np.array_equal(alone, again)
     among = _run([items[1], items[30], items[50], item, items[60], items[8], items[70], items[127]])[3]
     assert np.array_equal(alone, among)
+
+
+# ---- more work items than workgroups, and the three ways the table travels -------------------------------------------------------
+# Sizes the shapes below sit on (tests/test_mix_abi.py::test_launch_constants_the_gpu_shapes_sit_on fails when one of them moves):
+INLINE_BYTES = 3328      # kMbInlineBytes, lhotse_amd/csrc/kernel_minibatch.hpp:31: a table up to this size travels in the kernel arguments
+LDS_TABLE_BYTES = 24576  # kMbLdsTableBytes, kernel_minibatch.hpp:32: a staged table up to this size is copied to LDS, a larger one searched in HBM
+MAX_WORKGROUPS = 1792    # hipfeat_reverb_run, lhotse_amd/csrc/hipfeat.hip:2498: grid = ceil(work / ceil(work / 1792))
+RV_ITEM_BYTES = 48       # sizeof(RvItem), lhotse_amd/csrc/kernel_reverb.hpp:58
+RV_BLOCK = 2048          # kRvBlock, kernel_reverb.hpp:43: outputs per work item
+
+
+def _route(num_items):
+    bytes_ = num_items * RV_ITEM_BYTES
+    return "kernel arguments" if bytes_ <= INLINE_BYTES else "LDS copy" if bytes_ <= LDS_TABLE_BYTES else "HBM"
+
+
+def _work(items, info):
+    """info: what the plan that ran reported -> (its work items, the workgroups of the two launches, the pairs of normalise flags a
+    workgroup meets on consecutive trips of its loop)"""
+    lens = [len(x) for x, _, _, _ in items]
+    work = int(info[2])
+    assert work == sum(-(-n // RV_BLOCK) for n in lens) and int(info[3]) == 2 * work
+    per_wg = max(1, -(-work // MAX_WORKGROUPS))
+    grid = -(-work // per_wg)
+    owner = np.repeat(np.arange(len(items)), [-(-n // RV_BLOCK) for n in lens])
+    flags = np.array([int(f) for _, _, _, f in items])[owner]
+    pairs = {(int(flags[w]), int(flags[w + grid])) for w in range(work - grid)}
+    return work, grid, pairs
+
+
+def _integer_batch(seed, n_of, count):
+    """`count` integer-valued items: L cycles through 1, 255, 256, 257, 300 and the shifts through 0, L / 2, L - 1; normalisation is on
+    for an irregular half of them."""
+    rng = np.random.default_rng(seed)
+    combos = [(taps, s) for taps in (1, 255, 256, 257, 300) for s in _shifts(taps)]
+    norm = rng.integers(0, 2, size=count)
+    return [R.integer_item(rng, n_of(k), *combos[k % len(combos)], bool(norm[k])) for k in range(count)]
+
+
+def _assert_exact(items, got):
+    for k, ((x, hs, shift, norm), y) in enumerate(zip(items, got)):
+        assert np.array_equal(y, R.integer_expected(x, hs, shift, norm)), (k, len(x), len(hs), shift, norm)
+
+
+@pytest.mark.parametrize("count,n,route", [(40, 100000, "kernel arguments"), (80, 50000, "LDS copy")])
+def test_workgroups_that_take_a_second_work_item(count, n, route):
+    """More than 1792 work items: every workgroup makes a second trip through both kernels' loops -- xs / hs / red / gain are re-used, the
+    partials are indexed by a work item that is not blockIdx.x, and in the gain kernel a skipped item precedes a scaled one and the other
+    way round.  Integer-valued items: the expected output is exact (tests/_reverb_ref.py), so the comparison is array_equal."""
+    items = _integer_batch(count, lambda k: n, count)
+    info = []
+    got = _run(items, info=info)  # (_run: sources untouched, nothing written outside the outputs)
+    work, grid, pairs = _work(items, info[0])
+    print(f"{count} x {n}: {work} work items over {grid} workgroups, table {count * RV_ITEM_BYTES} B ({_route(count)}), flag pairs {sorted(pairs)}")
+    assert work > MAX_WORKGROUPS and grid < work and _route(count) == route
+    assert {(0, 1), (1, 0), (1, 1), (0, 0)} <= pairs
+    _assert_exact(items, got)
+
+
+@pytest.mark.parametrize("count", [69, 70, 512, 513, 2000])
+def test_table_routes_at_their_boundaries(count):
+    """69 | 70 items: the last table that fits the kernel arguments and the first that is staged; 512 | 513: the last that is searched in
+    LDS and the first that is searched in HBM; 2000: HBM, and more work items (one per item) than workgroups."""
+    rng = np.random.default_rng(count)
+    items = [R.integer_item(rng, int(n), int(taps), int(rng.integers(0, taps)), bool(f))
+             for n, taps, f in zip(rng.integers(1, 301, size=count), rng.integers(1, 41, size=count), rng.integers(0, 2, size=count))]
+    info = []
+    got = _run(items, info=info)
+    work, grid, pairs = _work(items, info[0])
+    print(f"{count} items: {work} work items over {grid} workgroups, table {count * RV_ITEM_BYTES} B ({_route(count)})")
+    want = {69: "kernel arguments", 70: "LDS copy", 512: "LDS copy", 513: "HBM", 2000: "HBM"}[count]
+    assert _route(count) == want and work == count and (grid < work) == (count == 2000)
+    _assert_exact(items, got)
+    for k in (0, count // 4, count // 2, count - 2, count - 1):
+        assert np.array_equal(_run([items[k]])[0], got[k]), k
 
 
 def test_plan_refuses_bad_tables_and_a_ticket_runs_once():

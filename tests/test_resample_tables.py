@@ -83,6 +83,32 @@ def test_hop_tiles_follow_the_lds_budget_and_small_ratios_are_not_routed(lib):
     assert geometry(lib, 3, 16, 7)["routed"] == 1 and geometry(lib, 2, 16, 7)["routed"] == 0
 
 
+def test_gpu_ratios_reach_every_instance_and_every_path_of_the_kernel(lib):
+    """What the list of tests/_resample_rates.py is for: over the ratios tests/test_gpu_resample_mfma.py runs, `res_mfma_geometry` yields
+    every hop-tile instance of resample_mfma_kernel (the dispatch of hipfeat_resample), an even and an odd number of trips of the tap loop
+    (its two register sets take turns: behind an odd count the last fetched set is not used), and fewer, as many and more phase tiles
+    than a workgroup has waves (waves without work; waves with a second tile); one ratio's last tile is partly filled."""
+    import _resample_rates as RATES
+
+    assert len(set(RATES.ALL)) == len(RATES.ALL) == len(RATES.ROUTED) + 1 + len(RATES.EXTRA)
+    geo = {}
+    for rates in RATES.ALL:
+        _, width, orig, nw = C.sinc_resample_kernel(*rates)
+        g = geometry(lib, orig, nw, width)
+        assert g["fits"] == 1 and nw >= 16  # (what HIPFEAT_RESAMPLE_MFMA=1 needs to put a ratio on the kernel)
+        assert g["routed"] == (0 if rates in (RATES.EVEN_HOP, RATES.ONE_HOP_TILE) else 1)
+        geo[rates] = dict(g, orig=orig, nw=nw, trips=g["kwp"] // 16, tiles=g["nwp"] // 16)
+    assert {g["hop_tiles"] for g in geo.values()} == {1, 2, 4}
+    assert {g["trips"] % 2 for g in geo.values()} == {0, 1}
+    tiles = {g["tiles"] for g in geo.values()}
+    assert min(tiles) < 4 and 4 in tiles and max(tiles) > 4
+    assert any(g["nw"] % 16 for g in geo.values()) and any(g["nw"] % 16 == 0 for g in geo.values())
+    one = geo[RATES.ONE_HOP_TILE]
+    assert (one["orig"], one["nw"], one["kw"], one["kwp"], one["trips"], one["tiles"], one["hop_tiles"]) == (640, 441, 658, 672, 42, 28, 1)
+    assert (geo[RATES.ONE_PHASE_TILE]["orig"], geo[RATES.ONE_PHASE_TILE]["nw"], geo[RATES.ONE_PHASE_TILE]["tiles"]) == (49, 16, 1)
+    assert (geo[RATES.FOUR_PHASE_TILES]["orig"], geo[RATES.FOUR_PHASE_TILES]["nw"], geo[RATES.FOUR_PHASE_TILES]["tiles"]) == (147, 64, 4)
+
+
 def test_stand_alone_program_of_the_shim(tmp_path):
     exe = str(tmp_path / "restab")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-DRESAMPLE_TABLES_MAIN", SHIM, "-o", exe])

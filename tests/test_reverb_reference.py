@@ -62,6 +62,36 @@ def test_goldens_reload_and_the_rule_reproduces_the_stored_truth(tmp_path, golde
     assert n_audio >= 5
 
 
+@pytest.mark.parametrize("n,taps", [(300, 257), (2049, 300), (600, 513)])
+def test_integer_valued_items_come_out_the_same_in_every_summation_order(n, taps):
+    """The yardstick of the large GPU batches (tests/test_gpu_reverb.py): for integer-valued items the float64 form, the device's order and one
+    serial float32 chain are the same numbers, and the normalised output is float32(exact) x float32(gain), one rounded multiply."""
+    rng = np.random.default_rng(1000 * n + taps)
+    for shift in sorted({0, taps // 2, taps - 1}):
+        x, hs, s, _ = R.integer_item(rng, n, taps, shift, False)
+        assert s == shift and x.dtype == hs.dtype == np.float32 and np.abs(x).max() == 15 and hs[shift] == np.float32(16 * 2.0 ** -15)
+        want = R.integer_expected(x, hs, shift, False)
+        assert want.dtype == np.float32 and np.array_equal(want.astype(np.float64), R.exact(x, hs, shift, False))
+        assert np.array_equal(want, R.chunked32(x, hs, shift, False))
+        assert np.array_equal(want, R.chunked32(x, hs, shift, False, chunk=None))
+        scaled = R.integer_expected(x, hs, shift, True)
+        gain = np.float32(np.sqrt((np.sum(x.astype(np.float64) ** 2) / n) / (np.sum(want.astype(np.float64) ** 2) / n)))
+        assert np.array_equal(scaled, want * gain) and not np.array_equal(scaled, want)
+        assert np.array_equal(scaled, R.chunked32(x, hs, shift, True))
+        # ... and it is the rule: within one float32 rounding of the float64 form scaled by the float64 gain
+        assert np.abs(scaled - R.exact(x, hs, shift, True)).max() <= 2.0 ** -23 * np.abs(scaled).max()
+
+
+def test_integer_items_refuse_sizes_that_would_not_be_exact():
+    R.assert_integer_exact(100000, 300)
+    with pytest.raises(AssertionError):
+        R.assert_integer_exact(10, 2 ** 24 // (15 * 16) + 1)  # 15 * 16 * L >= 2^24
+    with pytest.raises(AssertionError):
+        R.assert_integer_exact(2 ** 31, 300)                  # sum(y^2) past 2^53 units
+    with pytest.raises(AssertionError):
+        R.integer_expected(np.full(8, 0.5, np.float32), np.ones(1, np.float32) * R.SCALE, 0)
+
+
 # ---- under the real lhotse ---------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def env(tmp_path_factory):
