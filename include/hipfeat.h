@@ -40,6 +40,9 @@ extern "C" {
 #else
 #define HIPFEAT_API
 #endif
+/* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
+ * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES next to _SIGNATURES). */
+#define HIPFEAT_LEVEL_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -380,6 +383,50 @@ HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* reverb, int64_t n
                                                const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
                                                const int32_t* h_normalize, int64_t tail_start, int64_t* h_out_offsets, int64_t* h_info);
 HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* reverb, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
+
+/* ---- level changes of cuts on the device (additive to ABI v8) ------------------------------------------------------ */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_level_*; the version number did not change because nothing that existed
+ * changed (a caller that needs them looks the symbols up, or catches the loader's error).
+ *
+ * Volume.__call__ (lhotse/augmentation/torchaudio.py:395-406; what PerturbVolume / cut.perturb_volume append) multiplies the float32
+ * samples by (float)factor.  Clipping.__call__ (lhotse/augmentation/clipping.py:28-61; what the Clipping cut transform /
+ * cut.clip_amplitude append) takes p = max |x| over everything it is given, leaves the samples alone when p == 0 or
+ * 20 * log10(p) < -96, and otherwise computes [x / p] [* g] clip(., -1, 1) | tanh [/ g] [* p] with float32 array operations.
+ * Here the cuts of a whole mini-batch lie in ONE device arena and two stream-ordered launches -- max |x| per item, then the ops --
+ * change them where they lie or write them elsewhere; no value visits the host in between.
+ * An ITEM is h_src_len[i] samples at h_src_offset[i], written to h_dst_offset[i] (== h_src_offset[i]: in place), with a PROGRAM of
+ * 1 ... 4 ops [h_op_first[i], h_op_first[i + 1]) of the three op tables (h_op_first[0] = 0), applied to every sample in order:
+ *   h_op_kind 0 = SCALE: y = x * h_op_value (one rounded float32 product); h_op_flags 0.
+ *   h_op_kind 1 = CLIP:  h_op_flags = 1 (hard; else soft) | 2 (normalize) | 4 (use the gain: the caller sets it when |gain_db| >= 0.1),
+ *     h_op_value = g = (float)10^(gain_db / 20).  p = max |x| of the op's INPUT over the item: the peak of the source pushed through the
+ *     SCALE ops in front with the same float32 products, p = fl(fl(peak * |f1|) * |f2|), which equals the maximum of the scaled samples
+ *     exactly (rounding is monotone and odd).  p == 0 or p < 0x1.09e69ep-16 (the float32 values for which the reference's dB test says
+ *     silence): y = x.  Else, float32, in this order: x / p if normalize; * g if gain; clamp(., -1, 1) when hard, else the float64 tanh
+ *     rounded once to float32; / g if gain; * p if normalize.  Divisions are IEEE divisions, never products with a reciprocal.
+ *     SCALE and hard CLIP reproduce the reference bit for bit; a NaN sample does not raise the peak (in the reference it turns the
+ *     whole output into NaN).  A program holds at most one CLIP.
+ *   Results are bit-identical from run to run and do not depend on the other items of the batch.
+ *
+ * hipfeat_level_create / _destroy: the object that owns the workspace (partial peaks, staged table) on `device`; calls are serialised
+ * inside, up to 16 plans may be outstanding, destroy waits for the work it enqueued.
+ * hipfeat_level_plan (host only).  h_info[4] = {ticket, floats the arena must hold, peak work items, apply work items}.  A bad table (a
+ * negative offset, h_src_len < 1 -- np.max of nothing raises in the reference too --, a program of 0 or more than 4 ops, an unknown
+ * kind or flag, a gain that is not positive and finite, a destination that overlaps its own source in part or another item's source
+ * or destination, a 17th plan while 16 are planned and not yet run) returns HIPFEAT_ERR_INVALID, a second CLIP in a program
+ * HIPFEAT_ERR_UNSUPPORTED, and plans nothing.  num_items == 0 is a valid plan whose run launches nothing.
+ * hipfeat_level_run enqueues the launches of a planned level change on `stream` (a ticket runs once; the peak launch is left out when
+ * no program has a CLIP); an unknown ticket or an arena smaller than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.  A ticket
+ * is consumed when its launches have been enqueued: after a HIPFEAT_ERR_HIP from an allocation or the table copy in front of them it can
+ * be run again.
+ */
+typedef struct hipfeat_level hipfeat_level;
+HIPFEAT_LEVEL_API hipfeat_status hipfeat_level_create(int32_t device, hipfeat_level** level);
+HIPFEAT_LEVEL_API hipfeat_status hipfeat_level_destroy(hipfeat_level* level);
+HIPFEAT_LEVEL_API hipfeat_status hipfeat_level_plan(hipfeat_level* level, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                              const int64_t* h_dst_offset, const int64_t* h_op_first, const int32_t* h_op_kind,
+                                              const float* h_op_value, const int32_t* h_op_flags, int64_t* h_info);
+HIPFEAT_LEVEL_API hipfeat_status hipfeat_level_run(hipfeat_level* level, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

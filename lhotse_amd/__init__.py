@@ -16,6 +16,7 @@ from .extractors import (  # noqa: F401
 )
 
 from .augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_arena, reverb_tail_floats  # noqa: F401,E402
+from .augmentation import HipClipping, HipLevel, HipVolume, get_or_create_level, level_in_arena  # noqa: F401,E402
 from .augmentation import resample_in_arena, resample_layout, resampled_tail_floats  # noqa: F401,E402
 from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
 
@@ -74,6 +75,11 @@ __all__ = [
     "HipReverbWithImpulseResponse",
     "reverb_in_arena",
     "reverb_tail_floats",
+    "HipLevel",
+    "HipVolume",
+    "HipClipping",
+    "get_or_create_level",
+    "level_in_arena",
     "resample_in_arena",
     "resample_layout",
     "resampled_tail_floats",

@@ -119,6 +119,23 @@ _SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
 }
 
+# Entry points added to ABI v8 without a bump (HIPFEAT_LEVEL_API in the header), kept apart from the v8 set.
+_LEVEL_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_level_create": ("int", ["int32_t", "hipfeat_level**"]),
+    "hipfeat_level_destroy": ("int", ["hipfeat_level*"]),
+    "hipfeat_level_plan": (
+        "int",
+        ["hipfeat_level*", "int64_t", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "const int32_t*", "const float*",
+         "const int32_t*", "int64_t*"],
+    ),
+    "hipfeat_level_run": ("int", ["hipfeat_level*", "int64_t", "float*", "int64_t", "void*"]),
+}
+
+
+def _signature(name: str) -> Tuple[str, List[str]]:
+    return _SIGNATURES[name] if name in _SIGNATURES else _LEVEL_SIGNATURES[name]
+
+
 # numpy mirror of `struct hipfeat_config` (include/hipfeat.h); field order and sizes must match.
 CONFIG_DTYPE = np.dtype(
     [
@@ -173,7 +190,7 @@ class _CtypesBackend:
     def __init__(self, path: str):
         self.dll = ctypes.CDLL(path)
         self.fns = {}
-        for name, (ret, args) in _SIGNATURES.items():
+        for name, (ret, args) in list(_SIGNATURES.items()) + list(_LEVEL_SIGNATURES.items()):
             fn = getattr(self.dll, name)  # AttributeError here == a symbol the header declares is missing
             fn.restype = ctypes.c_char_p if ret == "const char*" else self._SCALARS[ret]
             fn.argtypes = [ctypes.c_void_p if _is_ptr(a) else self._SCALARS[a] for a in args]
@@ -203,20 +220,26 @@ class _CffiBackend:
             s = line.strip()
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
-            decl.append(line.replace("HIPFEAT_API ", ""))
+            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}
 
     def call(self, name: str, *args):
-        sig = _SIGNATURES[name][1]
+        sig = _signature(name)[1]
         conv = []
         for a, t in zip(args, sig):
             if _is_ptr(t):
                 conv.append(self.ffi.NULL if a is None else self.ffi.cast(t, int(a)))
             else:
                 conv.append(a)
-        return self.fns[name](*conv)
+        return self._fn(name)(*conv)
+
+    def _fn(self, name: str):
+        fn = self.fns.get(name)
+        if fn is None:  # an entry point of _LEVEL_SIGNATURES: looked up at its first use
+            fn = self.fns[name] = getattr(self.dll, name)
+        return fn
 
     def bound(self, name: str):
         return lambda *args: self.call(name, *args)

@@ -772,3 +772,172 @@ class HipReverbWithImpulseResponse(AudioTransform):
     def reverse_timestamps(self, offset: Seconds, duration: Optional[Seconds], sampling_rate: Optional[int]) -> Tuple[Seconds, Optional[Seconds]]:
         """The output is shifted to the input's length: timestamps are unchanged (rir.py:155-166)."""
         return offset, duration
+
+
+# ---- level changes (PerturbVolume, Clipping) in the same arena ------------------------------------------------------------------
+LEVEL_MAX_OPS = 4  # ops of one program (kLvMaxOps)
+_LV_SCALE, _LV_CLIP = 0, 1
+_LV_HARD, _LV_NORMALIZE, _LV_USE_GAIN = 1, 2, 4
+
+
+def level_op_tables(programs) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``programs`` -- per item a list of ``("volume", factor)`` / ``("clip", hard, gain_db, normalize)`` -- as the op tables of
+    ``hipfeat_level_plan``: ``(op_first[n + 1], kind, value, flags)``.  ``g = (float)10**(gain_db / 20)`` and ``|gain_db| >= 0.1``
+    are decided here, with the reference's own expressions (lhotse/augmentation/clipping.py:44-45)."""
+    first, kind, value, flags = [0], [], [], []
+    for prog in programs:
+        for op in prog:
+            if op[0] == "volume" and len(op) == 2:
+                kind.append(_LV_SCALE), value.append(np.float32(op[1])), flags.append(0)
+            elif op[0] == "clip" and len(op) == 4:
+                _, hard, gain_db, normalize = op
+                use_gain = abs(gain_db) >= 0.1
+                kind.append(_LV_CLIP), value.append(np.float32(10 ** (gain_db / 20.0)))
+                flags.append((_LV_HARD if hard else 0) | (_LV_NORMALIZE if normalize else 0) | (_LV_USE_GAIN if use_gain else 0))
+            else:
+                raise ValueError(f"unknown level op {op!r}: expected ('volume', factor) or ('clip', hard, gain_db, normalize)")
+        first.append(len(kind))
+    return _lib.i64(first), np.asarray(kind, dtype=np.int32), np.asarray(value, dtype=np.float32), np.asarray(flags, dtype=np.int32)
+
+
+class HipLevel:
+    """The device half of ``Volume.__call__`` (lhotse/augmentation/torchaudio.py:395-406) and ``Clipping.__call__``
+    (lhotse/augmentation/clipping.py:28-61) for a packed mini-batch: ``hipfeat_level`` (include/hipfeat.h) owns the workspace of the two
+    launches -- max |x| per item, then the ops.  One object per device (``get_or_create_level``); it may be shared by threads."""
+
+    def __init__(self, device: Union[str, torch.device, None] = None):
+        self.lib = _lib.load()
+        self.handle = 0
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.HipFeatError(1, f"HipLevel runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        out = np.zeros(1, dtype=np.uint64)
+        self.lib.check("hipfeat_level_create", int(self.device.index), _lib.addr(out))
+        self.handle = int(out[0])
+        self._lock = threading.Lock()
+
+    def plan(self, src_offsets, src_lens, programs, dst_offsets=None):
+        """Host only -> (ticket, info = [ticket, arena floats needed, peak work items, apply work items])."""
+        so, sl = _lib.i64(src_offsets), _lib.i64(src_lens)
+        do = so if dst_offsets is None else _lib.i64(dst_offsets)
+        first, kind, value, flags = level_op_tables(programs)
+        n = len(so)
+        if not (len(sl) == len(do) == len(first) - 1 == n):
+            raise ValueError("level tables: one entry per item in every table")
+        info = np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_level_plan", self.handle, n, _lib.addr(so), _lib.addr(sl), _lib.addr(do), _lib.addr(first), _lib.addr(kind), _lib.addr(value),
+                           _lib.addr(flags), _lib.addr(info))
+        return int(info[0]), info
+
+    def run(self, ticket: int, arena: torch.Tensor, stream: Optional[int] = None) -> None:
+        assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
+        with torch.cuda.device(self.device):
+            self.lib.check("hipfeat_level_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
+
+    def close(self):
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_level_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_levels: Dict[int, HipLevel] = {}
+
+
+def get_or_create_level(device: Union[str, torch.device, None] = None) -> HipLevel:
+    dev = torch.device("cuda" if device is None else device)
+    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    with _cache_lock:
+        r = _levels.get(int(index))
+        if r is None:
+            r = _levels[int(index)] = HipLevel(torch.device(dev.type, index))
+        return r
+
+
+def level_in_arena(arena: torch.Tensor, src_offsets, src_lens, programs, dst_offsets=None, level: Optional[HipLevel] = None) -> np.ndarray:
+    """Scale and clip runs of a device-resident packed mini-batch (``Volume`` / ``Clipping``); the counterpart of
+    ``perturb_speed_in_arena`` / ``reverb_in_arena`` / ``mix_in_arena``.
+
+    Item ``i`` takes the ``src_lens[i]`` samples at ``src_offsets[i]`` of ``arena`` (ONE float32 device buffer) through ``programs[i]``
+    -- 1 to 4 ops ``("volume", factor)`` / ``("clip", hard, gain_db, normalize)``, at most one clip, whose peak is taken over the whole
+    item -- and writes them at ``dst_offsets[i]`` (``None``: in place).  A destination may be its item's source, and may overlap
+    nothing else.  Returns the destination offsets.  Two launches on the current stream (one when no program clips, none for no items),
+    no device -> host copy, bit-identical from run to run."""
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    so = _lib.i64(src_offsets)
+    do = so.copy() if dst_offsets is None else _lib.i64(dst_offsets)
+    if len(so) == 0:
+        return do
+    sl = _lib.i64(src_lens)
+    need = int((np.maximum(so, do) + sl).max()) if len(sl) == len(so) == len(do) else 0
+    if need > arena.numel():  # (before anything is planned: a plan that is never run would stay outstanding)
+        raise ValueError(f"arena too small: {arena.numel()} floats, the items reach to {need}")
+    if level is None:
+        level = get_or_create_level(arena.device)
+    ticket, info = level.plan(so, sl, programs, do)
+    assert int(info[1]) == need
+    level.run(ticket, arena)
+    return do
+
+
+def _level_call(samples: Union[np.ndarray, torch.Tensor], program, device: str) -> Union[np.ndarray, torch.Tensor]:
+    """One array (all its channels: ONE item, as ``np.max(np.abs(samples))`` takes the peak over all of them) through ``program``."""
+    is_tensor = isinstance(samples, torch.Tensor)
+    x = samples if is_tensor else torch.from_numpy(np.ascontiguousarray(samples))
+    if x.dtype != torch.float32:
+        raise TypeError(f"expected float32 samples, got {x.dtype}")
+    if x.numel() == 0:
+        raise ValueError("zero-size array: the reference's np.max raises here too")
+    dev = torch.device(device)
+    dev = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index) if dev.type == "cuda" else dev
+    arena = torch.empty(x.numel(), dtype=torch.float32, device=dev)  # (a copy: the caller's samples stay as they are)
+    arena.copy_(x.reshape(-1))
+    level_in_arena(arena, [0], [arena.numel()], [program])
+    out = arena.view(x.shape)
+    return out.to(samples.device) if is_tensor else out.cpu().numpy()
+
+
+@dataclass
+class HipVolume(AudioTransform):
+    """Volume perturbation (``sox vol``) on the GPU; drop-in for ``lhotse.augmentation.Volume`` (torchaudio.py:394-418): the samples times
+    ``(float)factor``, bit for bit."""
+
+    factor: float
+    device: str = "cuda"
+
+    def __call__(self, samples: Union[np.ndarray, torch.Tensor], sampling_rate: int) -> Union[np.ndarray, torch.Tensor]:
+        return _level_call(samples, [("volume", self.factor)], self.device)
+
+    def reverse_timestamps(self, offset: Seconds, duration: Optional[Seconds], sampling_rate: Optional[int]) -> Tuple[Seconds, Optional[Seconds]]:
+        """Volume perturbation changes no timing (torchaudio.py:408-418)."""
+        return offset, duration
+
+
+@dataclass
+class HipClipping(AudioTransform):
+    """Clipping / saturation on the GPU; drop-in for ``lhotse.augmentation.Clipping`` (clipping.py:9-67): same fields and defaults; the
+    peak is taken over all channels of the array.  Hard clipping reproduces the reference bit for bit; soft clipping is the float64
+    ``tanh`` rounded once."""
+
+    hard: bool = False
+    gain_db: float = 0.0
+    normalize: bool = True
+    device: str = "cuda"
+
+    def __call__(self, samples: Union[np.ndarray, torch.Tensor], sampling_rate: int) -> Union[np.ndarray, torch.Tensor]:
+        return _level_call(samples, [("clip", self.hard, self.gain_db, self.normalize)], self.device)
+
+    def reverse_timestamps(self, offset, duration, sampling_rate):
+        """Clipping changes no timing (clipping.py:63-67)."""
+        return offset, duration

@@ -200,3 +200,8 @@ def make_slaney_mel(num_filters: int, fft: int, sampling_rate: int, fmin: float 
     tri = np.maximum(0.0, np.minimum(rising, falling))
     tri *= (2.0 / (edges[2:] - edges[:-2]))[:, None]
     return np.ascontiguousarray(tri.astype(np.float32).T)
+
+
+# Clipping treats a peak p with ``20 * np.log10(p) < -96`` (float32) as silence (lhotse/augmentation/clipping.py:36).  On float32 peaks that
+# is ``p < SILENCE_PEAK``: the smallest float32 for which the expression is False (kLvSilencePeak of csrc/level_tables.hpp).
+SILENCE_PEAK = np.float32(float.fromhex("0x1.09e69ep-16"))  # 1.5848926e-05

@@ -28,6 +28,7 @@
 #include "kernel_minibatch.hpp"
 #include "kernel_mix.hpp"
 #include "kernel_reverb.hpp"
+#include "kernel_level.hpp"
 #include "kernel_specaug.hpp"
 #include "kernel_whisper2.hpp"
 #include "kernel_whisper3.hpp"
@@ -2515,6 +2516,157 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int
   hipError_t e2 = hipEventRecord(s.ev, st);
   s.busy = (e2 == hipSuccess);
   if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "reverb launch failed: %s", hipGetErrorName(e1));
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Level changes on the device (Volume, Clipping): peak + apply in two launches (kernel_level.hpp; the table: level_tables.hpp)
+// --------------------------------------------------------------------------------------
+constexpr int kLvSlots = 16;
+
+struct LvSlot {
+  int64_t ticket = -1;
+  bool planned = false;
+  std::vector<LvItem> items;
+  int64_t work_items = 0, arena_need = 0;
+  void* h = nullptr;  // pinned staging (a table that does not fit the kernel arguments)
+  void* d = nullptr;  // device: the staged table, then the partial peaks
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool busy = false;
+};
+
+struct hipfeat_level {
+  int device = 0;
+  bool allow_inline = true;
+  std::mutex mu;
+  LvSlot slots[kLvSlots];
+  int64_t next_ticket = 0;
+};
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_level_create(int32_t device, hipfeat_level** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "level pointer is NULL");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  hipfeat_level* l = new (std::nothrow) hipfeat_level();
+  if (!l) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  l->device = device;
+  l->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
+  *out = l;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_level_destroy(hipfeat_level* l) {
+  if (!l) return HIPFEAT_OK;
+  DeviceGuard g(l->device);
+  for (auto& s : l->slots) {
+    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    if (s.ev) (void)hipEventDestroy(s.ev);
+  }
+  delete l;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_level_plan(hipfeat_level* lv, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                         const int64_t* h_dst_offset, const int64_t* h_op_first, const int32_t* h_op_kind,
+                                                         const float* h_op_value, const int32_t* h_op_flags, int64_t* h_info) {
+  if (!lv || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  // (validated into a local first: a refused table leaves the outstanding plans as they were)
+  LvPlan p = build_level_plan(num_items, h_src_offset, h_src_len, h_dst_offset, h_op_first, h_op_kind, h_op_value, h_op_flags);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(lv->mu);
+  if (lv->slots[lv->next_ticket % kLvSlots].planned)  // (never drop a live plan: its ticket would fail at run)
+    return fail(HIPFEAT_ERR_INVALID, "%d planned level changes are outstanding: run ticket %lld first", kLvSlots, (long long)lv->slots[lv->next_ticket % kLvSlots].ticket);
+  const int64_t ticket = lv->next_ticket++;
+  LvSlot& s = lv->slots[ticket % kLvSlots];
+  s.ticket = ticket;
+  s.items.swap(p.items);
+  s.work_items = p.work_items;
+  s.arena_need = p.arena_need;
+  s.planned = true;
+  h_info[0] = ticket;
+  h_info[1] = s.arena_need;
+  h_info[2] = p.peak_items;
+  h_info[3] = s.work_items;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_API hipfeat_status hipfeat_level_run(hipfeat_level* lv, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
+  if (!lv) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(lv->mu);
+  LvSlot& s = lv->slots[((ticket % kLvSlots) + kLvSlots) % kLvSlots];
+  if (s.ticket != ticket || !s.planned)
+    return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned level change (at most %d plans may be outstanding)", (long long)ticket, kLvSlots);
+  if (s.items.empty()) {  // nothing to do: no launch
+    s.planned = false;
+    return HIPFEAT_OK;
+  }
+  if (!d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (arena_floats < s.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the items reach to %lld", (long long)arena_floats, (long long)s.arena_need);
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
+  DeviceGuard g(lv->device);  // (the ticket stays planned until its launches are enqueued: a failed allocation or copy below leaves it to be run again)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = s.items.size() * sizeof(LvItem);  // (a multiple of 16)
+  const size_t part_bytes = (size_t)s.work_items * sizeof(float);
+  const bool inl = lv->allow_inline && bytes <= (size_t)kMbInlineBytes;
+  if (s.busy) {  // the launches that used this slot's device memory last time
+    HIP_TRY(hipEventSynchronize(s.ev));
+    s.busy = false;
+  }
+  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  const size_t dev_bytes = bytes + part_bytes;
+  if (s.cap < dev_bytes) {
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    s.h = s.d = nullptr;
+    s.cap = 0;
+    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
+    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&s.d, cap));
+    s.cap = cap;
+  }
+  LvInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
+  LvHeader& h = args.h;
+  h.arena = d_arena;
+  h.partials = reinterpret_cast<float*>(static_cast<unsigned char*>(s.d) + bytes);
+  h.tables = nullptr;
+  h.num_items = (int32_t)s.items.size();
+  h.work_items = (int32_t)s.work_items;
+  h.table_bytes = (int32_t)bytes;
+  h.pad = 0;
+  // a few workgroups per CU take the work items round-robin (as hipfeat_reverb_run)
+  const int64_t per_wg = std::max<int64_t>(1, (s.work_items + 1791) / 1792);
+  const unsigned grid = (unsigned)std::max<int64_t>(1, (s.work_items + per_wg - 1) / per_wg);
+  const size_t dyn = bytes <= (size_t)kMbLdsTableBytes ? bytes : 0;
+  bool any_clip = false;
+  for (const LvItem& it : s.items) any_clip = any_clip || it.clip_at >= 0;
+  hipError_t e1 = hipSuccess;
+  if (inl) {
+    std::memcpy(args.blob, s.items.data(), bytes);
+    if (any_clip) hipLaunchKernelGGL(level_peak_inline_kernel, dim3(grid), dim3(256), 0, st, args);
+    hipLaunchKernelGGL(level_apply_inline_kernel, dim3(grid), dim3(256), 0, st, args);
+    e1 = hipGetLastError();
+  } else {
+    std::memcpy(s.h, s.items.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+    h.tables = static_cast<const unsigned char*>(s.d);
+    if (any_clip) hipLaunchKernelGGL(level_peak_kernel, dim3(grid), dim3(256), dyn, st, h);
+    hipLaunchKernelGGL(level_apply_kernel, dim3(grid), dim3(256), dyn, st, h);
+    e1 = hipGetLastError();
+  }
+  s.planned = false;  // enqueued (or refused by the runtime at launch): the ticket has run
+  hipError_t e2 = hipEventRecord(s.ev, st);
+  s.busy = (e2 == hipSuccess);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "level launch failed: %s", hipGetErrorName(e1));
+  if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
+    (void)hipStreamSynchronize(st);
+    return fail(HIPFEAT_ERR_HIP, "level: hipEventRecord failed: %s (the launches were enqueued and have been waited for)", hipGetErrorName(e2));
+  }
   return HIPFEAT_OK;
 }
 

@@ -52,6 +52,16 @@ source rate (``read_before_chain``), and the chain runs on the device: the rate 
 its output, then reverb and mix as before.  ``pending_chain`` says which cuts qualify; a ``Resample`` that is not first or not alone,
 the ``sox`` backend and a filter bank of more than 2^20 floats keep the reference's path.
 
+Level changes.  ``PerturbVolume`` appends a ``Volume`` to the recording's transforms, the ``Clipping`` cut transform / ``cut.clip_amplitude`` a
+``Clipping`` -- with ``oversampling=k`` between ``Resample(sr -> k sr)`` and ``Resample(k sr -> sr)`` (lhotse/audio/recording.py:937-975).  With
+``gpu_level`` (default: on unless ``wave_transforms`` are given) a mono recording whose transforms are ``[Resample]? [Speed]? L? [Reverb]? L?``, L =
+1 ... 4 such ops with at most one ``Clipping``, is read in front of all of them and scaled / clipped on the device, in place, behind the speed
+pass and on both sides of the reverb (``lhotse_amd.augmentation.level_in_arena``: ``Volume`` and hard ``Clipping`` bit for bit, soft ``Clipping`` as
+the float64 tanh rounded once); the oversampled form takes two more resample passes and needs the resampling route.  ``pending_level_chain`` says
+which cuts qualify -- a new rule: the older ones answer for such cuts what they always did --, ``deferred_mix(..., gpu_level=True)`` lets such
+tracks into a device mix.  A level op in front of the ``Speed``, more than 4 ops or two ``Clipping``s in a block and k outside 2 ... 8 keep the
+reference's path.
+
 Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the class does not.
 """
 from __future__ import annotations
@@ -106,6 +116,13 @@ def _reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts
     return reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start)
 
 
+def _level_in_arena(arena, src_offsets, src_lens, programs):
+    """(indirection for the CPU stand-in of the tests)"""
+    from .augmentation import level_in_arena
+
+    return level_in_arena(arena, src_offsets, src_lens, programs)
+
+
 def _is_plain(tracks) -> bool:
     """One track with samples that starts at 0 and is not scaled: the cut IS that track (a MonoCut, speed-perturbed or not; when the
     track carries a reverb, the cut is the reverb's output)."""
@@ -121,6 +138,38 @@ def _source_rate_of(track, sampling_rate: int) -> Optional[int]:
     """The optional 8th element of a track: the rate its samples are at, when that is not the mini-batch's (a pending ``Resample``)."""
     rate = track[7] if len(track) > 7 else None
     return None if rate is None or int(rate) == int(sampling_rate) else int(rate)
+
+
+def _level_of(track):
+    """The optional 9th element of a track: ``(block in front of the reverb, block behind it)`` or None.  A block is None or a list of
+    steps ``("level", [ops])`` / ``("up", k)`` / ``("down", k)`` (``pending_level_chain``)."""
+    lv = track[8] if len(track) > 8 else None
+    return None if lv is None or (not lv[0] and not lv[1]) else lv
+
+
+def _level_steps(arena, offs, lens, blocks, sr: int, tail: int):
+    """Run one block per track (``blocks[i]`` = its steps or None) over the tracks at ``offs`` / ``lens``: step s of every track that has
+    one, s = 0, 1, ... -- the level steps of a round in ONE ``level_in_arena`` call, in place; its rate steps (the oversampling around
+    a ``Clipping``: sr -> k sr, k n samples, and back, n samples) in one ``resample_in_arena`` call that writes behind ``tail``.
+    ``arena`` None: host arithmetic only.  -> (offsets, lengths, the first free float behind what was written, 16-byte aligned)."""
+    from .augmentation import resample_layout
+
+    offs, lens = np.array(offs, dtype=np.int64), np.array(lens, dtype=np.int64)
+    tail = (int(tail) + 3) & ~3
+    for s in range(max((len(b) for b in blocks if b), default=0)):
+        step = [b[s] if b and s < len(b) else None for b in blocks]
+        idx = [i for i, st in enumerate(step) if st is not None and st[0] == "level"]
+        if idx and arena is not None:
+            _level_in_arena(arena, offs[idx], lens[idx], [step[i][1] for i in idx])
+        ratios = [None if st is None or st[0] == "level" else ((sr, sr * int(st[1])) if st[0] == "up" else (sr * int(st[1]), sr)) for st in step]
+        if any(r is not None for r in ratios):
+            if arena is None:
+                offs, lens, tail = resample_layout(offs, lens, ratios, tail)
+            else:
+                end = resample_layout(offs, lens, ratios, tail)[2]
+                offs, lens = _resample_in_arena(arena, offs, lens, ratios, tail)
+                tail = end
+    return offs, lens, tail
 
 
 class FusedMiniBatch:
@@ -162,7 +211,12 @@ class FusedMiniBatch:
         ``Speed``, lhotse/augmentation/torchaudio.py:86-139 with the sinc backend) and are resampled to ``sampling_rate`` first, one launch
         per distinct rate (``lhotse_amd.augmentation.resample_in_arena``); the track's ``Speed`` then is a second pass over the first
         pass's output, and only the final length is capped (recording.py:486-490).  A mini-batch without a ``source_rate`` takes exactly
-        the route it took before there was one.
+        the route it took before there was one.  An optional 9th element ``(block in front of the reverb, block behind it)`` changes
+        the track's level (``Volume`` / ``Clipping``, ``lhotse_amd.augmentation.level_in_arena``): a block is None or a list of steps
+        ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``, ``("up", k)``, ``("down", k)`` -- the last two are
+        the ``Resample(sr -> k sr)`` / ``Resample(k sr -> sr)`` that ``clip_amplitude(oversampling=k)`` puts around its ``Clipping``; the
+        blocks run behind the ``Speed`` on the untruncated track, the first in front of the reverb, the second behind it.  Absent or
+        None: exactly the route of before.
 
         Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> convolution and gain launch of
         the reverberated tracks (``lhotse_amd.augmentation.reverb_in_arena``) -> energy launch -> mix launch
@@ -171,7 +225,7 @@ class FusedMiniBatch:
         -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None."""
         if len(cuts_tracks) != len(wants):
             raise ValueError("features_of_tracks: one wanted sample count per cut")
-        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None for t in cuts_tracks):
+        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None and _level_of(t[0]) is None for t in cuts_tracks):
             audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
             audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
             if any(f != 1.0 for f in factors):
@@ -189,6 +243,7 @@ class FusedMiniBatch:
         ex = self.extractor
         ex._check_sr(sr)
         items, factors, caps, ratios = [], [], [], []  # the tracks that have a source, in cut / track order; ratios: (source rate, sr) or None
+        levels = []  # per such track: its two level blocks or None
         rirs, rir_of, rv_idx, rv_rir, rv_norm = [], {}, [], [], []  # distinct scaled RIRs (hs, shift); reverberated tracks -> their RIR
         for tracks in cuts_tracks:
             for tr in tracks:
@@ -211,6 +266,7 @@ class FusedMiniBatch:
                     rv_idx.append(len(items)), rv_rir.append(rir_of[id(rv[0])]), rv_norm.append(int(bool(rv[1])))
                 items.append(_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures"))
                 factors.append(float(tr[1]))
+                levels.append(_level_of(tr))
                 rate = _source_rate_of(tr, sr)
                 ratios.append(None if rate is None else (rate, int(sr)))
                 caps.append(-1 if len(tr) < 6 or tr[5] is None else int(tr[5]))
@@ -223,6 +279,8 @@ class FusedMiniBatch:
         factors += [1.0] * len(rirs)
         ratios += [None] * len(rirs)
         two_pass = any(r is not None for r in ratios)
+        has_level = any(lv is not None for lv in levels)
+        blocks = [[None if lv is None else (lv[w] or None) for lv in levels] for w in (0, 1)]  # [in front of | behind the reverb][track]
         rv_idx = np.asarray(rv_idx, dtype=np.int64)
         cut_off, cut_len = np.zeros(len(cuts_tracks), dtype=np.int64), np.zeros(len(cuts_tracks), dtype=np.int64)
 
@@ -259,13 +317,16 @@ class FusedMiniBatch:
                 _, lens0, rs_floats = resample_layout(np.zeros(len(items), dtype=np.int64), lens0, ratios, 0)  # (a multiple of 4)
             _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
             rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) resampled tracks
+            lv_floats = [0, 0]  # what the oversampling passes of the two level blocks write (a level step itself works in place)
+            if has_level:
+                lv_floats = [_level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[w], int(sr), 0)[2] for w in (0, 1)]
             first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
             if mixed_ids:
                 short = mixed_num_samples(first, sl, do) < np.asarray(cap, dtype=np.int64)
                 if short.any():
                     raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
                                      "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
-            headroom = 3 + rs_floats + res_floats + rv_floats + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
+            headroom = 3 + rs_floats + res_floats + rv_floats + sum(lv_floats) + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
             arena, offs, lens = ex._pack(items, headroom=headroom)
             front = int(offs[-1] + lens[-1])
             if two_pass:  # the tracks at another rate come to sr behind the pack; the speed pass reads them there
@@ -276,6 +337,11 @@ class FusedMiniBatch:
             else:
                 po, pl = offs, lens
             mix_start = ((front + 3) & ~3) + res_floats  # behind the resampled tracks (perturbed_layout's own end)
+            if has_level:  # the block in front of the reverb: on the whole resampled track, as the reference's transforms see it
+                po, pl = np.array(po, dtype=np.int64), np.array(pl, dtype=np.int64)
+                po[:num_tracks], pl[:num_tracks], end = _level_steps(arena, po[:num_tracks], pl[:num_tracks], blocks[0], int(sr), mix_start)
+                assert end == mix_start + lv_floats[0]
+                mix_start = end
             if len(rv_idx):
                 # the reverb sees the whole resampled track and takes its powers over that length; the sample or two that
                 # assert_and_maybe_fix_num_samples removes come off afterwards (recording.py:1032-1070): `tables` applies the caps
@@ -284,6 +350,10 @@ class FusedMiniBatch:
                 po = np.array(po, dtype=np.int64)
                 po[rv_idx] = ro
                 mix_start += rv_floats
+            if has_level:  # the block behind the reverb
+                po[:num_tracks], pl[:num_tracks], end = _level_steps(arena, po[:num_tracks], pl[:num_tracks], blocks[1], int(sr), mix_start)
+                assert end == mix_start + lv_floats[1]
+                mix_start = end
             first, so, sl, do, snrs, refs, cap, mixed_ids = tables(po, pl)
             if not mixed_ids:  # (every cut turned out to be one plain track, e.g. a mixed cut whose other tracks are muted: nothing to mix)
                 mo = ml = np.zeros(0, dtype=np.int64)
@@ -454,6 +524,111 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         rest = pending_transforms(fastcopy(cut, recording=fastcopy(cut.recording, transforms=tf[1:])), gpu_reverb)
         return None if rest is None else (src, rest[0], rest[1])
 
+    LEVEL_NAMES = ("Volume", "Clipping")
+    MAX_LEVEL_OPS = 4  # ops of one block = of one program of hipfeat_level_plan
+
+    def _has_level_op(cut) -> bool:
+        tf = cut.recording.transforms if type(cut).__name__ == "MonoCut" and cut.has_recording else None
+        return bool(tf) and any(_transform_name(t) in LEVEL_NAMES for t in tf)
+
+    def _kwargs_of(t, names) -> dict:
+        return {k: t["kwargs"][k] for k in names if k in t["kwargs"]} if isinstance(t, dict) else {k: getattr(t, k) for k in names}
+
+    def _resample_rates(t) -> Tuple[int, int]:
+        kw = _kwargs_of(t, ("source_sampling_rate", "target_sampling_rate"))
+        return int(kw["source_sampling_rate"]), int(kw["target_sampling_rate"])
+
+    def _level_block(tf: list, pos: int, sr: int):
+        """The run of level elements of ``tf`` from ``pos`` on -- ``Volume`` | ``Clipping`` | ``Resample(sr -> k sr) Clipping
+        Resample(k sr -> sr)`` -- as steps -> (steps or None when there is none, the position behind it); ``False`` in place of the steps:
+        the run is not served (more than 4 ops, two ``Clipping``s, k outside 2 ... 8 or not an integer, a ``Resample`` that is not such a
+        bracket)."""
+        steps, ops, clips = [], 0, 0
+
+        def level(op):
+            if steps and steps[-1][0] == "level":
+                steps[-1][1].append(op)
+            else:
+                steps.append(("level", [op]))
+
+        def clip_op(t):
+            kw = {"hard": False, "gain_db": 0.0, "normalize": True, **_kwargs_of(t, ("hard", "gain_db", "normalize"))}
+            return ("clip", bool(kw["hard"]), float(kw["gain_db"]), bool(kw["normalize"]))
+
+        while pos < len(tf):
+            name = _transform_name(tf[pos])
+            if name == "Volume":
+                level(("volume", float(_kwargs_of(tf[pos], ("factor",))["factor"])))
+                pos += 1
+            elif name == "Clipping":
+                level(clip_op(tf[pos]))
+                clips, pos = clips + 1, pos + 1
+            elif name == "Resample" and _resample_rates(tf[pos])[0] == sr:  # the opening of clip_amplitude(oversampling=k) (recording.py:959-973)
+                up = _resample_rates(tf[pos])[1]
+                if pos + 2 >= len(tf) or _transform_name(tf[pos + 1]) != "Clipping" or _transform_name(tf[pos + 2]) != "Resample":
+                    return False, pos
+                if _resample_rates(tf[pos + 2]) != (up, sr) or up % sr or not 2 <= up // sr <= 8:
+                    return False, pos
+                steps += [("up", up // sr), ("level", [clip_op(tf[pos + 1])]), ("down", up // sr)]
+                clips, pos = clips + 1, pos + 3
+            else:
+                break
+            ops += 1
+            if ops > MAX_LEVEL_OPS or clips > 1:
+                return False, pos
+        return (steps or None), pos
+
+    def pending_level_chain(cut, gpu_reverb: bool = True, gpu_resample: bool = True):
+        """The rule of the level route: a mono cut (no video) over a recording whose transform list is
+
+            [Resample(a -> sr)]? [Speed]? L? [ReverbWithImpulseResponse]? L?
+            L = ( Volume | Clipping | Resample(sr -> k sr) Clipping Resample(k sr -> sr) ){1 ... 4 ops, at most one Clipping}
+
+        with at least one level op -> ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None, (the steps of
+        the L in front of the reverb or None, of the L behind it or None))``; the first three are ``pending_chain``'s answer for the
+        chain without its level ops.  The bracketed form is what ``clip_amplitude(oversampling=k)`` appends (recording.py:937-975), k an
+        integer 2 ... 8; it needs ``gpu_resample`` and a reference that resamples with its sinc module (``_reference_resamples_with_sinc``).  Steps: ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``,
+        ``("up", k)``, ``("down", k)`` (``FusedMiniBatch.features_of_tracks``).  None = not this rule's business -- a chain without a level
+        op, which the older rules decide -- or not served: anything but a ``MonoCut`` (a ``MultiCut``, a ``MixedCut`` as a whole), a recording
+        with more than one channel (also when the ``MonoCut`` selects one of them), a level op in front of the ``Speed`` or the leading ``Resample``, a block of
+        more than 4 ops or with two ``Clipping``s, k outside 2 ... 8, anything else in the list, and whatever ``pending_chain`` refuses
+        in the rest."""
+        if not _has_level_op(cut) or getattr(cut.recording, "has_video", False) or cut.recording.num_channels != 1:
+            return None  # (a MonoCut over one channel of a multi-channel recording is left to the reference too: level ops there are out of scope)
+        tf = list(cut.recording.transforms)
+        sr, pos = int(cut.sampling_rate), 0
+        if _transform_name(tf[pos]) == "Resample" and _resample_rates(tf[pos])[0] != sr:  # cuts.resample(sr); one FROM sr opens a bracket
+            pos += 1
+        if pos < len(tf) and _transform_name(tf[pos]) == "Speed":
+            pos += 1
+        rest = tf[:pos]
+        pre, pos = _level_block(tf, pos, sr)
+        if pre is False:
+            return None
+        if pos < len(tf) and _transform_name(tf[pos]) == "ReverbWithImpulseResponse":
+            rest.append(tf[pos])
+            pos += 1
+        post, pos = _level_block(tf, pos, sr)
+        if post is False or pos != len(tf) or (pre is None and post is None):
+            return None
+        if any(st[0] != "level" for st in (pre or []) + (post or [])) and not (gpu_resample and _reference_resamples_with_sinc()):
+            return None  # (the oversampling runs the device's sinc resampler: only where the reference's Resample runs its own)
+        from lhotse.utils import fastcopy
+
+        chain = pending_chain(fastcopy(cut, recording=fastcopy(cut.recording, transforms=rest)), gpu_reverb, gpu_resample)
+        return None if chain is None else (chain[0], chain[1], chain[2], (pre, post))
+
+    def _read_level_track(cut, lc, offset: int = 0, snr=None, is_ref: bool = True) -> Optional[tuple]:
+        """The 9-element track of ``FusedMiniBatch.features_of_tracks`` for a cut with level ops (``lc`` = ``pending_level_chain(cut)``),
+        or None when the chain's output would be shorter than the cut (it would need reflect-padding: the rule of ``_read_one``)."""
+        source_rate, factor, rv, blocks = lc
+        sr = cut.sampling_rate
+        raw = read_before_chain(cut)
+        want = compute_num_samples(cut.duration, sr)
+        if chain_num_samples(len(raw), source_rate, factor, sr) < want:
+            return None
+        return (raw, factor, offset, snr, is_ref, want, None if rv is None else (load_reverb_rir(rv), rv["normalize_output"]), source_rate, blocks)
+
     def chain_num_samples(num_samples: int, source_rate: Optional[int], factor: float, sampling_rate: int) -> int:
         """Samples that come out of ``[Resample(source_rate -> sr)]? [Speed(factor)]?`` for ``num_samples`` going in: per stage
         ``ceil(new * n / orig)`` in float32 with the rates reduced by their gcd (resample.py:219-222, :309)."""
@@ -562,16 +737,21 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         return raw
 
     def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False, gpu_reverb: bool = False,
-                  gpu_resample: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
+                  gpu_resample: bool = False, gpu_level: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
         """(samples, factor still to be applied, samples the cut must end up with) or None when the read failed and errors are suppressed.
         For a mixed cut the device will mix, and for a cut the device will reverberate, ``samples`` is the list of its loaded tracks
         (``FusedMiniBatch.features_of_tracks``); a failed track drops the cut."""
         with suppress_audio_loading_errors(enabled=suppress_errors):
-            tracks = deferred_mix(cut, gpu_reverb, gpu_resample=gpu_resample) if gpu_mix else None
+            tracks = deferred_mix(cut, gpu_reverb, gpu_resample=gpu_resample, gpu_level=gpu_level) if gpu_mix else None
             if tracks is not None and (gpu_speed or all(t[1] in (None, 1.0) for t in tracks)):
                 res = _read_tracks(cut, tracks)
                 if res is not None:
                     return res
+            lc = pending_level_chain(cut, gpu_reverb, gpu_resample) if gpu_level else None
+            if lc is not None and (gpu_speed or lc[1] == 1.0):  # level ops in the chain: the cut is one track
+                track = _read_level_track(cut, lc)
+                if track is not None:
+                    return [track], 1.0, track[5]
             chain = pending_chain(cut, gpu_reverb) if gpu_resample else None
             if chain is not None and chain[0] is not None and (gpu_speed or chain[1] == 1.0):  # a Resample in front: the cut is one track
                 track = _read_chain_track(cut, chain)
@@ -609,7 +789,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         p = pending_transforms(cut, gpu_reverb)
         return None if p is None else p[0]
 
-    def deferred_mix(cut, gpu_reverb: bool = True, gpu_resample: bool = False) -> Optional[List[tuple]]:
+    def deferred_mix(cut, gpu_reverb: bool = True, gpu_resample: bool = False, gpu_level: bool = False) -> Optional[List[tuple]]:
         """The tracks of a ``MixedCut`` the device can mix -- ``[(track cut, factor, offset_samples, snr, is_reference)]`` over its audible
         tracks, ``factor`` = None for a ``PaddingCut`` track -- or None: load it the reference's way (``cut.load_audio()``).  Decided on
         the host before anything is read.  Refused: anything but a ``MixedCut`` with audio and without video or ``transforms`` of its own;
@@ -620,7 +800,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         mixed.py:1346-1350); a mix that comes out shorter than ``cut.num_samples`` (reflect-
         padded, mixed.py:1386-1387) or longer by lhotse's tolerance or more.  With ``gpu_resample`` a track may also carry a ``Resample`` in
         front (``pending_chain``); such a track comes with two more elements, its reverb or None and its source rate.  (A perturbed track that would need reflect-padding is found when
-        it is read, as for a mono cut: ``_read_tracks`` returns None and the cut is loaded the reference's way.)"""
+        it is read, as for a mono cut: ``_read_tracks`` returns None and the cut is loaded the reference's way.)  With ``gpu_level`` a track
+        may carry level ops (``pending_level_chain``); such a track has eight elements, the last one its level blocks."""
         if type(cut).__name__ != "MixedCut" or not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
             return None
         from lhotse.audio.utils import get_audio_duration_mismatch_tolerance
@@ -644,6 +825,14 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             if type(c).__name__ == "PaddingCut":
                 factor = None
                 chain = None
+            elif gpu_level and _has_level_op(c):
+                lc = pending_level_chain(c, gpu_reverb, gpu_resample)
+                if lc is None:
+                    return None
+                off = compute_num_samples(t.offset, sr)
+                total = max(total, off + compute_num_samples(c.duration, sr))
+                out.append((c, lc[1], off, t.snr, t is ref, lc[2], lc[0], lc[3]))  # (reverb or None, source rate or None, level blocks)
+                continue
             elif gpu_resample and _has_pending_resample(c):
                 chain = pending_chain(c, gpu_reverb)
                 if chain is None:
@@ -676,6 +865,11 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             n = compute_num_samples(c.duration, sr)
             if factor is None:
                 loaded.append((n, 1.0, off, snr, is_ref, n))
+            elif len(tr) > 7:  # level ops somewhere in the chain
+                track = _read_level_track(c, (tr[6], factor, tr[5], tr[7]), off, snr, is_ref)
+                if track is None:
+                    return None
+                loaded.append(track)
             elif len(tr) > 6:  # a Resample in front of the (possibly pending) Speed and reverb
                 track = _read_chain_track(c, (tr[6], factor, tr[5]), off, snr, is_ref)
                 if track is None:
@@ -708,11 +902,11 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
     class HipOnTheFlyFeatures(OnTheFlyFeatures, FusedMiniBatch):
         """Same constructor as ``OnTheFlyFeatures`` plus ``return_device`` (``None`` keeps the padded feature tensor on the
         extractor's GPU, ready for the training step; ``"cpu"`` hands back a host tensor like the reference does) and
-        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` (see the module docstring)."""
+        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` / ``gpu_level`` (see the module docstring)."""
 
         def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
                      gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, gpu_reverb: Optional[bool] = None,
-                     gpu_resample: Optional[bool] = None, **kwargs) -> None:
+                     gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, **kwargs) -> None:
             if not hasattr(extractor, "extract_collated"):
                 raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
             super().__init__(extractor, *args, **kwargs)
@@ -736,6 +930,11 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             # implement; False = always Recording.load_audio; True forces the device's sinc resampler, and raises together with
             # wave_transforms when such a cut is met
             self.gpu_resample = (not self.wave_transforms and _reference_resamples_with_sinc()) if gpu_resample is None else bool(gpu_resample)
+            # and for Volume / Clipping in a recording's transforms (PerturbVolume, the Clipping cut transform): None = on the device unless
+            # wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a cut is met.  The
+            # oversampled clip (clip_amplitude(oversampling=k)) and a leading Resample in such a chain also need the resampling route, and
+            # that only where the reference itself would run its sinc resampler
+            self.gpu_level = (not self.wave_transforms) if gpu_level is None else bool(gpu_level)
 
         def _read(self, cuts, pool, recording_field):
             """read_audio_from_cuts (lhotse/dataset/collation.py:541-600) with the Speed of eligible cuts left for the device."""
@@ -744,7 +943,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 (self.gpu_speed_perturb and any(deferred_speed_factor(c) not in (None, 1.0) for c in cuts))
                 or (self.gpu_mix and any(type(c).__name__ == "MixedCut" for c in cuts))
                 or (self.gpu_reverb and any(deferred_reverb(c) is not None for c in cuts))
-                or (self.gpu_resample and any(_has_pending_resample(c) for c in cuts)))
+                or (self.gpu_resample and any(_has_pending_resample(c) for c in cuts))
+                or (self.gpu_level and any(_has_level_op(c) for c in cuts)))
             if not on_device:
                 audios, ok = read_audio_from_cuts(cuts, executor=pool, suppress_errors=self.fault_tolerant, recording_field=recording_field)
                 return audios, [1.0] * len(audios), [int(a.shape[-1]) for a in audios], ok
@@ -755,7 +955,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             map_fn = map if pool is None else pool.map
             audios, factors, wants, ok = [], [], [], []
             read = partial(_read_one, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix,
-                           gpu_reverb=self.gpu_reverb, gpu_resample=self.gpu_resample)
+                           gpu_reverb=self.gpu_reverb, gpu_resample=self.gpu_resample, gpu_level=self.gpu_level)
             for cut, res in zip(cuts, map_fn(read, cuts)):
                 if res is None:
                     continue
@@ -771,6 +971,10 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             audios, factors, wants, cuts = self._read(cuts, pool, recording_field)
             mixed = any(isinstance(a, list) for a in audios)  # (the loaded tracks of the cuts the device mixes)
             for transform in self.wave_transforms:
+                if any(isinstance(a, list) and any(_level_of(t) is not None for t in a) for a in audios):
+                    raise ValueError("gpu_level=True was requested together with wave_transforms: the transforms run on the scaled and clipped "
+                                     "samples, before the device scales and clips them; leave gpu_level at its default (None: "
+                                     "Recording.load_audio whenever wave_transforms are given) or pass False")
                 if any(isinstance(a, list) and any(len(t) > 7 and t[7] is not None for t in a) for a in audios):
                     raise ValueError("gpu_resample=True was requested together with wave_transforms: the transforms run on the resampled "
                                      "samples, before the device resamples them; leave gpu_resample at its default (None: "

@@ -1,0 +1,353 @@
+"""CPU, under the real lhotse (authoring container only): the level rule against the reference's own ``Volume`` / ``Clipping``.
+
+  * ``_level_ref.model32`` -- the numpy statement of the device's arithmetic -- is ``array_equal`` to the reference for SCALE and hard CLIP;
+  * the peak-propagation identity: max |fl(fl(x f1) f2)| == fl(fl(max|x| |f1|) |f2|), on random data;
+  * the silence threshold is the reference's ``20 * np.log10(p) < -96`` on float32, restated as one float32 number;
+  * ``pending_level_chain`` accepts every form of its grammar and refuses what it must, and every older rule function still answers None
+    for those cuts with its default arguments;
+  * ``HipOnTheFlyFeatures`` with CPU stand-ins for the device reproduces the reference's features (and, for Volume / hard Clipping, its
+    audio bit for bit) over level cuts, plain cuts, a speed-only cut and a mixed cut, and leaves the cuts without a level op exactly as a
+    mini-batch without the level cuts leaves them."""
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import _level_ref as L
+from test_resample_chain_reference import cpu_perturb, cpu_resample, cpu_reverb
+
+SR = 16000
+REL_TOL, ABS_TOL = 1e-4, 2e-3  # the suite's bar for driver goldens (tests/test_gpu_reference_drivers.py)
+pytestmark = pytest.mark.reference
+
+
+@pytest.fixture(scope="module")
+def env(tmp_path_factory):
+    from _dropin_support import import_lhotse, install_wave_backend, write_cutset
+
+    import_lhotse()
+    import lhotse.augmentation.torchaudio as ref_ta
+    from lhotse.audio.backend import set_current_audio_backend
+
+    was = ref_ta.is_torchaudio_available
+    ref_ta.is_torchaudio_available = lambda: True  # the reference's sinc branch, as in the generator of the goldens
+    prev = install_wave_backend()
+    cuts = list(write_cutset(tmp_path_factory.mktemp("levelwav"), [6000, 4800, 7200, 5000, 8000, 3000], seed=5))
+    yield cuts
+    set_current_audio_backend(prev)
+    ref_ta.is_torchaudio_available = was
+
+
+def reference_program(x, program):
+    from lhotse.augmentation import Clipping, Volume
+
+    y = np.asarray(x, np.float32)[None, :]
+    for op in program:
+        y = (Volume(factor=op[1]) if op[0] == "volume" else Clipping(hard=op[1], gain_db=op[2], normalize=op[3]))(y, SR)
+    return y[0]
+
+
+def test_model32_equals_the_reference_for_scale_and_hard_clip(env):
+    programs = [[("volume", 0.37)], [("volume", -2.5)], [("clip", True, 0.0, True)], [("clip", True, 0.05, False)], [("clip", True, -6.0, True)],
+                [("clip", True, 20.0, False)], [("volume", 1.9), ("clip", True, 20.0, True)], [("clip", True, -6.0, True), ("volume", 0.6)],
+                [("volume", -1.3), ("volume", 0.9), ("clip", True, 20.0, True), ("volume", 1.1)]]
+    for k, prog in enumerate(programs):
+        for n, amp in ((1, 0.5), (5, 0.5), (4099, 1.5), (70001, 0.5), (257, 1e-6), (64, 0.0)):
+            x = L.signal(10 * k + n, n, amp)
+            want = reference_program(x, prog)
+            assert want.dtype == np.float32 and np.array_equal(L.model32(x, prog), want), (prog, n, amp)
+
+
+def test_the_propagated_peak_is_the_peak_of_the_scaled_samples():
+    rng = np.random.RandomState(3)
+    for trial in range(300):
+        x = (rng.standard_normal(rng.randint(1, 3000)) * 10.0 ** rng.uniform(-6, 2)).astype(np.float32)
+        factors = [float(np.float32(rng.choice([-1, 1]) * 10.0 ** rng.uniform(-2, 2))) for _ in range(rng.randint(1, 4))]
+        y = x
+        for f in factors:
+            y = y * np.float32(f)  # Volume.__call__
+        assert y.dtype == np.float32 and np.max(np.abs(y)) == L.propagated_peak(x, factors), (trial, factors)
+
+
+def test_the_silence_threshold_restates_the_reference_expression():
+    from lhotse_amd import constants
+
+    def reference_says_silence(p):  # clipping.py:36 on the float32 scalar np.max returns
+        return bool(p == 0 or 20 * np.log10(p) < -96)
+
+    t = constants.SILENCE_PEAK
+    assert t.dtype == np.float32 and t == L.SILENCE_PEAK and not reference_says_silence(t)
+    lo = hi = t
+    for _ in range(256):
+        lo, hi = np.nextafter(lo, np.float32(0)), np.nextafter(hi, np.float32(1))
+        assert lo.dtype == np.float32 and reference_says_silence(lo) and not reference_says_silence(hi)
+    assert reference_says_silence(np.float32(0)) and reference_says_silence(np.float32(1e-30)) and not reference_says_silence(np.float32(1.0))
+    # ... and the transform acts on it: an item whose peak is one float below comes back unchanged, at the threshold it does not
+    for p, same in ((np.nextafter(t, np.float32(0)), True), (t, False)):
+        x = np.array([p, -p / 2, 0], dtype=np.float32)
+        y = reference_program(x, [("clip", True, 20.0, True)])
+        assert np.array_equal(y, x) is same and np.array_equal(y, L.model32(x, [("clip", True, 20.0, True)]))
+
+
+def test_transforms_have_the_fields_of_the_reference(env):
+    from dataclasses import fields
+
+    from lhotse.augmentation import AudioTransform, Clipping, Volume
+
+    from lhotse_amd.augmentation import HipClipping, HipVolume
+
+    for ours, theirs, kw in ((HipVolume, Volume, {"factor": 0.5}), (HipClipping, Clipping, {})):
+        a, b = ours(**kw), theirs(**kw)
+        assert [(f.name, f.default) for f in fields(ours)][:-1] == [(f.name, f.default) for f in fields(theirs)] and fields(ours)[-1].name == "device"
+        da = a.to_dict()
+        assert da["name"] == ours.__name__ and {k: v for k, v in da["kwargs"].items() if k != "device"} == b.to_dict()["kwargs"]
+        assert AudioTransform.from_dict(da) == a
+        assert a.reverse_timestamps(0.25, 1.5, SR) == b.reverse_timestamps(0.25, 1.5, SR) == (0.25, 1.5)
+        assert a.reverse_timestamps(0.25, None, SR) == b.reverse_timestamps(0.25, None, SR)
+
+
+# ---- the rule --------------------------------------------------------------------------------------------------------------------
+def _rir(tmp_path):
+    from lhotse import Recording
+    from lhotse.audio import AudioSource
+    from oracle.driver_corpus import write_wav
+
+    h = np.random.RandomState(1).randn(300) * np.exp(-np.arange(300) / 40.0) * 0.1
+    h[3] = 1.0
+    write_wav(tmp_path / "rir.wav", np.round(h * 20000).astype(np.int16))
+    return Recording(id="rir", sources=[AudioSource(type="file", channels=[0], source=str(tmp_path / "rir.wav"))], sampling_rate=SR, num_samples=300,
+                     duration=300 / SR)
+
+
+def _with_transforms(cut, transforms):
+    from lhotse.utils import fastcopy
+
+    return fastcopy(cut, recording=fastcopy(cut.recording, transforms=[t if isinstance(t, dict) else t.to_dict() for t in transforms]))
+
+
+def test_pending_level_chain_accepts_its_grammar_and_refuses_the_rest(env, tmp_path, monkeypatch):
+    import lhotse.augmentation.torchaudio as ref_ta
+    from lhotse.augmentation import Clipping, Resample, Speed, Volume
+
+    import lhotse_amd.input_strategies as IS
+
+    c = env[0]
+    rir = _rir(tmp_path)
+    vol, clip = ("volume", 0.5), ("clip", True, 6.0, False)
+    lvl = lambda *ops: ("level", list(ops))  # noqa: E731
+
+    # every form of the grammar
+    assert IS.pending_level_chain(c.perturb_volume(0.5)) == (None, 1.0, None, ([lvl(vol)], None))
+    assert IS.pending_level_chain(c.clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None)) == (None, 1.0, None, ([lvl(clip)], None))
+    assert IS.pending_level_chain(c.clip_amplitude()) == (None, 1.0, None, ([("up", 2), lvl(("clip", False, 0.0, True)), ("down", 2)], None))
+    for k in (2, 4, 8):
+        got = IS.pending_level_chain(c.clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=k))
+        assert got == (None, 1.0, None, ([("up", k), lvl(clip), ("down", k)], None))
+    got = IS.pending_level_chain(c.perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=4).perturb_volume(2.0))
+    assert got == (None, 1.0, None, ([lvl(vol), ("up", 4), lvl(clip), ("down", 4), lvl(("volume", 2.0))], None))
+    assert IS.pending_level_chain(c.perturb_speed(1.1).perturb_volume(0.5))[:2] == (None, 1.1)
+    full = c.perturb_speed(0.9).perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None).reverb_rir(rir).perturb_volume(2.0)
+    src, factor, rv, blocks = IS.pending_level_chain(full)
+    assert (src, factor) == (None, 0.9) and rv["normalize_output"] is True and blocks == ([lvl(vol, clip)], [lvl(("volume", 2.0))])
+    assert IS.pending_level_chain(c.reverb_rir(rir).perturb_volume(0.5))[3] == (None, [lvl(vol)])
+    assert IS.pending_level_chain(c.perturb_volume(0.5).reverb_rir(rir))[3] == ([lvl(vol)], None)
+    res = _with_transforms(c, [Resample(44100, SR), Speed(1.1), Volume(0.5)])
+    assert IS.pending_level_chain(res) == (44100, 1.1, None, ([lvl(vol)], None))
+    four = c.perturb_volume(0.5).perturb_volume(0.5).perturb_volume(0.5).perturb_volume(0.5)
+    assert IS.pending_level_chain(four)[3] == ([lvl(vol, vol, vol, vol)], None)
+    # serialised transforms (dicts, as a manifest carries them) and objects give the same answer
+    assert IS.pending_level_chain(_with_transforms(c, [Volume(0.5), Clipping(True, 6.0, False)])) == (None, 1.0, None, ([lvl(vol, clip)], None))
+
+    # what keeps cut.load_audio()
+    refused = {
+        "no level op": c.perturb_speed(1.1),
+        "plain": c,
+        "a level op in front of the Speed": c.perturb_volume(0.5).perturb_speed(1.1),
+        "five ops in one block": four.perturb_volume(0.5),
+        "two Clippings in one block": c.clip_amplitude(oversampling=None).clip_amplitude(oversampling=None),
+        "k = 9": c.clip_amplitude(oversampling=9),
+        "k = 1": c.clip_amplitude(oversampling=1),
+        "an open bracket": _with_transforms(c, [Resample(SR, 2 * SR), Clipping()]),
+        "a bracket that closes at another rate": _with_transforms(c, [Resample(SR, 4 * SR), Clipping(), Resample(2 * SR, SR)]),
+        "a bracket around a Volume": _with_transforms(c, [Resample(SR, 2 * SR), Volume(0.5), Resample(2 * SR, SR)]),
+        "a level op in front of the leading Resample": _with_transforms(c, [Volume(0.5), Resample(44100, SR)]),
+        "two reverbs": c.perturb_volume(0.5).reverb_rir(rir).reverb_rir(rir),
+        "a Speed behind the level op": c.perturb_volume(0.5).perturb_speed(1.1),
+        "the random RIR generator": c.perturb_volume(0.5).reverb_rir(),
+    }
+    for why, cut in refused.items():
+        assert IS.pending_level_chain(cut) is None, why
+    assert IS.pending_level_chain(c.pad(duration=1.0).perturb_volume(0.5)) is None  # a MixedCut as a whole
+    assert IS.pending_level_chain(full, gpu_reverb=False) is None
+    assert IS.pending_level_chain(res, gpu_resample=False) is None
+    assert IS.pending_level_chain(c.clip_amplitude(), gpu_resample=False) is None
+    assert IS.pending_level_chain(c.clip_amplitude(oversampling=None), gpu_reverb=False, gpu_resample=False) is not None
+    monkeypatch.setattr(ref_ta, "is_torchaudio_available", lambda: False)  # the reference would oversample with scipy's resample_poly
+    assert IS.pending_level_chain(c.clip_amplitude()) is None and IS.pending_level_chain(c.clip_amplitude(oversampling=None)) is not None
+    monkeypatch.setattr(ref_ta, "is_torchaudio_available", lambda: True)
+
+    # the older rules keep their answers on every cut the new rule takes
+    for cut in (c.perturb_volume(0.5), c.clip_amplitude(), c.clip_amplitude(oversampling=None), full, res, four):
+        assert IS.deferred_speed_factor(cut) is None and IS.pending_transforms(cut) is None and IS.pending_chain(cut) is None
+        assert IS.deferred_reverb(cut) is None
+        mixed = cut.pad(duration=cut.duration + 0.1)
+        assert IS.deferred_mix(mixed) is None and IS.deferred_mix(mixed, gpu_resample=True) is None
+        tracks = IS.deferred_mix(mixed, gpu_resample=True, gpu_level=True)
+        assert tracks is not None and len(tracks[0]) == 8 and tracks[0][7] == IS.pending_level_chain(cut)[3]
+    padded = c.pad(duration=c.duration + 0.1)
+    assert IS.deferred_mix(padded.perturb_volume(0.5), gpu_level=True) is not None  # (MixedCut.perturb_volume perturbs the tracks)
+    from lhotse.utils import fastcopy
+
+    assert IS.deferred_mix(fastcopy(padded, transforms=[Volume(0.5).to_dict()]), gpu_level=True) is None  # a MixedCut with transforms of its own
+    # a refused track sends the whole mixed cut back
+    assert IS.deferred_mix(four.perturb_volume(0.5).pad(duration=c.duration + 0.1), gpu_level=True) is None
+
+
+# ---- the route, with CPU stand-ins for the device ----------------------------------------------------------------------------------
+def cpu_level(arena, offsets, lengths, programs):
+    for o, n, prog in zip(offsets, lengths, programs):
+        arena[int(o) : int(o) + int(n)] = torch.from_numpy(L.model32(arena[int(o) : int(o) + int(n)].numpy().copy(), prog))
+    return np.asarray(offsets, dtype=np.int64)
+
+
+@pytest.fixture
+def stand_ins(monkeypatch):
+    import lhotse_amd.extractors as E
+    import lhotse_amd.input_strategies as IS
+    from _dropin_support import make_cpu_plan
+    from _mix_ref import mix_in_arena_cpu
+
+    calls = {"level": 0, "resample": 0}
+
+    def counted(name, fn):
+        def run(*a):
+            calls[name] += 1
+            return fn(*a)
+
+        return run
+
+    monkeypatch.setattr(E, "_Plan", make_cpu_plan())
+    monkeypatch.setattr(IS, "_level_in_arena", counted("level", cpu_level))
+    monkeypatch.setattr(IS, "_resample_in_arena", counted("resample", cpu_resample))
+    monkeypatch.setattr(IS, "_perturb_in_arena", cpu_perturb)
+    monkeypatch.setattr(IS, "_mix_in_arena", mix_in_arena_cpu)
+    monkeypatch.setattr(IS, "_reverb_in_arena", cpu_reverb)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    return calls
+
+
+def test_the_route_with_stand_ins_equals_the_reference(env, tmp_path, stand_ins, monkeypatch):
+    from lhotse import CutSet
+    from lhotse.dataset.cut_transforms import CutMix
+    from lhotse.dataset.input_strategies import OnTheFlyFeatures
+    from lhotse.features.kaldi.extractors import Fbank
+
+    import lhotse_amd as LA
+
+    c0, c1, c2, c3, c4, c5 = env
+    rir = _rir(tmp_path)
+    noise = CutSet.from_cuts([c4])
+    mixed = list(CutMix(noise, snr=15, p=1.0, pad_to_longest=False, random_mix_offset=False, seed=3)(CutSet.from_cuts([c3.perturb_volume(0.4)])))[0]
+    assert type(mixed).__name__ == "MixedCut"
+    level = [c0.perturb_volume(1.7),  # 0: audio bit for bit
+             c1.clip_amplitude(hard=True, gain_db=12.0, oversampling=None),  # 1: audio bit for bit
+             c1.clip_amplitude(hard=False, gain_db=6.0, oversampling=None),  # 2
+             c2.clip_amplitude(hard=True, gain_db=12.0, oversampling=2),  # 3
+             c2.clip_amplitude(hard=False, gain_db=3.0, oversampling=4).perturb_volume(0.8),  # 4
+             c0.perturb_speed(1.1).perturb_volume(0.5).clip_amplitude(hard=True, gain_db=9.0, oversampling=None).reverb_rir(rir).perturb_volume(1.5),  # 5
+             mixed]  # 6: a volume on the speech track of a mix
+    others = [c5, c1.perturb_speed(0.9), c2]
+    batch = CutSet.from_cuts(level[:4] + others[:2] + level[4:] + others[2:])
+    want_f, want_l, want_a, want_al = OnTheFlyFeatures(Fbank(), return_audio=True)(batch)
+    loads = {"n": 0}
+    strat = LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), return_audio=True, gpu_resample=True)
+    assert strat.gpu_level is True and LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), gpu_level=False).gpu_level is False
+    for cls in {type(c) for c in batch}:
+        real = cls.load_audio
+        monkeypatch.setattr(cls, "load_audio", lambda self, *a, _real=real, **k: (loads.__setitem__("n", loads["n"] + 1), _real(self, *a, **k))[1])
+    got_f, got_l, got_a, got_al = strat(batch)
+    assert stand_ins["level"] > 0 and stand_ins["resample"] > 0
+    assert torch.equal(got_l, want_l) and torch.equal(got_al, want_al)
+    got_f, got_a = got_f.numpy().astype(np.float64), got_a.numpy()
+    for i, cut in enumerate(batch):
+        n, t = int(want_al[i]), int(want_l[i])
+        # (the reference extracts from ONE zero-padded batch: edge_rule "batch_zero_pad")
+        w = want_f[i, :t].numpy().astype(np.float64)
+        rel, mx = float(np.linalg.norm(got_f[i, :t] - w) / np.linalg.norm(w)), float(np.abs(got_f[i, :t] - w).max())
+        assert rel <= REL_TOL and mx <= ABS_TOL, (i, cut.id, rel, mx)
+        if i in (0, 1):  # only a Volume, only a hard Clipping
+            assert np.array_equal(got_a[i, :n], want_a[i, :n].numpy()), (i, cut.id)
+        else:
+            assert float(np.abs(got_a[i, :n] - want_a[i, :n].numpy()).max()) <= 2e-5, (i, cut.id)  # (resampler + soft clip + reverb, float32)
+    # the cuts without a level op: exactly what the same call without the level cuts gives (audio; the features of a cut do not depend on the batch)
+    base = CutSet.from_cuts(others)
+    stand_ins["level"] = 0
+    f0, l0, a0, al0 = strat(base)
+    assert stand_ins["level"] == 0
+    for j, i in enumerate((4, 5, 9)):
+        n = int(al0[j])
+        assert int(want_al[i]) == n and np.array_equal(a0[j, :n].numpy(), got_a[i, :n]) and np.array_equal(f0[j, : int(l0[j])].numpy(), strat(batch)[0][i, : int(l0[j])].numpy())
+    # with the flag off every level cut is loaded the reference's way
+    off = LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), return_audio=True, gpu_resample=True, gpu_level=False)
+    stand_ins["level"] = 0
+    a_off = off(batch)[2].numpy()
+    assert stand_ins["level"] == 0
+    for i in range(len(batch)):
+        n = int(want_al[i])
+        if i not in (5,):  # (the speed-only cut goes through the stand-in resampler either way)
+            assert np.array_equal(a_off[i, :n], want_a[i, :n].numpy()), i
+
+
+def test_gpu_level_with_wave_transforms_raises_when_a_level_cut_is_met(env, stand_ins):
+    from lhotse import CutSet
+
+    import lhotse_amd as LA
+
+    strat = LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), wave_transforms=[lambda a: a])
+    assert strat.gpu_level is False
+    strat(CutSet.from_cuts([env[0].perturb_volume(0.5)]))  # the default with wave_transforms: the reference's path
+    strat = LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), wave_transforms=[lambda a: a], gpu_level=True)
+    strat(CutSet.from_cuts([env[0]]))
+    with pytest.raises(ValueError, match="gpu_level=True was requested together with wave_transforms"):
+        strat(CutSet.from_cuts([env[0].perturb_volume(0.5)]))
+
+
+def test_multi_channel_recordings_keep_the_reference_path(env, tmp_path, stand_ins):
+    """A ``MultiCut``, and a ``MonoCut`` that selects one channel of a two-channel recording: the rule refuses both (``num_channels != 1``),
+    alone and as the track of a mix, and the strategy loads them the reference's way -- sample for sample what lhotse returns."""
+    import wave
+
+    from lhotse import CutSet, MonoCut, MultiCut, Recording
+    from lhotse.audio import AudioSource
+    from lhotse.dataset.input_strategies import OnTheFlyFeatures
+    from lhotse.features.kaldi.extractors import Fbank
+
+    import lhotse_amd as LA
+    import lhotse_amd.input_strategies as IS
+
+    n = 4000
+    pcm = (np.random.RandomState(9).rand(n, 2) * 2.0 - 1.0) * np.array([3000.0, 20000.0])  # the louder channel is NOT the one the MonoCut selects
+    with wave.open(str(tmp_path / "two.wav"), "wb") as f:
+        f.setnchannels(2), f.setsampwidth(2), f.setframerate(SR)
+        f.writeframes(pcm.astype(np.int16).tobytes())
+    rec = Recording(id="two", sources=[AudioSource(type="file", channels=[0, 1], source=str(tmp_path / "two.wav"))], sampling_rate=SR, num_samples=n,
+                    duration=n / SR)
+    assert rec.num_channels == 2
+
+    def level(cut):
+        return cut.perturb_volume(0.5).clip_amplitude(hard=True, gain_db=12.0, oversampling=None)
+
+    multi = level(MultiCut(id="multi", start=0, duration=n / SR, channel=[0, 1], recording=rec))
+    mono = level(MonoCut(id="mono-of-two", start=0, duration=n / SR, channel=0, recording=rec))
+    for cut in (multi, mono):
+        assert IS._transform_name(cut.recording.transforms[0]) == "Volume" and IS._transform_name(cut.recording.transforms[1]) == "Clipping"
+        assert IS.pending_level_chain(cut) is None and IS.pending_transforms(cut) is None and IS.pending_chain(cut) is None
+    assert IS.deferred_mix(mono.pad(duration=0.3), gpu_resample=True, gpu_level=True) is None  # ... and the mix around such a track goes back with it
+    ok = level(env[0])
+    assert IS.pending_level_chain(ok) is not None
+    batch = CutSet.from_cuts([mono, ok])
+    want = OnTheFlyFeatures(Fbank(), return_audio=True)(batch)
+    got = LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), return_audio=True)(batch)
+    assert stand_ins["level"] == 1  # one level launch: the single-channel cut's
+    assert torch.equal(got[3], want[3]) and np.array_equal(got[2].numpy(), want[2].numpy())  # (Volume + hard Clipping: bit for bit, both ways)
