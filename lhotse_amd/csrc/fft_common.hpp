@@ -60,14 +60,26 @@ __device__ __forceinline__ v2 cmul2(v2 a, v2 w) {
   return r;
 }
 
-// 16-point complex FFT in registers (radix-4 x radix-4, natural order in and out)
-__device__ __forceinline__ void fft16(const v2 (&x)[16], v2 (&X)[16]) {
+// 16-point complex FFT in registers (radix-4 x radix-4, natural order in and out).  Inputs x[NLIVE..15] are zero by construction
+// (rows of the frame past its length) and are never read: without fast-math `t + 0.0f` does not fold, so the full butterfly spends
+// packed adds, multiply-adds by zero and the moves that make the zeros on them.  The live terms keep their operation order and rounding, so
+// every non-zero value has the same bits as with the zeros added in; a zero may come out as +0 where the full form gives -0 (x + 0 is +0
+// for x = -0), which cannot reach a non-zero value downstream and is squared away in |X|^2.
+template <int NLIVE>
+__device__ __forceinline__ void fft16_lead(const v2 (&x)[16], v2 (&X)[16]) {
+  static_assert(NLIVE >= 8 && NLIVE <= 16, "rows 0..7 are always live");
   constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R2 = 0.70710678118654752f;
   v2 y[16];  // y[4*m + n]
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
-    const v2 s0 = x[n] + x[n + 8], s1 = x[n] - x[n + 8];
-    const v2 s2 = x[n + 4] + x[n + 12], u3 = swap2(x[n + 4] - x[n + 12]);
+    const bool l8 = n + 8 < NLIVE, l12 = n + 12 < NLIVE;
+    // an input that stands alone where a sum stood is pinned as a ROUNDED value: it usually is a product (sample x window), which hipcc
+    // would now contract into the add that follows (x[n + 4] + s0 as one fma), where the full form rounds it first (x[n + 4] + 0)
+    v2 xa = x[n], xb = x[n + 4];
+    if (!l8) asm("" : "+v"(xa));
+    if (!l12) asm("" : "+v"(xb));
+    const v2 s0 = l8 ? xa + x[n + 8] : xa, s1 = l8 ? xa - x[n + 8] : xa;
+    const v2 s2 = l12 ? xb + x[n + 12] : xb, u3 = swap2(l12 ? xb - x[n + 12] : xb);
     y[n] = s0 + s2;
     y[8 + n] = s0 - s2;
     y[4 + n] = u3 * HF_CJ + s1;    // s1 + (-i) t : one packed fma, the swap folds into op_sel
@@ -93,6 +105,7 @@ __device__ __forceinline__ void fft16(const v2 (&x)[16], v2 (&X)[16]) {
     X[m + 12] = u3 * HF_NCJ + s1;  // k' = 3
   }
 }
+__device__ __forceinline__ void fft16(const v2 (&x)[16], v2 (&X)[16]) { fft16_lead<16>(x, X); }
 
 // 32-point complex FFT in registers: one radix-2 decimation-in-frequency stage, then two 16-point FFTs
 //   X[2 k]     = FFT16(x[n] + x[n + 16])[k]

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
     int lane_o = lane;  // opaque copy: keeps LICM from pinning per-lane addresses in VGPRs for the whole kernel
     asm volatile("" : "+v"(lane_o));
     const int q = (lane_o & 15) >> 1, g = 2 * (lane_o >> 4) + (lane_o & 1);  // two frames interleaved per 16-lane row
-    int early_poff[kDSets];
+    f32x4 lt4[kDSets];  // the lane's four table values per set in one 16-byte read (four dword reads at a 16-byte lane stride hit 8 banks)
 
     {
       v2 Z1[8], Z2[8];  // rows k1 = q and q + 8: bins q + 16 k2 and q + 8 + 16 k2
@@ -161,10 +161,8 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
             z[n1] = (t - v2{mu1, mu1}) * win[n1];
           }
         }
-#pragma unroll
-        for (int n1 = NROWS; n1 < 16; ++n1) z[n1] = v2{0.f, 0.f};
         v2 a[16];
-        fft16(z, a);
+        fft16_lead<NROWS>(z, a);  // rows NROWS.. are past the frame: zero, and never read
         if (kRegTwp) {
 #pragma unroll
           for (int k1 = 1; k1 < 16; ++k1) a[k1] = cmul2(a[k1], twpreg[k1]);
@@ -199,9 +197,9 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
         }
-        // the power-row offsets of this lane's filterbank slots, a phase early (no dependent LDS look-up in front of the operand reads)
+        // the lane-table entries of this lane's filterbank slots, a phase early (no dependent LDS look-up in front of the operand reads)
 #pragma unroll
-        for (int s = 0; s < kDSets; ++s) early_poff[s] = __builtin_bit_cast(int, ltab[s * 256 + 4 * lane_o]);
+        for (int s = 0; s < kDSets; ++s) lt4[s] = *reinterpret_cast<const f32x4*>(ltab + s * 256 + 4 * lane_o);
         fft8(b, Z1);
         fft8(b + 8, Z2);
       }
@@ -240,7 +238,8 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
     f32x4 av[kDSets][2][kDSteps / 4], bv[kDSets][kDSteps / 4];
 #pragma unroll
     for (int s = 0; s < kDSets; ++s) {
-      const float* pa = myreg + early_poff[s];
+      const float poff_f = lt4[s][0];  // (by value: __builtin_bit_cast of a vector element reads element 0)
+      const float* pa = myreg + __builtin_bit_cast(int, poff_f);
       const float* wb = wtab + s * (kDSteps * 64) + 4 * lane_o;
 #pragma unroll
       for (int c4 = 0; c4 < kDSteps / 4; ++c4) {
@@ -251,9 +250,9 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
     }
 #pragma unroll
     for (int s = 0; s < kDSets; ++s) {
-      const float* lt = ltab + s * 256 + 4 * lane_o;
-      const int col = __builtin_bit_cast(int, lt[1]);
-      const float m4 = lt[2], m8 = lt[3];
+      const float col_f = lt4[s][1];
+      const int col = __builtin_bit_cast(int, col_f);
+      const float m4 = lt4[s][2], m8 = lt4[s][3];
       f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c4 = 0; c4 < kDSteps / 4; ++c4) {

@@ -69,6 +69,71 @@ struct Fft512cParams {
 // lane-index multiplies: v_mul_u32_u24 issues at the full VALU rate, v_mul_lo_u32 at a quarter of it
 __device__ __forceinline__ int mul24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
 
+// The LDS exchange between the two FFT passes of one wave, as ONE instruction sequence: the rows k1 = 0..7 (`lo`, replaced by the
+// result) go through the wave's 8-row blocks and every lane reads "its" row q % 8 back, then the rows k1 = 8..15 (`hi`) go through the
+// same blocks and the lanes with q >= 8 (`hi_lanes`, an exec mask) read their row again, over the first result.  A wave's LDS operations
+// execute and return in order, so nothing has to be waited for in between: half 1's writes follow half 0's reads of the same block
+// through the queue, half 1's reads see half 1's writes, and their data lands in the registers after half 0's.  hipcc, which orders
+// the two loads of one register with a wait, put a full `s_waitcnt lgkmcnt(0)` -- one loaded LDS round trip per round on the wave's
+// serial path -- between half 1's writes and reads.  The one wait at the end covers all of it.  `hi` and the addresses are read by
+// instructions issued after the first loads, so no result register may share theirs (early clobber).
+// wr: LDS byte address of (block of the lane's frame, row 0, column q); rd: of (same block, row q % 8, column 0)
+__device__ __forceinline__ void exchange_halves(unsigned wr, unsigned rd, unsigned long long hi_lanes, v2 (&lo)[8], const v2 (&hi)[8],
+                                                v2 (&up)[8]) {
+  static_assert(kCExRowStride == 34, "the row offsets below are 17 rr (in 8-byte units)");
+  unsigned long long saved;
+  asm volatile(
+      "ds_write2_b64 %[wr], %[l0], %[l1] offset1:17\n\t"
+      "ds_write2_b64 %[wr], %[l2], %[l3] offset0:34 offset1:51\n\t"
+      "ds_write2_b64 %[wr], %[l4], %[l5] offset0:68 offset1:85\n\t"
+      "ds_write2_b64 %[wr], %[l6], %[l7] offset0:102 offset1:119\n\t"
+      "ds_read_b64 %[l0], %[rd]\n\t"
+      "ds_read_b64 %[l1], %[rd] offset:8\n\t"
+      "ds_read_b64 %[l2], %[rd] offset:16\n\t"
+      "ds_read_b64 %[l3], %[rd] offset:24\n\t"
+      "ds_read_b64 %[l4], %[rd] offset:32\n\t"
+      "ds_read_b64 %[l5], %[rd] offset:40\n\t"
+      "ds_read_b64 %[l6], %[rd] offset:48\n\t"
+      "ds_read_b64 %[l7], %[rd] offset:56\n\t"
+      "ds_read_b64 %[u0], %[rd] offset:64\n\t"
+      "ds_read_b64 %[u1], %[rd] offset:72\n\t"
+      "ds_read_b64 %[u2], %[rd] offset:80\n\t"
+      "ds_read_b64 %[u3], %[rd] offset:88\n\t"
+      "ds_read_b64 %[u4], %[rd] offset:96\n\t"
+      "ds_read_b64 %[u5], %[rd] offset:104\n\t"
+      "ds_read_b64 %[u6], %[rd] offset:112\n\t"
+      "ds_read_b64 %[u7], %[rd] offset:120\n\t"
+      "ds_write2_b64 %[wr], %[h0], %[h1] offset1:17\n\t"
+      "ds_write2_b64 %[wr], %[h2], %[h3] offset0:34 offset1:51\n\t"
+      "ds_write2_b64 %[wr], %[h4], %[h5] offset0:68 offset1:85\n\t"
+      "ds_write2_b64 %[wr], %[h6], %[h7] offset0:102 offset1:119\n\t"
+      "s_and_saveexec_b64 %[sv], %[hm]\n\t"
+      "ds_read_b64 %[l0], %[rd]\n\t"
+      "ds_read_b64 %[l1], %[rd] offset:8\n\t"
+      "ds_read_b64 %[l2], %[rd] offset:16\n\t"
+      "ds_read_b64 %[l3], %[rd] offset:24\n\t"
+      "ds_read_b64 %[l4], %[rd] offset:32\n\t"
+      "ds_read_b64 %[l5], %[rd] offset:40\n\t"
+      "ds_read_b64 %[l6], %[rd] offset:48\n\t"
+      "ds_read_b64 %[l7], %[rd] offset:56\n\t"
+      "ds_read_b64 %[u0], %[rd] offset:64\n\t"
+      "ds_read_b64 %[u1], %[rd] offset:72\n\t"
+      "ds_read_b64 %[u2], %[rd] offset:80\n\t"
+      "ds_read_b64 %[u3], %[rd] offset:88\n\t"
+      "ds_read_b64 %[u4], %[rd] offset:96\n\t"
+      "ds_read_b64 %[u5], %[rd] offset:104\n\t"
+      "ds_read_b64 %[u6], %[rd] offset:112\n\t"
+      "ds_read_b64 %[u7], %[rd] offset:120\n\t"
+      "s_mov_b64 exec, %[sv]\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : [l0] "+&v"(lo[0]), [l1] "+&v"(lo[1]), [l2] "+&v"(lo[2]), [l3] "+&v"(lo[3]), [l4] "+&v"(lo[4]), [l5] "+&v"(lo[5]),
+        [l6] "+&v"(lo[6]), [l7] "+&v"(lo[7]), [u0] "=&v"(up[0]), [u1] "=&v"(up[1]), [u2] "=&v"(up[2]), [u3] "=&v"(up[3]),
+        [u4] "=&v"(up[4]), [u5] "=&v"(up[5]), [u6] "=&v"(up[6]), [u7] "=&v"(up[7]), [sv] "=&s"(saved)
+      : [h0] "v"(hi[0]), [h1] "v"(hi[1]), [h2] "v"(hi[2]), [h3] "v"(hi[3]), [h4] "v"(hi[4]), [h5] "v"(hi[5]), [h6] "v"(hi[6]),
+        [h7] "v"(hi[7]), [wr] "v"(wr), [rd] "v"(rd), [hm] "s"(hi_lanes)
+      : "memory", "scc");
+}
+
 // NROWS: pass-1 rows that can hold samples; NFULL: rows known to lie entirely inside the frame (N >= 32 NFULL): no length masks there;
 // MODE 0: log-mel filterbank on 2 accumulator sets x 16 steps (many narrow filters: the 80-filter default); 1: log-mel on 1 set x 32
 // steps (few, wide filters: 23 / 40); 2: MFCC = mode 1 + the DCT as a second run of 4 x 4 x 1 blocks (Wav2MFCC, layers.py:708-724);
@@ -220,7 +285,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
     asm volatile("" : "+v"(lane_o));
     const int q = lane_o & 15, g = lane_o >> 4;
 
-    int early_poff[2] = {0, 0};
+    f32x4 lt4[2];  // the lane's four table values per set in one 16-byte read (four dword reads at a 16-byte lane stride hit 8 banks)
     v2 Z[16];
     {
       const float* x = xs + mul24(g, shift) + 2 * q;
@@ -232,16 +297,20 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
         z[n1] = *reinterpret_cast<const v2*>(x + 32 * n1);
         HFC_SEP();
       }
+      float pv[NROWS];  // left neighbour of each pair's first sample (the frame's first sample replicates itself)
+#pragma unroll
+      for (int n1 = 0; n1 < NROWS; ++n1) pv[n1] = n1 == 0 ? x[q == 0 ? 0 : -1] : x[32 * n1 - 1];
+      HFC_SEP();
+      // the window comes last: its NROWS reads (one ds_read_b64 each, kept apart and in place by the separators) do not touch the span
 #pragma unroll
       for (int n1 = 0; n1 < NROWS; ++n1) {
         win[n1] = cwin[n1 * 16 + q];
         HFC_SEP();
       }
-      float pv[NROWS];  // left neighbour of each pair's first sample (the frame's first sample replicates itself)
-#pragma unroll
-      for (int n1 = 0; n1 < NROWS; ++n1) pv[n1] = n1 == 0 ? x[q == 0 ? 0 : -1] : x[32 * n1 - 1];
-      // the samples are in flight to registers; once they have arrived the buffer is free for the next round's span
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      // the samples are in flight to registers; once they have arrived the buffer is free for the next round's span.  LDS reads return in
+      // order, so a count that leaves only the window reads outstanding has seen every read of the span; hipcc's own counted waits cover
+      // the window registers where they are first used.
+      asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NROWS < 15 ? NROWS : 15) : "memory");  // (the counter has 4 bits)
       HFC_T(1);  // sample + window reads
       if (FLAT) {
         if (r + 1 < p.rounds && quad_n < p.total_quads) stage_span(cd_n, f0_n, (unsigned)lane_o * 4u);
@@ -287,10 +356,8 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
           z[n1] = (t - v2{mu1, mu1}) * win[n1];
         }
       }
-#pragma unroll
-      for (int n1 = NROWS; n1 < 16; ++n1) z[n1] = v2{0.f, 0.f};
       v2 a[16];
-      fft16(z, a);
+      fft16_lead<NROWS>(z, a);  // rows NROWS.. are past the frame: zero, and never read
       // pass twiddles W_256^(q k1): fetched from LDS in two bursts of 8 (one latency exposure each)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -318,29 +385,22 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
 #pragma unroll
       for (int n2 = 0; n2 < 16; ++n2) b[n2] = a[n2];
 #else
+      {
+        typedef __attribute__((address_space(3))) float lds_float;
+        v2 lo[8], hi[8], up[8];
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
+        for (int rr = 0; rr < 8; ++rr) lo[rr] = a[rr], hi[rr] = a[8 + rr];
+        exchange_halves((unsigned)(size_t)(lds_float*)(exf + 2 * q), (unsigned)(size_t)(lds_float*)(exf + mul24(q % 8, kCExRowStride)),
+                        __builtin_amdgcn_ballot_w64(q >= 8), lo, hi, up);
 #pragma unroll
-        for (int rr = 0; rr < 8; ++rr) *reinterpret_cast<v2*>(exf + rr * kCExRowStride + 2 * q) = a[8 * h + rr];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (h == 0 || q >= 8) {  // half 0: every lane reads (b is never undefined: nothing for hipcc to carry around the round loop); half 1: lanes 8.. replace it
-#pragma unroll
-          for (int n2 = 0; n2 < 16; ++n2) {
-            b[n2] = *reinterpret_cast<const v2*>(exf + (q % 8) * kCExRowStride + 2 * n2);
-            HFC_SEP();
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        for (int n2 = 0; n2 < 8; ++n2) b[n2] = lo[n2], b[8 + n2] = up[n2];
       }
 #endif
       HFC_T(3);  // exchange
-      // the power-row offsets of this lane's filterbank slots are requested here, a phase early: the operand reads of the mel phase then
+      // the lane-table entries of this lane's filterbank slots are requested here, a phase early: the operand reads of the mel phase then
       // start without a dependent LDS look-up in front of them (+ 0.6 %)
-      early_poff[0] = __builtin_bit_cast(int, ltab[4 * lane_o]);
-      if (MODE == 0) early_poff[1] = __builtin_bit_cast(int, ltab[256 + 4 * lane_o]);
+#pragma unroll
+      for (int s = 0; s < (MODE == 0 ? kCMaxSets : 1); ++s) lt4[s] = *reinterpret_cast<const f32x4*>(ltab + s * 256 + 4 * lane_o);
       fft16(b, Z);
     }
 
@@ -423,11 +483,11 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
     float lt_m4[S], lt_m8[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      const float* lt = ltab + s * 256 + 4 * lane_o;
-      lt_poff[s] = early_poff[s];
-      lt_col[s] = __builtin_bit_cast(int, lt[1]);
-      lt_m4[s] = lt[2];
-      lt_m8[s] = lt[3];
+      const float poff_f = lt4[s][0], col_f = lt4[s][1];  // (by value: __builtin_bit_cast of a vector element reads element 0)
+      lt_poff[s] = __builtin_bit_cast(int, poff_f);
+      lt_col[s] = __builtin_bit_cast(int, col_f);
+      lt_m4[s] = lt4[s][2];
+      lt_m8[s] = lt4[s][3];
     }
     f32x4 av[S][T / 4], bv[S][T / 4];
 #pragma unroll
