@@ -32,6 +32,7 @@
 #include "kernel_specaug.hpp"
 #include "kernel_whisper2.hpp"
 #include "kernel_whisper3.hpp"
+#include "layout_rounds.hpp"
 #include "kernel_fft256.hpp"
 #include "kernel_fft256c.hpp"
 #include "kernel_wave.hpp"
@@ -823,43 +824,21 @@ static hipfeat_status build_descs(const hipfeat_plan* plan, int64_t batch, const
     row += T;
     lay->num_frames[(size_t)b] = T;
   }
-  // frames per workgroup: fixed by the plan, or (wave-autonomous kernels) rounds x fpb_unit.  A workgroup pays a fixed start-up (the
-  // constant image, its first, un-overlapped span: ~0.64 of a round, from the 8-vs-16-rounds A/B of round 3), its last round-set is
-  // only partly filled (a cut's frames are not shared between workgroups), and the launch runs in ceil(workgroups / resident slots)
-  // waves of workgroups: the rounds that minimise  waves x (start-up + rounds).  10 000 x 1000 frames end up at the maximum (16: two
-  // workgroups per cut, start-up amortised); LibriSpeech-like lengths (mean 1230 frames) at 8 (16 would leave the third workgroup of a
-  // cut 60 % empty); a 600 s mini-batch (60 000 frames) at 4 rounds in ONE wave of ~470 workgroups instead of two waves of 2-round
-  // workgroups (round 3's rule: the largest power of two that still gave four waves, else 2).  Evaluated on at most 512 evenly spaced
-  // cuts of the batch (a transient layout is built per call).
+  // frames per workgroup: fixed by the plan, or (wave-autonomous kernels) rounds x fpb_unit with the rounds that minimise
+  // waves x (start-up + rounds) for this batch (layout_rounds.hpp; round 3's rule: the largest power of two that still gave four waves,
+  // else 2)
   int fpb = plan->fpb;
   if (plan->fpb_unit > 0) {
     static const int forced = exp_env("HIPFEAT_ROUNDS") ? atoi(exp_env("HIPFEAT_ROUNDS")) : 0;
     static const bool old_rule = exp_env("HIPFEAT_ROUNDS_R3") != nullptr;
-    const int64_t slots = 256LL * std::max(plan->blocks_per_cu, 1);
-    const int64_t stride = std::max<int64_t>(1, batch / 512);
-    auto workgroups = [&](int rounds, int64_t step) {  // (estimate for step > 1)
-      const int64_t per = (int64_t)plan->fpb_unit * rounds;
-      int64_t nb = 0, n = 0;
-      for (int64_t b = 0; b < batch; b += step, ++n) nb += (lay->num_frames[(size_t)b] + per - 1) / per;
-      return step == 1 ? nb : (nb * batch + n / 2) / std::max<int64_t>(n, 1);
-    };
     int rounds = plan->c_rounds_max;
     if (forced >= 1 && forced <= plan->c_rounds_max) {
       rounds = forced;
     } else if (old_rule) {
       for (; rounds > 2; rounds >>= 1)
-        if (workgroups(rounds, 1) >= 4 * slots) break;
+        if (layout_workgroups_per_cut(lay->num_frames.data(), batch, plan->fpb_unit, rounds, 1) >= 4 * layout_slots(plan->blocks_per_cu)) break;
     } else {
-      double best = -1.0;
-      for (int r = std::min(2, plan->c_rounds_max); r <= plan->c_rounds_max; ++r) {
-        const int64_t nb = workgroups(r, stride);
-        const double waves = nb >= 8 * slots ? (double)nb / (double)slots : (double)((nb + slots - 1) / slots);  // (many waves: the last one hardly matters)
-        const double cost = waves * (0.64 + r);
-        if (best < 0.0 || cost <= best * (1.0 + 1e-9)) {  // ties go to the larger workgroup
-          best = cost;
-          rounds = r;
-        }
-      }
+      rounds = layout_rounds_per_cut(lay->num_frames.data(), batch, plan->fpb_unit, plan->c_rounds_max, plan->blocks_per_cu);
     }
     fpb = plan->fpb_unit * rounds;
   }
@@ -879,23 +858,9 @@ static hipfeat_status build_descs(const hipfeat_plan* plan, int64_t batch, const
       quads += (lay->num_frames[(size_t)b] + 3) / 4;
     }
     static const int forced = exp_env("HIPFEAT_ROUNDS") ? atoi(exp_env("HIPFEAT_ROUNDS")) : 0;
-    const int64_t slots = 256LL * std::max(plan->blocks_per_cu, 1);
     const int waves_per_wg = plan->fpb_unit / 4;  // a wave takes one quad per round
-    int rounds = plan->c_rounds_max;
-    if (forced >= 1 && forced <= plan->c_rounds_max) {
-      rounds = forced;
-    } else {
-      double best = -1.0;
-      for (int r = std::min(2, plan->c_rounds_max); r <= plan->c_rounds_max; ++r) {
-        const int64_t nb = (quads + (int64_t)waves_per_wg * r - 1) / ((int64_t)waves_per_wg * r);
-        const double waves = nb >= 8 * slots ? (double)nb / (double)slots : (double)((nb + slots - 1) / slots);
-        const double cost = waves * (0.64 + r);
-        if (best < 0.0 || cost <= best * (1.0 + 1e-9)) {
-          best = cost;
-          rounds = r;
-        }
-      }
-    }
+    const int rounds = forced >= 1 && forced <= plan->c_rounds_max ? forced
+                                                                   : layout_rounds_quads(quads, plan->fpb_unit, plan->c_rounds_max, plan->blocks_per_cu);
     fpb = plan->fpb_unit * rounds;
     const int64_t qpw = (int64_t)waves_per_wg * rounds;
     blocks = (quads + qpw - 1) / qpw;
