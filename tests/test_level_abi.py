@@ -125,6 +125,26 @@ def test_plan_time_errors_are_decided_on_the_host(shim):
     assert "item 0" in msg and "1 ..." in msg
 
 
+def test_offsets_past_2_31_travel_unchanged_and_overlaps_up_there_are_seen(shim):
+    """64-bit offsets: nothing of the table or of the overlap checks may pass through an int (tests/test_gpu_large_offsets.py runs the
+    kernels on such tables)."""
+    far, farther = 2 ** 31 + 1, 2 ** 40
+    st, info, items, msg = plan(shim, [far, farther, 5], [4099, 70001, 8], [[VOL], [CLIP], [VOL]], dst=[far, farther + 70001, far + 4099])
+    assert st == OK, msg
+    assert items["src_off"].tolist() == [far, farther, 5] and items["dst_off"].tolist() == [far, farther + 70001, far + 4099]
+    assert items["len"].tolist() == [4099, 70001, 8] and items["item_first"].tolist() == [0, 2, 20]  # (far & 3 = 1: 1 + 4099 samples: 2 tiles)
+    assert info.tolist() == [0, farther + 2 * 70001, 18, 21]
+    # the same refusals as for small offsets (test_plan_time_errors_are_decided_on_the_host), with every range behind 2^31 / 2^40
+    for base in (far, farther):
+        assert plan(shim, [base, base + 8], [8, 8], [[VOL], [VOL]])[0] == OK
+        st, _, _, msg = plan(shim, [base, base + 7], [8, 8], [[VOL], [VOL]])
+        assert st == INVALID and "overlap" in msg, msg
+        assert plan(shim, [base], [8], [[VOL]], dst=[base + 7])[0] == INVALID and plan(shim, [base], [8], [[VOL]], dst=[base + 8])[0] == OK
+        assert plan(shim, [0, base], [8, 8], [[VOL], [VOL]], dst=[base + 4, 2 * base])[0] == INVALID  # item 0 writes what item 1 reads
+        assert plan(shim, [base, base + 2 ** 32], [8, 8], [[VOL], [VOL]])[0] == OK  # equal lower dwords are not an overlap
+    assert plan(shim, [0], [2 ** 30], [[VOL]])[0] == INVALID and plan(shim, [farther], [2 ** 30 - 1], [[VOL]])[0] == OK  # INT32_MAX / 2 samples
+
+
 def test_zero_items_plan_nothing_to_launch(shim):
     st, info, items, msg = plan(shim, [], [], [])
     assert st == OK and info.tolist() == [0, 0, 0, 0]
