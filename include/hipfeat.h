@@ -41,7 +41,8 @@ extern "C" {
 #define HIPFEAT_API
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
- * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES next to _SIGNATURES). */
+ * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES and _COLLATE_SIGNATURES next to _SIGNATURES). */
+#define HIPFEAT_COLLATE_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
 
 typedef enum hipfeat_status {
@@ -427,6 +428,42 @@ HIPFEAT_LEVEL_API hipfeat_status hipfeat_level_plan(hipfeat_level* level, int64_
                                               const int64_t* h_dst_offset, const int64_t* h_op_first, const int32_t* h_op_kind,
                                               const float* h_op_value, const int32_t* h_op_flags, int64_t* h_info);
 HIPFEAT_LEVEL_API hipfeat_status hipfeat_level_run(hipfeat_level* level, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
+
+/* ---- collation of cuts on the device (additive to ABI v8) ----------------------------------------------------------- */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_collate_*; as with hipfeat_level_*, the version number did not change
+ * because nothing that existed changed.
+ *
+ * collate_audio (lhotse/dataset/collation.py:148-260) pads the cuts of a mini-batch to the longest one (cuts.pad) and stacks them with
+ * collate_vectors(..., padding_value=0.0); it is what AudioSamples.__call__ (lhotse/dataset/input_strategies.py:208-299) returns and what
+ * return_audio=True of the feature input strategies collates on the host.  Here the cuts already lie in ONE device arena (where the
+ * augmentation chain left them) and ONE launch writes the dense zero-padded tensor; no value visits the host.
+ * Row r of `out` (num_rows x row_len elements, dense) receives the h_src_len[r] float32 samples at arena + h_src_offset[r], starting at
+ * element h_dst_offset[r] of the row (NULL = 0 for every row: right padding; row_len - h_src_len[r]: left padding).  Every other element
+ * of the row is written as +0.  Every element of out[0 : num_rows * row_len] is written exactly once by the launch (no memset in front of
+ * it), nothing outside that range is written and nothing of the arena is written.  out_type 0 = float32: a bit copy; 1 = binary16,
+ * 2 = bfloat16: one round-to-nearest-even conversion per sample (the value torch's .to(dtype) gives).  All element indexing is 64-bit.
+ *
+ * hipfeat_collate_create / _destroy: the object that owns the staged row table on `device`; calls are serialised inside, up to 16 plans
+ * may be outstanding, destroy waits for the work it enqueued.
+ * hipfeat_collate_plan (host only).  h_info[4] = {ticket, floats the arena must hold (rows of no samples do not count), elements `out`
+ * must hold (num_rows * row_len), work items}.  A negative h_src_offset or h_dst_offset, h_src_len < 0, row_len < 0, num_rows < 0,
+ * h_dst_offset + h_src_len > row_len, num_rows * row_len or h_src_offset + h_src_len beyond INT64_MAX, an unknown out_type, a 17th plan
+ * while 16 are planned and not yet run: HIPFEAT_ERR_INVALID, and nothing is planned.  h_src_len == 0 (a row of padding only) and
+ * num_rows == 0 (a plan whose run launches nothing) are valid.
+ * hipfeat_collate_run enqueues the launch of a planned collation on `stream` (a ticket runs once).  An unknown ticket, arena_floats <
+ * h_info[1], out_elements < h_info[2], or an `out` whose byte range [d_out, d_out + out_elements * size) overlaps the arena's
+ * [d_arena, d_arena + 4 * arena_floats): HIPFEAT_ERR_INVALID, and nothing is launched.  The arena starts on a 16-byte boundary, `out` on
+ * a multiple of its element size.  A ticket is consumed when its launch has been enqueued: after a HIPFEAT_ERR_HIP from an allocation
+ * or the table copy in front of it, it can be run again.
+ */
+typedef struct hipfeat_collate hipfeat_collate;
+HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_create(int32_t device, hipfeat_collate** collate);
+HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_destroy(hipfeat_collate* collate);
+HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_collate* collate, int64_t num_rows, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                        const int64_t* h_dst_offset, int64_t row_len, int32_t out_type, int64_t* h_info);
+HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collate* collate, int64_t ticket, const float* d_arena, int64_t arena_floats, void* d_out,
+                                                       int64_t out_elements, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

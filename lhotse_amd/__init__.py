@@ -17,6 +17,7 @@ from .extractors import (  # noqa: F401
 
 from .augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_arena, reverb_tail_floats  # noqa: F401,E402
 from .augmentation import HipClipping, HipLevel, HipVolume, get_or_create_level, level_in_arena  # noqa: F401,E402
+from .augmentation import COLLATE_TILE, HipCollator, collate_in_arena, get_or_create_collator, left_pad_offsets  # noqa: F401,E402
 from .augmentation import resample_in_arena, resample_layout, resampled_tail_floats  # noqa: F401,E402
 from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
 
@@ -29,7 +30,7 @@ from .kaldifeat import (  # noqa: F401,E402
     HipKaldifeatMfccConfig,
 )
 
-from .input_strategies import HipOnTheFlyFeatures  # noqa: F401,E402
+from .input_strategies import FusedAudioBatch, HipAudioSamples, HipOnTheFlyFeatures  # noqa: F401,E402
 
 from .whisper import HipWhisperFbank, HipWhisperFbankConfig  # noqa: F401,E402
 
@@ -80,6 +81,13 @@ __all__ = [
     "HipClipping",
     "get_or_create_level",
     "level_in_arena",
+    "COLLATE_TILE",
+    "HipCollator",
+    "collate_in_arena",
+    "get_or_create_collator",
+    "left_pad_offsets",
+    "FusedAudioBatch",
+    "HipAudioSamples",
     "resample_in_arena",
     "resample_layout",
     "resampled_tail_floats",

@@ -131,9 +131,21 @@ _LEVEL_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     "hipfeat_level_run": ("int", ["hipfeat_level*", "int64_t", "float*", "int64_t", "void*"]),
 }
 
+# Likewise (HIPFEAT_COLLATE_API in the header).
+_COLLATE_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_collate_create": ("int", ["int32_t", "hipfeat_collate**"]),
+    "hipfeat_collate_destroy": ("int", ["hipfeat_collate*"]),
+    "hipfeat_collate_plan": (
+        "int",
+        ["hipfeat_collate*", "int64_t", "const int64_t*", "const int64_t*", "const int64_t*", "int64_t", "int32_t", "int64_t*"],
+    ),
+    "hipfeat_collate_run": ("int", ["hipfeat_collate*", "int64_t", "const float*", "int64_t", "void*", "int64_t", "void*"]),
+}
+_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES}
+
 
 def _signature(name: str) -> Tuple[str, List[str]]:
-    return _SIGNATURES[name] if name in _SIGNATURES else _LEVEL_SIGNATURES[name]
+    return _SIGNATURES[name] if name in _SIGNATURES else _ADDED_SIGNATURES[name]
 
 
 # numpy mirror of `struct hipfeat_config` (include/hipfeat.h); field order and sizes must match.
@@ -190,7 +202,7 @@ class _CtypesBackend:
     def __init__(self, path: str):
         self.dll = ctypes.CDLL(path)
         self.fns = {}
-        for name, (ret, args) in list(_SIGNATURES.items()) + list(_LEVEL_SIGNATURES.items()):
+        for name, (ret, args) in list(_SIGNATURES.items()) + list(_ADDED_SIGNATURES.items()):
             fn = getattr(self.dll, name)  # AttributeError here == a symbol the header declares is missing
             fn.restype = ctypes.c_char_p if ret == "const char*" else self._SCALARS[ret]
             fn.argtypes = [ctypes.c_void_p if _is_ptr(a) else self._SCALARS[a] for a in args]
@@ -220,7 +232,7 @@ class _CffiBackend:
             s = line.strip()
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
-            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", ""))
+            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}
@@ -237,7 +249,7 @@ class _CffiBackend:
 
     def _fn(self, name: str):
         fn = self.fns.get(name)
-        if fn is None:  # an entry point of _LEVEL_SIGNATURES: looked up at its first use
+        if fn is None:  # an entry point of _LEVEL_SIGNATURES / _COLLATE_SIGNATURES: looked up at its first use
             fn = self.fns[name] = getattr(self.dll, name)
         return fn
 

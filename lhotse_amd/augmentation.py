@@ -941,3 +941,142 @@ class HipClipping(AudioTransform):
     def reverse_timestamps(self, offset, duration, sampling_rate):
         """Clipping changes no timing (clipping.py:63-67)."""
         return offset, duration
+
+
+# ---- collation: the cuts of the arena as ONE dense zero-padded (B, row_len) tensor ----------------------------------------------
+COLLATE_TILE = 4096  # output elements per work item of the collate launch (kCoTile)
+_COLLATE_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def left_pad_offsets(lengths, row_len: int) -> np.ndarray:
+    """Destination offsets that put every cut at the END of its row (``pad_direction="left"``): ``row_len - lengths``."""
+    sl = _lib.i64(lengths)
+    if len(sl) and int(sl.max()) > int(row_len):
+        raise ValueError(f"a cut of {int(sl.max())} samples does not fit a row of {int(row_len)}")
+    return int(row_len) - sl
+
+
+def collate_layout(arena_floats: int, offsets, lengths, row_len: Optional[int] = None, dst_offsets=None):
+    """The host arithmetic of ``collate_in_arena`` -> ``(src_offsets, lengths, dst_offsets, row_len)`` as int64; raises ``ValueError``
+    for what no launch could serve (tables of unequal length, negative entries, a cut that does not fit its row or the arena)."""
+    so, sl = _lib.i64(offsets), _lib.i64(lengths)
+    if so.ndim != 1 or so.shape != sl.shape:
+        raise ValueError("collate tables: one offset and one length per row")
+    if row_len is None:
+        row_len = int(sl.max()) if len(sl) else 0
+    row_len = int(row_len)
+    do = np.zeros(len(so), dtype=np.int64) if dst_offsets is None else _lib.i64(dst_offsets)
+    if do.shape != so.shape:
+        raise ValueError("collate tables: one destination offset per row")
+    if row_len < 0 or (len(so) and (int(so.min()) < 0 or int(sl.min()) < 0 or int(do.min()) < 0)):
+        raise ValueError("collate tables: negative offset, length or row length")
+    if len(so) and int((do + sl).max()) > row_len:
+        raise ValueError(f"a cut reaches to element {int((do + sl).max())} of a row of {row_len}")
+    need = int((so + sl)[sl > 0].max()) if (sl > 0).any() else 0
+    if need > int(arena_floats):
+        raise ValueError(f"arena too small: {int(arena_floats)} floats, the cuts reach to {need}")
+    return so, sl, do, row_len
+
+
+class HipCollator:
+    """The device half of ``collate_audio`` (lhotse/dataset/collation.py:148-260) for a packed mini-batch: ``hipfeat_collate``
+    (include/hipfeat.h) owns the staged row table of the one launch.  One object per device (``get_or_create_collator``); it may be
+    shared by threads."""
+
+    def __init__(self, device: Union[str, torch.device, None] = None):
+        self.lib = _lib.load()
+        self.handle = 0
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.HipFeatError(1, f"HipCollator runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        out = np.zeros(1, dtype=np.uint64)
+        self.lib.check("hipfeat_collate_create", int(self.device.index), _lib.addr(out))
+        self.handle = int(out[0])
+        self._lock = threading.Lock()
+
+    def plan(self, src_offsets, src_lens, dst_offsets, row_len: int, dtype: torch.dtype = torch.float32):
+        """Host only -> (ticket, info = [ticket, arena floats needed, elements of out, work items])."""
+        if dtype not in _COLLATE_TYPES:
+            raise ValueError(f"collate: float32, float16 or bfloat16 output, got {dtype}")
+        so, sl = _lib.i64(src_offsets), _lib.i64(src_lens)
+        do = None if dst_offsets is None else _lib.i64(dst_offsets)
+        if len(so) != len(sl) or (do is not None and len(do) != len(so)):
+            raise ValueError("collate tables: one entry per row in every table")
+        info = np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_collate_plan", self.handle, len(so), _lib.addr(so), _lib.addr(sl), _lib.addr(do), int(row_len), _COLLATE_TYPES[dtype],
+                           _lib.addr(info))
+        return int(info[0]), info
+
+    def run(self, ticket: int, arena: torch.Tensor, out: torch.Tensor, stream: Optional[int] = None) -> None:
+        assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
+        assert out.is_contiguous() and out.device == self.device
+        with torch.cuda.device(self.device):
+            self.lib.check("hipfeat_collate_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), out.data_ptr(), out.numel(),
+                           int(_raw_stream(arena.device) if stream is None else stream))
+
+    def close(self):
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_collate_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_collators: Dict[int, HipCollator] = {}
+
+
+def get_or_create_collator(device: Union[str, torch.device, None] = None) -> HipCollator:
+    dev = torch.device("cuda" if device is None else device)
+    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    with _cache_lock:
+        r = _collators.get(int(index))
+        if r is None:
+            r = _collators[int(index)] = HipCollator(torch.device(dev.type, index))
+        return r
+
+
+def collate_in_arena(arena: torch.Tensor, offsets, lengths, row_len: Optional[int] = None, dst_offsets=None, dtype: torch.dtype = torch.float32,
+                     out: Optional[torch.Tensor] = None, collator: Optional[HipCollator] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """The cuts of a device-resident packed mini-batch as ONE dense zero-padded tensor (``collate_audio``, lhotse/dataset/collation.py:148-260);
+    what follows ``perturb_speed_in_arena`` / ``level_in_arena`` / ``reverb_in_arena`` / ``mix_in_arena`` when the consumer wants samples.
+
+    Row ``i`` of the result receives the ``lengths[i]`` samples at ``offsets[i]`` of ``arena`` (ONE float32 device buffer), starting at
+    element ``dst_offsets[i]`` (``None``: 0, right padding; ``left_pad_offsets(lengths, row_len)``: left padding; "both" is the caller's
+    arithmetic, lhotse halves a duration there, lhotse/cut/set.py:3314-3322); everything else of the row is +0.  ``row_len=None``: the
+    longest cut (0 for no rows: an empty (0, 0) tensor, nothing is launched).  ``dtype``: float32 (a bit copy), float16 or bfloat16 (one
+    round-to-nearest-even conversion, as ``.to(dtype)``).  ``out``: a contiguous tensor of ``dtype`` on the arena's device with at least
+    ``B * row_len`` elements that does not overlap the arena; its first ``B * row_len`` elements are the result.  Returns
+    ``(out (B, row_len), lengths as int64 numpy)``.  One launch on the current stream, no memset, no device -> host copy."""
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    if dtype not in _COLLATE_TYPES:
+        raise ValueError(f"collate: float32, float16 or bfloat16 output, got {dtype}")
+    so, sl, do, row_len = collate_layout(arena.numel(), offsets, lengths, row_len, dst_offsets)  # (before anything is planned)
+    rows = len(so)
+    if out is not None:
+        if out.dtype != dtype or out.device != arena.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor on {arena.device}")
+        if out.numel() < rows * row_len:
+            raise ValueError(f"out too small: {out.numel()} elements, {rows} rows of {row_len} take {rows * row_len}")
+        a0, o0 = arena.data_ptr(), out.data_ptr()
+        if a0 < o0 + out.numel() * out.element_size() and o0 < a0 + arena.numel() * 4:  # (a plan that is never run would stay outstanding)
+            raise ValueError("out overlaps the arena")
+        res = out.view(-1)[: rows * row_len].view(rows, row_len)
+    else:
+        res = torch.empty((rows, row_len), dtype=dtype, device=arena.device)
+    if rows * row_len == 0:
+        return res, sl
+    if collator is None:
+        collator = get_or_create_collator(arena.device)
+    ticket, info = collator.plan(so, sl, None if dst_offsets is None else do, row_len, dtype)
+    collator.run(ticket, arena, res)
+    return res, sl

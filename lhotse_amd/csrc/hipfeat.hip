@@ -28,6 +28,7 @@
 #include "kernel_minibatch.hpp"
 #include "kernel_mix.hpp"
 #include "kernel_reverb.hpp"
+#include "kernel_collate.hpp"
 #include "kernel_level.hpp"
 #include "kernel_specaug.hpp"
 #include "kernel_whisper2.hpp"
@@ -2631,6 +2632,140 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_level_run(hipfeat_level* lv, int64
   if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
     (void)hipStreamSynchronize(st);
     return fail(HIPFEAT_ERR_HIP, "level: hipEventRecord failed: %s (the launches were enqueued and have been waited for)", hipGetErrorName(e2));
+  }
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Collation on the device (AudioSamples, return_audio): one launch (kernel_collate.hpp; the table: collate_tables.hpp)
+// --------------------------------------------------------------------------------------
+struct CoSlot {
+  CoPlan plan;
+  void* h = nullptr;  // pinned staging of the row table
+  void* d = nullptr;  // device: the row table
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool busy = false;
+};
+
+struct hipfeat_collate {
+  int device = 0;
+  std::mutex mu;
+  CoSlots tickets;  // which tickets are planned and not yet run (collate_tables.hpp)
+  CoSlot slots[kCoSlots];
+};
+
+extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_create(int32_t device, hipfeat_collate** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "collate pointer is NULL");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  hipfeat_collate* c = new (std::nothrow) hipfeat_collate();
+  if (!c) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  c->device = device;
+  *out = c;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_destroy(hipfeat_collate* c) {
+  if (!c) return HIPFEAT_OK;
+  DeviceGuard g(c->device);
+  for (auto& s : c->slots) {
+    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    if (s.ev) (void)hipEventDestroy(s.ev);
+  }
+  delete c;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_collate* c, int64_t num_rows, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                                   const int64_t* h_dst_offset, int64_t row_len, int32_t out_type, int64_t* h_info) {
+  if (!c || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  // (validated into a local first: a refused table leaves the outstanding plans as they were)
+  CoPlan p = build_collate_plan(num_rows, h_src_offset, h_src_len, h_dst_offset, row_len, out_type);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(c->mu);
+  const int64_t ticket = c->tickets.take();
+  if (ticket < 0)  // (never drop a live plan: its ticket would fail at run)
+    return fail(HIPFEAT_ERR_INVALID, "%d planned collations are outstanding: run ticket %lld first", kCoSlots,
+                (long long)c->tickets.ticket[c->tickets.next_ticket % kCoSlots]);
+  CoSlot& s = c->slots[ticket % kCoSlots];
+  s.plan = std::move(p);
+  h_info[0] = ticket;
+  h_info[1] = s.plan.arena_need;
+  h_info[2] = s.plan.out_need;
+  h_info[3] = s.plan.work_items;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collate* c, int64_t ticket, const float* d_arena, int64_t arena_floats, void* d_out,
+                                                                  int64_t out_elements, void* stream) {
+  if (!c) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  const int slot = c->tickets.slot_of(ticket);
+  if (slot < 0) return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned collation (at most %d plans may be outstanding)", (long long)ticket, kCoSlots);
+  CoSlot& s = c->slots[slot];
+  const CoPlan& p = s.plan;
+  if (arena_floats < p.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the rows read up to %lld", (long long)arena_floats, (long long)p.arena_need);
+  if (out_elements < p.out_need)
+    return fail(HIPFEAT_ERR_INVALID, "out holds %lld elements, the rows take %lld", (long long)out_elements, (long long)p.out_need);
+  if (p.work_items == 0) {  // no rows, or rows of no elements: no launch
+    c->tickets.release(ticket);
+    return HIPFEAT_OK;
+  }
+  const int esz = co_elem_bytes(p.out_type);
+  if (!d_out || (!d_arena && p.arena_need > 0)) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
+  if (reinterpret_cast<uintptr_t>(d_out) & (uintptr_t)(esz - 1)) return fail(HIPFEAT_ERR_INVALID, "out must be aligned to its element size");
+  {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_arena), a1 = a0 + (uintptr_t)arena_floats * 4;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)out_elements * (uintptr_t)esz;
+    if (a0 < o1 && o0 < a1) return fail(HIPFEAT_ERR_INVALID, "out overlaps the arena");
+  }
+  DeviceGuard g(c->device);  // (the ticket stays planned until its launch is enqueued: a failed allocation or copy below leaves it to be run again)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = p.rows.size() * sizeof(CoRow);
+  if (s.busy) {  // the launch that used this slot's device memory last time
+    HIP_TRY(hipEventSynchronize(s.ev));
+    s.busy = false;
+  }
+  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  if (s.cap < bytes) {
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    s.h = s.d = nullptr;
+    s.cap = 0;
+    const size_t cap = std::max<size_t>(bytes * 2, 1 << 14);
+    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&s.d, cap));
+    s.cap = cap;
+  }
+  std::memcpy(s.h, p.rows.data(), bytes);
+  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+  CoArgs a;
+  a.arena = reinterpret_cast<const uint32_t*>(d_arena);
+  a.out = d_out;
+  a.rows = static_cast<const CoRow*>(s.d);
+  a.row_len = p.row_len;
+  a.tiles_per_row = p.tiles_per_row;
+  a.work_items = p.work_items;
+  // a flat 1-D grid over (row, tile); beyond 2^22 workgroups (2^34 elements) the workgroups stride
+  const unsigned grid = (unsigned)std::min<int64_t>(p.work_items, (int64_t)1 << 22);
+  if (p.out_type == kCoF32) hipLaunchKernelGGL(collate_wave_kernel<float>, dim3(grid), dim3(256), 0, st, a);
+  else if (p.out_type == kCoF16) hipLaunchKernelGGL(collate_wave_kernel<__half>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(collate_wave_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, a);
+  hipError_t e1 = hipGetLastError();
+  c->tickets.release(ticket);  // enqueued (or refused by the runtime at launch): the ticket has run
+  hipError_t e2 = hipEventRecord(s.ev, st);
+  s.busy = (e2 == hipSuccess);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "collate launch failed: %s", hipGetErrorName(e1));
+  if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
+    (void)hipStreamSynchronize(st);
+    return fail(HIPFEAT_ERR_HIP, "collate: hipEventRecord failed: %s (the launch was enqueued and has been waited for)", hipGetErrorName(e2));
   }
   return HIPFEAT_OK;
 }

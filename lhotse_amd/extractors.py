@@ -755,6 +755,23 @@ def pack_to_device(items: Sequence[ArrayLike], device: torch.device, stage: Opti
     return wave, offs, lens
 
 
+def pack_items(items: Sequence[ArrayLike], device: torch.device, stage: Optional["_HostStaging"] = None,
+               headroom: int = 0) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+    """``pack_to_device`` for whoever has a device to pack into and no extractor (``_HipExtractor._pack``, ``FusedAudioBatch``); a
+    device that is not a GPU is only reachable with the CPU stand-ins of the tests and packs into a host tensor, no staging needed."""
+    if device.type != "cuda":
+        lens = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
+        padded = (lens + 3) & ~3
+        offs = np.zeros(len(items), dtype=np.int64)
+        np.cumsum(padded[:-1], out=offs[1:])
+        total = int(offs[-1] + lens[-1]) if len(items) else 0
+        host = torch.zeros(total + int(headroom), dtype=torch.float32)
+        for x, o, n in zip(items, offs, lens):
+            host[o : o + n] = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        return host, offs, lens
+    return pack_to_device(items, device, stage, headroom)
+
+
 # --------------------------------------------------------------------------------------
 # shared extractor implementation
 # --------------------------------------------------------------------------------------
@@ -980,16 +997,7 @@ class _HipExtractor(FeatureExtractor):
             if headroom:  # (the conversion wrote a buffer of its own size: one copy, int16 input only)
                 wave = torch.cat([wave, torch.empty(int(headroom), dtype=wave.dtype, device=wave.device)])
             return wave, offs, lens
-        if dev.type != "cuda":  # only reachable with a stand-in plan (tests); no staging needed
-            padded = (lens + 3) & ~3
-            offs = np.zeros(len(items), dtype=np.int64)
-            np.cumsum(padded[:-1], out=offs[1:])
-            total = int(offs[-1] + lens[-1]) if len(items) else 0
-            host = torch.zeros(total + int(headroom), dtype=torch.float32)
-            for x, o, n in zip(items, offs, lens):
-                host[o : o + n] = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-            return host, offs, lens
-        return pack_to_device(items, dev, self._stage(), headroom)
+        return pack_items(items, dev, self._stage() if dev.type == "cuda" else None, headroom)
 
     def _pack_pcm16(self, items: Sequence[ArrayLike], lens: np.ndarray) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
         """int16 PCM items -> one pinned int16 buffer -> H2D (half the bytes) -> float32 on the device."""

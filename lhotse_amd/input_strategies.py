@@ -62,7 +62,13 @@ which cuts qualify -- a new rule: the older ones answer for such cuts what they 
 tracks into a device mix.  A level op in front of the ``Speed``, more than 4 ops or two ``Clipping``s in a block and k outside 2 ... 8 keep the
 reference's path.
 
-Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the class does not.
+Raw audio.  ``AudioSamples`` (lhotse/dataset/input_strategies.py:208-299) and ``return_audio=True`` want the cuts' SAMPLES as one zero-padded
+``(B, Tmax)`` tensor (``collate_audio``, lhotse/dataset/collation.py:148-260).  The chain above leaves them ragged in the arena; one launch
+(``lhotse_amd.augmentation.collate_in_arena``) writes the dense tensor from there.  ``FusedAudioBatch`` is ``FusedMiniBatch`` with that launch in
+place of the feature launch, ``HipAudioSamples`` the drop-in for ``AudioSamples``; ``return_audio_device=None`` (or a device) on
+``HipOnTheFlyFeatures`` collates the audio of ``return_audio`` there too, instead of one blocking copy per cut and a host ``collate_vectors``.
+
+Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the classes does not.
 """
 from __future__ import annotations
 
@@ -123,6 +129,13 @@ def _level_in_arena(arena, src_offsets, src_lens, programs):
     return level_in_arena(arena, src_offsets, src_lens, programs)
 
 
+def _collate_in_arena(arena, offsets, lengths, row_len, dtype):
+    """(indirection for the CPU stand-in of the tests) -> the dense zero-padded (B, row_len) tensor on the arena's device"""
+    from .augmentation import collate_in_arena
+
+    return collate_in_arena(arena, offsets, lengths, row_len=row_len, dtype=dtype)[0]
+
+
 def _is_plain(tracks) -> bool:
     """One track with samples that starts at 0 and is not scaled: the cut IS that track (a MonoCut, speed-perturbed or not; when the
     track carries a reverb, the cut is the reverb's output)."""
@@ -172,76 +185,25 @@ def _level_steps(arena, offs, lens, blocks, sr: int, tail: int):
     return offs, lens, tail
 
 
-class FusedMiniBatch:
-    """The device-facing half of ``HipOnTheFlyFeatures`` -- packing a (partly speed-perturbed) mini-batch into one arena, the launch pair
-    of ``hipfeat_minibatch_*`` (or the per-factor route), the collated feature tensor -- WITHOUT any lhotse type in its interface:
-    plain waveforms, factors and sample counts in, tensors out.  ``HipOnTheFlyFeatures`` inherits these methods unchanged; on a machine
-    without lhotse (the GPU box of the test suite) the class is usable on its own, so that the GPU tests drive the product's code and not
-    a restatement of it (tests/test_gpu_reference_drivers.py holds it to what lhotse's K2SpeechRecognitionDataset returned with the
-    reference's CPU Speed + Fbank on the same files)."""
+class _ArenaChain:
+    """The augmentation chain of a mini-batch in ONE arena -- rate conversion -> speed -> level -> reverb -> level -> mix -- up to where its
+    consumer takes over: ``(arena, cut_off, cut_len)``, the cuts' samples where the chain left them.  The feature launch
+    (``FusedMiniBatch``) and the collate launch (``FusedAudioBatch``) both read from there.  A user says where to pack (``_chain_pack``)
+    and which sampling rates it takes (``_chain_check_sr``)."""
 
-    def __init__(self, extractor, return_audio: bool = False) -> None:
-        if not hasattr(extractor, "extract_collated"):
-            raise TypeError("FusedMiniBatch needs a Hip* extractor (with extract_collated)")
-        self.extractor = extractor
-        self.return_audio = return_audio
+    def _chain_pack(self, items, headroom: int = 0):
+        raise NotImplementedError
 
-    def features_of(self, audios: List[torch.Tensor], factors: List[float], wants: List[int], sampling_rate: int):
-        """What ``HipOnTheFlyFeatures.__call__`` does between reading the audio and returning: ``audios`` as read from the files (the
-        segments in front of a pending ``Speed``), ``factors`` still to be applied (1.0 = none), ``wants`` = samples each cut must end up
-        with (``compute_num_samples(cut.duration)``) -> ``(feats (B, Tmax, F) on the extractor's device, feat_lens)``."""
-        if any(f != 1.0 for f in factors):
-            feats, feat_lens, _ = self._perturb_and_extract(audios, factors, wants, sampling_rate)
-            return feats, feat_lens
-        return self.extractor.extract_collated(audios, sampling_rate=sampling_rate, padding_value=LOG_EPSILON)
+    def _chain_check_sr(self, sr: int) -> None:
+        pass
 
-    def features_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
-        """``features_of`` for a mini-batch in which some cuts are ``MixedCut``s (``CutMix``, ``CutSet.mix`` / ``.pad``), without a lhotse
-        type: every cut is a list of tracks ``(samples, factor, offset_samples, snr, is_reference[, num_samples])`` -- ``samples`` as read
-        from the file (in front of a pending ``Speed(factor)``; 1.0 = none) or, for a ``PaddingCut`` track, its sample COUNT as an int;
-        the track's first sample inside the cut; its SNR in dB or None; whether it is the cut's SNR reference track
-        (``_get_snr_reference_track``, lhotse/cut/mixed.py:1909-1918); optionally the samples the track must end up with after its
-        ``Speed`` (a sample or two are truncated, recording.py:1058-1060).  ``wants[c]`` = samples cut ``c`` must end up with
-        (``cut.num_samples``).  A cut of one unscaled track at offset 0 is a plain cut and is not copied.  An optional 7th element
-        ``(rir_samples, normalize_output)`` reverberates the track (``ReverbWithImpulseResponse`` with a recorded RIR behind the track's
-        ``Speed``, lhotse/augmentation/rir.py:78-153): ``rir_samples`` = the float32 RIR as the reference loads it (channel selected,
-        ``early_only`` applied).  The RIRs of the mini-batch are packed into the arena with the tracks, each distinct one once, scaled by
-        2^-15 on the host; the reverb sees the untruncated resampled track, the mix and the plain cuts read its output.  An optional 8th
-        element ``source_rate``: the samples are at that rate (a pending ``Resample(source_rate -> sampling_rate)`` in front of the
-        ``Speed``, lhotse/augmentation/torchaudio.py:86-139 with the sinc backend) and are resampled to ``sampling_rate`` first, one launch
-        per distinct rate (``lhotse_amd.augmentation.resample_in_arena``); the track's ``Speed`` then is a second pass over the first
-        pass's output, and only the final length is capped (recording.py:486-490).  A mini-batch without a ``source_rate`` takes exactly
-        the route it took before there was one.  An optional 9th element ``(block in front of the reverb, block behind it)`` changes
-        the track's level (``Volume`` / ``Clipping``, ``lhotse_amd.augmentation.level_in_arena``): a block is None or a list of steps
-        ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``, ``("up", k)``, ``("down", k)`` -- the last two are
-        the ``Resample(sr -> k sr)`` / ``Resample(k sr -> sr)`` that ``clip_amplitude(oversampling=k)`` puts around its ``Clipping``; the
-        blocks run behind the ``Speed`` on the untruncated track, the first in front of the reverb, the second behind it.  Absent or
-        None: exactly the route of before.
-
-        Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> convolution and gain launch of
-        the reverberated tracks (``lhotse_amd.augmentation.reverb_in_arena``) -> energy launch -> mix launch
-        (``lhotse_amd.augmentation.mix_in_arena``) -> the feature launch over the mixed offsets / lengths; one arena, one stream, no
-        device -> host copy in between.  Without a mixed cut this IS ``features_of``.
-        -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None."""
-        if len(cuts_tracks) != len(wants):
-            raise ValueError("features_of_tracks: one wanted sample count per cut")
-        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None and _level_of(t[0]) is None for t in cuts_tracks):
-            audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
-            audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
-            if any(f != 1.0 for f in factors):
-                return self._perturb_and_extract(audios, factors, wants, sampling_rate)
-            feats, feat_lens = self.extractor.extract_collated(audios, sampling_rate=sampling_rate, padding_value=LOG_EPSILON)
-            return feats, feat_lens, ([a.reshape(-1) for a in audios] if self.return_audio else None)
-        return self._mix_and_extract(cuts_tracks, wants, sampling_rate)
-
-    def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int):
+    def _tracks_chain(self, cuts_tracks, wants: List[int], sr: int):
         """Pack every track (and every distinct RIR), resample the tracks with a pending factor into the tail, reverberate those with a RIR
-        behind them, mix the mixed cuts behind that, extract."""
+        behind them, mix the mixed cuts behind that -> (arena, cut_off, cut_len).  (Runs under the caller's ``torch.no_grad()``.)"""
         from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout, resample_layout, scaled_rir
         from .extractors import _as_1d_float
 
-        ex = self.extractor
-        ex._check_sr(sr)
+        self._chain_check_sr(sr)
         items, factors, caps, ratios = [], [], [], []  # the tracks that have a source, in cut / track order; ratios: (source rate, sr) or None
         levels = []  # per such track: its two level blocks or None
         rirs, rir_of, rv_idx, rv_rir, rv_norm = [], {}, [], [], []  # distinct scaled RIRs (hs, shift); reverberated tracks -> their RIR
@@ -308,65 +270,154 @@ class FusedMiniBatch:
                 first.append(len(so)), refs.append(ref), cap.append(int(wants[c])), ids.append(c)
             return first, so, sl, do, snrs, refs, cap, ids
 
-        with torch.no_grad():
-            # sizes first, from the lengths alone (the sample counts of the resampled tracks are known on the host, resample.py:309), so
-            # that the tracks are packed straight into the ONE arena everything behind them is written to
-            lens0 = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
-            rs_floats = 0  # the first pass (source rate -> sr), in front of the pass of the speed factors: both count for the head-room
-            if two_pass:
-                _, lens0, rs_floats = resample_layout(np.zeros(len(items), dtype=np.int64), lens0, ratios, 0)  # (a multiple of 4)
-            _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
-            rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) resampled tracks
-            lv_floats = [0, 0]  # what the oversampling passes of the two level blocks write (a level step itself works in place)
-            if has_level:
-                lv_floats = [_level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[w], int(sr), 0)[2] for w in (0, 1)]
-            first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
-            if mixed_ids:
-                short = mixed_num_samples(first, sl, do) < np.asarray(cap, dtype=np.int64)
-                if short.any():
-                    raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
-                                     "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
-            headroom = 3 + rs_floats + res_floats + rv_floats + sum(lv_floats) + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
-            arena, offs, lens = ex._pack(items, headroom=headroom)
-            front = int(offs[-1] + lens[-1])
-            if two_pass:  # the tracks at another rate come to sr behind the pack; the speed pass reads them there
-                offs, lens = _resample_in_arena(arena, offs, lens, ratios, front)
-                front = ((front + 3) & ~3) + rs_floats  # (resample_layout's own end)
+        # sizes first, from the lengths alone (the sample counts of the resampled tracks are known on the host, resample.py:309), so
+        # that the tracks are packed straight into the ONE arena everything behind them is written to
+        lens0 = np.array([int(x.shape[0]) for x in items], dtype=np.int64)
+        rs_floats = 0  # the first pass (source rate -> sr), in front of the pass of the speed factors: both count for the head-room
+        if two_pass:
+            _, lens0, rs_floats = resample_layout(np.zeros(len(items), dtype=np.int64), lens0, ratios, 0)  # (a multiple of 4)
+        _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
+        rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) resampled tracks
+        lv_floats = [0, 0]  # what the oversampling passes of the two level blocks write (a level step itself works in place)
+        if has_level:
+            lv_floats = [_level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[w], int(sr), 0)[2] for w in (0, 1)]
+        first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
+        if mixed_ids:
+            short = mixed_num_samples(first, sl, do) < np.asarray(cap, dtype=np.int64)
+            if short.any():
+                raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
+                                 "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
+        headroom = 3 + rs_floats + res_floats + rv_floats + sum(lv_floats) + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
+        arena, offs, lens = self._chain_pack(items, headroom=headroom)
+        front = int(offs[-1] + lens[-1])
+        if two_pass:  # the tracks at another rate come to sr behind the pack; the speed pass reads them there
+            offs, lens = _resample_in_arena(arena, offs, lens, ratios, front)
+            front = ((front + 3) & ~3) + rs_floats  # (resample_layout's own end)
+        if any(f != 1.0 for f in factors):
+            po, pl = _perturb_in_arena(arena, offs, lens, factors, sr, front)
+        else:
+            po, pl = offs, lens
+        mix_start = ((front + 3) & ~3) + res_floats  # behind the resampled tracks (perturbed_layout's own end)
+        if has_level:  # the block in front of the reverb: on the whole resampled track, as the reference's transforms see it
+            po, pl = np.array(po, dtype=np.int64), np.array(pl, dtype=np.int64)
+            po[:num_tracks], pl[:num_tracks], end = _level_steps(arena, po[:num_tracks], pl[:num_tracks], blocks[0], int(sr), mix_start)
+            assert end == mix_start + lv_floats[0]
+            mix_start = end
+        if len(rv_idx):
+            # the reverb sees the whole resampled track and takes its powers over that length; the sample or two that
+            # assert_and_maybe_fix_num_samples removes come off afterwards (recording.py:1032-1070): `tables` applies the caps
+            ro = _reverb_in_arena(arena, po[rv_idx], pl[rv_idx], [int(po[num_tracks + r]) for r in rv_rir], [len(rirs[r][0]) for r in rv_rir],
+                                  [rirs[r][1] for r in rv_rir], rv_norm, mix_start)
+            po = np.array(po, dtype=np.int64)
+            po[rv_idx] = ro
+            mix_start += rv_floats
+        if has_level:  # the block behind the reverb
+            po[:num_tracks], pl[:num_tracks], end = _level_steps(arena, po[:num_tracks], pl[:num_tracks], blocks[1], int(sr), mix_start)
+            assert end == mix_start + lv_floats[1]
+            mix_start = end
+        first, so, sl, do, snrs, refs, cap, mixed_ids = tables(po, pl)
+        if not mixed_ids:  # (every cut turned out to be one plain track, e.g. a mixed cut whose other tracks are muted: nothing to mix)
+            mo = ml = np.zeros(0, dtype=np.int64)
+        else:
+            mo, ml = _mix_in_arena(arena, first, so, sl, do, snrs, refs, cap, mix_start)
+        cut_off[mixed_ids], cut_len[mixed_ids] = mo, ml
+        return arena, cut_off, cut_len
+
+    def _speed_arena(self, audios: List[torch.Tensor], factors: List[float], sr: int):
+        """Pack the (partly unperturbed) batch into an arena with room for the resampled cuts behind it -> (arena, offsets, lengths, the
+        first float behind the pack)."""
+        from .augmentation import perturbed_tail_floats
+        from .extractors import _as_1d_float
+
+        self._chain_check_sr(sr)
+        items = [_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures") for a in audios]
+        packed, offs, lens = self._chain_pack(items)
+        front = int(packed.numel())
+        arena = torch.empty(((front + 3) & ~3) + perturbed_tail_floats(lens, factors, sr), dtype=torch.float32, device=packed.device)
+        arena[:front].copy_(packed, non_blocking=True)
+        return arena, offs, lens, front
+
+
+class FusedMiniBatch(_ArenaChain):
+    """The device-facing half of ``HipOnTheFlyFeatures`` -- packing a (partly speed-perturbed) mini-batch into one arena, the launch pair
+    of ``hipfeat_minibatch_*`` (or the per-factor route), the collated feature tensor -- WITHOUT any lhotse type in its interface:
+    plain waveforms, factors and sample counts in, tensors out.  ``HipOnTheFlyFeatures`` inherits these methods unchanged; on a machine
+    without lhotse (the GPU box of the test suite) the class is usable on its own, so that the GPU tests drive the product's code and not
+    a restatement of it (tests/test_gpu_reference_drivers.py holds it to what lhotse's K2SpeechRecognitionDataset returned with the
+    reference's CPU Speed + Fbank on the same files)."""
+
+    audio_device: Union[str, torch.device, None] = "cpu"  # where `return_audio` hands the samples out ("cpu": per cut, as host tensors)
+
+    def __init__(self, extractor, return_audio: bool = False, audio_device: Union[str, torch.device, None] = "cpu") -> None:
+        if not hasattr(extractor, "extract_collated"):
+            raise TypeError("FusedMiniBatch needs a Hip* extractor (with extract_collated)")
+        self.extractor = extractor
+        self.return_audio = return_audio
+        self.audio_device = "cpu" if audio_device is not None and torch.device(audio_device).type == "cpu" else audio_device
+
+    def _chain_pack(self, items, headroom: int = 0):
+        return self.extractor._pack(items, headroom=headroom)
+
+    def _chain_check_sr(self, sr: int) -> None:
+        self.extractor._check_sr(sr)
+
+    def features_of(self, audios: List[torch.Tensor], factors: List[float], wants: List[int], sampling_rate: int):
+        """What ``HipOnTheFlyFeatures.__call__`` does between reading the audio and returning: ``audios`` as read from the files (the
+        segments in front of a pending ``Speed``), ``factors`` still to be applied (1.0 = none), ``wants`` = samples each cut must end up
+        with (``compute_num_samples(cut.duration)``) -> ``(feats (B, Tmax, F) on the extractor's device, feat_lens)``."""
+        if any(f != 1.0 for f in factors):
+            return self._perturb_and_extract(audios, factors, wants, sampling_rate)[:2]
+        return self.extractor.extract_collated(audios, sampling_rate=sampling_rate, padding_value=LOG_EPSILON)
+
+    def features_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
+        """``features_of`` for a mini-batch in which some cuts are ``MixedCut``s (``CutMix``, ``CutSet.mix`` / ``.pad``), without a lhotse
+        type: every cut is a list of tracks ``(samples, factor, offset_samples, snr, is_reference[, num_samples])`` -- ``samples`` as read
+        from the file (in front of a pending ``Speed(factor)``; 1.0 = none) or, for a ``PaddingCut`` track, its sample COUNT as an int;
+        the track's first sample inside the cut; its SNR in dB or None; whether it is the cut's SNR reference track
+        (``_get_snr_reference_track``, lhotse/cut/mixed.py:1909-1918); optionally the samples the track must end up with after its
+        ``Speed`` (a sample or two are truncated, recording.py:1058-1060).  ``wants[c]`` = samples cut ``c`` must end up with
+        (``cut.num_samples``).  A cut of one unscaled track at offset 0 is a plain cut and is not copied.  An optional 7th element
+        ``(rir_samples, normalize_output)`` reverberates the track (``ReverbWithImpulseResponse`` with a recorded RIR behind the track's
+        ``Speed``, lhotse/augmentation/rir.py:78-153): ``rir_samples`` = the float32 RIR as the reference loads it (channel selected,
+        ``early_only`` applied).  The RIRs of the mini-batch are packed into the arena with the tracks, each distinct one once, scaled by
+        2^-15 on the host; the reverb sees the untruncated resampled track, the mix and the plain cuts read its output.  An optional 8th
+        element ``source_rate``: the samples are at that rate (a pending ``Resample(source_rate -> sampling_rate)`` in front of the
+        ``Speed``, lhotse/augmentation/torchaudio.py:86-139 with the sinc backend) and are resampled to ``sampling_rate`` first, one launch
+        per distinct rate (``lhotse_amd.augmentation.resample_in_arena``); the track's ``Speed`` then is a second pass over the first
+        pass's output, and only the final length is capped (recording.py:486-490).  A mini-batch without a ``source_rate`` takes exactly
+        the route it took before there was one.  An optional 9th element ``(block in front of the reverb, block behind it)`` changes
+        the track's level (``Volume`` / ``Clipping``, ``lhotse_amd.augmentation.level_in_arena``): a block is None or a list of steps
+        ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``, ``("up", k)``, ``("down", k)`` -- the last two are
+        the ``Resample(sr -> k sr)`` / ``Resample(k sr -> sr)`` that ``clip_amplitude(oversampling=k)`` puts around its ``Clipping``; the
+        blocks run behind the ``Speed`` on the untruncated track, the first in front of the reverb, the second behind it.  Absent or
+        None: exactly the route of before.
+
+        Route of a mini-batch with mixed cuts: pack all tracks -> resample launch per pending factor -> convolution and gain launch of
+        the reverberated tracks (``lhotse_amd.augmentation.reverb_in_arena``) -> energy launch -> mix launch
+        (``lhotse_amd.augmentation.mix_in_arena``) -> the feature launch over the mixed offsets / lengths; one arena, one stream, no
+        device -> host copy in between.  Without a mixed cut this IS ``features_of``.
+        -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None.  With
+        ``return_audio`` and an ``audio_device`` other than ``"cpu"`` (None: the extractor's device): ``(feats, feat_lens, audio (B, Tmax),
+        audio_lens)``, the samples collated on the device out of the arena the feature launch read, with no per-cut copy."""
+        if len(cuts_tracks) != len(wants):
+            raise ValueError("features_of_tracks: one wanted sample count per cut")
+        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None and _level_of(t[0]) is None for t in cuts_tracks):
+            audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
+            audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
             if any(f != 1.0 for f in factors):
-                po, pl = _perturb_in_arena(arena, offs, lens, factors, sr, front)
-            else:
-                po, pl = offs, lens
-            mix_start = ((front + 3) & ~3) + res_floats  # behind the resampled tracks (perturbed_layout's own end)
-            if has_level:  # the block in front of the reverb: on the whole resampled track, as the reference's transforms see it
-                po, pl = np.array(po, dtype=np.int64), np.array(pl, dtype=np.int64)
-                po[:num_tracks], pl[:num_tracks], end = _level_steps(arena, po[:num_tracks], pl[:num_tracks], blocks[0], int(sr), mix_start)
-                assert end == mix_start + lv_floats[0]
-                mix_start = end
-            if len(rv_idx):
-                # the reverb sees the whole resampled track and takes its powers over that length; the sample or two that
-                # assert_and_maybe_fix_num_samples removes come off afterwards (recording.py:1032-1070): `tables` applies the caps
-                ro = _reverb_in_arena(arena, po[rv_idx], pl[rv_idx], [int(po[num_tracks + r]) for r in rv_rir], [len(rirs[r][0]) for r in rv_rir],
-                                      [rirs[r][1] for r in rv_rir], rv_norm, mix_start)
-                po = np.array(po, dtype=np.int64)
-                po[rv_idx] = ro
-                mix_start += rv_floats
-            if has_level:  # the block behind the reverb
-                po[:num_tracks], pl[:num_tracks], end = _level_steps(arena, po[:num_tracks], pl[:num_tracks], blocks[1], int(sr), mix_start)
-                assert end == mix_start + lv_floats[1]
-                mix_start = end
-            first, so, sl, do, snrs, refs, cap, mixed_ids = tables(po, pl)
-            if not mixed_ids:  # (every cut turned out to be one plain track, e.g. a mixed cut whose other tracks are muted: nothing to mix)
-                mo = ml = np.zeros(0, dtype=np.int64)
-            else:
-                mo, ml = _mix_in_arena(arena, first, so, sl, do, snrs, refs, cap, mix_start)
-            cut_off[mixed_ids], cut_len[mixed_ids] = mo, ml
+                return self._perturb_and_extract(audios, factors, wants, sampling_rate)
+            return self._plain_extract(audios, sampling_rate)
+        return self._mix_and_extract(cuts_tracks, wants, sampling_rate)
+
+    def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int):
+        """The chain (``_tracks_chain``), then the feature launch over the cuts where it left them."""
+        ex = self.extractor
+        with torch.no_grad():
+            arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sr)
             zero_pad = getattr(ex.config, "edge_rule", "reflect") == "batch_zero_pad"  # as extract_collated
             padded = np.full(len(cut_len), int(cut_len.max()), dtype=np.int64) if zero_pad else None
             feats, frames = ex.plan.run_collated(arena, cut_off, cut_len, padded, float(LOG_EPSILON))
-        audio = None
-        if self.return_audio:
-            audio = [arena[int(o) : int(o) + int(n)].cpu() for o, n in zip(cut_off, cut_len)]
-        return feats, torch.from_numpy(np.asarray(frames, dtype=np.int64)), audio
+        return (feats, torch.from_numpy(np.asarray(frames, dtype=np.int64))) + self._audio_of_arena(arena, cut_off, cut_len)
 
     def _speed_bank(self, factors, sr: int, device):
         """The bank of the factors met so far on this device (rebuilt when a new factor shows up); None if one of them is not among
@@ -400,20 +451,12 @@ class FusedMiniBatch:
 
     def _perturb_and_extract(self, audios: List[torch.Tensor], factors: List[float], wants: List[int], sr: int):
         """Pack the (partly unperturbed) batch, resample the cuts with a pending factor into the tail of the same buffer, extract."""
-        from .augmentation import perturbed_tail_floats
-        from .extractors import _as_1d_float
-
         ex = self.extractor
-        ex._check_sr(sr)
-        items = [_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures") for a in audios]
         with torch.no_grad():
-            packed, offs, lens = ex._pack(items)
-            front = int(packed.numel())
-            arena = torch.empty(((front + 3) & ~3) + perturbed_tail_floats(lens, factors, sr), dtype=torch.float32, device=packed.device)
-            arena[:front].copy_(packed, non_blocking=True)
+            arena, offs, lens, front = self._speed_arena(audios, factors, sr)
             zero_pad = getattr(ex.config, "edge_rule", "reflect") == "batch_zero_pad"  # as extract_collated
             want = np.ascontiguousarray(wants, dtype=np.int64)
-            bank = self._speed_bank(factors, sr, packed.device) if hasattr(ex.plan, "handle") else None
+            bank = self._speed_bank(factors, sr, arena.device) if hasattr(ex.plan, "handle") else None
             if bank is not None:  # ONE launch for all factors + the padding rows, then the feature launch (hipfeat_minibatch_*)
                 feats, frames, po, pl = bank.extract_collated(ex.plan, arena, np.ascontiguousarray(offs, dtype=np.int64),
                                                               np.ascontiguousarray(lens, dtype=np.int64), bank.index_of(factors), front,
@@ -423,16 +466,106 @@ class FusedMiniBatch:
                 pl = np.minimum(pl, want)  # a sample or two to truncate (recording.py:1058-1060)
                 padded = np.full(len(pl), int(pl.max()), dtype=np.int64) if zero_pad else None
                 feats, frames = ex.plan.run_collated(arena, po, pl, padded, float(LOG_EPSILON))
-        perturbed = None
-        if self.return_audio:
-            perturbed = [arena[int(o) : int(o) + int(n)].cpu() for o, n in zip(po, pl)]
-        return feats, torch.from_numpy(np.asarray(frames, dtype=np.int64)), perturbed
+        return (feats, torch.from_numpy(np.asarray(frames, dtype=np.int64))) + self._audio_of_arena(arena, po, pl)
+
+    def _plain_extract(self, audios, sr: int):
+        """A mini-batch with nothing pending: ``extract_collated``; with ``return_audio`` on a device, the same pack and the same launch
+        with the arena kept for the collate launch."""
+        ex = self.extractor
+        if not (self.return_audio and self.audio_device != "cpu"):
+            feats, feat_lens = ex.extract_collated(audios, sampling_rate=sr, padding_value=LOG_EPSILON)
+            return (feats, feat_lens, ([a.reshape(-1) for a in audios] if self.return_audio else None))
+        from . import _lib
+        from .extractors import _as_1d_float
+
+        ex._check_sr(sr)
+        items = [_as_1d_float(a.squeeze() if a.ndim > 1 else a, "extract_collated()") for a in audios]
+        if not items:
+            raise ValueError("extract_collated(): empty batch")
+        zero_pad = getattr(ex.config, "edge_rule", "reflect") == "batch_zero_pad"
+        with torch.no_grad():
+            arena, offs, lens = ex._pack(items)
+            padded = np.full(len(items), int(lens.max()), dtype=np.int64) if zero_pad else None
+            try:
+                feats, frames = ex.plan.run_collated(arena, offs, lens, padded, float(LOG_EPSILON))
+            except _lib.HipFeatError as e:
+                if e.status == _lib.ERR_TOO_SHORT:
+                    raise ValueError(str(e)) from e
+                raise
+        return (feats, torch.from_numpy(frames)) + self._audio_of_arena(arena, offs, lens)
+
+    def _audio_of_arena(self, arena, cut_off, cut_len) -> tuple:
+        """The ``return_audio`` results of a mini-batch whose cuts lie at cut_off / cut_len of the arena the feature launch read:
+        ``(None,)`` without ``return_audio``; ``audio_device="cpu"``: ``(the cuts' samples as host tensors,)``, one blocking copy per cut;
+        a device or None (the arena's): ``(the dense zero-padded (B, Tmax) tensor there, the lengths)``, one collate launch."""
+        if not self.return_audio:
+            return (None,)
+        if self.audio_device == "cpu":
+            return ([arena[int(o) : int(o) + int(n)].cpu() for o, n in zip(cut_off, cut_len)],)
+        lens = np.asarray(cut_len, dtype=np.int64)
+        audio = _collate_in_arena(arena, cut_off, lens, int(lens.max()) if len(lens) else 0, torch.float32)
+        return (audio if self.audio_device is None else audio.to(self.audio_device), torch.from_numpy(lens.copy()))
+
+
+class FusedAudioBatch(_ArenaChain):
+    """``FusedMiniBatch`` for a consumer of samples (``AudioSamples``: wav2vec 2.0 / HuBERT-style encoders, Whisper fine-tuning with the model's
+    own front end, codec models): the same packing and the same chain in the arena, then ONE collate launch
+    (``lhotse_amd.augmentation.collate_in_arena``) instead of the feature launch.  No lhotse type in its interface, and no extractor: the
+    chain needs a device to pack into, nothing else.  ``dtype``: float32, float16 or bfloat16 samples."""
+
+    def __init__(self, device: Union[str, torch.device, None] = None, dtype: torch.dtype = torch.float32) -> None:
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type == "cuda" and dev.index is None and torch.cuda.is_available():
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"FusedAudioBatch: float32, float16 or bfloat16 samples, got {dtype}")
+        self.device, self.dtype = dev, dtype
+
+    def _chain_pack(self, items, headroom: int = 0):
+        from .extractors import pack_items
+
+        if any(x.dtype not in (torch.float32, np.float32) for x in items):
+            raise TypeError("FusedAudioBatch: expected float32 samples")
+        return pack_items(items, self.device, None, headroom)
+
+    def _collated(self, arena, cut_off, cut_len, wants):
+        lens = np.minimum(np.asarray(cut_len, dtype=np.int64), np.asarray(wants, dtype=np.int64))
+        audio = _collate_in_arena(arena, cut_off, lens, int(max(wants)) if len(lens) else 0, self.dtype)
+        return audio, torch.from_numpy(lens.copy())
+
+    def audio_of(self, audios: List[torch.Tensor], factors: List[float], wants: List[int], sampling_rate: int):
+        """The arguments of ``FusedMiniBatch.features_of`` -> ``(audio (B, Tmax) on the device, audio_lens)``, ``Tmax = max(wants)``,
+        zeros behind every cut.  A mini-batch with nothing pending is packed and collated with nothing in between."""
+        from .extractors import _as_1d_float
+
+        if len(audios) != len(wants) or len(audios) != len(factors):
+            raise ValueError("audio_of: one factor and one wanted sample count per cut")
+        with torch.no_grad():
+            if any(f != 1.0 for f in factors):
+                arena, offs, lens, front = self._speed_arena(audios, factors, sampling_rate)
+                po, pl = _perturb_in_arena(arena, offs, lens, factors, sampling_rate, front)
+            else:
+                arena, po, pl = self._chain_pack([_as_1d_float(a.squeeze() if a.ndim > 1 else a, "FusedAudioBatch") for a in audios])
+            return self._collated(arena, po, pl, wants)
+
+    def audio_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
+        """The arguments of ``FusedMiniBatch.features_of_tracks`` (tracks with their pending speed, reverb, source rate and level blocks)
+        -> ``(audio (B, Tmax) on the device, audio_lens)``: the same chain in the same arena, then the collate launch."""
+        if len(cuts_tracks) != len(wants):
+            raise ValueError("audio_of_tracks: one wanted sample count per cut")
+        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None and _level_of(t[0]) is None for t in cuts_tracks):
+            audios = [t[0][0] for t in cuts_tracks]
+            audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
+            return self.audio_of(audios, [float(t[0][1]) for t in cuts_tracks], wants, sampling_rate)
+        with torch.no_grad():
+            arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sampling_rate)
+            return self._collated(arena, cut_off, cut_len, wants)
 
 
 if HAVE_LHOTSE:  # pragma: no cover - authoring container only
     from lhotse.audio.utils import suppress_audio_loading_errors  # type: ignore
     from lhotse.dataset.collation import collate_vectors, read_audio_from_cuts  # type: ignore
-    from lhotse.dataset.input_strategies import OnTheFlyFeatures, _get_executor  # type: ignore
+    from lhotse.dataset.input_strategies import AudioSamples, OnTheFlyFeatures, _get_executor  # type: ignore
     from lhotse.utils import compute_num_samples  # type: ignore
 
     def deferred_speed_factor(cut) -> Optional[float]:
@@ -899,42 +1032,10 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
 
         return bool(ref.is_torchaudio_available()) and get_current_resampling_backend() == "default"
 
-    class HipOnTheFlyFeatures(OnTheFlyFeatures, FusedMiniBatch):
-        """Same constructor as ``OnTheFlyFeatures`` plus ``return_device`` (``None`` keeps the padded feature tensor on the
-        extractor's GPU, ready for the training step; ``"cpu"`` hands back a host tensor like the reference does) and
-        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` / ``gpu_level`` (see the module docstring)."""
-
-        def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
-                     gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, gpu_reverb: Optional[bool] = None,
-                     gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, **kwargs) -> None:
-            if not hasattr(extractor, "extract_collated"):
-                raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
-            super().__init__(extractor, *args, **kwargs)
-            self.return_device = return_device
-            # None (default) = on the device unless `wave_transforms` are given: those run on the LOADED samples, i.e. after the
-            # Speed that Recording.load_audio applies, so with them the reference order (CPU Speed inside load_audio, then the
-            # transforms) is kept and the strategy behaves exactly like OnTheFlyFeatures.  An explicit True together with
-            # wave_transforms is a contradiction and raises when a perturbed cut is met.
-            self._gpu_speed_explicit = gpu_speed_perturb is not None
-            self.gpu_speed_perturb = (not self.wave_transforms) if gpu_speed_perturb is None else bool(gpu_speed_perturb)
-            # the same for the tracks of mixed cuts: wave_transforms run on the MIXED samples, so with them the mix stays where the
-            # reference does it (MixedCut.load_audio); an explicit True together with wave_transforms raises when a mixed cut is met
-            self.gpu_mix = (not self.wave_transforms) if gpu_mix is None else bool(gpu_mix)
-            # and for a reverb with a recorded RIR at the end of a recording's transforms (ReverbWithImpulseResponse): None = on the
-            # device unless wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a
-            # cut is met
-            self.gpu_reverb = (not self.wave_transforms) if gpu_reverb is None else bool(gpu_reverb)
-            # and for a Resample at the front of a recording's transforms (cuts.resample(sr)): None = on the device unless wave_transforms
-            # are given AND only where the reference itself would run its sinc resampler -- without torchaudio its Resample substitutes
-            # scipy.signal.resample_poly, another filter (lhotse/augmentation/torchaudio.py:124-139), which the device does not
-            # implement; False = always Recording.load_audio; True forces the device's sinc resampler, and raises together with
-            # wave_transforms when such a cut is met
-            self.gpu_resample = (not self.wave_transforms and _reference_resamples_with_sinc()) if gpu_resample is None else bool(gpu_resample)
-            # and for Volume / Clipping in a recording's transforms (PerturbVolume, the Clipping cut transform): None = on the device unless
-            # wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a cut is met.  The
-            # oversampled clip (clip_amplitude(oversampling=k)) and a leading Resample in such a chain also need the resampling route, and
-            # that only where the reference itself would run its sinc resampler
-            self.gpu_level = (not self.wave_transforms) if gpu_level is None else bool(gpu_level)
+    class _ChainReader:
+        """The reading half of ``HipOnTheFlyFeatures`` and ``HipAudioSamples``: the cuts of a mini-batch as read in front of the transforms
+        the device takes over (``self.gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` / ``gpu_level``,
+        ``self.fault_tolerant``)."""
 
         def _read(self, cuts, pool, recording_field):
             """read_audio_from_cuts (lhotse/dataset/collation.py:541-600) with the Speed of eligible cuts left for the device."""
@@ -961,6 +1062,48 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                     continue
                 audios.append(res[0]), factors.append(res[1]), wants.append(res[2]), ok.append(cut)
             return audios, factors, wants, CutSet.from_cuts(ok)
+
+    class HipOnTheFlyFeatures(_ChainReader, OnTheFlyFeatures, FusedMiniBatch):
+        """Same constructor as ``OnTheFlyFeatures`` plus ``return_device`` (``None`` keeps the padded feature tensor on the
+        extractor's GPU, ready for the training step; ``"cpu"`` hands back a host tensor like the reference does) and
+        ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` / ``gpu_level`` (see the module docstring), and
+        ``return_audio_device`` for the samples of ``return_audio`` (``"cpu"``, the default: as the reference; ``None`` or a device: the
+        ``(B, Tmax)`` tensor is collated there, see ``FusedMiniBatch.features_of_tracks``)."""
+
+        def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
+                     return_audio_device: Optional[Union[str, torch.device]] = "cpu", gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, gpu_reverb: Optional[bool] = None,
+                     gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, **kwargs) -> None:
+            if not hasattr(extractor, "extract_collated"):
+                raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
+            super().__init__(extractor, *args, **kwargs)
+            self.return_device = return_device
+            # where `return_audio` hands the samples out: "cpu" (default) = host tensors, collated on the host as the parent does;
+            # None (the extractor's device) or a device = collated there by one launch out of the arena the feature launch read
+            self.audio_device = "cpu" if return_audio_device is not None and torch.device(return_audio_device).type == "cpu" else return_audio_device
+            # None (default) = on the device unless `wave_transforms` are given: those run on the LOADED samples, i.e. after the
+            # Speed that Recording.load_audio applies, so with them the reference order (CPU Speed inside load_audio, then the
+            # transforms) is kept and the strategy behaves exactly like OnTheFlyFeatures.  An explicit True together with
+            # wave_transforms is a contradiction and raises when a perturbed cut is met.
+            self._gpu_speed_explicit = gpu_speed_perturb is not None
+            self.gpu_speed_perturb = (not self.wave_transforms) if gpu_speed_perturb is None else bool(gpu_speed_perturb)
+            # the same for the tracks of mixed cuts: wave_transforms run on the MIXED samples, so with them the mix stays where the
+            # reference does it (MixedCut.load_audio); an explicit True together with wave_transforms raises when a mixed cut is met
+            self.gpu_mix = (not self.wave_transforms) if gpu_mix is None else bool(gpu_mix)
+            # and for a reverb with a recorded RIR at the end of a recording's transforms (ReverbWithImpulseResponse): None = on the
+            # device unless wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a
+            # cut is met
+            self.gpu_reverb = (not self.wave_transforms) if gpu_reverb is None else bool(gpu_reverb)
+            # and for a Resample at the front of a recording's transforms (cuts.resample(sr)): None = on the device unless wave_transforms
+            # are given AND only where the reference itself would run its sinc resampler -- without torchaudio its Resample substitutes
+            # scipy.signal.resample_poly, another filter (lhotse/augmentation/torchaudio.py:124-139), which the device does not
+            # implement; False = always Recording.load_audio; True forces the device's sinc resampler, and raises together with
+            # wave_transforms when such a cut is met
+            self.gpu_resample = (not self.wave_transforms and _reference_resamples_with_sinc()) if gpu_resample is None else bool(gpu_resample)
+            # and for Volume / Clipping in a recording's transforms (PerturbVolume, the Clipping cut transform): None = on the device unless
+            # wave_transforms are given, False = always Recording.load_audio, True with wave_transforms raises when such a cut is met.  The
+            # oversampled clip (clip_amplitude(oversampling=k)) and a leading Resample in such a chain also need the resampling route, and
+            # that only where the reference itself would run its sinc resampler
+            self.gpu_level = (not self.wave_transforms) if gpu_level is None else bool(gpu_level)
 
         def __call__(self, cuts, recording_field: Optional[str] = None):
             """Only the middle of the parent's pipeline differs: ``extract_batch`` + ``collate_matrices`` become ONE fused launch, and
@@ -995,24 +1138,83 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             rates = {c.sampling_rate for c in cuts}
             assert len(rates) == 1, f"one launch per batch needs a single sampling rate, got {sorted(rates)}"
             sr = rates.pop()
-            perturbed = None
             if mixed:  # (FusedMiniBatch.features_of_tracks: a plain cut is a cut of one track)
                 tracks = [a if isinstance(a, list) else [(a, f, 0, None, True)] for a, f in zip(audios, factors)]
-                feats, feat_lens, perturbed = self._mix_and_extract(tracks, wants, sr)
+                feats, feat_lens, *audio = self._mix_and_extract(tracks, wants, sr)
             elif any(f != 1.0 for f in factors):  # (FusedMiniBatch.features_of, with the perturbed samples kept for `return_audio`)
-                feats, feat_lens, perturbed = self._perturb_and_extract(audios, factors, wants, sr)
+                feats, feat_lens, *audio = self._perturb_and_extract(audios, factors, wants, sr)
             else:
-                feats, feat_lens = self.extractor.extract_collated(audios, sampling_rate=sr, padding_value=LOG_EPSILON)
+                feats, feat_lens, *audio = self._plain_extract(audios, sr)
             result = [feats if self.return_device is None else feats.to(self.return_device), feat_lens]
-            if self.return_audio:  # (B, Tmax) zero-padded samples + their lengths, as the parent returns them
-                flat = [a.reshape(-1) for a in (perturbed if perturbed is not None else audios)]
+            if self.return_audio and self.audio_device != "cpu":  # (B, Tmax) zero-padded samples, collated on the device, + their lengths
+                result += audio
+            elif self.return_audio:  # (B, Tmax) zero-padded samples + their lengths, as the parent returns them
+                flat = [a.reshape(-1) for a in audio[0]]
                 result += [collate_vectors(flat, padding_value=0), torch.tensor([len(a) for a in flat], dtype=torch.int64)]
             if self.fault_tolerant:  # the cuts that survived audio loading
                 result.append(cuts)
             return tuple(result)
+
+    def _num_channels(cut) -> int:
+        try:
+            return int(cut.num_channels or 1)
+        except Exception:  # noqa: BLE001  (a cut that cannot say: the reference's path decides)
+            return 2
+
+    class HipAudioSamples(_ChainReader, AudioSamples):
+        """``AudioSamples`` (lhotse/dataset/input_strategies.py:208-299) with the transforms of the cuts and the collation on the GPU: the
+        cuts are read in front of the transforms the device takes over (as ``HipOnTheFlyFeatures`` reads them), the chain runs in one arena
+        and ONE launch writes the zero-padded ``(B, T)`` tensor (``FusedAudioBatch``).  Same constructor as ``AudioSamples`` plus ``device``
+        (where the chain runs), ``return_device`` (``None`` keeps the samples there, ``"cpu"`` hands back a host tensor like the reference),
+        ``dtype`` (float32, float16 or bfloat16 samples) and ``gpu_speed_perturb`` / ``gpu_mix`` / ``gpu_reverb`` / ``gpu_resample`` /
+        ``gpu_level`` with the meaning and defaults they have on ``HipOnTheFlyFeatures`` (there are no ``wave_transforms`` here: None = on).
+        Returns ``(audio, audio_lens[, cuts])`` with the parent's int32 lengths and its ``fault_tolerant`` contract.
+
+        The parent's own ``__call__`` runs, and its result is moved to ``return_device`` (None: ``device``), for ``recording_field``,
+        ``use_batch_loader``, ``mono_downmix=False`` and a batch in which any cut has more than one channel."""
+
+        def __init__(self, *args, device: Union[str, torch.device, None] = None, return_device: Optional[Union[str, torch.device]] = None,
+                     dtype: torch.dtype = torch.float32, gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None,
+                     gpu_reverb: Optional[bool] = None, gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, **kwargs) -> None:
+            super().__init__(*args, **kwargs)
+            self.batch = FusedAudioBatch(device, dtype)
+            self.device, self.dtype, self.return_device = self.batch.device, dtype, return_device
+            self.gpu_speed_perturb = True if gpu_speed_perturb is None else bool(gpu_speed_perturb)
+            self.gpu_mix = True if gpu_mix is None else bool(gpu_mix)
+            self.gpu_reverb = True if gpu_reverb is None else bool(gpu_reverb)
+            # (only where the reference itself would run its sinc resampler, as on HipOnTheFlyFeatures)
+            self.gpu_resample = _reference_resamples_with_sinc() if gpu_resample is None else bool(gpu_resample)
+            self.gpu_level = True if gpu_level is None else bool(gpu_level)
+
+        def _moved(self, result):
+            dev = self.device if self.return_device is None else self.return_device
+            return (result[0].to(dev),) + tuple(result[1:])
+
+        def __call__(self, cuts, recording_field: Optional[str] = None):
+            if (recording_field is not None or self.use_batch_loader or self.mono_downmix is False
+                    or any(_num_channels(c) != 1 for c in cuts)):
+                return self._moved(super().__call__(cuts, recording_field=recording_field))
+            pool = _get_executor(self.num_workers, executor_type=self._executor_type)
+            audios, factors, wants, ok = self._read(cuts, pool, None)
+            if not len(audios):
+                raise ValueError("HipAudioSamples: no cut of the mini-batch could be read")
+            rates = {c.sampling_rate for c in ok}
+            assert len(rates) == 1, f"one launch per batch needs a single sampling rate, got {sorted(rates)}"
+            sr = rates.pop()
+            if any(isinstance(a, list) for a in audios):  # (the loaded tracks of the cuts the device mixes, reverberates, resamples, scales)
+                tracks = [a if isinstance(a, list) else [(a, f, 0, None, True)] for a, f in zip(audios, factors)]
+                audio, lens = self.batch.audio_of_tracks(tracks, wants, sr)
+            else:
+                audio, lens = self.batch.audio_of(audios, factors, wants, sr)
+            result = self._moved((audio, lens.to(torch.int32)))  # (collation.py:242)
+            return result + (ok,) if self.fault_tolerant else result
 
 else:
 
     class HipOnTheFlyFeatures:  # type: ignore[no-redef]
         def __init__(self, *args, **kwargs):
             raise ImportError("HipOnTheFlyFeatures consumes lhotse CutSets: install lhotse (lhotse.dataset.input_strategies.OnTheFlyFeatures)")
+
+    class HipAudioSamples:  # type: ignore[no-redef]
+        def __init__(self, *args, **kwargs):
+            raise ImportError("HipAudioSamples consumes lhotse CutSets: install lhotse (lhotse.dataset.input_strategies.AudioSamples)")
