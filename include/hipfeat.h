@@ -41,9 +41,10 @@ extern "C" {
 #define HIPFEAT_API
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
- * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES and _COLLATE_SIGNATURES next to _SIGNATURES). */
+ * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES and _SINC_SIGNATURES next to _SIGNATURES). */
 #define HIPFEAT_COLLATE_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
+#define HIPFEAT_SINC_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -464,6 +465,42 @@ HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_collate* collate
                                                         const int64_t* h_dst_offset, int64_t row_len, int32_t out_type, int64_t* h_info);
 HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collate* collate, int64_t ticket, const float* d_arena, int64_t arena_floats, void* d_out,
                                                        int64_t out_elements, void* stream);
+
+/* ---- sinc resampling without a filter bank: any rate pair, every row with its own (additive to ABI v8) ------------------------ */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_sinc_*.  What they replace: ResampleTensor = _get_sinc_resample_kernel +
+ * _apply_sinc_resample_kernel (lhotse/augmentation/resample.py:184-315) for rate pairs whose dense filter bank (new x (2 width + orig)
+ * weights, rates reduced by their gcd) is too large to build -- the two Resample transforms that LowpassUsingResampling appends
+ * (lhotse/dataset/cut_transforms/lowpass.py: Resample(sr -> 2c), Resample(2c -> sr), a random integer cutoff c per cut; 16000 -> 9346 is
+ * 8000 : 4673, a bank of 37.5 M weights of which 22 per phase are not zero), and any Resample (lhotse/augmentation/torchaudio.py:86-139)
+ * between such rates.  The weights of the reference (resample.py:239-281; hann window, lowpass_filter_width 6, rolloff 0.99) are
+ * evaluated on the device where they are not zero, in float64 rounded once to float32, per launch; nothing grows with the rates.
+ * Row r of a launch takes the h_in_len[r] samples at arena + h_in_offset[r] from h_src_rate[r] to h_dst_rate[r] (unreduced) and writes
+ * h_out_len[r] = hipfeat_resampled_length(h_in_len[r], src, dst) samples (resample.py:309) at arena + h_out_offset[r]; each output is
+ * the ascending-tap fmaf chain of hipfeat_resample over the taps whose weight is not zero.  All offsets are 64-bit.
+ *
+ * hipfeat_sinc_create / _destroy: the object that owns the staged row table on `device`; calls are serialised inside, up to 16 plans
+ * may be outstanding, destroy waits for the work it enqueued.
+ * hipfeat_sinc_plan (host only) writes h_out_len[num_rows] and h_info[4] = {ticket, floats the arena must hold, workgroups, largest
+ * window W = 2 width + 2 of the rows}.  Refused, and nothing planned: a rate <= 0, equal rates, a negative offset or length, an input
+ * or output range past arena_floats, an output range that overlaps any row's input range (its own included) or another row's output, a
+ * 17th plan while 16 are planned and not yet run: HIPFEAT_ERR_INVALID; a rate pair whose window exceeds 96 taps (width > 47: a
+ * downsampling ratio beyond 7.75) or whose reduced rates exceed 2^24: HIPFEAT_ERR_UNSUPPORTED.  Rows of no samples and num_rows == 0 are valid.
+ * hipfeat_sinc_run enqueues the ONE launch of a planned resampling on `stream` (a ticket runs once).  An unknown ticket or arena_floats
+ * < h_info[1]: HIPFEAT_ERR_INVALID, nothing is launched.  The arena starts on a 16-byte boundary.
+ * hipfeat_sinc_weights: the filter a rate pair gets here, for inspection: h_dims[3] = {new, W, width} (host, written at once),
+ * d_weights[new][W] float32 and d_first[new] int32, the window's first tap counted in taps of the zero-padded input (resample.py:307);
+ * tap d of phase ph is the reference's kernel[ph][d_first[ph] + d].  d_weights == d_first == NULL: the sizes alone.
+ */
+typedef struct hipfeat_sinc hipfeat_sinc;
+HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_create(int32_t device, hipfeat_sinc** sinc);
+HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_destroy(hipfeat_sinc* sinc);
+HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_plan(hipfeat_sinc* sinc, int64_t num_rows, const int64_t* h_in_offset, const int64_t* h_in_len,
+                                                  const int32_t* h_src_rate, const int32_t* h_dst_rate, const int64_t* h_out_offset,
+                                                  int64_t arena_floats, int64_t* h_out_len, int64_t* h_info);
+HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sinc, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
+HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_weights(hipfeat_sinc* sinc, int32_t src_rate, int32_t dst_rate, float* d_weights, int32_t* d_first,
+                                                     int32_t* h_dims, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

@@ -19,6 +19,7 @@ from .augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_are
 from .augmentation import HipClipping, HipLevel, HipVolume, get_or_create_level, level_in_arena  # noqa: F401,E402
 from .augmentation import COLLATE_TILE, HipCollator, collate_in_arena, get_or_create_collator, left_pad_offsets  # noqa: F401,E402
 from .augmentation import resample_in_arena, resample_layout, resampled_tail_floats  # noqa: F401,E402
+from .augmentation import HipSincResampler, get_or_create_sinc, sinc_in_arena  # noqa: F401,E402
 from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
 
 from .kaldifeat import (  # noqa: F401,E402
@@ -89,6 +90,9 @@ __all__ = [
     "FusedAudioBatch",
     "HipAudioSamples",
     "resample_in_arena",
+    "HipSincResampler",
+    "get_or_create_sinc",
+    "sinc_in_arena",
     "resample_layout",
     "resampled_tail_floats",
     "HipResample",

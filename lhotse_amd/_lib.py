@@ -141,7 +141,19 @@ _COLLATE_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
     "hipfeat_collate_run": ("int", ["hipfeat_collate*", "int64_t", "const float*", "int64_t", "void*", "int64_t", "void*"]),
 }
-_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES}
+# Likewise (HIPFEAT_SINC_API in the header).
+_SINC_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_sinc_create": ("int", ["int32_t", "hipfeat_sinc**"]),
+    "hipfeat_sinc_destroy": ("int", ["hipfeat_sinc*"]),
+    "hipfeat_sinc_plan": (
+        "int",
+        ["hipfeat_sinc*", "int64_t", "const int64_t*", "const int64_t*", "const int32_t*", "const int32_t*", "const int64_t*", "int64_t", "int64_t*",
+         "int64_t*"],
+    ),
+    "hipfeat_sinc_run": ("int", ["hipfeat_sinc*", "int64_t", "float*", "int64_t", "void*"]),
+    "hipfeat_sinc_weights": ("int", ["hipfeat_sinc*", "int32_t", "int32_t", "float*", "int32_t*", "int32_t*", "void*"]),
+}
+_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -232,7 +244,7 @@ class _CffiBackend:
             s = line.strip()
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
-            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", ""))
+            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}
@@ -249,7 +261,7 @@ class _CffiBackend:
 
     def _fn(self, name: str):
         fn = self.fns.get(name)
-        if fn is None:  # an entry point of _LEVEL_SIGNATURES / _COLLATE_SIGNATURES: looked up at its first use
+        if fn is None:  # an entry point of _ADDED_SIGNATURES: looked up at its first use
             fn = self.fns[name] = getattr(self.dll, name)
         return fn
 

@@ -58,15 +58,66 @@ def _compute_num_samples(duration: Seconds, sampling_rate: int) -> int:
     return int(Decimal(round(duration * sampling_rate, ndigits=8)).quantize(0, rounding=ROUND_HALF_UP))
 
 
+MAX_RESAMPLE_BANK_FLOATS = 1 << 20  # the largest dense filter bank (new x (2 width + orig) floats, reduced rates) that is built and uploaded
+SINC_MAX_WINDOW = 96  # kSincMaxW of csrc/sinc_tables.hpp: the widest window (2 width + 2 taps per phase) the bankless kernel holds
+
+
+def _sinc_geometry(source_rate: int, target_rate: int) -> Tuple[int, int, int]:
+    """(orig, new, width) of the reference's filter for source -> target (lhotse/augmentation/resample.py:219-239: rates reduced by their
+    gcd, lowpass_filter_width 6, rolloff 0.99), from the rates alone."""
+    from math import ceil, gcd
+
+    g = gcd(int(source_rate), int(target_rate))
+    orig, new = int(source_rate) // g, int(target_rate) // g
+    return orig, new, ceil(6 * orig / (min(orig, new) * 0.99))
+
+
+def _sinc_bank_floats(source_rate: int, target_rate: int) -> int:
+    """Floats of the reference's dense filter bank for source -> target, from the rates alone."""
+    orig, new, width = _sinc_geometry(source_rate, target_rate)
+    return new * (2 * width + orig)
+
+
+def _dense_kernel_fits(orig: int, new: int, width: int) -> bool:
+    """The support rule of ``hipfeat_resampler_create`` for a bank it is given (csrc/hipfeat.hip): the generic kernel stages the input span
+    of at least 64 outputs -- ``(ceil(64 / new) + 1) * orig + 2 * width + orig`` floats, rounded up to 4 -- in LDS, next to the bank when
+    that has at most 8192 floats, and has 64 KiB."""
+    kw = 2 * width + orig
+    span = ((-(-64 // new) + 1) * orig + kw + 3) & ~3
+    return 4 * (span + (new * kw if new * kw <= 8192 else 0)) <= 64 * 1024
+
+
+def resample_route(source_rate: int, target_rate: int) -> Optional[str]:
+    """THE routing rule of a rate pair: ``"bank"`` -- its dense bank has at most ``MAX_RESAMPLE_BANK_FLOATS`` floats and the dense kernels
+    take it (``_dense_kernel_fits``): a cached ``HipResampleTensor`` with the bank in HBM (``hipfeat_resample``) --, ``"sinc"`` -- the
+    bankless kernel (``hipfeat_sinc_run``): a window of at most ``SINC_MAX_WINDOW`` taps, reduced rates up to 2^24 --, or None: no kernel
+    serves it (16000 -> 2001: a bank of 32 M floats and a window of 100 taps; 16000 -> 202: a bank of 905 K floats whose hop of 8000
+    samples does not fit the dense kernel's LDS, and a window of 954 taps)."""
+    if int(source_rate) <= 0 or int(target_rate) <= 0 or int(source_rate) == int(target_rate):
+        return None
+    orig, new, width = _sinc_geometry(source_rate, target_rate)
+    if new * (2 * width + orig) <= MAX_RESAMPLE_BANK_FLOATS and _dense_kernel_fits(orig, new, width):
+        return "bank"
+    return "sinc" if 2 * width + 2 <= SINC_MAX_WINDOW and max(orig, new) <= 1 << 24 else None
+
+
 class HipResampleTensor:
     """Device counterpart of the ``Resample`` nn.Module (lhotse/augmentation/resample.py:42-142): the filter
-    bank lives in HBM; calling it resamples every row of a ``(..., T)`` float32 tensor."""
+    bank lives in HBM; calling it resamples every row of a ``(..., T)`` float32 tensor.  A rate pair whose dense bank would exceed
+    ``MAX_RESAMPLE_BANK_FLOATS`` (11127 -> 16000: 178 M floats) builds no bank: it runs the bankless kernel (``HipSincResampler``),
+    ``kernel_name == "resample_sinc"``, ``kernel is None``."""
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, lowpass_filter_width: int = 6, rolloff: float = 0.99,
                  device: Union[str, torch.device, None] = None):
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
         self.lowpass_filter_width, self.rolloff = lowpass_filter_width, rolloff
-        self.kernel, self.width, self.orig, self.new = constants.sinc_resample_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        self.bankless = (lowpass_filter_width, rolloff) == (6, 0.99) and self.orig_freq != self.new_freq and min(self.orig_freq, self.new_freq) > 0 \
+            and (_sinc_bank_floats(orig_freq, new_freq) > MAX_RESAMPLE_BANK_FLOATS or resample_route(orig_freq, new_freq) == "sinc")
+        if self.bankless:
+            self.kernel = None
+            self.orig, self.new, self.width = _sinc_geometry(orig_freq, new_freq)
+        else:
+            self.kernel, self.width, self.orig, self.new = constants.sinc_resample_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff)
         self.lib = _lib.load()
         self.handle = 0
         dev = torch.device("cuda" if device is None else device)
@@ -75,6 +126,13 @@ class HipResampleTensor:
         if not torch.cuda.is_available():
             raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        if self.bankless:
+            if resample_route(orig_freq, new_freq) != "sinc":
+                raise _lib.HipFeatError(_lib.ERR_UNSUPPORTED, f"{orig_freq} -> {new_freq}: a window of {2 * self.width + 2} taps per phase, the bankless "
+                                                              f"kernel holds {SINC_MAX_WINDOW}")
+            self.sinc = get_or_create_sinc(self.device)
+            self.kernel_name = "resample_sinc"
+            return
         out = np.zeros(1, dtype=np.uint64)
         self.lib.check("hipfeat_resampler_create", self.orig, self.new, self.width, _lib.addr(self.kernel), int(self.device.index), _lib.addr(out))
         self.handle = int(out[0])
@@ -106,6 +164,15 @@ class HipResampleTensor:
         step = ((out_lens + 3) & ~3) if align else out_lens
         np.cumsum(step[:-1], out=out_offs[1:])
         total = int(out_offs[-1] + out_lens[-1]) if len(lengths) else 0
+        if self.bankless:  # one arena: a copy of the input in front, the outputs behind it
+            front = (wave.numel() + 3) & ~3
+            with torch.cuda.device(self.device):
+                arena = torch.empty(front + total, dtype=torch.float32, device=self.device)
+                arena[: wave.numel()].copy_(wave)
+                ticket, planned, _ = self.sinc.plan(offsets, lengths, [(self.orig_freq, self.new_freq)] * len(lengths), out_offs + front, arena.numel())
+                assert np.array_equal(planned, out_lens)  # the library's own length rule
+                self.sinc.run(ticket, arena)
+            return arena[front:], out_offs, out_lens
         with torch.cuda.device(self.device):
             out = torch.empty(total, dtype=torch.float32, device=self.device)
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -271,14 +338,21 @@ def _grouped_layout(offsets, lengths, keys, ratio_of, tail_start):
 
 
 def _resample_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups, ratio_of, what):
-    """One ``hipfeat_resample`` launch per group of ``_grouped_layout``, input and output in the same arena."""
+    """One ``hipfeat_resample`` launch per group of ``_grouped_layout`` whose ratio has a dense bank (``resample_route``), ONE
+    ``hipfeat_sinc_run`` for all the others (what no kernel serves: the plan refuses it by name); input and output in the same arena."""
     assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
     last = max((int((offsets[idx] + lengths[idx]).max()) for _, idx in groups), default=0)
     if last > arena.numel():
         raise ValueError(f"arena too small: {arena.numel()} floats, the {what} cuts need {last} (see {what}_tail_floats)")
     dev = arena.device
+    # a ratio without a dense bank (Speed(1.037) at 16 kHz is 1037 : 1000, a bank of 1.05 M floats) goes, with all its like, into ONE
+    # launch of the bankless kernel; the placement is the same
+    bankless = [(tuple(int(v) for v in ratio_of(key)), idx) for key, idx in groups if resample_route(*ratio_of(key)) != "bank"]
+    _sinc_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, bankless)
     for key, idx in groups:
         src, dst = (int(v) for v in ratio_of(key))
+        if resample_route(src, dst) != "bank":
+            continue
         r = get_or_create_resampler(src, dst, dev)
         in_offs, in_lens = np.ascontiguousarray(in_offsets[idx]), np.ascontiguousarray(in_lengths[idx])  # (named: they must outlive the call)
         out_offs = np.ascontiguousarray(offsets[idx])
@@ -313,15 +387,126 @@ def resample_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np.ndar
     sinc backend): the generalisation of ``perturb_speed_in_arena`` from speed factors to any (source, target) rates per cut.
 
     ``arena`` is ONE float32 device buffer: the cuts at ``offsets`` / ``lengths`` in its front part, free space from ``tail_start`` on
-    (``resampled_tail_floats`` says how much).  Cuts with ratio None stay where they are; the others are resampled -- one
-    ``hipfeat_resample`` launch per distinct ratio, in ascending order -- into the tail.  Returns the per-cut (offsets, lengths) inside
-    the same arena.  A second pass (a ``Speed`` behind the ``Resample``) takes these as its input with ``tail_start`` = the end
-    ``resample_layout`` reports."""
+    (``resampled_tail_floats`` says how much).  Cuts with ratio None stay where they are; the others are resampled into the tail.  This
+    is the ROUTER (``resample_route``): ratios whose dense bank has at most ``MAX_RESAMPLE_BANK_FLOATS`` floats go to their cached
+    ``HipResampleTensor`` -- one ``hipfeat_resample`` launch per distinct ratio, in ascending order --, all the others together into ONE
+    ``hipfeat_sinc_run`` (``sinc_in_arena``); the placement (``resample_layout``) does not depend on the route.  Returns the per-cut
+    (offsets, lengths) inside the same arena.  A second pass (a ``Speed`` behind the ``Resample``) takes these as its input with
+    ``tail_start`` = the end ``resample_layout`` reports."""
     keys = _ratio_keys(ratios)
     in_offsets, in_lengths = _lib.i64(offsets), _lib.i64(lengths)
     offsets, lengths, _, groups = _grouped_layout(in_offsets, in_lengths, keys, lambda k: k, tail_start)
-    _resample_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups, lambda k: k, "resampled")
+    _resample_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups, lambda k: k, "resampled")  # (routes group by group)
     return offsets, lengths
+
+
+def _check_arena(arena, offsets, lengths, groups, what):
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    last = max((int((offsets[idx] + lengths[idx]).max()) for _, idx in groups), default=0)
+    if last > arena.numel():
+        raise ValueError(f"arena too small: {arena.numel()} floats, the {what} cuts need {last} (see {what}_tail_floats)")
+
+
+def _sinc_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups):
+    """ONE ``hipfeat_sinc_run`` for the cuts of all ``groups`` of ``_grouped_layout``, input and output in the same arena."""
+    if not groups:
+        return
+    idx = np.concatenate([i for _, i in groups])
+    rates = [key for key, i in groups for _ in range(len(i))]
+    sinc = get_or_create_sinc(arena.device)
+    ticket, out_lens, _ = sinc.plan(in_offsets[idx], in_lengths[idx], rates, offsets[idx], arena.numel())
+    assert np.array_equal(out_lens, lengths[idx])  # the library's own length rule
+    sinc.run(ticket, arena)
+
+
+def sinc_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np.ndarray, ratios: Sequence[Optional[Tuple[int, int]]],
+                  tail_start: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``resample_in_arena`` with every ratio on the bankless kernel, whatever its bank would take: same arguments, same placement
+    (``resample_layout``), ONE ``hipfeat_sinc_run`` launch for all cuts, each with its own rates (none when every ratio is None)."""
+    keys = _ratio_keys(ratios)
+    in_offsets, in_lengths = _lib.i64(offsets), _lib.i64(lengths)
+    offsets, lengths, _, groups = _grouped_layout(in_offsets, in_lengths, keys, lambda k: k, tail_start)
+    _check_arena(arena, offsets, lengths, groups, "resampled")
+    _sinc_groups_in_arena(arena, in_offsets, in_lengths, offsets, lengths, groups)
+    return offsets, lengths
+
+
+class HipSincResampler:
+    """The sinc resampler without a filter bank (``hipfeat_sinc``, include/hipfeat.h; csrc/kernel_sinc.hpp): the arithmetic of
+    ``ResampleTensor`` (lhotse/augmentation/resample.py:184-315) for ANY rate pair, every row of a launch with its own -- the weights are
+    evaluated on the device where they are not zero.  One object per device (``get_or_create_sinc``); it may be shared by threads."""
+
+    def __init__(self, device: Union[str, torch.device, None] = None):
+        self.lib = _lib.load()
+        self.handle = 0
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.HipFeatError(1, f"HipSincResampler runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        out = np.zeros(1, dtype=np.uint64)
+        self.lib.check("hipfeat_sinc_create", int(self.device.index), _lib.addr(out))
+        self.handle = int(out[0])
+        self._lock = threading.Lock()
+
+    def plan(self, in_offsets, in_lens, rates: Sequence[Tuple[int, int]], out_offsets, arena_floats: int):
+        """Host only -> (ticket, output lengths, info = [ticket, arena floats needed, workgroups, largest window])."""
+        io, il, oo = _lib.i64(in_offsets), _lib.i64(in_lens), _lib.i64(out_offsets)
+        src = np.ascontiguousarray([r[0] for r in rates], dtype=np.int32)
+        dst = np.ascontiguousarray([r[1] for r in rates], dtype=np.int32)
+        n = len(io)
+        if not (len(il) == len(oo) == len(src) == n):
+            raise ValueError("sinc tables: one entry per row in every table")
+        out_lens, info = np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_sinc_plan", self.handle, n, _lib.addr(io), _lib.addr(il), _lib.addr(src), _lib.addr(dst), _lib.addr(oo), int(arena_floats),
+                           _lib.addr(out_lens), _lib.addr(info))
+        return int(info[0]), out_lens, info
+
+    def run(self, ticket: int, arena: torch.Tensor, stream: Optional[int] = None) -> None:
+        assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
+        with torch.cuda.device(self.device):
+            self.lib.check("hipfeat_sinc_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
+
+    def weights(self, source_rate: int, target_rate: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """The filter of a rate pair as the kernel evaluates it -> (weights ``(new, W)`` float32, first taps ``(new,)`` int32, width):
+        tap d of phase ph is the reference's ``kernel[ph][first[ph] + d]``."""
+        dims = np.zeros(3, dtype=np.int32)
+        self.lib.check("hipfeat_sinc_weights", self.handle, int(source_rate), int(target_rate), None, None, _lib.addr(dims), None)
+        with torch.cuda.device(self.device):
+            w = torch.empty((int(dims[0]), int(dims[1])), dtype=torch.float32, device=self.device)
+            first = torch.empty(int(dims[0]), dtype=torch.int32, device=self.device)
+            self.lib.check("hipfeat_sinc_weights", self.handle, int(source_rate), int(target_rate), w.data_ptr(), first.data_ptr(), _lib.addr(dims),
+                           int(_raw_stream(self.device)))
+        return w, first, int(dims[2])
+
+    def close(self):
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_sinc_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_sincs: Dict[int, HipSincResampler] = {}
+_sinc_lock = threading.Lock()  # (its own: get_or_create_resampler holds _cache_lock while a bankless HipResampleTensor asks for the device's object)
+
+
+def get_or_create_sinc(device: Union[str, torch.device, None] = None) -> HipSincResampler:
+    dev = torch.device("cuda" if device is None else device)
+    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    with _sinc_lock:
+        r = _sincs.get(int(index))
+        if r is None:
+            r = _sincs[int(index)] = HipSincResampler(torch.device(dev.type, index))
+        return r
 
 
 def _speed_keys(factors) -> list:
@@ -384,9 +569,12 @@ class HipSpeedBank:
         else:  # a bank without resamplers (plain collated extraction through the launch pair): the device is the caller's
             dev = torch.device("cuda" if device is None else device)
             self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        self.handle = 0
+        for f, r in zip(self.factors, self.resamplers):
+            if r.handle == 0:  # (no dense bank: not a ratio of the mixed launch either)
+                raise _lib.HipFeatError(_lib.ERR_UNSUPPORTED, f"speed factor {f} at {sampling_rate} Hz has no dense filter bank; use perturb_speed_in_arena")
         handles = np.array([r.handle for r in self.resamplers], dtype=np.uint64)
         out = np.zeros(1, dtype=np.uint64)
-        self.handle = 0
         self.lib.check("hipfeat_speed_bank_create", _lib.addr(handles) if len(handles) else None, len(handles), _lib.addr(out))
         self.handle = int(out[0])
         self._info = np.zeros(4, dtype=np.int64)

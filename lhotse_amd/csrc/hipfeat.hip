@@ -30,6 +30,7 @@
 #include "kernel_reverb.hpp"
 #include "kernel_collate.hpp"
 #include "kernel_level.hpp"
+#include "kernel_sinc.hpp"
 #include "kernel_specaug.hpp"
 #include "kernel_whisper2.hpp"
 #include "kernel_whisper3.hpp"
@@ -2767,6 +2768,153 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
     (void)hipStreamSynchronize(st);
     return fail(HIPFEAT_ERR_HIP, "collate: hipEventRecord failed: %s (the launch was enqueued and has been waited for)", hipGetErrorName(e2));
   }
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Sinc resampler without a filter bank (LowpassUsingResampling, any Resample): one launch (kernel_sinc.hpp; the table: sinc_tables.hpp)
+// --------------------------------------------------------------------------------------
+struct SincSlot {
+  SincPlan plan;
+  void* h = nullptr;  // pinned staging of the row table
+  void* d = nullptr;  // device: the row table
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool busy = false;
+};
+
+struct hipfeat_sinc {
+  int device = 0;
+  std::mutex mu;
+  CoSlots tickets;  // which tickets are planned and not yet run (the 16 slots of collate_tables.hpp)
+  SincSlot slots[kCoSlots];
+};
+
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_create(int32_t device, hipfeat_sinc** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "sinc pointer is NULL");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  hipfeat_sinc* s = new (std::nothrow) hipfeat_sinc();
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  s->device = device;
+  *out = s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_destroy(hipfeat_sinc* sc) {
+  if (!sc) return HIPFEAT_OK;
+  DeviceGuard g(sc->device);
+  for (auto& s : sc->slots) {
+    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    if (s.ev) (void)hipEventDestroy(s.ev);
+  }
+  delete sc;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_plan(hipfeat_sinc* sc, int64_t num_rows, const int64_t* h_in_offset, const int64_t* h_in_len,
+                                                             const int32_t* h_src_rate, const int32_t* h_dst_rate, const int64_t* h_out_offset,
+                                                             int64_t arena_floats, int64_t* h_out_len, int64_t* h_info) {
+  if (!sc || !h_info || (num_rows > 0 && !h_out_len)) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  // (validated into a local first: a refused table leaves the outstanding plans as they were)
+  SincPlan p = build_sinc_plan(num_rows, h_in_offset, h_in_len, h_src_rate, h_dst_rate, h_out_offset, arena_floats);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(sc->mu);
+  const int64_t ticket = sc->tickets.take();
+  if (ticket < 0)  // (never drop a live plan: its ticket would fail at run)
+    return fail(HIPFEAT_ERR_INVALID, "%d planned resamplings are outstanding: run ticket %lld first", kCoSlots,
+                (long long)sc->tickets.ticket[sc->tickets.next_ticket % kCoSlots]);
+  SincSlot& s = sc->slots[ticket % kCoSlots];
+  s.plan = std::move(p);
+  for (int64_t i = 0; i < num_rows; ++i) h_out_len[i] = s.plan.out_len[(size_t)i];
+  h_info[0] = ticket;
+  h_info[1] = s.plan.arena_need;
+  h_info[2] = s.plan.workgroups;
+  h_info[3] = s.plan.max_w;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sc, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
+  if (!sc) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(sc->mu);
+  const int slot = sc->tickets.slot_of(ticket);
+  if (slot < 0) return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned resampling (at most %d plans may be outstanding)", (long long)ticket, kCoSlots);
+  SincSlot& s = sc->slots[slot];
+  const SincPlan& p = s.plan;
+  if (arena_floats < p.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the rows reach to %lld", (long long)arena_floats, (long long)p.arena_need);
+  if (p.workgroups == 0) {  // no rows, or rows of no samples: no launch
+    sc->tickets.release(ticket);
+    return HIPFEAT_OK;
+  }
+  if (!d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
+  DeviceGuard g(sc->device);  // (the ticket stays planned until its launch is enqueued: a failed allocation or copy below leaves it to be run again)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = p.rows.size() * sizeof(SincRow);
+  const size_t lds = (size_t)p.max_w * kSincPhases * sizeof(float);
+  {
+    hipError_t e = ensure_dynamic_lds(entry<sinc_kernel>(), lds);
+    if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
+  }
+  if (s.busy) {  // the launch that used this slot's device memory last time
+    HIP_TRY(hipEventSynchronize(s.ev));
+    s.busy = false;
+  }
+  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  if (s.cap < bytes) {
+    if (s.h) (void)hipHostFree(s.h);
+    if (s.d) (void)hipFree(s.d);
+    s.h = s.d = nullptr;
+    s.cap = 0;
+    const size_t cap = std::max<size_t>(bytes * 2, 1 << 14);
+    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&s.d, cap));
+    s.cap = cap;
+  }
+  std::memcpy(s.h, p.rows.data(), bytes);
+  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+  SincArgs a;
+  a.arena = d_arena;
+  a.rows = static_cast<const SincRow*>(s.d);
+  a.num_rows = (int32_t)p.rows.size();
+  a.pad = 0;
+  hipLaunchKernelGGL(sinc_kernel, dim3((unsigned)p.workgroups), dim3(256), lds, st, a);
+  hipError_t e1 = hipGetLastError();
+  sc->tickets.release(ticket);  // enqueued (or refused by the runtime at launch): the ticket has run
+  hipError_t e2 = hipEventRecord(s.ev, st);
+  s.busy = (e2 == hipSuccess);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "sinc launch failed: %s", hipGetErrorName(e1));
+  if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
+    (void)hipStreamSynchronize(st);
+    return fail(HIPFEAT_ERR_HIP, "sinc: hipEventRecord failed: %s (the launch was enqueued and has been waited for)", hipGetErrorName(e2));
+  }
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_weights(hipfeat_sinc* sc, int32_t src_rate, int32_t dst_rate, float* d_weights, int32_t* d_first,
+                                                                int32_t* h_dims, void* stream) {
+  if (!sc || !h_dims) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  int32_t dims[4] = {0, 0, 0, 0};
+  const int st = sinc_supported(src_rate, dst_rate, dims);
+  if (st == 1) return fail(HIPFEAT_ERR_INVALID, "rates %d -> %d: both must be positive and they must differ", src_rate, dst_rate);
+  if (st != 0 && dims[3] == 0) return fail(HIPFEAT_ERR_UNSUPPORTED, "%d -> %d: the rates reduced by their gcd must not exceed 2^24", src_rate, dst_rate);
+  if (st != 0) return fail(HIPFEAT_ERR_UNSUPPORTED, "%d -> %d needs a window of %d taps per phase, the kernel holds %d", src_rate, dst_rate, dims[3], kSincMaxW);
+  h_dims[0] = dims[1];
+  h_dims[1] = dims[3];
+  h_dims[2] = dims[2];
+  if (!d_weights && !d_first) return HIPFEAT_OK;  // the sizes alone
+  if (!d_weights || !d_first) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(sc->mu);
+  DeviceGuard g(sc->device);
+  hipLaunchKernelGGL(sinc_weights_kernel, dim3((unsigned)((dims[1] + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_weights, d_first, dims[0], dims[1], dims[2],
+                     sinc_base(dims[0], dims[1]));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "sinc weights launch failed: %s", hipGetErrorName(e));
   return HIPFEAT_OK;
 }
 

@@ -155,7 +155,7 @@ def _source_rate_of(track, sampling_rate: int) -> Optional[int]:
 
 def _level_of(track):
     """The optional 9th element of a track: ``(block in front of the reverb, block behind it)`` or None.  A block is None or a list of
-    steps ``("level", [ops])`` / ``("up", k)`` / ``("down", k)`` (``pending_level_chain``)."""
+    steps ``("level", [ops])`` / ``("up", k)`` / ``("down", k)`` / ``("rate", src, dst)`` (``pending_level_chain``)."""
     lv = track[8] if len(track) > 8 else None
     return None if lv is None or (not lv[0] and not lv[1]) else lv
 
@@ -163,7 +163,8 @@ def _level_of(track):
 def _level_steps(arena, offs, lens, blocks, sr: int, tail: int):
     """Run one block per track (``blocks[i]`` = its steps or None) over the tracks at ``offs`` / ``lens``: step s of every track that has
     one, s = 0, 1, ... -- the level steps of a round in ONE ``level_in_arena`` call, in place; its rate steps (the oversampling around
-    a ``Clipping``: sr -> k sr, k n samples, and back, n samples) in one ``resample_in_arena`` call that writes behind ``tail``.
+    a ``Clipping``: sr -> k sr, k n samples, and back, n samples; the two halves of a band bracket, ``("rate", src, dst)``: the router
+    sends their rate pairs to one bankless launch) in one ``resample_in_arena`` call that writes behind ``tail``.
     ``arena`` None: host arithmetic only.  -> (offsets, lengths, the first free float behind what was written, 16-byte aligned)."""
     from .augmentation import resample_layout
 
@@ -174,7 +175,8 @@ def _level_steps(arena, offs, lens, blocks, sr: int, tail: int):
         idx = [i for i, st in enumerate(step) if st is not None and st[0] == "level"]
         if idx and arena is not None:
             _level_in_arena(arena, offs[idx], lens[idx], [step[i][1] for i in idx])
-        ratios = [None if st is None or st[0] == "level" else ((sr, sr * int(st[1])) if st[0] == "up" else (sr * int(st[1]), sr)) for st in step]
+        ratios = [None if st is None or st[0] == "level" else (int(st[1]), int(st[2])) if st[0] == "rate" else
+                  ((sr, sr * int(st[1])) if st[0] == "up" else (sr * int(st[1]), sr)) for st in step]
         if any(r is not None for r in ratios):
             if arena is None:
                 offs, lens, tail = resample_layout(offs, lens, ratios, tail)
@@ -277,10 +279,13 @@ class _ArenaChain:
         if two_pass:
             _, lens0, rs_floats = resample_layout(np.zeros(len(items), dtype=np.int64), lens0, ratios, 0)  # (a multiple of 4)
         _, ll, res_floats = perturbed_layout(np.zeros(len(items), dtype=np.int64), lens0, factors, sr, 0)  # (a multiple of 4)
-        rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) resampled tracks
-        lv_floats = [0, 0]  # what the oversampling passes of the two level blocks write (a level step itself works in place)
+        lv_floats = [0, 0]  # what the rate steps of the two level blocks write (a level step itself works in place)
+        if has_level:  # (a band bracket may give back a sample more than it took: what follows a block counts with the block's lengths)
+            ll = np.array(ll, dtype=np.int64)
+            _, ll[:num_tracks], lv_floats[0] = _level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[0], int(sr), 0)
+        rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) tracks that reach it
         if has_level:
-            lv_floats = [_level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[w], int(sr), 0)[2] for w in (0, 1)]
+            _, ll[:num_tracks], lv_floats[1] = _level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[1], int(sr), 0)
         first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
         if mixed_ids:
             short = mixed_num_samples(first, sl, do) < np.asarray(cap, dtype=np.int64)
@@ -388,7 +393,9 @@ class FusedMiniBatch(_ArenaChain):
         the route it took before there was one.  An optional 9th element ``(block in front of the reverb, block behind it)`` changes
         the track's level (``Volume`` / ``Clipping``, ``lhotse_amd.augmentation.level_in_arena``): a block is None or a list of steps
         ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``, ``("up", k)``, ``("down", k)`` -- the last two are
-        the ``Resample(sr -> k sr)`` / ``Resample(k sr -> sr)`` that ``clip_amplitude(oversampling=k)`` puts around its ``Clipping``; the
+        the ``Resample(sr -> k sr)`` / ``Resample(k sr -> sr)`` that ``clip_amplitude(oversampling=k)`` puts around its ``Clipping`` --,
+        ``("rate", src, dst)`` -- one ``Resample(src -> dst)`` between any two rates that ``resample_in_arena`` routes; the band bracket
+        of ``LowpassUsingResampling`` is ``("rate", sr, m)``, ``("rate", m, sr)`` --; the
         blocks run behind the ``Speed`` on the untruncated track, the first in front of the reverb, the second behind it.  Absent or
         None: exactly the route of before.
 
@@ -615,25 +622,18 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         p = pending_transforms(cut, gpu_reverb)
         return None if p is None or p[1] is None else p
 
-    MAX_RESAMPLE_BANK_FLOATS = 1 << 20  # the largest filter bank (new x (2 width + orig) floats, reduced rates) the device route takes
+    from .augmentation import MAX_RESAMPLE_BANK_FLOATS, _sinc_bank_floats, resample_route  # noqa: F401  (one rule for both sides)
 
-    def _sinc_bank_floats(source_rate: int, target_rate: int) -> int:
-        """Floats of the reference's filter bank for source -> target (lhotse/augmentation/resample.py:219-236: rates reduced by their
-        gcd, lowpass_filter_width 6, rolloff 0.99), from the rates alone."""
-        from math import ceil
-
-        g = gcd(int(source_rate), int(target_rate))
-        orig, new = int(source_rate) // g, int(target_rate) // g
-        width = ceil(6 * orig / (min(orig, new) * 0.99))
-        return new * (2 * width + orig)
-
-    def pending_chain(cut, gpu_reverb: bool = True, gpu_resample: bool = True) -> Optional[Tuple[Optional[int], float, Optional[dict]]]:
+    def pending_chain(cut, gpu_reverb: bool = True, gpu_resample: bool = True, bankless: bool = False) -> Optional[Tuple[Optional[int], float, Optional[dict]]]:
         """``pending_transforms`` with a ``Resample`` in front: a mono cut (no video) over a recording whose transform list is
         ``[Resample(a -> sr)]? [Speed]? [ReverbWithImpulseResponse]?`` with ``sr == cut.sampling_rate`` and ``a != sr`` ->
         ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None)``.  None = load it the reference's way:
         whatever ``pending_transforms`` refuses behind the ``Resample``; a ``Resample`` that is not the first transform
-        (``[Speed, Resample]``) or not the only one (``LowpassUsingResampling`` adds two); one to another rate than the cut's; the
-        ``sox`` resampling backend (``LHOTSE_RESAMPLING_BACKEND=sox``: another filter); a reduced filter bank of more than 2^20 floats;
+        (``[Speed, Resample]``) or not the only one (the two that ``LowpassUsingResampling`` adds are ``pending_level_chain``'s band bracket,
+        not this rule's); one to another rate than the cut's; the
+        ``sox`` resampling backend (``LHOTSE_RESAMPLING_BACKEND=sox``: another filter); a reduced filter bank of more than 2^20 floats
+        -- unless ``bankless`` is set, as the strategies set it: then any pair of rates that ``resample_in_arena`` routes is taken
+        (``resample_route``: 11127 -> 16000 goes to the kernel without a bank), and only what no kernel serves is refused --;
         any ``Resample`` when ``gpu_resample`` is off."""
         if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
             return None
@@ -650,7 +650,9 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             return None
         from lhotse.audio.resampling_backend import get_current_resampling_backend  # the reference's own switch is the contract
 
-        if get_current_resampling_backend() != "default" or _sinc_bank_floats(src, dst) > MAX_RESAMPLE_BANK_FLOATS:
+        if get_current_resampling_backend() != "default":
+            return None
+        if resample_route(src, dst) is None if bankless else _sinc_bank_floats(src, dst) > MAX_RESAMPLE_BANK_FLOATS:
             return None
         from lhotse.utils import fastcopy
 
@@ -661,8 +663,13 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
     MAX_LEVEL_OPS = 4  # ops of one block = of one program of hipfeat_level_plan
 
     def _has_level_op(cut) -> bool:
+        """A ``Volume`` or ``Clipping`` in the list, or a ``Resample`` FROM the cut's rate: the opening of a bracket (a band bracket may
+        be a block's only element)."""
         tf = cut.recording.transforms if type(cut).__name__ == "MonoCut" and cut.has_recording else None
-        return bool(tf) and any(_transform_name(t) in LEVEL_NAMES for t in tf)
+        if not tf:
+            return False
+        sr = int(cut.sampling_rate)
+        return any(_transform_name(t) in LEVEL_NAMES or (_transform_name(t) == "Resample" and _resample_rates(t)[0] == sr) for t in tf)
 
     def _kwargs_of(t, names) -> dict:
         return {k: t["kwargs"][k] for k in names if k in t["kwargs"]} if isinstance(t, dict) else {k: getattr(t, k) for k in names}
@@ -673,9 +680,10 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
 
     def _level_block(tf: list, pos: int, sr: int):
         """The run of level elements of ``tf`` from ``pos`` on -- ``Volume`` | ``Clipping`` | ``Resample(sr -> k sr) Clipping
-        Resample(k sr -> sr)`` -- as steps -> (steps or None when there is none, the position behind it); ``False`` in place of the steps:
-        the run is not served (more than 4 ops, two ``Clipping``s, k outside 2 ... 8 or not an integer, a ``Resample`` that is not such a
-        bracket)."""
+        Resample(k sr -> sr)`` | the band bracket ``Resample(sr -> m) Resample(m -> sr)``, which counts as two ops -- as steps -> (steps or
+        None when there is none, the position behind it); ``False`` in place of the steps: the run is not served (more than 4 ops, two
+        ``Clipping``s, k outside 2 ... 8 or not an integer, a ``Resample`` that is not such a bracket, a band bracket whose rates no
+        route serves: ``resample_route``)."""
         steps, ops, clips = [], 0, 0
 
         def level(op):
@@ -696,6 +704,13 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             elif name == "Clipping":
                 level(clip_op(tf[pos]))
                 clips, pos = clips + 1, pos + 1
+            elif name == "Resample" and _resample_rates(tf[pos])[0] == sr and pos + 1 < len(tf) and _transform_name(tf[pos + 1]) == "Resample":
+                # the band bracket B = Resample(sr -> m) Resample(m -> sr) of LowpassUsingResampling (cut_transforms/lowpass.py): two ops
+                m = _resample_rates(tf[pos])[1]
+                if _resample_rates(tf[pos + 1]) != (m, sr) or m == sr or resample_route(sr, m) is None or resample_route(m, sr) is None:
+                    return False, pos  # (among them a window beyond the bankless kernel's cap: 48 kHz -> under 6.2 kHz)
+                steps += [("rate", sr, m), ("rate", m, sr)]
+                pos, ops = pos + 2, ops + 1  # (and the common count below: a bracket is two of a block's four ops)
             elif name == "Resample" and _resample_rates(tf[pos])[0] == sr:  # the opening of clip_amplitude(oversampling=k) (recording.py:959-973)
                 up = _resample_rates(tf[pos])[1]
                 if pos + 2 >= len(tf) or _transform_name(tf[pos + 1]) != "Clipping" or _transform_name(tf[pos + 2]) != "Resample":
@@ -715,13 +730,14 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         """The rule of the level route: a mono cut (no video) over a recording whose transform list is
 
             [Resample(a -> sr)]? [Speed]? L? [ReverbWithImpulseResponse]? L?
-            L = ( Volume | Clipping | Resample(sr -> k sr) Clipping Resample(k sr -> sr) ){1 ... 4 ops, at most one Clipping}
+            L = ( Volume | Clipping | Resample(sr -> k sr) Clipping Resample(k sr -> sr) | B ){1 ... 4 ops, at most one Clipping}
+            B = Resample(sr -> m) Resample(m -> sr), m != sr: the band bracket of LowpassUsingResampling (m = 2 x cutoff); two ops
 
-        with at least one level op -> ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None, (the steps of
+        with at least one level op or bracket -> ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None, (the steps of
         the L in front of the reverb or None, of the L behind it or None))``; the first three are ``pending_chain``'s answer for the
         chain without its level ops.  The bracketed form is what ``clip_amplitude(oversampling=k)`` appends (recording.py:937-975), k an
         integer 2 ... 8; it needs ``gpu_resample`` and a reference that resamples with its sinc module (``_reference_resamples_with_sinc``).  Steps: ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``,
-        ``("up", k)``, ``("down", k)`` (``FusedMiniBatch.features_of_tracks``).  None = not this rule's business -- a chain without a level
+        ``("up", k)``, ``("down", k)``, and for a band bracket ``("rate", sr, m)``, ``("rate", m, sr)`` -- any rates: ``resample_in_arena`` routes each pair to its dense bank or to the bankless kernel; the preconditions are the oversampling bracket's -- (``FusedMiniBatch.features_of_tracks``).  None = not this rule's business -- a chain without a level
         op, which the older rules decide -- or not served: anything but a ``MonoCut`` (a ``MultiCut``, a ``MixedCut`` as a whole), a recording
         with more than one channel (also when the ``MonoCut`` selects one of them), a level op in front of the ``Speed`` or the leading ``Resample``, a block of
         more than 4 ops or with two ``Clipping``s, k outside 2 ... 8, anything else in the list, and whatever ``pending_chain`` refuses
@@ -748,7 +764,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             return None  # (the oversampling runs the device's sinc resampler: only where the reference's Resample runs its own)
         from lhotse.utils import fastcopy
 
-        chain = pending_chain(fastcopy(cut, recording=fastcopy(cut.recording, transforms=rest)), gpu_reverb, gpu_resample)
+        chain = pending_chain(fastcopy(cut, recording=fastcopy(cut.recording, transforms=rest)), gpu_reverb, gpu_resample, bankless=True)
         return None if chain is None else (chain[0], chain[1], chain[2], (pre, post))
 
     def _read_level_track(cut, lc, offset: int = 0, snr=None, is_ref: bool = True) -> Optional[tuple]:
@@ -758,15 +774,23 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         sr = cut.sampling_rate
         raw = read_before_chain(cut)
         want = compute_num_samples(cut.duration, sr)
-        if chain_num_samples(len(raw), source_rate, factor, sr) < want:
+        if chain_num_samples(len(raw), source_rate, factor, sr, blocks) < want:
             return None
         return (raw, factor, offset, snr, is_ref, want, None if rv is None else (load_reverb_rir(rv), rv["normalize_output"]), source_rate, blocks)
 
-    def chain_num_samples(num_samples: int, source_rate: Optional[int], factor: float, sampling_rate: int) -> int:
-        """Samples that come out of ``[Resample(source_rate -> sr)]? [Speed(factor)]?`` for ``num_samples`` going in: per stage
-        ``ceil(new * n / orig)`` in float32 with the rates reduced by their gcd (resample.py:219-222, :309)."""
+    def chain_num_samples(num_samples: int, source_rate: Optional[int], factor: float, sampling_rate: int, blocks=None) -> int:
+        """Samples that come out of ``[Resample(source_rate -> sr)]? [Speed(factor)]?`` and the rate steps of the level ``blocks`` behind
+        them (``pending_level_chain``: the two stages of a band bracket; an oversampling bracket gives back what it took; the level
+        ops and the reverb keep the length) for ``num_samples`` going in: per stage ``ceil(new * n / orig)`` in float32 with the rates
+        reduced by their gcd (resample.py:219-222, :309)."""
+        sr = int(sampling_rate)
+        stages = [(source_rate, sr), (None if factor == 1.0 else round(sr * factor), sr)]
+        for block in blocks or ():
+            for st in block or ():
+                if st[0] != "level":
+                    stages.append((int(st[1]), int(st[2])) if st[0] == "rate" else (sr, sr * int(st[1])) if st[0] == "up" else (sr * int(st[1]), sr))
         n = int(num_samples)
-        for src, dst in ((source_rate, sampling_rate), (None if factor == 1.0 else round(sampling_rate * factor), sampling_rate)):
+        for src, dst in stages:
             if src is not None and int(src) != int(dst):
                 g = gcd(int(src), int(dst))
                 n = int(np.ceil(np.float32((int(dst) // g) * n / (int(src) // g))))
@@ -885,7 +909,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 track = _read_level_track(cut, lc)
                 if track is not None:
                     return [track], 1.0, track[5]
-            chain = pending_chain(cut, gpu_reverb) if gpu_resample else None
+            chain = pending_chain(cut, gpu_reverb, bankless=True) if gpu_resample else None
             if chain is not None and chain[0] is not None and (gpu_speed or chain[1] == 1.0):  # a Resample in front: the cut is one track
                 track = _read_chain_track(cut, chain)
                 if track is not None:
@@ -967,7 +991,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 out.append((c, lc[1], off, t.snr, t is ref, lc[2], lc[0], lc[3]))  # (reverb or None, source rate or None, level blocks)
                 continue
             elif gpu_resample and _has_pending_resample(c):
-                chain = pending_chain(c, gpu_reverb)
+                chain = pending_chain(c, gpu_reverb, bankless=True)
                 if chain is None:
                     return None
                 factor = chain[1]
