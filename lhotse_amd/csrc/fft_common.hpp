@@ -219,4 +219,25 @@ __device__ __forceinline__ float fast_log(float x) {
 #endif
 }
 
+// Epilogue of a TRANSPOSED 4 x 4 x 1 accumulator (lane = 4 slot + frame, register = filter 4g .. 4g + 3: the MFMA's source operands
+// swapped, every product and every chain as before): log and ONE 16-byte store per lane, all under one lane mask that is built first
+// ("the slot has an output, and the lane's frame exists"), so nothing in it branches on the wave-uniform nf.  `col0` is the slot's first
+// column 4g (a filter count that is a multiple of 4 fills a slot's four columns or none); rows need not be 16-byte aligned (global
+// stores have no alignment rule).  The round's row base is the scalar address and the lane adds (frame * stride + col0) * 4 as a 32-bit
+// offset: one 24-bit multiply per round (v_mul_lo_u32 issues at a quarter of its rate) and an add-shift per set.  The host launches
+// these instances only with a row stride below kMel4WideMaxStride floats, where three rows and a column fit both.
+constexpr int64_t kMel4WideMaxStride = 1 << 22;
+__device__ __forceinline__ void mel4_store_wide(float* row0, int lane, unsigned col0, int M, int stride, int nf, const float (&v)[4]) {
+  const int fr = lane & 3;
+  if (col0 < (unsigned)M && fr < nf) {
+    f32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = fast_log(v[i]);
+    unsigned rowoff;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(rowoff) : "v"(fr), "s"(stride));
+    const unsigned off = (rowoff + col0) << 2;
+    asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(off), "v"(o), "s"(row0) : "memory");
+  }
+}
+
 }  // namespace hipfeat

@@ -49,7 +49,7 @@ static thread_local char g_err[512] = "";
 
 // Environment switches, two classes:
 //   route_env  ROUTING switches choose among kernels / launch routes that ALL meet the parity bar (HIPFEAT_FORCE_GENERIC, *_VARIANT,
-//              HIPFEAT_NO_FIXED_SCHEDULE, HIPFEAT_NO_WAVE_*, HIPFEAT_NO_FLAT, HIPFEAT_RESAMPLE_GENERIC / _MFMA, HIPFEAT_MB_NO_INLINE): the GPU
+//              HIPFEAT_NO_FIXED_SCHEDULE, HIPFEAT_NO_WAVE_*, HIPFEAT_NO_FLAT, HIPFEAT_NO_WIDE_STORE, HIPFEAT_RESAMPLE_GENERIC / _MFMA, HIPFEAT_MB_NO_INLINE): the GPU
 //              suite uses them to compare the instances of ONE library against each other, bit for bit where the arithmetic is the same.
 //   exp_env    EXPERIMENT switches skip work or retune launch shapes (HIPFEAT_MB_SKIP = deliberately wrong results, HIPFEAT_MB_SLOTS,
 //              HIPFEAT_ROUNDS, HIPFEAT_ROUNDS_R3).  They exist only in builds with -DHIPFEAT_EXPERIMENTS (tools/variants.py); in the
@@ -128,6 +128,10 @@ struct hipfeat_plan {
   Route route = Route::Generic;
   const void* fn = nullptr;       // kernel instance
   const void* fn_flat = nullptr;  // fft512c: the FLAT instance of ragged batches (nullptr: none)
+  // fft512c with the 16-byte feature store: the one-dword-per-frame twins of fn / fn_flat, launched where the layout's row stride is
+  // kMel4WideMaxStride or more (the wide store's 32-bit lane offset holds three rows and a column only below it); nullptr: fn / fn_flat serve all
+  const void* fn_far = nullptr;
+  const void* fn_flat_far = nullptr;
   int block = 0;                  // threads per workgroup
   size_t lds = 0;                 // dynamic LDS bytes
   // device constants
@@ -402,16 +406,18 @@ static hipfeat_status claim_tile(hipfeat_plan* p, Route route, const void* fn, c
 static bool fft512c_has_flat(int nrows, int N) { return nrows == 13 && N >= 384; }
 
 // (rows, frame length, mode) -> kernel instance
-template <int MODE>
+template <int MODE, bool WIDE = false>
 static const void* fft512c_pick(int nrows, int N, bool flat) {
-  if (flat && fft512c_has_flat(nrows, N)) return entry<fft512c_kernel<13, 12, MODE, true>>();
-  if (nrows == 10) return entry<fft512c_kernel<10, 0, MODE>>();
+  if (flat && fft512c_has_flat(nrows, N)) return entry<fft512c_kernel<13, 12, MODE, true, WIDE>>();
+  if (nrows == 10) return entry<fft512c_kernel<10, 0, MODE, false, WIDE>>();
   // 25 ms at 16 kHz (N = 400: 12 full rows of 32 samples + a partial one) gets the instance without length masks on the full rows
-  if (nrows == 13 && N >= 384) return entry<fft512c_kernel<13, 12, MODE>>();
-  if (nrows == 13) return entry<fft512c_kernel<13, 0, MODE>>();
-  return entry<fft512c_kernel<16, 0, MODE>>();
+  if (nrows == 13 && N >= 384) return entry<fft512c_kernel<13, 12, MODE, false, WIDE>>();
+  if (nrows == 13) return entry<fft512c_kernel<13, 0, MODE, false, WIDE>>();
+  return entry<fft512c_kernel<16, 0, MODE, false, WIDE>>();
 }
-static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat) {
+// wide: the transposed accumulators with one 16-byte store per lane and set (log-mel modes only)
+static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat, bool wide) {
+  if (wide && mode <= 1) return mode == 0 ? fft512c_pick<0, true>(nrows, N, flat) : fft512c_pick<1, true>(nrows, N, flat);
   return mode == 0 ? fft512c_pick<0>(nrows, N, flat)
                    : (mode == 1 ? fft512c_pick<1>(nrows, N, flat) : (mode == 2 ? fft512c_pick<2>(nrows, N, flat) : fft512c_pick<3>(nrows, N, flat)));
 }
@@ -422,13 +428,22 @@ static hipfeat_status setup_fft512c(hipfeat_plan* p, const PlanInputs& in, int n
   const bool mfcc = p->cfg.kind == HIPFEAT_MFCC;
   if (mfcc && (in.M > 4 * kCDctChunks || in.C > 64 || !in.dct)) return HIPFEAT_OK;
   const WaveAutoTables t = build_fft512c_tables(in, nrows, {kCPRowStride, kCMaxSets, kCMaxSteps, kCWaves, kCRegion}, kCDctChunks, kCDctChunksSmall);
-  if (!t.fits || t.lds > 80 * 1024 || (t.xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
+  // two workgroups of 8 waves per CU or nothing; the span request covers kCSpanPieces KiB (the LDS budget leaves a wave's span less)
+  if (!t.fits || t.lds > 80 * 1024 || t.xs_floats > 256 * kCSpanPieces) return HIPFEAT_OK;
+  // A filter count that is a multiple of 4 fills the four columns of a schedule slot or none of them (mel4_schedule.hpp): the log-mel
+  // instances with transposed accumulators then store a lane's four columns with one 16-byte store.  HIPFEAT_NO_WIDE_STORE (routing switch)
+  // keeps the one-dword-per-frame epilogue, which the other filter counts and the MFCC modes always have: same bits either way.
+  const bool wide = !mfcc && t.mode <= 1 && in.M % 4 == 0 && !route_env("HIPFEAT_NO_WIDE_STORE");
   // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
-  hipfeat_status st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false), t, 4, 8, 16,
+  hipfeat_status st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false, wide), t, 4, 8, 16,
                                       strf("fft512c_kernel<%d> %s", nrows, mfcc ? "mfcc" : "fbank"));
-  if (st == HIPFEAT_OK && fft512c_has_flat(nrows, in.N)) {  // the same launch shape, chosen per layout (build_descs)
-    p->fn_flat = fft512c_dispatch(t.mode, nrows, in.N, true);
-    hipError_t e = ensure_dynamic_lds(p->fn_flat, t.lds);
+  if (st == HIPFEAT_OK && wide) p->kernel_name += " store=16B";
+  const void** more[3] = {&p->fn_flat, &p->fn_far, &p->fn_flat_far};  // the same launch shape, chosen per layout (build_descs) / per launch
+  for (int i = 0; st == HIPFEAT_OK && i < 3; ++i) {
+    const bool flat = i != 1, far = i != 0;
+    if ((flat && !fft512c_has_flat(nrows, in.N)) || (far && !wide)) continue;
+    *more[i] = fft512c_dispatch(t.mode, nrows, in.N, flat, wide && !far);
+    hipError_t e = ensure_dynamic_lds(*more[i], t.lds);
     if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", t.lds, hipGetErrorName(e));
   }
   return st;
@@ -1172,7 +1187,8 @@ static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay
       arg = &bp;
       break;
   }
-  const void* fn = lay->flat && plan->fn_flat ? plan->fn_flat : plan->fn;
+  const bool far = plan->fn_far && lay->out_row_stride >= kMel4WideMaxStride;
+  const void* fn = lay->flat && plan->fn_flat ? (far ? plan->fn_flat_far : plan->fn_flat) : (far ? plan->fn_far : plan->fn);
   void* args[] = {arg};
   DeviceGuard g(plan->device);
   set_lds_poison(plan->lds);

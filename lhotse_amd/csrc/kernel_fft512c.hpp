@@ -134,6 +134,41 @@ __device__ __forceinline__ void exchange_halves(unsigned wr, unsigned rd, unsign
       : "memory", "scc");
 }
 
+// The request for a wave's sample span by LDS-DMA, as ONE branch-free instruction sequence of kCSpanPieces 1 KiB pieces: lane i supplies the
+// global address of its 16 bytes (src + lane_bytes, lane_bytes = 16 i) and the hardware writes them to M0 + 16 i; a piece's position rides
+// in the immediate offset, which advances the global and the LDS address alike, so the pieces share one lane offset and one M0.  Piece c
+// is issued under the lane mask lane_bytes + 1024 c < span_bytes -- every lane of a whole piece, the first lanes of the last one, none
+// beyond (a vector-memory instruction without lanes does nothing).  hipcc turned a wave-uniform test per piece on the run-time piece count
+// into an out-of-line block per piece: a taken branch out and one back for each, round after round.  Four pieces cover every span a plan
+// can have: two workgroups per CU leave a wave's span buffer less than 1024 floats (hipfeat.hip::setup_fft512c checks it).
+// src: wave-uniform address of the span's first sample; lds: LDS byte address of the wave's span buffer; span_bytes: 4 xs_floats
+constexpr int kCSpanPieces = 4;
+__device__ __forceinline__ void span_pieces(const char* src, unsigned lds, unsigned lane_bytes, int span_bytes) {
+  static_assert(kCSpanPieces == 4, "the immediate offset reaches 4095");
+  unsigned long long saved;
+  int rem;  // bytes of the span from this lane's 16 onwards
+  asm volatile(
+      "v_sub_u32 %[rem], %[sb], %[lb]\n\t"
+      "s_mov_b32 m0, %[lds]\n\t"
+      "s_mov_b64 %[sv], exec\n\t"
+      "v_cmp_lt_i32 vcc, 0, %[rem]\n\t"
+      "s_and_b64 exec, %[sv], vcc\n\t"
+      "global_load_lds_dwordx4 %[lb], %[src]\n\t"
+      "v_cmp_lt_i32 vcc, 0x400, %[rem]\n\t"
+      "s_and_b64 exec, %[sv], vcc\n\t"
+      "global_load_lds_dwordx4 %[lb], %[src] offset:1024\n\t"
+      "v_cmp_lt_i32 vcc, 0x800, %[rem]\n\t"
+      "s_and_b64 exec, %[sv], vcc\n\t"
+      "global_load_lds_dwordx4 %[lb], %[src] offset:2048\n\t"
+      "v_cmp_lt_i32 vcc, 0xc00, %[rem]\n\t"
+      "s_and_b64 exec, %[sv], vcc\n\t"
+      "global_load_lds_dwordx4 %[lb], %[src] offset:3072\n\t"
+      "s_mov_b64 exec, %[sv]"
+      : [rem] "=&v"(rem), [sv] "=&s"(saved)
+      : [sb] "s"(span_bytes), [lb] "v"(lane_bytes), [lds] "s"(lds), [src] "s"(src)
+      : "memory", "vcc", "scc", "m0");
+}
+
 // NROWS: pass-1 rows that can hold samples; NFULL: rows known to lie entirely inside the frame (N >= 32 NFULL): no length masks there;
 // MODE 0: log-mel filterbank on 2 accumulator sets x 16 steps (many narrow filters: the 80-filter default); 1: log-mel on 1 set x 32
 // steps (few, wide filters: 23 / 40); 2: MFCC = mode 1 + the DCT as a second run of 4 x 4 x 1 blocks (Wav2MFCC, layers.py:708-724);
@@ -145,7 +180,14 @@ __device__ __forceinline__ void exchange_halves(unsigned wr, unsigned rd, unsign
 // work: 17 % of a LibriSpeech-like batch.  A wave keeps the descriptor of the cut it is in and steps to the next one when its quad index
 // passes the cut's last quad (CutDesc::first_block = first quad of the cut; one wave-uniform compare per round, a descriptor load per
 // crossing); the workgroup's first cut comes from the workgroup -> cut map (common.hpp).  The four frames of a quad always belong to ONE cut.
-template <int NROWS, int NFULL, int MODE, bool FLAT = false>
+//
+// WIDE (log-mel modes, filter count a multiple of 4): the filterbank MFMAs take the weight as their first and the power as their second
+// source operand, so the 4 x 4 block lands transposed -- lane = 4 slot + frame, register = filter 4g .. 4g + 3 -- with every product and
+// every accumulation chain as before (bit-identical values).  A lane then holds four CONSECUTIVE columns of ONE output row: one
+// global_store_dwordx4 per lane and set instead of four global_store_dword per set, one row base per round instead of four, and no
+// wave-uniform branch on the number of live frames (fft_common.hpp::mel4_store_wide).  Chosen at plan creation (hipfeat.hip); launched
+// with row strides below kMel4WideMaxStride only.
+template <int NROWS, int NFULL, int MODE, bool FLAT = false, bool WIDE = false>
 __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   HF_POISON_LDS(smem);
@@ -177,6 +219,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
   for (int i = tid; i < p.shared_floats; i += 64 * kCWaves) smem[i] = p.shared_consts[i];
   float* xs = smem + p.shared_floats + wv * (p.xs_floats + kCRegion);
   float* myreg = xs + p.xs_floats;
+  static_assert(!WIDE || MODE == 0 || MODE == 1, "the 16-byte store is the log-mel epilogue's");
   const bool dc = (p.flags & F_REMOVE_DC) != 0;
   const float inv_n = 1.0f / (float)N;
   const float c = p.preemph;
@@ -187,9 +230,14 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
   auto stage_span = [&](const CutDesc& cd, int f0, unsigned lane4) {  // (the descriptor of the round that is being staged)
     const float* __restrict__ w = p.wave + cd.wave_off;
     const int64_t j0 = (int64_t)f0 * shift - p.npad_left;
-    if (j0 >= 0 && j0 + p.xs_floats <= cd.num_samples) {
+    if (__builtin_expect(j0 >= 0 && j0 + p.xs_floats <= cd.num_samples, 1)) {  // (the edge rule's code lies out of the interior round's way)
       const char* src = reinterpret_cast<const char*>(w + j0);  // uniform
-      // whole 1 KiB pieces without a lane mask, then the (shorter) last piece: straight-line code, one exec mask
+#ifndef HIPFEAT_ABL_SPAN_BRANCHES
+      // 1 KiB pieces, each under the lane mask "my 16 bytes start inside the span" (full for the whole pieces, partial for the last one):
+      // straight-line code without a branch (span_pieces)
+      typedef __attribute__((address_space(3))) float lds_float;
+      span_pieces(src, (unsigned)(size_t)(lds_float*)xs, 4u * lane4, 4 * p.xs_floats);
+#else  // experiment build: a wave-uniform test per whole piece, as before (the same requests)
       const int nfull = p.xs_floats >> 8;
 #pragma unroll
       for (int ch = 0; ch < 6; ++ch) {
@@ -200,6 +248,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       if ((unsigned)nfull * 256u + lane4 < (unsigned)p.xs_floats)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)nfull * 1024u + 4u * lane4)),
                                          (__attribute__((address_space(3))) void*)(xs + nfull * 256), 16, 0, 0);
+#endif
     } else {
       for (int i = (int)(lane4 >> 2); i < p.xs_floats; i += 64) xs[i] = load_sample(w, j0 + i, cd.num_samples, cd.padded_len);  // the whole buffer: rows past N are read (and met by a zero window) too
     }
@@ -518,7 +567,13 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       for (int c4 = 0; c4 < (S * T) / 8; ++c4) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          if (MODE == 0) {
+          if (MODE == 0 && WIDE) {  // D[i][j] += A[i] B[j], register i, lane j: weight first = filters in the registers, frames on the lanes
+            acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[0][c4][i], av[0][c4][i], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[S - 1][c4][i], av[S - 1][c4][i], acc[1], 0, 0, 0);
+          } else if (WIDE) {
+            acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[0][2 * c4][i], av[0][2 * c4][i], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[0][2 * c4 + 1][i], av[0][2 * c4 + 1][i], acc[1], 0, 0, 0);
+          } else if (MODE == 0) {
             acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[0][c4][i], bv[0][c4][i], acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[S - 1][c4][i], bv[S - 1][c4][i], acc[1], 0, 0, 0);
           } else {  // one set of 32 steps: even chunks on chain 0, odd chunks on chain 1
@@ -533,14 +588,20 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       float val[S][4];
 #pragma unroll
       for (int s = 0; s < S; ++s) {
-        mel4_reduce_floor(acc[s], lt_m4[s], lt_m8[s], p.mel_floor, val[s]);
+        mel4_reduce_floor(acc[s], lt_m4[s], lt_m8[s], p.mel_floor, val[s]);  // (m4 / m8 are per slot: the same on the transposed block)
+        if (!WIDE) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) val[s][i] = fast_log(val[s][i]);
+          for (int i = 0; i < 4; ++i) val[s][i] = fast_log(val[s][i]);
+        }
       }
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         const int col = lt_col[s];
-        if (kMfcc) {
+        if (WIDE) {
+          // the slot's first column is the table entry of its quad lane 0 (the table itself keeps lane = 4 slot + filter)
+          const int col0 = __builtin_amdgcn_update_dpp(0, col, DPP_QUAD(0, 0, 0, 0), 0xF, 0xF, true);
+          mel4_store_wide(orow, lane_o, (unsigned)col0, p.M, (int)p.out_stride, nf, val[s]);
+        } else if (kMfcc) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) lm[i] = val[s][i];
         } else if (col < p.M) {

@@ -118,7 +118,7 @@ def main():
         name, root = sys.argv[2], sys.argv[3]
         entry = config_entry(name, root)
         if len(sys.argv) > 4 and os.path.exists(sys.argv[4]):  # tools/pmc_any.sh summary of the same config (separate --pmc passes)
-            sym = {"mfcc40_libri": "fft512c_kernel<13, 12, 2, true>", "onthefly": "fft512c_kernel<13, 12, 0, true>"}[name]
+            sym = {"mfcc40_libri": "fft512c_kernel<13, 12, 2, true", "onthefly": "fft512c_kernel<13, 12, 0, true"}[name]
             entry["sq_counters_per_dispatch"] = sq_counters(sys.argv[4], sym)
             if name == "onthefly":
                 entry["sq_counters_per_dispatch_prep_launch"] = sq_counters(sys.argv[4], "minibatch_prep_inline_kernel")

@@ -32,9 +32,10 @@ def main():
     run = sys.argv[1]
     lens = bench.libri_like_lengths(8000, 1000)
     frames = {"fbank16k": 1e7, "mfcc40_libri": float(((lens + 80) // 160).sum())}
-    fb = block(f"{run}/pmc_fbank16k/summary.txt", "void hipfeat::fft512c_kernel<13, 12, 0, false>")
-    mf = block(f"{run}/pmc_mfcc40_libri/summary.txt", "void hipfeat::fft512c_kernel<13, 12, 2, true>")
-    of = block(f"{run}/pmc_onthefly/summary.txt", "void hipfeat::fft512c_kernel<13, 12, 0, true>")
+    # (symbols without their closing bracket: the instances carry a fifth template argument, the 16-byte store, since profiles/r08_fft512c_epilogue_ab.txt)
+    fb = block(f"{run}/pmc_fbank16k/summary.txt", "void hipfeat::fft512c_kernel<13, 12, 0, false")
+    mf = block(f"{run}/pmc_mfcc40_libri/summary.txt", "void hipfeat::fft512c_kernel<13, 12, 2, true")
+    of = block(f"{run}/pmc_onthefly/summary.txt", "void hipfeat::fft512c_kernel<13, 12, 0, true")
     pr = block(f"{run}/pmc_onthefly/summary.txt", "hipfeat::minibatch_prep_inline_kernel")
     # a 600 s mini-batch, two thirds of its cuts perturbed by 0.9 / 1.1: frames of the collated feature launch from its matrix-core count
     # (8 blocks per full frame quad in MODE 0): the launch covers ~ SQ_INSTS_MFMA / 8 frames
