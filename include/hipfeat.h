@@ -340,7 +340,8 @@ HIPFEAT_API hipfeat_status hipfeat_minibatch_run(hipfeat_speed_bank* bank, int64
  * cut, a 17th plan while 16 are planned and not yet run) returns HIPFEAT_ERR_INVALID, more than 256 tracks in a cut HIPFEAT_ERR_UNSUPPORTED,
  * and plans nothing.
  * hipfeat_mix_run enqueues the two launches of a planned mix on `stream` (a ticket runs once); an unknown ticket or an arena smaller
- * than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.
+ * than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.  A ticket is consumed when its launch has been enqueued: after a
+ * HIPFEAT_ERR_HIP from an allocation or the table copy in front of it, it can be run again.
  */
 typedef struct hipfeat_mixer hipfeat_mixer;
 HIPFEAT_API hipfeat_status hipfeat_mixer_create(int32_t device, hipfeat_mixer** mixer);
@@ -376,7 +377,8 @@ HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int64_t ticket,
  * A bad table (a negative offset, N < 1 or L < 1, a shift outside [0, L), a source or impulse response that reaches past tail_start, a
  * 17th plan while 16 are planned and not yet run) returns HIPFEAT_ERR_INVALID and plans nothing.
  * hipfeat_reverb_run enqueues the two launches of a planned reverberation on `stream` (a ticket runs once); an unknown ticket or an arena
- * smaller than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.
+ * smaller than h_info[1] returns HIPFEAT_ERR_INVALID and launches nothing.  A ticket is consumed when its launch has been enqueued: after
+ * a HIPFEAT_ERR_HIP from an allocation or the table copy in front of it, it can be run again.
  */
 typedef struct hipfeat_reverb hipfeat_reverb;
 HIPFEAT_API hipfeat_status hipfeat_reverb_create(int32_t device, hipfeat_reverb** reverb);

@@ -431,24 +431,57 @@ def sinc_in_arena(arena: torch.Tensor, offsets: np.ndarray, lengths: np.ndarray,
     return offsets, lengths
 
 
-class HipSincResampler:
-    """The sinc resampler without a filter bank (``hipfeat_sinc``, include/hipfeat.h; csrc/kernel_sinc.hpp): the arithmetic of
-    ``ResampleTensor`` (lhotse/augmentation/resample.py:184-315) for ANY rate pair, every row of a launch with its own -- the weights are
-    evaluated on the device where they are not zero.  One object per device (``get_or_create_sinc``); it may be shared by threads."""
+class _ArenaHandle:
+    """What the per-device objects of the arena launches share: the library's ticketed handle ``hipfeat_<_KIND>`` on one device, created
+    here and destroyed by ``close``; ``_lock`` serialises the subclass's ``plan``."""
+
+    _KIND = ""
 
     def __init__(self, device: Union[str, torch.device, None] = None):
         self.lib = _lib.load()
         self.handle = 0
         dev = torch.device("cuda" if device is None else device)
         if dev.type != "cuda":
-            raise _lib.HipFeatError(1, f"HipSincResampler runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
+            raise _lib.HipFeatError(1, f"{type(self).__name__} runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
         if not torch.cuda.is_available():
             raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
         out = np.zeros(1, dtype=np.uint64)
-        self.lib.check("hipfeat_sinc_create", int(self.device.index), _lib.addr(out))
+        self.lib.check(f"hipfeat_{self._KIND}_create", int(self.device.index), _lib.addr(out))
         self.handle = int(out[0])
         self._lock = threading.Lock()
+
+    def close(self):
+        if self.handle:
+            try:
+                self.lib.raw(f"hipfeat_{self._KIND}_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _get_or_create(cache: dict, cls, lock, device: Union[str, torch.device, None]):
+    """The one object of ``cls`` per device index, kept in ``cache``."""
+    dev = torch.device("cuda" if device is None else device)
+    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    with lock:
+        r = cache.get(int(index))
+        if r is None:
+            r = cache[int(index)] = cls(torch.device(dev.type, index))
+        return r
+
+
+class HipSincResampler(_ArenaHandle):
+    """The sinc resampler without a filter bank (``hipfeat_sinc``, include/hipfeat.h; csrc/kernel_sinc.hpp): the arithmetic of
+    ``ResampleTensor`` (lhotse/augmentation/resample.py:184-315) for ANY rate pair, every row of a launch with its own -- the weights are
+    evaluated on the device where they are not zero.  One object per device (``get_or_create_sinc``); it may be shared by threads."""
+
+    _KIND = "sinc"  # hipfeat_sinc_create / _destroy
 
     def plan(self, in_offsets, in_lens, rates: Sequence[Tuple[int, int]], out_offsets, arena_floats: int):
         """Host only -> (ticket, output lengths, info = [ticket, arena floats needed, workgroups, largest window])."""
@@ -481,32 +514,13 @@ class HipSincResampler:
                            int(_raw_stream(self.device)))
         return w, first, int(dims[2])
 
-    def close(self):
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_sinc_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _sincs: Dict[int, HipSincResampler] = {}
 _sinc_lock = threading.Lock()  # (its own: get_or_create_resampler holds _cache_lock while a bankless HipResampleTensor asks for the device's object)
 
 
 def get_or_create_sinc(device: Union[str, torch.device, None] = None) -> HipSincResampler:
-    dev = torch.device("cuda" if device is None else device)
-    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    with _sinc_lock:
-        r = _sincs.get(int(index))
-        if r is None:
-            r = _sincs[int(index)] = HipSincResampler(torch.device(dev.type, index))
-        return r
+    return _get_or_create(_sincs, HipSincResampler, _sinc_lock, device)
 
 
 def _speed_keys(factors) -> list:
@@ -678,25 +692,13 @@ def mixed_tail_floats(track_first, src_lens, dst_offsets, max_samples=None) -> i
     return int(((mixed_num_samples(track_first, src_lens, dst_offsets, max_samples) + 3) & ~3).sum()) + 3
 
 
-class HipMixer:
+class HipMixer(_ArenaHandle):
     """The device half of ``MixedCut.load_audio`` (lhotse/cut/mixed.py:1312-1409) for a packed mini-batch: ``hipfeat_mixer``
     (include/hipfeat.h) owns the workspace of the two launches -- track energies, then gains + the scaled sum in track order.  Energies
     and gains never visit the host, so the feature launch can follow on the same stream.  One mixer per device (``get_or_create_mixer``);
     it may be shared by threads."""
 
-    def __init__(self, device: Union[str, torch.device, None] = None):
-        self.lib = _lib.load()
-        self.handle = 0
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise _lib.HipFeatError(1, f"HipMixer runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
-        if not torch.cuda.is_available():
-            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        out = np.zeros(1, dtype=np.uint64)
-        self.lib.check("hipfeat_mixer_create", int(self.device.index), _lib.addr(out))
-        self.handle = int(out[0])
-        self._lock = threading.Lock()
+    _KIND = "mixer"  # hipfeat_mixer_create / _destroy
 
     def plan(self, track_first, src_offsets, src_lens, dst_offsets, snrs=None, ref_tracks=None, max_samples=None, tail_start: int = 0):
         """Host only -> (ticket, out_offsets, out_lengths, info = [ticket, arena floats needed, energy items, mix items])."""
@@ -713,31 +715,12 @@ class HipMixer:
         with torch.cuda.device(self.device):
             self.lib.check("hipfeat_mix_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
 
-    def close(self):
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_mixer_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _mixers: Dict[int, HipMixer] = {}
 
 
 def get_or_create_mixer(device: Union[str, torch.device, None] = None) -> HipMixer:
-    dev = torch.device("cuda" if device is None else device)
-    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    with _cache_lock:
-        m = _mixers.get(int(index))
-        if m is None:
-            m = _mixers[int(index)] = HipMixer(torch.device(dev.type, index))
-        return m
+    return _get_or_create(_mixers, HipMixer, _cache_lock, device)
 
 
 def mix_in_arena(arena: torch.Tensor, track_first, src_offsets, src_lens, dst_offsets, snrs=None, ref_tracks=None, max_samples=None,
@@ -777,24 +760,12 @@ def scaled_rir(rir: np.ndarray) -> Tuple[np.ndarray, int]:
     return hs, int(np.argmax(hs))
 
 
-class HipReverb:
+class HipReverb(_ArenaHandle):
     """The device half of ``ReverbWithImpulseResponse.__call__`` (lhotse/augmentation/rir.py:78-153) for a packed mini-batch:
     ``hipfeat_reverb`` (include/hipfeat.h) owns the workspace of the two launches -- direct-form float32 convolution with float64 sums
     of squares, then the power-preserving gain.  One object per device (``get_or_create_reverb``); it may be shared by threads."""
 
-    def __init__(self, device: Union[str, torch.device, None] = None):
-        self.lib = _lib.load()
-        self.handle = 0
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise _lib.HipFeatError(1, f"HipReverb runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
-        if not torch.cuda.is_available():
-            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        out = np.zeros(1, dtype=np.uint64)
-        self.lib.check("hipfeat_reverb_create", int(self.device.index), _lib.addr(out))
-        self.handle = int(out[0])
-        self._lock = threading.Lock()
+    _KIND = "reverb"  # hipfeat_reverb_create / _destroy
 
     def plan(self, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0):
         """Host only -> (ticket, out_offsets, info = [ticket, arena floats needed, convolution work items, partial sums])."""
@@ -816,31 +787,12 @@ class HipReverb:
         with torch.cuda.device(self.device):
             self.lib.check("hipfeat_reverb_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
 
-    def close(self):
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_reverb_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _reverbs: Dict[int, HipReverb] = {}
 
 
 def get_or_create_reverb(device: Union[str, torch.device, None] = None) -> HipReverb:
-    dev = torch.device("cuda" if device is None else device)
-    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    with _cache_lock:
-        r = _reverbs.get(int(index))
-        if r is None:
-            r = _reverbs[int(index)] = HipReverb(torch.device(dev.type, index))
-        return r
+    return _get_or_create(_reverbs, HipReverb, _cache_lock, device)
 
 
 def reverb_in_arena(arena: torch.Tensor, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0,
@@ -988,24 +940,12 @@ def level_op_tables(programs) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.nd
     return _lib.i64(first), np.asarray(kind, dtype=np.int32), np.asarray(value, dtype=np.float32), np.asarray(flags, dtype=np.int32)
 
 
-class HipLevel:
+class HipLevel(_ArenaHandle):
     """The device half of ``Volume.__call__`` (lhotse/augmentation/torchaudio.py:395-406) and ``Clipping.__call__``
     (lhotse/augmentation/clipping.py:28-61) for a packed mini-batch: ``hipfeat_level`` (include/hipfeat.h) owns the workspace of the two
     launches -- max |x| per item, then the ops.  One object per device (``get_or_create_level``); it may be shared by threads."""
 
-    def __init__(self, device: Union[str, torch.device, None] = None):
-        self.lib = _lib.load()
-        self.handle = 0
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise _lib.HipFeatError(1, f"HipLevel runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
-        if not torch.cuda.is_available():
-            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        out = np.zeros(1, dtype=np.uint64)
-        self.lib.check("hipfeat_level_create", int(self.device.index), _lib.addr(out))
-        self.handle = int(out[0])
-        self._lock = threading.Lock()
+    _KIND = "level"  # hipfeat_level_create / _destroy
 
     def plan(self, src_offsets, src_lens, programs, dst_offsets=None):
         """Host only -> (ticket, info = [ticket, arena floats needed, peak work items, apply work items])."""
@@ -1026,31 +966,12 @@ class HipLevel:
         with torch.cuda.device(self.device):
             self.lib.check("hipfeat_level_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), int(_raw_stream(arena.device) if stream is None else stream))
 
-    def close(self):
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_level_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _levels: Dict[int, HipLevel] = {}
 
 
 def get_or_create_level(device: Union[str, torch.device, None] = None) -> HipLevel:
-    dev = torch.device("cuda" if device is None else device)
-    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    with _cache_lock:
-        r = _levels.get(int(index))
-        if r is None:
-            r = _levels[int(index)] = HipLevel(torch.device(dev.type, index))
-        return r
+    return _get_or_create(_levels, HipLevel, _cache_lock, device)
 
 
 def level_in_arena(arena: torch.Tensor, src_offsets, src_lens, programs, dst_offsets=None, level: Optional[HipLevel] = None) -> np.ndarray:
@@ -1166,24 +1087,12 @@ def collate_layout(arena_floats: int, offsets, lengths, row_len: Optional[int] =
     return so, sl, do, row_len
 
 
-class HipCollator:
+class HipCollator(_ArenaHandle):
     """The device half of ``collate_audio`` (lhotse/dataset/collation.py:148-260) for a packed mini-batch: ``hipfeat_collate``
     (include/hipfeat.h) owns the staged row table of the one launch.  One object per device (``get_or_create_collator``); it may be
     shared by threads."""
 
-    def __init__(self, device: Union[str, torch.device, None] = None):
-        self.lib = _lib.load()
-        self.handle = 0
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise _lib.HipFeatError(1, f"HipCollator runs on an AMD GPU ('cuda[:i]' device), got device={dev}")
-        if not torch.cuda.is_available():
-            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        out = np.zeros(1, dtype=np.uint64)
-        self.lib.check("hipfeat_collate_create", int(self.device.index), _lib.addr(out))
-        self.handle = int(out[0])
-        self._lock = threading.Lock()
+    _KIND = "collate"  # hipfeat_collate_create / _destroy
 
     def plan(self, src_offsets, src_lens, dst_offsets, row_len: int, dtype: torch.dtype = torch.float32):
         """Host only -> (ticket, info = [ticket, arena floats needed, elements of out, work items])."""
@@ -1206,31 +1115,12 @@ class HipCollator:
             self.lib.check("hipfeat_collate_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), out.data_ptr(), out.numel(),
                            int(_raw_stream(arena.device) if stream is None else stream))
 
-    def close(self):
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_collate_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _collators: Dict[int, HipCollator] = {}
 
 
 def get_or_create_collator(device: Union[str, torch.device, None] = None) -> HipCollator:
-    dev = torch.device("cuda" if device is None else device)
-    index = dev.index if dev.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    with _cache_lock:
-        r = _collators.get(int(index))
-        if r is None:
-            r = _collators[int(index)] = HipCollator(torch.device(dev.type, index))
-        return r
+    return _get_or_create(_collators, HipCollator, _cache_lock, device)
 
 
 def collate_in_arena(arena: torch.Tensor, offsets, lengths, row_len: Optional[int] = None, dst_offsets=None, dtype: torch.dtype = torch.float32,

@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include "ticket_slots.hpp"
+
 namespace hipfeat {
 
 constexpr int kCoTile = 4096;  // output elements per work item (256 lanes x 16-byte stores: 4 rounds of float32, 2 of the 2-byte types)
@@ -81,34 +83,9 @@ inline CoPlan build_collate_plan(int64_t num_rows, const int64_t* h_src_offset, 
   return p;
 }
 
-// The tickets of hipfeat_collate: up to kCoSlots plans may be outstanding; ticket t lives in slot t % kCoSlots, and a plan is refused
-// while the slot its ticket would take still holds one that has not run.
+// The tickets of hipfeat_collate are the ring every ticketed handle shares (ticket_slots.hpp); its names from before the ring was shared
+using CoSlots = TicketRing;
 constexpr int kCoSlots = 16;
-
-struct CoSlots {
-  int64_t ticket[kCoSlots];
-  bool planned[kCoSlots];
-  int64_t next_ticket = 0;
-  CoSlots() {
-    for (int i = 0; i < kCoSlots; ++i) ticket[i] = -1, planned[i] = false;
-  }
-  bool full() const { return planned[next_ticket % kCoSlots]; }
-  int64_t take() {  // -> the new ticket, or -1 when kCoSlots plans are outstanding
-    if (full()) return -1;
-    const int64_t t = next_ticket++;
-    ticket[t % kCoSlots] = t;
-    planned[t % kCoSlots] = true;
-    return t;
-  }
-  int slot_of(int64_t t) const {  // -> the slot of a planned ticket, or -1
-    const int i = (int)(((t % kCoSlots) + kCoSlots) % kCoSlots);
-    return ticket[i] == t && planned[i] ? i : -1;
-  }
-  bool release(int64_t t) {
-    const int i = slot_of(t);
-    if (i >= 0) planned[i] = false;
-    return i >= 0;
-  }
-};
+static_assert(kCoSlots == kTicketSlots, "one ring");
 
 }  // namespace hipfeat

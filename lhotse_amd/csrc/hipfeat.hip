@@ -35,6 +35,7 @@
 #include "kernel_whisper2.hpp"
 #include "kernel_whisper3.hpp"
 #include "layout_rounds.hpp"
+#include "ticket_slots.hpp"
 #include "kernel_fft256.hpp"
 #include "kernel_fft256c.hpp"
 #include "kernel_wave.hpp"
@@ -1798,12 +1799,143 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resample(const hipfeat_resampler* 
 }
 
 // --------------------------------------------------------------------------------------
+// What the arena handles share ("Ticketed handles"): the staging slot, the handle with its ticket ring (ticket_slots.hpp),
+// the two ends of a run, and the grid and table-route rules of the launches that walk a flat item list
+// --------------------------------------------------------------------------------------
+// A pinned host buffer and a device buffer of one capacity, and the event that says when the launches that used them last are done.
+struct StagedSlot : StagingSlot {
+  hipError_t wait() {  // for the launches that used this slot's memory last time
+    if (!busy) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(ev);
+    if (e == hipSuccess) busy = false;
+    return e;
+  }
+  hipError_t reserve(size_t bytes) {  // the event exists and both buffers hold `bytes`; their old contents are not kept
+    hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess || cap >= bytes) return e;
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    h = d = nullptr;
+    cap = 0;
+    const size_t grown = std::max<size_t>(bytes * 2, 1 << 14);
+    if ((e = hipHostMalloc(&h, grown, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipMalloc(&d, grown)) != hipSuccess) return e;
+    cap = grown;
+    return hipSuccess;
+  }
+  hipError_t record(hipStream_t st) {  // behind the launches; memory its event cannot guard is waited for here instead
+    const hipError_t e = hipEventRecord(ev, st);
+    busy = (e == hipSuccess);
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    return e;
+  }
+  void free_all() {
+    if (busy && ev) (void)hipEventSynchronize(ev);
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    if (ev) (void)hipEventDestroy(ev);
+  }
+};
+
+// Plan hands out a ticket and keeps the validated tables in plans[ticket % kTicketSlots]; run stages them through the slot of the same
+// index.  A ticket is consumed when its launch has been enqueued (finish_run): an argument refusal or a failed allocation leaves it planned.
+template <typename Plan>
+struct TicketedHandle {
+  int device = 0;
+  bool allow_inline = true;
+  std::mutex mu;
+  TicketRing tickets;
+  Plan plans[kTicketSlots];
+  StagedSlot slots[kTicketSlots];
+};
+struct hipfeat_mixer : TicketedHandle<MixPlan> {};
+struct hipfeat_reverb : TicketedHandle<RvPlan> {};
+struct hipfeat_level : TicketedHandle<LvPlan> {};
+struct hipfeat_collate : TicketedHandle<CoPlan> {};
+struct hipfeat_sinc : TicketedHandle<SincPlan> {};
+
+template <typename H>
+static hipfeat_status handle_create(int32_t device, H** out, const char* what) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "%s pointer is NULL", what);
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  H* h = new (std::nothrow) H();
+  if (!h) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  h->device = device;
+  h->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
+  *out = h;
+  return HIPFEAT_OK;
+}
+
+template <typename H>
+static hipfeat_status handle_destroy(H* h) {
+  if (!h) return HIPFEAT_OK;
+  DeviceGuard g(h->device);
+  for (auto& s : h->slots) s.free_all();
+  delete h;
+  return HIPFEAT_OK;
+}
+
+// under the handle's mutex: the ticket of a new plan (never drop a live plan: its ticket would fail at run)
+static hipfeat_status take_ticket(TicketRing& tickets, const char* what_plural, int64_t* ticket) {
+  *ticket = tickets.take();
+  if (*ticket >= 0) return HIPFEAT_OK;
+  return fail(HIPFEAT_ERR_INVALID, "%d planned %s are outstanding: run ticket %lld first", kTicketSlots, what_plural,
+              (long long)tickets.ticket[tickets.next_ticket % kTicketSlots]);
+}
+
+// under the handle's mutex: the slot of a planned ticket, or -1 with the refusal written
+static int find_ticket(const TicketRing& tickets, int64_t ticket, const char* what) {
+  const int slot = tickets.slot_of(ticket);
+  if (slot < 0) (void)fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned %s (at most %d plans may be outstanding)", (long long)ticket, what, kTicketSlots);
+  return slot;
+}
+
+// the end of a run whose launches have been issued (e1: hipGetLastError behind them).  Enqueued, or refused by the runtime at launch:
+// the ticket has run.
+constexpr const char* kWaitedLaunch = "the launch was enqueued and has been waited for";
+constexpr const char* kWaitedLaunches = "the launches were enqueued and have been waited for";
+static hipfeat_status finish_run(TicketRing& tickets, int64_t ticket, StagedSlot& s, hipStream_t st, hipError_t e1, const char* kind, const char* waited) {
+  tickets.release(ticket);
+  const hipError_t e2 = s.record(st);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s launch failed: %s", kind, hipGetErrorName(e1));
+  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s: hipEventRecord failed: %s (%s)", kind, hipGetErrorName(e2), waited);
+  return HIPFEAT_OK;
+}
+
+// a few workgroups per CU take the items round-robin; the grid is the smallest one that gives every workgroup the same number of
+// items: ceil(items / ceil(items / slots))
+static unsigned items_grid(int64_t items, int64_t slots = 1792) {
+  const int64_t per_wg = std::max<int64_t>(1, (items + slots - 1) / slots);
+  return (unsigned)std::max<int64_t>(1, (items + per_wg - 1) / per_wg);
+}
+
+// where a launch finds its tables: in its kernel arguments, or staged -- and then searched in LDS (dynamic LDS = bytes) or where they are
+struct TableRoute {
+  bool inl;
+  size_t dyn;
+};
+static TableRoute table_route(bool allow_inline, size_t bytes) {
+  return {allow_inline && bytes <= (size_t)kMbInlineBytes, bytes <= (size_t)kMbLdsTableBytes ? bytes : 0};
+}
+
+// the tables of `args` to where its route reads them: args.blob, or through the slot's pinned buffer to the front of its device buffer
+template <typename Args, typename Fill>
+static hipError_t place_tables(Args& args, const TableRoute& r, StagedSlot& s, size_t bytes, hipStream_t st, Fill fill) {
+  args.h.tables = r.inl ? nullptr : static_cast<const unsigned char*>(s.d);
+  fill(r.inl ? args.blob : static_cast<unsigned char*>(s.h));
+  return r.inl ? hipSuccess : hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st);
+}
+
+// --------------------------------------------------------------------------------------
 // on-the-fly mini-batch: mixed-factor speed perturbation + collated extraction in two launches (kernel_minibatch.hpp)
 // --------------------------------------------------------------------------------------
 constexpr int kMbSlots = 16;
 constexpr int kMbMaxResamplers = 8;
 
-struct MbSlot {
+struct MbSlot : StagedSlot {  // device: the feature launch's CutDesc table and map, then (staged path) the blob
   int64_t ticket = -1;
   bool planned = false;
   const hipfeat_plan* plan = nullptr;
@@ -1815,11 +1947,6 @@ struct MbSlot {
   int64_t total_rows = 0;
   std::vector<int32_t> fill_first;  // prefix sum of the cuts' padding items (16 KB each)
   int64_t res_blocks = 0, arena_need = 0, max_frames = 0;  // res_blocks: resampler items (256 hops each) of the whole mini-batch
-  void* h = nullptr;  // pinned staging (tables that do not fit the kernel arguments)
-  void* d = nullptr;  // device tables: CutDesc[batch], then (staged path) ResCut[num_res]
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
 };
 
 struct hipfeat_speed_bank {
@@ -1883,12 +2010,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_speed_bank_destroy(hipfeat_speed_b
     return HIPFEAT_OK;
   }
   DeviceGuard g(b->device);
-  for (auto& s : b->slots) {
-    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
+  for (auto& s : b->slots) s.free_all();
   delete b;
   return HIPFEAT_OK;
 }
@@ -2033,29 +2155,17 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_minibatch_run(hipfeat_speed_bank* 
   s.fill_first[(size_t)batch] = (int32_t)fill_items;
   const size_t res_bytes = s.res.size() * sizeof(ResCut), cut_bytes = (size_t)batch * sizeof(CutDesc), fill_bytes = ((size_t)batch + 1) * sizeof(int32_t),
                row_bytes = (size_t)batch * sizeof(int32_t), bytes = (res_bytes + cut_bytes + fill_bytes + row_bytes + 15) & ~(size_t)15;
-  const bool inl = bank->allow_inline && bytes <= (size_t)kMbInlineBytes;
-  if (s.busy) {  // the launches that used this slot's device table last time
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  const TableRoute route = table_route(bank->allow_inline, bytes);
+  const bool inl = route.inl;
   const size_t map_bytes = ((size_t)s.lay.total_blocks * sizeof(int32_t) + 15) & ~(size_t)15;  // the feature launch's workgroup -> cut map
   const size_t dev_bytes = cut_bytes + map_bytes + bytes;  // the feature launch's CutDesc table and map, then (staged path) the blob
-  if (s.cap < dev_bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
+  HIP_TRY(s.wait());  // the launches that used this slot's device table last time
+  HIP_TRY(s.reserve(dev_bytes));
   s.lay.d_cuts = static_cast<CutDesc*>(s.d);
   // a few workgroups per CU take the items round-robin; the grid is the smallest one that gives every workgroup the same number of items
   static const int64_t mb_slots = exp_env("HIPFEAT_MB_SLOTS") ? std::max(1, atoi(exp_env("HIPFEAT_MB_SLOTS"))) : 1792;
-  const int64_t items = fill_items + s.res_blocks, per_wg = std::max<int64_t>(1, (items + mb_slots - 1) / mb_slots);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, (items + per_wg - 1) / per_wg);
+  const int64_t items = fill_items + s.res_blocks;
+  const unsigned grid = items_grid(items, mb_slots);
   MbInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
   MbHeader& h = args.h;
   h.arena = d_arena;
@@ -2107,150 +2217,34 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_minibatch_run(hipfeat_speed_bank* 
     fill_blob(hb + cut_bytes + map_bytes);
     HIP_TRY(hipMemcpyAsync(s.d, s.h, dev_bytes, hipMemcpyHostToDevice, st));
     h.tables = static_cast<const unsigned char*>(s.d) + cut_bytes + map_bytes;
-    hipLaunchKernelGGL(minibatch_prep_kernel, dim3(grid), dim3(256), bytes <= (size_t)kMbLdsTableBytes ? bytes : 0, st, h);
+    hipLaunchKernelGGL(minibatch_prep_kernel, dim3(grid), dim3(256), route.dyn, st, h);
     e1 = hipGetLastError();
   }
   hipfeat_status rc = HIPFEAT_OK;
   if (e1 != hipSuccess) rc = fail(HIPFEAT_ERR_HIP, "mini-batch prep launch failed: %s", hipGetErrorName(e1));
   if (rc == HIPFEAT_OK && s.lay.total_blocks > 0 && dbg_skip != 1) rc = launch(plan, &s.lay, d_arena, d_out, st);
-  hipError_t e2 = hipEventRecord(s.ev, st);
-  s.busy = (e2 == hipSuccess);
+  (void)s.record(st);
   return rc;
 }
 
 // --------------------------------------------------------------------------------------
-// MixedCut tracks mixed on the device: energies, gains and the scaled sum in two launches (kernel_mix.hpp)
+// MixedCut tracks mixed on the device: energies, gains and the scaled sum in two launches (kernel_mix.hpp; the tables: mix_tables.hpp)
 // --------------------------------------------------------------------------------------
-constexpr int kMixSlots = 16;
-
-struct MixSlot {
-  int64_t ticket = -1;
-  bool planned = false;
-  std::vector<MixCut> cuts;
-  std::vector<MixTrack> tracks;
-  int64_t energy_items = 0, mix_items = 0, arena_need = 0;
-  void* h = nullptr;  // pinned staging (tables that do not fit the kernel arguments)
-  void* d = nullptr;  // device: the staged tables, then the partial sums of squares
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-};
-
-struct hipfeat_mixer {
-  int device = 0;
-  bool allow_inline = true;
-  std::mutex mu;
-  MixSlot slots[kMixSlots];
-  int64_t next_ticket = 0;
-};
-
-extern "C" HIPFEAT_API hipfeat_status hipfeat_mixer_create(int32_t device, hipfeat_mixer** out) {
-  if (!out) return fail(HIPFEAT_ERR_INVALID, "mixer pointer is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
-  hipfeat_mixer* m = new (std::nothrow) hipfeat_mixer();
-  if (!m) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  m->device = device;
-  m->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
-  *out = m;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_API hipfeat_status hipfeat_mixer_destroy(hipfeat_mixer* m) {
-  if (!m) return HIPFEAT_OK;
-  DeviceGuard g(m->device);
-  for (auto& s : m->slots) {
-    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  delete m;
-  return HIPFEAT_OK;
-}
+extern "C" HIPFEAT_API hipfeat_status hipfeat_mixer_create(int32_t device, hipfeat_mixer** out) { return handle_create(device, out, "mixer"); }
+extern "C" HIPFEAT_API hipfeat_status hipfeat_mixer_destroy(hipfeat_mixer* m) { return handle_destroy(m); }
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_plan(hipfeat_mixer* mixer, int64_t num_cuts, const int64_t* h_track_first, const int64_t* h_src_offset,
                                                        const int64_t* h_src_len, const int64_t* h_dst_offset, const double* h_snr_db,
                                                        const int32_t* h_ref_track, const int64_t* h_max_samples, int64_t tail_start,
                                                        int64_t* h_out_offsets, int64_t* h_out_num_samples, int64_t* h_info) {
-  if (!mixer || !h_track_first || !h_src_offset || !h_src_len || !h_dst_offset || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  if (num_cuts <= 0 || num_cuts > 65535) return fail(HIPFEAT_ERR_INVALID, "bad batch arguments (1 ... 65535 cuts)");
-  if (tail_start < 0) return fail(HIPFEAT_ERR_INVALID, "tail_start %lld is negative", (long long)tail_start);
-  if (h_track_first[0] != 0) return fail(HIPFEAT_ERR_INVALID, "h_track_first[0] must be 0");
-  constexpr int64_t kMaxLen = INT32_MAX / 2;
+  if (!mixer || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  // (validated into a local first: a refused table leaves the outstanding plans as they were)
+  MixPlan p = build_mix_plan(num_cuts, h_track_first, h_src_offset, h_src_len, h_dst_offset, h_snr_db, h_ref_track, h_max_samples, tail_start);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
   std::lock_guard<std::mutex> lk(mixer->mu);
-  // (validated into locals first: a refused table leaves the outstanding plans as they were)
-  std::vector<MixCut> cuts((size_t)num_cuts);
-  std::vector<MixTrack> tracks;
-  int64_t tail = (tail_start + 3) & ~(int64_t)3, parts = 0, items = 0;
-  for (int64_t c = 0; c < num_cuts; ++c) {
-    const int64_t t0 = h_track_first[c], t1 = h_track_first[c + 1], nt = t1 - t0;
-    if (nt < 1 || t0 > INT32_MAX / 4) return fail(HIPFEAT_ERR_INVALID, "cut %lld: tracks [%lld, %lld): every cut has at least one track", (long long)c, (long long)t0, (long long)t1);
-    if (nt > kMixMaxTracks) return fail(HIPFEAT_ERR_UNSUPPORTED, "cut %lld has %lld tracks, the mix launch serves up to %d per cut", (long long)c, (long long)nt, kMixMaxTracks);
-    const int64_t ref = h_ref_track ? h_ref_track[c] : -1;
-    if (ref < -1 || ref >= nt) return fail(HIPFEAT_ERR_INVALID, "cut %lld: reference track %lld of %lld", (long long)c, (long long)ref, (long long)nt);
-    if (ref >= 0 && h_src_offset[t0 + ref] < 0) return fail(HIPFEAT_ERR_INVALID, "cut %lld: reference track %lld is a padding track", (long long)c, (long long)ref);
-    int64_t total = 0;
-    bool any_snr = false;
-    for (int64_t t = t0; t < t1; ++t) {
-      const int64_t so = h_src_offset[t], n = h_src_len[t], off = h_dst_offset[t];
-      const bool padding = so == -1;
-      if (so < -1 || off < 0) return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld: negative offset (source %lld, in the cut %lld)", (long long)c, (long long)(t - t0), (long long)so, (long long)off);
-      if (n < (padding ? 0 : 1) || n > kMaxLen || off + n > kMaxLen)
-        return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld: %lld samples at offset %lld out of range", (long long)c, (long long)(t - t0), (long long)n, (long long)off);
-      if (!padding && so + n > tail_start)  // the mixed cuts are written from tail_start on: output and source ranges would overlap
-        return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld (offset %lld, %lld samples) reaches into the arena's tail (tail_start %lld), where the mixed cuts are written",
-                    (long long)c, (long long)(t - t0), (long long)so, (long long)n, (long long)tail_start);
-      const double snr = h_snr_db ? h_snr_db[t] : NAN;
-      // no SNR, no reference, a padding track, or the first track being the reference itself (mixed.py:1346-1350): gain 1
-      const bool scaled = !std::isnan(snr) && ref >= 0 && !padding && !(t == t0 && ref == 0);
-      MixTrack tr{};
-      tr.src_off = so;
-      tr.src_len = (int32_t)n;
-      tr.dst_off = (int32_t)off;
-      tr.part_first = 0;
-      tr.part_count = scaled ? 1 : 0;  // (flag; counted below)
-      tr.ratio = scaled ? std::pow(10.0, -snr / 10.0) : -1.0;
-      if (scaled && !(tr.ratio >= 0.0 && std::isfinite(tr.ratio))) return fail(HIPFEAT_ERR_INVALID, "cut %lld, track %lld: SNR %g dB out of range", (long long)c, (long long)(t - t0), snr);
-      any_snr |= scaled;
-      tracks.push_back(tr);
-      total = std::max(total, off + n);
-    }
-    if (any_snr) tracks[(size_t)(t0 + ref)].part_count = 1;
-    for (int64_t t = t0; t < t1; ++t) {
-      MixTrack& tr = tracks[(size_t)t];
-      tr.part_first = (int32_t)parts;
-      if (tr.part_count) tr.part_count = (tr.src_len + kMixEnergyBlock - 1) / kMixEnergyBlock;
-      parts += tr.part_count;
-    }
-    int64_t n_out = total;
-    if (h_max_samples && h_max_samples[c] >= 0) n_out = std::min(n_out, h_max_samples[c]);  // (mixed.py:1381-1385: a sample or two to truncate)
-    if (n_out < 1) return fail(HIPFEAT_ERR_INVALID, "cut %lld: the mix is empty", (long long)c);
-    MixCut& cd = cuts[(size_t)c];
-    cd.out_off = tail;
-    cd.out_len = (int32_t)n_out;
-    cd.item_first = (int32_t)items;
-    cd.track_first = (int32_t)t0;
-    cd.track_count = (int32_t)nt;
-    cd.ref_track = ref >= 0 ? (int32_t)(t0 + ref) : -1;
-    cd.pad = 0;
-    items += (n_out + kMixBlock - 1) / kMixBlock;
-    tail += (n_out + 3) & ~(int64_t)3;
-    if (items > INT32_MAX - (1 << 24) || parts > INT32_MAX - (1 << 24)) return fail(HIPFEAT_ERR_INVALID, "batch too large for one launch");
-  }
-  if (mixer->slots[mixer->next_ticket % kMixSlots].planned)  // (never drop a live plan: its ticket would fail at run)
-    return fail(HIPFEAT_ERR_INVALID, "%d planned mixes are outstanding: run ticket %lld first", kMixSlots, (long long)mixer->slots[mixer->next_ticket % kMixSlots].ticket);
-  const int64_t ticket = mixer->next_ticket++;
-  MixSlot& s = mixer->slots[ticket % kMixSlots];
-  s.ticket = ticket;
-  s.cuts.swap(cuts);
-  s.tracks.swap(tracks);
-  s.energy_items = parts;
-  s.mix_items = items;
-  s.arena_need = tail;
-  s.planned = true;
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(mixer->tickets, "mixes", &ticket)) return st;
+  const MixPlan& s = mixer->plans[ticket % kTicketSlots] = std::move(p);
   for (int64_t c = 0; c < num_cuts; ++c) {
     if (h_out_offsets) h_out_offsets[c] = s.cuts[(size_t)c].out_off;
     if (h_out_num_samples) h_out_num_samples[c] = s.cuts[(size_t)c].out_len;
@@ -2265,170 +2259,63 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_plan(hipfeat_mixer* mixer, int
 extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
   if (!mixer || !d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   std::lock_guard<std::mutex> lk(mixer->mu);
-  MixSlot& s = mixer->slots[((ticket % kMixSlots) + kMixSlots) % kMixSlots];
-  if (s.ticket != ticket || !s.planned)
-    return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned mix (at most %d plans may be outstanding)", (long long)ticket, kMixSlots);
-  if (arena_floats < s.arena_need)
-    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the mixed cuts need %lld", (long long)arena_floats, (long long)s.arena_need);
+  const int slot = find_ticket(mixer->tickets, ticket, "mix");
+  if (slot < 0) return HIPFEAT_ERR_INVALID;
+  const MixPlan& p = mixer->plans[slot];
+  StagedSlot& s = mixer->slots[slot];  // device: the staged tables, then the partial sums of squares
+  if (arena_floats < p.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the mixed cuts need %lld", (long long)arena_floats, (long long)p.arena_need);
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
-  s.planned = false;
   DeviceGuard g(mixer->device);
   hipStream_t st = (hipStream_t)stream;
-  const size_t cut_bytes = s.cuts.size() * sizeof(MixCut), trk_bytes = s.tracks.size() * sizeof(MixTrack), bytes = cut_bytes + trk_bytes;  // (multiples of 32)
-  const size_t part_bytes = (size_t)std::max<int64_t>(s.energy_items, 1) * sizeof(double);
-  const bool inl = mixer->allow_inline && bytes <= (size_t)kMbInlineBytes;
-  if (s.busy) {  // the launches that used this slot's device memory last time
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  const size_t dev_bytes = bytes + part_bytes;
-  if (s.cap < dev_bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
+  const size_t cut_bytes = p.cuts.size() * sizeof(MixCut), trk_bytes = p.tracks.size() * sizeof(MixTrack), bytes = cut_bytes + trk_bytes;  // (multiples of 32)
+  const size_t part_bytes = (size_t)std::max<int64_t>(p.energy_items, 1) * sizeof(double);
+  const TableRoute r = table_route(mixer->allow_inline, bytes);
+  HIP_TRY(s.wait());
+  HIP_TRY(s.reserve(bytes + part_bytes));
   MixInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
   MixHeader& h = args.h;
   h.arena = d_arena;
   h.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(s.d) + bytes);
-  h.tables = nullptr;
-  h.num_cuts = (int32_t)s.cuts.size();
-  h.num_tracks = (int32_t)s.tracks.size();
-  h.energy_items = (int32_t)s.energy_items;
-  h.mix_items = (int32_t)s.mix_items;
+  h.num_cuts = (int32_t)p.cuts.size();
+  h.num_tracks = (int32_t)p.tracks.size();
+  h.energy_items = (int32_t)p.energy_items;
+  h.mix_items = (int32_t)p.mix_items;
   h.table_bytes = (int32_t)bytes;
   h.pad = 0;
-  auto fill_blob = [&](unsigned char* dst) {
-    std::memcpy(dst, s.cuts.data(), cut_bytes);
-    std::memcpy(dst + cut_bytes, s.tracks.data(), trk_bytes);
-  };
-  // a few workgroups per CU take the items round-robin (as hipfeat_minibatch_run)
-  auto grid_of = [](int64_t items) {
-    const int64_t per_wg = std::max<int64_t>(1, (items + 1791) / 1792);
-    return (unsigned)std::max<int64_t>(1, (items + per_wg - 1) / per_wg);
-  };
-  const size_t dyn = bytes <= (size_t)kMbLdsTableBytes ? bytes : 0;
-  hipError_t e1 = hipSuccess;
-  if (inl) {
-    fill_blob(args.blob);
-    if (s.energy_items > 0) hipLaunchKernelGGL(mix_energy_inline_kernel, dim3(grid_of(s.energy_items)), dim3(256), 0, st, args);
-    hipLaunchKernelGGL(mix_inline_kernel, dim3(grid_of(s.mix_items)), dim3(256), 0, st, args);
-    e1 = hipGetLastError();
+  HIP_TRY(place_tables(args, r, s, bytes, st, [&](unsigned char* dst) {
+    std::memcpy(dst, p.cuts.data(), cut_bytes);
+    std::memcpy(dst + cut_bytes, p.tracks.data(), trk_bytes);
+  }));
+  const dim3 energy_grid(items_grid(p.energy_items)), mix_grid(items_grid(p.mix_items)), wg(256);
+  if (r.inl) {
+    if (p.energy_items > 0) hipLaunchKernelGGL(mix_energy_inline_kernel, energy_grid, wg, 0, st, args);
+    hipLaunchKernelGGL(mix_inline_kernel, mix_grid, wg, 0, st, args);
   } else {
-    fill_blob(static_cast<unsigned char*>(s.h));
-    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
-    h.tables = static_cast<const unsigned char*>(s.d);
-    if (s.energy_items > 0) hipLaunchKernelGGL(mix_energy_kernel, dim3(grid_of(s.energy_items)), dim3(256), dyn, st, h);
-    hipLaunchKernelGGL(mix_kernel, dim3(grid_of(s.mix_items)), dim3(256), dyn, st, h);
-    e1 = hipGetLastError();
+    if (p.energy_items > 0) hipLaunchKernelGGL(mix_energy_kernel, energy_grid, wg, r.dyn, st, h);
+    hipLaunchKernelGGL(mix_kernel, mix_grid, wg, r.dyn, st, h);
   }
-  hipError_t e2 = hipEventRecord(s.ev, st);
-  s.busy = (e2 == hipSuccess);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "mix launch failed: %s", hipGetErrorName(e1));
-  return HIPFEAT_OK;
+  return finish_run(mixer->tickets, ticket, s, st, hipGetLastError(), "mix", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
-// Reverberation with a recorded impulse response on the device: convolution + power normalisation in two launches (kernel_reverb.hpp)
+// Reverberation with a recorded impulse response on the device: convolution + power normalisation in two launches (kernel_reverb.hpp;
+// the table: reverb_tables.hpp)
 // --------------------------------------------------------------------------------------
-constexpr int kRvSlots = 16;
-
-struct RvSlot {
-  int64_t ticket = -1;
-  bool planned = false;
-  std::vector<RvItem> items;
-  int64_t work_items = 0, arena_need = 0;
-  void* h = nullptr;  // pinned staging (a table that does not fit the kernel arguments)
-  void* d = nullptr;  // device: the staged table, then the partial sums of squares
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-};
-
-struct hipfeat_reverb {
-  int device = 0;
-  bool allow_inline = true;
-  std::mutex mu;
-  RvSlot slots[kRvSlots];
-  int64_t next_ticket = 0;
-};
-
-extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_create(int32_t device, hipfeat_reverb** out) {
-  if (!out) return fail(HIPFEAT_ERR_INVALID, "reverb pointer is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
-  hipfeat_reverb* r = new (std::nothrow) hipfeat_reverb();
-  if (!r) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  r->device = device;
-  r->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
-  *out = r;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_destroy(hipfeat_reverb* r) {
-  if (!r) return HIPFEAT_OK;
-  DeviceGuard g(r->device);
-  for (auto& s : r->slots) {
-    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  delete r;
-  return HIPFEAT_OK;
-}
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_create(int32_t device, hipfeat_reverb** out) { return handle_create(device, out, "reverb"); }
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_destroy(hipfeat_reverb* r) { return handle_destroy(r); }
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* rv, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
                                                           const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
                                                           const int32_t* h_normalize, int64_t tail_start, int64_t* h_out_offsets, int64_t* h_info) {
-  if (!rv || !h_src_offset || !h_src_len || !h_rir_offset || !h_rir_len || !h_shift || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  if (num_items <= 0 || num_items > 65535) return fail(HIPFEAT_ERR_INVALID, "bad batch arguments (1 ... 65535 items)");
-  if (tail_start < 0) return fail(HIPFEAT_ERR_INVALID, "tail_start %lld is negative", (long long)tail_start);
-  constexpr int64_t kMaxLen = INT32_MAX / 2;
-  std::lock_guard<std::mutex> lk(rv->mu);
+  if (!rv || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   // (validated into a local first: a refused table leaves the outstanding plans as they were)
-  std::vector<RvItem> items((size_t)num_items);
-  int64_t tail = (tail_start + 3) & ~(int64_t)3, work = 0;
-  for (int64_t i = 0; i < num_items; ++i) {
-    const int64_t so = h_src_offset[i], n = h_src_len[i], ro = h_rir_offset[i], taps = h_rir_len[i], shift = h_shift[i];
-    if (so < 0 || ro < 0) return fail(HIPFEAT_ERR_INVALID, "item %lld: negative offset (source %lld, impulse response %lld)", (long long)i, (long long)so, (long long)ro);
-    if (n < 1 || n > kMaxLen || taps < 1 || taps > kMaxLen)
-      return fail(HIPFEAT_ERR_INVALID, "item %lld: %lld samples, %lld taps: both must be 1 ... %lld", (long long)i, (long long)n, (long long)taps, (long long)kMaxLen);
-    if (shift < 0 || shift >= taps) return fail(HIPFEAT_ERR_INVALID, "item %lld: shift %lld outside [0, %lld)", (long long)i, (long long)shift, (long long)taps);
-    if (so + n > tail_start || ro + taps > tail_start)  // the outputs are written from tail_start on: output and source ranges would overlap
-      return fail(HIPFEAT_ERR_INVALID, "item %lld (source %lld + %lld, impulse response %lld + %lld) reaches into the arena's tail (tail_start %lld), where the outputs are written",
-                  (long long)i, (long long)so, (long long)n, (long long)ro, (long long)taps, (long long)tail_start);
-    RvItem& it = items[(size_t)i];
-    it.src_off = so;
-    it.rir_off = ro;
-    it.out_off = tail;
-    it.n = (int32_t)n;
-    it.taps = (int32_t)taps;
-    it.shift = (int32_t)shift;
-    it.item_first = (int32_t)work;
-    it.normalize = (h_normalize && h_normalize[i]) ? 1 : 0;
-    it.pad = 0;
-    work += (n + kRvBlock - 1) / kRvBlock;
-    tail += (n + 3) & ~(int64_t)3;
-    if (work > INT32_MAX - (1 << 24)) return fail(HIPFEAT_ERR_INVALID, "batch too large for one launch");
-  }
-  if (rv->slots[rv->next_ticket % kRvSlots].planned)  // (never drop a live plan: its ticket would fail at run)
-    return fail(HIPFEAT_ERR_INVALID, "%d planned reverberations are outstanding: run ticket %lld first", kRvSlots, (long long)rv->slots[rv->next_ticket % kRvSlots].ticket);
-  const int64_t ticket = rv->next_ticket++;
-  RvSlot& s = rv->slots[ticket % kRvSlots];
-  s.ticket = ticket;
-  s.items.swap(items);
-  s.work_items = work;
-  s.arena_need = tail;
-  s.planned = true;
+  RvPlan p = build_reverb_plan(num_items, h_src_offset, h_src_len, h_rir_offset, h_rir_len, h_shift, h_normalize, tail_start);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(rv->mu);
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(rv->tickets, "reverberations", &ticket)) return st;
+  const RvPlan& s = rv->plans[ticket % kTicketSlots] = std::move(p);
   if (h_out_offsets)
     for (int64_t i = 0; i < num_items; ++i) h_out_offsets[i] = s.items[(size_t)i].out_off;
   h_info[0] = ticket;
@@ -2441,118 +2328,45 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* rv, in
 extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
   if (!rv || !d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   std::lock_guard<std::mutex> lk(rv->mu);
-  RvSlot& s = rv->slots[((ticket % kRvSlots) + kRvSlots) % kRvSlots];
-  if (s.ticket != ticket || !s.planned)
-    return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned reverberation (at most %d plans may be outstanding)", (long long)ticket, kRvSlots);
-  if (arena_floats < s.arena_need)
-    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the reverberated cuts need %lld", (long long)arena_floats, (long long)s.arena_need);
+  const int slot = find_ticket(rv->tickets, ticket, "reverberation");
+  if (slot < 0) return HIPFEAT_ERR_INVALID;
+  const RvPlan& p = rv->plans[slot];
+  StagedSlot& s = rv->slots[slot];  // device: the staged table, then the partial sums of squares
+  if (arena_floats < p.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the reverberated cuts need %lld", (long long)arena_floats, (long long)p.arena_need);
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
-  s.planned = false;
   DeviceGuard g(rv->device);
   hipStream_t st = (hipStream_t)stream;
-  const size_t bytes = s.items.size() * sizeof(RvItem);  // (a multiple of 16)
-  const size_t part_bytes = (size_t)s.work_items * 2 * sizeof(double);
-  const bool inl = rv->allow_inline && bytes <= (size_t)kMbInlineBytes;
-  if (s.busy) {  // the launches that used this slot's device memory last time
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  const size_t dev_bytes = bytes + part_bytes;
-  if (s.cap < dev_bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
+  const size_t bytes = p.items.size() * sizeof(RvItem);  // (a multiple of 16)
+  const size_t part_bytes = (size_t)p.work_items * 2 * sizeof(double);
+  const TableRoute r = table_route(rv->allow_inline, bytes);
+  HIP_TRY(s.wait());
+  HIP_TRY(s.reserve(bytes + part_bytes));
   RvInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
   RvHeader& h = args.h;
   h.arena = d_arena;
   h.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(s.d) + bytes);
-  h.tables = nullptr;
-  h.num_items = (int32_t)s.items.size();
-  h.work_items = (int32_t)s.work_items;
+  h.num_items = (int32_t)p.items.size();
+  h.work_items = (int32_t)p.work_items;
   h.table_bytes = (int32_t)bytes;
   h.pad = 0;
-  // a few workgroups per CU take the work items round-robin (as hipfeat_mix_run)
-  const int64_t per_wg = std::max<int64_t>(1, (s.work_items + 1791) / 1792);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, (s.work_items + per_wg - 1) / per_wg);
-  const size_t dyn = bytes <= (size_t)kMbLdsTableBytes ? bytes : 0;
-  hipError_t e1 = hipSuccess;
-  if (inl) {
-    std::memcpy(args.blob, s.items.data(), bytes);
-    hipLaunchKernelGGL(reverb_conv_inline_kernel, dim3(grid), dim3(256), 0, st, args);
-    hipLaunchKernelGGL(reverb_gain_inline_kernel, dim3(grid), dim3(256), 0, st, args);
-    e1 = hipGetLastError();
+  HIP_TRY(place_tables(args, r, s, bytes, st, [&](unsigned char* dst) { std::memcpy(dst, p.items.data(), bytes); }));
+  const dim3 grid(items_grid(p.work_items)), wg(256);
+  if (r.inl) {
+    hipLaunchKernelGGL(reverb_conv_inline_kernel, grid, wg, 0, st, args);
+    hipLaunchKernelGGL(reverb_gain_inline_kernel, grid, wg, 0, st, args);
   } else {
-    std::memcpy(s.h, s.items.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
-    h.tables = static_cast<const unsigned char*>(s.d);
-    hipLaunchKernelGGL(reverb_conv_kernel, dim3(grid), dim3(256), dyn, st, h);
-    hipLaunchKernelGGL(reverb_gain_kernel, dim3(grid), dim3(256), dyn, st, h);
-    e1 = hipGetLastError();
+    hipLaunchKernelGGL(reverb_conv_kernel, grid, wg, r.dyn, st, h);
+    hipLaunchKernelGGL(reverb_gain_kernel, grid, wg, r.dyn, st, h);
   }
-  hipError_t e2 = hipEventRecord(s.ev, st);
-  s.busy = (e2 == hipSuccess);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "reverb launch failed: %s", hipGetErrorName(e1));
-  return HIPFEAT_OK;
+  return finish_run(rv->tickets, ticket, s, st, hipGetLastError(), "reverb", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
 // Level changes on the device (Volume, Clipping): peak + apply in two launches (kernel_level.hpp; the table: level_tables.hpp)
 // --------------------------------------------------------------------------------------
-constexpr int kLvSlots = 16;
-
-struct LvSlot {
-  int64_t ticket = -1;
-  bool planned = false;
-  std::vector<LvItem> items;
-  int64_t work_items = 0, arena_need = 0;
-  void* h = nullptr;  // pinned staging (a table that does not fit the kernel arguments)
-  void* d = nullptr;  // device: the staged table, then the partial peaks
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-};
-
-struct hipfeat_level {
-  int device = 0;
-  bool allow_inline = true;
-  std::mutex mu;
-  LvSlot slots[kLvSlots];
-  int64_t next_ticket = 0;
-};
-
-extern "C" HIPFEAT_API hipfeat_status hipfeat_level_create(int32_t device, hipfeat_level** out) {
-  if (!out) return fail(HIPFEAT_ERR_INVALID, "level pointer is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
-  hipfeat_level* l = new (std::nothrow) hipfeat_level();
-  if (!l) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  l->device = device;
-  l->allow_inline = route_env("HIPFEAT_MB_NO_INLINE") == nullptr;
-  *out = l;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_API hipfeat_status hipfeat_level_destroy(hipfeat_level* l) {
-  if (!l) return HIPFEAT_OK;
-  DeviceGuard g(l->device);
-  for (auto& s : l->slots) {
-    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  delete l;
-  return HIPFEAT_OK;
-}
+extern "C" HIPFEAT_API hipfeat_status hipfeat_level_create(int32_t device, hipfeat_level** out) { return handle_create(device, out, "level"); }
+extern "C" HIPFEAT_API hipfeat_status hipfeat_level_destroy(hipfeat_level* l) { return handle_destroy(l); }
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_level_plan(hipfeat_level* lv, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
                                                          const int64_t* h_dst_offset, const int64_t* h_op_first, const int32_t* h_op_kind,
@@ -2562,18 +2376,12 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_level_plan(hipfeat_level* lv, int6
   LvPlan p = build_level_plan(num_items, h_src_offset, h_src_len, h_dst_offset, h_op_first, h_op_kind, h_op_value, h_op_flags);
   if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
   std::lock_guard<std::mutex> lk(lv->mu);
-  if (lv->slots[lv->next_ticket % kLvSlots].planned)  // (never drop a live plan: its ticket would fail at run)
-    return fail(HIPFEAT_ERR_INVALID, "%d planned level changes are outstanding: run ticket %lld first", kLvSlots, (long long)lv->slots[lv->next_ticket % kLvSlots].ticket);
-  const int64_t ticket = lv->next_ticket++;
-  LvSlot& s = lv->slots[ticket % kLvSlots];
-  s.ticket = ticket;
-  s.items.swap(p.items);
-  s.work_items = p.work_items;
-  s.arena_need = p.arena_need;
-  s.planned = true;
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(lv->tickets, "level changes", &ticket)) return st;
+  const LvPlan& s = lv->plans[ticket % kTicketSlots] = std::move(p);
   h_info[0] = ticket;
   h_info[1] = s.arena_need;
-  h_info[2] = p.peak_items;
+  h_info[2] = s.peak_items;
   h_info[3] = s.work_items;
   return HIPFEAT_OK;
 }
@@ -2581,122 +2389,52 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_level_plan(hipfeat_level* lv, int6
 extern "C" HIPFEAT_API hipfeat_status hipfeat_level_run(hipfeat_level* lv, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
   if (!lv) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   std::lock_guard<std::mutex> lk(lv->mu);
-  LvSlot& s = lv->slots[((ticket % kLvSlots) + kLvSlots) % kLvSlots];
-  if (s.ticket != ticket || !s.planned)
-    return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned level change (at most %d plans may be outstanding)", (long long)ticket, kLvSlots);
-  if (s.items.empty()) {  // nothing to do: no launch
-    s.planned = false;
+  const int slot = find_ticket(lv->tickets, ticket, "level change");
+  if (slot < 0) return HIPFEAT_ERR_INVALID;
+  const LvPlan& p = lv->plans[slot];
+  StagedSlot& s = lv->slots[slot];  // device: the staged table, then the partial peaks
+  if (p.items.empty()) {  // nothing to do: no launch
+    lv->tickets.release(ticket);
     return HIPFEAT_OK;
   }
   if (!d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  if (arena_floats < s.arena_need)
-    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the items reach to %lld", (long long)arena_floats, (long long)s.arena_need);
+  if (arena_floats < p.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the items reach to %lld", (long long)arena_floats, (long long)p.arena_need);
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
-  DeviceGuard g(lv->device);  // (the ticket stays planned until its launches are enqueued: a failed allocation or copy below leaves it to be run again)
+  DeviceGuard g(lv->device);
   hipStream_t st = (hipStream_t)stream;
-  const size_t bytes = s.items.size() * sizeof(LvItem);  // (a multiple of 16)
-  const size_t part_bytes = (size_t)s.work_items * sizeof(float);
-  const bool inl = lv->allow_inline && bytes <= (size_t)kMbInlineBytes;
-  if (s.busy) {  // the launches that used this slot's device memory last time
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  const size_t dev_bytes = bytes + part_bytes;
-  if (s.cap < dev_bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(dev_bytes * 2, 1 << 14);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
+  const size_t bytes = p.items.size() * sizeof(LvItem);  // (a multiple of 16)
+  const size_t part_bytes = (size_t)p.work_items * sizeof(float);
+  const TableRoute r = table_route(lv->allow_inline, bytes);
+  HIP_TRY(s.wait());
+  HIP_TRY(s.reserve(bytes + part_bytes));
   LvInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
   LvHeader& h = args.h;
   h.arena = d_arena;
   h.partials = reinterpret_cast<float*>(static_cast<unsigned char*>(s.d) + bytes);
-  h.tables = nullptr;
-  h.num_items = (int32_t)s.items.size();
-  h.work_items = (int32_t)s.work_items;
+  h.num_items = (int32_t)p.items.size();
+  h.work_items = (int32_t)p.work_items;
   h.table_bytes = (int32_t)bytes;
   h.pad = 0;
-  // a few workgroups per CU take the work items round-robin (as hipfeat_reverb_run)
-  const int64_t per_wg = std::max<int64_t>(1, (s.work_items + 1791) / 1792);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, (s.work_items + per_wg - 1) / per_wg);
-  const size_t dyn = bytes <= (size_t)kMbLdsTableBytes ? bytes : 0;
+  HIP_TRY(place_tables(args, r, s, bytes, st, [&](unsigned char* dst) { std::memcpy(dst, p.items.data(), bytes); }));
+  const dim3 grid(items_grid(p.work_items)), wg(256);
   bool any_clip = false;
-  for (const LvItem& it : s.items) any_clip = any_clip || it.clip_at >= 0;
-  hipError_t e1 = hipSuccess;
-  if (inl) {
-    std::memcpy(args.blob, s.items.data(), bytes);
-    if (any_clip) hipLaunchKernelGGL(level_peak_inline_kernel, dim3(grid), dim3(256), 0, st, args);
-    hipLaunchKernelGGL(level_apply_inline_kernel, dim3(grid), dim3(256), 0, st, args);
-    e1 = hipGetLastError();
+  for (const LvItem& it : p.items) any_clip = any_clip || it.clip_at >= 0;
+  if (r.inl) {
+    if (any_clip) hipLaunchKernelGGL(level_peak_inline_kernel, grid, wg, 0, st, args);
+    hipLaunchKernelGGL(level_apply_inline_kernel, grid, wg, 0, st, args);
   } else {
-    std::memcpy(s.h, s.items.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
-    h.tables = static_cast<const unsigned char*>(s.d);
-    if (any_clip) hipLaunchKernelGGL(level_peak_kernel, dim3(grid), dim3(256), dyn, st, h);
-    hipLaunchKernelGGL(level_apply_kernel, dim3(grid), dim3(256), dyn, st, h);
-    e1 = hipGetLastError();
+    if (any_clip) hipLaunchKernelGGL(level_peak_kernel, grid, wg, r.dyn, st, h);
+    hipLaunchKernelGGL(level_apply_kernel, grid, wg, r.dyn, st, h);
   }
-  s.planned = false;  // enqueued (or refused by the runtime at launch): the ticket has run
-  hipError_t e2 = hipEventRecord(s.ev, st);
-  s.busy = (e2 == hipSuccess);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "level launch failed: %s", hipGetErrorName(e1));
-  if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
-    (void)hipStreamSynchronize(st);
-    return fail(HIPFEAT_ERR_HIP, "level: hipEventRecord failed: %s (the launches were enqueued and have been waited for)", hipGetErrorName(e2));
-  }
-  return HIPFEAT_OK;
+  return finish_run(lv->tickets, ticket, s, st, hipGetLastError(), "level", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
 // Collation on the device (AudioSamples, return_audio): one launch (kernel_collate.hpp; the table: collate_tables.hpp)
 // --------------------------------------------------------------------------------------
-struct CoSlot {
-  CoPlan plan;
-  void* h = nullptr;  // pinned staging of the row table
-  void* d = nullptr;  // device: the row table
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-};
-
-struct hipfeat_collate {
-  int device = 0;
-  std::mutex mu;
-  CoSlots tickets;  // which tickets are planned and not yet run (collate_tables.hpp)
-  CoSlot slots[kCoSlots];
-};
-
-extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_create(int32_t device, hipfeat_collate** out) {
-  if (!out) return fail(HIPFEAT_ERR_INVALID, "collate pointer is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
-  hipfeat_collate* c = new (std::nothrow) hipfeat_collate();
-  if (!c) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  c->device = device;
-  *out = c;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_destroy(hipfeat_collate* c) {
-  if (!c) return HIPFEAT_OK;
-  DeviceGuard g(c->device);
-  for (auto& s : c->slots) {
-    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  delete c;
-  return HIPFEAT_OK;
-}
+extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_create(int32_t device, hipfeat_collate** out) { return handle_create(device, out, "collate"); }
+extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_destroy(hipfeat_collate* c) { return handle_destroy(c); }
 
 extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_collate* c, int64_t num_rows, const int64_t* h_src_offset, const int64_t* h_src_len,
                                                                    const int64_t* h_dst_offset, int64_t row_len, int32_t out_type, int64_t* h_info) {
@@ -2705,16 +2443,13 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_colla
   CoPlan p = build_collate_plan(num_rows, h_src_offset, h_src_len, h_dst_offset, row_len, out_type);
   if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
   std::lock_guard<std::mutex> lk(c->mu);
-  const int64_t ticket = c->tickets.take();
-  if (ticket < 0)  // (never drop a live plan: its ticket would fail at run)
-    return fail(HIPFEAT_ERR_INVALID, "%d planned collations are outstanding: run ticket %lld first", kCoSlots,
-                (long long)c->tickets.ticket[c->tickets.next_ticket % kCoSlots]);
-  CoSlot& s = c->slots[ticket % kCoSlots];
-  s.plan = std::move(p);
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(c->tickets, "collations", &ticket)) return st;
+  const CoPlan& s = c->plans[ticket % kTicketSlots] = std::move(p);
   h_info[0] = ticket;
-  h_info[1] = s.plan.arena_need;
-  h_info[2] = s.plan.out_need;
-  h_info[3] = s.plan.work_items;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.out_need;
+  h_info[3] = s.work_items;
   return HIPFEAT_OK;
 }
 
@@ -2722,10 +2457,10 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
                                                                   int64_t out_elements, void* stream) {
   if (!c) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   std::lock_guard<std::mutex> lk(c->mu);
-  const int slot = c->tickets.slot_of(ticket);
-  if (slot < 0) return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned collation (at most %d plans may be outstanding)", (long long)ticket, kCoSlots);
-  CoSlot& s = c->slots[slot];
-  const CoPlan& p = s.plan;
+  const int slot = find_ticket(c->tickets, ticket, "collation");
+  if (slot < 0) return HIPFEAT_ERR_INVALID;
+  const CoPlan& p = c->plans[slot];
+  StagedSlot& s = c->slots[slot];  // device: the row table
   if (arena_floats < p.arena_need)
     return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the rows read up to %lld", (long long)arena_floats, (long long)p.arena_need);
   if (out_elements < p.out_need)
@@ -2743,24 +2478,11 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)out_elements * (uintptr_t)esz;
     if (a0 < o1 && o0 < a1) return fail(HIPFEAT_ERR_INVALID, "out overlaps the arena");
   }
-  DeviceGuard g(c->device);  // (the ticket stays planned until its launch is enqueued: a failed allocation or copy below leaves it to be run again)
+  DeviceGuard g(c->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = p.rows.size() * sizeof(CoRow);
-  if (s.busy) {  // the launch that used this slot's device memory last time
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1 << 14);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
+  HIP_TRY(s.wait());
+  HIP_TRY(s.reserve(bytes));
   std::memcpy(s.h, p.rows.data(), bytes);
   HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
   CoArgs a;
@@ -2775,62 +2497,14 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
   if (p.out_type == kCoF32) hipLaunchKernelGGL(collate_wave_kernel<float>, dim3(grid), dim3(256), 0, st, a);
   else if (p.out_type == kCoF16) hipLaunchKernelGGL(collate_wave_kernel<__half>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(collate_wave_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, a);
-  hipError_t e1 = hipGetLastError();
-  c->tickets.release(ticket);  // enqueued (or refused by the runtime at launch): the ticket has run
-  hipError_t e2 = hipEventRecord(s.ev, st);
-  s.busy = (e2 == hipSuccess);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "collate launch failed: %s", hipGetErrorName(e1));
-  if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
-    (void)hipStreamSynchronize(st);
-    return fail(HIPFEAT_ERR_HIP, "collate: hipEventRecord failed: %s (the launch was enqueued and has been waited for)", hipGetErrorName(e2));
-  }
-  return HIPFEAT_OK;
+  return finish_run(c->tickets, ticket, s, st, hipGetLastError(), "collate", kWaitedLaunch);
 }
 
 // --------------------------------------------------------------------------------------
 // Sinc resampler without a filter bank (LowpassUsingResampling, any Resample): one launch (kernel_sinc.hpp; the table: sinc_tables.hpp)
 // --------------------------------------------------------------------------------------
-struct SincSlot {
-  SincPlan plan;
-  void* h = nullptr;  // pinned staging of the row table
-  void* d = nullptr;  // device: the row table
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-};
-
-struct hipfeat_sinc {
-  int device = 0;
-  std::mutex mu;
-  CoSlots tickets;  // which tickets are planned and not yet run (the 16 slots of collate_tables.hpp)
-  SincSlot slots[kCoSlots];
-};
-
-extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_create(int32_t device, hipfeat_sinc** out) {
-  if (!out) return fail(HIPFEAT_ERR_INVALID, "sinc pointer is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
-  hipfeat_sinc* s = new (std::nothrow) hipfeat_sinc();
-  if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  s->device = device;
-  *out = s;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_destroy(hipfeat_sinc* sc) {
-  if (!sc) return HIPFEAT_OK;
-  DeviceGuard g(sc->device);
-  for (auto& s : sc->slots) {
-    if (s.busy && s.ev) (void)hipEventSynchronize(s.ev);
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
-  delete sc;
-  return HIPFEAT_OK;
-}
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_create(int32_t device, hipfeat_sinc** out) { return handle_create(device, out, "sinc"); }
+extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_destroy(hipfeat_sinc* sc) { return handle_destroy(sc); }
 
 extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_plan(hipfeat_sinc* sc, int64_t num_rows, const int64_t* h_in_offset, const int64_t* h_in_len,
                                                              const int32_t* h_src_rate, const int32_t* h_dst_rate, const int64_t* h_out_offset,
@@ -2840,27 +2514,24 @@ extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_plan(hipfeat_sinc* sc, i
   SincPlan p = build_sinc_plan(num_rows, h_in_offset, h_in_len, h_src_rate, h_dst_rate, h_out_offset, arena_floats);
   if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
   std::lock_guard<std::mutex> lk(sc->mu);
-  const int64_t ticket = sc->tickets.take();
-  if (ticket < 0)  // (never drop a live plan: its ticket would fail at run)
-    return fail(HIPFEAT_ERR_INVALID, "%d planned resamplings are outstanding: run ticket %lld first", kCoSlots,
-                (long long)sc->tickets.ticket[sc->tickets.next_ticket % kCoSlots]);
-  SincSlot& s = sc->slots[ticket % kCoSlots];
-  s.plan = std::move(p);
-  for (int64_t i = 0; i < num_rows; ++i) h_out_len[i] = s.plan.out_len[(size_t)i];
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(sc->tickets, "resamplings", &ticket)) return st;
+  const SincPlan& s = sc->plans[ticket % kTicketSlots] = std::move(p);
+  for (int64_t i = 0; i < num_rows; ++i) h_out_len[i] = s.out_len[(size_t)i];
   h_info[0] = ticket;
-  h_info[1] = s.plan.arena_need;
-  h_info[2] = s.plan.workgroups;
-  h_info[3] = s.plan.max_w;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.workgroups;
+  h_info[3] = s.max_w;
   return HIPFEAT_OK;
 }
 
 extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sc, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream) {
   if (!sc) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   std::lock_guard<std::mutex> lk(sc->mu);
-  const int slot = sc->tickets.slot_of(ticket);
-  if (slot < 0) return fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned resampling (at most %d plans may be outstanding)", (long long)ticket, kCoSlots);
-  SincSlot& s = sc->slots[slot];
-  const SincPlan& p = s.plan;
+  const int slot = find_ticket(sc->tickets, ticket, "resampling");
+  if (slot < 0) return HIPFEAT_ERR_INVALID;
+  const SincPlan& p = sc->plans[slot];
+  StagedSlot& s = sc->slots[slot];  // device: the row table
   if (arena_floats < p.arena_need)
     return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the rows reach to %lld", (long long)arena_floats, (long long)p.arena_need);
   if (p.workgroups == 0) {  // no rows, or rows of no samples: no launch
@@ -2869,7 +2540,7 @@ extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sc, in
   }
   if (!d_arena) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
-  DeviceGuard g(sc->device);  // (the ticket stays planned until its launch is enqueued: a failed allocation or copy below leaves it to be run again)
+  DeviceGuard g(sc->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = p.rows.size() * sizeof(SincRow);
   const size_t lds = (size_t)p.max_w * kSincPhases * sizeof(float);
@@ -2877,21 +2548,8 @@ extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sc, in
     hipError_t e = ensure_dynamic_lds(entry<sinc_kernel>(), lds);
     if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
   }
-  if (s.busy) {  // the launch that used this slot's device memory last time
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1 << 14);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
+  HIP_TRY(s.wait());
+  HIP_TRY(s.reserve(bytes));
   std::memcpy(s.h, p.rows.data(), bytes);
   HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
   SincArgs a;
@@ -2900,16 +2558,7 @@ extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sc, in
   a.num_rows = (int32_t)p.rows.size();
   a.pad = 0;
   hipLaunchKernelGGL(sinc_kernel, dim3((unsigned)p.workgroups), dim3(256), lds, st, a);
-  hipError_t e1 = hipGetLastError();
-  sc->tickets.release(ticket);  // enqueued (or refused by the runtime at launch): the ticket has run
-  hipError_t e2 = hipEventRecord(s.ev, st);
-  s.busy = (e2 == hipSuccess);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "sinc launch failed: %s", hipGetErrorName(e1));
-  if (e2 != hipSuccess) {  // the slot's memory cannot be guarded by its event: wait here instead, then report
-    (void)hipStreamSynchronize(st);
-    return fail(HIPFEAT_ERR_HIP, "sinc: hipEventRecord failed: %s (the launch was enqueued and has been waited for)", hipGetErrorName(e2));
-  }
-  return HIPFEAT_OK;
+  return finish_run(sc->tickets, ticket, s, st, hipGetLastError(), "sinc", kWaitedLaunch);
 }
 
 extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_weights(hipfeat_sinc* sc, int32_t src_rate, int32_t dst_rate, float* d_weights, int32_t* d_first,

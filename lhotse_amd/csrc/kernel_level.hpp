@@ -165,47 +165,30 @@ __device__ __forceinline__ void level_apply_body(const LvHeader& h, const unsign
   }
 }
 
-// the table from the kernel-argument segment to LDS, 16 bytes per lane, once (as reverb_inline_tables)
-__device__ __forceinline__ void level_inline_tables(unsigned char* tb, int table_bytes) {
-  const __attribute__((address_space(4))) mb_i4* src =
-      (const __attribute__((address_space(4))) mb_i4*)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                       offsetof(LvInlineArgs, blob));
-  for (int k = threadIdx.x; 16 * k < table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb)[k] = src[k];
-  __syncthreads();
-}
-
-// staged table: to LDS when it fits kMbLdsTableBytes (dynamic LDS = table_bytes), else searched where it is
-__device__ __forceinline__ const unsigned char* level_staged_tables(const LvHeader& h, unsigned char* tb_dyn) {
-  if (h.table_bytes > kMbLdsTableBytes) return h.tables;
-  for (int k = threadIdx.x; 16 * k < h.table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb_dyn)[k] = reinterpret_cast<const mb_i4*>(h.tables)[k];
-  __syncthreads();
-  return tb_dyn;
-}
-
 __global__ __launch_bounds__(256) void level_peak_inline_kernel(const LvInlineArgs a) {
   __shared__ float red[4];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
-  level_inline_tables(tb, a.h.table_bytes);
+  mb_inline_tables(tb, a.h.table_bytes, offsetof(LvInlineArgs, blob));
   level_peak_body(a.h, tb, red);
 }
 
 __global__ __launch_bounds__(256) void level_peak_kernel(const LvHeader h) {
   __shared__ float red[4];
   extern __shared__ __attribute__((aligned(16))) unsigned char level_tb_dyn[];
-  level_peak_body(h, level_staged_tables(h, level_tb_dyn), red);
+  level_peak_body(h, mb_staged_tables(h.tables, h.table_bytes, level_tb_dyn), red);
 }
 
 __global__ __launch_bounds__(256) void level_apply_inline_kernel(const LvInlineArgs a) {
   __shared__ float red[4];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
-  level_inline_tables(tb, a.h.table_bytes);
+  mb_inline_tables(tb, a.h.table_bytes, offsetof(LvInlineArgs, blob));
   level_apply_body(a.h, tb, red);
 }
 
 __global__ __launch_bounds__(256) void level_apply_kernel(const LvHeader h) {
   __shared__ float red[4];
   extern __shared__ __attribute__((aligned(16))) unsigned char level_tb_dyn[];
-  level_apply_body(h, level_staged_tables(h, level_tb_dyn), red);
+  level_apply_body(h, mb_staged_tables(h.tables, h.table_bytes, level_tb_dyn), red);
 }
 
 }  // namespace hipfeat

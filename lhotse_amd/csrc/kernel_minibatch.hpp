@@ -56,6 +56,23 @@ static_assert(offsetof(MbInlineArgs, blob) % 16 == 0 && sizeof(MbInlineArgs) <= 
 
 typedef int mb_i4 __attribute__((ext_vector_type(4)));
 
+// a launch's tables from where the launch put them -- the kernel-argument segment (constant address space), blob_offset =
+// offsetof(<its arguments>, blob) -- to LDS, 16 bytes per lane, once
+__device__ __forceinline__ void mb_inline_tables(unsigned char* tb, int table_bytes, size_t blob_offset) {
+  const __attribute__((address_space(4))) mb_i4* src =
+      (const __attribute__((address_space(4))) mb_i4*)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() + blob_offset);
+  for (int k = threadIdx.x; 16 * k < table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb)[k] = src[k];
+  __syncthreads();
+}
+
+// staged tables: to LDS when they fit kMbLdsTableBytes (dynamic LDS = table_bytes), else searched where they are
+__device__ __forceinline__ const unsigned char* mb_staged_tables(const unsigned char* tables, int table_bytes, unsigned char* tb_dyn) {
+  if (table_bytes > kMbLdsTableBytes) return tables;
+  for (int k = threadIdx.x; 16 * k < table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb_dyn)[k] = reinterpret_cast<const mb_i4*>(tables)[k];
+  __syncthreads();
+  return tb_dyn;
+}
+
 // first index i in [0, n) with prefix[i * stride] > v, minus one (prefix[0] == 0 <= v): the owner of item v.  Wave-uniform.
 __device__ __forceinline__ int mb_owner(const int32_t* prefix, int stride, int n, int v) {
   int lo = 0, hi = n - 1;
@@ -147,6 +164,7 @@ __global__ __launch_bounds__(256) void minibatch_prep_inline_kernel(const MbInli
   __shared__ __attribute__((aligned(16))) float xs[kMbXsFloats];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
   // the tables are read where the launch put them: the kernel-argument segment (constant address space), 16 bytes per lane, once
+  // (mb_inline_tables spelled out: through the helper this kernel, alone of all, compiles to another instruction stream)
   const __attribute__((address_space(4))) mb_i4* src =
       (const __attribute__((address_space(4))) mb_i4*)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
                                                        offsetof(MbInlineArgs, blob));
@@ -158,13 +176,7 @@ __global__ __launch_bounds__(256) void minibatch_prep_inline_kernel(const MbInli
 __global__ __launch_bounds__(256) void minibatch_prep_kernel(const MbHeader h) {
   __shared__ __attribute__((aligned(16))) float xs[kMbXsFloats];
   extern __shared__ __attribute__((aligned(16))) unsigned char tb_dyn[];  // table_bytes when they fit kMbLdsTableBytes, else nothing
-  const unsigned char* tb = h.tables;
-  if (h.table_bytes <= kMbLdsTableBytes) {
-    for (int k = threadIdx.x; 16 * k < h.table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb_dyn)[k] = reinterpret_cast<const mb_i4*>(h.tables)[k];
-    __syncthreads();
-    tb = tb_dyn;
-  }
-  minibatch_prep_body(h, tb, xs);
+  minibatch_prep_body(h, mb_staged_tables(h.tables, h.table_bytes, tb_dyn), xs);
 }
 
 }  // namespace hipfeat

@@ -24,31 +24,9 @@
 #pragma once
 #include "common.hpp"
 #include "kernel_minibatch.hpp"
+#include "mix_tables.hpp"
 
 namespace hipfeat {
-
-constexpr int kMixEnergyBlock = 16384;  // samples per energy item (256 lanes x 64): a 30 s track at 16 kHz is 30 partials
-constexpr int kMixBlock = 4096;         // output samples per mix item (256 lanes x 4 x float4)
-constexpr int kMixMaxTracks = 256;      // tracks of one cut (their gains live in LDS, one lane forms each)
-
-struct MixTrack {
-  int64_t src_off;     // arena offset of the track's samples; < 0: a padding track (no source)
-  int32_t src_len;     // samples
-  int32_t dst_off;     // first sample of the track inside its cut
-  int32_t part_first;  // exclusive prefix sum of the tracks' energy items = index of the track's first partial
-  int32_t part_count;  // 0: no energy needed
-  double ratio;        // 10^(-snr/10); < 0: no SNR (gain 1)
-};
-struct MixCut {
-  int64_t out_off;      // arena offset of the mixed cut (16-byte aligned)
-  int32_t out_len;      // samples written
-  int32_t item_first;   // exclusive prefix sum of the cuts' mix items
-  int32_t track_first;  // tracks of the cut = [track_first, track_first + track_count)
-  int32_t track_count;
-  int32_t ref_track;    // index into the track table, < 0: none
-  int32_t pad;
-};
-static_assert(sizeof(MixTrack) == 32 && sizeof(MixCut) == 32, "descriptor size");
 
 struct MixHeader {
   float* arena;
@@ -156,47 +134,30 @@ __device__ __forceinline__ void mix_body(const MixHeader& h, const unsigned char
   }
 }
 
-// the tables from the kernel-argument segment to LDS, 16 bytes per lane, once (as minibatch_prep_inline_kernel)
-__device__ __forceinline__ void mix_inline_tables(unsigned char* tb, int table_bytes) {
-  const __attribute__((address_space(4))) mb_i4* src =
-      (const __attribute__((address_space(4))) mb_i4*)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                       offsetof(MixInlineArgs, blob));
-  for (int k = threadIdx.x; 16 * k < table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb)[k] = src[k];
-  __syncthreads();
-}
-
-// staged tables: to LDS when they fit kMbLdsTableBytes (dynamic LDS = table_bytes), else searched where they are
-__device__ __forceinline__ const unsigned char* mix_staged_tables(const MixHeader& h, unsigned char* tb_dyn) {
-  if (h.table_bytes > kMbLdsTableBytes) return h.tables;
-  for (int k = threadIdx.x; 16 * k < h.table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb_dyn)[k] = reinterpret_cast<const mb_i4*>(h.tables)[k];
-  __syncthreads();
-  return tb_dyn;
-}
-
 __global__ __launch_bounds__(256) void mix_energy_inline_kernel(const MixInlineArgs a) {
   __shared__ double red[4];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
-  mix_inline_tables(tb, a.h.table_bytes);
+  mb_inline_tables(tb, a.h.table_bytes, offsetof(MixInlineArgs, blob));
   mix_energy_body(a.h, tb, red);
 }
 
 __global__ __launch_bounds__(256) void mix_energy_kernel(const MixHeader h) {
   __shared__ double red[4];
   extern __shared__ __attribute__((aligned(16))) unsigned char mix_tb_dyn[];
-  mix_energy_body(h, mix_staged_tables(h, mix_tb_dyn), red);
+  mix_energy_body(h, mb_staged_tables(h.tables, h.table_bytes, mix_tb_dyn), red);
 }
 
 __global__ __launch_bounds__(256) void mix_inline_kernel(const MixInlineArgs a) {
   __shared__ float gains[kMixMaxTracks];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
-  mix_inline_tables(tb, a.h.table_bytes);
+  mb_inline_tables(tb, a.h.table_bytes, offsetof(MixInlineArgs, blob));
   mix_body(a.h, tb, gains);
 }
 
 __global__ __launch_bounds__(256) void mix_kernel(const MixHeader h) {
   __shared__ float gains[kMixMaxTracks];
   extern __shared__ __attribute__((aligned(16))) unsigned char mix_tb_dyn[];
-  mix_body(h, mix_staged_tables(h, mix_tb_dyn), gains);
+  mix_body(h, mb_staged_tables(h.tables, h.table_bytes, mix_tb_dyn), gains);
 }
 
 }  // namespace hipfeat

@@ -36,26 +36,9 @@
 #pragma once
 #include "common.hpp"
 #include "kernel_minibatch.hpp"
+#include "reverb_tables.hpp"
 
 namespace hipfeat {
-
-constexpr int kRvLane = 8;                     // consecutive outputs per lane
-constexpr int kRvBlock = 256 * kRvLane;        // outputs per work item
-constexpr int kRvChunk = 256;                  // taps per partial sum
-constexpr int kRvWindow = kRvBlock + kRvChunk; // floats of x in LDS per chunk (the last one is never used)
-
-struct RvItem {
-  int64_t src_off;     // arena offset of the input channel
-  int64_t rir_off;     // arena offset of the scaled RIR
-  int64_t out_off;     // arena offset of the output (16-byte aligned)
-  int32_t n;           // samples in = samples out
-  int32_t taps;        // L
-  int32_t shift;       // first index of max(hs)
-  int32_t item_first;  // exclusive prefix sum of the items' work items
-  int32_t normalize;
-  int32_t pad;
-};
-static_assert(sizeof(RvItem) == 48, "descriptor size");
 
 struct RvHeader {
   float* arena;
@@ -214,29 +197,12 @@ __device__ __forceinline__ void reverb_gain_body(const RvHeader& h, const unsign
   }
 }
 
-// the table from the kernel-argument segment to LDS, 16 bytes per lane, once (as mix_inline_tables)
-__device__ __forceinline__ void reverb_inline_tables(unsigned char* tb, int table_bytes) {
-  const __attribute__((address_space(4))) mb_i4* src =
-      (const __attribute__((address_space(4))) mb_i4*)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                       offsetof(RvInlineArgs, blob));
-  for (int k = threadIdx.x; 16 * k < table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb)[k] = src[k];
-  __syncthreads();
-}
-
-// staged table: to LDS when it fits kMbLdsTableBytes (dynamic LDS = table_bytes), else searched where it is
-__device__ __forceinline__ const unsigned char* reverb_staged_tables(const RvHeader& h, unsigned char* tb_dyn) {
-  if (h.table_bytes > kMbLdsTableBytes) return h.tables;
-  for (int k = threadIdx.x; 16 * k < h.table_bytes; k += 256) reinterpret_cast<mb_i4*>(tb_dyn)[k] = reinterpret_cast<const mb_i4*>(h.tables)[k];
-  __syncthreads();
-  return tb_dyn;
-}
-
 __global__ __launch_bounds__(256) void reverb_conv_inline_kernel(const RvInlineArgs a) {
   __shared__ __attribute__((aligned(16))) float xs[kRvWindow];
   __shared__ __attribute__((aligned(16))) float hs[kRvChunk];
   __shared__ double red[4];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
-  reverb_inline_tables(tb, a.h.table_bytes);
+  mb_inline_tables(tb, a.h.table_bytes, offsetof(RvInlineArgs, blob));
   reverb_conv_body(a.h, tb, xs, hs, red);
 }
 
@@ -245,20 +211,20 @@ __global__ __launch_bounds__(256) void reverb_conv_kernel(const RvHeader h) {
   __shared__ __attribute__((aligned(16))) float hs[kRvChunk];
   __shared__ double red[4];
   extern __shared__ __attribute__((aligned(16))) unsigned char reverb_tb_dyn[];
-  reverb_conv_body(h, reverb_staged_tables(h, reverb_tb_dyn), xs, hs, red);
+  reverb_conv_body(h, mb_staged_tables(h.tables, h.table_bytes, reverb_tb_dyn), xs, hs, red);
 }
 
 __global__ __launch_bounds__(256) void reverb_gain_inline_kernel(const RvInlineArgs a) {
   __shared__ float gain[2];
   __shared__ __attribute__((aligned(16))) unsigned char tb[kMbInlineBytes];
-  reverb_inline_tables(tb, a.h.table_bytes);
+  mb_inline_tables(tb, a.h.table_bytes, offsetof(RvInlineArgs, blob));
   reverb_gain_body(a.h, tb, gain);
 }
 
 __global__ __launch_bounds__(256) void reverb_gain_kernel(const RvHeader h) {
   __shared__ float gain[2];
   extern __shared__ __attribute__((aligned(16))) unsigned char reverb_tb_dyn[];
-  reverb_gain_body(h, reverb_staged_tables(h, reverb_tb_dyn), gain);
+  reverb_gain_body(h, mb_staged_tables(h.tables, h.table_bytes, reverb_tb_dyn), gain);
 }
 
 }  // namespace hipfeat

@@ -1,8 +1,9 @@
-// Test shim (CPU only): a C entry point around lhotse_amd/csrc/collate_tables.hpp -- the whole of what hipfeat_collate_plan decides, the
-// 16 ticket slots included -- so that tests/test_collate_abi.py can check the table and the plan-time errors without a device.  With
-// -DCOLLATE_TABLES_MAIN it is a stand-alone program (also built with -fsanitize=address,undefined) that walks the same code over row
+// Test shim (CPU only): a C entry point around lhotse_amd/csrc/collate_tables.hpp and ticket_slots.hpp -- the whole of what
+// hipfeat_collate_plan decides, the 16 ticket slots every ticketed handle shares included -- so that
+// tests/test_collate_abi.py can check the table and the plan-time errors without a device.  With -DCOLLATE_TABLES_MAIN it is a stand-alone program (also built with -fsanitize=address,undefined) that walks the same code over row
 // lengths around the tile and group boundaries and checks the invariants the kernel relies on for its bounds.
 #include "../../lhotse_amd/csrc/collate_tables.hpp"
+#include "../../lhotse_amd/csrc/ticket_slots.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -21,15 +22,15 @@ extern "C" int ct_plan(long long num_rows, const int64_t* h_src_offset, const in
   return 0;
 }
 
-// the ticket slots of hipfeat_collate: ct_slots_plan takes the next ticket (-1: all kCoSlots are planned and not yet run), ct_slots_run
+// the ticket ring (ticket_slots.hpp): ct_slots_plan takes the next ticket (-1: all kTicketSlots are planned and not yet run), ct_slots_run
 // frees one (0: it was planned, 1: unknown ticket)
-static hipfeat::CoSlots g_slots;
-extern "C" void ct_slots_reset() { g_slots = hipfeat::CoSlots(); }
+static hipfeat::TicketRing g_slots;
+extern "C" void ct_slots_reset() { g_slots = hipfeat::TicketRing(); }
 extern "C" long long ct_slots_plan() { return g_slots.take(); }
 extern "C" int ct_slots_run(long long ticket) { return g_slots.release(ticket) ? 0 : 1; }
 
 extern "C" int ct_tile() { return hipfeat::kCoTile; }
-extern "C" int ct_slots() { return hipfeat::kCoSlots; }
+extern "C" int ct_slots() { return hipfeat::kTicketSlots; }
 extern "C" long long ct_tiles(long long row_len, int out_type) { return hipfeat::co_tiles(row_len, out_type); }
 
 #ifdef COLLATE_TABLES_MAIN

@@ -178,9 +178,9 @@ def _check_against_rule(cuts, wants, got):
 # Sizes the large shapes sit on (tests/test_mix_abi.py::test_launch_constants_the_gpu_shapes_sit_on fails when one of them moves):
 INLINE_BYTES = 3328      # kMbInlineBytes, lhotse_amd/csrc/kernel_minibatch.hpp:31: tables up to this size travel in the kernel arguments
 LDS_TABLE_BYTES = 24576  # kMbLdsTableBytes, kernel_minibatch.hpp:32: staged tables up to this size are copied to LDS, larger ones searched in HBM
-MAX_WORKGROUPS = 1792    # grid_of in hipfeat_mix_run, lhotse_amd/csrc/hipfeat.hip:2329: grid = ceil(items / ceil(items / 1792))
-DESCRIPTOR_BYTES = 32    # sizeof(MixCut) = sizeof(MixTrack), lhotse_amd/csrc/kernel_mix.hpp:51: one per cut and one per track
-MIX_BLOCK, ENERGY_BLOCK = 4096, 16384  # kMixBlock, kMixEnergyBlock (kernel_mix.hpp:30-31): samples per mix item / energy item
+MAX_WORKGROUPS = 1792    # items_grid (hipfeat_mix_run), lhotse_amd/csrc/hipfeat.hip:1910: grid = ceil(items / ceil(items / 1792))
+DESCRIPTOR_BYTES = 32    # sizeof(MixCut) = sizeof(MixTrack), lhotse_amd/csrc/mix_tables.hpp:39: one per cut and one per track
+MIX_BLOCK, ENERGY_BLOCK = 4096, 16384  # kMixBlock, kMixEnergyBlock (mix_tables.hpp:18-19): samples per mix item / energy item
 
 
 def _route(table_bytes):

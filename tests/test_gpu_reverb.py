@@ -141,9 +141,9 @@ def test_runs_repeat_and_items_do_not_depend_on_their_neighbours(grid):
 # Sizes the shapes below sit on (tests/test_mix_abi.py::test_launch_constants_the_gpu_shapes_sit_on fails when one of them moves):
 INLINE_BYTES = 3328      # kMbInlineBytes, lhotse_amd/csrc/kernel_minibatch.hpp:31: a table up to this size travels in the kernel arguments
 LDS_TABLE_BYTES = 24576  # kMbLdsTableBytes, kernel_minibatch.hpp:32: a staged table up to this size is copied to LDS, a larger one searched in HBM
-MAX_WORKGROUPS = 1792    # hipfeat_reverb_run, lhotse_amd/csrc/hipfeat.hip:2498: grid = ceil(work / ceil(work / 1792))
-RV_ITEM_BYTES = 48       # sizeof(RvItem), lhotse_amd/csrc/kernel_reverb.hpp:58
-RV_BLOCK = 2048          # kRvBlock, kernel_reverb.hpp:43: outputs per work item
+MAX_WORKGROUPS = 1792    # items_grid (hipfeat_reverb_run), lhotse_amd/csrc/hipfeat.hip:1910: grid = ceil(work / ceil(work / 1792))
+RV_ITEM_BYTES = 48       # sizeof(RvItem), lhotse_amd/csrc/reverb_tables.hpp:30
+RV_BLOCK = 2048          # kRvBlock, reverb_tables.hpp:15: outputs per work item
 
 
 def _route(num_items):

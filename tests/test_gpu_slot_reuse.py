@@ -1,0 +1,225 @@
+"""GPU: a staging slot's SECOND use while its first may still be in flight, with a table that has outgrown the slot -- for each of the
+five ticketed handles (mix, reverb, level, collate, sinc).
+
+A private handle gets 17 plan -> run pairs on one stream with no host synchronisation between them.  Runs 0 ... 15 carry a table of one or
+two entries (the kernel-argument route where the kind has one) and make every slot allocate its first 16384 bytes; run 16 lands on
+slot 0 again with a table LARGER than that, so the slot has to wait for run 0's launches, free both buffers and allocate anew before it
+stages.  Every run has its own small arena; after ONE final synchronise, runs 0, 15 and 16 are held to the reference and the tolerance
+of the kind's own GPU test (imported from there: nothing is restated here)."""
+import numpy as np
+import pytest
+import torch
+
+import _level_ref as L
+import _reverb_ref as R
+import _sinc_ref as SR
+import test_gpu_mix
+import test_gpu_reverb
+import test_gpu_sinc
+from _collate_ref import bits_of, collate_ref
+
+from lhotse_amd.augmentation import HipCollator, HipLevel, HipMixer, HipReverb, HipSincResampler, mixed_tail_floats, reverb_tail_floats, scaled_rir
+
+pytestmark = pytest.mark.gpu
+SLOTS = 16
+FIRST_ALLOCATION = 16384  # bytes a slot holds after its first use with a small table: max(2 * bytes, 1 << 14)
+RUNS = [1, 2] * (SLOTS // 2)  # entries of the tables of runs 0 ... 15
+CHECKED = (0, SLOTS - 1, SLOTS)
+SINC_ROW_BYTES, LEVEL_ITEM_BYTES, COLLATE_ROW_BYTES = 64, 64, 32  # sizeof(SincRow), sizeof(LvItem), sizeof(CoRow): the static_asserts of csrc/*_tables.hpp
+
+
+def _lengths(rng, n):
+    return [int(v) for v in rng.integers(8, 65, size=n)]
+
+
+def _drive(handle, cases):
+    """cases: 17 of (issue(handle) -> ticket, check(), bytes of the table), their device buffers already filled"""
+    assert len(cases) == SLOTS + 1
+    small, big = [c[2] for c in cases[:SLOTS]], cases[SLOTS][2]
+    assert max(small) <= test_gpu_mix.INLINE_BYTES and 2 * max(small) <= FIRST_ALLOCATION < big
+    torch.cuda.synchronize()  # the uploads; from here on nothing waits until every run is enqueued
+    tickets = [issue(handle) for issue, _, _ in cases]
+    assert tickets == list(range(SLOTS + 1)) and tickets[SLOTS] % SLOTS == 0  # run 16 reuses the slot of run 0
+    torch.cuda.synchronize()
+    for k in CHECKED:
+        cases[k][1]()
+    handle.close()
+
+
+def _mix_case(seed, entries):
+    """entries <= 2: ONE cut of that many tracks (the second at an SNR against the first); else that many one-track cuts"""
+    rng = np.random.default_rng(seed)
+    rs = np.random.RandomState(seed)
+    if entries <= 2:
+        cuts = [test_gpu_mix._random_cut(rs, _lengths(rng, 1)[0], [(n, 3, 10.0) for n in _lengths(rng, entries - 1)])]
+    else:
+        cuts = [test_gpu_mix._random_cut(rs, n, []) for n in _lengths(rng, entries)]
+    first, so, sl, do, snrs, refs, chunks, pos = [0], [], [], [], [], [], [], 0
+    for tracks, ref in cuts:
+        for x, o, snr in tracks:
+            so.append(pos), sl.append(len(x)), do.append(int(o)), snrs.append(snr), chunks.append(x)
+            pos += len(x)
+        first.append(len(so)), refs.append(ref)
+    host = np.full(((pos + 3) & ~3) + mixed_tail_floats(first, sl, do), np.nan, dtype=np.float32)
+    host[:pos] = np.concatenate(chunks)
+    arena, where = torch.from_numpy(host).cuda(), []
+
+    def issue(mixer):
+        ticket, offs, lens, info = mixer.plan(first, so, sl, do, snrs, refs, None, pos)
+        assert int(info[1]) <= arena.numel()
+        where.extend(zip(offs.tolist(), lens.tolist()))
+        mixer.run(ticket, arena)
+        return ticket
+
+    def check():
+        got = arena.cpu().numpy()
+        test_gpu_mix._check_against_rule(cuts, [-1] * len(cuts), [got[o : o + n] for o, n in where])
+
+    return issue, check, (len(cuts) + len(so)) * test_gpu_mix.DESCRIPTOR_BYTES
+
+
+def test_mix():
+    cases = [_mix_case(100 + k, n) for k, n in enumerate(RUNS)] + [_mix_case(116, 300)]
+    assert cases[SLOTS][2] == 600 * test_gpu_mix.DESCRIPTOR_BYTES  # 300 cuts + 300 tracks
+    _drive(HipMixer("cuda:0"), cases)
+
+
+def _reverb_case(seed, entries):
+    rng = np.random.default_rng(seed)
+    items = []
+    for k, n in enumerate(_lengths(rng, entries)):
+        taps = int(rng.integers(1, 33))
+        hs, shift = scaled_rir(test_gpu_reverb._rir(rng, taps, int(rng.integers(0, taps))))
+        items.append((rng.standard_normal(n).astype(np.float32) * np.float32(0.1), hs, shift, k % 2 == 0))
+    chunks, so, ro, pos = [], [], [], 0
+    for x, hs, _, _ in items:
+        so.append(pos), chunks.append(x)
+        pos += len(x)
+        ro.append(pos), chunks.append(hs)
+        pos += len(hs)
+    lens = [len(x) for x, _, _, _ in items]
+    host = np.full(((pos + 3) & ~3) + reverb_tail_floats(lens), np.nan, dtype=np.float32)
+    host[:pos] = np.concatenate(chunks)
+    arena, where = torch.from_numpy(host).cuda(), []
+
+    def issue(rv):
+        ticket, offs, info = rv.plan(so, lens, ro, [len(h) for _, h, _, _ in items], [s for _, _, s, _ in items], [int(f) for _, _, _, f in items], pos)
+        assert int(info[1]) <= arena.numel()
+        where.extend(offs.tolist())
+        rv.run(ticket, arena)
+        return ticket
+
+    def check():
+        got = arena.cpu().numpy()
+        for (x, hs, shift, norm), o in zip(items, where):
+            y, truth = got[o : o + len(x)], R.exact(x, hs, shift, norm)
+            bar_rel, bar_max = R.bars(*R.distances(R.fft32(x, hs, shift, norm), truth), truth)
+            rel, mx = R.distances(y, truth)
+            assert np.isfinite(y).all() and rel <= bar_rel and mx <= bar_max, (len(x), len(hs), shift, norm, rel, bar_rel, mx, bar_max)
+
+    return issue, check, entries * test_gpu_reverb.RV_ITEM_BYTES
+
+
+def test_reverb():
+    cases = [_reverb_case(200 + k, n) for k, n in enumerate(RUNS)] + [_reverb_case(216, 342)]
+    _drive(HipReverb("cuda:0"), cases)
+
+
+def _level_case(seed, entries):
+    rng = np.random.default_rng(seed)
+    programs = [[("volume", 0.37)], [("clip", True, -6.0, True)], [("volume", 1.9), ("clip", True, 20.0, True)]]
+    items, so, pos = [], [], 0
+    for k, n in enumerate(_lengths(rng, entries)):
+        pos += 1 + k % 4  # sources at every residue modulo 4
+        so.append(pos)
+        items.append((L.signal(seed * 1000 + k, n), programs[k % 3]))
+        pos += n
+    host = np.full(pos + 5, np.nan, dtype=np.float32)
+    for (x, _), s in zip(items, so):
+        host[s : s + len(x)] = x
+    arena = torch.from_numpy(host).cuda()
+
+    def issue(level):
+        ticket, info = level.plan(so, [len(x) for x, _ in items], [p for _, p in items])
+        assert int(info[1]) <= arena.numel()
+        level.run(ticket, arena)
+        return ticket
+
+    def check():
+        got = arena.cpu().numpy()
+        for (x, prog), s in zip(items, so):
+            assert np.array_equal(got[s : s + len(x)], L.model32(x, prog)), (len(x), prog)
+
+    return issue, check, entries * LEVEL_ITEM_BYTES
+
+
+def test_level():
+    cases = [_level_case(300 + k, n) for k, n in enumerate(RUNS)] + [_level_case(316, 257)]
+    _drive(HipLevel("cuda:0"), cases)
+
+
+def _collate_case(seed, entries):
+    rng = np.random.default_rng(seed)
+    lens, row_len = _lengths(rng, entries), 67
+    offs, pos = [], 0
+    for k, n in enumerate(lens):
+        pos += k % 4
+        offs.append(pos)
+        pos += n
+    host = rng.standard_normal(pos + 5).astype(np.float32)
+    dst = [k % 3 for k in range(entries)]
+    arena, out = torch.from_numpy(host).cuda(), torch.full((entries, row_len), float("nan"), dtype=torch.float32, device="cuda:0")
+
+    def issue(collator):
+        ticket, info = collator.plan(offs, lens, dst, row_len, torch.float32)
+        assert int(info[1]) <= arena.numel() and int(info[2]) == out.numel()
+        collator.run(ticket, arena, out)
+        return ticket
+
+    def check():
+        assert np.array_equal(bits_of(out.cpu()), bits_of(collate_ref(host, offs, lens, row_len, dst, torch.float32)))
+
+    return issue, check, entries * COLLATE_ROW_BYTES
+
+
+def test_collate():
+    cases = [_collate_case(400 + k, n) for k, n in enumerate(RUNS)] + [_collate_case(416, 513)]
+    _drive(HipCollator("cuda:0"), cases)
+
+
+def _sinc_case(seed, entries):
+    rng = np.random.default_rng(seed)
+    rows = [(rng.random(n).astype(np.float32) - np.float32(0.5), test_gpu_sinc.WEIGHT_RATES[k % 2]) for k, n in enumerate(_lengths(rng, entries))]
+    in_off, pos = [], 5
+    for k, (x, _) in enumerate(rows):
+        pos += (k % 4 - pos) % 4
+        in_off.append(pos)
+        pos += len(x) + 3
+    out_len = [SR.resampled_length(len(x), *SR.geometry(*r)[:2]) for x, r in rows]
+    out_off = []
+    for k, n in enumerate(out_len):
+        pos += ((k + 1) % 4 - pos) % 4
+        out_off.append(pos)
+        pos += n + 3
+    host = np.full(pos + 64, test_gpu_sinc.FILL, dtype=np.float32)
+    for o, (x, _) in zip(in_off, rows):
+        host[o : o + len(x)] = x
+    arena = torch.from_numpy(host).cuda()
+
+    def issue(sinc):
+        ticket, planned, info = sinc.plan(in_off, [len(x) for x, _ in rows], [r for _, r in rows], out_off, arena.numel())
+        assert planned.tolist() == out_len and info[1] <= arena.numel()
+        sinc.run(ticket, arena)
+        return ticket
+
+    def check():
+        got = arena.cpu().numpy()
+        for (x, r), o, n in zip(rows, out_off, out_len):
+            assert np.abs(got[o : o + n] - SR.resample(x, *r, filt=test_gpu_sinc.filt(r))).max() <= test_gpu_sinc.ABS_TOL, (len(x), r)
+
+    return issue, check, entries * SINC_ROW_BYTES
+
+
+def test_sinc():
+    cases = [_sinc_case(500 + k, n) for k, n in enumerate(RUNS)] + [_sinc_case(516, 257)]
+    _drive(HipSincResampler("cuda:0"), cases)
