@@ -41,8 +41,10 @@ extern "C" {
 #define HIPFEAT_API
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
- * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES and _SINC_SIGNATURES next to _SIGNATURES). */
+ * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES, _SINC_SIGNATURES and
+ * _FEATMIX_SIGNATURES next to _SIGNATURES). */
 #define HIPFEAT_COLLATE_API HIPFEAT_API
+#define HIPFEAT_FEATMIX_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
 #define HIPFEAT_SINC_API HIPFEAT_API
 
@@ -503,6 +505,66 @@ HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_plan(hipfeat_sinc* sinc, int64_t nu
 HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sinc, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
 HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_weights(hipfeat_sinc* sinc, int32_t src_rate, int32_t dst_rate, float* d_weights, int32_t* d_first,
                                                      int32_t* h_dims, void* stream);
+
+/* ---- stored features mixed and collated on the device (additive to ABI v8) -------------------------------------------- */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_featmix_*; as with hipfeat_level_* and hipfeat_collate_*, the version number
+ * did not change because nothing that existed changed.
+ *
+ * PrecomputedFeatures.__call__ -> collate_features (lhotse/dataset/collation.py:115-145) pads every cut of a mini-batch (cuts.pad) and
+ * fills row c of a (B, max num_frames, F) float32 tensor with cut.load_features(), cut by cut on the host.  For a MixedCut that call
+ * (lhotse/cut/mixed.py:1199-1309) loads every track and runs FeatureMixer (lhotse/features/mixer.py) with Fbank.mix / Fbank.compute_energy
+ * (lhotse/features/kaldi/extractors.py:135-152).  Here the tracks of the whole mini-batch lie in ONE device arena AS THEY WERE STORED
+ * (float32 or binary16) and two stream-ordered launches -- sum(exp(x)) per track that needs one, then the fold and the padded batch --
+ * write the (num_cuts, row_frames, F) tensor; no value visits the host in between, no memset, no intermediate matrix.
+ * EPSILON = 1e-10 (lhotse.utils).  A cut has one of two forms:
+ *   COPY (form 0; mixed.py:1223-1243: a plain cut, or one cut with PaddingCuts behind it): ONE track; the cut's first h_frames frames are
+ *     bit copies of the track (binary16 widened exactly; a constant track: (float)h_value), its other frames (float)h_pad_value.
+ *   FOLD (form 1; mixed.py:1245-1307): tracks t = 0 ... K-1 in order; track t is a matrix x_t of n_t = h_frames frames (or a constant
+ *     matrix, a PaddingCut) that starts at frame o_t = h_first (compute_num_frames(track.offset, frame_shift, sampling_rate)).
+ *     N = max_t(o_t + n_t); a frame a track does not cover holds the mixer's padding value -1000, whose exp is 0.
+ *     S(x) = sum(exp(x)) over a track's own frames, in float64.  E_ref = S(x_ref), ref = h_ref_track (_get_snr_reference_track,
+ *     mixed.py:1909-1918).  Gains: a track with an SNR (track 0 only when the reference is another track; _scale_features_for_snr,
+ *     mixed.py:1945-1957; mixer.py:168-175) gets g_t = (float)(E_ref * 10^(-snr_t/10) / S(x_t)) when E_ref > 0 and S(x_t) > 0, every
+ *     other track and every other case g_t = 1.
+ *     Per frame and bin, float32: e = g_0 * exp(x_0); for t = 1 ... K-1 in order: e = max(EPSILON, e + g_t * exp(x_t)) -- the floor
+ *     after EVERY track over ALL N frames (a frame only a later track covers already holds 1e-10 when that track arrives; a tail two
+ *     paddings cover ends at log(2e-10)); a track t >= 1 of no frames is not mixed at all (mixer.py:116-117).  out = log(e), taken once.
+ *     N - h_num_frames == +1: the last frame is dropped; == -1: the last frame is repeated (mixed.py:1294-1300).
+ *   The MonoCut fix-up (lhotse/cut/mono.py:61-64) is per track: h_src_rows stored rows stand for h_frames frames; one row too many is
+ *   not read, one too few repeats the last row (energies are those of the fixed-up matrix).
+ *   The cut's h_num_frames frames go to frames [h_dst_first, h_dst_first + h_num_frames) of row c; every other element of the row is
+ *   (float)log(1e-10).  Results are bit-identical from run to run and a cut's row does not depend on the other cuts of the batch.
+ *
+ * hipfeat_featmix_create / _destroy: the object that owns the workspace (staged tables, partial sums) on `device`; calls are serialised
+ * inside, up to 16 plans may be outstanding, destroy waits for the work it enqueued.
+ * hipfeat_featmix_plan (host only): the tracks of cut c are [h_track_first[c], h_track_first[c + 1]) of the track tables
+ * (h_track_first[0] = 0; 1 ... 256 tracks per cut, exactly 1 in the copy form).  Per cut: h_form, h_num_frames, h_pad_value (may be NULL:
+ * 0), h_dst_first (may be NULL: 0), h_ref_track = the SNR reference as an index WITHIN the cut, -1 = none (may be NULL).  Per track:
+ * h_src_offset = BYTE offset of its first stored value in the arena (a multiple of 4 for float32, of 2 for binary16), -1 = a constant
+ * track; h_src_rows (may be NULL: h_frames); h_frames; h_dtype 0 = float32, 1 = binary16 (may be NULL: float32); h_first (may be NULL: 0);
+ * h_snr_db, NaN = none (may be NULL); h_value of constant tracks (may be NULL: 0).  num_features = F >= 1 (any value); row_frames = the
+ * frames of one row of `out`.  h_info[4] = {ticket, bytes the arena must hold, energy work items, fold work items}.
+ * A bad table (a negative or misaligned offset, frames that do not fit the row, h_src_rows further than one from h_frames, a mix whose
+ * length is further than one from h_num_frames, a reference index outside the cut, an unknown form or type, a copy form with more than one
+ * track, a 17th plan while 16 are planned and not yet run) returns HIPFEAT_ERR_INVALID, more than 256 tracks in a cut
+ * HIPFEAT_ERR_UNSUPPORTED, and plans nothing.
+ * hipfeat_featmix_run enqueues the two launches of a planned feature mix on `stream` (a ticket runs once; the energy launch is left out
+ * when no track needs an energy).  An unknown ticket, arena_bytes < h_info[1], out_elements < num_cuts * row_frames * F, or an `out`
+ * that overlaps the arena: HIPFEAT_ERR_INVALID, and nothing is launched.  The arena starts on a 16-byte boundary, `out` on a 4-byte one.
+ * A ticket is consumed when its launches have been enqueued: after a HIPFEAT_ERR_HIP from an allocation or the table copy in front of
+ * them, it can be run again.
+ */
+typedef struct hipfeat_featmix hipfeat_featmix;
+HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_create(int32_t device, hipfeat_featmix** featmix);
+HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_destroy(hipfeat_featmix* featmix);
+HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_plan(hipfeat_featmix* featmix, int64_t num_cuts, const int64_t* h_track_first, const int32_t* h_form,
+                                                        const int64_t* h_num_frames, const double* h_pad_value, const int64_t* h_dst_first,
+                                                        const int32_t* h_ref_track, const int64_t* h_src_offset, const int64_t* h_src_rows,
+                                                        const int64_t* h_frames, const int32_t* h_dtype, const int64_t* h_first, const double* h_snr_db,
+                                                        const double* h_value, int64_t num_features, int64_t row_frames, int64_t* h_info);
+HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmix* featmix, int64_t ticket, const void* d_arena, int64_t arena_bytes, float* d_out,
+                                                       int64_t out_elements, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

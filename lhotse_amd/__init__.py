@@ -31,7 +31,8 @@ from .kaldifeat import (  # noqa: F401,E402
     HipKaldifeatMfccConfig,
 )
 
-from .input_strategies import FusedAudioBatch, HipAudioSamples, HipOnTheFlyFeatures  # noqa: F401,E402
+from .input_strategies import FusedAudioBatch, FusedFeatureBatch, HipAudioSamples, HipOnTheFlyFeatures, HipPrecomputedFeatures  # noqa: F401,E402
+from .augmentation import FeatCut, FeatTrack, HipFeatureMixer, featmix_in_arena, featmix_layout, get_or_create_featmixer  # noqa: F401,E402
 
 from .whisper import HipWhisperFbank, HipWhisperFbankConfig  # noqa: F401,E402
 
@@ -89,6 +90,14 @@ __all__ = [
     "left_pad_offsets",
     "FusedAudioBatch",
     "HipAudioSamples",
+    "FusedFeatureBatch",
+    "HipPrecomputedFeatures",
+    "HipFeatureMixer",
+    "FeatCut",
+    "FeatTrack",
+    "featmix_in_arena",
+    "featmix_layout",
+    "get_or_create_featmixer",
     "resample_in_arena",
     "HipSincResampler",
     "get_or_create_sinc",

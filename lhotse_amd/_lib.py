@@ -153,7 +153,19 @@ _SINC_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     "hipfeat_sinc_run": ("int", ["hipfeat_sinc*", "int64_t", "float*", "int64_t", "void*"]),
     "hipfeat_sinc_weights": ("int", ["hipfeat_sinc*", "int32_t", "int32_t", "float*", "int32_t*", "int32_t*", "void*"]),
 }
-_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES}
+# Likewise (HIPFEAT_FEATMIX_API in the header).
+_FEATMIX_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_featmix_create": ("int", ["int32_t", "hipfeat_featmix**"]),
+    "hipfeat_featmix_destroy": ("int", ["hipfeat_featmix*"]),
+    "hipfeat_featmix_plan": (
+        "int",
+        ["hipfeat_featmix*", "int64_t", "const int64_t*", "const int32_t*", "const int64_t*", "const double*", "const int64_t*", "const int32_t*",
+         "const int64_t*", "const int64_t*", "const int64_t*", "const int32_t*", "const int64_t*", "const double*", "const double*", "int64_t", "int64_t",
+         "int64_t*"],
+    ),
+    "hipfeat_featmix_run": ("int", ["hipfeat_featmix*", "int64_t", "const void*", "int64_t", "float*", "int64_t", "void*"]),
+}
+_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -244,7 +256,8 @@ class _CffiBackend:
             s = line.strip()
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
-            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", ""))
+            decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
+                        .replace("HIPFEAT_FEATMIX_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

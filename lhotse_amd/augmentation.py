@@ -19,7 +19,7 @@ from __future__ import annotations
 import threading
 from dataclasses import asdict, dataclass
 from decimal import ROUND_HALF_DOWN, ROUND_HALF_UP, Decimal
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -1158,3 +1158,190 @@ def collate_in_arena(arena: torch.Tensor, offsets, lengths, row_len: Optional[in
     ticket, info = collator.plan(so, sl, None if dst_offsets is None else do, row_len, dtype)
     collator.run(ticket, arena, res)
     return res, sl
+
+
+# ---- stored features: the tracks of a mini-batch mixed and collated as ONE (B, row_frames, F) tensor ---------------------------
+FEATMIX_TILE = 4096  # output elements per work item of the fold launch (kFmTile)
+FEATMIX_ENERGY_BLOCK = 16384  # track elements per work item of the energy launch (kFmEnergyBlock)
+FEATMIX_MAX_TRACKS = 256  # tracks of one cut (kFmMaxTracks)
+FEATMIX_COPY, FEATMIX_FOLD = 0, 1
+_FEATMIX_MAX_ROW = (2 ** 31 - 1) // 2  # elements of one row and of one track
+
+
+class FeatTrack(NamedTuple):
+    """One track of a cut of stored features: ``rows`` stored rows of F values at BYTE ``offset`` of the arena (-1: a constant matrix of
+    ``value``, a PaddingCut) that stand for ``frames`` frames (``rows=None``: as many; one more or one less is the MonoCut fix-up,
+    lhotse/cut/mono.py:61-64) from frame ``first`` of the cut on; ``f16``: stored as binary16; ``snr``: dB, None = none."""
+
+    offset: int
+    frames: int
+    rows: Optional[int] = None
+    f16: bool = False
+    first: int = 0
+    snr: Optional[float] = None
+    value: float = 0.0
+
+
+class FeatCut(NamedTuple):
+    """One cut of the mini-batch: ``form`` FEATMIX_COPY (ONE track, ``pad_value`` behind it; lhotse/cut/mixed.py:1223-1243) or
+    FEATMIX_FOLD (the FeatureMixer fold of the tracks, mixed.py:1245-1307); its ``num_frames`` frames go to frames ``[dst_first,
+    dst_first + num_frames)`` of its row; ``ref_track``: the SNR reference as an index within ``tracks``, -1 = none."""
+
+    tracks: Sequence[FeatTrack]
+    num_frames: int
+    form: int = FEATMIX_COPY
+    pad_value: float = 0.0
+    dst_first: int = 0
+    ref_track: int = -1
+
+
+def featmix_layout(arena_bytes: int, cuts_table: Sequence[FeatCut], F: int, row_frames: Optional[int] = None) -> dict:
+    """The host arithmetic of ``featmix_in_arena``: the tables of ``hipfeat_featmix_plan`` as C-contiguous arrays (keys named like its
+    arguments, plus ``num_features`` and ``row_frames``; ``row_frames=None``: the longest ``dst_first + num_frames``).  Raises
+    ``ValueError`` for what no launch could serve, before anything is planned."""
+    F = int(F)
+    if F < 1 or F > _FEATMIX_MAX_ROW:
+        raise ValueError(f"featmix: {F} features per frame")
+    cuts = [c if isinstance(c, FeatCut) else FeatCut(*c) for c in cuts_table]
+    if not 1 <= len(cuts) <= 65535:
+        raise ValueError(f"featmix: {len(cuts)} cuts (1 ... 65535)")
+    if row_frames is None:
+        row_frames = max(int(c.dst_first) + int(c.num_frames) for c in cuts)
+    row_frames = int(row_frames)
+    if row_frames < 0 or row_frames * F > _FEATMIX_MAX_ROW:
+        raise ValueError(f"featmix: a row of {row_frames} frames of {F} features is out of range")
+    max_frames = _FEATMIX_MAX_ROW // F
+    first, form, frames_c, pad, dst, ref = [0], [], [], [], [], []
+    so, rows, frames, dtype, start, snr, value = [], [], [], [], [], [], []
+    need = 0
+    for ci, c in enumerate(cuts):
+        trs = [t if isinstance(t, FeatTrack) else FeatTrack(*t) for t in c.tracks]
+        if not trs:
+            raise ValueError(f"featmix: cut {ci} has no track")
+        if len(trs) > FEATMIX_MAX_TRACKS:
+            raise ValueError(f"featmix: cut {ci} has {len(trs)} tracks, the launch serves up to {FEATMIX_MAX_TRACKS} per cut")
+        if c.form not in (FEATMIX_COPY, FEATMIX_FOLD):
+            raise ValueError(f"featmix: cut {ci}: unknown form {c.form!r}")
+        T, d0, r = int(c.num_frames), int(c.dst_first), int(c.ref_track)
+        if T < 0 or d0 < 0 or d0 + T > row_frames:
+            raise ValueError(f"featmix: cut {ci}: {T} frames at frame {d0} do not fit a row of {row_frames}")
+        if not -1 <= r < len(trs):
+            raise ValueError(f"featmix: cut {ci}: reference track {r} of {len(trs)}")
+        if c.form == FEATMIX_COPY and len(trs) != 1:
+            raise ValueError(f"featmix: cut {ci}: the copy form takes one track, got {len(trs)}")
+        total = 0
+        for ti, t in enumerate(trs):
+            off, n, o = int(t.offset), int(t.frames), int(t.first)
+            const = off == -1
+            nr = n if const or t.rows is None else int(t.rows)
+            if off < -1 or o < 0:
+                raise ValueError(f"featmix: cut {ci}, track {ti}: negative offset")
+            if n < 0 or n > max_frames or o + n > max_frames:
+                raise ValueError(f"featmix: cut {ci}, track {ti}: {n} frames at frame {o} out of range")
+            if abs(nr - n) > 1 or (n > 0 and nr < 1):
+                raise ValueError(f"featmix: cut {ci}, track {ti}: {nr} stored rows for {n} frames (one more or one less at the most)")
+            esz = 2 if t.f16 else 4
+            if not const and off % esz:
+                raise ValueError(f"featmix: cut {ci}, track {ti}: byte offset {off} is not aligned to the track's type")
+            scaled = c.form == FEATMIX_FOLD and t.snr is not None and not np.isnan(t.snr) and r >= 0 and not (ti == 0 and r == 0)
+            if scaled and -float(t.snr) / 10.0 > 308.0:  # (10^(-snr/10) is not finite)
+                raise ValueError(f"featmix: cut {ci}, track {ti}: SNR {t.snr} dB out of range")
+            if not const and n > 0:
+                need = max(need, off + min(nr, n) * F * esz)
+            if n > 0 or ti == 0:
+                total = max(total, o + n)
+            so.append(off), rows.append(nr), frames.append(n), dtype.append(1 if t.f16 else 0), start.append(o)
+            snr.append(np.nan if t.snr is None else float(t.snr)), value.append(float(t.value))
+        if c.form == FEATMIX_COPY:
+            if start[-1] != 0:
+                raise ValueError(f"featmix: cut {ci}: the track of the copy form starts at frame 0")
+            if total > T:
+                raise ValueError(f"featmix: cut {ci}: a track of {total} frames does not fit a cut of {T}")
+        elif abs(total - T) > 1 or (T > 0 and total < 1):
+            raise ValueError(f"featmix: cut {ci}: the tracks mix to {total} frames, the cut has {T} (one more or one less at the most)")
+        first.append(first[-1] + len(trs)), form.append(int(c.form)), frames_c.append(T), pad.append(float(c.pad_value)), dst.append(d0), ref.append(r)
+    if need > int(arena_bytes):
+        raise ValueError(f"arena too small: {int(arena_bytes)} bytes, the tracks reach to {need}")
+    return {
+        "h_track_first": _lib.i64(first), "h_form": np.ascontiguousarray(form, dtype=np.int32), "h_num_frames": _lib.i64(frames_c),
+        "h_pad_value": np.ascontiguousarray(pad, dtype=np.float64), "h_dst_first": _lib.i64(dst), "h_ref_track": np.ascontiguousarray(ref, dtype=np.int32),
+        "h_src_offset": _lib.i64(so), "h_src_rows": _lib.i64(rows), "h_frames": _lib.i64(frames), "h_dtype": np.ascontiguousarray(dtype, dtype=np.int32),
+        "h_first": _lib.i64(start), "h_snr_db": np.ascontiguousarray(snr, dtype=np.float64), "h_value": np.ascontiguousarray(value, dtype=np.float64),
+        "num_features": F, "row_frames": row_frames, "arena_need": need,
+    }
+
+
+_FEATMIX_ARGS = ("h_track_first", "h_form", "h_num_frames", "h_pad_value", "h_dst_first", "h_ref_track", "h_src_offset", "h_src_rows", "h_frames", "h_dtype",
+                 "h_first", "h_snr_db", "h_value")
+
+
+class HipFeatureMixer(_ArenaHandle):
+    """The device half of ``collate_features`` (lhotse/dataset/collation.py:115-145) over ``MixedCut.load_features``
+    (lhotse/cut/mixed.py:1199-1309) for the stored tracks of a mini-batch: ``hipfeat_featmix`` (include/hipfeat.h) owns the workspace of
+    the two launches -- track energies, then the fold and the padded batch.  One object per device (``get_or_create_featmixer``); it may
+    be shared by threads."""
+
+    _KIND = "featmix"  # hipfeat_featmix_create / _destroy
+
+    def plan(self, layout: dict):
+        """Host only: ``layout`` as ``featmix_layout`` returns it -> (ticket, info = [ticket, arena bytes needed, energy items, fold items])."""
+        info = np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_featmix_plan", self.handle, len(layout["h_form"]), *(_lib.addr(layout[k]) for k in _FEATMIX_ARGS),
+                           int(layout["num_features"]), int(layout["row_frames"]), _lib.addr(info))
+        return int(info[0]), info
+
+    def run(self, ticket: int, arena: torch.Tensor, out: torch.Tensor, stream: Optional[int] = None) -> None:
+        assert arena.dtype == torch.uint8 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device
+        with torch.cuda.device(self.device):
+            self.lib.check("hipfeat_featmix_run", self.handle, int(ticket), arena.data_ptr(), arena.numel(), out.data_ptr(), out.numel(),
+                           int(_raw_stream(arena.device) if stream is None else stream))
+
+
+_featmixers: Dict[int, HipFeatureMixer] = {}
+
+
+def get_or_create_featmixer(device: Union[str, torch.device, None] = None) -> HipFeatureMixer:
+    return _get_or_create(_featmixers, HipFeatureMixer, _cache_lock, device)
+
+
+def featmix_in_arena(arena_bytes: torch.Tensor, cuts_table: Sequence[FeatCut], F: int, row_frames: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None, mixer: Optional[HipFeatureMixer] = None,
+                     layout: Optional[dict] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """The stored feature tracks of a mini-batch as ONE padded ``(B, row_frames, F)`` float32 tensor: what ``collate_features``
+    (lhotse/dataset/collation.py:115-145) returns for cuts with precomputed features, ``CutMix`` / ``.pad`` included
+    (``MixedCut.load_features``, lhotse/cut/mixed.py:1199-1309; ``FeatureMixer``, lhotse/features/mixer.py).
+
+    ``arena_bytes`` is ONE uint8 device buffer that holds every track as it was stored (float32 rows at 4-byte, binary16 rows at 2-byte
+    boundaries); ``cuts_table`` one ``FeatCut`` per cut.  ``row_frames=None``: the longest cut.  ``out``: a contiguous float32 tensor on
+    the arena's device with at least ``B * row_frames * F`` elements that does not overlap the arena.  Returns ``(out (B, row_frames, F),
+    num_frames as int32 numpy)``.  Two launches on the current stream, no memset, no device -> host copy, bit-identical from run to run.
+    ``layout``: what ``featmix_layout`` returned for this very table, ``F`` and ``row_frames``, for a caller that has it already."""
+    assert arena_bytes.dtype == torch.uint8 and arena_bytes.is_contiguous() and arena_bytes.ndim == 1
+    if layout is None:
+        lay = featmix_layout(arena_bytes.numel(), cuts_table, F, row_frames)  # (before anything is planned)
+    else:
+        lay = layout
+        if lay["arena_need"] > arena_bytes.numel():
+            raise ValueError(f"arena too small: {arena_bytes.numel()} bytes, the tracks reach to {lay['arena_need']}")
+    B, T, F = len(lay["h_form"]), lay["row_frames"], lay["num_features"]
+    if out is not None:
+        if out.dtype != torch.float32 or out.device != arena_bytes.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor on {arena_bytes.device}")
+        if out.numel() < B * T * F:
+            raise ValueError(f"out too small: {out.numel()} elements, {B} rows of {T} x {F} take {B * T * F}")
+        a0, o0 = arena_bytes.data_ptr(), out.data_ptr()
+        if a0 < o0 + out.numel() * 4 and o0 < a0 + arena_bytes.numel():  # (a plan that is never run would stay outstanding)
+            raise ValueError("out overlaps the arena")
+        res = out.view(-1)[: B * T * F].view(B, T, F)
+    else:
+        res = torch.empty((B, T, F), dtype=torch.float32, device=arena_bytes.device)
+    lens = lay["h_num_frames"].astype(np.int32)
+    if B * T * F == 0:
+        return res, lens
+    if mixer is None:
+        mixer = get_or_create_featmixer(arena_bytes.device)
+    ticket, _ = mixer.plan(lay)
+    mixer.run(ticket, arena_bytes, res)
+    return res, lens

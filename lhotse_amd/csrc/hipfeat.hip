@@ -29,6 +29,7 @@
 #include "kernel_mix.hpp"
 #include "kernel_reverb.hpp"
 #include "kernel_collate.hpp"
+#include "kernel_featmix.hpp"
 #include "kernel_level.hpp"
 #include "kernel_sinc.hpp"
 #include "kernel_specaug.hpp"
@@ -1853,6 +1854,7 @@ struct hipfeat_reverb : TicketedHandle<RvPlan> {};
 struct hipfeat_level : TicketedHandle<LvPlan> {};
 struct hipfeat_collate : TicketedHandle<CoPlan> {};
 struct hipfeat_sinc : TicketedHandle<SincPlan> {};
+struct hipfeat_featmix : TicketedHandle<FmPlan> {};
 
 template <typename H>
 static hipfeat_status handle_create(int32_t device, H** out, const char* what) {
@@ -2581,6 +2583,88 @@ extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_weights(hipfeat_sinc* sc
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "sinc weights launch failed: %s", hipGetErrorName(e));
   return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Stored features mixed and collated on the device (PrecomputedFeatures + CutMix / .pad): energies, then the fold and the padded
+// batch, in two launches (kernel_featmix.hpp; the tables: featmix_tables.hpp)
+// --------------------------------------------------------------------------------------
+extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_create(int32_t device, hipfeat_featmix** out) { return handle_create(device, out, "featmix"); }
+extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_destroy(hipfeat_featmix* fm) { return handle_destroy(fm); }
+
+extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_plan(hipfeat_featmix* fm, int64_t num_cuts, const int64_t* h_track_first, const int32_t* h_form,
+                                                                   const int64_t* h_num_frames, const double* h_pad_value, const int64_t* h_dst_first,
+                                                                   const int32_t* h_ref_track, const int64_t* h_src_offset, const int64_t* h_src_rows,
+                                                                   const int64_t* h_frames, const int32_t* h_dtype, const int64_t* h_first, const double* h_snr_db,
+                                                                   const double* h_value, int64_t num_features, int64_t row_frames, int64_t* h_info) {
+  if (!fm || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  // (validated into a local first: a refused table leaves the outstanding plans as they were)
+  FmPlan p = build_featmix_plan(num_cuts, h_track_first, h_form, h_num_frames, h_pad_value, h_dst_first, h_ref_track, h_src_offset, h_src_rows, h_frames, h_dtype,
+                                h_first, h_snr_db, h_value, num_features, row_frames);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(fm->mu);
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(fm->tickets, "feature mixes", &ticket)) return st;
+  const FmPlan& s = fm->plans[ticket % kTicketSlots] = std::move(p);
+  h_info[0] = ticket;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.energy_items;
+  h_info[3] = s.fold_items;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmix* fm, int64_t ticket, const void* d_arena, int64_t arena_bytes, float* d_out,
+                                                                  int64_t out_elements, void* stream) {
+  if (!fm) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(fm->mu);
+  const int slot = find_ticket(fm->tickets, ticket, "feature mix");
+  if (slot < 0) return HIPFEAT_ERR_INVALID;
+  const FmPlan& p = fm->plans[slot];
+  StagedSlot& s = fm->slots[slot];  // device: the staged tables, then the partial sums
+  if (arena_bytes < p.arena_need)
+    return fail(HIPFEAT_ERR_INVALID, "arena holds %lld bytes, the tracks reach to %lld", (long long)arena_bytes, (long long)p.arena_need);
+  if (out_elements < p.out_need)
+    return fail(HIPFEAT_ERR_INVALID, "out holds %lld elements, the batch takes %lld", (long long)out_elements, (long long)p.out_need);
+  if (p.fold_items == 0) {  // rows of no frames: no launch
+    fm->tickets.release(ticket);
+    return HIPFEAT_OK;
+  }
+  if (!d_out || (!d_arena && p.arena_need > 0)) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
+  if (reinterpret_cast<uintptr_t>(d_out) & 3) return fail(HIPFEAT_ERR_INVALID, "out must be aligned to its element size");
+  {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_arena), a1 = a0 + (uintptr_t)arena_bytes;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)out_elements * 4;
+    if (a0 < o1 && o0 < a1) return fail(HIPFEAT_ERR_INVALID, "out overlaps the arena");
+  }
+  DeviceGuard g(fm->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cut_bytes = p.cuts.size() * sizeof(FmCut), trk_bytes = p.tracks.size() * sizeof(FmTrack), bytes = cut_bytes + trk_bytes;  // (multiples of 16)
+  const size_t part_bytes = (size_t)std::max<int64_t>(p.energy_items, 1) * sizeof(double);
+  HIP_TRY(s.wait());
+  HIP_TRY(s.reserve(bytes + part_bytes));
+  std::memcpy(s.h, p.cuts.data(), cut_bytes);
+  std::memcpy(static_cast<unsigned char*>(s.h) + cut_bytes, p.tracks.data(), trk_bytes);
+  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+  FmArgs a;
+  a.arena = static_cast<const unsigned char*>(d_arena);
+  a.out = d_out;
+  a.cuts = static_cast<const FmCut*>(s.d);
+  a.tracks = reinterpret_cast<const FmTrack*>(static_cast<const unsigned char*>(s.d) + cut_bytes);
+  a.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(s.d) + bytes);
+  a.row_len = p.row_len;
+  a.tiles_per_row = p.tiles_per_row;
+  a.fold_items = p.fold_items;
+  a.num_cuts = (int32_t)p.cuts.size();
+  a.num_tracks = (int32_t)p.tracks.size();
+  a.energy_items = (int32_t)p.energy_items;
+  a.num_features = (int32_t)p.num_features;
+  a.log_eps = (float)std::log(1e-10);
+  a.pad = 0;
+  if (p.energy_items > 0) hipLaunchKernelGGL(featmix_energy_kernel, dim3(items_grid(p.energy_items)), dim3(256), 0, st, a);
+  // a flat 1-D grid over (cut, tile); beyond 2^22 workgroups (2^34 elements) the workgroups stride
+  hipLaunchKernelGGL(featmix_fold_kernel, dim3((unsigned)std::min<int64_t>(p.fold_items, (int64_t)1 << 22)), dim3(256), 0, st, a);
+  return finish_run(fm->tickets, ticket, s, st, hipGetLastError(), "feature mix", kWaitedLaunches);
 }
 
 // ---- bulk save path: per-batch host work of the offline driver (host_bulk.hpp) -------------------------------------------------

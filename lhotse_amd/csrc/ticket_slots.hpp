@@ -1,4 +1,4 @@
-// The tickets of the ticketed handles (hipfeat_mixer, hipfeat_reverb, hipfeat_level, hipfeat_collate, hipfeat_sinc): a plan hands out
+// The tickets of the ticketed handles (hipfeat_mixer, hipfeat_reverb, hipfeat_level, hipfeat_collate, hipfeat_sinc, hipfeat_featmix): a plan hands out
 // a ticket, a run consumes it.  Up to kTicketSlots plans may be outstanding; ticket t lives in slot t % kTicketSlots, and a plan is
 // refused while the slot its ticket would take still holds one that has not run.
 // Pure C++ (no HIP): also compiled by tests/native/collate_tables_capi.cpp and checked on the CPU (tests/test_collate_abi.py).

@@ -569,10 +569,105 @@ class FusedAudioBatch(_ArenaChain):
             return self._collated(arena, cut_off, cut_len, wants)
 
 
+
+def _featmix_in_arena(arena_bytes, cuts_table, num_features, row_frames, layout=None):
+    from . import augmentation as A
+
+    return A.featmix_in_arena(arena_bytes, cuts_table, num_features, row_frames, layout=layout)
+
+
+class FusedFeatureBatch:
+    """The mini-batch of the PRECOMPUTED-features recipe on the device: the stored tracks of every cut go into ONE byte arena as they
+    were stored (binary16 stays binary16: half the bytes over PCIe), and the two launches of ``lhotse_amd.augmentation.featmix_in_arena``
+    write the padded ``(B, T, F)`` float32 batch -- copies for plain and right-padded cuts, the ``FeatureMixer`` fold (``CutMix``, left /
+    both-sided padding) for the rest.  No lhotse type in its interface.
+
+    A CUT is a dict ``{"form": FEATMIX_COPY | FEATMIX_FOLD, "num_frames", "pad_value", "ref_track", "tracks"}`` (``"dst_first"``
+    optional), a TRACK a dict ``{"frames", "first", "snr", "value"}`` plus its source: ``"array"`` (a loaded ``(rows, F)`` float32 or
+    float16 matrix), or ``"read"`` with ``"rows"`` and ``"f16"`` (``read(out)`` fills the C-contiguous uint8 view ``out`` of ``rows * F *
+    itemsize`` bytes, e.g. ``reader.read_raw(key, lo, hi, out=out)``), or neither: a constant track of ``value``."""
+
+    _ALIGN = 16  # every track starts on a 16-byte boundary of the arena
+
+    def __init__(self, device: Union[str, torch.device, None] = None) -> None:
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type == "cuda" and dev.index is None and torch.cuda.is_available():
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self._staging: Optional[torch.Tensor] = None  # page-locked where a GPU is there
+        self._uploaded = None  # the event behind the upload that read the staging buffer last
+
+    def _stage(self, nbytes: int) -> torch.Tensor:
+        if self._uploaded is not None:  # the previous batch's upload has read the buffer
+            self._uploaded.synchronize()
+            self._uploaded = None
+        if self._staging is None or self._staging.numel() < nbytes:
+            pin = self.device.type == "cuda" and torch.cuda.is_available()
+            self._staging = torch.empty(max(2 * nbytes, 1 << 16), dtype=torch.uint8, pin_memory=pin)
+        return self._staging
+
+    def features_of(self, cuts: List[dict], num_features: int, row_frames: Optional[int] = None, pool=None):
+        """-> ``(features (B, row_frames, F) float32 on the device, features_lens int32)``; ``row_frames=None``: the longest cut.
+        ``pool``: a thread pool for the reads."""
+        from .augmentation import FeatCut, FeatTrack
+
+        F = int(num_features)
+        table, jobs, pos = [], [], 0
+        for c in cuts:
+            tracks = []
+            for t in c["tracks"]:
+                arr, read = t.get("array"), t.get("read")
+                if arr is None and read is None:
+                    tracks.append(FeatTrack(-1, int(t["frames"]), None, False, int(t.get("first", 0)), t.get("snr"), float(t.get("value", 0.0))))
+                    continue
+                if arr is not None:
+                    arr = np.ascontiguousarray(arr)
+                    if arr.ndim != 2 or arr.shape[1] != F or arr.dtype not in (np.float32, np.float16):
+                        raise ValueError(f"FusedFeatureBatch: a track is a (rows, {F}) float32 or float16 matrix, got {arr.dtype} {arr.shape}")
+                    rows, f16 = arr.shape[0], arr.dtype == np.float16
+                else:
+                    rows, f16 = int(t["rows"]), bool(t["f16"])
+                nbytes = rows * F * (2 if f16 else 4)
+                jobs.append((pos, nbytes, arr, read))
+                tracks.append(FeatTrack(pos, int(t["frames"]), rows, f16, int(t.get("first", 0)), t.get("snr"), 0.0))
+                pos += -(-nbytes // self._ALIGN) * self._ALIGN
+            table.append(FeatCut(tracks, int(c["num_frames"]), int(c["form"]), float(c.get("pad_value", 0.0)), int(c.get("dst_first", 0)),
+                                 int(c.get("ref_track", -1))))
+        from .augmentation import featmix_layout
+
+        layout = featmix_layout(max(pos, 1), table, F, row_frames)  # (ValueError before anything is read; the launches take it as it is)
+        total = max(pos, self._ALIGN)
+        host = self._stage(total).numpy()
+
+        def fill(job):
+            at, nbytes, arr, read = job
+            out = host[at: at + nbytes]
+            if arr is not None:
+                out[:] = arr.reshape(-1).view(np.uint8)
+            elif nbytes:
+                read(out)
+
+        if pool is not None and len(jobs) > 1:
+            list(pool.map(fill, jobs))
+        else:
+            for j in jobs:
+                fill(j)
+        with torch.no_grad():
+            arena = torch.empty(total, dtype=torch.uint8, device=self.device)
+            arena.copy_(self._staging[:total], non_blocking=True)
+            if self.device.type == "cuda":
+                self._uploaded = torch.cuda.Event()
+                self._uploaded.record()
+            feats, lens = _featmix_in_arena(arena, table, F, row_frames, layout)
+        return feats, torch.from_numpy(np.asarray(lens, dtype=np.int32).copy())
+
+
 if HAVE_LHOTSE:  # pragma: no cover - authoring container only
+    from concurrent.futures import ThreadPoolExecutor
+
     from lhotse.audio.utils import suppress_audio_loading_errors  # type: ignore
     from lhotse.dataset.collation import collate_vectors, read_audio_from_cuts  # type: ignore
-    from lhotse.dataset.input_strategies import AudioSamples, OnTheFlyFeatures, _get_executor  # type: ignore
+    from lhotse.dataset.input_strategies import AudioSamples, OnTheFlyFeatures, PrecomputedFeatures, _get_executor  # type: ignore
     from lhotse.utils import compute_num_samples  # type: ignore
 
     def deferred_speed_factor(cut) -> Optional[float]:
@@ -1233,6 +1328,174 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             result = self._moved((audio, lens.to(torch.int32)))  # (collation.py:242)
             return result + (ok,) if self.fault_tolerant else result
 
+    # ---- precomputed features: CutMix / padding mixed and collated on the device --------------------------------------------------
+    _ARCHIVE_STORAGES = ("hip_archive", "hip_archive_f16")
+    _LOG_DOMAIN_TYPES: Optional[frozenset] = None
+    _archive_readers: Dict[Tuple[str, str], object] = {}
+
+    def _method_body(fn) -> str:
+        """The statements of a function without its signature, comments and layout (the dump of its syntax tree's body)."""
+        import ast
+        import inspect
+        import textwrap
+
+        body = ast.parse(textwrap.dedent(inspect.getsource(fn))).body[0].body
+        return "\n".join(ast.dump(st) for st in body)
+
+    def log_domain_feature_types() -> frozenset:
+        """The ``features.type`` names whose mix is the log-sum-exp pair of ``Fbank`` (lhotse/features/kaldi/extractors.py:135-152:
+        ``log(max(EPSILON, exp(a) + g * exp(b)))`` and ``sum(exp(x))``): ``kaldi-fbank``, ``hip-fbank``, and every other registered
+        extractor whose ``mix`` / ``compute_energy`` bodies are exactly those.  ``Spectrogram``'s linear mix is not among them."""
+        global _LOG_DOMAIN_TYPES
+        if _LOG_DOMAIN_TYPES is None:
+            from lhotse.features.base import FEATURE_EXTRACTORS  # type: ignore
+            from lhotse.features.kaldi.extractors import Fbank  # type: ignore
+
+            from .extractors import _log_mix
+
+            want = (_method_body(Fbank.mix), _method_body(Fbank.compute_energy))
+            names = {"kaldi-fbank", "hip-fbank"}
+            for name, cls in FEATURE_EXTRACTORS.items():
+                try:
+                    if getattr(cls, "mix", None) is _log_mix or (_method_body(cls.mix), _method_body(cls.compute_energy)) == want:
+                        names.add(name)
+                except Exception:  # noqa: BLE001  (no source to read: not served)
+                    pass
+            _LOG_DOMAIN_TYPES = frozenset(names)
+        return _LOG_DOMAIN_TYPES
+
+    def _archive_reader(storage_type: str, storage_path: str):
+        from lhotse.features.io import get_reader  # type: ignore
+
+        r = _archive_readers.get((storage_type, storage_path))
+        if r is None:
+            r = _archive_readers[(storage_type, storage_path)] = get_reader(storage_type)(storage_path)
+        return r
+
+    def _feature_track(cut, num_features: int) -> Optional[dict]:
+        """The source of one single-channel cut's features, or None: a PaddingCut is a constant; a cut stored in ``hip_archive`` /
+        ``hip_archive_f16`` is read raw with the frame range ``Features.load`` computes (lhotse/features/base.py:488-524); every other
+        storage is loaded through ``cut.load_features()`` here and uploaded as float32."""
+        from lhotse.cut import MonoCut, PaddingCut  # type: ignore
+        from lhotse.utils import compute_num_frames  # type: ignore
+
+        if isinstance(cut, PaddingCut):
+            return {"frames": int(cut.num_frames), "value": float(cut.feat_value)}
+        if not isinstance(cut, MonoCut) or not cut.has_features or int(cut.num_features) != num_features:
+            return None
+        f, frames = cut.features, int(cut.num_frames)
+        if f.storage_type in _ARCHIVE_STORAGES:
+            from math import isclose
+
+            from .storage import _parse_key
+
+            _, rows, cols, dt = _parse_key(f.storage_key)
+            if cols != num_features or cut.start < f.start - 1e-3:
+                return None
+            lo = 0 if isclose(cut.start, f.start) else compute_num_frames(cut.start - f.start, frame_shift=f.frame_shift, sampling_rate=f.sampling_rate)
+            hi = lo + compute_num_frames(cut.duration, frame_shift=f.frame_shift, sampling_rate=f.sampling_rate)
+            n = max(0, min(rows, hi) - max(0, lo))
+            if abs(n - frames) > 1 or (frames > 0 and n < 1):
+                return None
+            reader, key = _archive_reader(f.storage_type, f.storage_path), f.storage_key
+            return {"frames": frames, "rows": n, "f16": dt == "<f2", "read": lambda out: reader.read_raw(key, lo, hi, out=out)}
+        m = cut.load_features()  # (the fix-up of mono.py:61-64 applied)
+        if m is None or m.ndim != 2 or m.shape != (frames, num_features):
+            return None
+        return {"frames": frames, "array": np.ascontiguousarray(m, dtype=np.float32)}
+
+    def pending_feature_mix(cut) -> Optional[dict]:
+        """The track table of one (padded) cut for ``FusedFeatureBatch``, or None when the cut keeps lhotse's own path: the classifier of
+        ``MixedCut.load_features`` (lhotse/cut/mixed.py:1199-1309).  None for: multi-channel (3-D) features, tracks with differing
+        ``num_features`` or ``frame_shift``, a frame-count mismatch beyond +-1, more than 256 tracks, a fold whose ``features.type`` is
+        not a log-domain type (``log_domain_feature_types``), a fold of a single audible track, and a reference track that is muted."""
+        from lhotse.cut import MixedCut, MonoCut, PaddingCut  # type: ignore
+        from lhotse.utils import compute_num_frames  # type: ignore
+
+        from .augmentation import FEATMIX_COPY, FEATMIX_FOLD, FEATMIX_MAX_TRACKS
+
+        if not getattr(cut, "has_features", False):
+            return None
+        F, T = int(cut.num_features), int(cut.num_frames)
+        if isinstance(cut, (MonoCut, PaddingCut)):
+            tr = _feature_track(cut, F)
+            return None if tr is None else {"form": FEATMIX_COPY, "num_frames": T, "pad_value": 0.0, "ref_track": -1, "num_features": F, "tracks": [tr]}
+        if not isinstance(cut, MixedCut):
+            return None
+        tracks = [t for t in cut.tracks if not getattr(t, "mute", False)] or list(cut.tracks)  # (_get_audible_tracks)
+        if len(tracks) > FEATMIX_MAX_TRACKS or not all(isinstance(t.cut, (MonoCut, PaddingCut)) for t in tracks):
+            return None
+        shift = tracks[0].cut.frame_shift
+        if any(t.cut.num_features != F or t.cut.frame_shift != shift for t in tracks):
+            return None
+        first = tracks[0]
+        if first.snr is None and tracks[1:] and all(isinstance(t.cut, PaddingCut) for t in tracks[1:]):  # (mixed.py:1223-1243)
+            tr = _feature_track(first.cut, F)
+            if tr is None or tr["frames"] > T:
+                return None
+            return {"form": FEATMIX_COPY, "num_frames": T, "pad_value": float(tracks[1].cut.feat_value), "ref_track": -1, "num_features": F, "tracks": [tr]}
+        if len(tracks) < 2:  # (the reference hands the one track back as it is: not a fold)
+            return None
+        try:
+            from lhotse.cut.mixed import _get_snr_reference_track  # type: ignore
+
+            _, ref_track = _get_snr_reference_track(cut)
+        except Exception:  # noqa: BLE001  (no reference can be told: lhotse's path raises its own error)
+            return None
+        ref = next((i for i, t in enumerate(tracks) if t is ref_track), -1)
+        if ref < 0 or getattr(ref_track.cut, "features_type", None) not in log_domain_feature_types():
+            return None
+        out, total = [], 0
+        for i, t in enumerate(tracks):
+            tr = _feature_track(t.cut, F)
+            if tr is None:
+                return None
+            tr["first"] = 0 if i == 0 else compute_num_frames(t.offset, frame_shift=shift, sampling_rate=t.cut.sampling_rate)
+            tr["snr"] = None if t.snr is None else float(t.snr)
+            if i == 0 or tr["frames"] > 0:
+                total = max(total, tr["first"] + tr["frames"])
+            out.append(tr)
+        if abs(total - T) > 1 or (T > 0 and total < 1):  # (the reference's assertion, mixed.py:1301-1306)
+            return None
+        return {"form": FEATMIX_FOLD, "num_frames": T, "pad_value": 0.0, "ref_track": ref, "num_features": F, "tracks": out}
+
+    class HipPrecomputedFeatures(PrecomputedFeatures):
+        """``PrecomputedFeatures`` (lhotse/dataset/input_strategies.py:102-129) with the mix and the collation on the GPU: the stored
+        tracks of the padded cuts go to the device as they were stored and two launches write the ``(B, T, F)`` batch
+        (``FusedFeatureBatch``) -- what ``collate_features`` (lhotse/dataset/collation.py:115-145) does per cut on the host through
+        ``MixedCut.load_features`` and ``FeatureMixer``.  Same constructor as the parent plus ``device`` (where the launches run) and
+        ``return_device`` (``None`` keeps the batch there, ``"cpu"`` hands back a host tensor like the reference).  Returns
+        ``(features, features_lens)`` with the parent's dtypes; ``supervision_intervals`` is inherited.
+
+        The parent's own ``__call__`` runs, and its result is moved to ``return_device`` (None: ``device``), when ``pending_feature_mix``
+        returns None for any cut of the batch or the cuts differ in ``num_features``."""
+
+        def __init__(self, *args, device: Union[str, torch.device, None] = None, return_device: Optional[Union[str, torch.device]] = None, **kwargs) -> None:
+            super().__init__(*args, **kwargs)
+            self.batch = FusedFeatureBatch(device)
+            self.device, self.return_device = self.batch.device, return_device
+
+        def _moved(self, result):
+            dev = self.device if self.return_device is None else self.return_device
+            return (result[0].to(dev),) + tuple(result[1:])
+
+        def __call__(self, cuts, pad_direction: Optional[str] = "right"):
+            assert all(cut.has_features for cut in cuts)
+            lens = torch.tensor([cut.num_frames for cut in cuts], dtype=torch.int)  # (collation.py:133)
+            padded = cuts.pad(num_frames=max(lens).item(), direction=pad_direction)
+            tables = []
+            for cut in padded:
+                tab = pending_feature_mix(cut)
+                if tab is None or (tables and tab["num_features"] != tables[0]["num_features"]):
+                    return self._moved(super().__call__(cuts, pad_direction=pad_direction))
+                tables.append(tab)
+            pool = _get_executor(self.num_workers, executor_type=self._executor_type)
+            if pool is not None and not isinstance(pool, ThreadPoolExecutor):  # (the reads fill this process's staging buffer)
+                pool = None
+            feats, _ = self.batch.features_of(tables, tables[0]["num_features"], int(max(lens).item()), pool)
+            return self._moved((feats, lens))
+
+
 else:
 
     class HipOnTheFlyFeatures:  # type: ignore[no-redef]
@@ -1242,3 +1505,7 @@ else:
     class HipAudioSamples:  # type: ignore[no-redef]
         def __init__(self, *args, **kwargs):
             raise ImportError("HipAudioSamples consumes lhotse CutSets: install lhotse (lhotse.dataset.input_strategies.AudioSamples)")
+
+    class HipPrecomputedFeatures:  # type: ignore[no-redef]
+        def __init__(self, *args, **kwargs):
+            raise ImportError("HipPrecomputedFeatures consumes lhotse CutSets: install lhotse (lhotse.dataset.input_strategies.PrecomputedFeatures)")

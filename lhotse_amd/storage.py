@@ -125,20 +125,34 @@ class _ArchiveReaderImpl:
         self._fd = None
         self._lock = threading.Lock()
 
-    def read(self, key: str, left_offset_frames: int = 0, right_offset_frames: Optional[int] = None) -> np.ndarray:
+    def read_raw(self, key: str, left_offset_frames: int = 0, right_offset_frames: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The rows ``[left_offset_frames, right_offset_frames)`` of ``key`` in their STORED dtype (binary16 stays binary16), read with one
+        ``preadv`` of exactly their bytes.  ``out``: a C-contiguous buffer of at least that many bytes (any dtype, e.g. a slice of a pinned
+        uint8 staging buffer) that receives them; the returned ``(n, cols)`` array is then a view of it."""
         off, rows, cols, dt = _parse_key(key)
         lo = max(0, int(left_offset_frames))
         hi = rows if right_offset_frames is None else min(rows, int(right_offset_frames))
         n = max(0, hi - lo)
-        out = np.empty((n, cols), dtype=dt)
+        item = np.dtype(dt).itemsize
+        if out is None:
+            res = np.empty((n, cols), dtype=dt)
+        else:
+            flat = out.reshape(-1).view(np.uint8)  # (raises for a buffer that is not contiguous)
+            if flat.nbytes < n * cols * item:
+                raise ValueError(f"out holds {flat.nbytes} bytes, key {key!r} rows [{lo}, {hi}) take {n * cols * item}")
+            res = flat[: n * cols * item].view(dt).reshape(n, cols)
         if n:
             with self._lock:
                 if self._fd is None:
                     self._fd = os.open(self._path, os.O_RDONLY)
-            got = os.preadv(self._fd, [memoryview(out).cast("B")], off + lo * cols * out.dtype.itemsize)
-            if got != out.nbytes:
-                raise IOError(f"{self._path}: short read for key {key!r} ({got} of {out.nbytes} bytes)")
-        return out if dt == "<f4" else out.astype("<f4")  # lhotse's readers hand out float32
+            got = os.preadv(self._fd, [memoryview(res).cast("B")], off + lo * cols * item)
+            if got != res.nbytes:
+                raise IOError(f"{self._path}: short read for key {key!r} ({got} of {res.nbytes} bytes)")
+        return res
+
+    def read(self, key: str, left_offset_frames: int = 0, right_offset_frames: Optional[int] = None) -> np.ndarray:
+        out = self.read_raw(key, left_offset_frames, right_offset_frames)
+        return out if out.dtype.itemsize == 4 else out.astype("<f4")  # lhotse's readers hand out float32
 
     def __del__(self):
         try:
