@@ -41,12 +41,13 @@ extern "C" {
 #define HIPFEAT_API
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
- * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES, _SINC_SIGNATURES and
- * _FEATMIX_SIGNATURES next to _SIGNATURES). */
+ * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES, _SINC_SIGNATURES,
+ * _FEATMIX_SIGNATURES and _STATS_SIGNATURES next to _SIGNATURES). */
 #define HIPFEAT_COLLATE_API HIPFEAT_API
 #define HIPFEAT_FEATMIX_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
 #define HIPFEAT_SINC_API HIPFEAT_API
+#define HIPFEAT_STATS_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -565,6 +566,53 @@ HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_plan(hipfeat_featmix* featmix
                                                         const double* h_value, int64_t num_features, int64_t row_frames, int64_t* h_info);
 HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmix* featmix, int64_t ticket, const void* d_arena, int64_t arena_bytes, float* d_out,
                                                        int64_t out_elements, void* stream);
+
+/* ---- global feature statistics on the device (additive to ABI v8) ----------------------------------------------------- */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_stats_*; the version number did not change because nothing that existed
+ * changed.
+ *
+ * CutSet.compute_global_feature_stats (lhotse/cut/set.py:2533-2583) hands one feature matrix per cut to StatsAccumulator.update
+ * (lhotse/features/base.py:957-1033), float64 numpy on the host.  Here the matrices of many cuts lie in ONE device buffer, float32
+ * (dtype 0) or IEEE binary16 (dtype 1), row-major with row_stride >= feature_dim ELEMENTS per row; cut b owns the rows
+ * [h_first_row[b], h_first_row[b] + h_num_frames[b]) -- the packed (sum T, F) matrix hipfeat_extract writes as well as a padded
+ * (B, Tmax, F) tensor, whose padding rows are never read.  Rows need not ascend; h_first_row * row_stride may exceed 2^31.
+ *
+ * State: total_frames (int64, also known to the host), total_sum[F], total_unnorm_var[F] (float64, on the device).  Cut by cut, in the
+ * order of the table, all in float64:
+ *   curr_sum = sum(x), curr_unnorm_var = sum((x - mean_cut)^2) (= np.var(x, axis=0) * curr_frames; E[x^2] - E[x]^2 is never formed);
+ *   total_frames > 0:  r = total_frames / curr_frames;
+ *                      total_unnorm_var = total_unnorm_var + curr_unnorm_var + r / (total_frames + curr_frames) * (total_sum / r - curr_sum)^2
+ *   total_frames == 0: total_unnorm_var = curr_unnorm_var                      (the first cut into an empty state assigns)
+ *   total_sum = total_sum + curr_sum;  total_frames = total_frames + curr_frames.
+ * A cut is summed in blocks of 256 frames (block sums about the block's own mean), and its blocks are merged in block order with
+ * the pairwise update of Chan, Golub and LeVeque; no floating-point atomic is used, the order is the table's, so the result is bit-identical
+ * from run to run and does not depend on how the cuts were grouped into updates.  A cut of 0 frames contributes NOTHING (the reference's
+ * np.var of an empty matrix would turn every bin into NaN).  Non-finite values propagate as float64 arithmetic makes them, in their
+ * own bin only.
+ *
+ * hipfeat_stats_create / _destroy: the object that owns the state, the slab of block partials (grows on demand) and 16 staging slots on
+ * `device`, for feature_dim = 1 ... 65535 bins; calls are serialised inside; destroy waits for the work it enqueued; destroying NULL is OK.
+ * hipfeat_stats_update validates on the host, stages the table and enqueues the two launches on `stream` without waiting (a 17th update
+ * waits for the first one's launches).  1 ... 65535 cuts; h_first_row == NULL: the cuts are packed back to back from row 0.  Negative
+ * rows or frames, row_stride < feature_dim, a cut whose last element lies beyond feats_elems, a dtype other than 0 or 1, a base pointer
+ * that is not a multiple of the element size (the stride counts elements and cannot break it), counts out of range:
+ * HIPFEAT_ERR_INVALID; more than 2^24 blocks in one update: HIPFEAT_ERR_UNSUPPORTED; nothing is enqueued and the state is unchanged.
+ * The calls of one object are meant for ONE stream at a time: the host's total_frames is that of what has been enqueued.
+ * hipfeat_stats_merge folds another accumulator's state (host arrays of feature_dim float64 each) in with the update above, `frames`
+ * standing for curr_frames: the ranks of a sharded pass combine their parts.  frames == 0 is a no-op.
+ * hipfeat_stats_get waits for `stream` and copies the state out (any of the three pointers may be NULL).
+ * hipfeat_stats_reset zeroes the state.  Every call on a NULL object is HIPFEAT_ERR_INVALID and needs no device.
+ */
+typedef struct hipfeat_stats hipfeat_stats;
+HIPFEAT_STATS_API hipfeat_status hipfeat_stats_create(int32_t device, int32_t feature_dim, hipfeat_stats** stats);
+HIPFEAT_STATS_API hipfeat_status hipfeat_stats_destroy(hipfeat_stats* stats);
+HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* stats, const void* d_feats, int64_t feats_elems, int32_t dtype,
+                                                      int64_t num_cuts, const int64_t* h_first_row, const int64_t* h_num_frames,
+                                                      int64_t row_stride, void* stream);
+HIPFEAT_STATS_API hipfeat_status hipfeat_stats_merge(hipfeat_stats* stats, int64_t frames, const double* h_sum, const double* h_unnorm_var, void* stream);
+HIPFEAT_STATS_API hipfeat_status hipfeat_stats_get(hipfeat_stats* stats, int64_t* h_frames, double* h_sum, double* h_unnorm_var, void* stream);
+HIPFEAT_STATS_API hipfeat_status hipfeat_stats_reset(hipfeat_stats* stats, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

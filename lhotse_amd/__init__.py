@@ -40,6 +40,8 @@ from .librosa_fbank import HipLibrosaFbank, HipLibrosaFbankConfig  # noqa: F401,
 
 from .signal_transforms import HipGlobalMVN, HipSpecAugment  # noqa: F401,E402
 
+from .stats import GlobalStatsPass, HipStatsAccumulator, compute_global_feature_stats, get_or_create_stats  # noqa: F401,E402
+
 from .layers import HipWav2LogFilterBank, HipWav2LogSpec, HipWav2MFCC, HipWav2Spec  # noqa: F401,E402
 
 from .storage import HipArchiveF16Writer, HipArchiveReader, HipArchiveWriter, compute_and_store_features_batch  # noqa: F401,E402
@@ -55,6 +57,10 @@ __all__ = [
     "HipWhisperFbank",
     "HipLibrosaFbank",
     "HipGlobalMVN",
+    "HipStatsAccumulator",
+    "GlobalStatsPass",
+    "compute_global_feature_stats",
+    "get_or_create_stats",
     "HipWav2Spec",
     "HipWav2LogSpec",
     "HipWav2LogFilterBank",

@@ -165,7 +165,19 @@ _FEATMIX_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
     "hipfeat_featmix_run": ("int", ["hipfeat_featmix*", "int64_t", "const void*", "int64_t", "float*", "int64_t", "void*"]),
 }
-_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES}
+# Likewise (HIPFEAT_STATS_API in the header).
+_STATS_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_stats_create": ("int", ["int32_t", "int32_t", "hipfeat_stats**"]),
+    "hipfeat_stats_destroy": ("int", ["hipfeat_stats*"]),
+    "hipfeat_stats_update": (
+        "int",
+        ["hipfeat_stats*", "const void*", "int64_t", "int32_t", "int64_t", "const int64_t*", "const int64_t*", "int64_t", "void*"],
+    ),
+    "hipfeat_stats_merge": ("int", ["hipfeat_stats*", "int64_t", "const double*", "const double*", "void*"]),
+    "hipfeat_stats_get": ("int", ["hipfeat_stats*", "int64_t*", "double*", "double*", "void*"]),
+    "hipfeat_stats_reset": ("int", ["hipfeat_stats*", "void*"]),
+}
+_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -257,7 +269,7 @@ class _CffiBackend:
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
-                        .replace("HIPFEAT_FEATMIX_API ", ""))
+                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

@@ -30,6 +30,8 @@
 #include "kernel_reverb.hpp"
 #include "kernel_collate.hpp"
 #include "kernel_featmix.hpp"
+#include "kernel_stats.hpp"
+#include "stats_tables.hpp"
 #include "kernel_level.hpp"
 #include "kernel_sinc.hpp"
 #include "kernel_specaug.hpp"
@@ -2665,6 +2667,158 @@ extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmi
   // a flat 1-D grid over (cut, tile); beyond 2^22 workgroups (2^34 elements) the workgroups stride
   hipLaunchKernelGGL(featmix_fold_kernel, dim3((unsigned)std::min<int64_t>(p.fold_items, (int64_t)1 << 22)), dim3(256), 0, st, a);
   return finish_run(fm->tickets, ticket, s, st, hipGetLastError(), "feature mix", kWaitedLaunches);
+}
+
+// --------------------------------------------------------------------------------------
+// Global feature statistics on the device (StatsAccumulator, lhotse/features/base.py:990-1033): block partials, then the fold in
+// table order, in two launches (kernel_stats.hpp; the table: stats_tables.hpp)
+// --------------------------------------------------------------------------------------
+struct hipfeat_stats {
+  int device = 0;
+  int32_t feature_dim = 0;
+  std::mutex mu;
+  int64_t frames = 0;         // total_frames of what has been enqueued
+  double* d_state = nullptr;  // [2][F]: total_sum, total_unnorm_var
+  double* d_slab = nullptr;   // [blocks][2][F] of the update in flight; grows on demand
+  size_t slab_cap = 0;        // bytes
+  StagedSlot slots[kTicketSlots];
+  int next_slot = 0;
+  StagedSlot& take_slot() {
+    StagedSlot& s = slots[next_slot];
+    next_slot = (next_slot + 1) % kTicketSlots;
+    return s;
+  }
+};
+
+extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_create(int32_t device, int32_t feature_dim, hipfeat_stats** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "stats pointer is NULL");
+  *out = nullptr;
+  if (feature_dim < 1 || feature_dim > kStMaxDim) return fail(HIPFEAT_ERR_INVALID, "%d bins per frame (1 ... %d)", (int)feature_dim, kStMaxDim);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  DeviceGuard g(device);
+  double* state = nullptr;
+  const size_t bytes = (size_t)feature_dim * 2 * sizeof(double);
+  HIP_TRY(hipMalloc(&state, bytes));
+  if (hipError_t e = hipMemset(state, 0, bytes)) {
+    (void)hipFree(state);
+    return fail(HIPFEAT_ERR_HIP, "hipMemset failed: %s", hipGetErrorName(e));
+  }
+  hipfeat_stats* s = new (std::nothrow) hipfeat_stats();
+  if (!s) {
+    (void)hipFree(state);
+    return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  }
+  s->device = device;
+  s->feature_dim = feature_dim;
+  s->d_state = state;
+  *out = s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_destroy(hipfeat_stats* s) {
+  if (!s) return HIPFEAT_OK;
+  DeviceGuard g(s->device);
+  for (auto& slot : s->slots) slot.free_all();  // (waits for the launches that used the slot)
+  if (s->d_slab) (void)hipFree(s->d_slab);
+  if (s->d_state) (void)hipFree(s->d_state);
+  delete s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* s, const void* d_feats, int64_t feats_elems, int32_t dtype, int64_t num_cuts,
+                                                                 const int64_t* h_first_row, const int64_t* h_num_frames, int64_t row_stride, void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  const StPlan p = build_stats_plan(s->feature_dim, (uint64_t)reinterpret_cast<uintptr_t>(d_feats), feats_elems, dtype, num_cuts, h_first_row, h_num_frames, row_stride);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  if (p.total_blocks == 0) return HIPFEAT_OK;  // cuts of no frames: nothing to add
+  if (!d_feats) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t F = (size_t)s->feature_dim, slab_bytes = (size_t)p.total_blocks * 2 * F * sizeof(double);
+  if (s->slab_cap < slab_bytes) {  // the launches that read the old slab are waited for before it goes
+    for (auto& slot : s->slots) HIP_TRY(slot.wait());
+    HIP_TRY(hipStreamSynchronize(st));
+    if (s->d_slab) (void)hipFree(s->d_slab);
+    s->d_slab = nullptr;
+    s->slab_cap = 0;
+    const size_t grown = std::max<size_t>(slab_bytes * 2, 1 << 20);
+    HIP_TRY(hipMalloc(&s->d_slab, grown));
+    s->slab_cap = grown;
+  }
+  StagedSlot& slot = s->take_slot();
+  const size_t bytes = p.cuts.size() * sizeof(StCut);
+  HIP_TRY(slot.wait());
+  HIP_TRY(slot.reserve(bytes));
+  std::memcpy(slot.h, p.cuts.data(), bytes);
+  HIP_TRY(hipMemcpyAsync(slot.d, slot.h, bytes, hipMemcpyHostToDevice, st));
+  StArgs a;
+  a.feats = d_feats;
+  a.cuts = static_cast<const StCut*>(slot.d);
+  a.slab = s->d_slab;
+  a.state = s->d_state;
+  a.row_stride = p.row_stride;
+  a.frames_before = s->frames;
+  a.num_cuts = (int32_t)p.cuts.size();
+  a.feature_dim = s->feature_dim;
+  a.items = (int32_t)p.items;
+  a.col_tiles = (int32_t)p.col_tiles;
+  a.vec_ok = p.vec_ok;
+  a.pad = 0;
+  if (dtype == kStF16) hipLaunchKernelGGL(stats_partial_kernel<true>, dim3(items_grid(p.items)), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(stats_partial_kernel<false>, dim3(items_grid(p.items)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, st, a);
+  const hipError_t e1 = hipGetLastError(), e2 = slot.record(st);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats launch failed: %s", hipGetErrorName(e1));
+  s->frames += p.total_frames;  // (the launches are enqueued: the state on the stream has them)
+  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats: hipEventRecord failed: %s (%s)", hipGetErrorName(e2), kWaitedLaunches);
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_merge(hipfeat_stats* s, int64_t frames, const double* h_sum, const double* h_unnorm_var, void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (frames < 0) return fail(HIPFEAT_ERR_INVALID, "a state of %lld frames", (long long)frames);
+  if (frames == 0) return HIPFEAT_OK;  // an empty state adds nothing
+  if (!h_sum || !h_unnorm_var) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t F = (size_t)s->feature_dim, bytes = 2 * F * sizeof(double);
+  StagedSlot& slot = s->take_slot();
+  HIP_TRY(slot.wait());
+  HIP_TRY(slot.reserve(bytes));
+  std::memcpy(slot.h, h_sum, bytes / 2);
+  std::memcpy(static_cast<unsigned char*>(slot.h) + bytes / 2, h_unnorm_var, bytes / 2);
+  HIP_TRY(hipMemcpyAsync(slot.d, slot.h, bytes, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(stats_merge_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, st, s->d_state, static_cast<const double*>(slot.d), (int)F, s->frames, frames);
+  const hipError_t e1 = hipGetLastError(), e2 = slot.record(st);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats merge launch failed: %s", hipGetErrorName(e1));
+  s->frames += frames;
+  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats: hipEventRecord failed: %s (%s)", hipGetErrorName(e2), kWaitedLaunch);
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_get(hipfeat_stats* s, int64_t* h_frames, double* h_sum, double* h_unnorm_var, void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  const size_t F = (size_t)s->feature_dim;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (h_sum) HIP_TRY(hipMemcpy(h_sum, s->d_state, F * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_unnorm_var) HIP_TRY(hipMemcpy(h_unnorm_var, s->d_state + F, F * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_frames) *h_frames = s->frames;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_reset(hipfeat_stats* s, void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  HIP_TRY(hipMemsetAsync(s->d_state, 0, (size_t)s->feature_dim * 2 * sizeof(double), (hipStream_t)stream));
+  s->frames = 0;
+  return HIPFEAT_OK;
 }
 
 // ---- bulk save path: per-batch host work of the offline driver (host_bulk.hpp) -------------------------------------------------

@@ -44,8 +44,14 @@ class HipGlobalMVN(torch.nn.Module):
         self.register_buffer("norm_stds", torch.ones(feature_dim))
 
     @classmethod
-    def from_cuts(cls, cuts, max_cuts: Optional[int] = None, extractor=None) -> "HipGlobalMVN":
-        stats = cuts.compute_global_feature_stats(max_cuts=max_cuts, extractor=extractor)
+    def from_cuts(cls, cuts, max_cuts: Optional[int] = None, extractor=None, device_stats: bool = False) -> "HipGlobalMVN":
+        """``device_stats=True``: the statistics are estimated on the device too (``lhotse_amd.compute_global_feature_stats``)."""
+        if device_stats:
+            from .stats import compute_global_feature_stats
+
+            stats = compute_global_feature_stats(cuts, extractor=extractor, max_cuts=max_cuts)
+        else:
+            stats = cuts.compute_global_feature_stats(max_cuts=max_cuts, extractor=extractor)
         stats = {name: torch.as_tensor(value) for name, value in stats.items()}
         (feature_dim,) = stats["norm_means"].shape
         mvn = cls(feature_dim)
