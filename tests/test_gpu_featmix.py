@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import _featmix_ref as R
+from _featmix_cases import Arena
 
 from lhotse_amd import augmentation as A
 from lhotse_amd.augmentation import FEATMIX_COPY as COPY, FEATMIX_FOLD as FOLD, FeatCut, FeatTrack
@@ -22,38 +23,6 @@ pytestmark = pytest.mark.gpu
 GUARD = 64
 POISON = 0x5A5A5A5A
 FS = [1, 23, 40, 80, 257]
-
-
-class Arena:
-    """Tracks packed by hand into a byte buffer: float32 at 4-byte boundaries that are no 16-byte boundaries, binary16 at odd 2-byte ones."""
-
-    def __init__(self, seed=0):
-        self.rs = np.random.RandomState(seed)
-        self.buf = bytearray(self.rs.bytes(6))
-        self.k = 0
-
-    def add(self, m: np.ndarray, f16=False) -> int:
-        self.k += 1
-        if f16:
-            while len(self.buf) % 4 != 2:  # an odd multiple of 2
-                self.buf += b"\x7b"
-        else:
-            while len(self.buf) % 16 != 4 * (1 + self.k % 3):
-                self.buf += b"\x7b"
-        off = len(self.buf)
-        self.buf += np.ascontiguousarray(m, dtype=np.float16 if f16 else np.float32).tobytes()
-        return off
-
-    def feats(self, n, F, f16=False, lo=-15.0, hi=5.0):
-        m = self.rs.uniform(lo, hi, (n, F)).astype(np.float32)
-        return m.astype(np.float16).astype(np.float32) if f16 else m
-
-    def track(self, n, F, f16=False, rows=None, **kw) -> FeatTrack:
-        m = self.feats(n if rows is None else rows, F, f16)
-        return FeatTrack(self.add(m, f16), n, rows, f16, **kw)
-
-    def host(self) -> np.ndarray:
-        return np.frombuffer(bytes(self.buf) + b"\x00" * (-len(self.buf) % 16), dtype=np.uint8).copy()
 
 
 def run(host: np.ndarray, cuts, F, row_frames=None):
