@@ -96,13 +96,91 @@ struct DeviceGuard {
 // --------------------------------------------------------------------------------------
 // objects
 // --------------------------------------------------------------------------------------
-struct StagingSlot {
+// How every entry point gets its tables to the device ("Ticketed handles"): a pinned host buffer and a device buffer of one
+// capacity, and the event that says when the launches that used them last are done.
+struct StagedSlot {
   void* h = nullptr;  // pinned host
   void* d = nullptr;  // device
   size_t cap = 0;
   hipEvent_t ev = nullptr;
   bool busy = false;
+  hipError_t wait() {  // for the launches that used this slot's memory last time
+    if (!busy) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(ev);
+    if (e == hipSuccess) busy = false;
+    return e;
+  }
+  hipError_t reserve(size_t bytes) {  // the event exists and both buffers hold `bytes`; their old contents are not kept
+    hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess || cap >= bytes) return e;
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    h = d = nullptr;
+    cap = 0;
+    const size_t grown = std::max<size_t>(bytes * 2, 1 << 14);
+    if ((e = hipHostMalloc(&h, grown, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipMalloc(&d, grown)) != hipSuccess) return e;
+    cap = grown;
+    return hipSuccess;
+  }
+  hipError_t record(hipStream_t st) {  // behind the launches; memory its event cannot guard is waited for here instead
+    const hipError_t e = hipEventRecord(ev, st);
+    busy = (e == hipSuccess);
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    return e;
+  }
+  void free_all() {
+    if (busy && ev) (void)hipEventSynchronize(ev);
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    if (ev) (void)hipEventDestroy(ev);
+  }
 };
+
+// the slots of an entry point without tickets, taken round-robin under its owner's mutex
+template <int N>
+struct SlotRing {
+  StagedSlot slots[N];
+  int next = 0;
+  StagedSlot& take() {
+    StagedSlot& s = slots[next];
+    next = (next + 1) % N;
+    return s;
+  }
+  void free_all() {
+    for (auto& s : slots) s.free_all();
+  }
+};
+
+// the way in: the slot's last launches are done, both buffers hold `total` bytes, `fill` has written the pinned one and its first
+// `copied` bytes are on their way to the device (what lies behind them is device scratch of the launches)
+template <typename Fill>
+static hipError_t stage(StagedSlot& s, size_t total, size_t copied, hipStream_t st, Fill fill) {
+  hipError_t e = s.wait();
+  if (e == hipSuccess) e = s.reserve(total);
+  if (e != hipSuccess) return e;
+  fill(static_cast<unsigned char*>(s.h));
+  return hipMemcpyAsync(s.d, s.h, copied, hipMemcpyHostToDevice, st);
+}
+
+// the way out, behind the issued launches (e1: hipGetLastError behind them): the slot's event guards its memory, or the stream has been
+// waited for
+constexpr const char* kWaitedLaunch = "the launch was enqueued and has been waited for";
+constexpr const char* kWaitedLaunches = "the launches were enqueued and have been waited for";
+static hipfeat_status finish_launches(StagedSlot& s, hipStream_t st, hipError_t e1, const char* kind, const char* waited) {
+  const hipError_t e2 = s.record(st);
+  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s launch failed: %s", kind, hipGetErrorName(e1));
+  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s: hipEventRecord failed: %s (%s)", kind, hipGetErrorName(e2), waited);
+  return HIPFEAT_OK;
+}
+
+// HIP device `device` exists, or the refusal is written
+static hipfeat_status check_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  return HIPFEAT_OK;
+}
 
 // The kernel family a plan runs.  hipfeat_plan_create tries the families in a fixed order; the first setup that accepts the
 // configuration claims the plan, the generic kernel takes the rest.
@@ -181,8 +259,7 @@ struct hipfeat_plan {
   int32_t* d_wh2_sched = nullptr;
   // transient-layout staging ring (hipfeat_extract)
   mutable std::mutex mu;
-  mutable StagingSlot slots[4];
-  mutable int next_slot = 0;
+  mutable SlotRing<4> ring;
   // host-form scratch (hipfeat_extract_host)
   mutable float* d_scratch_wave = nullptr;
   mutable size_t scratch_wave_cap = 0;
@@ -287,11 +364,7 @@ static void plan_free(hipfeat_plan* p) {
   (void)hipFree(p->d_work);
   (void)hipFree(p->d_mel_t);
   (void)hipFree(p->d_c_shared);
-  for (auto& s : p->slots) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
+  p->ring.free_all();  // (waits for the launches that used a slot)
   delete p;
 }
 
@@ -696,10 +769,9 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
   const int C = cfg->kind == HIPFEAT_MFCC ? cfg->num_ceps : 0;
   p->feature_dim = cfg->kind == HIPFEAT_FBANK ? M + (cfg->use_energy ? 1 : 0) : (cfg->kind == HIPFEAT_MFCC ? C : ((whisper || librosa) ? M : p->K));
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+  if (hipfeat_status bad = check_device(device)) {
     delete p;
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+    return bad;
   }
   {  // the kernels are gfx950 code objects and lean on gfx950's memory pipeline (hipfeat.h, HIPFEAT_WHISPER): any other device is refused here
     hipDeviceProp_t prop;
@@ -1319,32 +1391,17 @@ static hipfeat_status extract_transient(const hipfeat_plan* plan, const float* d
   const size_t desc_bytes = descs.size() * sizeof(CutDesc) + map_bytes;
   const size_t bytes = desc_bytes + (plan->route == Route::Whisper3 ? norm_slot_bytes(&lay) : 0);
   std::lock_guard<std::mutex> lk(plan->mu);
-  StagingSlot& s = plan->slots[plan->next_slot];
-  plan->next_slot = (plan->next_slot + 1) % 4;
-  if (s.busy) {
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
-  std::memcpy(s.h, descs.data(), descs.size() * sizeof(CutDesc));
-  if (map_bytes) std::memcpy(static_cast<unsigned char*>(s.h) + descs.size() * sizeof(CutDesc), lay.block_cut.data(), lay.block_cut.size() * sizeof(int32_t));
+  StagedSlot& s = plan->ring.take();
+  HIP_TRY(stage(s, bytes, bytes, (hipStream_t)stream, [&](unsigned char* h) {
+    std::memcpy(h, descs.data(), descs.size() * sizeof(CutDesc));
+    if (map_bytes) std::memcpy(h + descs.size() * sizeof(CutDesc), lay.block_cut.data(), lay.block_cut.size() * sizeof(int32_t));
+    std::memset(h + desc_bytes, 0, bytes - desc_bytes);
+  }));
+  lay.d_cuts = static_cast<CutDesc*>(s.d);
   if (bytes > desc_bytes) {
-    std::memset(static_cast<unsigned char*>(s.h) + desc_bytes, 0, bytes - desc_bytes);
     lay.d_norm = static_cast<unsigned char*>(s.d) + desc_bytes;
     lay.norm_slots = 1;
   }
-  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-  lay.d_cuts = static_cast<CutDesc*>(s.d);
   st = HIPFEAT_OK;
   if (lay.total_blocks > 0) st = launch(plan, &lay, d_wave, d_out, (hipStream_t)stream);
   if (st == HIPFEAT_OK && max_pad > 0) {
@@ -1355,9 +1412,11 @@ static hipfeat_status extract_transient(const hipfeat_plan* plan, const float* d
     hipError_t e1 = hipGetLastError();
     if (e1 != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "padding fill launch failed: %s", hipGetErrorName(e1));
   }
-  hipError_t e = hipEventRecord(s.ev, (hipStream_t)stream);
-  s.busy = (e == hipSuccess);
-  return st;
+  if (st != HIPFEAT_OK) {  // the refusal of launch() or of the padding fill stands, with its text
+    (void)s.record((hipStream_t)stream);
+    return st;
+  }
+  return finish_launches(s, (hipStream_t)stream, hipSuccess, "extract", kWaitedLaunches);
 }
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_extract(const hipfeat_plan* plan, const float* d_wave, const int64_t* h_wave_offsets,
@@ -1456,10 +1515,9 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_global_mvn(const float* d_in, floa
 namespace {
 struct StagingRing {
   std::mutex mu;
-  StagingSlot slots[4];
-  int next = 0;
+  SlotRing<4> ring;
 };
-StagingRing g_rings[64];  // per device, process lifetime (descriptors of plan-less calls)
+StagingRing g_rings[64];  // per device, process lifetime, never freed (descriptors of plan-less calls)
 }  // namespace
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_specaug(const float* d_in, float* d_out, int64_t batch, int64_t num_frames, int64_t feature_dim,
@@ -1524,32 +1582,15 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_specaug(const float* d_in, float* 
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return fail(HIPFEAT_ERR_INVALID, "device index %d out of range", dev);
-  StagingRing& ring = g_rings[dev];
-  std::lock_guard<std::mutex> lk(ring.mu);
-  StagingSlot& sl = ring.slots[ring.next];
-  ring.next = (ring.next + 1) % 4;
-  if (sl.busy) {
-    HIP_TRY(hipEventSynchronize(sl.ev));
-    sl.busy = false;
-  }
-  if (!sl.ev) HIP_TRY(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-  if (sl.cap < total) {
-    if (sl.h) (void)hipHostFree(sl.h);
-    if (sl.d) (void)hipFree(sl.d);
-    sl.h = sl.d = nullptr;
-    sl.cap = 0;
-    const size_t cap = std::max<size_t>(total * 2, 1 << 16);
-    HIP_TRY(hipHostMalloc(&sl.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&sl.d, cap));
-    sl.cap = cap;
-  }
-  char* h = static_cast<char*>(sl.h);
-  std::memcpy(h + o_seg_off, seg_off.data(), seg_off.size() * 4);
-  std::memcpy(h + o_mask_off, mask_off.data(), mask_off.size() * 4);
-  if (!segs.empty()) std::memcpy(h + o_segs, segs.data(), segs.size() * sizeof(WarpSeg));
-  if (!masks.empty()) std::memcpy(h + o_masks, masks.data(), masks.size() * 4);
+  std::lock_guard<std::mutex> lk(g_rings[dev].mu);
+  StagedSlot& sl = g_rings[dev].ring.take();  // device: the tables, then the partial sums
   hipStream_t st_ = (hipStream_t)stream;
-  HIP_TRY(hipMemcpyAsync(sl.d, sl.h, h_bytes, hipMemcpyHostToDevice, st_));
+  HIP_TRY(stage(sl, total, h_bytes, st_, [&](unsigned char* h) {
+    std::memcpy(h + o_seg_off, seg_off.data(), seg_off.size() * 4);
+    std::memcpy(h + o_mask_off, mask_off.data(), mask_off.size() * 4);
+    if (!segs.empty()) std::memcpy(h + o_segs, segs.data(), segs.size() * sizeof(WarpSeg));
+    if (!masks.empty()) std::memcpy(h + o_masks, masks.data(), masks.size() * 4);
+  }));
   char* d = static_cast<char*>(sl.d);
   SpecAugParams sp{};
   sp.in = d_in;
@@ -1572,10 +1613,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_specaug(const float* d_in, float* 
     hipLaunchKernelGGL(specaug_mask_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), (size_t)F + rows_per_tile, st_, sp);
     e = hipGetLastError();
   }
-  hipError_t e2 = hipEventRecord(sl.ev, st_);
-  sl.busy = (e2 == hipSuccess);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "specaug launch failed: %s", hipGetErrorName(e));
-  return HIPFEAT_OK;
+  return finish_launches(sl, st_, e, "specaug", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1595,8 +1633,7 @@ struct hipfeat_resampler {
   ResMfmaGeometry mfma;
   char kernel_name[48] = "resample_generic";
   mutable std::mutex mu;
-  mutable StagingSlot slots[4];
-  mutable int next_slot = 0;
+  mutable SlotRing<4> ring;
 };
 
 template <int ORIG, int NEW, int WIDTH>
@@ -1626,9 +1663,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
   if (!out || !h_kernel) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   *out = nullptr;
   if (orig_freq <= 0 || new_freq <= 0 || width <= 0) return fail(HIPFEAT_ERR_INVALID, "bad resampler geometry");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  if (hipfeat_status bad = check_device(device)) return bad;
   hipfeat_resampler* r = new (std::nothrow) hipfeat_resampler();
   if (!r) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
   r->device = device;
@@ -1637,11 +1672,12 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
   r->width = width;
   r->kw = 2 * width + orig_freq;
   DeviceGuard g(device);
+  auto bail = [&](hipfeat_status s) {
+    (void)hipfeat_resampler_destroy(r);
+    return s;
+  };
   hipfeat_status st = upload(&r->d_kernel, h_kernel, (size_t)r->nw * r->kw);
-  if (st != HIPFEAT_OK) {
-    delete r;
-    return st;
-  }
+  if (st != HIPFEAT_OK) return bail(st);
   // speed 0.9 / 1.1 / 0.95 / 1.05 at any rate, and the 1:2, 2:1, 3:1 rate conversions
   const bool generic_only = route_env("HIPFEAT_RESAMPLE_GENERIC");
   const bool fast = !generic_only &&
@@ -1654,11 +1690,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
     for (int ph = 0; ph < r->nw; ++ph)
       for (int i = 0; i < r->kw; ++i) kt[(size_t)i * newp + ph] = h_kernel[(size_t)ph * r->kw + i];
     st = upload(&r->d_kernel_t, kt.data(), kt.size());
-    if (st != HIPFEAT_OK) {
-      (void)hipFree(r->d_kernel);
-      delete r;
-      return st;
-    }
+    if (st != HIPFEAT_OK) return bail(st);
   } else if (!generic_only && (res_mfma_routed(r->orig, r->nw, r->width) ||
                                (route_env("HIPFEAT_RESAMPLE_MFMA") && r->nw >= kResMfmaTile && res_mfma_geometry(r->orig, r->nw, r->width).fits))) {
     // many phases, odd hop: the matrix-core kernel (measured against the generic one by tools/bench_resample_rates.py, which sets
@@ -1666,11 +1698,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
     r->mfma = res_mfma_geometry(r->orig, r->nw, r->width);
     const std::vector<float> kt = res_mfma_bank(h_kernel, r->nw, r->kw, r->mfma.kwp, r->mfma.nwp);
     st = upload(&r->d_kernel_mfma, kt.data(), kt.size());
-    if (st != HIPFEAT_OK) {
-      (void)hipFree(r->d_kernel);
-      delete r;
-      return st;
-    }
+    if (st != HIPFEAT_OK) return bail(st);
     std::snprintf(r->kernel_name, sizeof(r->kernel_name), "resample_mfma");
   }
   r->kernel_in_lds = ((size_t)r->nw * r->kw <= 8192) ? 1 : 0;
@@ -1679,11 +1707,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_create(int32_t orig_freq
     r->lds_bytes = ((size_t)r->span_floats + (r->kernel_in_lds ? (size_t)r->nw * r->kw : 0)) * sizeof(float);
     if (r->lds_bytes <= 64 * 1024) break;
   }
-  if (r->outs_per_block < 64) {
-    (void)hipFree(r->d_kernel);
-    delete r;
-    return fail(HIPFEAT_ERR_UNSUPPORTED, "resampling ratio %d/%d needs too much LDS", orig_freq, new_freq);
-  }
+  if (r->outs_per_block < 64) return bail(fail(HIPFEAT_ERR_UNSUPPORTED, "resampling ratio %d/%d needs too much LDS", orig_freq, new_freq));
   *out = r;
   return HIPFEAT_OK;
 }
@@ -1694,11 +1718,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resampler_destroy(hipfeat_resample
   (void)hipFree(r->d_kernel);
   if (r->d_kernel_t) (void)hipFree(r->d_kernel_t);
   if (r->d_kernel_mfma) (void)hipFree(r->d_kernel_mfma);
-  for (auto& s : r->slots) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
+  r->ring.free_all();  // (waits for the launches that used a slot)
   delete r;
   return HIPFEAT_OK;
 }
@@ -1727,38 +1747,17 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resample(const hipfeat_resampler* 
   DeviceGuard g(r->device);
   const size_t bytes = cuts.size() * sizeof(ResCut);
   std::lock_guard<std::mutex> lk(r->mu);
-  StagingSlot& s = r->slots[r->next_slot];
-  r->next_slot = (r->next_slot + 1) % 4;
-  if (s.busy) {
-    HIP_TRY(hipEventSynchronize(s.ev));
-    s.busy = false;
-  }
-  if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-  if (s.cap < bytes) {
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = s.d = nullptr;
-    s.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-    HIP_TRY(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.d, cap));
-    s.cap = cap;
-  }
-  std::memcpy(s.h, cuts.data(), bytes);
-  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  StagedSlot& s = r->ring.take();
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(stage(s, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, cuts.data(), bytes); }));
+  const ResCut* d_cuts = static_cast<const ResCut*>(s.d);
   if (r->fast) {
-    r->fast(d_in, d_out, static_cast<const ResCut*>(s.d), r->d_kernel_t, (int)batch, (unsigned)blocks, (hipStream_t)stream);
-    hipError_t e1 = hipGetLastError();
-    hipError_t e2 = hipEventRecord(s.ev, (hipStream_t)stream);
-    s.busy = (e2 == hipSuccess);
-    if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "resample launch failed: %s", hipGetErrorName(e1));
-    return HIPFEAT_OK;
-  }
-  if (r->d_kernel_mfma) {
+    r->fast(d_in, d_out, d_cuts, r->d_kernel_t, (int)batch, (unsigned)blocks, st);
+  } else if (r->d_kernel_mfma) {
     ResMfmaParams mp{};
     mp.in = d_in;
     mp.out = d_out;
-    mp.cuts = static_cast<const ResCut*>(s.d);
+    mp.cuts = d_cuts;
     mp.kt = r->d_kernel_mfma;
     mp.num_cuts = (int32_t)batch;
     mp.orig = r->orig;
@@ -1769,79 +1768,37 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_resample(const hipfeat_resampler* 
     mp.span_floats = r->mfma.span_floats;
     const dim3 grid((unsigned)blocks), wg(256);
     if (r->mfma.hop_tiles == 4)
-      hipLaunchKernelGGL(resample_mfma_kernel<4>, grid, wg, r->mfma.lds_bytes, (hipStream_t)stream, mp);
+      hipLaunchKernelGGL(resample_mfma_kernel<4>, grid, wg, r->mfma.lds_bytes, st, mp);
     else if (r->mfma.hop_tiles == 2)
-      hipLaunchKernelGGL(resample_mfma_kernel<2>, grid, wg, r->mfma.lds_bytes, (hipStream_t)stream, mp);
+      hipLaunchKernelGGL(resample_mfma_kernel<2>, grid, wg, r->mfma.lds_bytes, st, mp);
     else
-      hipLaunchKernelGGL(resample_mfma_kernel<1>, grid, wg, r->mfma.lds_bytes, (hipStream_t)stream, mp);
-    hipError_t e1 = hipGetLastError();
-    hipError_t e2 = hipEventRecord(s.ev, (hipStream_t)stream);
-    s.busy = (e2 == hipSuccess);
-    if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "resample launch failed: %s", hipGetErrorName(e1));
-    return HIPFEAT_OK;
+      hipLaunchKernelGGL(resample_mfma_kernel<1>, grid, wg, r->mfma.lds_bytes, st, mp);
+  } else {
+    ResampleParams rp{};
+    rp.in = d_in;
+    rp.out = d_out;
+    rp.cuts = d_cuts;
+    rp.kernel = r->d_kernel;
+    rp.num_cuts = (int32_t)batch;
+    rp.orig = r->orig;
+    rp.nw = r->nw;
+    rp.kw = r->kw;
+    rp.width = r->width;
+    rp.outs_per_block = r->outs_per_block;
+    rp.span_floats = r->span_floats;
+    rp.kernel_in_lds = r->kernel_in_lds;
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), r->lds_bytes, st, rp);
   }
-  ResampleParams rp{};
-  rp.in = d_in;
-  rp.out = d_out;
-  rp.cuts = static_cast<const ResCut*>(s.d);
-  rp.kernel = r->d_kernel;
-  rp.num_cuts = (int32_t)batch;
-  rp.orig = r->orig;
-  rp.nw = r->nw;
-  rp.kw = r->kw;
-  rp.width = r->width;
-  rp.outs_per_block = r->outs_per_block;
-  rp.span_floats = r->span_floats;
-  rp.kernel_in_lds = r->kernel_in_lds;
-  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), r->lds_bytes, (hipStream_t)stream, rp);
-  hipError_t e1 = hipGetLastError();
-  hipError_t e2 = hipEventRecord(s.ev, (hipStream_t)stream);
-  s.busy = (e2 == hipSuccess);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "resample launch failed: %s", hipGetErrorName(e1));
-  return HIPFEAT_OK;
+  return finish_launches(s, st, hipGetLastError(), "resample", kWaitedLaunch);
 }
 
 // --------------------------------------------------------------------------------------
-// What the arena handles share ("Ticketed handles"): the staging slot, the handle with its ticket ring (ticket_slots.hpp),
-// the two ends of a run, and the grid and table-route rules of the launches that walk a flat item list
+// What the arena handles share ("Ticketed handles"): the handle with its ticket ring (ticket_slots.hpp) and one StagedSlot per
+// ticket, and the grid and table-route rules of the launches that walk a flat item list
 // --------------------------------------------------------------------------------------
-// A pinned host buffer and a device buffer of one capacity, and the event that says when the launches that used them last are done.
-struct StagedSlot : StagingSlot {
-  hipError_t wait() {  // for the launches that used this slot's memory last time
-    if (!busy) return hipSuccess;
-    const hipError_t e = hipEventSynchronize(ev);
-    if (e == hipSuccess) busy = false;
-    return e;
-  }
-  hipError_t reserve(size_t bytes) {  // the event exists and both buffers hold `bytes`; their old contents are not kept
-    hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess || cap >= bytes) return e;
-    if (h) (void)hipHostFree(h);
-    if (d) (void)hipFree(d);
-    h = d = nullptr;
-    cap = 0;
-    const size_t grown = std::max<size_t>(bytes * 2, 1 << 14);
-    if ((e = hipHostMalloc(&h, grown, hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipMalloc(&d, grown)) != hipSuccess) return e;
-    cap = grown;
-    return hipSuccess;
-  }
-  hipError_t record(hipStream_t st) {  // behind the launches; memory its event cannot guard is waited for here instead
-    const hipError_t e = hipEventRecord(ev, st);
-    busy = (e == hipSuccess);
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    return e;
-  }
-  void free_all() {
-    if (busy && ev) (void)hipEventSynchronize(ev);
-    if (h) (void)hipHostFree(h);
-    if (d) (void)hipFree(d);
-    if (ev) (void)hipEventDestroy(ev);
-  }
-};
-
 // Plan hands out a ticket and keeps the validated tables in plans[ticket % kTicketSlots]; run stages them through the slot of the same
-// index.  A ticket is consumed when its launch has been enqueued (finish_run): an argument refusal or a failed allocation leaves it planned.
+// index.  A ticket is released when its launches have been issued (enqueued, or refused by the runtime at launch: the ticket has run), just
+// before finish_launches: an argument refusal or a failed allocation leaves it planned.
 template <typename Plan>
 struct TicketedHandle {
   int device = 0;
@@ -1862,9 +1819,7 @@ template <typename H>
 static hipfeat_status handle_create(int32_t device, H** out, const char* what) {
   if (!out) return fail(HIPFEAT_ERR_INVALID, "%s pointer is NULL", what);
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  if (hipfeat_status bad = check_device(device)) return bad;
   H* h = new (std::nothrow) H();
   if (!h) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
   h->device = device;
@@ -1895,18 +1850,6 @@ static int find_ticket(const TicketRing& tickets, int64_t ticket, const char* wh
   const int slot = tickets.slot_of(ticket);
   if (slot < 0) (void)fail(HIPFEAT_ERR_INVALID, "ticket %lld is not a planned %s (at most %d plans may be outstanding)", (long long)ticket, what, kTicketSlots);
   return slot;
-}
-
-// the end of a run whose launches have been issued (e1: hipGetLastError behind them).  Enqueued, or refused by the runtime at launch:
-// the ticket has run.
-constexpr const char* kWaitedLaunch = "the launch was enqueued and has been waited for";
-constexpr const char* kWaitedLaunches = "the launches were enqueued and have been waited for";
-static hipfeat_status finish_run(TicketRing& tickets, int64_t ticket, StagedSlot& s, hipStream_t st, hipError_t e1, const char* kind, const char* waited) {
-  tickets.release(ticket);
-  const hipError_t e2 = s.record(st);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s launch failed: %s", kind, hipGetErrorName(e1));
-  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s: hipEventRecord failed: %s (%s)", kind, hipGetErrorName(e2), waited);
-  return HIPFEAT_OK;
 }
 
 // a few workgroups per CU take the items round-robin; the grid is the smallest one that gives every workgroup the same number of
@@ -2299,7 +2242,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int6
     if (p.energy_items > 0) hipLaunchKernelGGL(mix_energy_kernel, energy_grid, wg, r.dyn, st, h);
     hipLaunchKernelGGL(mix_kernel, mix_grid, wg, r.dyn, st, h);
   }
-  return finish_run(mixer->tickets, ticket, s, st, hipGetLastError(), "mix", kWaitedLaunches);
+  mixer->tickets.release(ticket);
+  return finish_launches(s, st, hipGetLastError(), "mix", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2363,7 +2307,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int
     hipLaunchKernelGGL(reverb_conv_kernel, grid, wg, r.dyn, st, h);
     hipLaunchKernelGGL(reverb_gain_kernel, grid, wg, r.dyn, st, h);
   }
-  return finish_run(rv->tickets, ticket, s, st, hipGetLastError(), "reverb", kWaitedLaunches);
+  rv->tickets.release(ticket);
+  return finish_launches(s, st, hipGetLastError(), "reverb", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2431,7 +2376,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_level_run(hipfeat_level* lv, int64
     if (any_clip) hipLaunchKernelGGL(level_peak_kernel, grid, wg, r.dyn, st, h);
     hipLaunchKernelGGL(level_apply_kernel, grid, wg, r.dyn, st, h);
   }
-  return finish_run(lv->tickets, ticket, s, st, hipGetLastError(), "level", kWaitedLaunches);
+  lv->tickets.release(ticket);
+  return finish_launches(s, st, hipGetLastError(), "level", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2485,10 +2431,7 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
   DeviceGuard g(c->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = p.rows.size() * sizeof(CoRow);
-  HIP_TRY(s.wait());
-  HIP_TRY(s.reserve(bytes));
-  std::memcpy(s.h, p.rows.data(), bytes);
-  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(stage(s, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, p.rows.data(), bytes); }));
   CoArgs a;
   a.arena = reinterpret_cast<const uint32_t*>(d_arena);
   a.out = d_out;
@@ -2501,7 +2444,8 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
   if (p.out_type == kCoF32) hipLaunchKernelGGL(collate_wave_kernel<float>, dim3(grid), dim3(256), 0, st, a);
   else if (p.out_type == kCoF16) hipLaunchKernelGGL(collate_wave_kernel<__half>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(collate_wave_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, a);
-  return finish_run(c->tickets, ticket, s, st, hipGetLastError(), "collate", kWaitedLaunch);
+  c->tickets.release(ticket);
+  return finish_launches(s, st, hipGetLastError(), "collate", kWaitedLaunch);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2552,17 +2496,15 @@ extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_run(hipfeat_sinc* sc, in
     hipError_t e = ensure_dynamic_lds(entry<sinc_kernel>(), lds);
     if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
   }
-  HIP_TRY(s.wait());
-  HIP_TRY(s.reserve(bytes));
-  std::memcpy(s.h, p.rows.data(), bytes);
-  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(stage(s, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, p.rows.data(), bytes); }));
   SincArgs a;
   a.arena = d_arena;
   a.rows = static_cast<const SincRow*>(s.d);
   a.num_rows = (int32_t)p.rows.size();
   a.pad = 0;
   hipLaunchKernelGGL(sinc_kernel, dim3((unsigned)p.workgroups), dim3(256), lds, st, a);
-  return finish_run(sc->tickets, ticket, s, st, hipGetLastError(), "sinc", kWaitedLaunch);
+  sc->tickets.release(ticket);
+  return finish_launches(s, st, hipGetLastError(), "sinc", kWaitedLaunch);
 }
 
 extern "C" HIPFEAT_SINC_API hipfeat_status hipfeat_sinc_weights(hipfeat_sinc* sc, int32_t src_rate, int32_t dst_rate, float* d_weights, int32_t* d_first,
@@ -2643,11 +2585,10 @@ extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmi
   hipStream_t st = (hipStream_t)stream;
   const size_t cut_bytes = p.cuts.size() * sizeof(FmCut), trk_bytes = p.tracks.size() * sizeof(FmTrack), bytes = cut_bytes + trk_bytes;  // (multiples of 16)
   const size_t part_bytes = (size_t)std::max<int64_t>(p.energy_items, 1) * sizeof(double);
-  HIP_TRY(s.wait());
-  HIP_TRY(s.reserve(bytes + part_bytes));
-  std::memcpy(s.h, p.cuts.data(), cut_bytes);
-  std::memcpy(static_cast<unsigned char*>(s.h) + cut_bytes, p.tracks.data(), trk_bytes);
-  HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(stage(s, bytes + part_bytes, bytes, st, [&](unsigned char* h) {
+    std::memcpy(h, p.cuts.data(), cut_bytes);
+    std::memcpy(h + cut_bytes, p.tracks.data(), trk_bytes);
+  }));
   FmArgs a;
   a.arena = static_cast<const unsigned char*>(d_arena);
   a.out = d_out;
@@ -2666,7 +2607,8 @@ extern "C" HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmi
   if (p.energy_items > 0) hipLaunchKernelGGL(featmix_energy_kernel, dim3(items_grid(p.energy_items)), dim3(256), 0, st, a);
   // a flat 1-D grid over (cut, tile); beyond 2^22 workgroups (2^34 elements) the workgroups stride
   hipLaunchKernelGGL(featmix_fold_kernel, dim3((unsigned)std::min<int64_t>(p.fold_items, (int64_t)1 << 22)), dim3(256), 0, st, a);
-  return finish_run(fm->tickets, ticket, s, st, hipGetLastError(), "feature mix", kWaitedLaunches);
+  fm->tickets.release(ticket);
+  return finish_launches(s, st, hipGetLastError(), "feature mix", kWaitedLaunches);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2681,22 +2623,14 @@ struct hipfeat_stats {
   double* d_state = nullptr;  // [2][F]: total_sum, total_unnorm_var
   double* d_slab = nullptr;   // [blocks][2][F] of the update in flight; grows on demand
   size_t slab_cap = 0;        // bytes
-  StagedSlot slots[kTicketSlots];
-  int next_slot = 0;
-  StagedSlot& take_slot() {
-    StagedSlot& s = slots[next_slot];
-    next_slot = (next_slot + 1) % kTicketSlots;
-    return s;
-  }
+  SlotRing<kTicketSlots> ring;
 };
 
 extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_create(int32_t device, int32_t feature_dim, hipfeat_stats** out) {
   if (!out) return fail(HIPFEAT_ERR_INVALID, "stats pointer is NULL");
   *out = nullptr;
   if (feature_dim < 1 || feature_dim > kStMaxDim) return fail(HIPFEAT_ERR_INVALID, "%d bins per frame (1 ... %d)", (int)feature_dim, kStMaxDim);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(HIPFEAT_ERR_HIP, "device %d not available (%d HIP devices visible)", device, ndev);
+  if (hipfeat_status bad = check_device(device)) return bad;
   DeviceGuard g(device);
   double* state = nullptr;
   const size_t bytes = (size_t)feature_dim * 2 * sizeof(double);
@@ -2720,7 +2654,7 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_create(int32_t device,
 extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_destroy(hipfeat_stats* s) {
   if (!s) return HIPFEAT_OK;
   DeviceGuard g(s->device);
-  for (auto& slot : s->slots) slot.free_all();  // (waits for the launches that used the slot)
+  s->ring.free_all();  // (waits for the launches that used a slot)
   if (s->d_slab) (void)hipFree(s->d_slab);
   if (s->d_state) (void)hipFree(s->d_state);
   delete s;
@@ -2739,7 +2673,7 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* 
   hipStream_t st = (hipStream_t)stream;
   const size_t F = (size_t)s->feature_dim, slab_bytes = (size_t)p.total_blocks * 2 * F * sizeof(double);
   if (s->slab_cap < slab_bytes) {  // the launches that read the old slab are waited for before it goes
-    for (auto& slot : s->slots) HIP_TRY(slot.wait());
+    for (auto& slot : s->ring.slots) HIP_TRY(slot.wait());
     HIP_TRY(hipStreamSynchronize(st));
     if (s->d_slab) (void)hipFree(s->d_slab);
     s->d_slab = nullptr;
@@ -2748,12 +2682,9 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* 
     HIP_TRY(hipMalloc(&s->d_slab, grown));
     s->slab_cap = grown;
   }
-  StagedSlot& slot = s->take_slot();
+  StagedSlot& slot = s->ring.take();
   const size_t bytes = p.cuts.size() * sizeof(StCut);
-  HIP_TRY(slot.wait());
-  HIP_TRY(slot.reserve(bytes));
-  std::memcpy(slot.h, p.cuts.data(), bytes);
-  HIP_TRY(hipMemcpyAsync(slot.d, slot.h, bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(stage(slot, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, p.cuts.data(), bytes); }));
   StArgs a;
   a.feats = d_feats;
   a.cuts = static_cast<const StCut*>(slot.d);
@@ -2770,11 +2701,9 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* 
   if (dtype == kStF16) hipLaunchKernelGGL(stats_partial_kernel<true>, dim3(items_grid(p.items)), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(stats_partial_kernel<false>, dim3(items_grid(p.items)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, st, a);
-  const hipError_t e1 = hipGetLastError(), e2 = slot.record(st);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats launch failed: %s", hipGetErrorName(e1));
-  s->frames += p.total_frames;  // (the launches are enqueued: the state on the stream has them)
-  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats: hipEventRecord failed: %s (%s)", hipGetErrorName(e2), kWaitedLaunches);
-  return HIPFEAT_OK;
+  const hipError_t e1 = hipGetLastError();
+  if (e1 == hipSuccess) s->frames += p.total_frames;  // (the launches are enqueued: the state on the stream has them)
+  return finish_launches(slot, st, e1, "stats", kWaitedLaunches);
 }
 
 extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_merge(hipfeat_stats* s, int64_t frames, const double* h_sum, const double* h_unnorm_var, void* stream) {
@@ -2786,18 +2715,15 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_merge(hipfeat_stats* s
   DeviceGuard g(s->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t F = (size_t)s->feature_dim, bytes = 2 * F * sizeof(double);
-  StagedSlot& slot = s->take_slot();
-  HIP_TRY(slot.wait());
-  HIP_TRY(slot.reserve(bytes));
-  std::memcpy(slot.h, h_sum, bytes / 2);
-  std::memcpy(static_cast<unsigned char*>(slot.h) + bytes / 2, h_unnorm_var, bytes / 2);
-  HIP_TRY(hipMemcpyAsync(slot.d, slot.h, bytes, hipMemcpyHostToDevice, st));
+  StagedSlot& slot = s->ring.take();
+  HIP_TRY(stage(slot, bytes, bytes, st, [&](unsigned char* h) {
+    std::memcpy(h, h_sum, bytes / 2);
+    std::memcpy(h + bytes / 2, h_unnorm_var, bytes / 2);
+  }));
   hipLaunchKernelGGL(stats_merge_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, st, s->d_state, static_cast<const double*>(slot.d), (int)F, s->frames, frames);
-  const hipError_t e1 = hipGetLastError(), e2 = slot.record(st);
-  if (e1 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats merge launch failed: %s", hipGetErrorName(e1));
-  s->frames += frames;
-  if (e2 != hipSuccess) return fail(HIPFEAT_ERR_HIP, "stats: hipEventRecord failed: %s (%s)", hipGetErrorName(e2), kWaitedLaunch);
-  return HIPFEAT_OK;
+  const hipError_t e1 = hipGetLastError();
+  if (e1 == hipSuccess) s->frames += frames;
+  return finish_launches(slot, st, e1, "stats merge", kWaitedLaunch);
 }
 
 extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_get(hipfeat_stats* s, int64_t* h_frames, double* h_sum, double* h_unnorm_var, void* stream) {

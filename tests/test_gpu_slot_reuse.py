@@ -5,7 +5,14 @@ A private handle gets 17 plan -> run pairs on one stream with no host synchronis
 two entries (the kernel-argument route where the kind has one) and make every slot allocate its first 16384 bytes; run 16 lands on
 slot 0 again with a table LARGER than that, so the slot has to wait for run 0's launches, free both buffers and allocate anew before it
 stages.  Every run has its own small arena; after ONE final synchronise, runs 0, 15 and 16 are held to the reference and the tolerance
-of the kind's own GPU test (imported from there: nothing is restated here)."""
+of the kind's own GPU test (imported from there: nothing is restated here).
+
+The entry points without tickets take their slots round-robin from a ring and get the same treatment: hipfeat_extract
+(a plan's ring of 4), hipfeat_resample (a resampler's ring of 4) and hipfeat_stats_update (an accumulator's ring of 16).  One private
+handle gets ring-size small calls and then one whose table is LARGER than any first allocation such a ring has ever made (64 KiB once,
+16384 bytes now), all on one stream with no host synchronisation in between; every call writes a NaN-filled buffer of its own.  After
+ONE final synchronise the first call, the last small one and the big one are bit-equal to the same call made alone, with a synchronise
+behind it, on a second private handle (the accumulator: its state to that of a second one fed update by update)."""
 import numpy as np
 import pytest
 import torch
@@ -17,8 +24,12 @@ import test_gpu_mix
 import test_gpu_reverb
 import test_gpu_sinc
 from _collate_ref import bits_of, collate_ref
+from _hip import make_hip
 
-from lhotse_amd.augmentation import HipCollator, HipLevel, HipMixer, HipReverb, HipSincResampler, mixed_tail_floats, reverb_tail_floats, scaled_rir
+from lhotse_amd import _lib
+from lhotse_amd.augmentation import (HipCollator, HipLevel, HipMixer, HipResampleTensor, HipReverb, HipSincResampler, mixed_tail_floats, reverb_tail_floats,
+                                     scaled_rir)
+from lhotse_amd.stats import HipStatsAccumulator
 
 pytestmark = pytest.mark.gpu
 SLOTS = 16
@@ -26,6 +37,11 @@ FIRST_ALLOCATION = 16384  # bytes a slot holds after its first use with a small 
 RUNS = [1, 2] * (SLOTS // 2)  # entries of the tables of runs 0 ... 15
 CHECKED = (0, SLOTS - 1, SLOTS)
 SINC_ROW_BYTES, LEVEL_ITEM_BYTES, COLLATE_ROW_BYTES = 64, 64, 32  # sizeof(SincRow), sizeof(LvItem), sizeof(CoRow): the static_asserts of csrc/*_tables.hpp
+RING = 4  # slots of a plan's and of a resampler's ring
+FORMER_FIRST_ALLOCATION = 65536  # what the rings of hipfeat_extract and hipfeat_resample allocated at least before they shared StagedSlot::reserve
+CUT_DESC_BYTES = 32  # sizeof(CutDesc): the static_assert of csrc/common.hpp
+RES_CUT_BYTES = 32   # sizeof(ResCut), csrc/kernel_resample.hpp (tests/test_gpu_minibatch.py cites it for the mini-batch blob)
+ST_CUT_BYTES = 16    # sizeof(StCut): the static_assert of csrc/stats_tables.hpp
 
 
 def _lengths(rng, n):
@@ -223,3 +239,93 @@ def _sinc_case(seed, entries):
 def test_sinc():
     cases = [_sinc_case(500 + k, n) for k, n in enumerate(RUNS)] + [_sinc_case(516, 257)]
     _drive(HipSincResampler("cuda:0"), cases)
+
+
+# ---- the rings of the entry points without tickets --------------------------------------------------------------------------------
+def _drive_ring(make_handle, close, calls):
+    """calls: RING + 1 of (issue(handle, out, stream), shape of out, bytes of the table), their inputs already on the device"""
+    assert len(calls) == RING + 1
+    small, big = max(c[2] for c in calls[:RING]), calls[RING][2]
+    assert 4 * small <= FIRST_ALLOCATION and big > FORMER_FIRST_ALLOCATION  # the big table outgrows the slot whatever floor sized it
+    checked = (0, RING - 1, RING)
+    outs = [torch.full(shape, float("nan"), dtype=torch.float32, device="cuda") for _, shape, _ in calls]
+    alone = {k: torch.full(calls[k][1], float("nan"), dtype=torch.float32, device="cuda") for k in checked}
+    stream = torch.cuda.current_stream().cuda_stream
+    handle, second = make_handle(), make_handle()
+    torch.cuda.synchronize()  # the uploads and fills; from here on nothing waits until every call is enqueued
+    for (issue, _, _), out in zip(calls, outs):  # call RING lands on the slot of call 0
+        issue(handle, out, stream)
+    torch.cuda.synchronize()
+    for k in checked:
+        calls[k][0](second, alone[k], stream)
+        torch.cuda.synchronize()
+        got, want = outs[k].cpu().numpy(), alone[k].cpu().numpy()
+        assert np.isfinite(want).all() and np.array_equal(got, want), (k, calls[k][1])
+    close(handle), close(second)
+
+
+def _extract_call(seed, cuts, longest):
+    rng = np.random.default_rng(seed)
+    lens = _lib.i64(rng.integers(400, longest + 1, size=cuts))
+    offs = _lib.i64(np.cumsum(lens) - lens)
+    wave = torch.from_numpy(rng.random(int(lens.sum()), dtype=np.float32) - np.float32(0.5)).cuda()
+
+    def issue(ex, out, stream):
+        plan = ex.plan
+        plan.lib.check("hipfeat_extract", plan.handle, wave.data_ptr(), _lib.addr(offs), _lib.addr(lens), None, cuts, out.data_ptr(), None, 80, stream)
+
+    return issue, (int(((lens + 80) // 160).sum()), 80), cuts * CUT_DESC_BYTES  # (the ragged batch's workgroup map comes on top)
+
+
+def test_extract():
+    calls = [_extract_call(600 + k, n, 2000) for k, n in enumerate(RUNS[:RING])] + [_extract_call(604, 2100, 800)]
+    _drive_ring(lambda: make_hip("fbank", {}), lambda ex: ex.plan.close(), calls)  # (an extractor's plan is its own)
+
+
+def _resample_call(seed, cuts, resampler_of_lengths):
+    rng = np.random.default_rng(seed)
+    lens = _lib.i64(_lengths(rng, cuts))
+    out_lens = _lib.i64(resampler_of_lengths.output_lengths(lens))
+    offs, out_offs = _lib.i64(np.cumsum(lens) - lens), _lib.i64(np.cumsum(out_lens) - out_lens)
+    wave = torch.from_numpy(rng.random(int(lens.sum()), dtype=np.float32) - np.float32(0.5)).cuda()
+
+    def issue(r, out, stream):
+        r.lib.check("hipfeat_resample", r.handle, wave.data_ptr(), _lib.addr(offs), _lib.addr(lens), cuts, out.data_ptr(), _lib.addr(out_offs), stream)
+
+    return issue, (int(out_lens.sum()),), cuts * RES_CUT_BYTES
+
+
+def test_resample():
+    make = lambda: HipResampleTensor(17600, 16000)  # noqa: E731
+    lengths = make()
+    assert lengths.kernel_name == "resample_fast<11,10,7>"  # a compile-time ratio
+    calls = [_resample_call(700 + k, n, lengths) for k, n in enumerate(RUNS[:RING])] + [_resample_call(704, 2100, lengths)]
+    _drive_ring(make, lambda r: r.close(), calls)
+    lengths.close()
+
+
+def test_stats():
+    F = 8
+    rng = np.random.default_rng(800)
+    updates = []
+    for cuts in RUNS + [1100]:
+        frames = _lib.i64(rng.integers(1, 4, size=cuts))
+        updates.append((torch.from_numpy(rng.standard_normal((int(frames.sum()), F)).astype(np.float32)).cuda(), frames))
+    small, big = max(len(f) for _, f in updates[:SLOTS]) * ST_CUT_BYTES, len(updates[SLOTS][1]) * ST_CUT_BYTES
+    assert 2 * small <= FIRST_ALLOCATION < big
+    acc, one_by_one = HipStatsAccumulator(F, "cuda:0"), HipStatsAccumulator(F, "cuda:0")
+    torch.cuda.synchronize()  # the uploads; from here on nothing waits until every update is enqueued
+    for feats, frames in updates:  # update 16 lands on the slot of update 0
+        acc.update(feats, frames)
+    torch.cuda.synchronize()
+    for feats, frames in updates:
+        one_by_one.update(feats, frames)
+        torch.cuda.synchronize()
+    got, want = acc.state(), one_by_one.state()
+    assert got["total_frames"] == want["total_frames"] == sum(int(f.sum()) for _, f in updates)
+    for key in ("total_sum", "total_unnorm_var"):
+        assert np.isfinite(want[key]).all() and np.array_equal(got[key].view(np.uint64), want[key].view(np.uint64)), key
+    got, want = acc.get(), one_by_one.get()
+    for key in ("norm_means", "norm_stds"):
+        assert np.array_equal(got[key].view(np.uint64), want[key].view(np.uint64)), key
+    acc.close(), one_by_one.close()

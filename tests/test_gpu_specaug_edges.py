@@ -226,7 +226,8 @@ def test_the_fill_is_the_mean_of_the_warped_sequence(case):
 def _ring_call(i):
     """Calls 0, 2, 4, ... are (2, 50, 16); calls 1, 3, 5, 7 have B * tiles = 24, 48, 96, 192 partial sums and 3000, 6000, 12000, 24000 masks
     (12 bytes each on the device: 36, 72, 144, 288 KB).  A slot of the four-slot ring is used every fourth call, so it sees a descriptor
-    block four times the one it was sized for (twice that, and 64 KB at least): it has to be released and allocated again."""
+    block four times the one it was sized for and holds twice that one (36 -> 144 KB on slot 1, 72 -> 288 KB on slot 3): it has to be
+    released and allocated again."""
     name = f"ring-{i}"
     if i % 2 == 0:
         x = C.data(name, (2, 50, 16))
