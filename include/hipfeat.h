@@ -42,12 +42,13 @@ extern "C" {
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
  * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES, _SINC_SIGNATURES,
- * _FEATMIX_SIGNATURES and _STATS_SIGNATURES next to _SIGNATURES). */
+ * _FEATMIX_SIGNATURES, _STATS_SIGNATURES and _STFT_SIGNATURES next to _SIGNATURES). */
 #define HIPFEAT_COLLATE_API HIPFEAT_API
 #define HIPFEAT_FEATMIX_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
 #define HIPFEAT_SINC_API HIPFEAT_API
 #define HIPFEAT_STATS_API HIPFEAT_API
+#define HIPFEAT_STFT_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -613,6 +614,65 @@ HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* stats, cons
 HIPFEAT_STATS_API hipfeat_status hipfeat_stats_merge(hipfeat_stats* stats, int64_t frames, const double* h_sum, const double* h_unnorm_var, void* stream);
 HIPFEAT_STATS_API hipfeat_status hipfeat_stats_get(hipfeat_stats* stats, int64_t* h_frames, double* h_sum, double* h_unnorm_var, void* stream);
 HIPFEAT_STATS_API hipfeat_status hipfeat_stats_reset(hipfeat_stats* stats, void* stream);
+
+/* ---- Kaldi frames and their complex STFT on the device (additive to ABI v8) --------------------------------------------- */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_stft_*; the version number did not change because nothing that existed
+ * changed.
+ *
+ * The two layers of lhotse/features/kaldi/layers.py whose output is not a real feature matrix: Wav2Win (layers.py:151-197), the
+ * preprocessed frames, and Wav2FFT (layers.py:309-324), their complex spectrum.  One launch maps a (batch, num_samples) float32
+ * batch of equally long rows -- row b at d_wave + b * row_stride ELEMENTS, the base 4-byte aligned -- to one of two outputs.
+ *
+ * HIPFEAT_STFT_FRAMES.  For frame t, tap i < frame_length, in this order:
+ *   1. the sample at frame_indices (layers.py:727-772): j = t * frame_shift + i when snip_edges, else j = t * frame_shift + i -
+ *      (frame_length - frame_shift) / 2 with the flip-reflection at both ends: j < 0 -> -j - 1, j >= S -> 2 S - 1 - j;
+ *   2. minus the mean of the frame if remove_dc_offset (layers.py:155-157); the mean is a float64 sum rounded to float32 once;
+ *   3. the raw log-energy max(log(sum x^2 + 1e-15), log(energy_floor)) (layers.py:859-870) if want_energy and raw_energy;
+ *   4. pre-emphasis x[i] - c x[max(i - 1, 0)] if preemph_coeff != 0 (layers.py:165-167);
+ *   5. times window[i] (layers.py:170);
+ *   6. zeros for the taps frame_length ... pad_length - 1 (layers.py:173-181);
+ *   7. the log-energy of the windowed frame if want_energy and not raw_energy (layers.py:183-185).
+ * d_out is (batch, T, pad_length) float32 with any pad_length >= frame_length, d_log_energy (batch, T) float32 (may be NULL; it is
+ * written only when want_energy).  frame_length <= 2048.  Only [d_out, d_out + batch * T * pad_length) is written.
+ *
+ * HIPFEAT_STFT_SPECTRUM.  The same frame with pad_length = fft_length, then its real FFT (layers.py:314): bins 0 ... fft_length / 2 as
+ * interleaved (re, im) float32 pairs, rows of fft_length + 2 floats, d_out 8-byte aligned -- a (batch, T, fft_length / 2 + 1) complex64
+ * tensor.  With want_energy bin 0 of every frame is (log_energy, 0) (layers.py:317-318).  fft_length is 256, 512, 1024 or 2048 (8 to 48
+ * kHz at 25 ms): a complex FFT of fft_length / 2 points in three register passes plus the split step, in float32; there is no direct-DFT
+ * path, whose rounding error is not that of the reference's FFT, so every other pad_length -- the frame_length of
+ * round_to_power_of_two=False included -- is HIPFEAT_ERR_UNSUPPORTED at creation.
+ *
+ * dither must be added by the caller (layers.py:191-193 draws torch.randn).  T = hipfeat_num_frames(num_samples, ...); a row too short
+ * for the reflection (hipfeat_check_length) is HIPFEAT_ERR_TOO_SHORT.
+ *
+ * hipfeat_stft_create validates BEFORE any device call: a NULL argument, a struct_size other than sizeof(hipfeat_stft_config),
+ * frame_length <= 0, frame_shift <= 0, pad_length < frame_length, an output other than the two above: HIPFEAT_ERR_INVALID; an unsupported
+ * size: HIPFEAT_ERR_UNSUPPORTED.  h_window[frame_length] is copied.  hipfeat_stft_run enqueues one launch on `stream` and waits for
+ * nothing; out_floats is the capacity of d_out in floats: smaller than batch * T * row floats is HIPFEAT_ERR_INVALID and nothing is
+ * launched, as are negative sizes, row_stride < num_samples with batch > 1, and a NULL or misaligned pointer.  batch == 0, or T == 0 with
+ * snip_edges, is HIPFEAT_OK and launches nothing (without snip_edges a row of no frames is too short, as for hipfeat_extract).  Every call on a NULL object is HIPFEAT_ERR_INVALID and needs no device; destroying NULL is OK.
+ */
+#define HIPFEAT_STFT_FRAMES 0
+#define HIPFEAT_STFT_SPECTRUM 1
+typedef struct hipfeat_stft_config {
+  int32_t struct_size;      /* = sizeof(hipfeat_stft_config); ABI guard                  */
+  int32_t output;           /* HIPFEAT_STFT_FRAMES or HIPFEAT_STFT_SPECTRUM              */
+  int32_t frame_length;     /* N = floor(frame_length_s * sampling_rate) layers.py:114   */
+  int32_t frame_shift;      /* floor(frame_shift_s * sampling_rate)      layers.py:116   */
+  int32_t pad_length;       /* layers.py:121; the fft_length of Wav2FFT  layers.py:265   */
+  int32_t snip_edges;       /* layers.py:747-753                                         */
+  int32_t remove_dc_offset; /* layers.py:155-157                                         */
+  int32_t raw_energy;       /* layers.py:161 vs :183                                     */
+  int32_t want_energy;      /* return_log_energy / use_energy            layers.py:107   */
+  float preemph_coeff;      /* 0 disables                                layers.py:165   */
+  float energy_floor;       /* floored at log(energy_floor) if > 0       layers.py:864   */
+} hipfeat_stft_config;
+typedef struct hipfeat_stft hipfeat_stft;
+HIPFEAT_STFT_API hipfeat_status hipfeat_stft_create(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_stft** out);
+HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* stft);
+HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* stft, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
+                                                 float* d_out, int64_t out_floats, float* d_log_energy, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

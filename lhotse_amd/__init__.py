@@ -42,7 +42,7 @@ from .signal_transforms import HipGlobalMVN, HipSpecAugment  # noqa: F401,E402
 
 from .stats import GlobalStatsPass, HipStatsAccumulator, compute_global_feature_stats, get_or_create_stats  # noqa: F401,E402
 
-from .layers import HipWav2LogFilterBank, HipWav2LogSpec, HipWav2MFCC, HipWav2Spec  # noqa: F401,E402
+from .layers import HipWav2FFT, HipWav2LogFilterBank, HipWav2LogSpec, HipWav2MFCC, HipWav2Spec, HipWav2Win  # noqa: F401,E402
 
 from .storage import HipArchiveF16Writer, HipArchiveReader, HipArchiveWriter, compute_and_store_features_batch  # noqa: F401,E402
 
@@ -61,6 +61,8 @@ __all__ = [
     "GlobalStatsPass",
     "compute_global_feature_stats",
     "get_or_create_stats",
+    "HipWav2Win",
+    "HipWav2FFT",
     "HipWav2Spec",
     "HipWav2LogSpec",
     "HipWav2LogFilterBank",

@@ -177,7 +177,13 @@ _STATS_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     "hipfeat_stats_get": ("int", ["hipfeat_stats*", "int64_t*", "double*", "double*", "void*"]),
     "hipfeat_stats_reset": ("int", ["hipfeat_stats*", "void*"]),
 }
-_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES}
+# Likewise (HIPFEAT_STFT_API in the header).
+_STFT_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_stft_create": ("int", ["const hipfeat_stft_config*", "const float*", "int32_t", "hipfeat_stft**"]),
+    "hipfeat_stft_destroy": ("int", ["hipfeat_stft*"]),
+    "hipfeat_stft_run": ("int", ["hipfeat_stft*", "const float*", "int64_t", "int64_t", "int64_t", "float*", "int64_t", "float*", "void*"]),
+}
+_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -209,6 +215,25 @@ CONFIG_DTYPE = np.dtype(
     ],
     align=True,
 )
+
+# numpy mirror of `struct hipfeat_stft_config`
+STFT_CONFIG_DTYPE = np.dtype(
+    [
+        ("struct_size", "<i4"),
+        ("output", "<i4"),
+        ("frame_length", "<i4"),
+        ("frame_shift", "<i4"),
+        ("pad_length", "<i4"),
+        ("snip_edges", "<i4"),
+        ("remove_dc_offset", "<i4"),
+        ("raw_energy", "<i4"),
+        ("want_energy", "<i4"),
+        ("preemph_coeff", "<f4"),
+        ("energy_floor", "<f4"),
+    ],
+    align=True,
+)
+STFT_FRAMES, STFT_SPECTRUM = 0, 1
 
 # numpy mirrors of `hipfeat_warp_segment` / `hipfeat_mask`
 WARP_SEGMENT_DTYPE = np.dtype([("sequence", "<i4"), ("start", "<i4"), ("num_frames", "<i4"), ("center", "<i4"), ("warped", "<i4")])
@@ -269,7 +294,7 @@ class _CffiBackend:
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
-                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", ""))
+                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

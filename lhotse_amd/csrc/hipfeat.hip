@@ -42,6 +42,7 @@
 #include "kernel_fft256.hpp"
 #include "kernel_fft256c.hpp"
 #include "kernel_wave.hpp"
+#include "kernel_stft.hpp"
 #include "host_bulk.hpp"
 
 using namespace hipfeat;
@@ -2744,6 +2745,150 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_reset(hipfeat_stats* s
   DeviceGuard g(s->device);
   HIP_TRY(hipMemsetAsync(s->d_state, 0, (size_t)s->feature_dim * 2 * sizeof(double), (hipStream_t)stream));
   s->frames = 0;
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Kaldi frames (Wav2Win, layers.py:151-197) and their complex STFT (Wav2FFT, layers.py:309-324) of a uniform batch: one launch of
+// scalar arguments (kernel_stft.hpp)
+// --------------------------------------------------------------------------------------
+struct hipfeat_stft {
+  hipfeat_stft_config cfg{};
+  int device = 0;
+  int n1 = 0;  // 64 n1 complex points per frame (spectrum: fft / 128; frames: the smallest of 2, 4, 8, 16 that holds the frame)
+  const void* fn = nullptr;
+  size_t lds = 0;
+  float* d_window = nullptr;
+  float2* d_tw = nullptr;  // spectrum: W_fft^k, k < fft / 2
+};
+constexpr int kStftFramesPerWave = 8;  // 4 waves x 8 frames per workgroup, as the wave kernel
+
+static const void* stft_entry(int n1, int output) {
+  switch (n1 * 2 + output) {
+    case 4: return entry<stft_kernel<2, 0>>();
+    case 5: return entry<stft_kernel<2, 1>>();
+    case 8: return entry<stft_kernel<4, 0>>();
+    case 9: return entry<stft_kernel<4, 1>>();
+    case 16: return entry<stft_kernel<8, 0>>();
+    case 17: return entry<stft_kernel<8, 1>>();
+    case 32: return entry<stft_kernel<16, 0>>();
+    default: return entry<stft_kernel<16, 1>>();
+  }
+}
+
+extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_create(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_stft** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "stft pointer is NULL");
+  *out = nullptr;
+  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (cfg->struct_size != (int32_t)sizeof(hipfeat_stft_config))
+    return fail(HIPFEAT_ERR_INVALID, "hipfeat_stft_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_stft_config));
+  if (cfg->output != HIPFEAT_STFT_FRAMES && cfg->output != HIPFEAT_STFT_SPECTRUM) return fail(HIPFEAT_ERR_INVALID, "unknown output %d", (int)cfg->output);
+  if (cfg->frame_length <= 0 || cfg->frame_shift <= 0)
+    return fail(HIPFEAT_ERR_INVALID, "frame_length = %d, frame_shift = %d: both must be positive", (int)cfg->frame_length, (int)cfg->frame_shift);
+  if (cfg->pad_length < cfg->frame_length)
+    return fail(HIPFEAT_ERR_INVALID, "pad_length (or fft_length) = %d cannot be smaller than N = %d", (int)cfg->pad_length, (int)cfg->frame_length);
+  int n1 = 0;
+  if (cfg->output == HIPFEAT_STFT_SPECTRUM) {
+    const int fft = cfg->pad_length;
+    if (fft != 256 && fft != 512 && fft != 1024 && fft != 2048)
+      return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the device STFT has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)", fft);
+    n1 = fft / 128;
+  } else {
+    if (cfg->frame_length > 2048) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_length = %d: the device front end holds frames of at most 2048 samples", (int)cfg->frame_length);
+    for (n1 = 2; 128 * n1 < cfg->frame_length; n1 *= 2) {
+    }
+  }
+  if (hipfeat_status bad = check_device(device)) return bad;
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+      return fail(HIPFEAT_ERR_UNSUPPORTED, "device %d is not a gfx950 (MI355X-class) GPU: libhipfeat is built for that architecture alone", device);
+  }
+  DeviceGuard g(device);
+  hipfeat_stft* s = new (std::nothrow) hipfeat_stft();
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  s->cfg = *cfg;
+  s->device = device;
+  s->n1 = n1;
+  s->fn = stft_entry(n1, cfg->output);
+  s->lds = stft_lds_bytes(n1, cfg->output, cfg->frame_length);
+  hipfeat_status st = upload(&s->d_window, h_window, (size_t)cfg->frame_length);
+  if (st == HIPFEAT_OK && cfg->output == HIPFEAT_STFT_SPECTRUM) {  // twiddles, computed in double: W_fft^k = exp(-2 pi i k / fft)
+    const int fft = cfg->pad_length;
+    std::vector<float2> tw(fft / 2);
+    for (int k = 0; k < fft / 2; ++k) {
+      const double a = -2.0 * M_PI * (double)k / (double)fft;
+      tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    st = upload(&s->d_tw, tw.data(), tw.size());
+  }
+  if (st == HIPFEAT_OK) {
+    const hipError_t e = ensure_dynamic_lds(s->fn, s->lds);
+    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", s->lds, hipGetErrorName(e));
+  }
+  if (st != HIPFEAT_OK) {
+    (void)hipFree(s->d_window);
+    (void)hipFree(s->d_tw);
+    delete s;
+    return st;
+  }
+  *out = s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* s) {
+  if (!s) return HIPFEAT_OK;
+  DeviceGuard g(s->device);
+  (void)hipFree(s->d_window);
+  (void)hipFree(s->d_tw);
+  delete s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* s, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
+                                                            float* d_out, int64_t out_floats, float* d_log_energy, void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  const hipfeat_stft_config& c = s->cfg;
+  if (batch < 0 || num_samples < 0 || out_floats < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  if (batch > 1 && row_stride < num_samples) return fail(HIPFEAT_ERR_INVALID, "row_stride = %lld < num_samples = %lld", (long long)row_stride, (long long)num_samples);
+  const int64_t T = hipfeat_num_frames(num_samples, c.frame_length, c.frame_shift, c.snip_edges);
+  if (batch == 0) return HIPFEAT_OK;
+  // (without snip_edges a row of no frames is too short as well, as for the feature plans)
+  if (hipfeat_status bad = hipfeat_check_length(num_samples, c.frame_length, c.frame_shift, c.snip_edges)) return bad;
+  if (T == 0) return HIPFEAT_OK;
+  const int64_t width = c.output == HIPFEAT_STFT_SPECTRUM ? (int64_t)c.pad_length + 2 : (int64_t)c.pad_length;
+  if (batch > INT64_MAX / T || batch * T > INT64_MAX / width) return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
+  if (out_floats < batch * T * width)
+    return fail(HIPFEAT_ERR_INVALID, "output of %lld floats, %lld x %lld x %lld needed", (long long)out_floats, (long long)batch, (long long)T, (long long)width);
+  if (!d_wave || !d_out) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
+  const int align = c.output == HIPFEAT_STFT_SPECTRUM ? 8 : 4;
+  if (reinterpret_cast<uintptr_t>(d_wave) % 4 || reinterpret_cast<uintptr_t>(d_out) % align || reinterpret_cast<uintptr_t>(d_log_energy) % 4)
+    return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples and log-energies: 4 bytes, output: %d)", align);
+  const int64_t fpb = 4 * kStftFramesPerWave, bpr = (T + fpb - 1) / fpb;
+  if (bpr > INT32_MAX / batch) return fail(HIPFEAT_ERR_UNSUPPORTED, "%lld workgroups in one launch", (long long)batch * (long long)bpr);
+  StftParams p{};
+  p.wave = d_wave;
+  p.out = d_out;
+  p.log_energy = c.want_energy ? d_log_energy : nullptr;
+  p.window = s->d_window;
+  p.tw = s->d_tw;
+  p.row_stride = row_stride;
+  p.num_samples = num_samples;
+  p.frames_per_row = T;
+  p.blocks_per_row = bpr;
+  p.N = c.frame_length;
+  p.shift = c.frame_shift;
+  p.pad = c.pad_length;
+  p.npad_left = c.snip_edges ? 0 : (c.frame_length - c.frame_shift) / 2;
+  p.frames_per_wave = kStftFramesPerWave;
+  p.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.want_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0);
+  p.preemph = c.preemph_coeff;
+  p.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
+  void* args[] = {&p};
+  DeviceGuard g(s->device);
+  set_lds_poison(s->lds);
+  (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->lds, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
   return HIPFEAT_OK;
 }
 

@@ -7,11 +7,16 @@ defaults (in the same order), same attributes, ``forward(x)`` maps a ``(B, T)`` 
 waveforms on the GPU to ``(B, num_frames, F)`` on the same device -- one fused launch instead of the ~12 tensor ops of
 ``Wav2Win`` + ``_rfft`` + matmul + log.  Not covered, by design: autograd (inputs that
 require grad are refused), TorchScript, ``online_inference``.
+
+``HipWav2Win`` (:59-197) and ``HipWav2FFT`` (:227-324) hand out what the four above compute on the way and discard: the preprocessed
+frames, ``(B, num_frames, pad_length)`` with the optional ``(B, num_frames)`` log-energies, and their complex STFT,
+``(B, num_frames, fft_length / 2 + 1)`` ``complex64`` -- one launch of ``hipfeat_stft_run`` each, under the same restrictions.
 """
 from __future__ import annotations
 
+import warnings
 from types import SimpleNamespace
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -20,7 +25,7 @@ from . import _lib, constants
 from . import extractors as _E
 from .compat import EPSILON, Seconds
 
-__all__ = ["HipWav2Spec", "HipWav2LogSpec", "HipWav2LogFilterBank", "HipWav2MFCC"]
+__all__ = ["HipWav2Win", "HipWav2FFT", "HipWav2Spec", "HipWav2LogSpec", "HipWav2LogFilterBank", "HipWav2MFCC"]
 
 
 class _HipLayer(torch.nn.Module):
@@ -144,3 +149,211 @@ class HipWav2MFCC(_HipLayer):
                                    dither, snip_edges, energy_floor, raw_energy, use_energy), use_fft_mag=use_fft_mag, low_freq=low_freq,
                          high_freq=high_freq, num_filters=num_filters, norm_filters=norm_filters, num_ceps=num_ceps,
                          cepstral_lifter=cepstral_lifter, torchaudio_compatible_mel_scale=torchaudio_compatible_mel_scale)
+
+
+# --------------------------------------------------------------------------------------
+# Wav2Win / Wav2FFT: the two layers whose output is not a real feature matrix (hipfeat_stft_*, csrc/kernel_stft.hpp)
+# --------------------------------------------------------------------------------------
+class _Stft:
+    """Owns one ``hipfeat_stft`` handle: the window (and twiddles) of one configuration on one device."""
+
+    def __init__(self, output: int, n: int, shift: int, pad: int, layer, window: np.ndarray, device: torch.device):
+        self.lib = _lib.load()
+        self.handle = 0
+        if device.type != "cuda":
+            raise _lib.HipFeatError(1, f"Hip* layers run on an AMD GPU ('cuda[:i]' device), got device={device}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.output, self.n, self.shift, self.pad = output, n, shift, pad
+        self.snip_edges = bool(layer.snip_edges)
+        self.want_energy = bool(layer.return_log_energy)
+        self.width = pad + 2 if output == _lib.STFT_SPECTRUM else pad
+        cfg = np.zeros(1, dtype=_lib.STFT_CONFIG_DTYPE)
+        cfg["struct_size"] = _lib.STFT_CONFIG_DTYPE.itemsize
+        cfg["output"], cfg["frame_length"], cfg["frame_shift"], cfg["pad_length"] = output, n, shift, pad
+        cfg["snip_edges"], cfg["remove_dc_offset"] = int(self.snip_edges), int(bool(layer.remove_dc_offset))
+        cfg["raw_energy"], cfg["want_energy"] = int(bool(layer.raw_energy)), int(self.want_energy)
+        cfg["preemph_coeff"], cfg["energy_floor"] = float(layer.preemph_coeff), float(layer.energy_floor)
+        window = np.ascontiguousarray(window, dtype=np.float32)
+        assert window.shape == (n,)
+        handle = np.zeros(1, dtype=np.uint64)
+        self.lib.check("hipfeat_stft_create", _lib.addr(cfg), _lib.addr(window), int(self.device.index), _lib.addr(handle))
+        self.handle = int(handle[0])
+        _lib.note_plan_created()
+
+    def run(self, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """x: (B, S) float32 on the handle's device -> ((B, T, width) float32, (B, T) log-energies or None), on the current stream."""
+        B, S = x.shape
+        if (S > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < S):
+            x = x.contiguous()
+        frames = int(self.lib.raw("hipfeat_num_frames", S, self.n, self.shift, int(self.snip_edges)))
+        with torch.cuda.device(self.device):
+            out = torch.empty((B, frames, self.width), dtype=torch.float32, device=self.device)
+            # the spectrum carries its log-energy in bin 0: no separate row of them is asked for
+            want_rows = self.want_energy and self.output == _lib.STFT_FRAMES
+            log_e = torch.empty((B, frames), dtype=torch.float32, device=self.device) if want_rows else None
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.lib.check("hipfeat_stft_run", self.handle, x.data_ptr(), B, S, int(x.stride(0)) if B > 1 else S, out.data_ptr(), out.numel(),
+                           None if log_e is None else log_e.data_ptr(), int(stream))
+        return out, log_e
+
+    def close(self) -> None:
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_stft_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_waveforms(layer, x) -> Tuple[torch.Tensor, bool]:
+    """The argument checks of ``_HipLayer.forward``: a float32 ``(B, T)`` or ``(T,)`` tensor that does not ask for a gradient."""
+    name = type(layer).__name__
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}.forward expects a torch.Tensor, got {type(x).__name__}")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} is inference-only (no autograd); call it under torch.no_grad() or detach the input")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32 samples, got {x.dtype}")
+    squeeze = x.ndim == 1
+    if squeeze:
+        x = x.unsqueeze(0)
+    assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
+    return x.detach(), squeeze
+
+
+class HipWav2Win(torch.nn.Module):
+    """Kaldi preprocessing (DC offset, pre-emphasis, window, zero padding to ``pad_length``) of overlapping frames: the reference's
+    ``Wav2Win`` (layers.py:59-197).  ``forward(x)`` returns the 2-tuple ``(frames, log_energy or None)`` with ``frames`` of shape
+    ``(B, num_frames, pad_length)`` and ``log_energy`` of shape ``(B, num_frames)`` when ``return_log_energy``."""
+
+    _output = _lib.STFT_FRAMES
+
+    def __init__(self, sampling_rate: int = 16000, frame_length: Seconds = 0.025, frame_shift: Seconds = 0.01, pad_length: Optional[int] = None,
+                 remove_dc_offset: bool = True, preemph_coeff: float = 0.97, window_type: str = "povey", dither: float = 0.0,
+                 snip_edges: bool = False, energy_floor: float = EPSILON, raw_energy: bool = True, return_log_energy: bool = False) -> None:
+        super().__init__()
+        self.sampling_rate = sampling_rate
+        self.frame_length = frame_length
+        self.frame_shift = frame_shift
+        self.remove_dc_offset = remove_dc_offset
+        self.preemph_coeff = preemph_coeff
+        self.window_type = window_type
+        self.dither = dither
+        self.snip_edges = snip_edges
+        self.energy_floor = energy_floor
+        self.raw_energy = raw_energy
+        self.return_log_energy = return_log_energy
+        if snip_edges:
+            warnings.warn("Setting snip_edges=True is generally incompatible with Lhotse -- "
+                          "you might experience mismatched duration/num_frames errors.")
+        n, shift, _ = constants.frame_sizes(sampling_rate, frame_length, frame_shift, False)
+        self._length = n
+        self._shift = shift
+        self._window = torch.nn.Parameter(torch.from_numpy(np.array(constants.make_window(n, window_type), dtype=np.float32)), requires_grad=False)
+        self.pad_length = n if pad_length is None else pad_length
+        assert self.pad_length >= n, f"pad_length (or fft_length) = {pad_length} cannot be smaller than N = {n}"
+        self._handles = {}
+
+    def __repr__(self):
+        return self.__str__()
+
+    def __str__(self):
+        return ("{}(sampling_rate={}, frame_length={}, frame_shift={}, pad_length={}, remove_dc_offset={}, preemph_coeff={}, window_type={} "
+                "dither={}, snip_edges={}, energy_floor={}, raw_energy={}, return_log_energy={})").format(
+                    self.__class__.__name__, self.sampling_rate, self.frame_length, self.frame_shift, self.pad_length, self.remove_dc_offset,
+                    self.preemph_coeff, self.window_type, self.dither, self.snip_edges, self.energy_floor, self.raw_energy, self.return_log_energy)
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st["_handles"] = {}  # device handles are per process
+        return st
+
+    def _handle_for(self, device: torch.device, output: int) -> _Stft:
+        key = (device.type, device.index, output)
+        h = self._handles.get(key)
+        if h is None:
+            try:
+                h = _Stft(output, self._length, self._shift, self.pad_length, self, self._window.detach().cpu().numpy(), device)
+            except _lib.HipFeatError as e:
+                if e.status == _lib.ERR_UNSUPPORTED:
+                    raise NotImplementedError(
+                        f"{e} -- the device layers have the FFT sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True) and frames of at "
+                        f"most 2048 samples; this layer has frame length {self._length} and pad / fft length {self.pad_length}") from e
+                raise
+            self._handles[key] = h
+        return h
+
+    def _run(self, x: torch.Tensor, output: int) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
+        x, squeeze = _check_waveforms(self, x)
+        handle = self._handle_for(x.device, output)
+        if self.dither != 0.0:  # layers.py:191-193
+            x = x + self.dither * torch.randn(x.shape, device=x.device)
+        try:
+            out, log_e = handle.run(x)
+        except _lib.HipFeatError as e:
+            if e.status == _lib.ERR_TOO_SHORT:
+                raise ValueError(str(e)) from e
+            raise
+        return out, log_e, squeeze
+
+    def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        out, log_e, squeeze = self._run(x, self._output)
+        if squeeze:
+            return out[0], (None if log_e is None else log_e[0])
+        return out, log_e
+
+
+class HipWav2FFT(torch.nn.Module):
+    """The complex STFT of the Kaldi-preprocessed frames: the reference's ``Wav2FFT`` (layers.py:227-324).  ``forward(x)`` returns a
+    ``complex64`` tensor of shape ``(B, num_frames, fft_length / 2 + 1)``; ``use_energy`` (default True) puts the log-energy in bin 0."""
+
+    def __init__(self, sampling_rate: int = 16000, frame_length: Seconds = 0.025, frame_shift: Seconds = 0.01, round_to_power_of_two: bool = True,
+                 remove_dc_offset: bool = True, preemph_coeff: float = 0.97, window_type: str = "povey", dither: float = 0.0,
+                 snip_edges: bool = False, energy_floor: float = EPSILON, raw_energy: bool = True, use_energy: bool = True) -> None:
+        super().__init__()
+        self.use_energy = use_energy
+        _, _, self.fft_length = constants.frame_sizes(sampling_rate, frame_length, frame_shift, round_to_power_of_two)
+        self.wav2win = HipWav2Win(sampling_rate, frame_length, frame_shift, pad_length=self.fft_length, remove_dc_offset=remove_dc_offset,
+                                  preemph_coeff=preemph_coeff, window_type=window_type, dither=dither, snip_edges=snip_edges,
+                                  energy_floor=energy_floor, raw_energy=raw_energy, return_log_energy=use_energy)
+
+    @property
+    def sampling_rate(self) -> int:
+        return self.wav2win.sampling_rate
+
+    @property
+    def frame_length(self) -> Seconds:
+        return self.wav2win.frame_length
+
+    @property
+    def frame_shift(self) -> Seconds:
+        return self.wav2win.frame_shift
+
+    @property
+    def remove_dc_offset(self) -> bool:
+        return self.wav2win.remove_dc_offset
+
+    @property
+    def preemph_coeff(self) -> float:
+        return self.wav2win.preemph_coeff
+
+    @property
+    def window_type(self) -> str:
+        return self.wav2win.window_type
+
+    @property
+    def dither(self) -> float:
+        return self.wav2win.dither
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _check_waveforms(self, x)  # (refusals name this layer)
+        out, _, squeeze = self.wav2win._run(x, _lib.STFT_SPECTRUM)
+        spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
+        return spec[0] if squeeze else spec
