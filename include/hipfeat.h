@@ -49,6 +49,7 @@ extern "C" {
 #define HIPFEAT_SINC_API HIPFEAT_API
 #define HIPFEAT_STATS_API HIPFEAT_API
 #define HIPFEAT_STFT_API HIPFEAT_API
+#define HIPFEAT_STREAM_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -673,6 +674,56 @@ HIPFEAT_STFT_API hipfeat_status hipfeat_stft_create(const hipfeat_stft_config* c
 HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* stft);
 HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* stft, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
                                                  float* d_out, int64_t out_floats, float* d_log_energy, void* stream);
+
+/* ---- streaming layers: online_inference of the six Kaldi layers (additive to ABI v8) ------------------------------------- */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_stream_*; the version number did not change because nothing that existed
+ * changed.
+ *
+ * Every layer of lhotse/features/kaldi/layers.py has online_inference(x, context=None) next to forward (layers.py:199-224, 326-333 and
+ * 775-856): a chunk x of chunk_len = S samples per row is framed together with what the previous call left over, and what this call
+ * leaves over is returned.  One launch does all of it.  With N = frame_length, s = frame_shift, P = (N - s) / 2:
+ *
+ *   virtual waveform  V = [A | x] of L = R + S samples.  A is the context, R = context_len samples per row (ANY R >= 0, not only a
+ *                     remainder this library returned), when d_context is not NULL.  d_context == NULL is the start of a stream:
+ *                     A is empty with snip_edges, else the flipped head of the chunk, R = min(P, S), A(j) = x[R - 1 - j] -- a first chunk
+ *                     shorter than P reflects only what it has.  Index map: V(j) = A(j) for j < R, x[j - R] otherwise.
+ *   frames            frame f is V[f s : f s + N] for f < T, T = 1 + (L - N) / s when L >= N -- the same number under both snip_edges
+ *                     values.  A stream has no end, so nothing is ever reflected on the right.
+ *   per frame         the arithmetic of hipfeat_stft_run (frames, spectrum) or of the wave-per-frame feature kernel (the four kinds of
+ *                     hipfeat_config), by one wave from the frame's own samples alone: the output of a stream does not depend on how it
+ *                     was cut into chunks, bit for bit.
+ *   remainder         V[T s : L], L - T s < N samples per row, written to row b of d_remainder, a contiguous (batch, L - T s) matrix.
+ *   zero-frame rule   L < N: T = 0, nothing is written to d_out, and all of V is the remainder.  (The reference raises there; this lets a
+ *                     caller feed chunks shorter than a frame.)
+ *
+ * hipfeat_stream_counts is host arithmetic and needs no device: T and the remainder length of one call; `first` != 0 is the start of a
+ * stream (context_len must be 0 then).  hipfeat_stream_create_stft takes the configuration of hipfeat_stft_create (frames of any
+ * pad_length, or the spectrum), hipfeat_stream_create_features that of hipfeat_plan_create for the kinds HIPFEAT_SPECTROGRAM ...
+ * HIPFEAT_MFCC; the feature handle builds the wave-per-frame kernel's tables itself and serves EVERY supported configuration with that
+ * one kernel body (one arithmetic for every chunking), also where hipfeat_extract picks a specialised kernel -- so a streamed feature
+ * row agrees with hipfeat_extract's to rounding, not bit for bit.  Rows: context row b at d_context + b * context_stride ELEMENTS, chunk
+ * row b at d_chunk + b * chunk_stride, any stride >= the row, bases 4-byte aligned; d_out as for hipfeat_stft_run (the spectrum 8-byte
+ * aligned) or (batch, T, feature_dim) float32; d_log_energy (batch, T) is written by a frames handle with want_energy (may be NULL) and
+ * by no other.  dither must be added to the chunk by the caller.
+ *
+ * Statuses, as for hipfeat_stft_*: NULL arguments, negative sizes, a NULL context with context_len != 0, misaligned pointers, buffers
+ * smaller than batch * T * row / batch * (L - T s) floats and (batch > 1) a stride shorter than its row are HIPFEAT_ERR_INVALID and
+ * launch nothing; an fft_length other than 256, 512, 1024 or 2048, frames of more than 2048 samples, more than 128 filters, frame_shift >
+ * frame_length, kinds beyond the four and a device that is not a gfx950 are HIPFEAT_ERR_UNSUPPORTED.  Every refusal that does not depend
+ * on the device comes BEFORE any device call.  batch == 0 is HIPFEAT_OK and launches nothing.  Every call on a NULL object is
+ * HIPFEAT_ERR_INVALID and needs no device; destroying NULL is OK.
+ */
+typedef struct hipfeat_stream hipfeat_stream;
+HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_counts(int32_t frame_length, int32_t frame_shift, int32_t snip_edges, int32_t first,
+                                                        int64_t context_len, int64_t chunk_len, int64_t* frames, int64_t* remainder_len);
+HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_features(const hipfeat_config* cfg, const float* h_window, const float* h_mel,
+                                                                 const float* h_dct, const float* h_lifter, int32_t device, hipfeat_stream** out);
+HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_stft(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_stream** out);
+HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* stream_handle, const float* d_context, int64_t context_len, int64_t context_stride,
+                                                     const float* d_chunk, int64_t chunk_len, int64_t chunk_stride, int64_t batch, float* d_out,
+                                                     int64_t out_floats, float* d_log_energy, float* d_remainder, int64_t remainder_floats, void* stream);
+HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_destroy(hipfeat_stream* stream_handle);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

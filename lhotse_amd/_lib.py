@@ -183,7 +183,23 @@ _STFT_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     "hipfeat_stft_destroy": ("int", ["hipfeat_stft*"]),
     "hipfeat_stft_run": ("int", ["hipfeat_stft*", "const float*", "int64_t", "int64_t", "int64_t", "float*", "int64_t", "float*", "void*"]),
 }
-_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES}
+# Likewise (HIPFEAT_STREAM_API in the header).
+_STREAM_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_stream_counts": ("int", ["int32_t", "int32_t", "int32_t", "int32_t", "int64_t", "int64_t", "int64_t*", "int64_t*"]),
+    "hipfeat_stream_create_features": (
+        "int",
+        ["const hipfeat_config*", "const float*", "const float*", "const float*", "const float*", "int32_t", "hipfeat_stream**"],
+    ),
+    "hipfeat_stream_create_stft": ("int", ["const hipfeat_stft_config*", "const float*", "int32_t", "hipfeat_stream**"]),
+    "hipfeat_stream_run": (
+        "int",
+        ["hipfeat_stream*", "const float*", "int64_t", "int64_t", "const float*", "int64_t", "int64_t", "int64_t", "float*", "int64_t", "float*", "float*",
+         "int64_t", "void*"],
+    ),
+    "hipfeat_stream_destroy": ("int", ["hipfeat_stream*"]),
+}
+_ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
+                     **_STREAM_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -294,7 +310,7 @@ class _CffiBackend:
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
-                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", ""))
+                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

@@ -43,6 +43,7 @@
 #include "kernel_fft256c.hpp"
 #include "kernel_wave.hpp"
 #include "kernel_stft.hpp"
+#include "kernel_stream.hpp"
 #include "host_bulk.hpp"
 
 using namespace hipfeat;
@@ -2885,6 +2886,309 @@ extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* s, con
   p.preemph = c.preemph_coeff;
   p.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
   void* args[] = {&p};
+  DeviceGuard g(s->device);
+  set_lds_poison(s->lds);
+  (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->lds, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Streaming layers (online_inference, layers.py:199-224, 326-333, 775-856): one launch frames V = [context | chunk], computes what
+// `forward` computes per frame and writes the remainder (kernel_stream.hpp)
+// --------------------------------------------------------------------------------------
+struct hipfeat_stream {
+  bool features = false;
+  hipfeat_config fcfg{};       // features
+  hipfeat_stft_config scfg{};  // frames / spectrum
+  int device = 0, n1 = 0;
+  int N = 0, shift = 0, snip = 0, width = 0;  // width: floats per output row
+  int H = 0, K = 0, blob_floats = 0, dct_in_lds = 0;
+  const void* fn = nullptr;
+  size_t lds = 0;
+  float* d_window = nullptr;
+  float2* d_tw = nullptr;
+  float* d_mel_blob = nullptr;
+  float* d_dct = nullptr;
+  float* d_lifter = nullptr;
+};
+
+static void stream_free(hipfeat_stream* s) {
+  if (!s) return;
+  (void)hipFree(s->d_window);
+  (void)hipFree(s->d_tw);
+  (void)hipFree(s->d_mel_blob);
+  (void)hipFree(s->d_dct);
+  (void)hipFree(s->d_lifter);
+  delete s;
+}
+
+static const void* stream_wave_entry(int n1) {
+  return n1 == 2 ? entry<wave_stream_kernel<2>>() : (n1 == 4 ? entry<wave_stream_kernel<4>>() : (n1 == 8 ? entry<wave_stream_kernel<8>>() : entry<wave_stream_kernel<16>>()));
+}
+
+static const void* stream_stft_entry(int n1, int output) {
+  switch (n1 * 2 + output) {
+    case 4: return entry<stft_stream_kernel<2, 0>>();
+    case 5: return entry<stft_stream_kernel<2, 1>>();
+    case 8: return entry<stft_stream_kernel<4, 0>>();
+    case 9: return entry<stft_stream_kernel<4, 1>>();
+    case 16: return entry<stft_stream_kernel<8, 0>>();
+    case 17: return entry<stft_stream_kernel<8, 1>>();
+    case 32: return entry<stft_stream_kernel<16, 0>>();
+    default: return entry<stft_stream_kernel<16, 1>>();
+  }
+}
+
+static hipfeat_status stream_check_gfx950(int device) {
+  if (hipfeat_status bad = check_device(device)) return bad;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "device %d is not a gfx950 (MI355X-class) GPU: libhipfeat is built for that architecture alone", device);
+  return HIPFEAT_OK;
+}
+
+static std::vector<float2> stream_twiddles(int fft) {  // computed in double: W_fft^k = exp(-2 pi i k / fft), k < fft / 2
+  std::vector<float2> tw(fft / 2);
+  for (int k = 0; k < fft / 2; ++k) {
+    const double a = -2.0 * M_PI * (double)k / (double)fft;
+    tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+  }
+  return tw;
+}
+
+static bool stream_fft_size(int fft) { return fft == 256 || fft == 512 || fft == 1024 || fft == 2048; }
+
+extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_counts(int32_t frame_length, int32_t frame_shift, int32_t snip_edges, int32_t first,
+                                                                   int64_t context_len, int64_t chunk_len, int64_t* frames, int64_t* remainder_len) {
+  if (!frames || !remainder_len) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  *frames = *remainder_len = 0;
+  if (frame_length <= 0 || frame_shift <= 0)
+    return fail(HIPFEAT_ERR_INVALID, "frame_length = %d, frame_shift = %d: both must be positive", (int)frame_length, (int)frame_shift);
+  if (context_len < 0 || chunk_len < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  if (first && context_len != 0) return fail(HIPFEAT_ERR_INVALID, "the first call of a stream has no context, context_len = %lld", (long long)context_len);
+  if (frame_shift > frame_length) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", (int)frame_shift, (int)frame_length);
+  const int64_t head = first ? (snip_edges ? 0 : std::min<int64_t>((frame_length - frame_shift) / 2, chunk_len)) : context_len;
+  if (head > INT64_MAX - chunk_len) return fail(HIPFEAT_ERR_INVALID, "%lld + %lld samples overflow", (long long)head, (long long)chunk_len);
+  const int64_t L = head + chunk_len;
+  const int64_t T = L < frame_length ? 0 : 1 + (L - frame_length) / frame_shift;
+  *frames = T;
+  *remainder_len = L - T * frame_shift;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_features(const hipfeat_config* cfg, const float* h_window, const float* h_mel,
+                                                                            const float* h_dct, const float* h_lifter, int32_t device, hipfeat_stream** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "stream pointer is NULL");
+  *out = nullptr;
+  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (cfg->struct_size != (int32_t)sizeof(hipfeat_config))
+    return fail(HIPFEAT_ERR_INVALID, "hipfeat_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_config));
+  const int N = cfg->frame_length, shift = cfg->frame_shift, fft = cfg->fft_length;
+  if (cfg->kind < 0 || cfg->kind > 5) return fail(HIPFEAT_ERR_INVALID, "unknown kind %d", (int)cfg->kind);
+  if (cfg->kind > HIPFEAT_MFCC) return fail(HIPFEAT_ERR_UNSUPPORTED, "kind %d: the streaming kernel has the four Kaldi layer kinds (spectrogram, log-spectrogram, fbank, mfcc)", (int)cfg->kind);
+  if (N <= 0 || shift <= 0 || fft < N)
+    return fail(HIPFEAT_ERR_INVALID, "need frame_length>0, frame_shift>0, fft_length>=frame_length (got %d, %d, %d)", N, shift, fft);
+  const bool need_mel = cfg->kind == HIPFEAT_FBANK || cfg->kind == HIPFEAT_MFCC;
+  if (need_mel && (cfg->num_filters <= 0 || !h_mel)) return fail(HIPFEAT_ERR_INVALID, "fbank/mfcc need num_filters>0 and a mel matrix");
+  if (cfg->kind == HIPFEAT_MFCC) {
+    if (cfg->num_ceps <= 0 || !h_dct) return fail(HIPFEAT_ERR_INVALID, "mfcc needs num_ceps>0 and a dct matrix");
+    if (cfg->apply_lifter && !h_lifter) return fail(HIPFEAT_ERR_INVALID, "apply_lifter set but lifter is NULL");
+  }
+  if (shift > N) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", shift, N);
+  if (cfg->dither != 0.0f) return fail(HIPFEAT_ERR_UNSUPPORTED, "dither != 0 is not supported by the library: the host adds it to the chunk");
+  if (!stream_fft_size(fft))
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the streaming kernel has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)", fft);
+  if (need_mel && cfg->num_filters > 128) return fail(HIPFEAT_ERR_UNSUPPORTED, "num_filters = %d: the streaming kernel holds at most 128 filters", (int)cfg->num_filters);
+  const int M = need_mel ? cfg->num_filters : 0, C = cfg->kind == HIPFEAT_MFCC ? cfg->num_ceps : 0;
+  // the wave kernel's own tables (plan_tables.hpp), not a plan's: a plan's tables are those of the instance it picked
+  PlanInputs in;
+  in.N = N, in.shift = shift, in.K = fft / 2 + 1, in.M = M, in.C = C;
+  in.window = h_window, in.mel = h_mel, in.dct = h_dct, in.lifter = cfg->apply_lifter ? h_lifter : nullptr;
+  const WaveTables t = build_wave_tables(in, fft / 2);
+  if (t.lds > 160 * 1024) return fail(HIPFEAT_ERR_UNSUPPORTED, "configuration does not fit in LDS (%zu bytes)", t.lds);
+  if (hipfeat_status bad = stream_check_gfx950(device)) return bad;
+  DeviceGuard g(device);
+  hipfeat_stream* s = new (std::nothrow) hipfeat_stream();
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  s->features = true;
+  s->fcfg = *cfg;
+  s->device = device;
+  s->n1 = fft / 128;
+  s->N = N, s->shift = shift, s->snip = cfg->snip_edges ? 1 : 0;
+  s->H = fft / 2, s->K = fft / 2 + 1;
+  s->width = cfg->kind == HIPFEAT_FBANK ? M + (cfg->use_energy ? 1 : 0) : (cfg->kind == HIPFEAT_MFCC ? C : s->K);
+  s->blob_floats = (int)t.blob.size();
+  s->dct_in_lds = t.dct_in_lds ? 1 : 0;
+  s->fn = stream_wave_entry(s->n1);
+  s->lds = t.lds;
+  const std::vector<float2> tw = stream_twiddles(fft);
+  hipfeat_status st = upload(&s->d_window, h_window, (size_t)N);
+  if (st == HIPFEAT_OK) st = upload(&s->d_tw, tw.data(), tw.size());
+  if (st == HIPFEAT_OK && M > 0) st = upload(&s->d_mel_blob, t.blob.data(), t.blob.size());
+  if (st == HIPFEAT_OK && C > 0) st = upload(&s->d_dct, h_dct, (size_t)M * C);
+  if (st == HIPFEAT_OK && C > 0 && cfg->apply_lifter) st = upload(&s->d_lifter, h_lifter, (size_t)C);
+  if (st == HIPFEAT_OK) {
+    const hipError_t e = ensure_dynamic_lds(s->fn, s->lds);
+    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", s->lds, hipGetErrorName(e));
+  }
+  if (st != HIPFEAT_OK) {
+    stream_free(s);
+    return st;
+  }
+  *out = s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_stft(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_stream** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "stream pointer is NULL");
+  *out = nullptr;
+  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (cfg->struct_size != (int32_t)sizeof(hipfeat_stft_config))
+    return fail(HIPFEAT_ERR_INVALID, "hipfeat_stft_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_stft_config));
+  if (cfg->output != HIPFEAT_STFT_FRAMES && cfg->output != HIPFEAT_STFT_SPECTRUM) return fail(HIPFEAT_ERR_INVALID, "unknown output %d", (int)cfg->output);
+  if (cfg->frame_length <= 0 || cfg->frame_shift <= 0)
+    return fail(HIPFEAT_ERR_INVALID, "frame_length = %d, frame_shift = %d: both must be positive", (int)cfg->frame_length, (int)cfg->frame_shift);
+  if (cfg->pad_length < cfg->frame_length)
+    return fail(HIPFEAT_ERR_INVALID, "pad_length (or fft_length) = %d cannot be smaller than N = %d", (int)cfg->pad_length, (int)cfg->frame_length);
+  if (cfg->frame_shift > cfg->frame_length)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", (int)cfg->frame_shift, (int)cfg->frame_length);
+  int n1 = 0;
+  if (cfg->output == HIPFEAT_STFT_SPECTRUM) {
+    if (!stream_fft_size(cfg->pad_length))
+      return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the streaming kernel has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)",
+                  (int)cfg->pad_length);
+    n1 = cfg->pad_length / 128;
+  } else {
+    if (cfg->frame_length > 2048) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_length = %d: the device front end holds frames of at most 2048 samples", (int)cfg->frame_length);
+    for (n1 = 2; 128 * n1 < cfg->frame_length; n1 *= 2) {
+    }
+  }
+  if (hipfeat_status bad = stream_check_gfx950(device)) return bad;
+  DeviceGuard g(device);
+  hipfeat_stream* s = new (std::nothrow) hipfeat_stream();
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  s->scfg = *cfg;
+  s->device = device;
+  s->n1 = n1;
+  s->N = cfg->frame_length, s->shift = cfg->frame_shift, s->snip = cfg->snip_edges ? 1 : 0;
+  s->width = cfg->output == HIPFEAT_STFT_SPECTRUM ? cfg->pad_length + 2 : cfg->pad_length;
+  s->fn = stream_stft_entry(n1, cfg->output);
+  s->lds = stft_lds_bytes(n1, cfg->output, cfg->frame_length);
+  hipfeat_status st = upload(&s->d_window, h_window, (size_t)cfg->frame_length);
+  if (st == HIPFEAT_OK && cfg->output == HIPFEAT_STFT_SPECTRUM) {
+    const std::vector<float2> tw = stream_twiddles(cfg->pad_length);
+    st = upload(&s->d_tw, tw.data(), tw.size());
+  }
+  if (st == HIPFEAT_OK) {
+    const hipError_t e = ensure_dynamic_lds(s->fn, s->lds);
+    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", s->lds, hipGetErrorName(e));
+  }
+  if (st != HIPFEAT_OK) {
+    stream_free(s);
+    return st;
+  }
+  *out = s;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_destroy(hipfeat_stream* s) {
+  if (!s) return HIPFEAT_OK;
+  DeviceGuard g(s->device);
+  stream_free(s);
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* s, const float* d_context, int64_t context_len, int64_t context_stride,
+                                                                const float* d_chunk, int64_t chunk_len, int64_t chunk_stride, int64_t batch, float* d_out,
+                                                                int64_t out_floats, float* d_log_energy, float* d_remainder, int64_t remainder_floats,
+                                                                void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (batch < 0 || context_len < 0 || chunk_len < 0 || out_floats < 0 || remainder_floats < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  const bool first = d_context == nullptr;
+  if (first && context_len != 0) return fail(HIPFEAT_ERR_INVALID, "NULL context with context_len = %lld", (long long)context_len);
+  if (batch > 1 && (chunk_stride < chunk_len || (!first && context_stride < context_len)))
+    return fail(HIPFEAT_ERR_INVALID, "a row stride is shorter than its row (context %lld < %lld or chunk %lld < %lld)", (long long)context_stride, (long long)context_len,
+                (long long)chunk_stride, (long long)chunk_len);
+  int64_t T = 0, rem = 0;
+  if (hipfeat_status bad = hipfeat_stream_counts(s->N, s->shift, s->snip, first ? 1 : 0, context_len, chunk_len, &T, &rem)) return bad;
+  if (batch == 0) return HIPFEAT_OK;
+  const int64_t width = s->width;
+  if (T > INT32_MAX || (T > 0 && (batch > INT64_MAX / T || batch * T > INT64_MAX / width)) || (rem > 0 && batch > INT64_MAX / rem))
+    return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
+  if (out_floats < batch * T * width)
+    return fail(HIPFEAT_ERR_INVALID, "output of %lld floats, %lld x %lld x %lld needed", (long long)out_floats, (long long)batch, (long long)T, (long long)width);
+  if (remainder_floats < batch * rem)
+    return fail(HIPFEAT_ERR_INVALID, "remainder of %lld floats, %lld x %lld needed", (long long)remainder_floats, (long long)batch, (long long)rem);
+  if ((chunk_len > 0 && !d_chunk) || (T > 0 && !d_out) || (rem > 0 && !d_remainder)) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
+  const bool spectrum = !s->features && s->scfg.output == HIPFEAT_STFT_SPECTRUM;
+  const int align = spectrum ? 8 : 4;
+  if (reinterpret_cast<uintptr_t>(d_context) % 4 || reinterpret_cast<uintptr_t>(d_chunk) % 4 || reinterpret_cast<uintptr_t>(d_out) % align ||
+      reinterpret_cast<uintptr_t>(d_log_energy) % 4 || reinterpret_cast<uintptr_t>(d_remainder) % 4)
+    return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples, log-energies and remainder: 4 bytes, output: %d)", align);
+  if (T == 0 && rem == 0) return HIPFEAT_OK;  // nothing to frame and nothing to hand back
+  const int64_t fpb = 4 * kStftFramesPerWave, bpr = std::max<int64_t>((T + fpb - 1) / fpb, 1);
+  if (bpr > INT32_MAX / batch) return fail(HIPFEAT_ERR_UNSUPPORTED, "%lld workgroups in one launch", (long long)batch * (long long)bpr);
+  StreamArgs a{};
+  a.ctx = d_context;
+  a.chunk = d_chunk;
+  a.remainder = d_remainder;
+  a.ctx_stride = context_stride;
+  a.chunk_stride = chunk_stride;
+  a.flipped = first && !s->snip ? 1 : 0;
+  a.R = first ? (s->snip ? 0 : std::min<int64_t>((s->N - s->shift) / 2, chunk_len)) : context_len;
+  a.S = chunk_len;
+  a.T = T;
+  a.blocks_per_row = bpr;
+  a.shift = s->shift;
+  WaveParams wp{};
+  StftParams sp{};
+  void* args[] = {nullptr, &a};
+  if (s->features) {
+    const hipfeat_config& c = s->fcfg;
+    wp.out = d_out;
+    wp.window = s->d_window;
+    wp.tw = s->d_tw;
+    wp.mel_blob = s->d_mel_blob;
+    wp.mel_blob_floats = s->blob_floats;
+    wp.dct_in_lds = s->dct_in_lds;
+    wp.dct = s->d_dct;
+    wp.lifter = s->d_lifter;
+    wp.out_stride = width;
+    wp.frames_per_wave = kStftFramesPerWave;
+    wp.N = c.frame_length;
+    wp.shift = c.frame_shift;
+    wp.H = s->H;
+    wp.K = s->K;
+    wp.M = (c.kind == HIPFEAT_FBANK || c.kind == HIPFEAT_MFCC) ? c.num_filters : 0;
+    wp.C = c.kind == HIPFEAT_MFCC ? c.num_ceps : 0;
+    wp.kind = c.kind;
+    wp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) |
+               (c.apply_lifter ? F_LIFTER : 0);
+    wp.npad_left = 0;  // V starts at its first frame
+    wp.preemph = c.preemph_coeff;
+    wp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
+    wp.mel_floor = c.mel_floor;
+    wp.log_offset = c.log_offset;
+    args[0] = &wp;
+  } else {
+    const hipfeat_stft_config& c = s->scfg;
+    sp.out = d_out;
+    sp.log_energy = (c.want_energy && c.output == HIPFEAT_STFT_FRAMES) ? d_log_energy : nullptr;  // (the spectrum carries it in bin 0)
+    sp.window = s->d_window;
+    sp.tw = s->d_tw;
+    sp.frames_per_row = T;
+    sp.blocks_per_row = bpr;
+    sp.N = c.frame_length;
+    sp.shift = c.frame_shift;
+    sp.pad = c.pad_length;
+    sp.npad_left = 0;
+    sp.frames_per_wave = kStftFramesPerWave;
+    sp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.want_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0);
+    sp.preemph = c.preemph_coeff;
+    sp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
+    args[0] = &sp;
+  }
   DeviceGuard g(s->device);
   set_lds_poison(s->lds);
   (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->lds, (hipStream_t)stream);

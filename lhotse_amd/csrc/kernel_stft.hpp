@@ -18,6 +18,9 @@
 //     is 8-byte aligned: the host checks it); consecutive lanes store consecutive bins.  With want_energy bin 0 is (log_energy, 0).
 //
 // All arguments are scalars (the batch is uniform: no device table).  All element indexing is 64-bit.  No scratch, no atomics.
+//
+// The kernel's text is stft_body, parametrised by the source policy of kernel_wave.hpp: stft_kernel is the body on RowSource (the row
+// with its reflections, as described above), kernel_stream.hpp runs it on the two-span source of the streaming layers.
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
@@ -69,8 +72,28 @@ inline size_t stft_lds_bytes(int N1, int OUT, int N) {
   return sizeof(float) * (size_t)(4 * stft_buf_floats(N1, OUT) + ((N + 3) & ~3) + (OUT == 1 ? 4 * 64 * N1 : 0));
 }
 
-template <int N1, int OUT>
-__global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_kernel(const StftParams p) {
+// Source policy of stft_body (kernel_wave.hpp says what a policy offers): RowSource is what stft_kernel has always done, one row of
+// num_samples samples with the flip-reflection at both ends.
+struct RowSource {
+  using Args = NoSourceArgs;
+  const float* __restrict__ w;
+  int64_t row, fb, T, S;
+  __device__ __forceinline__ RowSource(const StftParams& p, const NoSourceArgs&, int64_t blk) {
+    row = blk / p.blocks_per_row, fb = blk - row * p.blocks_per_row;
+    T = p.frames_per_row, S = p.num_samples;
+    w = p.wave + row * p.row_stride;
+  }
+  __device__ __forceinline__ bool inside(int64_t j0, int span) const { return j0 >= 0 && j0 + span <= S; }
+  __device__ __forceinline__ const float* base(int64_t j0) const { return w + j0; }
+  __device__ __forceinline__ v2 slow_pair(int64_t j, bool second) const {
+    v2 v = {stft_sample(w, j, S), 0.f};
+    if (second) v.y = stft_sample(w, j + 1, S);
+    return v;
+  }
+};
+
+template <int N1, int OUT, class Src>
+__device__ __forceinline__ void stft_body(const StftParams& p, const typename Src::Args& sa) {
   constexpr int H = 64 * N1, BUF = stft_buf_floats(N1, OUT);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   HF_POISON_LDS(smem);
@@ -90,10 +113,8 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_k
   }
   __syncthreads();
 
-  const int64_t blk = blockIdx.x;
-  const int64_t row = blk / p.blocks_per_row, fb = blk - row * p.blocks_per_row;
-  const int64_t T = p.frames_per_row, S = p.num_samples;
-  const float* __restrict__ w = p.wave + row * p.row_stride;
+  const Src src(p, sa, (int64_t)blockIdx.x);
+  const int64_t row = src.row, fb = src.fb, T = src.T;
   const bool want_e = (p.flags & F_USE_ENERGY) != 0;
   const int64_t fbase = fb * 4 * p.frames_per_wave;
 #pragma unroll 1
@@ -106,18 +127,18 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_k
     // Frames that lie inside the row (almost all) use one 8-byte load per pair; edge frames go sample by sample.
     v2 xp[N1];
     double s = 0.0;
-    const bool inside = j0 >= 0 && j0 + ((N + 1) & ~1) <= S;
+    const bool inside = src.inside(j0, (N + 1) & ~1);
+    const float* __restrict__ w = src.base(j0);
 #pragma unroll
     for (int q = 0; q < N1; ++q) {
       const int m0 = 2 * (lane + 64 * q);
       v2 v = {0.f, 0.f};
       if (m0 < N) {
         if (inside) {
-          __builtin_memcpy(&v, w + j0 + m0, sizeof(v2));  // 4-byte aligned 8-byte load
+          __builtin_memcpy(&v, w + m0, sizeof(v2));  // 4-byte aligned 8-byte load
           if (m0 + 1 >= N) v.y = 0.f;
         } else {
-          v.x = stft_sample(w, j0 + m0, S);
-          if (m0 + 1 < N) v.y = stft_sample(w, j0 + m0 + 1, S);
+          v = src.slow_pair(j0 + m0, m0 + 1 < N);
         }
       }
       xp[q] = v;
@@ -211,6 +232,11 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_k
     }
     wave_lds_sync();  // the buffer is reused by the next frame
   }
+}
+
+template <int N1, int OUT>
+__global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_kernel(const StftParams p) {
+  stft_body<N1, OUT, RowSource>(p, NoSourceArgs{});
 }
 
 }  // namespace hipfeat

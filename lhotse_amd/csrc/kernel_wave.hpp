@@ -147,11 +147,55 @@ __device__ __forceinline__ void fft3_frame(v2* zf, const v2* __restrict__ twh, i
 }
 
 
+// Source policy: where a workgroup's frames come from and where their rows go.  A policy is built once per workgroup from the kernel's
+// arguments and the workgroup index and offers
+//   fb, T, out_row        the workgroup's index inside its row of frames, the row's frame count, its first output row
+//   inside(j0, span)      samples [j0, j0 + span) of the frame that starts at j0 can be read with 8-byte loads from base(j0)
+//   slow_pair(j, second)  samples j and (when `second`) j + 1 one by one, whatever edge rule the source has
+// The choice between the two is per frame and therefore wave-uniform.  CutSource is what wave_kernel has always done: a cut of the
+// descriptor table, reflected at its edges.  kernel_stream.hpp has the two-span source of the streaming layers.
+struct NoSourceArgs {};
+
+struct CutSource {
+  using Args = NoSourceArgs;
+  const float* __restrict__ w;
+  int64_t out_row;
+  int32_t num_samples, padded_len, T, flags;
+  int fb;
+  __device__ __forceinline__ CutSource(const WaveParams& p, const NoSourceArgs&, int blk) {
+    int cut;
+    if (p.uniform_bpc > 0) {
+      cut = blk / p.uniform_bpc;
+      fb = blk - cut * p.uniform_bpc;
+    } else {
+      cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
+      fb = blk - p.cuts[cut].first_block;
+    }
+    const CutDesc cd = p.cuts[cut];
+    w = p.wave + cd.wave_off;
+    out_row = cd.out_row;
+    num_samples = cd.num_samples, padded_len = cd.padded_len, T = cd.num_frames, flags = p.flags;
+  }
+  __device__ __forceinline__ bool inside(int64_t j0, int span) const { return j0 >= 0 && j0 + span <= (int64_t)num_samples; }
+  __device__ __forceinline__ const float* base(int64_t j0) const { return w + j0; }
+  __device__ __forceinline__ v2 slow_pair(int64_t j, bool second) const {
+    v2 v = {0.f, 0.f};
+    if (flags & F_CENTER) {
+      v.x = load_sample_center(w, j, num_samples);
+      if (second) v.y = load_sample_center(w, j + 1, num_samples);
+    } else {
+      v.x = load_sample(w, j, num_samples, padded_len);
+      if (second) v.y = load_sample(w, j + 1, num_samples, padded_len);
+    }
+    return v;
+  }
+};
+
 #ifndef HIPFEAT_WAVE_OCC
 #define HIPFEAT_WAVE_OCC 4
 #endif
-template <int N1>
-__global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_kernel(const WaveParams p) {
+template <int N1, class Src>
+__device__ __forceinline__ void wave_body(const WaveParams& p, const typename Src::Args& sa) {
   constexpr int H = 64 * N1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   HF_POISON_LDS(smem);
@@ -165,17 +209,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_k
   float* buf = smem + 2 * H + wv * (144 * N1 + 8);               // wave-private: 72 N1 complex (padded FFT buffer), later the power row
   v2* zf = reinterpret_cast<v2*>(buf);
 
-  const int blk = blockIdx.x;
-  int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
-  const CutDesc cd = p.cuts[cut];
-  const float* __restrict__ w = p.wave + cd.wave_off;
+  const Src src(p, sa, blockIdx.x);
   for (int i = tid; i < H; i += 256) {
     tw[i] = p.tw[i];
     twh[i] = twiddle_h(p.tw, i, H);
@@ -191,11 +225,11 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_k
 
   const int N = p.N, K = p.K, M = p.M;
   const bool use_e = (p.flags & F_USE_ENERGY) != 0;
-  const int fbase = fb * 4 * p.frames_per_wave;
+  const int fbase = src.fb * 4 * p.frames_per_wave;
 #pragma unroll 1
   for (int i = 0; i < p.frames_per_wave; ++i) {
     const int f = fbase + 4 * i + wv;
-    if (f >= cd.num_frames) break;
+    if (f >= src.T) break;
     const int64_t j0 = (int64_t)f * p.shift - p.npad_left;
 
     // ---- samples, DC mean, raw log-energy (layers.py:155-162), in FFT order: lane l holds the sample pairs ----------
@@ -203,21 +237,18 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_k
     // Frames that lie inside the cut (almost all) use one 8-byte load per pair; edge frames go sample by sample.
     v2 xp[N1];
     float s = 0.f;
-    const bool inside = j0 >= 0 && j0 + ((N + 1) & ~1) <= (int64_t)cd.num_samples;
+    const bool inside = src.inside(j0, (N + 1) & ~1);
+    const float* __restrict__ w = src.base(j0);
 #pragma unroll
     for (int q = 0; q < N1; ++q) {
       const int m0 = 2 * (lane + 64 * q);
       v2 v = {0.f, 0.f};
       if (m0 < N) {
         if (inside) {
-          __builtin_memcpy(&v, w + j0 + m0, sizeof(v2));  // 4-byte aligned 8-byte load
+          __builtin_memcpy(&v, w + m0, sizeof(v2));  // 4-byte aligned 8-byte load
           if (m0 + 1 >= N) v.y = 0.f;
-        } else if (p.flags & F_CENTER) {
-          v.x = load_sample_center(w, j0 + m0, cd.num_samples);
-          if (m0 + 1 < N) v.y = load_sample_center(w, j0 + m0 + 1, cd.num_samples);
         } else {
-          v.x = load_sample(w, j0 + m0, cd.num_samples, cd.padded_len);
-          if (m0 + 1 < N) v.y = load_sample(w, j0 + m0 + 1, cd.num_samples, cd.padded_len);
+          v = src.slow_pair(j0 + m0, m0 + 1 < N);
         }
       }
       xp[q] = v;
@@ -299,7 +330,7 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_k
     wave_lds_sync();
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------
-    float* __restrict__ orow = p.out + (cd.out_row + f) * p.out_stride;
+    float* __restrict__ orow = p.out + (src.out_row + f) * p.out_stride;
     if (p.kind == 0 || p.kind == 1) {
       for (int k = lane; k < K; k += 64) {
         float v = buf[k];
@@ -367,6 +398,11 @@ __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_k
     }
     wave_lds_sync();  // the buffer is reused by the next frame
   }
+}
+
+template <int N1>
+__global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void wave_kernel(const WaveParams p) {
+  wave_body<N1, CutSource>(p, NoSourceArgs{});
 }
 
 }  // namespace hipfeat

@@ -6,11 +6,19 @@ Drop-ins for the ``torch.nn.Module``s of lhotse/features/kaldi/layers.py (``Wav2
 defaults (in the same order), same attributes, ``forward(x)`` maps a ``(B, T)`` (or ``(T,)``) float32 batch of equally long
 waveforms on the GPU to ``(B, num_frames, F)`` on the same device -- one fused launch instead of the ~12 tensor ops of
 ``Wav2Win`` + ``_rfft`` + matmul + log.  Not covered, by design: autograd (inputs that
-require grad are refused), TorchScript, ``online_inference``.
+require grad are refused) and TorchScript.
 
 ``HipWav2Win`` (:59-197) and ``HipWav2FFT`` (:227-324) hand out what the four above compute on the way and discard: the preprocessed
 frames, ``(B, num_frames, pad_length)`` with the optional ``(B, num_frames)`` log-energies, and their complex STFT,
 ``(B, num_frames, fft_length / 2 + 1)`` ``complex64`` -- one launch of ``hipfeat_stft_run`` each, under the same restrictions.
+
+All six have the reference's second public method, ``online_inference(x, context=None)`` (:199-224, :326-333, :775-856): the chunked,
+stateless streaming call that frames ``[context | x]``, returns what ``forward`` computes for the complete frames and hands back the
+samples they did not consume.  One launch of ``hipfeat_stream_run`` per chunk (csrc/kernel_stream.hpp: the wave-per-frame kernels on a
+two-span source), for the FFT sizes 256 / 512 / 1024 / 2048; every frame is computed by one wave from its own samples alone, so the
+concatenated outputs of a stream are the same bits under any chunking.  One deliberate difference: where ``[context | x]`` is shorter
+than a frame the reference raises; these return zero frames and the whole of ``[context | x]`` as the remainder, so a caller may feed
+chunks shorter than a frame.
 """
 from __future__ import annotations
 
@@ -28,6 +36,109 @@ from .compat import EPSILON, Seconds
 __all__ = ["HipWav2Win", "HipWav2FFT", "HipWav2Spec", "HipWav2LogSpec", "HipWav2LogFilterBank", "HipWav2MFCC"]
 
 
+# --------------------------------------------------------------------------------------
+# online_inference: one hipfeat_stream handle per (layer, device, output), one launch per chunk (csrc/kernel_stream.hpp)
+# --------------------------------------------------------------------------------------
+_STREAM_SIZES = ("online_inference runs on the device for the FFT sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms), "
+                 "frames of at most 2048 samples, frame_shift <= frame_length and at most 128 mel filters")
+
+
+class _Stream:
+    """Owns one ``hipfeat_stream`` handle: the tables of one configuration on one device."""
+
+    def __init__(self, create: str, args: tuple, n: int, shift: int, snip_edges: bool, width: int, energy_rows: bool, device: torch.device):
+        self.lib = _lib.load()
+        self.handle = 0
+        if device.type != "cuda":
+            raise _lib.HipFeatError(1, f"Hip* layers run on an AMD GPU ('cuda[:i]' device), got device={device}")
+        if not torch.cuda.is_available():
+            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n, self.shift, self.snip_edges, self.width, self.energy_rows = n, shift, bool(snip_edges), width, energy_rows
+        handle = np.zeros(1, dtype=np.uint64)
+        self.lib.check(create, *args, int(self.device.index), _lib.addr(handle))
+        self.handle = int(handle[0])
+        _lib.note_plan_created()
+        self._counts = np.zeros(2, dtype=np.int64)
+        self._spare = torch.empty(2, dtype=torch.float32, device=self.device)  # a valid address for a context of no samples
+
+    def counts(self, first: bool, context_len: int, chunk_len: int) -> Tuple[int, int]:
+        """(frames, remainder length) of one call: hipfeat_stream_counts."""
+        c = self._counts
+        self.lib.check("hipfeat_stream_counts", self.n, self.shift, int(self.snip_edges), int(first), int(context_len), int(chunk_len), c.ctypes.data,
+                       c.ctypes.data + 8)
+        return int(c[0]), int(c[1])
+
+    @staticmethod
+    def _rows(t: torch.Tensor) -> torch.Tensor:
+        B, S = t.shape
+        if (S > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < S):
+            t = t.contiguous()
+        return t
+
+    def run(self, x: torch.Tensor, context: Optional[torch.Tensor]) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+        """x (B, S), context (B, R) or None -> (out (B, T, width), log-energies (B, T) or None, remainder (B, L - T shift)): fresh tensors,
+        one launch on the current stream."""
+        x = self._rows(x)
+        B, S = x.shape
+        first = context is None
+        R = 0
+        if not first:
+            context = self._rows(context)
+            R = int(context.shape[1])
+        T, rem = self.counts(first, R, S)
+        with torch.cuda.device(self.device):
+            out = torch.empty((B, T, self.width), dtype=torch.float32, device=self.device)
+            log_e = torch.empty((B, T), dtype=torch.float32, device=self.device) if self.energy_rows else None
+            remainder = torch.empty((B, rem), dtype=torch.float32, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.lib.check("hipfeat_stream_run", self.handle,
+                           None if first else (context.data_ptr() or self._spare.data_ptr()), R, R if (first or B <= 1) else int(context.stride(0)),
+                           x.data_ptr() or None, S, int(x.stride(0)) if B > 1 else S, B, out.data_ptr() or None, out.numel(),
+                           None if log_e is None else (log_e.data_ptr() or None), remainder.data_ptr() or None, remainder.numel(), int(stream))
+        return out, log_e, remainder
+
+    def close(self) -> None:
+        if self.handle:
+            try:
+                self.lib.raw("hipfeat_stream_destroy", self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _stream_unsupported(layer, e: "_lib.HipFeatError") -> NotImplementedError:
+    return NotImplementedError(f"{type(layer).__name__}.online_inference: {e} -- {_STREAM_SIZES}; forward() still serves this configuration where it did before")
+
+
+def _check_stream_input(layer, x, context) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
+    """The argument checks of ``forward`` on the chunk, and the reference's assertions on the context (layers.py:832-833): a 2-D tensor
+    with the chunk's batch size -- here also float32 and on the chunk's device."""
+    name = type(layer).__name__
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}.online_inference expects a torch.Tensor, got {type(x).__name__}")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} is inference-only (no autograd); call it under torch.no_grad() or detach the input")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32 samples, got {x.dtype}")
+    squeeze = x.ndim == 1
+    if squeeze:
+        x = x.unsqueeze(0)
+    assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
+    if context is not None:
+        assert isinstance(context, torch.Tensor) and context.ndim == 2, "context must be a (B, R) tensor: the remainder of the previous call"
+        assert context.shape[0] == x.shape[0], f"context has batch size {context.shape[0]}, the chunk {x.shape[0]}"
+        assert context.dtype == torch.float32 and context.device == x.device, (
+            f"context must be float32 on the chunk's device ({x.device}), got {context.dtype} on {context.device}")
+        context = context.detach()
+    return x.detach(), context, squeeze
+
+
 class _HipLayer(torch.nn.Module):
     kind: int = -1
 
@@ -40,6 +151,7 @@ class _HipLayer(torch.nn.Module):
         self.fft_length = fft  # Wav2FFT.fft_length (layers.py:281-286)
         self._n, self._shift = n, shift
         self._plans = {}
+        self._streams = {}
 
     def _plan_for(self, device: torch.device):
         key = (device.type, device.index)
@@ -57,7 +169,66 @@ class _HipLayer(torch.nn.Module):
     def __getstate__(self):
         st = dict(self.__dict__)
         st["_plans"] = {}  # device handles are per process
+        st["_streams"] = {}
         return st
+
+    def _stream_for(self, device: torch.device) -> _Stream:
+        key = (device.type, device.index)
+        s = self.__dict__.setdefault("_streams", {}).get(key)
+        if s is None:
+            # the tables of hipfeat_plan_create (extractors._Plan), for the streaming kernel's own handle
+            o = {**dict(num_filters=0, num_ceps=0, cepstral_lifter=0, low_freq=20.0, high_freq=-400.0, norm_filters=False,
+                        torchaudio_compatible_mel_scale=True, use_fft_mag=False), **self._opts}
+            n, shift, fft = self._n, self._shift, self.fft_length
+            window = constants.make_window(n, o["window_type"], 0.42)
+            mel = dct = lifter = None
+            num_filters = num_ceps = apply_lifter = 0
+            if self.kind in (_E.KIND_FBANK, _E.KIND_MFCC):
+                num_filters = int(o["num_filters"])
+                if o["torchaudio_compatible_mel_scale"]:
+                    mel = constants.make_kaldi_mel(num_filters, fft, o["sampling_rate"], o["low_freq"], o["high_freq"])
+                else:
+                    mel = constants.make_htk_mel(num_filters, fft, o["sampling_rate"], o["low_freq"], o["high_freq"], o["norm_filters"])
+            if self.kind == _E.KIND_MFCC:
+                num_ceps = int(o["num_ceps"])
+                dct = constants.make_dct(num_ceps, num_filters)
+                apply_lifter = 1 if o["cepstral_lifter"] > 0 else 0
+                lifter = constants.make_lifter(num_ceps, o["cepstral_lifter"])
+            c = np.zeros(1, dtype=_lib.CONFIG_DTYPE)
+            c["struct_size"], c["kind"] = _lib.CONFIG_DTYPE.itemsize, self.kind
+            c["frame_length"], c["frame_shift"], c["fft_length"] = n, shift, fft
+            c["num_filters"], c["num_ceps"], c["apply_lifter"] = num_filters, num_ceps, apply_lifter
+            c["snip_edges"], c["remove_dc_offset"] = int(o["snip_edges"]), int(o["remove_dc_offset"])
+            c["use_energy"], c["raw_energy"], c["use_fft_mag"] = int(o["use_energy"]), int(o["raw_energy"]), int(o["use_fft_mag"])
+            c["preemph_coeff"], c["energy_floor"] = o["preemph_coeff"], o["energy_floor"]
+            c["mel_floor"], c["log_offset"] = constants.MEL_FLOOR, constants.LOG_SPEC_OFFSET
+            c["batch_hop"] = shift
+            width = {_E.KIND_FBANK: num_filters + int(bool(o["use_energy"])), _E.KIND_MFCC: num_ceps}.get(self.kind, fft // 2 + 1)
+            try:
+                s = _Stream("hipfeat_stream_create_features", (_lib.addr(c), _lib.addr(window), _lib.addr(mel), _lib.addr(dct), _lib.addr(lifter)),
+                            n, shift, o["snip_edges"], width, False, device)
+            except _lib.HipFeatError as e:
+                if e.status == _lib.ERR_UNSUPPORTED:
+                    raise _stream_unsupported(self, e) from e
+                raise
+            self._streams[key] = s
+        return s
+
+    def online_inference(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's chunked, stateless streaming call (layers.py:326-333): ``(output, remainder)`` for the chunk ``x`` and the
+        remainder of the previous call (``None`` at the start of a stream; any ``(B, R)`` tensor is accepted).  ``output`` holds the
+        frames of ``[context | x]`` that are complete -- what ``forward`` computes per frame, without a reflection on the right --
+        and ``remainder`` the ``(B, L - T * shift)`` samples they did not consume.  One launch on the current stream; the concatenated
+        outputs of a stream do not depend on how it was cut into chunks, bit for bit.  Unlike the reference, which raises when
+        ``[context | x]`` is shorter than a frame, this returns ``(B, 0, F)`` and all of ``[context | x]`` as the remainder.  A 1-D
+        chunk gives a 2-D output; the remainder stays ``(1, R)``, ready to be passed back."""
+        x, context, squeeze = _check_stream_input(self, x, context)
+        s = self._stream_for(x.device)
+        dither = self._opts["dither"]
+        if dither != 0.0:  # layers.py:209-212: the chunk alone
+            x = x + dither * torch.randn(x.shape, device=x.device)
+        out, _, remainder = s.run(x, context)
+        return (out[0] if squeeze else out), remainder
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not isinstance(x, torch.Tensor):
@@ -309,6 +480,52 @@ class HipWav2Win(torch.nn.Module):
             return out[0], (None if log_e is None else log_e[0])
         return out, log_e
 
+    def _stream_for(self, device: torch.device, output: int, layer) -> _Stream:
+        key = (device.type, device.index, output, "stream")
+        s = self._handles.get(key)
+        if s is None:
+            cfg = np.zeros(1, dtype=_lib.STFT_CONFIG_DTYPE)
+            cfg["struct_size"] = _lib.STFT_CONFIG_DTYPE.itemsize
+            cfg["output"], cfg["frame_length"], cfg["frame_shift"], cfg["pad_length"] = output, self._length, self._shift, self.pad_length
+            cfg["snip_edges"], cfg["remove_dc_offset"] = int(bool(self.snip_edges)), int(bool(self.remove_dc_offset))
+            cfg["raw_energy"], cfg["want_energy"] = int(bool(self.raw_energy)), int(bool(self.return_log_energy))
+            cfg["preemph_coeff"], cfg["energy_floor"] = float(self.preemph_coeff), float(self.energy_floor)
+            window = np.ascontiguousarray(self._window.detach().cpu().numpy(), dtype=np.float32)
+            spectrum = output == _lib.STFT_SPECTRUM
+            try:
+                # (the spectrum carries its log-energy in bin 0: no separate row of them is asked for)
+                s = _Stream("hipfeat_stream_create_stft", (_lib.addr(cfg), _lib.addr(window)), self._length, self._shift, self.snip_edges,
+                            self.pad_length + 2 if spectrum else self.pad_length, bool(self.return_log_energy) and not spectrum, device)
+            except _lib.HipFeatError as e:
+                if e.status == _lib.ERR_UNSUPPORTED:
+                    raise _stream_unsupported(layer, e) from e
+                raise
+            self._handles[key] = s
+        return s
+
+    def _online(self, x: torch.Tensor, context: Optional[torch.Tensor], output: int, layer):
+        x, context, squeeze = _check_stream_input(layer, x, context)
+        s = self._stream_for(x.device, output, layer)
+        if self.dither != 0.0:  # layers.py:209-212: the chunk alone, before the concatenation
+            x = x + self.dither * torch.randn(x.shape, device=x.device)
+        out, log_e, remainder = s.run(x, context)
+        return out, log_e, remainder, squeeze
+
+    def online_inference(self, x: torch.Tensor, context: Optional[torch.Tensor] = None
+                         ) -> Tuple[Tuple[torch.Tensor, Optional[torch.Tensor]], torch.Tensor]:
+        """The reference's chunked, stateless streaming call (layers.py:199-224): ``((frames, log_energy), remainder)`` for the chunk
+        ``x`` and the remainder of the previous call (``None`` at the start of a stream, where without ``snip_edges`` the first
+        ``min((N - shift) // 2, S)`` samples are reflected in front; any ``(B, R)`` tensor is accepted as a context).  The frames are
+        those of ``[context | x]`` that are complete, ``T = 1 + (L - N) // shift`` of them, never reflected on the right; ``remainder``
+        is ``[context | x][:, T * shift:]``, fresh and contiguous.  One launch on the current stream; the concatenated outputs of a
+        stream do not depend on how it was cut into chunks, bit for bit.  Unlike the reference, which raises when ``[context | x]``
+        is shorter than a frame, this returns ``(B, 0, pad_length)`` frames (and ``(B, 0)`` log-energies) and all of ``[context | x]``
+        as the remainder.  A 1-D chunk gives 2-D frames; the remainder stays ``(1, R)``, ready to be passed back."""
+        out, log_e, remainder, squeeze = self._online(x, context, self._output, self)
+        if squeeze:
+            return (out[0], (None if log_e is None else log_e[0])), remainder
+        return (out, log_e), remainder
+
 
 class HipWav2FFT(torch.nn.Module):
     """The complex STFT of the Kaldi-preprocessed frames: the reference's ``Wav2FFT`` (layers.py:227-324).  ``forward(x)`` returns a
@@ -357,3 +574,11 @@ class HipWav2FFT(torch.nn.Module):
         out, _, squeeze = self.wav2win._run(x, _lib.STFT_SPECTRUM)
         spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
         return spec[0] if squeeze else spec
+
+    def online_inference(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's chunked, stateless streaming call (layers.py:326-333): ``(spectrum, remainder)``, the ``complex64`` STFT of the
+        complete frames of ``[context | x]`` and the samples they did not consume; see ``HipWav2Win.online_inference``, whose framing,
+        remainder and zero-frame rule (``(B, 0, fft_length / 2 + 1)`` where the reference raises) this shares."""
+        out, _, remainder, squeeze = self.wav2win._online(x, context, _lib.STFT_SPECTRUM, self)
+        spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
+        return (spec[0] if squeeze else spec), remainder
