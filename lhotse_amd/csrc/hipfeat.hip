@@ -13,6 +13,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -413,11 +414,194 @@ static hipError_t ensure_dynamic_lds(const void* fn, size_t bytes) {
   return e;
 }
 
+static hipfeat_status set_dynamic_lds(const void* fn, size_t bytes) {
+  const hipError_t e = ensure_dynamic_lds(fn, bytes);
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", bytes, hipGetErrorName(e));
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// The frame front end -- Kaldi frames, window, pre-emphasis, DC removal, energy, radix FFT with W_fft^k twiddles -- as the plans
+// (hipfeat_plan_*), the frame / STFT handles (hipfeat_stft_*) and the streams (hipfeat_stream_*) share it on the host
+// --------------------------------------------------------------------------------------
+// check_device, and: the kernels are gfx950 code objects and lean on gfx950's memory pipeline (hipfeat.h, HIPFEAT_WHISPER)
+static hipfeat_status require_gfx950(int device) {
+  if (hipfeat_status bad = check_device(device)) return bad;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "device %d is not a gfx950 (MI355X-class) GPU: libhipfeat is built for that architecture alone", device);
+  return HIPFEAT_OK;
+}
+
+// W_fft^k = exp(-2 pi i k / fft) for k < count, computed in double
+static std::vector<float2> fft_twiddles(int fft, int count) {
+  std::vector<float2> tw((size_t)count);
+  for (int k = 0; k < count; ++k) {
+    const double a = -2.0 * M_PI * (double)k / (double)fft;
+    tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+  }
+  return tw;
+}
+
+static bool radix_fft_size(int fft) { return fft == 256 || fft == 512 || fft == 1024 || fft == 2048; }
+
+// n1 (64 n1 complex points per frame) -> f(std::integral_constant<int, n1>): the instance of a kernel template for 2, 4, 8 or 16
+template <typename F>
+static const void* for_n1(int n1, F f) {
+  switch (n1) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
+
+static int energy_flags(bool remove_dc, bool use_energy, bool raw_energy) {
+  return (remove_dc ? F_REMOVE_DC : 0) | (use_energy ? F_USE_ENERGY : 0) | (raw_energy ? F_RAW_ENERGY : 0);
+}
+static int energy_flags(const hipfeat_stft_config& c) { return energy_flags(c.remove_dc_offset, c.want_energy, c.raw_energy); }
+static int energy_flags(const hipfeat_config& c) {  // ... and what the feature epilogues read
+  return energy_flags(c.remove_dc_offset, c.use_energy, c.raw_energy) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0);
+}
+static float log_energy_floor(float energy_floor) { return energy_floor > 0.0f ? logf(energy_floor) : -INFINITY; }
+
+// The rules of hipfeat_config that hipfeat_plan_create and hipfeat_stream_create_features both apply, in the plan's order; what only one
+// of them refuses (whisper / librosa constraints, the streaming kernel's kinds and sizes) stays in that entry point
+constexpr const char* kNeedMel = "fbank/mfcc need num_filters>0 and a mel matrix";
+static hipfeat_status check_feature_config(const hipfeat_config* cfg, const float* h_window, const float* h_mel, const float* h_dct, const float* h_lifter) {
+  if (cfg->struct_size != (int32_t)sizeof(hipfeat_config))
+    return fail(HIPFEAT_ERR_INVALID, "hipfeat_config.struct_size %d != %zu (ABI mismatch)", cfg->struct_size, sizeof(hipfeat_config));
+  const int N = cfg->frame_length, shift = cfg->frame_shift, fft = cfg->fft_length;
+  if (cfg->kind < 0 || cfg->kind > 5) return fail(HIPFEAT_ERR_INVALID, "unknown kind %d", cfg->kind);
+  if (N <= 0 || shift <= 0 || fft < N)
+    return fail(HIPFEAT_ERR_INVALID, "need frame_length>0, frame_shift>0, fft_length>=frame_length (got %d, %d, %d)", N, shift, fft);
+  if (shift > N) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", shift, N);
+  if (!h_window) return fail(HIPFEAT_ERR_INVALID, "window is NULL");
+  if (cfg->dither != 0.0f)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "dither != 0 is not supported by the library (ABI v%d): the host adds it to the samples", HIPFEAT_ABI_VERSION);
+  if ((cfg->kind == HIPFEAT_FBANK || cfg->kind == HIPFEAT_MFCC) && (cfg->num_filters <= 0 || !h_mel)) return fail(HIPFEAT_ERR_INVALID, kNeedMel);
+  if (cfg->kind == HIPFEAT_MFCC) {
+    if (cfg->num_ceps <= 0 || !h_dct) return fail(HIPFEAT_ERR_INVALID, "mfcc needs num_ceps>0 and a dct matrix");
+    if (cfg->apply_lifter && !h_lifter) return fail(HIPFEAT_ERR_INVALID, "apply_lifter set but lifter is NULL");
+  }
+  return HIPFEAT_OK;
+}
+
+// columns of a feature row
+static int feature_dim(const hipfeat_config& c) {
+  if (c.kind == HIPFEAT_FBANK) return c.num_filters + (c.use_energy ? 1 : 0);
+  if (c.kind == HIPFEAT_MFCC) return c.num_ceps;
+  return (c.kind == HIPFEAT_WHISPER || c.kind == HIPFEAT_LIBROSA_FBANK) ? c.num_filters : c.fft_length / 2 + 1;
+}
+
+// What the wave-per-frame kernel (kernel_wave.hpp) reads besides the config: its tables on the device and its LDS bytes
+struct WaveFront {
+  float* d_window = nullptr;
+  float2* d_tw = nullptr;
+  float* d_mel_blob = nullptr;  // filterbank blob (descriptors + compact weights)
+  float* d_dct = nullptr;
+  float* d_lifter = nullptr;
+  int blob_floats = 0;
+  bool dct_in_lds = false;
+  size_t lds = 0;
+};
+
+// the WaveParams fields that do not depend on the call (its buffers, batch, frames per wave and npad_left do)
+static void fill_wave_front(WaveParams& wp, const hipfeat_config& c, const WaveFront& t) {
+  const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
+  wp.window = t.d_window;
+  wp.tw = t.d_tw;
+  wp.mel_blob = t.d_mel_blob;
+  wp.mel_blob_floats = t.blob_floats;
+  wp.dct_in_lds = t.dct_in_lds ? 1 : 0;
+  wp.dct = t.d_dct;
+  wp.lifter = t.d_lifter;
+  wp.N = c.frame_length;
+  wp.shift = c.frame_shift;
+  wp.H = c.fft_length / 2;
+  wp.K = c.fft_length / 2 + 1;
+  wp.M = c.kind >= HIPFEAT_FBANK ? c.num_filters : 0;
+  wp.C = c.kind == HIPFEAT_MFCC ? c.num_ceps : 0;
+  wp.kind = librosa ? (int)HIPFEAT_FBANK : c.kind;
+  wp.flags = energy_flags(c) | (librosa ? (F_CENTER | F_LOG10) : 0);
+  wp.preemph = c.preemph_coeff;
+  wp.log_energy_floor = log_energy_floor(c.energy_floor);
+  wp.mel_floor = c.mel_floor;
+  wp.log_offset = c.log_offset;
+}
+
+// One check of hipfeat_stft_config for hipfeat_stft_create and hipfeat_stream_create_stft, which also yields n1: the spectrum's fft / 128,
+// for frames the smallest of 2, 4, 8, 16 that holds the frame.  A stream (`streaming`) refuses a shift longer than the frame as well.
+static hipfeat_status check_stft_config(const hipfeat_stft_config* cfg, const float* h_window, bool streaming, int* n1) {
+  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (cfg->struct_size != (int32_t)sizeof(hipfeat_stft_config))
+    return fail(HIPFEAT_ERR_INVALID, "hipfeat_stft_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_stft_config));
+  if (cfg->output != HIPFEAT_STFT_FRAMES && cfg->output != HIPFEAT_STFT_SPECTRUM) return fail(HIPFEAT_ERR_INVALID, "unknown output %d", (int)cfg->output);
+  if (cfg->frame_length <= 0 || cfg->frame_shift <= 0)
+    return fail(HIPFEAT_ERR_INVALID, "frame_length = %d, frame_shift = %d: both must be positive", (int)cfg->frame_length, (int)cfg->frame_shift);
+  if (cfg->pad_length < cfg->frame_length)
+    return fail(HIPFEAT_ERR_INVALID, "pad_length (or fft_length) = %d cannot be smaller than N = %d", (int)cfg->pad_length, (int)cfg->frame_length);
+  if (streaming && cfg->frame_shift > cfg->frame_length)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", (int)cfg->frame_shift, (int)cfg->frame_length);
+  if (cfg->output == HIPFEAT_STFT_SPECTRUM) {
+    if (!radix_fft_size(cfg->pad_length))
+      return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the device front end has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)",
+                  (int)cfg->pad_length);
+    *n1 = cfg->pad_length / 128;
+  } else {
+    if (cfg->frame_length > 2048) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_length = %d: the device front end holds frames of at most 2048 samples", (int)cfg->frame_length);
+    for (*n1 = 2; 128 * *n1 < cfg->frame_length;) *n1 *= 2;
+  }
+  return HIPFEAT_OK;
+}
+
+// The front end of the STFT pair (kernel_stft.hpp on a row, kernel_stream.hpp on [context | chunk]): the config and what create made of it
+struct StftFront {
+  hipfeat_stft_config cfg{};
+  int n1 = 0;
+  size_t lds = 0;
+  float* d_window = nullptr;
+  float2* d_tw = nullptr;  // spectrum: W_fft^k, k < fft / 2
+  bool spectrum() const { return cfg.output == HIPFEAT_STFT_SPECTRUM; }
+  int width() const { return cfg.pad_length + (spectrum() ? 2 : 0); }  // floats per output row
+};
+
+static void stft_front_free(StftFront& f) {
+  (void)hipFree(f.d_window);
+  (void)hipFree(f.d_tw);
+}
+
+// a checked config on the current device, for the kernel instance `fn`; after a failure the caller frees
+static hipfeat_status stft_front_create(StftFront& f, const hipfeat_stft_config& cfg, int n1, const float* h_window, const void* fn) {
+  f.cfg = cfg;
+  f.n1 = n1;
+  f.lds = stft_lds_bytes(n1, cfg.output, cfg.frame_length);
+  hipfeat_status st = upload(&f.d_window, h_window, (size_t)cfg.frame_length);
+  if (st == HIPFEAT_OK && f.spectrum()) {
+    const std::vector<float2> tw = fft_twiddles(cfg.pad_length, cfg.pad_length / 2);
+    st = upload(&f.d_tw, tw.data(), tw.size());
+  }
+  return st == HIPFEAT_OK ? set_dynamic_lds(fn, f.lds) : st;
+}
+
+// the StftParams fields that do not depend on the call (its buffers, strides, counts and npad_left do)
+constexpr int kStftFramesPerWave = 8;  // 4 waves x 8 frames per workgroup, as the wave kernel
+static void fill_stft_front(StftParams& p, const StftFront& f) {
+  p.window = f.d_window;
+  p.tw = f.d_tw;
+  p.N = f.cfg.frame_length;
+  p.shift = f.cfg.frame_shift;
+  p.pad = f.cfg.pad_length;
+  p.frames_per_wave = kStftFramesPerWave;
+  p.flags = energy_flags(f.cfg);
+  p.preemph = f.cfg.preemph_coeff;
+  p.log_energy_floor = log_energy_floor(f.cfg.energy_floor);
+}
+
 // The setup that accepts a configuration claims the plan with the instance it runs: the instance's dynamic-LDS limit is raised, its
 // occupancy read (blocks_per_cu, part of the kernel name) and the launch recorded for launch().
 static hipfeat_status claim(hipfeat_plan* p, Route route, const void* fn, int block, size_t lds) {
-  hipError_t e = ensure_dynamic_lds(fn, lds);
-  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", lds, hipGetErrorName(e));
+  if (hipfeat_status bad = set_dynamic_lds(fn, lds)) return bad;
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, block, lds) == hipSuccess) p->blocks_per_cu = nb;
   p->route = route;
@@ -522,8 +706,7 @@ static hipfeat_status setup_fft512c(hipfeat_plan* p, const PlanInputs& in, int n
     const bool flat = i != 1, far = i != 0;
     if ((flat && !fft512c_has_flat(nrows, in.N)) || (far && !wide)) continue;
     *more[i] = fft512c_dispatch(t.mode, nrows, in.N, flat, wide && !far);
-    hipError_t e = ensure_dynamic_lds(*more[i], t.lds);
-    if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", t.lds, hipGetErrorName(e));
+    st = set_dynamic_lds(*more[i], t.lds);
   }
   return st;
 }
@@ -649,7 +832,10 @@ static hipfeat_status setup_wave(hipfeat_plan* p, const PlanInputs& in) {
   if (in.M > 0 && (st = upload(&p->d_mel_t, t.blob.data(), t.blob.size())) != HIPFEAT_OK) return st;
   p->wave_blob_floats = (int)t.blob.size();
   p->wave_dct_in_lds = t.dct_in_lds;
-  const void* fn = H == 256 ? entry<wave_kernel<4>>() : (H == 512 ? entry<wave_kernel<8>>() : entry<wave_kernel<16>>());
+  const void* fn = for_n1(H / 64, [](auto n) -> const void* {  // (no instance for n1 = 2: H = 128 was turned away above)
+    if constexpr (decltype(n)::value > 2) return entry<wave_kernel<decltype(n)::value>>();
+    return nullptr;
+  });
   if ((st = claim(p, Route::Wave, fn, 256, t.lds)) != HIPFEAT_OK) return st;
   p->kernel_name = strf("wave_kernel<%d> fft=%d lds=%zuB blocks/CU=%d", H / 64, c.fft_length, t.lds, p->blocks_per_cu);
   p->fpb = 32;  // 4 waves x 8 frames (the tables copied to LDS per workgroup are ~12 KB)
@@ -729,33 +915,17 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
                                               int32_t device, hipfeat_plan** out) {
   if (!cfg || !out) return fail(HIPFEAT_ERR_INVALID, "cfg/plan pointer is NULL");
   *out = nullptr;
-  if (cfg->struct_size != (int32_t)sizeof(hipfeat_config))
-    return fail(HIPFEAT_ERR_INVALID, "hipfeat_config.struct_size %d != %zu (ABI mismatch)", cfg->struct_size,
-                sizeof(hipfeat_config));
+  if (hipfeat_status bad = check_feature_config(cfg, h_window, h_mel, h_dct, h_lifter)) return bad;
   const int N = cfg->frame_length, shift = cfg->frame_shift, fft = cfg->fft_length;
-  if (cfg->kind < 0 || cfg->kind > 5) return fail(HIPFEAT_ERR_INVALID, "unknown kind %d", cfg->kind);
-  if (N <= 0 || shift <= 0 || fft < N)
-    return fail(HIPFEAT_ERR_INVALID, "need frame_length>0, frame_shift>0, fft_length>=frame_length (got %d, %d, %d)",
-                N, shift, fft);
-  if (shift > N)
-    return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", shift, N);
-  if (!h_window) return fail(HIPFEAT_ERR_INVALID, "window is NULL");
-  if (cfg->dither != 0.0f)
-    return fail(HIPFEAT_ERR_UNSUPPORTED, "dither != 0 is not supported by the library (ABI v%d): the host adds it to the samples", HIPFEAT_ABI_VERSION);
   const bool whisper = cfg->kind == HIPFEAT_WHISPER;
   if (whisper && (fft != N || cfg->snip_edges || cfg->use_energy || cfg->use_fft_mag || cfg->remove_dc_offset || cfg->preemph_coeff != 0.0f))
     return fail(HIPFEAT_ERR_INVALID, "whisper: needs fft_length == frame_length and no snip_edges / energy / magnitude / DC removal / pre-emphasis");
   const bool librosa = cfg->kind == HIPFEAT_LIBROSA_FBANK;
   if (librosa && (cfg->snip_edges || cfg->use_energy))
     return fail(HIPFEAT_ERR_INVALID, "librosa fbank: snip_edges / use_energy are not defined");
-  const bool need_mel = cfg->kind == HIPFEAT_FBANK || cfg->kind == HIPFEAT_MFCC || whisper || librosa;
-  if (need_mel && (cfg->num_filters <= 0 || !h_mel))
-    return fail(HIPFEAT_ERR_INVALID, "fbank/mfcc need num_filters>0 and a mel matrix");
-  if (cfg->kind == HIPFEAT_MFCC) {
-    if (cfg->num_ceps <= 0 || !h_dct) return fail(HIPFEAT_ERR_INVALID, "mfcc needs num_ceps>0 and a dct matrix");
-    if (cfg->apply_lifter && !h_lifter) return fail(HIPFEAT_ERR_INVALID, "apply_lifter set but lifter is NULL");
-  }
+  if ((whisper || librosa) && (cfg->num_filters <= 0 || !h_mel)) return fail(HIPFEAT_ERR_INVALID, kNeedMel);
   if (fft > 8192) return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length %d > 8192 is not supported", fft);
+  const bool need_mel = cfg->kind >= HIPFEAT_FBANK;
 
   hipfeat_plan* p = new (std::nothrow) hipfeat_plan();
   if (!p) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
@@ -769,18 +939,11 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
   p->npad_left = (whisper || librosa) ? N / 2 : (cfg->snip_edges ? 0 : (N - shift) / 2);
   const int M = need_mel ? cfg->num_filters : 0;
   const int C = cfg->kind == HIPFEAT_MFCC ? cfg->num_ceps : 0;
-  p->feature_dim = cfg->kind == HIPFEAT_FBANK ? M + (cfg->use_energy ? 1 : 0) : (cfg->kind == HIPFEAT_MFCC ? C : ((whisper || librosa) ? M : p->K));
+  p->feature_dim = feature_dim(*cfg);
 
-  if (hipfeat_status bad = check_device(device)) {
+  if (hipfeat_status bad = require_gfx950(device)) {
     delete p;
     return bad;
-  }
-  {  // the kernels are gfx950 code objects and lean on gfx950's memory pipeline (hipfeat.h, HIPFEAT_WHISPER): any other device is refused here
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-      delete p;
-      return fail(HIPFEAT_ERR_UNSUPPORTED, "device %d is not a gfx950 (MI355X-class) GPU: libhipfeat is built for that architecture alone", device);
-    }
   }
   DeviceGuard g(device);
   hipfeat_status st = HIPFEAT_OK;
@@ -789,16 +952,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     return s;
   };
 
-  // twiddles, computed in double: W_fft^k = exp(-2 pi i k / fft)
-  {
-    const int nt = p->pow2 ? std::max(p->H, 1) : fft;
-    std::vector<float2> tw(nt);
-    for (int k = 0; k < nt; ++k) {
-      const double a = -2.0 * M_PI * (double)k / (double)fft;
-      tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    if ((st = upload(&p->d_tw, tw.data(), tw.size())) != HIPFEAT_OK) return bail(st);
-  }
+  const std::vector<float2> tw = fft_twiddles(fft, p->pow2 ? p->H : fft);
+  if ((st = upload(&p->d_tw, tw.data(), tw.size())) != HIPFEAT_OK) return bail(st);
   if ((st = upload(&p->d_window, h_window, (size_t)N)) != HIPFEAT_OK) return bail(st);
   if (need_mel) {
     if ((st = upload(&p->d_mel, h_mel, (size_t)p->K * M)) != HIPFEAT_OK) return bail(st);
@@ -843,8 +998,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
   // the generic kernel's launch: it stays unless a specialised kernel claims the plan
   p->fn = reinterpret_cast<const void*>(&generic_kernel);
   p->block = 256;
-  hipError_t e = ensure_dynamic_lds(p->fn, p->lds);
-  if (e != hipSuccess) return bail(fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", p->lds, hipGetErrorName(e)));
+  if ((st = set_dynamic_lds(p->fn, p->lds)) != HIPFEAT_OK) return bail(st);
 
   // the specialised kernels, in order of preference: the first setup that claims the plan ends the search
   auto unclaimed = [&](hipfeat_status s) {
@@ -1133,12 +1287,11 @@ static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay
       gp.M = c.num_filters;
       gp.C = c.num_ceps;
       gp.kind = (whisper || librosa) ? (int)HIPFEAT_FBANK : c.kind;  // same epilogue with log10; Whisper: the post-pass below finishes it
-      gp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) |
-                 (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0) | (plan->pow2 ? F_POW2 : 0) | ((whisper || librosa) ? (F_CENTER | F_LOG10) : 0);
+      gp.flags = energy_flags(c) | (plan->pow2 ? F_POW2 : 0) | ((whisper || librosa) ? (F_CENTER | F_LOG10) : 0);
       gp.fpb = plan->fpb;
       gp.npad_left = plan->npad_left;
       gp.preemph = c.preemph_coeff;
-      gp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
+      gp.log_energy_floor = log_energy_floor(c.energy_floor);
       gp.mel_floor = c.mel_floor;
       gp.log_offset = c.log_offset;
       gp.span = plan->span;
@@ -1153,31 +1306,12 @@ static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay
       wp.wave = d_wave;
       wp.out = d_out;
       wp.cuts = lay->d_cuts;
-      wp.window = plan->d_window;
-      wp.tw = plan->d_tw;
-      wp.mel_blob = plan->d_mel_t;
-      wp.mel_blob_floats = plan->wave_blob_floats;
-      wp.dct_in_lds = plan->wave_dct_in_lds ? 1 : 0;
-      wp.dct = plan->d_dct;
-      wp.lifter = plan->d_lifter;
+      fill_wave_front(wp, c, WaveFront{plan->d_window, plan->d_tw, plan->d_mel_t, plan->d_dct, plan->d_lifter, plan->wave_blob_floats, plan->wave_dct_in_lds, plan->lds});
       wp.out_stride = lay->out_row_stride;
       wp.num_cuts = (int32_t)lay->batch;
       wp.uniform_bpc = lay->uniform_bpc;
       wp.frames_per_wave = plan->fpb / 4;
-      wp.N = c.frame_length;
-      wp.shift = c.frame_shift;
-      wp.H = plan->H;
-      wp.K = plan->K;
-      wp.M = c.num_filters;
-      wp.C = c.num_ceps;
-      wp.kind = librosa ? (int)HIPFEAT_FBANK : c.kind;
-      wp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) |
-                 (c.use_fft_mag ? F_FFT_MAG : 0) | (c.apply_lifter ? F_LIFTER : 0) | (librosa ? (F_CENTER | F_LOG10) : 0);
       wp.npad_left = plan->npad_left;
-      wp.preemph = c.preemph_coeff;
-      wp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
-      wp.mel_floor = c.mel_floor;
-      wp.log_offset = c.log_offset;
       arg = &wp;
       break;
     case Route::Whisper2:
@@ -2754,102 +2888,43 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_reset(hipfeat_stats* s
 // scalar arguments (kernel_stft.hpp)
 // --------------------------------------------------------------------------------------
 struct hipfeat_stft {
-  hipfeat_stft_config cfg{};
+  StftFront front;
   int device = 0;
-  int n1 = 0;  // 64 n1 complex points per frame (spectrum: fft / 128; frames: the smallest of 2, 4, 8, 16 that holds the frame)
   const void* fn = nullptr;
-  size_t lds = 0;
-  float* d_window = nullptr;
-  float2* d_tw = nullptr;  // spectrum: W_fft^k, k < fft / 2
 };
-constexpr int kStftFramesPerWave = 8;  // 4 waves x 8 frames per workgroup, as the wave kernel
 
-static const void* stft_entry(int n1, int output) {
-  switch (n1 * 2 + output) {
-    case 4: return entry<stft_kernel<2, 0>>();
-    case 5: return entry<stft_kernel<2, 1>>();
-    case 8: return entry<stft_kernel<4, 0>>();
-    case 9: return entry<stft_kernel<4, 1>>();
-    case 16: return entry<stft_kernel<8, 0>>();
-    case 17: return entry<stft_kernel<8, 1>>();
-    case 32: return entry<stft_kernel<16, 0>>();
-    default: return entry<stft_kernel<16, 1>>();
-  }
+extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* s) {
+  if (!s) return HIPFEAT_OK;
+  DeviceGuard g(s->device);
+  stft_front_free(s->front);
+  delete s;
+  return HIPFEAT_OK;
 }
 
 extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_create(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_stft** out) {
   if (!out) return fail(HIPFEAT_ERR_INVALID, "stft pointer is NULL");
   *out = nullptr;
-  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  if (cfg->struct_size != (int32_t)sizeof(hipfeat_stft_config))
-    return fail(HIPFEAT_ERR_INVALID, "hipfeat_stft_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_stft_config));
-  if (cfg->output != HIPFEAT_STFT_FRAMES && cfg->output != HIPFEAT_STFT_SPECTRUM) return fail(HIPFEAT_ERR_INVALID, "unknown output %d", (int)cfg->output);
-  if (cfg->frame_length <= 0 || cfg->frame_shift <= 0)
-    return fail(HIPFEAT_ERR_INVALID, "frame_length = %d, frame_shift = %d: both must be positive", (int)cfg->frame_length, (int)cfg->frame_shift);
-  if (cfg->pad_length < cfg->frame_length)
-    return fail(HIPFEAT_ERR_INVALID, "pad_length (or fft_length) = %d cannot be smaller than N = %d", (int)cfg->pad_length, (int)cfg->frame_length);
   int n1 = 0;
-  if (cfg->output == HIPFEAT_STFT_SPECTRUM) {
-    const int fft = cfg->pad_length;
-    if (fft != 256 && fft != 512 && fft != 1024 && fft != 2048)
-      return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the device STFT has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)", fft);
-    n1 = fft / 128;
-  } else {
-    if (cfg->frame_length > 2048) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_length = %d: the device front end holds frames of at most 2048 samples", (int)cfg->frame_length);
-    for (n1 = 2; 128 * n1 < cfg->frame_length; n1 *= 2) {
-    }
-  }
-  if (hipfeat_status bad = check_device(device)) return bad;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-      return fail(HIPFEAT_ERR_UNSUPPORTED, "device %d is not a gfx950 (MI355X-class) GPU: libhipfeat is built for that architecture alone", device);
-  }
-  DeviceGuard g(device);
+  if (hipfeat_status bad = check_stft_config(cfg, h_window, false, &n1)) return bad;
+  if (hipfeat_status bad = require_gfx950(device)) return bad;
   hipfeat_stft* s = new (std::nothrow) hipfeat_stft();
   if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  s->cfg = *cfg;
   s->device = device;
-  s->n1 = n1;
-  s->fn = stft_entry(n1, cfg->output);
-  s->lds = stft_lds_bytes(n1, cfg->output, cfg->frame_length);
-  hipfeat_status st = upload(&s->d_window, h_window, (size_t)cfg->frame_length);
-  if (st == HIPFEAT_OK && cfg->output == HIPFEAT_STFT_SPECTRUM) {  // twiddles, computed in double: W_fft^k = exp(-2 pi i k / fft)
-    const int fft = cfg->pad_length;
-    std::vector<float2> tw(fft / 2);
-    for (int k = 0; k < fft / 2; ++k) {
-      const double a = -2.0 * M_PI * (double)k / (double)fft;
-      tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    st = upload(&s->d_tw, tw.data(), tw.size());
-  }
-  if (st == HIPFEAT_OK) {
-    const hipError_t e = ensure_dynamic_lds(s->fn, s->lds);
-    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", s->lds, hipGetErrorName(e));
-  }
-  if (st != HIPFEAT_OK) {
-    (void)hipFree(s->d_window);
-    (void)hipFree(s->d_tw);
-    delete s;
-    return st;
+  const bool spectrum = cfg->output == HIPFEAT_STFT_SPECTRUM;
+  s->fn = for_n1(n1, [&](auto n) { return spectrum ? entry<stft_kernel<decltype(n)::value, 1>>() : entry<stft_kernel<decltype(n)::value, 0>>(); });
+  DeviceGuard g(device);
+  if (hipfeat_status bad = stft_front_create(s->front, *cfg, n1, h_window, s->fn)) {
+    hipfeat_stft_destroy(s);
+    return bad;
   }
   *out = s;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* s) {
-  if (!s) return HIPFEAT_OK;
-  DeviceGuard g(s->device);
-  (void)hipFree(s->d_window);
-  (void)hipFree(s->d_tw);
-  delete s;
   return HIPFEAT_OK;
 }
 
 extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* s, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
                                                             float* d_out, int64_t out_floats, float* d_log_energy, void* stream) {
   if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  const hipfeat_stft_config& c = s->cfg;
+  const hipfeat_stft_config& c = s->front.cfg;
   if (batch < 0 || num_samples < 0 || out_floats < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
   if (batch > 1 && row_stride < num_samples) return fail(HIPFEAT_ERR_INVALID, "row_stride = %lld < num_samples = %lld", (long long)row_stride, (long long)num_samples);
   const int64_t T = hipfeat_num_frames(num_samples, c.frame_length, c.frame_shift, c.snip_edges);
@@ -2857,38 +2932,30 @@ extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* s, con
   // (without snip_edges a row of no frames is too short as well, as for the feature plans)
   if (hipfeat_status bad = hipfeat_check_length(num_samples, c.frame_length, c.frame_shift, c.snip_edges)) return bad;
   if (T == 0) return HIPFEAT_OK;
-  const int64_t width = c.output == HIPFEAT_STFT_SPECTRUM ? (int64_t)c.pad_length + 2 : (int64_t)c.pad_length;
+  const int64_t width = s->front.width();
   if (batch > INT64_MAX / T || batch * T > INT64_MAX / width) return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
   if (out_floats < batch * T * width)
     return fail(HIPFEAT_ERR_INVALID, "output of %lld floats, %lld x %lld x %lld needed", (long long)out_floats, (long long)batch, (long long)T, (long long)width);
   if (!d_wave || !d_out) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
-  const int align = c.output == HIPFEAT_STFT_SPECTRUM ? 8 : 4;
+  const int align = s->front.spectrum() ? 8 : 4;
   if (reinterpret_cast<uintptr_t>(d_wave) % 4 || reinterpret_cast<uintptr_t>(d_out) % align || reinterpret_cast<uintptr_t>(d_log_energy) % 4)
     return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples and log-energies: 4 bytes, output: %d)", align);
   const int64_t fpb = 4 * kStftFramesPerWave, bpr = (T + fpb - 1) / fpb;
   if (bpr > INT32_MAX / batch) return fail(HIPFEAT_ERR_UNSUPPORTED, "%lld workgroups in one launch", (long long)batch * (long long)bpr);
   StftParams p{};
+  fill_stft_front(p, s->front);
   p.wave = d_wave;
   p.out = d_out;
   p.log_energy = c.want_energy ? d_log_energy : nullptr;
-  p.window = s->d_window;
-  p.tw = s->d_tw;
   p.row_stride = row_stride;
   p.num_samples = num_samples;
   p.frames_per_row = T;
   p.blocks_per_row = bpr;
-  p.N = c.frame_length;
-  p.shift = c.frame_shift;
-  p.pad = c.pad_length;
   p.npad_left = c.snip_edges ? 0 : (c.frame_length - c.frame_shift) / 2;
-  p.frames_per_wave = kStftFramesPerWave;
-  p.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.want_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0);
-  p.preemph = c.preemph_coeff;
-  p.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
   void* args[] = {&p};
   DeviceGuard g(s->device);
-  set_lds_poison(s->lds);
-  (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->lds, (hipStream_t)stream);
+  set_lds_poison(s->front.lds);
+  (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->front.lds, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return HIPFEAT_OK;
 }
@@ -2898,66 +2965,26 @@ extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* s, con
 // `forward` computes per frame and writes the remainder (kernel_stream.hpp)
 // --------------------------------------------------------------------------------------
 struct hipfeat_stream {
-  bool features = false;
-  hipfeat_config fcfg{};       // features
-  hipfeat_stft_config scfg{};  // frames / spectrum
-  int device = 0, n1 = 0;
-  int N = 0, shift = 0, snip = 0, width = 0;  // width: floats per output row
-  int H = 0, K = 0, blob_floats = 0, dct_in_lds = 0;
+  int device = 0;
   const void* fn = nullptr;
-  size_t lds = 0;
-  float* d_window = nullptr;
-  float2* d_tw = nullptr;
-  float* d_mel_blob = nullptr;
-  float* d_dct = nullptr;
-  float* d_lifter = nullptr;
+  bool features = false;
+  StftFront front;        // frames / spectrum: the STFT front end on the two-span source
+  hipfeat_config fcfg{};  // features: the wave kernel on tables of its own
+  WaveFront wave;
 };
 
-static void stream_free(hipfeat_stream* s) {
-  if (!s) return;
-  (void)hipFree(s->d_window);
-  (void)hipFree(s->d_tw);
-  (void)hipFree(s->d_mel_blob);
-  (void)hipFree(s->d_dct);
-  (void)hipFree(s->d_lifter);
+extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_destroy(hipfeat_stream* s) {
+  if (!s) return HIPFEAT_OK;
+  DeviceGuard g(s->device);
+  stft_front_free(s->front);
+  (void)hipFree(s->wave.d_window);
+  (void)hipFree(s->wave.d_tw);
+  (void)hipFree(s->wave.d_mel_blob);
+  (void)hipFree(s->wave.d_dct);
+  (void)hipFree(s->wave.d_lifter);
   delete s;
-}
-
-static const void* stream_wave_entry(int n1) {
-  return n1 == 2 ? entry<wave_stream_kernel<2>>() : (n1 == 4 ? entry<wave_stream_kernel<4>>() : (n1 == 8 ? entry<wave_stream_kernel<8>>() : entry<wave_stream_kernel<16>>()));
-}
-
-static const void* stream_stft_entry(int n1, int output) {
-  switch (n1 * 2 + output) {
-    case 4: return entry<stft_stream_kernel<2, 0>>();
-    case 5: return entry<stft_stream_kernel<2, 1>>();
-    case 8: return entry<stft_stream_kernel<4, 0>>();
-    case 9: return entry<stft_stream_kernel<4, 1>>();
-    case 16: return entry<stft_stream_kernel<8, 0>>();
-    case 17: return entry<stft_stream_kernel<8, 1>>();
-    case 32: return entry<stft_stream_kernel<16, 0>>();
-    default: return entry<stft_stream_kernel<16, 1>>();
-  }
-}
-
-static hipfeat_status stream_check_gfx950(int device) {
-  if (hipfeat_status bad = check_device(device)) return bad;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(HIPFEAT_ERR_UNSUPPORTED, "device %d is not a gfx950 (MI355X-class) GPU: libhipfeat is built for that architecture alone", device);
   return HIPFEAT_OK;
 }
-
-static std::vector<float2> stream_twiddles(int fft) {  // computed in double: W_fft^k = exp(-2 pi i k / fft), k < fft / 2
-  std::vector<float2> tw(fft / 2);
-  for (int k = 0; k < fft / 2; ++k) {
-    const double a = -2.0 * M_PI * (double)k / (double)fft;
-    tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-  }
-  return tw;
-}
-
-static bool stream_fft_size(int fft) { return fft == 256 || fft == 512 || fft == 1024 || fft == 2048; }
 
 extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_counts(int32_t frame_length, int32_t frame_shift, int32_t snip_edges, int32_t first,
                                                                    int64_t context_len, int64_t chunk_len, int64_t* frames, int64_t* remainder_len) {
@@ -2981,24 +3008,13 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_features(cons
                                                                             const float* h_dct, const float* h_lifter, int32_t device, hipfeat_stream** out) {
   if (!out) return fail(HIPFEAT_ERR_INVALID, "stream pointer is NULL");
   *out = nullptr;
-  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  if (cfg->struct_size != (int32_t)sizeof(hipfeat_config))
-    return fail(HIPFEAT_ERR_INVALID, "hipfeat_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_config));
+  if (!cfg) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (hipfeat_status bad = check_feature_config(cfg, h_window, h_mel, h_dct, h_lifter)) return bad;
   const int N = cfg->frame_length, shift = cfg->frame_shift, fft = cfg->fft_length;
-  if (cfg->kind < 0 || cfg->kind > 5) return fail(HIPFEAT_ERR_INVALID, "unknown kind %d", (int)cfg->kind);
   if (cfg->kind > HIPFEAT_MFCC) return fail(HIPFEAT_ERR_UNSUPPORTED, "kind %d: the streaming kernel has the four Kaldi layer kinds (spectrogram, log-spectrogram, fbank, mfcc)", (int)cfg->kind);
-  if (N <= 0 || shift <= 0 || fft < N)
-    return fail(HIPFEAT_ERR_INVALID, "need frame_length>0, frame_shift>0, fft_length>=frame_length (got %d, %d, %d)", N, shift, fft);
-  const bool need_mel = cfg->kind == HIPFEAT_FBANK || cfg->kind == HIPFEAT_MFCC;
-  if (need_mel && (cfg->num_filters <= 0 || !h_mel)) return fail(HIPFEAT_ERR_INVALID, "fbank/mfcc need num_filters>0 and a mel matrix");
-  if (cfg->kind == HIPFEAT_MFCC) {
-    if (cfg->num_ceps <= 0 || !h_dct) return fail(HIPFEAT_ERR_INVALID, "mfcc needs num_ceps>0 and a dct matrix");
-    if (cfg->apply_lifter && !h_lifter) return fail(HIPFEAT_ERR_INVALID, "apply_lifter set but lifter is NULL");
-  }
-  if (shift > N) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", shift, N);
-  if (cfg->dither != 0.0f) return fail(HIPFEAT_ERR_UNSUPPORTED, "dither != 0 is not supported by the library: the host adds it to the chunk");
-  if (!stream_fft_size(fft))
+  if (!radix_fft_size(fft))
     return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the streaming kernel has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)", fft);
+  const bool need_mel = cfg->kind >= HIPFEAT_FBANK;
   if (need_mel && cfg->num_filters > 128) return fail(HIPFEAT_ERR_UNSUPPORTED, "num_filters = %d: the streaming kernel holds at most 128 filters", (int)cfg->num_filters);
   const int M = need_mel ? cfg->num_filters : 0, C = cfg->kind == HIPFEAT_MFCC ? cfg->num_ceps : 0;
   // the wave kernel's own tables (plan_tables.hpp), not a plan's: a plan's tables are those of the instance it picked
@@ -3007,33 +3023,27 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_features(cons
   in.window = h_window, in.mel = h_mel, in.dct = h_dct, in.lifter = cfg->apply_lifter ? h_lifter : nullptr;
   const WaveTables t = build_wave_tables(in, fft / 2);
   if (t.lds > 160 * 1024) return fail(HIPFEAT_ERR_UNSUPPORTED, "configuration does not fit in LDS (%zu bytes)", t.lds);
-  if (hipfeat_status bad = stream_check_gfx950(device)) return bad;
+  if (hipfeat_status bad = require_gfx950(device)) return bad;
   DeviceGuard g(device);
   hipfeat_stream* s = new (std::nothrow) hipfeat_stream();
   if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
   s->features = true;
   s->fcfg = *cfg;
   s->device = device;
-  s->n1 = fft / 128;
-  s->N = N, s->shift = shift, s->snip = cfg->snip_edges ? 1 : 0;
-  s->H = fft / 2, s->K = fft / 2 + 1;
-  s->width = cfg->kind == HIPFEAT_FBANK ? M + (cfg->use_energy ? 1 : 0) : (cfg->kind == HIPFEAT_MFCC ? C : s->K);
-  s->blob_floats = (int)t.blob.size();
-  s->dct_in_lds = t.dct_in_lds ? 1 : 0;
-  s->fn = stream_wave_entry(s->n1);
-  s->lds = t.lds;
-  const std::vector<float2> tw = stream_twiddles(fft);
-  hipfeat_status st = upload(&s->d_window, h_window, (size_t)N);
-  if (st == HIPFEAT_OK) st = upload(&s->d_tw, tw.data(), tw.size());
-  if (st == HIPFEAT_OK && M > 0) st = upload(&s->d_mel_blob, t.blob.data(), t.blob.size());
-  if (st == HIPFEAT_OK && C > 0) st = upload(&s->d_dct, h_dct, (size_t)M * C);
-  if (st == HIPFEAT_OK && C > 0 && cfg->apply_lifter) st = upload(&s->d_lifter, h_lifter, (size_t)C);
-  if (st == HIPFEAT_OK) {
-    const hipError_t e = ensure_dynamic_lds(s->fn, s->lds);
-    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", s->lds, hipGetErrorName(e));
-  }
+  s->fn = for_n1(fft / 128, [](auto n) { return entry<wave_stream_kernel<decltype(n)::value>>(); });
+  WaveFront& w = s->wave;
+  w.blob_floats = (int)t.blob.size();
+  w.dct_in_lds = t.dct_in_lds;
+  w.lds = t.lds;
+  const std::vector<float2> tw = fft_twiddles(fft, fft / 2);
+  hipfeat_status st = upload(&w.d_window, h_window, (size_t)N);
+  if (st == HIPFEAT_OK) st = upload(&w.d_tw, tw.data(), tw.size());
+  if (st == HIPFEAT_OK && M > 0) st = upload(&w.d_mel_blob, t.blob.data(), t.blob.size());
+  if (st == HIPFEAT_OK && C > 0) st = upload(&w.d_dct, h_dct, (size_t)M * C);
+  if (st == HIPFEAT_OK && C > 0 && cfg->apply_lifter) st = upload(&w.d_lifter, h_lifter, (size_t)C);
+  if (st == HIPFEAT_OK) st = set_dynamic_lds(s->fn, w.lds);
   if (st != HIPFEAT_OK) {
-    stream_free(s);
+    hipfeat_stream_destroy(s);
     return st;
   }
   *out = s;
@@ -3043,59 +3053,20 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_features(cons
 extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_stft(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_stream** out) {
   if (!out) return fail(HIPFEAT_ERR_INVALID, "stream pointer is NULL");
   *out = nullptr;
-  if (!cfg || !h_window) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
-  if (cfg->struct_size != (int32_t)sizeof(hipfeat_stft_config))
-    return fail(HIPFEAT_ERR_INVALID, "hipfeat_stft_config.struct_size = %d, expected %d", (int)cfg->struct_size, (int)sizeof(hipfeat_stft_config));
-  if (cfg->output != HIPFEAT_STFT_FRAMES && cfg->output != HIPFEAT_STFT_SPECTRUM) return fail(HIPFEAT_ERR_INVALID, "unknown output %d", (int)cfg->output);
-  if (cfg->frame_length <= 0 || cfg->frame_shift <= 0)
-    return fail(HIPFEAT_ERR_INVALID, "frame_length = %d, frame_shift = %d: both must be positive", (int)cfg->frame_length, (int)cfg->frame_shift);
-  if (cfg->pad_length < cfg->frame_length)
-    return fail(HIPFEAT_ERR_INVALID, "pad_length (or fft_length) = %d cannot be smaller than N = %d", (int)cfg->pad_length, (int)cfg->frame_length);
-  if (cfg->frame_shift > cfg->frame_length)
-    return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_shift (%d) > frame_length (%d) is not supported", (int)cfg->frame_shift, (int)cfg->frame_length);
   int n1 = 0;
-  if (cfg->output == HIPFEAT_STFT_SPECTRUM) {
-    if (!stream_fft_size(cfg->pad_length))
-      return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the streaming kernel has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)",
-                  (int)cfg->pad_length);
-    n1 = cfg->pad_length / 128;
-  } else {
-    if (cfg->frame_length > 2048) return fail(HIPFEAT_ERR_UNSUPPORTED, "frame_length = %d: the device front end holds frames of at most 2048 samples", (int)cfg->frame_length);
-    for (n1 = 2; 128 * n1 < cfg->frame_length; n1 *= 2) {
-    }
-  }
-  if (hipfeat_status bad = stream_check_gfx950(device)) return bad;
-  DeviceGuard g(device);
+  if (hipfeat_status bad = check_stft_config(cfg, h_window, true, &n1)) return bad;
+  if (hipfeat_status bad = require_gfx950(device)) return bad;
   hipfeat_stream* s = new (std::nothrow) hipfeat_stream();
   if (!s) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
-  s->scfg = *cfg;
   s->device = device;
-  s->n1 = n1;
-  s->N = cfg->frame_length, s->shift = cfg->frame_shift, s->snip = cfg->snip_edges ? 1 : 0;
-  s->width = cfg->output == HIPFEAT_STFT_SPECTRUM ? cfg->pad_length + 2 : cfg->pad_length;
-  s->fn = stream_stft_entry(n1, cfg->output);
-  s->lds = stft_lds_bytes(n1, cfg->output, cfg->frame_length);
-  hipfeat_status st = upload(&s->d_window, h_window, (size_t)cfg->frame_length);
-  if (st == HIPFEAT_OK && cfg->output == HIPFEAT_STFT_SPECTRUM) {
-    const std::vector<float2> tw = stream_twiddles(cfg->pad_length);
-    st = upload(&s->d_tw, tw.data(), tw.size());
-  }
-  if (st == HIPFEAT_OK) {
-    const hipError_t e = ensure_dynamic_lds(s->fn, s->lds);
-    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "hipFuncSetAttribute(dynamic LDS = %zu B) failed: %s", s->lds, hipGetErrorName(e));
-  }
-  if (st != HIPFEAT_OK) {
-    stream_free(s);
-    return st;
+  const bool spectrum = cfg->output == HIPFEAT_STFT_SPECTRUM;
+  s->fn = for_n1(n1, [&](auto n) { return spectrum ? entry<stft_stream_kernel<decltype(n)::value, 1>>() : entry<stft_stream_kernel<decltype(n)::value, 0>>(); });
+  DeviceGuard g(device);
+  if (hipfeat_status bad = stft_front_create(s->front, *cfg, n1, h_window, s->fn)) {
+    hipfeat_stream_destroy(s);
+    return bad;
   }
   *out = s;
-  return HIPFEAT_OK;
-}
-
-extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_destroy(hipfeat_stream* s) {
-  if (!s) return HIPFEAT_OK;
-  DeviceGuard g(s->device);
-  stream_free(s);
   return HIPFEAT_OK;
 }
 
@@ -3110,10 +3081,14 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* 
   if (batch > 1 && (chunk_stride < chunk_len || (!first && context_stride < context_len)))
     return fail(HIPFEAT_ERR_INVALID, "a row stride is shorter than its row (context %lld < %lld or chunk %lld < %lld)", (long long)context_stride, (long long)context_len,
                 (long long)chunk_stride, (long long)chunk_len);
+  const hipfeat_config& fc = s->fcfg;
+  const hipfeat_stft_config& sc = s->front.cfg;
+  const int N = s->features ? fc.frame_length : sc.frame_length, shift = s->features ? fc.frame_shift : sc.frame_shift;
+  const bool snip = (s->features ? fc.snip_edges : sc.snip_edges) != 0;
   int64_t T = 0, rem = 0;
-  if (hipfeat_status bad = hipfeat_stream_counts(s->N, s->shift, s->snip, first ? 1 : 0, context_len, chunk_len, &T, &rem)) return bad;
+  if (hipfeat_status bad = hipfeat_stream_counts(N, shift, snip ? 1 : 0, first ? 1 : 0, context_len, chunk_len, &T, &rem)) return bad;
   if (batch == 0) return HIPFEAT_OK;
-  const int64_t width = s->width;
+  const int64_t width = s->features ? feature_dim(fc) : s->front.width();
   if (T > INT32_MAX || (T > 0 && (batch > INT64_MAX / T || batch * T > INT64_MAX / width)) || (rem > 0 && batch > INT64_MAX / rem))
     return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
   if (out_floats < batch * T * width)
@@ -3121,8 +3096,7 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* 
   if (remainder_floats < batch * rem)
     return fail(HIPFEAT_ERR_INVALID, "remainder of %lld floats, %lld x %lld needed", (long long)remainder_floats, (long long)batch, (long long)rem);
   if ((chunk_len > 0 && !d_chunk) || (T > 0 && !d_out) || (rem > 0 && !d_remainder)) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
-  const bool spectrum = !s->features && s->scfg.output == HIPFEAT_STFT_SPECTRUM;
-  const int align = spectrum ? 8 : 4;
+  const int align = !s->features && s->front.spectrum() ? 8 : 4;
   if (reinterpret_cast<uintptr_t>(d_context) % 4 || reinterpret_cast<uintptr_t>(d_chunk) % 4 || reinterpret_cast<uintptr_t>(d_out) % align ||
       reinterpret_cast<uintptr_t>(d_log_energy) % 4 || reinterpret_cast<uintptr_t>(d_remainder) % 4)
     return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples, log-energies and remainder: 4 bytes, output: %d)", align);
@@ -3135,63 +3109,34 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* 
   a.remainder = d_remainder;
   a.ctx_stride = context_stride;
   a.chunk_stride = chunk_stride;
-  a.flipped = first && !s->snip ? 1 : 0;
-  a.R = first ? (s->snip ? 0 : std::min<int64_t>((s->N - s->shift) / 2, chunk_len)) : context_len;
+  a.flipped = first && !snip ? 1 : 0;
+  a.R = first ? (snip ? 0 : std::min<int64_t>((N - shift) / 2, chunk_len)) : context_len;
   a.S = chunk_len;
   a.T = T;
   a.blocks_per_row = bpr;
-  a.shift = s->shift;
+  a.shift = shift;
+  // the params of either kernel; npad_left stays 0: V starts at its first frame
   WaveParams wp{};
   StftParams sp{};
   void* args[] = {nullptr, &a};
   if (s->features) {
-    const hipfeat_config& c = s->fcfg;
+    fill_wave_front(wp, fc, s->wave);
     wp.out = d_out;
-    wp.window = s->d_window;
-    wp.tw = s->d_tw;
-    wp.mel_blob = s->d_mel_blob;
-    wp.mel_blob_floats = s->blob_floats;
-    wp.dct_in_lds = s->dct_in_lds;
-    wp.dct = s->d_dct;
-    wp.lifter = s->d_lifter;
     wp.out_stride = width;
     wp.frames_per_wave = kStftFramesPerWave;
-    wp.N = c.frame_length;
-    wp.shift = c.frame_shift;
-    wp.H = s->H;
-    wp.K = s->K;
-    wp.M = (c.kind == HIPFEAT_FBANK || c.kind == HIPFEAT_MFCC) ? c.num_filters : 0;
-    wp.C = c.kind == HIPFEAT_MFCC ? c.num_ceps : 0;
-    wp.kind = c.kind;
-    wp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) |
-               (c.apply_lifter ? F_LIFTER : 0);
-    wp.npad_left = 0;  // V starts at its first frame
-    wp.preemph = c.preemph_coeff;
-    wp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
-    wp.mel_floor = c.mel_floor;
-    wp.log_offset = c.log_offset;
     args[0] = &wp;
   } else {
-    const hipfeat_stft_config& c = s->scfg;
+    fill_stft_front(sp, s->front);
     sp.out = d_out;
-    sp.log_energy = (c.want_energy && c.output == HIPFEAT_STFT_FRAMES) ? d_log_energy : nullptr;  // (the spectrum carries it in bin 0)
-    sp.window = s->d_window;
-    sp.tw = s->d_tw;
+    sp.log_energy = (sc.want_energy && !s->front.spectrum()) ? d_log_energy : nullptr;  // (the spectrum carries it in bin 0)
     sp.frames_per_row = T;
     sp.blocks_per_row = bpr;
-    sp.N = c.frame_length;
-    sp.shift = c.frame_shift;
-    sp.pad = c.pad_length;
-    sp.npad_left = 0;
-    sp.frames_per_wave = kStftFramesPerWave;
-    sp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.want_energy ? F_USE_ENERGY : 0) | (c.raw_energy ? F_RAW_ENERGY : 0);
-    sp.preemph = c.preemph_coeff;
-    sp.log_energy_floor = c.energy_floor > 0.0f ? logf(c.energy_floor) : -INFINITY;
     args[0] = &sp;
   }
+  const size_t lds = s->features ? s->wave.lds : s->front.lds;
   DeviceGuard g(s->device);
-  set_lds_poison(s->lds);
-  (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->lds, (hipStream_t)stream);
+  set_lds_poison(lds);
+  (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, lds, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return HIPFEAT_OK;
 }

@@ -174,80 +174,107 @@ class HipMfccConfig:
 # --------------------------------------------------------------------------------------
 # device plan (lazy, per extractor instance)
 # --------------------------------------------------------------------------------------
-class _Plan:
-    """Owns one ``hipfeat_plan`` (constants resident in HBM + kernel selection)."""
+class _DeviceHandle:
+    """Owns one handle of the library on one 'cuda' device: any other device is refused (there is no CPU fallback), ``close`` and
+    garbage collection destroy the handle."""
 
-    def __init__(self, cfg, kind: int, device: torch.device, mel_floor: float = constants.MEL_FLOOR):
+    _what = "extractors"
+    _destroy = ""  # the library's destroy function of the handle
+
+    def __init__(self, device: torch.device):
         self.lib = _lib.load()
         self.handle = 0
         if device.type != "cuda":
-            raise _lib.HipFeatError(1, f"Hip* extractors run on an AMD GPU ('cuda[:i]' device), got device={device}")
+            raise _lib.HipFeatError(1, f"Hip* {self._what} run on an AMD GPU ('cuda[:i]' device), got device={device}")
         if not torch.cuda.is_available():
             raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
-        if kind == KIND_LIBROSA_FBANK:  # sizes in samples; the window is the zero-padded STFT window (librosa_fbank.py:111-118)
-            n = fft = int(cfg.fft_size)
-            shift = int(cfg.hop_size)
-            window = constants.make_stft_window(cfg.window, int(cfg.win_length or fft), fft)
-        else:
-            n, shift, fft = constants.frame_sizes(cfg.sampling_rate, cfg.frame_length, cfg.frame_shift, cfg.round_to_power_of_two)
-            window = constants.make_window(n, cfg.window_type, getattr(cfg, "blackman_coeff", 0.42))
-        self.n, self.shift, self.fft = n, shift, fft
-        mel = dct = lifter = None
-        num_filters = num_ceps = 0
-        apply_lifter = 0
-        if kind in (KIND_FBANK, KIND_MFCC, KIND_WHISPER, KIND_LIBROSA_FBANK):
-            num_filters = int(cfg.num_filters)
-            if kind == KIND_LIBROSA_FBANK:
-                mel = constants.make_slaney_mel(num_filters, fft, cfg.sampling_rate, cfg.fmin or 0.0, cfg.fmax)
-            elif kind == KIND_WHISPER:
-                mel = constants.make_slaney_mel(num_filters, fft, cfg.sampling_rate)
-            elif cfg.torchaudio_compatible_mel_scale:
-                mel = constants.make_kaldi_mel(num_filters, fft, cfg.sampling_rate, cfg.low_freq, cfg.high_freq)
-            else:
-                mel = constants.make_htk_mel(num_filters, fft, cfg.sampling_rate, cfg.low_freq, cfg.high_freq, cfg.norm_filters)
-        if kind == KIND_MFCC:
-            num_ceps = int(cfg.num_ceps)
-            dct = constants.make_dct(num_ceps, num_filters)
-            apply_lifter = 1 if cfg.cepstral_lifter > 0 else 0
-            lifter = constants.make_lifter(num_ceps, cfg.cepstral_lifter)
-        c = np.zeros((), dtype=_lib.CONFIG_DTYPE)
-        c["struct_size"] = _lib.CONFIG_DTYPE.itemsize
-        c["kind"] = kind
-        c["frame_length"], c["frame_shift"], c["fft_length"] = n, shift, fft
-        c["num_filters"], c["num_ceps"] = num_filters, num_ceps
-        c["snip_edges"] = int(cfg.snip_edges)
-        c["remove_dc_offset"] = int(cfg.remove_dc_offset)
-        c["use_energy"] = int(cfg.use_energy)
-        c["raw_energy"] = int(cfg.raw_energy)
-        c["use_fft_mag"] = int(cfg.use_fft_mag)
-        c["apply_lifter"] = apply_lifter
-        c["preemph_coeff"] = cfg.preemph_coeff
-        c["energy_floor"] = cfg.energy_floor
-        c["mel_floor"] = mel_floor
-        c["log_offset"] = constants.LOG_SPEC_OFFSET
-        # dither is applied by the host mirror to the packed waveform with the device RNG (torch.randn, exactly what the
-        # reference does, layers.py:189-193); the library itself takes the (dithered) samples
-        self.dither = float(cfg.dither)
-        c["dither"] = 0.0
-        # rows an item keeps of a zero-padded batch row: compute_num_frames_from_samples counts with round(), the framing
-        # itself with floor() (lhotse/utils.py:424-434 vs layers.py:116)
-        self.batch_hop = int(round(cfg.frame_shift * cfg.sampling_rate)) if hasattr(cfg, "frame_shift") and hasattr(cfg, "sampling_rate") else shift
-        c["batch_hop"] = self.batch_hop
-        cbuf = np.ascontiguousarray(c).reshape(1)
+
+    def _create(self, create: str, *args) -> None:
+        """``create(*args, device, &handle)``."""
         out = np.zeros(1, dtype=np.uint64)
-        self.lib.check(
-            "hipfeat_plan_create",
-            _lib.addr(cbuf),
-            _lib.addr(window),
-            _lib.addr(mel),
-            _lib.addr(dct),
-            _lib.addr(lifter),
-            int(self.device.index),
-            _lib.addr(out),
-        )
+        self.lib.check(create, *args, int(self.device.index), _lib.addr(out))
         self.handle = int(out[0])
         _lib.note_plan_created()  # (the fork hazard: _lib.hip_live)
+
+    def close(self) -> None:
+        if self.handle:
+            try:
+                self.lib.raw(self._destroy, self.handle)
+            finally:
+                self.handle = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def plan_inputs(cfg, kind: int, mel_floor: float = constants.MEL_FLOOR):
+    """What ``hipfeat_plan_create`` and ``hipfeat_stream_create_features`` take for the extractor / layer options ``cfg``: the
+    ``CONFIG_DTYPE`` record (shape ``(1,)``), the window, the mel, DCT and lifter tables (``None`` where the kind has none) and
+    ``(frame length, frame shift, fft length)`` in samples."""
+    if kind == KIND_LIBROSA_FBANK:  # sizes in samples; the window is the zero-padded STFT window (librosa_fbank.py:111-118)
+        n = fft = int(cfg.fft_size)
+        shift = int(cfg.hop_size)
+        window = constants.make_stft_window(cfg.window, int(cfg.win_length or fft), fft)
+    else:
+        n, shift, fft = constants.frame_sizes(cfg.sampling_rate, cfg.frame_length, cfg.frame_shift, cfg.round_to_power_of_two)
+        window = constants.make_window(n, cfg.window_type, getattr(cfg, "blackman_coeff", 0.42))
+    mel = dct = lifter = None
+    num_filters = num_ceps = 0
+    apply_lifter = 0
+    if kind in (KIND_FBANK, KIND_MFCC, KIND_WHISPER, KIND_LIBROSA_FBANK):
+        num_filters = int(cfg.num_filters)
+        if kind == KIND_LIBROSA_FBANK:
+            mel = constants.make_slaney_mel(num_filters, fft, cfg.sampling_rate, cfg.fmin or 0.0, cfg.fmax)
+        elif kind == KIND_WHISPER:
+            mel = constants.make_slaney_mel(num_filters, fft, cfg.sampling_rate)
+        elif cfg.torchaudio_compatible_mel_scale:
+            mel = constants.make_kaldi_mel(num_filters, fft, cfg.sampling_rate, cfg.low_freq, cfg.high_freq)
+        else:
+            mel = constants.make_htk_mel(num_filters, fft, cfg.sampling_rate, cfg.low_freq, cfg.high_freq, cfg.norm_filters)
+    if kind == KIND_MFCC:
+        num_ceps = int(cfg.num_ceps)
+        dct = constants.make_dct(num_ceps, num_filters)
+        apply_lifter = 1 if cfg.cepstral_lifter > 0 else 0
+        lifter = constants.make_lifter(num_ceps, cfg.cepstral_lifter)
+    c = np.zeros(1, dtype=_lib.CONFIG_DTYPE)
+    c["struct_size"] = _lib.CONFIG_DTYPE.itemsize
+    c["kind"] = kind
+    c["frame_length"], c["frame_shift"], c["fft_length"] = n, shift, fft
+    c["num_filters"], c["num_ceps"] = num_filters, num_ceps
+    c["snip_edges"] = int(cfg.snip_edges)
+    c["remove_dc_offset"] = int(cfg.remove_dc_offset)
+    c["use_energy"] = int(cfg.use_energy)
+    c["raw_energy"] = int(cfg.raw_energy)
+    c["use_fft_mag"] = int(cfg.use_fft_mag)
+    c["apply_lifter"] = apply_lifter
+    c["preemph_coeff"] = cfg.preemph_coeff
+    c["energy_floor"] = cfg.energy_floor
+    c["mel_floor"] = mel_floor
+    c["log_offset"] = constants.LOG_SPEC_OFFSET
+    # dither is applied by the host mirror to the samples with the device RNG (torch.randn, exactly what the reference does,
+    # layers.py:189-193); the library itself takes the (dithered) samples
+    c["dither"] = 0.0
+    # rows an item keeps of a zero-padded batch row: compute_num_frames_from_samples counts with round(), the framing
+    # itself with floor() (lhotse/utils.py:424-434 vs layers.py:116).  (The streams have no batch rows and ignore it.)
+    c["batch_hop"] = int(round(cfg.frame_shift * cfg.sampling_rate)) if hasattr(cfg, "frame_shift") and hasattr(cfg, "sampling_rate") else shift
+    return c, window, mel, dct, lifter, (n, shift, fft)
+
+
+class _Plan(_DeviceHandle):
+    """Owns one ``hipfeat_plan`` (constants resident in HBM + kernel selection)."""
+
+    _destroy = "hipfeat_plan_destroy"
+
+    def __init__(self, cfg, kind: int, device: torch.device, mel_floor: float = constants.MEL_FLOOR):
+        super().__init__(device)
+        c, window, mel, dct, lifter, (self.n, self.shift, self.fft) = plan_inputs(cfg, kind, mel_floor)
+        self.dither = float(cfg.dither)
+        self.batch_hop = int(c["batch_hop"][0])
+        self._create("hipfeat_plan_create", _lib.addr(c), _lib.addr(window), _lib.addr(mel), _lib.addr(dct), _lib.addr(lifter))
         self._pair_ok = os.environ.get("HIPFEAT_COLLATED_NO_PAIR") is None
         self.feature_dim = int(self.lib.raw("hipfeat_plan_feature_dim", self.handle))
         self.kernel_name = self.lib.string("hipfeat_plan_kernel_name", self.handle)
@@ -357,17 +384,7 @@ class _Plan:
         bank = self.__dict__.pop("_bank", None)
         if bank is not None:
             bank.close()
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_plan_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 # --------------------------------------------------------------------------------------

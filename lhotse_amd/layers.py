@@ -43,22 +43,15 @@ _STREAM_SIZES = ("online_inference runs on the device for the FFT sizes 256, 512
                  "frames of at most 2048 samples, frame_shift <= frame_length and at most 128 mel filters")
 
 
-class _Stream:
+class _Stream(_E._DeviceHandle):
     """Owns one ``hipfeat_stream`` handle: the tables of one configuration on one device."""
 
+    _what, _destroy = "layers", "hipfeat_stream_destroy"
+
     def __init__(self, create: str, args: tuple, n: int, shift: int, snip_edges: bool, width: int, energy_rows: bool, device: torch.device):
-        self.lib = _lib.load()
-        self.handle = 0
-        if device.type != "cuda":
-            raise _lib.HipFeatError(1, f"Hip* layers run on an AMD GPU ('cuda[:i]' device), got device={device}")
-        if not torch.cuda.is_available():
-            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        super().__init__(device)
         self.n, self.shift, self.snip_edges, self.width, self.energy_rows = n, shift, bool(snip_edges), width, energy_rows
-        handle = np.zeros(1, dtype=np.uint64)
-        self.lib.check(create, *args, int(self.device.index), _lib.addr(handle))
-        self.handle = int(handle[0])
-        _lib.note_plan_created()
+        self._create(create, *args)
         self._counts = np.zeros(2, dtype=np.int64)
         self._spare = torch.empty(2, dtype=torch.float32, device=self.device)  # a valid address for a context of no samples
 
@@ -98,30 +91,24 @@ class _Stream:
                            None if log_e is None else (log_e.data_ptr() or None), remainder.data_ptr() or None, remainder.numel(), int(stream))
         return out, log_e, remainder
 
-    def close(self) -> None:
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_stream_destroy", self.handle)
-            finally:
-                self.handle = 0
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _open_stream(layer, *args) -> _Stream:
+    """``_Stream(*args)``; a configuration the streaming kernels do not have is ``layer``'s NotImplementedError."""
+    try:
+        return _Stream(*args)
+    except _lib.HipFeatError as e:
+        if e.status == _lib.ERR_UNSUPPORTED:
+            raise NotImplementedError(f"{type(layer).__name__}.online_inference: {e} -- {_STREAM_SIZES}; forward() still serves this configuration "
+                                      "where it did before") from e
+        raise
 
 
-def _stream_unsupported(layer, e: "_lib.HipFeatError") -> NotImplementedError:
-    return NotImplementedError(f"{type(layer).__name__}.online_inference: {e} -- {_STREAM_SIZES}; forward() still serves this configuration where it did before")
-
-
-def _check_stream_input(layer, x, context) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
-    """The argument checks of ``forward`` on the chunk, and the reference's assertions on the context (layers.py:832-833): a 2-D tensor
-    with the chunk's batch size -- here also float32 and on the chunk's device."""
+def _check_waveforms(layer, x, method: str = "forward") -> Tuple[torch.Tensor, bool]:
+    """The argument check of every layer: a float32 ``(B, T)`` or ``(T,)`` tensor that does not ask for a gradient -> (the detached
+    ``(B, T)`` batch, whether it was 1-D)."""
     name = type(layer).__name__
     if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name}.online_inference expects a torch.Tensor, got {type(x).__name__}")
+        raise TypeError(f"{name}.{method} expects a torch.Tensor, got {type(x).__name__}")
     if x.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError(f"{name} is inference-only (no autograd); call it under torch.no_grad() or detach the input")
     if x.dtype != torch.float32:
@@ -130,13 +117,20 @@ def _check_stream_input(layer, x, context) -> Tuple[torch.Tensor, Optional[torch
     if squeeze:
         x = x.unsqueeze(0)
     assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
+    return x.detach(), squeeze
+
+
+def _check_stream_input(layer, x, context) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
+    """``_check_waveforms`` on the chunk, and the reference's assertions on the context (layers.py:832-833): a 2-D tensor with the
+    chunk's batch size -- here also float32 and on the chunk's device."""
+    x, squeeze = _check_waveforms(layer, x, "online_inference")
     if context is not None:
         assert isinstance(context, torch.Tensor) and context.ndim == 2, "context must be a (B, R) tensor: the remainder of the previous call"
         assert context.shape[0] == x.shape[0], f"context has batch size {context.shape[0]}, the chunk {x.shape[0]}"
         assert context.dtype == torch.float32 and context.device == x.device, (
             f"context must be float32 on the chunk's device ({x.device}), got {context.dtype} on {context.device}")
         context = context.detach()
-    return x.detach(), context, squeeze
+    return x, context, squeeze
 
 
 class _HipLayer(torch.nn.Module):
@@ -153,16 +147,16 @@ class _HipLayer(torch.nn.Module):
         self._plans = {}
         self._streams = {}
 
+    def _plan_config(self) -> SimpleNamespace:
+        """The layer's options as ``extractors.plan_inputs`` reads them: those a kind does not have at their neutral values."""
+        return SimpleNamespace(**{**dict(num_filters=0, num_ceps=0, cepstral_lifter=0, low_freq=20.0, high_freq=-400.0, norm_filters=False,
+                                         torchaudio_compatible_mel_scale=True, use_fft_mag=False), **self._opts})
+
     def _plan_for(self, device: torch.device):
         key = (device.type, device.index)
         plan = self._plans.get(key)
         if plan is None:
-            cfg = SimpleNamespace(**self._opts)
-            for name, default in (("num_filters", 0), ("num_ceps", 0), ("cepstral_lifter", 0), ("low_freq", 20.0), ("high_freq", -400.0),
-                                  ("norm_filters", False), ("torchaudio_compatible_mel_scale", True), ("use_fft_mag", False)):
-                if not hasattr(cfg, name):
-                    setattr(cfg, name, default)
-            plan = _E._Plan(cfg, self.kind, device)  # refuses anything but a 'cuda' device: there is no CPU fallback
+            plan = _E._Plan(self._plan_config(), self.kind, device)  # refuses anything but a 'cuda' device: there is no CPU fallback
             self._plans[key] = plan
         return plan
 
@@ -176,42 +170,11 @@ class _HipLayer(torch.nn.Module):
         key = (device.type, device.index)
         s = self.__dict__.setdefault("_streams", {}).get(key)
         if s is None:
-            # the tables of hipfeat_plan_create (extractors._Plan), for the streaming kernel's own handle
-            o = {**dict(num_filters=0, num_ceps=0, cepstral_lifter=0, low_freq=20.0, high_freq=-400.0, norm_filters=False,
-                        torchaudio_compatible_mel_scale=True, use_fft_mag=False), **self._opts}
-            n, shift, fft = self._n, self._shift, self.fft_length
-            window = constants.make_window(n, o["window_type"], 0.42)
-            mel = dct = lifter = None
-            num_filters = num_ceps = apply_lifter = 0
-            if self.kind in (_E.KIND_FBANK, _E.KIND_MFCC):
-                num_filters = int(o["num_filters"])
-                if o["torchaudio_compatible_mel_scale"]:
-                    mel = constants.make_kaldi_mel(num_filters, fft, o["sampling_rate"], o["low_freq"], o["high_freq"])
-                else:
-                    mel = constants.make_htk_mel(num_filters, fft, o["sampling_rate"], o["low_freq"], o["high_freq"], o["norm_filters"])
-            if self.kind == _E.KIND_MFCC:
-                num_ceps = int(o["num_ceps"])
-                dct = constants.make_dct(num_ceps, num_filters)
-                apply_lifter = 1 if o["cepstral_lifter"] > 0 else 0
-                lifter = constants.make_lifter(num_ceps, o["cepstral_lifter"])
-            c = np.zeros(1, dtype=_lib.CONFIG_DTYPE)
-            c["struct_size"], c["kind"] = _lib.CONFIG_DTYPE.itemsize, self.kind
-            c["frame_length"], c["frame_shift"], c["fft_length"] = n, shift, fft
-            c["num_filters"], c["num_ceps"], c["apply_lifter"] = num_filters, num_ceps, apply_lifter
-            c["snip_edges"], c["remove_dc_offset"] = int(o["snip_edges"]), int(o["remove_dc_offset"])
-            c["use_energy"], c["raw_energy"], c["use_fft_mag"] = int(o["use_energy"]), int(o["raw_energy"]), int(o["use_fft_mag"])
-            c["preemph_coeff"], c["energy_floor"] = o["preemph_coeff"], o["energy_floor"]
-            c["mel_floor"], c["log_offset"] = constants.MEL_FLOOR, constants.LOG_SPEC_OFFSET
-            c["batch_hop"] = shift
-            width = {_E.KIND_FBANK: num_filters + int(bool(o["use_energy"])), _E.KIND_MFCC: num_ceps}.get(self.kind, fft // 2 + 1)
-            try:
-                s = _Stream("hipfeat_stream_create_features", (_lib.addr(c), _lib.addr(window), _lib.addr(mel), _lib.addr(dct), _lib.addr(lifter)),
-                            n, shift, o["snip_edges"], width, False, device)
-            except _lib.HipFeatError as e:
-                if e.status == _lib.ERR_UNSUPPORTED:
-                    raise _stream_unsupported(self, e) from e
-                raise
-            self._streams[key] = s
+            # the tables of hipfeat_plan_create, for the streaming kernel's own handle
+            c, window, mel, dct, lifter, (n, shift, fft) = _E.plan_inputs(self._plan_config(), self.kind)
+            width = {_E.KIND_FBANK: int(c["num_filters"][0] + c["use_energy"][0]), _E.KIND_MFCC: int(c["num_ceps"][0])}.get(self.kind, fft // 2 + 1)
+            args = tuple(_lib.addr(a) for a in (c, window, mel, dct, lifter))
+            s = self._streams[key] = _open_stream(self, "hipfeat_stream_create_features", args, n, shift, self._opts["snip_edges"], width, False, device)
         return s
 
     def online_inference(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -231,19 +194,10 @@ class _HipLayer(torch.nn.Module):
         return (out[0] if squeeze else out), remainder
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{type(self).__name__}.forward expects a torch.Tensor, got {type(x).__name__}")
-        if x.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(f"{type(self).__name__} is inference-only (no autograd); call it under torch.no_grad() or detach the input")
-        if x.dtype != torch.float32:
-            raise TypeError(f"{type(self).__name__}: expected float32 samples, got {x.dtype}")
-        squeeze = x.ndim == 1
-        if squeeze:
-            x = x.unsqueeze(0)
-        assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
+        x, squeeze = _check_waveforms(self, x)
         plan = self._plan_for(x.device)
         B, T = x.shape
-        wave = x.detach().contiguous().reshape(-1)
+        wave = x.contiguous().reshape(-1)
         offs = np.arange(B, dtype=np.int64) * T
         lens = np.full(B, T, dtype=np.int64)
         try:
@@ -325,33 +279,32 @@ class HipWav2MFCC(_HipLayer):
 # --------------------------------------------------------------------------------------
 # Wav2Win / Wav2FFT: the two layers whose output is not a real feature matrix (hipfeat_stft_*, csrc/kernel_stft.hpp)
 # --------------------------------------------------------------------------------------
-class _Stft:
+def _stft_inputs(win: "HipWav2Win", output: int) -> Tuple[np.ndarray, np.ndarray, int, bool]:
+    """What ``hipfeat_stft_create`` and ``hipfeat_stream_create_stft`` take for ``win``: the ``STFT_CONFIG_DTYPE`` record and the window;
+    with them the floats of an output row and whether the log-energies come as rows of their own (the spectrum carries its log-energy
+    in bin 0: no separate row of them is asked for)."""
+    spectrum = output == _lib.STFT_SPECTRUM
+    cfg = np.zeros(1, dtype=_lib.STFT_CONFIG_DTYPE)
+    cfg["struct_size"] = _lib.STFT_CONFIG_DTYPE.itemsize
+    cfg["output"], cfg["frame_length"], cfg["frame_shift"], cfg["pad_length"] = output, win._length, win._shift, win.pad_length
+    cfg["snip_edges"], cfg["remove_dc_offset"] = int(bool(win.snip_edges)), int(bool(win.remove_dc_offset))
+    cfg["raw_energy"], cfg["want_energy"] = int(bool(win.raw_energy)), int(bool(win.return_log_energy))
+    cfg["preemph_coeff"], cfg["energy_floor"] = float(win.preemph_coeff), float(win.energy_floor)
+    window = np.ascontiguousarray(win._window.detach().cpu().numpy(), dtype=np.float32)
+    assert window.shape == (win._length,)
+    return cfg, window, win.pad_length + 2 if spectrum else win.pad_length, bool(win.return_log_energy) and not spectrum
+
+
+class _Stft(_E._DeviceHandle):
     """Owns one ``hipfeat_stft`` handle: the window (and twiddles) of one configuration on one device."""
 
-    def __init__(self, output: int, n: int, shift: int, pad: int, layer, window: np.ndarray, device: torch.device):
-        self.lib = _lib.load()
-        self.handle = 0
-        if device.type != "cuda":
-            raise _lib.HipFeatError(1, f"Hip* layers run on an AMD GPU ('cuda[:i]' device), got device={device}")
-        if not torch.cuda.is_available():
-            raise _lib.HipFeatError(2, "no HIP device is visible (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
-        self.output, self.n, self.shift, self.pad = output, n, shift, pad
-        self.snip_edges = bool(layer.snip_edges)
-        self.want_energy = bool(layer.return_log_energy)
-        self.width = pad + 2 if output == _lib.STFT_SPECTRUM else pad
-        cfg = np.zeros(1, dtype=_lib.STFT_CONFIG_DTYPE)
-        cfg["struct_size"] = _lib.STFT_CONFIG_DTYPE.itemsize
-        cfg["output"], cfg["frame_length"], cfg["frame_shift"], cfg["pad_length"] = output, n, shift, pad
-        cfg["snip_edges"], cfg["remove_dc_offset"] = int(self.snip_edges), int(bool(layer.remove_dc_offset))
-        cfg["raw_energy"], cfg["want_energy"] = int(bool(layer.raw_energy)), int(self.want_energy)
-        cfg["preemph_coeff"], cfg["energy_floor"] = float(layer.preemph_coeff), float(layer.energy_floor)
-        window = np.ascontiguousarray(window, dtype=np.float32)
-        assert window.shape == (n,)
-        handle = np.zeros(1, dtype=np.uint64)
-        self.lib.check("hipfeat_stft_create", _lib.addr(cfg), _lib.addr(window), int(self.device.index), _lib.addr(handle))
-        self.handle = int(handle[0])
-        _lib.note_plan_created()
+    _what, _destroy = "layers", "hipfeat_stft_destroy"
+
+    def __init__(self, win: "HipWav2Win", output: int, device: torch.device):
+        super().__init__(device)
+        self.n, self.shift, self.snip_edges = win._length, win._shift, bool(win.snip_edges)
+        cfg, window, self.width, self.energy_rows = _stft_inputs(win, output)
+        self._create("hipfeat_stft_create", _lib.addr(cfg), _lib.addr(window))
 
     def run(self, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """x: (B, S) float32 on the handle's device -> ((B, T, width) float32, (B, T) log-energies or None), on the current stream."""
@@ -361,42 +314,11 @@ class _Stft:
         frames = int(self.lib.raw("hipfeat_num_frames", S, self.n, self.shift, int(self.snip_edges)))
         with torch.cuda.device(self.device):
             out = torch.empty((B, frames, self.width), dtype=torch.float32, device=self.device)
-            # the spectrum carries its log-energy in bin 0: no separate row of them is asked for
-            want_rows = self.want_energy and self.output == _lib.STFT_FRAMES
-            log_e = torch.empty((B, frames), dtype=torch.float32, device=self.device) if want_rows else None
+            log_e = torch.empty((B, frames), dtype=torch.float32, device=self.device) if self.energy_rows else None
             stream = torch.cuda.current_stream(self.device).cuda_stream
             self.lib.check("hipfeat_stft_run", self.handle, x.data_ptr(), B, S, int(x.stride(0)) if B > 1 else S, out.data_ptr(), out.numel(),
                            None if log_e is None else log_e.data_ptr(), int(stream))
         return out, log_e
-
-    def close(self) -> None:
-        if self.handle:
-            try:
-                self.lib.raw("hipfeat_stft_destroy", self.handle)
-            finally:
-                self.handle = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _check_waveforms(layer, x) -> Tuple[torch.Tensor, bool]:
-    """The argument checks of ``_HipLayer.forward``: a float32 ``(B, T)`` or ``(T,)`` tensor that does not ask for a gradient."""
-    name = type(layer).__name__
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name}.forward expects a torch.Tensor, got {type(x).__name__}")
-    if x.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError(f"{name} is inference-only (no autograd); call it under torch.no_grad() or detach the input")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32 samples, got {x.dtype}")
-    squeeze = x.ndim == 1
-    if squeeze:
-        x = x.unsqueeze(0)
-    assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
-    return x.detach(), squeeze
 
 
 class HipWav2Win(torch.nn.Module):
@@ -451,7 +373,7 @@ class HipWav2Win(torch.nn.Module):
         h = self._handles.get(key)
         if h is None:
             try:
-                h = _Stft(output, self._length, self._shift, self.pad_length, self, self._window.detach().cpu().numpy(), device)
+                h = _Stft(self, output, device)
             except _lib.HipFeatError as e:
                 if e.status == _lib.ERR_UNSUPPORTED:
                     raise NotImplementedError(
@@ -484,23 +406,9 @@ class HipWav2Win(torch.nn.Module):
         key = (device.type, device.index, output, "stream")
         s = self._handles.get(key)
         if s is None:
-            cfg = np.zeros(1, dtype=_lib.STFT_CONFIG_DTYPE)
-            cfg["struct_size"] = _lib.STFT_CONFIG_DTYPE.itemsize
-            cfg["output"], cfg["frame_length"], cfg["frame_shift"], cfg["pad_length"] = output, self._length, self._shift, self.pad_length
-            cfg["snip_edges"], cfg["remove_dc_offset"] = int(bool(self.snip_edges)), int(bool(self.remove_dc_offset))
-            cfg["raw_energy"], cfg["want_energy"] = int(bool(self.raw_energy)), int(bool(self.return_log_energy))
-            cfg["preemph_coeff"], cfg["energy_floor"] = float(self.preemph_coeff), float(self.energy_floor)
-            window = np.ascontiguousarray(self._window.detach().cpu().numpy(), dtype=np.float32)
-            spectrum = output == _lib.STFT_SPECTRUM
-            try:
-                # (the spectrum carries its log-energy in bin 0: no separate row of them is asked for)
-                s = _Stream("hipfeat_stream_create_stft", (_lib.addr(cfg), _lib.addr(window)), self._length, self._shift, self.snip_edges,
-                            self.pad_length + 2 if spectrum else self.pad_length, bool(self.return_log_energy) and not spectrum, device)
-            except _lib.HipFeatError as e:
-                if e.status == _lib.ERR_UNSUPPORTED:
-                    raise _stream_unsupported(layer, e) from e
-                raise
-            self._handles[key] = s
+            cfg, window, width, energy_rows = _stft_inputs(self, output)
+            s = self._handles[key] = _open_stream(layer, "hipfeat_stream_create_stft", (_lib.addr(cfg), _lib.addr(window)), self._length, self._shift,
+                                                  self.snip_edges, width, energy_rows, device)
         return s
 
     def _online(self, x: torch.Tensor, context: Optional[torch.Tensor], output: int, layer):
@@ -569,16 +477,19 @@ class HipWav2FFT(torch.nn.Module):
     def dither(self) -> float:
         return self.wav2win.dither
 
+    def _complex(self, out: torch.Tensor, squeeze: bool) -> torch.Tensor:
+        """Rows of ``fft_length + 2`` floats as ``fft_length / 2 + 1`` complex bins."""
+        spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
+        return spec[0] if squeeze else spec
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _check_waveforms(self, x)  # (refusals name this layer)
         out, _, squeeze = self.wav2win._run(x, _lib.STFT_SPECTRUM)
-        spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
-        return spec[0] if squeeze else spec
+        return self._complex(out, squeeze)
 
     def online_inference(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The reference's chunked, stateless streaming call (layers.py:326-333): ``(spectrum, remainder)``, the ``complex64`` STFT of the
         complete frames of ``[context | x]`` and the samples they did not consume; see ``HipWav2Win.online_inference``, whose framing,
         remainder and zero-frame rule (``(B, 0, fft_length / 2 + 1)`` where the reference raises) this shares."""
         out, _, remainder, squeeze = self.wav2win._online(x, context, _lib.STFT_SPECTRUM, self)
-        spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
-        return (spec[0] if squeeze else spec), remainder
+        return self._complex(out, squeeze), remainder

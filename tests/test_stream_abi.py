@@ -205,6 +205,41 @@ def test_every_refusal_of_create_features_comes_before_any_device_call():
         assert create(cfg) == HIP and out[0] == 0
 
 
+def test_the_creators_that_share_a_config_refuse_it_with_one_status_and_one_text():
+    """hipfeat_stft_create / hipfeat_stream_create_stft and hipfeat_plan_create / hipfeat_stream_create_features check their config
+    struct with one piece of code each: a config that breaks one shared rule gets the same status and the same words from both."""
+    lib = _lib.load()
+    window = np.ones(2049, dtype=np.float32)
+    mel = np.zeros((1025, 128), dtype=np.float32)
+    dct = np.zeros((128, 40), dtype=np.float32)
+    lifter = np.ones(40, dtype=np.float32)
+    out = np.full(1, 7, dtype=np.uint64)
+
+    def refusal(name, *tables):
+        out[0] = 7
+        st = lib.raw(name, *[None if t is None else _lib.addr(t) for t in tables], FAR, _lib.addr(out))
+        assert out[0] == 0
+        return st, lib.last_error()
+
+    stft = [stft_config(struct_size=40), stft_config(struct_size=48), stft_config(output=-1), stft_config(output=2), stft_config(frame_shift=0),
+            stft_config(frame_shift=-160), stft_config(frame_length=0, pad_length=0), stft_config(pad_length=399), stft_config(output=0, pad_length=399),
+            stft_config(output=0, frame_length=2049, pad_length=2049)]
+    stft += [stft_config(pad_length=fft, frame_length=n, frame_shift=n // 2) for fft, n in ((400, 400), (128, 100), (768, 400), (513, 400), (4096, 2400))]
+    for cfg in stft:
+        one, two = refusal("hipfeat_stft_create", cfg, window), refusal("hipfeat_stream_create_stft", cfg, window)
+        assert one == two and one[0] in (INVALID, UNSUPPORTED) and one[1], (cfg, one, two)
+
+    mfcc = dict(kind=3, num_filters=23, num_ceps=13)
+    features = [(feature_config(struct_size=72),), (feature_config(kind=-1),), (feature_config(kind=6),), (feature_config(frame_length=0),),
+                (feature_config(frame_shift=0),), (feature_config(fft_length=399),), (feature_config(num_filters=0),),
+                (feature_config(kind=3, num_filters=23, num_ceps=0),), (feature_config(), window, None), (feature_config(**mfcc), window, mel, None),
+                (feature_config(**mfcc, apply_lifter=1), window, mel, dct, None), (feature_config(frame_shift=401),), (feature_config(dither=1.0),)]
+    for cfg, *given in features:
+        tables = given + [window, mel, dct, lifter][len(given):]
+        one, two = refusal("hipfeat_plan_create", cfg, *tables), refusal("hipfeat_stream_create_features", cfg, *tables)
+        assert one == two and one[0] in (INVALID, UNSUPPORTED) and one[1], (cfg, one, two)
+
+
 def test_null_handles_are_refused_without_a_device():
     lib = _lib.load()
     assert lib.raw("hipfeat_stream_run", None, None, 0, 0, None, 16000, 16000, 1, None, 0, None, None, 0, None) == INVALID
