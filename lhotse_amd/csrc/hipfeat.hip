@@ -669,17 +669,20 @@ static hipfeat_status claim_tile(hipfeat_plan* p, Route route, const void* fn, c
 static bool fft512c_has_flat(int nrows, int N) { return nrows == 13 && N >= 384; }
 
 // (rows, frame length, mode) -> kernel instance
-template <int MODE, bool WIDE = false>
+template <int MODE, bool WIDE = false, int T0 = kCMaxSteps, int T1 = kCMaxSteps>
 static const void* fft512c_pick(int nrows, int N, bool flat) {
-  if (flat && fft512c_has_flat(nrows, N)) return entry<fft512c_kernel<13, 12, MODE, true, WIDE>>();
-  if (nrows == 10) return entry<fft512c_kernel<10, 0, MODE, false, WIDE>>();
+  if (flat && fft512c_has_flat(nrows, N)) return entry<fft512c_kernel<13, 12, MODE, true, WIDE, T0, T1>>();
+  if (nrows == 10) return entry<fft512c_kernel<10, 0, MODE, false, WIDE, T0, T1>>();
   // 25 ms at 16 kHz (N = 400: 12 full rows of 32 samples + a partial one) gets the instance without length masks on the full rows
-  if (nrows == 13 && N >= 384) return entry<fft512c_kernel<13, 12, MODE, false, WIDE>>();
-  if (nrows == 13) return entry<fft512c_kernel<13, 0, MODE, false, WIDE>>();
-  return entry<fft512c_kernel<16, 0, MODE, false, WIDE>>();
+  if (nrows == 13 && N >= 384) return entry<fft512c_kernel<13, 12, MODE, false, WIDE, T0, T1>>();
+  if (nrows == 13) return entry<fft512c_kernel<13, 0, MODE, false, WIDE, T0, T1>>();
+  return entry<fft512c_kernel<16, 0, MODE, false, WIDE, T0, T1>>();
 }
-// wide: the transposed accumulators with one 16-byte store per lane and set (log-mel modes only)
-static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat, bool wide) {
+// wide: the transposed accumulators with one 16-byte store per lane and set (log-mel modes only); mode 0: with the steps `ts` of the
+// two accumulator sets compiled in (fft512c_geom.hpp::fft512c_mel_steps)
+static const void* fft512c_dispatch(int mode, int nrows, int N, bool flat, bool wide, Fft512cMelSteps ts) {
+  if (wide && mode == 0 && ts.t0 == 16 && ts.t1 == 12) return fft512c_pick<0, true, 16, 12>(nrows, N, flat);
+  if (wide && mode == 0 && ts.t0 == 16 && ts.t1 == 8) return fft512c_pick<0, true, 16, 8>(nrows, N, flat);
   if (wide && mode <= 1) return mode == 0 ? fft512c_pick<0, true>(nrows, N, flat) : fft512c_pick<1, true>(nrows, N, flat);
   return mode == 0 ? fft512c_pick<0>(nrows, N, flat)
                    : (mode == 1 ? fft512c_pick<1>(nrows, N, flat) : (mode == 2 ? fft512c_pick<2>(nrows, N, flat) : fft512c_pick<3>(nrows, N, flat)));
@@ -697,15 +700,21 @@ static hipfeat_status setup_fft512c(hipfeat_plan* p, const PlanInputs& in, int n
   // instances with transposed accumulators then store a lane's four columns with one 16-byte store.  HIPFEAT_NO_WIDE_STORE (routing switch)
   // keeps the one-dword-per-frame epilogue, which the other filter counts and the MFCC modes always have: same bits either way.
   const bool wide = !mfcc && t.mode <= 1 && in.M % 4 == 0 && !route_env("HIPFEAT_NO_WIDE_STORE");
+  // The wide two-set instances run the schedule's own steps per set where an instance has them compiled in; the table keeps the padded
+  // layout.  HIPFEAT_NO_FIXED_SCHEDULE (routing switch) keeps the instance that walks the padding too: same bits either way.
+  const Fft512cMelSteps padded = {kCMaxSteps, kCMaxSteps};
+  const Fft512cMelSteps ts = (wide && t.mode == 0 && !route_env("HIPFEAT_NO_FIXED_SCHEDULE")) ? fft512c_mel_steps(t.sch_nsets, t.sch_set_steps) : padded;
+  // the exchange rows are read 16 bytes at a time: every wave's region starts on a 16-byte boundary
+  if (t.shared_floats % 4 != 0 || t.xs_floats % 4 != 0) return fail(HIPFEAT_ERR_INVALID, "fft512c: a wave's LDS region is not 16-byte aligned");
   // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
-  hipfeat_status st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false, wide), t, 4, 8, 16,
+  hipfeat_status st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false, wide, ts), t, 4, 8, 16,
                                       strf("fft512c_kernel<%d> %s", nrows, mfcc ? "mfcc" : "fbank"));
   if (st == HIPFEAT_OK && wide) p->kernel_name += " store=16B";
   const void** more[3] = {&p->fn_flat, &p->fn_far, &p->fn_flat_far};  // the same launch shape, chosen per layout (build_descs) / per launch
   for (int i = 0; st == HIPFEAT_OK && i < 3; ++i) {
     const bool flat = i != 1, far = i != 0;
     if ((flat && !fft512c_has_flat(nrows, in.N)) || (far && !wide)) continue;
-    *more[i] = fft512c_dispatch(t.mode, nrows, in.N, flat, wide && !far);
+    *more[i] = fft512c_dispatch(t.mode, nrows, in.N, flat, wide && !far, far ? padded : ts);
     st = set_dynamic_lds(*more[i], t.lds);
   }
   return st;

@@ -23,16 +23,11 @@
 // One __syncthreads() at kernel start (constant tables), none afterwards.
 #pragma once
 #include "common.hpp"
+#include "fft512c_geom.hpp"  // kCExRowStride, kCExFrameStride, kCPRowStride, kCRegion, kCMaxSets, kCMaxSteps
 #include "fft_common.hpp"
 
 namespace hipfeat {
 
-constexpr int kCExRowStride = 34;                          // dwords per exchange row (16 complex + 2 pad)
-constexpr int kCExFrameStride = 8 * kCExRowStride + 16;    // 288 (== 32 mod 64): 8 rows per half
-constexpr int kCPRowStride = 272;                          // dwords per power row (== 16 mod 64: the 4 frames of a slot hit disjoint bank quads)
-constexpr int kCRegion = 4 * kCExFrameStride + 16;         // 1168 dwords per wave; the 4 power rows (1088) alias it
-constexpr int kCMaxSets = 2;                               // accumulator sets (16 slots each)
-constexpr int kCMaxSteps = 16;                             // MFMA steps per set
 constexpr int kCWaves = 8;                                 // waves per workgroup
 constexpr int kCLmStride = 48;                             // MFCC: floats per log-mel row in LDS (<= 40 filters; rows 3 bank quads apart)
 constexpr int kCDctChunks = 10;                            // MFCC: DCT steps / 4 (<= 40 filters), operands resident in registers
@@ -69,66 +64,57 @@ struct Fft512cParams {
 // lane-index multiplies: v_mul_u32_u24 issues at the full VALU rate, v_mul_lo_u32 at a quarter of it
 __device__ __forceinline__ int mul24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
 
-// The LDS exchange between the two FFT passes of one wave, as ONE instruction sequence: the rows k1 = 0..7 (`lo`, replaced by the
-// result) go through the wave's 8-row blocks and every lane reads "its" row q % 8 back, then the rows k1 = 8..15 (`hi`) go through the
-// same blocks and the lanes with q >= 8 (`hi_lanes`, an exec mask) read their row again, over the first result.  A wave's LDS operations
-// execute and return in order, so nothing has to be waited for in between: half 1's writes follow half 0's reads of the same block
-// through the queue, half 1's reads see half 1's writes, and their data lands in the registers after half 0's.  hipcc, which orders
-// the two loads of one register with a wait, put a full `s_waitcnt lgkmcnt(0)` -- one loaded LDS round trip per round on the wave's
-// serial path -- between half 1's writes and reads.  The one wait at the end covers all of it.  `hi` and the addresses are read by
-// instructions issued after the first loads, so no result register may share theirs (early clobber).
+// The LDS exchange between the two FFT passes of one wave, as ONE instruction sequence: the rows k1 = 0..7 (`lo`) go through the wave's
+// 8-row blocks and every lane reads "its" row q % 8 back, then the rows k1 = 8..15 (`hi`) go through the same blocks and the lanes with
+// q >= 8 (`hi_lanes`, an exec mask) read their row again, over the first result.  A wave's LDS operations execute and return in order, so
+// nothing has to be waited for in between: half 1's writes follow half 0's reads of the same block through the queue, half 1's reads see
+// half 1's writes, and their data lands in the registers after half 0's.  hipcc, which orders the two loads of one register with a wait,
+// put a full `s_waitcnt lgkmcnt(0)` -- one loaded LDS round trip per round on the wave's serial path -- between half 1's writes and
+// reads.  The one wait at the end covers all of it.  A row is read with eight ds_read_b128 (fft512c_geom.hpp): r[j] = columns 2 j and
+// 2 j + 1.  `hi` and the addresses are read by instructions issued after the first loads, so no result register may share theirs (early
+// clobber); `lo` is read by half 0's writes alone, which sit in a statement of their own in front: the results may take its registers
+// (a DS write has read its data by the time a later read of the same queue returns; an operand tied to `lo` would have to name half
+// of a 128-bit register group, which inline asm cannot), and 16 VGPRs of a 126-register kernel stay free.
 // wr: LDS byte address of (block of the lane's frame, row 0, column q); rd: of (same block, row q % 8, column 0)
-__device__ __forceinline__ void exchange_halves(unsigned wr, unsigned rd, unsigned long long hi_lanes, v2 (&lo)[8], const v2 (&hi)[8],
-                                                v2 (&up)[8]) {
-  static_assert(kCExRowStride == 34, "the row offsets below are 17 rr (in 8-byte units)");
+__device__ __forceinline__ void exchange_halves(unsigned wr, unsigned rd, unsigned long long hi_lanes, const v2 (&lo)[8], const v2 (&hi)[8],
+                                                f32x4 (&r)[8]) {
+  static_assert(kCExRowStride == 36, "the row offsets below are 18 rr (in 8-byte units)");
   unsigned long long saved;
   asm volatile(
-      "ds_write2_b64 %[wr], %[l0], %[l1] offset1:17\n\t"
-      "ds_write2_b64 %[wr], %[l2], %[l3] offset0:34 offset1:51\n\t"
-      "ds_write2_b64 %[wr], %[l4], %[l5] offset0:68 offset1:85\n\t"
-      "ds_write2_b64 %[wr], %[l6], %[l7] offset0:102 offset1:119\n\t"
-      "ds_read_b64 %[l0], %[rd]\n\t"
-      "ds_read_b64 %[l1], %[rd] offset:8\n\t"
-      "ds_read_b64 %[l2], %[rd] offset:16\n\t"
-      "ds_read_b64 %[l3], %[rd] offset:24\n\t"
-      "ds_read_b64 %[l4], %[rd] offset:32\n\t"
-      "ds_read_b64 %[l5], %[rd] offset:40\n\t"
-      "ds_read_b64 %[l6], %[rd] offset:48\n\t"
-      "ds_read_b64 %[l7], %[rd] offset:56\n\t"
-      "ds_read_b64 %[u0], %[rd] offset:64\n\t"
-      "ds_read_b64 %[u1], %[rd] offset:72\n\t"
-      "ds_read_b64 %[u2], %[rd] offset:80\n\t"
-      "ds_read_b64 %[u3], %[rd] offset:88\n\t"
-      "ds_read_b64 %[u4], %[rd] offset:96\n\t"
-      "ds_read_b64 %[u5], %[rd] offset:104\n\t"
-      "ds_read_b64 %[u6], %[rd] offset:112\n\t"
-      "ds_read_b64 %[u7], %[rd] offset:120\n\t"
-      "ds_write2_b64 %[wr], %[h0], %[h1] offset1:17\n\t"
-      "ds_write2_b64 %[wr], %[h2], %[h3] offset0:34 offset1:51\n\t"
-      "ds_write2_b64 %[wr], %[h4], %[h5] offset0:68 offset1:85\n\t"
-      "ds_write2_b64 %[wr], %[h6], %[h7] offset0:102 offset1:119\n\t"
+      "ds_write2_b64 %[wr], %[l0], %[l1] offset1:18\n\t"
+      "ds_write2_b64 %[wr], %[l2], %[l3] offset0:36 offset1:54\n\t"
+      "ds_write2_b64 %[wr], %[l4], %[l5] offset0:72 offset1:90\n\t"
+      "ds_write2_b64 %[wr], %[l6], %[l7] offset0:108 offset1:126"
+      :
+      : [l0] "v"(lo[0]), [l1] "v"(lo[1]), [l2] "v"(lo[2]), [l3] "v"(lo[3]), [l4] "v"(lo[4]), [l5] "v"(lo[5]), [l6] "v"(lo[6]),
+        [l7] "v"(lo[7]), [wr] "v"(wr)
+      : "memory");
+  asm volatile(
+      "ds_read_b128 %[r0], %[rd]\n\t"
+      "ds_read_b128 %[r1], %[rd] offset:16\n\t"
+      "ds_read_b128 %[r2], %[rd] offset:32\n\t"
+      "ds_read_b128 %[r3], %[rd] offset:48\n\t"
+      "ds_read_b128 %[r4], %[rd] offset:64\n\t"
+      "ds_read_b128 %[r5], %[rd] offset:80\n\t"
+      "ds_read_b128 %[r6], %[rd] offset:96\n\t"
+      "ds_read_b128 %[r7], %[rd] offset:112\n\t"
+      "ds_write2_b64 %[wr], %[h0], %[h1] offset1:18\n\t"
+      "ds_write2_b64 %[wr], %[h2], %[h3] offset0:36 offset1:54\n\t"
+      "ds_write2_b64 %[wr], %[h4], %[h5] offset0:72 offset1:90\n\t"
+      "ds_write2_b64 %[wr], %[h6], %[h7] offset0:108 offset1:126\n\t"
       "s_and_saveexec_b64 %[sv], %[hm]\n\t"
-      "ds_read_b64 %[l0], %[rd]\n\t"
-      "ds_read_b64 %[l1], %[rd] offset:8\n\t"
-      "ds_read_b64 %[l2], %[rd] offset:16\n\t"
-      "ds_read_b64 %[l3], %[rd] offset:24\n\t"
-      "ds_read_b64 %[l4], %[rd] offset:32\n\t"
-      "ds_read_b64 %[l5], %[rd] offset:40\n\t"
-      "ds_read_b64 %[l6], %[rd] offset:48\n\t"
-      "ds_read_b64 %[l7], %[rd] offset:56\n\t"
-      "ds_read_b64 %[u0], %[rd] offset:64\n\t"
-      "ds_read_b64 %[u1], %[rd] offset:72\n\t"
-      "ds_read_b64 %[u2], %[rd] offset:80\n\t"
-      "ds_read_b64 %[u3], %[rd] offset:88\n\t"
-      "ds_read_b64 %[u4], %[rd] offset:96\n\t"
-      "ds_read_b64 %[u5], %[rd] offset:104\n\t"
-      "ds_read_b64 %[u6], %[rd] offset:112\n\t"
-      "ds_read_b64 %[u7], %[rd] offset:120\n\t"
+      "ds_read_b128 %[r0], %[rd]\n\t"
+      "ds_read_b128 %[r1], %[rd] offset:16\n\t"
+      "ds_read_b128 %[r2], %[rd] offset:32\n\t"
+      "ds_read_b128 %[r3], %[rd] offset:48\n\t"
+      "ds_read_b128 %[r4], %[rd] offset:64\n\t"
+      "ds_read_b128 %[r5], %[rd] offset:80\n\t"
+      "ds_read_b128 %[r6], %[rd] offset:96\n\t"
+      "ds_read_b128 %[r7], %[rd] offset:112\n\t"
       "s_mov_b64 exec, %[sv]\n\t"
       "s_waitcnt lgkmcnt(0)"
-      : [l0] "+&v"(lo[0]), [l1] "+&v"(lo[1]), [l2] "+&v"(lo[2]), [l3] "+&v"(lo[3]), [l4] "+&v"(lo[4]), [l5] "+&v"(lo[5]),
-        [l6] "+&v"(lo[6]), [l7] "+&v"(lo[7]), [u0] "=&v"(up[0]), [u1] "=&v"(up[1]), [u2] "=&v"(up[2]), [u3] "=&v"(up[3]),
-        [u4] "=&v"(up[4]), [u5] "=&v"(up[5]), [u6] "=&v"(up[6]), [u7] "=&v"(up[7]), [sv] "=&s"(saved)
+      : [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]), [r5] "=&v"(r[5]), [r6] "=&v"(r[6]),
+        [r7] "=&v"(r[7]), [sv] "=&s"(saved)
       : [h0] "v"(hi[0]), [h1] "v"(hi[1]), [h2] "v"(hi[2]), [h3] "v"(hi[3]), [h4] "v"(hi[4]), [h5] "v"(hi[5]), [h6] "v"(hi[6]),
         [h7] "v"(hi[7]), [wr] "v"(wr), [rd] "v"(rd), [hm] "s"(hi_lanes)
       : "memory", "scc");
@@ -187,7 +173,12 @@ __device__ __forceinline__ void span_pieces(const char* src, unsigned lds, unsig
 // global_store_dwordx4 per lane and set instead of four global_store_dword per set, one row base per round instead of four, and no
 // wave-uniform branch on the number of live frames (fft_common.hpp::mel4_store_wide).  Chosen at plan creation (hipfeat.hip); launched
 // with row strides below kMel4WideMaxStride only.
-template <int NROWS, int NFULL, int MODE, bool FLAT = false, bool WIDE = false>
+//
+// T0 >= T1 (MODE 0 with WIDE): the steps of the two accumulator sets, where the plan's schedule is one an instance has compiled in
+// (fft512c_geom.hpp::fft512c_mel_steps; the 80-filter default is {16, 12}).  The weight table keeps its 16-step layout; the steps past a
+// set's own have zero weights, and fmaf(0, P, acc) with P finite (the padding past bin 256 is zeroed every round) and acc >= +0 is acc:
+// leaving out their operand reads and MFMAs -- 2 of 16 ds_read_b128 and 4 of 32 MFMAs per round for the default -- changes no bit.
+template <int NROWS, int NFULL, int MODE, bool FLAT = false, bool WIDE = false, int T0 = kCMaxSteps, int T1 = kCMaxSteps>
 __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   HF_POISON_LDS(smem);
@@ -220,6 +211,8 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
   float* xs = smem + p.shared_floats + wv * (p.xs_floats + kCRegion);
   float* myreg = xs + p.xs_floats;
   static_assert(!WIDE || MODE == 0 || MODE == 1, "the 16-byte store is the log-mel epilogue's");
+  static_assert((T0 == kCMaxSteps && T1 == kCMaxSteps) || (MODE == 0 && WIDE), "the trimmed sets are the wide MODE 0 instances'");
+  static_assert(T0 % 4 == 0 && T1 % 4 == 0 && 0 < T1 && T1 <= T0 && T0 <= kCMaxSteps, "whole chunks of 4 steps, the longer set first");
   const bool dc = (p.flags & F_REMOVE_DC) != 0;
   const float inv_n = 1.0f / (float)N;
   const float c = p.preemph;
@@ -436,13 +429,14 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
 #else
       {
         typedef __attribute__((address_space(3))) float lds_float;
-        v2 lo[8], hi[8], up[8];
+        v2 lo[8], hi[8];
+        f32x4 rw[8];  // the lane's row, two complex columns per 16-byte read
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) lo[rr] = a[rr], hi[rr] = a[8 + rr];
         exchange_halves((unsigned)(size_t)(lds_float*)(exf + 2 * q), (unsigned)(size_t)(lds_float*)(exf + mul24(q % 8, kCExRowStride)),
-                        __builtin_amdgcn_ballot_w64(q >= 8), lo, hi, up);
+                        __builtin_amdgcn_ballot_w64(q >= 8), lo, hi, rw);
 #pragma unroll
-        for (int n2 = 0; n2 < 8; ++n2) b[n2] = lo[n2], b[8 + n2] = up[n2];
+        for (int j = 0; j < 8; ++j) b[2 * j] = v2{rw[j][0], rw[j][1]}, b[2 * j + 1] = v2{rw[j][2], rw[j][3]};
       }
 #endif
       HFC_T(3);  // exchange
@@ -544,7 +538,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       const float* pa = myreg + lt_poff[s];
       const float* wb = wtab + s * (T * 64) + 4 * lane_o;
 #pragma unroll
-      for (int c4 = 0; c4 < T / 4; ++c4) {
+      for (int c4 = 0; c4 < (MODE == 0 ? (s == 0 ? T0 : T1) : T) / 4; ++c4) {  // (a set's own steps; the table keeps T per set)
 #if defined(HIPFEAT_ABL_NO_MELOPS) || defined(HIPFEAT_ABL_NO_MEL_A)
         av[s][c4] = f32x4{1.f, 2.f, 3.f, 4.f} * __builtin_bit_cast(float, lane_o);
 #else
@@ -564,12 +558,13 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       // next link of the SAME chain only after 16 -- set after set (what the per-set loop compiled to) ran at half the matrix-core rate.
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-      for (int c4 = 0; c4 < (S * T) / 8; ++c4) {
+      for (int c4 = 0; c4 < (MODE == 0 ? T0 / 4 : (S * T) / 8); ++c4) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           if (MODE == 0 && WIDE) {  // D[i][j] += A[i] B[j], register i, lane j: weight first = filters in the registers, frames on the lanes
             acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[0][c4][i], av[0][c4][i], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[S - 1][c4][i], av[S - 1][c4][i], acc[1], 0, 0, 0);
+            if (4 * c4 < T1)  // (the shorter chain ends early; the order inside each chain is the 16-step one)
+              acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[S - 1][c4][i], av[S - 1][c4][i], acc[1], 0, 0, 0);
           } else if (WIDE) {
             acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[0][2 * c4][i], av[0][2 * c4][i], acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(bv[0][2 * c4 + 1][i], av[0][2 * c4 + 1][i], acc[1], 0, 0, 0);

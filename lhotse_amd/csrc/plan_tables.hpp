@@ -107,6 +107,7 @@ struct WaveAutoTables {
   int wtab_off = 0, ltab_off = 0, shared_floats = 0, xs_floats = 0, tws_off = 0, tw32_off = 0;
   int w_nsets = 0, w_steps[4] = {}, w_step0[4] = {};  // fft1024c / fft2048c: the sets the kernel walks
   int sch_nsets = 0, sch_steps = 0;                   // the schedule as built: sets x total steps (kernel name)
+  int sch_set_steps[4] = {};                          // the schedule as built: steps of every set (fft512c: the instance with them compiled in)
   size_t lds = 0;
 };
 
@@ -127,6 +128,7 @@ inline void append_mel4(WaveAutoTables& t, const Mel4Schedule& sch, Mel4Pad pad,
     img.resize(img.size() + (size_t)(padded - sch.steps[s2]) * 64, 0.0f);
     if (pad != Mel4Pad::Fixed) t.w_steps[s2] = padded, t.w_step0[s2] = step0, t.w_nsets = sch.nsets;
     t.sch_steps += pad == Mel4Pad::Steps8 ? padded : sch.steps[s2];
+    t.sch_set_steps[s2] = sch.steps[s2];
     step0 += padded;
   }
   if (pad == Mel4Pad::Fixed) img.resize((size_t)t.wtab_off + (size_t)tsets * tsteps * 64, 0.0f);
