@@ -50,6 +50,7 @@ extern "C" {
 #define HIPFEAT_STATS_API HIPFEAT_API
 #define HIPFEAT_STFT_API HIPFEAT_API
 #define HIPFEAT_STREAM_API HIPFEAT_API
+#define HIPFEAT_GRAD_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -724,6 +725,66 @@ HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* stream_hand
                                                      const float* d_chunk, int64_t chunk_len, int64_t chunk_stride, int64_t batch, float* d_out,
                                                      int64_t out_floats, float* d_log_energy, float* d_remainder, int64_t remainder_floats, void* stream);
 HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_destroy(hipfeat_stream* stream_handle);
+
+/* ---- waveform gradient of the six Kaldi layers (additive to ABI v8) ------------------------------------------------------ */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_grad_*; the version number did not change because nothing that existed
+ * changed.  No new config struct: a gradient handle takes the hipfeat_config of hipfeat_stream_create_features (the four kinds
+ * HIPFEAT_SPECTROGRAM ... HIPFEAT_MFCC) or the hipfeat_stft_config of hipfeat_stream_create_stft (frames, spectrum), under the limits of
+ * the streaming kernels: fft_length 256, 512, 1024 or 2048, frames of at most 2048 samples, at most 128 filters, frame_shift <=
+ * frame_length.
+ *
+ * Every parameter of the reference layers has requires_grad=False; the only gradient there is is the one with respect to the waveform,
+ * and its definition is the autograd of lhotse/features/kaldi/layers.py.  Per frame t with gathered samples s_i, i < N, the forward is
+ * that of hipfeat_stft_run: d = s - mean(s) (layers.py:155-157), e_raw = max(log(sum d^2 + 1e-15), log floor) (layers.py:859-870),
+ * p_i = d_i - c d_{max(i-1,0)} (layers.py:165-167), w_i = p_i win_i with zeros up to pad / fft (layers.py:170-181), e_win the same energy
+ * on w (layers.py:183-185), X = rfft(w) (layers.py:314).  The backward, in this order:
+ *
+ *   1. seed        Gbar_k, k = 0 ... fft / 2, from the output cotangent ybar.  Power: Gbar = 2 Pbar X; magnitude: Gbar = Mbar X / |X|, 0
+ *                  where X = 0 (layers.py:38-42).  Log: Pbar = ybar / (P + 1e-15) (layers.py:466-468).  Mel: Pbar_k = sum_m fb[k,m] ybar_m
+ *                  [mel_m > eps] / mel_m with mel_m recomputed and eps = mel_floor (layers.py:571-572).  MFCC: first ybar_mel = dct (lifter *
+ *                  cbar) (layers.py:708-722).  Where use_energy puts the log-energy into bin 0 / column 0 (layers.py:317, 399, 470; the
+ *                  prepended column of layers.py:575; C0 of HIPFEAT_MFCC) that element's cotangent is ebar and seeds no bin.  The spectrum's
+ *                  cotangent is complex in torch's convention: for a real loss with dL = sum a dRe X + b dIm X it is a + ib, interleaved
+ *                  (re, im) pairs, no factor 2 and no 1 / fft.
+ *   2. adjoint FFT wbar_n = sum_k Re(Gbar_k e^{+2 pi i k n / fft}) for n < N: the imaginary parts of bins 0 and fft / 2 drop out, the adjoint
+ *                  of zero padding is truncation.  Computed as the adjoint split step and the forward's three register passes on
+ *                  conjugated data; there is no direct DFT.  A frames handle starts here with wbar = its cotangent.
+ *   3. front end   wbar_i += 2 w_i ebar / (sum w^2 + 1e-15) when the windowed energy was used and not floored; pbar = win wbar;
+ *                  dbar_i = pbar_i - c pbar_{i+1} for i < N - 1, dbar_{N-1} = pbar_{N-1}, and dbar_0 additionally gets -c pbar_0 (the replicate
+ *                  pad of layers.py:166); dbar_i += 2 d_i ebar / (sum d^2 + 1e-15) for the raw energy when not floored; sbar = dbar -
+ *                  mean(dbar) with remove_dc_offset.
+ *   4. overlap-add sample j of a row receives sbar_{t,i} from every (t, i) whose index lands on j; the index map is that of
+ *                  layers.py:747-772 (snip_edges, or the flip-reflection at both ends: j' = t shift - npad_left + i, j' < 0 -> -j' - 1,
+ *                  j' >= S -> 2 S - 1 - j').  The sum runs in a fixed order: ascending t, the direct contribution before the reflected one.
+ *                  Samples no frame reads get exactly 0.0.  Every element of d_grad_wave[b][0 .. num_samples) is written.
+ *
+ * Two launches per piece of rows on `stream`: steps 1-3 write every frame's sbar as a row of Nr = (N + 3) & ~3 floats into the caller's
+ * workspace (rows, T, Nr), step 4 gathers it.  No atomics: the gradient of a row is the same bits alone or in any batch, from run to run
+ * and under any piece size.  hipfeat_grad_workspace is host arithmetic and touches no device: rows_per_piece = max(1, budget_bytes / (T Nr
+ * 4)), at most batch, and floats = rows_per_piece T Nr -- a single row larger than the budget gets a workspace of its own size.
+ * hipfeat_grad_run processes workspace_floats / (T Nr) rows per piece, so any workspace that holds one row will do; it must be 16-byte
+ * aligned.  d_grad_out is the (batch, T, row) cotangent of the handle's output, contiguous, rows as hipfeat_stream_run writes them
+ * (the spectrum: fft_length + 2 floats); for a frames handle it may be NULL (a zero cotangent), as may d_grad_log_energy, the (batch, T)
+ * cotangent of its log-energies, which no other handle reads.  Waveform row b at d_wave + b * row_stride ELEMENTS, its gradient at
+ * d_grad_wave + b * grad_wave_stride.  dither: the caller adds it and passes the dithered waveform.
+ *
+ * Statuses, as for hipfeat_stft_* / hipfeat_stream_*: NULL arguments, negative sizes, misaligned pointers, a cotangent smaller than batch
+ * * T * row floats, a workspace smaller than one row's T Nr floats and (batch > 1) a stride shorter than its row are HIPFEAT_ERR_INVALID
+ * and launch nothing; a row too short for the reflection is HIPFEAT_ERR_TOO_SHORT; an unsupported size or kind and a device that is not a
+ * gfx950 are HIPFEAT_ERR_UNSUPPORTED.  Every refusal that does not depend on the device comes BEFORE any device call.  batch == 0 is
+ * HIPFEAT_OK and launches nothing.  Every call on a NULL object is HIPFEAT_ERR_INVALID and needs no device; destroying NULL is OK.
+ */
+typedef struct hipfeat_grad hipfeat_grad;
+HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_create_features(const hipfeat_config* cfg, const float* h_window, const float* h_mel, const float* h_dct,
+                                                             const float* h_lifter, int32_t device, hipfeat_grad** out);
+HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_create_stft(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_grad** out);
+HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_workspace(const hipfeat_grad* grad, int64_t batch, int64_t num_samples, int64_t budget_bytes,
+                                                       int64_t* rows_per_piece, int64_t* floats);
+HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_run(hipfeat_grad* grad, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
+                                                 const float* d_grad_out, int64_t grad_out_floats, const float* d_grad_log_energy, float* d_grad_wave,
+                                                 int64_t grad_wave_stride, float* d_workspace, int64_t workspace_floats, void* stream);
+HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_destroy(hipfeat_grad* grad);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

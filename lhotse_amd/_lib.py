@@ -198,8 +198,23 @@ _STREAM_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
     "hipfeat_stream_destroy": ("int", ["hipfeat_stream*"]),
 }
+# Likewise (HIPFEAT_GRAD_API in the header).
+_GRAD_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_grad_create_features": (
+        "int",
+        ["const hipfeat_config*", "const float*", "const float*", "const float*", "const float*", "int32_t", "hipfeat_grad**"],
+    ),
+    "hipfeat_grad_create_stft": ("int", ["const hipfeat_stft_config*", "const float*", "int32_t", "hipfeat_grad**"]),
+    "hipfeat_grad_workspace": ("int", ["const hipfeat_grad*", "int64_t", "int64_t", "int64_t", "int64_t*", "int64_t*"]),
+    "hipfeat_grad_run": (
+        "int",
+        ["hipfeat_grad*", "const float*", "int64_t", "int64_t", "int64_t", "const float*", "int64_t", "const float*", "float*", "int64_t", "float*", "int64_t",
+         "void*"],
+    ),
+    "hipfeat_grad_destroy": ("int", ["hipfeat_grad*"]),
+}
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
-                     **_STREAM_SIGNATURES}
+                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -310,7 +325,8 @@ class _CffiBackend:
             if s.startswith("#") or s.startswith('extern "C"') or s == "}":
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
-                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", ""))
+                        .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
+                        .replace("HIPFEAT_GRAD_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

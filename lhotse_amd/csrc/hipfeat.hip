@@ -45,6 +45,8 @@
 #include "kernel_wave.hpp"
 #include "kernel_stft.hpp"
 #include "kernel_stream.hpp"
+#include "kernel_grad.hpp"
+#include "grad_tables.hpp"
 #include "host_bulk.hpp"
 
 using namespace hipfeat;
@@ -3147,6 +3149,198 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* 
   set_lds_poison(lds);
   (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, lds, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Waveform gradient of the six layers (the autograd of layers.py): per piece of rows one launch that writes every frame's sbar into the
+// caller's workspace and one that gathers it into the waveform's gradient (kernel_grad.hpp, grad_tables.hpp)
+// --------------------------------------------------------------------------------------
+struct hipfeat_grad {
+  int device = 0;
+  const void* fn = nullptr;
+  int mode = 0, n1 = 0, N = 0, shift = 0, fft = 0, M = 0, C = 0, width = 0, flags = 0;
+  bool snip = false, energy_rows = false, blob_in_lds = false;
+  float preemph = 0.f, log_floor = 0.f, mel_floor = 0.f, log_offset = 0.f;
+  size_t lds = 0, off_tw = 0, off_tw64 = 0, off_blob = 0;  // bytes into the slot
+  int blob_floats = 0, off_fwd = 0, off_bwd = 0, off_dct = 0, off_lifter = 0;
+  StagedSlot slot;  // device: [window | W_fft^k | W_fft^k in float64 | filterbank blob], staged once at creation
+};
+
+extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_destroy(hipfeat_grad* g) {
+  if (!g) return HIPFEAT_OK;
+  DeviceGuard guard(g->device);
+  g->slot.free_all();
+  delete g;
+  return HIPFEAT_OK;
+}
+
+// the checked handle `g` on `device`: the kernel instance, its LDS, and the tables through the handle's slot
+static hipfeat_status grad_finish_create(hipfeat_grad* g, int32_t device, const float* h_window, const GradTables& t, hipfeat_grad** out) {
+  const bool spectral = g->mode != GRAD_FRAMES;
+  g->device = device;
+  g->fn = for_n1(g->n1, [](auto n) { return entry<grad_frames_kernel<decltype(n)::value>>(); });
+  g->blob_floats = (int)t.blob.size();
+  g->off_fwd = t.off_fwd, g->off_bwd = t.off_bwd, g->off_dct = t.off_dct, g->off_lifter = t.off_lifter;
+  g->blob_in_lds = g->blob_floats > 0 && grad_blob_fits_lds(g->n1, g->N, t.blob.size());
+  g->lds = sizeof(float) * (grad_lds_floats(g->n1, g->N) + (g->blob_in_lds ? t.blob.size() : 0));
+  const size_t win_bytes = sizeof(float) * (size_t)((g->N + 3) & ~3), tw_bytes = spectral ? sizeof(float2) * (size_t)(g->fft / 2) : 0;
+  g->off_tw = win_bytes;
+  g->off_tw64 = (win_bytes + tw_bytes + 15) & ~(size_t)15;
+  std::vector<double> tw64;  // (re, im) of W_fft^k, k < fft / 2: the recomputed spectrum of the feature kinds runs in float64
+  if (g->mode <= GRAD_MFCC)
+    for (int k = 0; k < g->fft / 2; ++k) {
+      const double a = -2.0 * M_PI * (double)k / (double)g->fft;
+      tw64.push_back(std::cos(a)), tw64.push_back(std::sin(a));
+    }
+  g->off_blob = g->off_tw64 + sizeof(double) * tw64.size();
+  const size_t total = g->off_blob + sizeof(float) * t.blob.size();
+  const std::vector<float2> tw = spectral ? fft_twiddles(g->fft, g->fft / 2) : std::vector<float2>();
+  DeviceGuard guard(device);
+  hipError_t e = stage(g->slot, total, total, nullptr, [&](unsigned char* h) {
+    std::memset(h, 0, total);
+    std::memcpy(h, h_window, sizeof(float) * (size_t)g->N);
+    if (!tw.empty()) std::memcpy(h + g->off_tw, tw.data(), tw_bytes);
+    if (!tw64.empty()) std::memcpy(h + g->off_tw64, tw64.data(), sizeof(double) * tw64.size());
+    if (!t.blob.empty()) std::memcpy(h + g->off_blob, t.blob.data(), sizeof(float) * t.blob.size());
+  });
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  hipfeat_status st = e == hipSuccess ? HIPFEAT_OK : fail(HIPFEAT_ERR_HIP, "staging the gradient tables failed: %s", hipGetErrorName(e));
+  if (st == HIPFEAT_OK) st = set_dynamic_lds(g->fn, g->lds);
+  if (st != HIPFEAT_OK) {
+    hipfeat_grad_destroy(g);
+    return st;
+  }
+  *out = g;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_create_features(const hipfeat_config* cfg, const float* h_window, const float* h_mel, const float* h_dct,
+                                                                        const float* h_lifter, int32_t device, hipfeat_grad** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "grad pointer is NULL");
+  *out = nullptr;
+  if (!cfg) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (hipfeat_status bad = check_feature_config(cfg, h_window, h_mel, h_dct, h_lifter)) return bad;
+  const int fft = cfg->fft_length;
+  if (cfg->kind > HIPFEAT_MFCC) return fail(HIPFEAT_ERR_UNSUPPORTED, "kind %d: the gradient kernel has the four Kaldi layer kinds (spectrogram, log-spectrogram, fbank, mfcc)", (int)cfg->kind);
+  if (!radix_fft_size(fft))
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "fft_length = %d: the gradient kernel has the sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms)", fft);
+  const bool need_mel = cfg->kind >= HIPFEAT_FBANK;
+  if (need_mel && cfg->num_filters > 128) return fail(HIPFEAT_ERR_UNSUPPORTED, "num_filters = %d: the gradient kernel holds at most 128 filters", (int)cfg->num_filters);
+  const int M = need_mel ? cfg->num_filters : 0, C = cfg->kind == HIPFEAT_MFCC ? cfg->num_ceps : 0;
+  const GradTables t = build_grad_tables(fft / 2 + 1, M, C, h_mel, h_dct, cfg->apply_lifter ? h_lifter : nullptr);
+  if (hipfeat_status bad = require_gfx950(device)) return bad;
+  hipfeat_grad* g = new (std::nothrow) hipfeat_grad();
+  if (!g) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  g->mode = cfg->kind;
+  g->n1 = fft / 128;
+  g->N = cfg->frame_length, g->shift = cfg->frame_shift, g->fft = fft, g->M = M, g->C = C;
+  g->width = feature_dim(*cfg);
+  g->flags = energy_flags(*cfg);
+  g->snip = cfg->snip_edges != 0;
+  g->preemph = cfg->preemph_coeff;
+  g->log_floor = log_energy_floor(cfg->energy_floor);
+  g->mel_floor = cfg->mel_floor;
+  g->log_offset = cfg->log_offset;
+  return grad_finish_create(g, device, h_window, t, out);
+}
+
+extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_create_stft(const hipfeat_stft_config* cfg, const float* h_window, int32_t device, hipfeat_grad** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "grad pointer is NULL");
+  *out = nullptr;
+  int n1 = 0;
+  if (hipfeat_status bad = check_stft_config(cfg, h_window, true, &n1)) return bad;
+  if (hipfeat_status bad = require_gfx950(device)) return bad;
+  hipfeat_grad* g = new (std::nothrow) hipfeat_grad();
+  if (!g) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  const bool spectrum = cfg->output == HIPFEAT_STFT_SPECTRUM;
+  g->mode = spectrum ? GRAD_SPECTRUM : GRAD_FRAMES;
+  g->n1 = n1;
+  g->N = cfg->frame_length, g->shift = cfg->frame_shift, g->fft = cfg->pad_length;
+  g->width = cfg->pad_length + (spectrum ? 2 : 0);
+  g->flags = energy_flags(*cfg);
+  g->snip = cfg->snip_edges != 0;
+  g->energy_rows = cfg->want_energy && !spectrum;
+  g->preemph = cfg->preemph_coeff;
+  g->log_floor = log_energy_floor(cfg->energy_floor);
+  return grad_finish_create(g, device, h_window, GradTables(), out);
+}
+
+extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_workspace(const hipfeat_grad* g, int64_t batch, int64_t num_samples, int64_t budget_bytes,
+                                                                  int64_t* rows_per_piece, int64_t* floats) {
+  if (!g || !rows_per_piece || !floats) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  *rows_per_piece = *floats = 0;
+  if (batch < 0 || num_samples < 0 || budget_bytes < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  GradPieces pc;
+  if (!grad_pieces(batch, hipfeat_num_frames(num_samples, g->N, g->shift, g->snip), g->N, budget_bytes, &pc))
+    return fail(HIPFEAT_ERR_INVALID, "%lld rows of %lld samples overflow", (long long)batch, (long long)num_samples);
+  *rows_per_piece = pc.rows_per_piece;
+  *floats = pc.floats;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_run(hipfeat_grad* g, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
+                                                            const float* d_grad_out, int64_t grad_out_floats, const float* d_grad_log_energy, float* d_grad_wave,
+                                                            int64_t grad_wave_stride, float* d_workspace, int64_t workspace_floats, void* stream) {
+  if (!g) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (batch < 0 || num_samples < 0 || grad_out_floats < 0 || workspace_floats < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  if (batch > 1 && (row_stride < num_samples || grad_wave_stride < num_samples))
+    return fail(HIPFEAT_ERR_INVALID, "a row stride is shorter than its row (waveform %lld, gradient %lld, num_samples = %lld)", (long long)row_stride,
+                (long long)grad_wave_stride, (long long)num_samples);
+  const int64_t T = hipfeat_num_frames(num_samples, g->N, g->shift, g->snip);
+  if (batch == 0) return HIPFEAT_OK;
+  if (hipfeat_status bad = hipfeat_check_length(num_samples, g->N, g->shift, g->snip)) return bad;
+  if (num_samples == 0) return HIPFEAT_OK;
+  GradPieces pc;
+  if (!grad_pieces(batch, T, g->N, 0, &pc) || (T > 0 && batch > INT64_MAX / T / g->width))
+    return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
+  const bool frames_mode = g->mode == GRAD_FRAMES;
+  if (!d_grad_out && !frames_mode) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer (only a frames handle takes a NULL output cotangent)");
+  if (d_grad_out && grad_out_floats < batch * T * g->width)
+    return fail(HIPFEAT_ERR_INVALID, "output cotangent of %lld floats, %lld x %lld x %lld needed", (long long)grad_out_floats, (long long)batch, (long long)T,
+                (long long)g->width);
+  if (!d_wave || !d_grad_wave) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
+  if (T > 0 && (!d_workspace || workspace_floats < pc.row_floats))
+    return fail(HIPFEAT_ERR_INVALID, "workspace of %lld floats, one row of %lld frames needs %lld", (long long)workspace_floats, (long long)T, (long long)pc.row_floats);
+  if (reinterpret_cast<uintptr_t>(d_wave) % 4 || reinterpret_cast<uintptr_t>(d_grad_out) % 4 || reinterpret_cast<uintptr_t>(d_grad_log_energy) % 4 ||
+      reinterpret_cast<uintptr_t>(d_grad_wave) % 4 || reinterpret_cast<uintptr_t>(d_workspace) % 16)
+    return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples, cotangents and gradient: 4 bytes, workspace: 16)");
+  const int64_t fpb = 4 * kStftFramesPerWave, bpr = (T + fpb - 1) / fpb, gpr = (num_samples + 3) / 4 + 1;
+  if (bpr > INT32_MAX || gpr > (int64_t)INT32_MAX * 128) return fail(HIPFEAT_ERR_UNSUPPORTED, "a row of %lld samples is too long for one launch", (long long)num_samples);
+  int64_t rpp = T > 0 ? workspace_floats / pc.row_floats : batch;
+  rpp = std::min({rpp, batch, T > 0 ? INT32_MAX / bpr : batch, (int64_t)INT32_MAX * 128 / gpr});
+  GradParams p{};
+  const unsigned char* tables = static_cast<const unsigned char*>(g->slot.d);
+  p.window = reinterpret_cast<const float*>(tables);
+  p.tw = frames_mode ? nullptr : reinterpret_cast<const float2*>(tables + g->off_tw);
+  p.tw64 = g->mode <= GRAD_MFCC ? reinterpret_cast<const double2*>(tables + g->off_tw64) : nullptr;
+  p.blob = g->blob_floats ? reinterpret_cast<const float*>(tables + g->off_blob) : nullptr;
+  p.ws = d_workspace;
+  p.row_stride = row_stride, p.num_samples = num_samples, p.frames_per_row = T, p.blocks_per_row = bpr, p.width = g->width;
+  p.N = g->N, p.Nr = (int32_t)pc.Nr, p.shift = g->shift, p.npad_left = g->snip ? 0 : (g->N - g->shift) / 2;
+  p.frames_per_wave = kStftFramesPerWave, p.flags = g->flags, p.mode = g->mode;
+  p.M = g->M, p.C = g->C, p.blob_floats = g->blob_floats, p.blob_in_lds = g->blob_in_lds ? 1 : 0;
+  p.off_fwd = g->off_fwd, p.off_bwd = g->off_bwd, p.off_dct = g->off_dct, p.off_lifter = g->off_lifter;
+  p.preemph = g->preemph, p.log_energy_floor = g->log_floor, p.mel_floor = g->mel_floor, p.log_offset = g->log_offset;
+  GradOlaParams o{};
+  o.ws = d_workspace;
+  o.S = num_samples, o.T = T, o.groups_per_row = gpr, o.stride = grad_wave_stride;
+  o.N = g->N, o.Nr = (int32_t)pc.Nr, o.shift = g->shift, o.npad_left = p.npad_left;
+  DeviceGuard guard(g->device);
+  set_lds_poison(g->lds);
+  for (int64_t r0 = 0; r0 < batch; r0 += rpp) {
+    const int64_t rows = std::min(rpp, batch - r0);
+    p.wave = d_wave + r0 * row_stride;
+    p.gout = d_grad_out ? d_grad_out + r0 * T * g->width : nullptr;
+    p.glog_e = (g->energy_rows && d_grad_log_energy) ? d_grad_log_energy + r0 * T : nullptr;
+    o.gwave = d_grad_wave + r0 * grad_wave_stride;
+    o.rows = rows;
+    void* pa[] = {&p};
+    void* oa[] = {&o};
+    if (T > 0) (void)hipLaunchKernel(g->fn, dim3((unsigned)(rows * bpr)), dim3(256), pa, g->lds, (hipStream_t)stream);
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(grad_overlap_add_kernel), dim3((unsigned)((rows * gpr + 255) / 256)), dim3(256), oa, 0, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+  }
   return HIPFEAT_OK;
 }
 

@@ -5,8 +5,14 @@ Drop-ins for the ``torch.nn.Module``s of lhotse/features/kaldi/layers.py (``Wav2
 ``Wav2LogFilterBank`` :476-578, ``Wav2MFCC`` :581-724) where they are used for inference: same constructor arguments and
 defaults (in the same order), same attributes, ``forward(x)`` maps a ``(B, T)`` (or ``(T,)``) float32 batch of equally long
 waveforms on the GPU to ``(B, num_frames, F)`` on the same device -- one fused launch instead of the ~12 tensor ops of
-``Wav2Win`` + ``_rfft`` + matmul + log.  Not covered, by design: autograd (inputs that
-require grad are refused) and TorchScript.
+``Wav2Win`` + ``_rfft`` + matmul + log.  Not covered, by design: TorchScript.
+
+Autograd is opt-in: ``layer.differentiable_()`` (all six classes; ``differentiable_(False)`` switches it off, ``layer.differentiable``
+reads it) makes ``forward`` backpropagate to the waveform, which is the only gradient the reference layers have (every parameter of
+theirs is ``requires_grad=False``).  The forward is the same launch and the same bits; the backward is ``hipfeat_grad_run``
+(csrc/kernel_grad.hpp: per frame the recomputed forward, the seeded spectrum cotangent, the adjoint FFT and front end into a workspace,
+then a gather without atomics), for the configurations of the streaming kernels.  A default layer refuses inputs that require a gradient
+exactly as before, and ``online_inference`` always does.
 
 ``HipWav2Win`` (:59-197) and ``HipWav2FFT`` (:227-324) hand out what the four above compute on the way and discard: the preprocessed
 frames, ``(B, num_frames, pad_length)`` with the optional ``(B, num_frames)`` log-energies, and their complex STFT,
@@ -103,6 +109,102 @@ def _open_stream(layer, *args) -> _Stream:
         raise
 
 
+# --------------------------------------------------------------------------------------
+# differentiable_(): the waveform gradient, one hipfeat_grad handle per (layer, device, output) (csrc/kernel_grad.hpp)
+# --------------------------------------------------------------------------------------
+_GRAD_WORKSPACE_BYTES = 128 << 20  # rows are processed in pieces whose per-frame gradients fit this many bytes (half the Infinity Cache)
+_GRAD_LIMITS = ("the waveform gradient runs on the device for the FFT sizes 256, 512, 1024 and 2048 (round_to_power_of_two=True, 8 to 48 kHz at 25 ms), "
+                "frames of at most 2048 samples, frame_shift <= frame_length and at most 128 mel filters")
+
+
+class _Grad(_E._DeviceHandle):
+    """Owns one ``hipfeat_grad`` handle: the tables of one configuration on one device."""
+
+    _what, _destroy = "layers", "hipfeat_grad_destroy"
+
+    def __init__(self, layer, create: str, args: tuple, device: torch.device):
+        super().__init__(device)
+        try:
+            self._create(create, *args)
+        except _lib.HipFeatError as e:
+            if e.status == _lib.ERR_UNSUPPORTED:
+                raise NotImplementedError(f"{type(layer).__name__} in differentiable mode: {e} -- {_GRAD_LIMITS}; the plain forward() still "
+                                          "serves this configuration where it did before") from e
+            raise
+        self._sizes = np.zeros(2, dtype=np.int64)
+
+    def run(self, x: torch.Tensor, grad_out: Optional[torch.Tensor], grad_log_e: Optional[torch.Tensor]) -> torch.Tensor:
+        """x (B, S): the saved waveform; grad_out (B, T, width) / grad_log_e (B, T): the cotangents (either may be None for the frames
+        output) -> the (B, S) gradient, a fresh tensor every element of which the launches write; on the current stream."""
+        x = _Stream._rows(x)
+        B, S = x.shape
+        with torch.cuda.device(self.device):
+            grad = torch.empty((B, S), dtype=torch.float32, device=self.device)
+            if B == 0 or S == 0:
+                return grad
+            z = self._sizes
+            self.lib.check("hipfeat_grad_workspace", self.handle, B, S, int(_GRAD_WORKSPACE_BYTES), z.ctypes.data, z.ctypes.data + 8)
+            workspace = torch.empty(max(int(z[1]), 4), dtype=torch.float32, device=self.device)
+            cots = [None if g is None else g.to(torch.float32).contiguous() for g in (grad_out, grad_log_e)]
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.lib.check("hipfeat_grad_run", self.handle, x.data_ptr(), B, S, int(x.stride(0)) if B > 1 else S,
+                           None if cots[0] is None else cots[0].data_ptr(), 0 if cots[0] is None else cots[0].numel(),
+                           None if cots[1] is None else cots[1].data_ptr(), grad.data_ptr(), S, workspace.data_ptr(), workspace.numel(), int(stream))
+        return grad
+
+
+class _WaveGrad(torch.autograd.Function):
+    """``forward``: the launch the plain path makes (``run(x) -> (out, log-energies or None)``); saves only the waveform.  ``backward``:
+    ``hipfeat_grad_run`` on the cotangents, either of which may be None."""
+
+    @staticmethod
+    def forward(ctx, x, run, grad: _Grad):
+        out, log_e = run(x.detach())
+        ctx.save_for_backward(x)
+        ctx.grad = grad
+        ctx.set_materialize_grads(False)
+        if log_e is None:
+            return out
+        return out, log_e
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, grad_log_e=None):
+        if grad_out is None and grad_log_e is None:
+            return None, None, None
+        (x,) = ctx.saved_tensors
+        return ctx.grad.run(x, grad_out, grad_log_e), None, None
+
+
+def _wants_grad(layer, x) -> bool:
+    """``layer`` is differentiable and ``x`` asks for a gradient under grad mode."""
+    return bool(getattr(layer, "_differentiable", False)) and isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+
+
+def _check_grad_input(layer, x) -> Tuple[torch.Tensor, bool]:
+    """``_check_waveforms`` for an input that keeps its graph: float32, ``(B, T)`` or ``(T,)`` -> (the ``(B, T)`` batch, whether 1-D)."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"{type(layer).__name__}: expected float32 samples, got {x.dtype}")
+    squeeze = x.ndim == 1
+    if squeeze:
+        x = x.unsqueeze(0)
+    assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
+    return x, squeeze
+
+
+class _Differentiable:
+    """``differentiable_()`` of the six layers: a private flag, kept by pickling, outside ``state_dict()`` and ``repr``."""
+
+    def differentiable_(self, flag: bool = True):
+        """Make ``forward`` backpropagate to the waveform (``flag=False``: refuse inputs that require a gradient again).  Returns self."""
+        self._differentiable = bool(flag)
+        return self
+
+    @property
+    def differentiable(self) -> bool:
+        return bool(getattr(self, "_differentiable", False))
+
+
 def _check_waveforms(layer, x, method: str = "forward") -> Tuple[torch.Tensor, bool]:
     """The argument check of every layer: a float32 ``(B, T)`` or ``(T,)`` tensor that does not ask for a gradient -> (the detached
     ``(B, T)`` batch, whether it was 1-D)."""
@@ -133,7 +235,7 @@ def _check_stream_input(layer, x, context) -> Tuple[torch.Tensor, Optional[torch
     return x, context, squeeze
 
 
-class _HipLayer(torch.nn.Module):
+class _HipLayer(_Differentiable, torch.nn.Module):
     kind: int = -1
 
     def __init__(self, **opts):
@@ -152,11 +254,17 @@ class _HipLayer(torch.nn.Module):
         return SimpleNamespace(**{**dict(num_filters=0, num_ceps=0, cepstral_lifter=0, low_freq=20.0, high_freq=-400.0, norm_filters=False,
                                          torchaudio_compatible_mel_scale=True, use_fft_mag=False), **self._opts})
 
-    def _plan_for(self, device: torch.device):
-        key = (device.type, device.index)
+    def _plan_for(self, device: torch.device, no_dither: bool = False):
+        """The layer's plan on ``device``; ``no_dither``: the plan of the same layer with dither 0 (the differentiable path adds the noise
+        itself, so that the gradient passes through the addition)."""
+        no_dither = no_dither and self._opts["dither"] != 0.0
+        key = (device.type, device.index, "no-dither") if no_dither else (device.type, device.index)
         plan = self._plans.get(key)
         if plan is None:
-            plan = _E._Plan(self._plan_config(), self.kind, device)  # refuses anything but a 'cuda' device: there is no CPU fallback
+            cfg = self._plan_config()
+            if no_dither:
+                cfg.dither = 0.0
+            plan = _E._Plan(cfg, self.kind, device)  # refuses anything but a 'cuda' device: there is no CPU fallback
             self._plans[key] = plan
         return plan
 
@@ -164,7 +272,40 @@ class _HipLayer(torch.nn.Module):
         st = dict(self.__dict__)
         st["_plans"] = {}  # device handles are per process
         st["_streams"] = {}
+        st["_grads"] = {}
         return st
+
+    def _grad_for(self, device: torch.device) -> _Grad:
+        key = (device.type, device.index)
+        g = self.__dict__.setdefault("_grads", {}).get(key)
+        if g is None:
+            c, window, mel, dct, lifter, _ = _E.plan_inputs(self._plan_config(), self.kind)
+            g = self._grads[key] = _Grad(self, "hipfeat_grad_create_features", tuple(_lib.addr(a) for a in (c, window, mel, dct, lifter)), device)
+        return g
+
+    def _run_plan(self, plan, x: torch.Tensor) -> torch.Tensor:
+        """(B, T) float32 on the plan's device -> (B, num_frames, F): the one launch of ``forward``."""
+        B, T = x.shape
+        wave = x.contiguous().reshape(-1)
+        offs = np.arange(B, dtype=np.int64) * T
+        lens = np.full(B, T, dtype=np.int64)
+        try:
+            packed, frames = plan.run(wave, offs, lens, None)
+        except _lib.HipFeatError as e:
+            if e.status == _lib.ERR_TOO_SHORT:
+                raise ValueError(str(e)) from e
+            raise
+        return packed.reshape(B, int(frames[0]) if B else 0, plan.feature_dim)
+
+    def _forward_differentiable(self, x: torch.Tensor) -> torch.Tensor:
+        x, squeeze = _check_grad_input(self, x)
+        grad = self._grad_for(x.device)  # (a configuration without a gradient kernel is refused before anything runs)
+        plan = self._plan_for(x.device, no_dither=True)
+        dither = self._opts["dither"]
+        if dither != 0.0:  # layers.py:191-193
+            x = x + dither * torch.randn(x.shape, device=x.device)
+        out = _WaveGrad.apply(x, lambda w: (self._run_plan(plan, w), None), grad)
+        return out[0] if squeeze else out
 
     def _stream_for(self, device: torch.device) -> _Stream:
         key = (device.type, device.index)
@@ -194,19 +335,10 @@ class _HipLayer(torch.nn.Module):
         return (out[0] if squeeze else out), remainder
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if _wants_grad(self, x):
+            return self._forward_differentiable(x)
         x, squeeze = _check_waveforms(self, x)
-        plan = self._plan_for(x.device)
-        B, T = x.shape
-        wave = x.contiguous().reshape(-1)
-        offs = np.arange(B, dtype=np.int64) * T
-        lens = np.full(B, T, dtype=np.int64)
-        try:
-            packed, frames = plan.run(wave, offs, lens, None)
-        except _lib.HipFeatError as e:
-            if e.status == _lib.ERR_TOO_SHORT:
-                raise ValueError(str(e)) from e
-            raise
-        out = packed.reshape(B, int(frames[0]) if B else 0, plan.feature_dim)
+        out = self._run_plan(self._plan_for(x.device), x)
         return out[0] if squeeze else out
 
 
@@ -321,7 +453,7 @@ class _Stft(_E._DeviceHandle):
         return out, log_e
 
 
-class HipWav2Win(torch.nn.Module):
+class HipWav2Win(_Differentiable, torch.nn.Module):
     """Kaldi preprocessing (DC offset, pre-emphasis, window, zero padding to ``pad_length``) of overlapping frames: the reference's
     ``Wav2Win`` (layers.py:59-197).  ``forward(x)`` returns the 2-tuple ``(frames, log_energy or None)`` with ``frames`` of shape
     ``(B, num_frames, pad_length)`` and ``log_energy`` of shape ``(B, num_frames)`` when ``return_log_energy``."""
@@ -383,17 +515,40 @@ class HipWav2Win(torch.nn.Module):
             self._handles[key] = h
         return h
 
-    def _run(self, x: torch.Tensor, output: int) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
-        x, squeeze = _check_waveforms(self, x)
-        handle = self._handle_for(x.device, output)
-        if self.dither != 0.0:  # layers.py:191-193
-            x = x + self.dither * torch.randn(x.shape, device=x.device)
+    def _grad_for(self, device: torch.device, output: int, layer) -> _Grad:
+        key = (device.type, device.index, output, "grad")
+        g = self._handles.get(key)
+        if g is None:
+            cfg, window, _, _ = _stft_inputs(self, output)
+            g = self._handles[key] = _Grad(layer, "hipfeat_grad_create_stft", (_lib.addr(cfg), _lib.addr(window)), device)
+        return g
+
+    @staticmethod
+    def _launch(handle: _Stft, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         try:
-            out, log_e = handle.run(x)
+            return handle.run(x)
         except _lib.HipFeatError as e:
             if e.status == _lib.ERR_TOO_SHORT:
                 raise ValueError(str(e)) from e
             raise
+
+    def _run(self, x: torch.Tensor, output: int, layer=None) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
+        """``layer``: the layer whose call this is (``HipWav2FFT`` runs its ``wav2win``), whose flag decides and whose name refusals carry."""
+        layer = self if layer is None else layer
+        if _wants_grad(layer, x):
+            x, squeeze = _check_grad_input(layer, x)
+            grad = self._grad_for(x.device, output, layer)  # (a configuration without a gradient kernel is refused before anything runs)
+            handle = self._handle_for(x.device, output)
+            if self.dither != 0.0:  # layers.py:191-193
+                x = x + self.dither * torch.randn(x.shape, device=x.device)
+            res = _WaveGrad.apply(x, lambda w: self._launch(handle, w), grad)
+            out, log_e = res if isinstance(res, tuple) else (res, None)
+            return out, log_e, squeeze
+        x, squeeze = _check_waveforms(layer, x)
+        handle = self._handle_for(x.device, output)
+        if self.dither != 0.0:  # layers.py:191-193
+            x = x + self.dither * torch.randn(x.shape, device=x.device)
+        out, log_e = self._launch(handle, x)
         return out, log_e, squeeze
 
     def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -435,7 +590,7 @@ class HipWav2Win(torch.nn.Module):
         return (out, log_e), remainder
 
 
-class HipWav2FFT(torch.nn.Module):
+class HipWav2FFT(_Differentiable, torch.nn.Module):
     """The complex STFT of the Kaldi-preprocessed frames: the reference's ``Wav2FFT`` (layers.py:227-324).  ``forward(x)`` returns a
     ``complex64`` tensor of shape ``(B, num_frames, fft_length / 2 + 1)``; ``use_energy`` (default True) puts the log-energy in bin 0."""
 
@@ -483,8 +638,7 @@ class HipWav2FFT(torch.nn.Module):
         return spec[0] if squeeze else spec
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _check_waveforms(self, x)  # (refusals name this layer)
-        out, _, squeeze = self.wav2win._run(x, _lib.STFT_SPECTRUM)
+        out, _, squeeze = self.wav2win._run(x, _lib.STFT_SPECTRUM, self)  # (refusals name this layer)
         return self._complex(out, squeeze)
 
     def online_inference(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
