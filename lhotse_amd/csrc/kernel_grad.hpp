@@ -58,7 +58,9 @@ constexpr int grad_buf_floats(int N1) { return 288 * N1 + 16; }  // per wave: th
 // multiplied by rms(X) / |X_k| -- 65 x for the bins under the first mel filters of a pre-emphasised noise frame.  In float32 the packed
 // half-size transform loses to the reference's real FFT there: bin k is the difference E_k + W^k O_k of two terms as large as the bins
 // around fft / 2 - k, and measured 3.4 x the reference's own float32 error on such a row.  The recomputed spectrum therefore
-// runs the same three passes and the same split step in float64 (W_2H^k from a float64 table); everything after it is float32.
+// runs the same three passes and the same split step in float64 (W_2H^k from a float64 table), on a windowed frame that is float64 from
+// the samples on (the float64 frame mean, the pre-emphasis and the window, rounded once): a frame rounded to float32 first puts
+// eps rms(X) onto every bin, which is as much as a float32 FFT does.  Everything after the spectrum is float32.
 struct cd {
   double x, y;
 };
@@ -205,6 +207,8 @@ __device__ __forceinline__ void grad_frames_body(const GradParams& p) {
 
     // ---- the forward's front end (kernel_stft.hpp): samples, float64 mean, d = x - mean -------------------------------------------
     v2 d[N1];
+    float mean = 0.f;
+    double mean64 = 0.0;
     {
       double s = 0.0;
       const bool inside = src.inside(j0, (N + 1) & ~1);
@@ -224,31 +228,45 @@ __device__ __forceinline__ void grad_frames_body(const GradParams& p) {
         d[q] = v;
         s += (double)v.x + (double)v.y;
       }
-      float mean = 0.f;
-      if (p.flags & F_REMOVE_DC) mean = (float)(wave_sum_f64(s) / (double)N);
-#pragma unroll
-      for (int q = 0; q < N1; ++q) {
-        const int m0 = 2 * (lane + 64 * q);
-        d[q].x = m0 < N ? d[q].x - mean : 0.f;
-        d[q].y = m0 + 1 < N ? d[q].y - mean : 0.f;
+      if (p.flags & F_REMOVE_DC) {
+        mean64 = wave_sum_f64(s) / (double)N;
+        mean = (float)mean64;
       }
     }
-    // y[m] = (d[m] - c d[max(m-1, 0)]) w[m]
+    // y[m] = (d[m] - c d[max(m-1, 0)]) w[m], d = x - mean.  The float32 y is the forward's and feeds the two log-energies; the feature
+    // kinds also take it in float64 from the samples themselves (yd: the float64 mean, one rounding at the end), for the float64 spectrum
+    // below: the rounding of a float32 y alone moves a bin at 6e-5 of the frame's rms by 1e-3 of itself (sweep case 87).
     v2 y[N1];
+    cd yd[N1];
     float sum_d = 0.f, sum_w = 0.f;
+    const bool feature = mode <= GRAD_MFCC;
+    const double c64 = (double)p.preemph;
+    float last_y = 0.f;  // the sample in front of this register's first one, in lane 63
 #pragma unroll
     for (int q = 0; q < N1; ++q) {
       const int m0 = 2 * (lane + 64 * q);
-      const float offer = (q > 0 && lane == 63) ? d[q > 0 ? q - 1 : 0].y : d[q].y;
-      float dm = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * ((lane - 1) & 63), __builtin_bit_cast(int, offer)));
-      if (q == 0 && lane == 0) dm = d[q].x;
+      const v2 x = d[q];  // the samples; d[q] becomes x - mean below
+      const float offer = (q > 0 && lane == 63) ? last_y : x.y;
+      float xm = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * ((lane - 1) & 63), __builtin_bit_cast(int, offer)));
+      if (q == 0 && lane == 0) xm = x.x;  // the replicate pad
+      last_y = x.y;
+      const float dm = xm - mean;
+      d[q].x = m0 < N ? x.x - mean : 0.f;
+      d[q].y = m0 + 1 < N ? x.y - mean : 0.f;
       v2 v = {0.f, 0.f};
+      cd vd = {0.0, 0.0};
       if (m0 < N) {
         const v2 wn = *reinterpret_cast<const v2*>(winl + m0);
         v.x = (d[q].x - p.preemph * dm) * wn.x;
         if (m0 + 1 < N) v.y = (d[q].y - p.preemph * d[q].x) * wn.y;
+        if (feature) {
+          const double dx = (double)x.x - mean64;
+          vd.x = (dx - c64 * ((double)xm - mean64)) * (double)wn.x;
+          if (m0 + 1 < N) vd.y = (((double)x.y - mean64) - c64 * dx) * (double)wn.y;
+        }
       }
       y[q] = v;
+      yd[q] = vd;
       sum_d = fmaf(d[q].x, d[q].x, fmaf(d[q].y, d[q].y, sum_d));
       sum_w = fmaf(v.x, v.x, fmaf(v.y, v.y, sum_w));
     }
@@ -293,12 +311,7 @@ __device__ __forceinline__ void grad_frames_body(const GradParams& p) {
       } else {
         // ---- the forward spectrum: X[k] and X[H - k] per lane, P = |X|^2 or |X| ------------------------------------------------
         cd* zd = reinterpret_cast<cd*>(buf);
-        {
-          cd yd[N1];
-#pragma unroll
-          for (int q = 0; q < N1; ++q) yd[q] = cd{(double)y[q].x, (double)y[q].y};
-          fft3_frame_f64<N1>(zd, tw64, lane, yd);
-        }
+        fft3_frame_f64<N1>(zd, tw64, lane, yd);
         v2 xlo[N1 / 2 + 1], xhi[N1 / 2 + 1];
         float plo[N1 / 2 + 1], phi[N1 / 2 + 1];
 #pragma unroll

@@ -79,6 +79,17 @@ def _log_energy(v: torch.Tensor, floor: float) -> torch.Tensor:
     return e
 
 
+def mel_filters(cls: str, kw: dict) -> np.ndarray:
+    """(fft / 2 + 1, num_filters) float32: the Kaldi filters, or with ``torchaudio_compatible_mel_scale=False`` the HTK ones (with or
+    without ``norm_filters``); tests/test_constants.py holds both matrices to the reference's."""
+    rate, fft = kw.get("sampling_rate", 16000), sizes(kw, cls)[2]
+    M = kw.get("num_filters", 80 if cls == "Wav2LogFilterBank" else 23)
+    low, high = kw.get("low_freq", 20.0), kw.get("high_freq", -400.0)
+    if kw.get("torchaudio_compatible_mel_scale", True):
+        return constants.make_kaldi_mel(M, fft, rate, low, high)
+    return constants.make_htk_mel(M, fft, rate, low, high, kw.get("norm_filters", False))
+
+
 def forward(cls: str, kw: dict, x: torch.Tensor):
     """``x``: (B, S) float32 or float64 (it may require a gradient) -> what the layer returns, in that dtype (Wav2FFT: its complex type;
     Wav2Win: the tuple (frames, log-energies or None))."""
@@ -113,9 +124,8 @@ def forward(cls: str, kw: dict, x: torch.Tensor):
         if energy:
             P = torch.cat([log_e.unsqueeze(-1), P[:, :, 1:]], dim=-1)
         return P
-    rate = kw.get("sampling_rate", 16000)
     M = kw.get("num_filters", 80 if cls == "Wav2LogFilterBank" else 23)
-    fb = constants.make_kaldi_mel(M, fft, rate, kw.get("low_freq", 20.0), kw.get("high_freq", -400.0))
+    fb = mel_filters(cls, kw)
     # (K, M) as the transposed view of an (M, K) matrix, which is how the reference holds it (layers.py:553): the matrix product then
     # sums in the reference's order
     fb = torch.from_numpy(np.ascontiguousarray(fb.T)).to(device=x.device, dtype=dt).T

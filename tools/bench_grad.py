@@ -11,8 +11,8 @@ Shapes, 16 kHz, 25 / 10 ms, povey, pre-emphasis 0.97, DC removal, 80 filters (th
 Legs alternate (ours, torch, ours with a second workspace budget, ...): every round times each leg once, by HIP events around forward +
 backward on the current stream, allocations included; the figures are the medians (min, max) of --steps rounds after --warmup untimed
 ones.  ``workspace_bytes`` is what the frames launch writes and the gather reads once more: rows x T x Nr x 4; ``pieces`` the launch
-pairs.  Before anything is timed the device gradient of the first rows is held to the torch leg's in float64 (the bar of
-tests/_grad_ref.py): faster and different is not faster.  No time is a pass / fail bar.  Prints one JSON line and writes it to --out.
+pairs.  Before anything is timed the device gradient of two rows under a fixed cotangent is held to the restatement's float64 autograd (the bar
+of tests/_grad_ref.py): faster and different is not faster.  No time is a pass / fail bar.  Prints one JSON line and writes it to --out.
 
     python tools/bench_grad.py [--steps 30] [--warmup 5] [--second-budget-mib 16] [--out profiles/grad_bench.json]"""
 import argparse
@@ -64,13 +64,15 @@ def main():
         ((GR.forward("Wav2LogFilterBank", {}, x) - target) ** 2).mean().backward()
         return x.grad
 
-    # parity first: the first two rows of the one-second shape, against the torch leg in float64
-    x0 = torch.rand((2, 16000), device="cuda", generator=gen) - 0.5
-    with torch.no_grad():  # (a random residual: a constant one makes sum log mel nearly scale-invariant, and its gradient all cancellation)
-        y0 = layer(x0)
-        t0 = y0 + torch.randn(y0.shape, device="cuda", generator=gen)
-    g64 = theirs(x0.double(), t0.double()).cpu().numpy()
-    worst = GR.hold("bench gradient", ours(x0, t0, default_budget).cpu().numpy(), theirs(x0, t0).cpu().numpy(), g64)
+    # parity first: two rows of the one-second shape under one fixed random cotangent (the residual of the timed loss), against the
+    # restatement's autograd in float32 and float64, as the tests do.  (Through the loss itself the cotangent 2 (y - t) / n carries the
+    # float32 error of whichever forward computed y, which the conditioning of 1 / mel then multiplies: that compares forwards.)
+    x0 = (torch.rand((2, 16000), device="cuda", generator=gen) - 0.5).cpu().numpy()
+    with torch.no_grad():
+        shape0 = layer(torch.from_numpy(x0).cuda()).shape
+    c0 = [(2.0 / int(np.prod(shape0)) * torch.randn(shape0, device="cuda", generator=gen)).cpu().numpy()]
+    worst = GR.hold("bench gradient", GR.device_gradient(layer, x0, c0), GR.gradient("Wav2LogFilterBank", {}, x0, c0, torch.float32),
+                    GR.gradient("Wav2LogFilterBank", {}, x0, c0, torch.float64))
     res["parity"] = {"worst_ratio_to_torch_float32": worst}
 
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
