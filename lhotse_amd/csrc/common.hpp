@@ -88,6 +88,18 @@ __device__ __forceinline__ float load_sample_center(const float* __restrict__ w,
   return (j >= 0 && j < S) ? w[j] : 0.0f;
 }
 
+// Ordering of one wave's LDS traffic where lanes read what other lanes of the SAME wave wrote (no workgroup barrier: the wave's LDS
+// queue is in order).  sync: the writes before it are visible to the reads after it.  release: the reads before it are done with the
+// locations that the writes after it overwrite.
+__device__ __forceinline__ void wave_lds_release() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ void wave_lds_sync() {
+  wave_lds_release();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Ragged batches: the host puts a workgroup -> cut map (int32 per workgroup) behind the descriptor table and says so with
 // uniform_bpc = -1: ONE dependent load instead of log2(cuts) of them in front of every workgroup (13 for a LibriSpeech-like batch of
 // 8000 cuts -- a few microseconds of a workgroup that lives for ~40).
@@ -117,6 +129,19 @@ __device__ __forceinline__ int find_cut(const CutDesc* __restrict__ cuts, int nu
     if (cuts[mid].first_block <= blk) lo = mid; else hi = mid - 1;
   }
   return lo;
+}
+
+// Workgroup `blk` -> the cut it works on and its index among that cut's workgroups.  P: any Params struct with cuts, num_cuts and
+// uniform_bpc (> 0: so many workgroups per cut; < 0: the map behind the table; 0: search).
+template <class P>
+__device__ __forceinline__ void block_owner(const P& p, int blk, int& cut, int& fb) {
+  if (p.uniform_bpc > 0) {
+    cut = blk / p.uniform_bpc;
+    fb = blk - cut * p.uniform_bpc;
+  } else {
+    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
+    fb = blk - p.cuts[cut].first_block;
+  }
 }
 
 }  // namespace hipfeat

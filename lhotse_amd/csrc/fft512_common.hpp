@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "fft_common.hpp"
 #include "plan_tables.hpp"  // WaveWork
+#include "wave_auto.hpp"    // stage_span_tile, HFC_SEP, g_phase_buf
 
 namespace hipfeat {
 
@@ -18,6 +19,8 @@ constexpr int kPRowStride = 260;                      // dwords per power row (=
 constexpr int kMaxGroups0 = 20;                       // 8-bin MFMA groups of a wave's first / second mel tile
 constexpr int kMaxGroups1 = 4;
 constexpr int kMelARegs = 2 * (kMaxGroups0 + kMaxGroups1);
+constexpr int kBMelVec = kMelARegs / 4;               // 16-byte loads of filter weights per lane per tile
+constexpr int kMaxDctGroups = 10;
 
 struct Fft512Params {
   const float* wave;
@@ -39,7 +42,6 @@ struct Fft512Params {
 
 // Optional phase timers (experiment builds only): per-phase shader-clock totals over all waves.
 #ifdef HIPFEAT_PHASE_TIMERS
-__device__ unsigned long long* g_phase_buf;  // [grid * 4 waves][8], written once per wave (no atomics)
 #define HF_T(i) const unsigned long long t##i = __builtin_readcyclecounter()
 #define HF_ACC(slot, a, b) hf_acc[slot] += (unsigned long long)((b) - (a))
 #define HF_U(i)

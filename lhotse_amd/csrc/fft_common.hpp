@@ -36,6 +36,20 @@ __device__ __forceinline__ float row16_sum(float v) {  // every lane of the row 
 // lane l <- lane (16 - l) % 16 of the same row
 __device__ __forceinline__ float row16_negate_index(float v) { return dpp_mov<DPP_ROW_ROR1>(dpp_mov<DPP_ROW_MIRROR>(v)); }
 
+constexpr int DPP_ROW_ROR4 = 0x124, DPP_ROW_ROR8 = 0x128, DPP_ROW_SHR2 = 0x112;
+// two frames interleaved in a 16-lane row (lane = 2 q + f; the fft256 kernels): total over the 8 lanes of the same parity, in every one of them
+__device__ __forceinline__ float row8i_sum(float v) {
+  v += dpp_mov<DPP_QUAD(2, 3, 0, 1)>(v);  // q ^ 1
+  v += dpp_mov<DPP_ROW_ROR4>(v);          // q - 2
+  v += dpp_mov<DPP_ROW_ROR8>(v);          // q - 4
+  return v;
+}
+// lane (q, f) <- lane ((8 - q) % 8, f) of `v`; the q = 0 lanes (no source in the last move) keep `keep`
+__device__ __forceinline__ float row8i_negate_index(float keep, float v) {
+  const float m = dpp_mov<DPP_QUAD(1, 0, 3, 2)>(dpp_mov<DPP_ROW_MIRROR>(v));  // q -> 7 - q, same frame
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, keep), __builtin_bit_cast(int, m), DPP_ROW_SHR2, 0xF, 0xF, false));
+}
+
 // ---- packed complex arithmetic ---------------------------------------------------------------
 // hipcc folds whole-register swaps / broadcasts of packed f32 operands into op_sel modifiers but not
 // a sign flip of ONE half, so conjugation and multiplication by +-i are written as a packed multiply

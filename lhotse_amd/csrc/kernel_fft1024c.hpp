@@ -18,7 +18,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
-#include "kernel_fft512c.hpp"  // HFC_SEP, mul24, phase-timer macros
+#include "wave_auto.hpp"
 
 namespace hipfeat {
 
@@ -48,14 +48,6 @@ struct Fft1024cParams {
   int32_t xs_floats;  // floats of one wave's sample-span buffer (multiple of 4)
   int32_t nsets, steps[kWMaxSets], step0[kWMaxSets];  // accumulator sets: MFMA steps (multiples of 4) and first step in the weight table
 };
-
-// r = m ? a : b per lane with the mask in an SGPR pair (VOP3 encoding: the VOP2 / VCC form of v_cndmask issues ~5x slower on gfx950)
-__device__ __forceinline__ float sel64(unsigned long long m, float a, float b) {
-  float r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-  return r;
-}
-__device__ __forceinline__ v2 sel64(unsigned long long m, v2 a, v2 b) { return v2{sel64(m, a.x, b.x), sel64(m, a.y, b.y)}; }
 
 // S0 / S1 / S2 != 0: the (padded) step counts of a three-set schedule as compile-time constants -- the 80-filter Kaldi defaults at 24 / 32 kHz
 // (24, 16, 8) and 22.05 kHz (24, 24, 8).  Without the "does this chunk exist" tests the mel phase needs 100 VGPRs, ~350 scalar instructions
@@ -89,6 +81,7 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
 
   const int blk = blockIdx.x;
   int cut, fb;
+  // (its own copy of common.hpp::block_owner: with the helper the PLAIN instance of a phase-timer build swaps the two stores of a bin pair)
   if (p.uniform_bpc > 0) {
     cut = blk / p.uniform_bpc;
     fb = blk - cut * p.uniform_bpc;
@@ -109,7 +102,8 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
   constexpr int kGeoN = NROWS == 26 ? 800 : (S1 == 24 ? 551 : 600), kGeoShift = NROWS == 26 ? 320 : (S1 == 24 ? 220 : 240);
   const int N = kGeo ? kGeoN : p.N, shift = kGeo ? kGeoShift : p.shift;
   const int npad_left = kGeo ? (kGeoN - kGeoShift) / 2 : p.npad_left;
-  const int xs_floats = kGeo ? ((3 * kGeoShift + 32 * NROWS + 3) & ~3) : p.xs_floats;
+  constexpr int kGeoXs = kGeo ? ((3 * kGeoShift + 32 * NROWS + 3) & ~3) : 0;
+  const int xs_floats = kGeo ? kGeoXs : p.xs_floats;
   const int M = kGeo ? 80 : p.M;
 
   for (int i = tid; i < p.shared_floats; i += 64 * kWv) smem[i] = p.shared_consts[i];
@@ -129,34 +123,19 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
   const float c = p.preemph;
 
   auto stage_span = [&](int f0, unsigned lane4) {
-    const int64_t j0 = (int64_t)f0 * shift - npad_left;
-    if (j0 >= 0 && j0 + xs_floats <= cd.num_samples) {
-      const char* src = reinterpret_cast<const char*>(w + j0);  // uniform
-      const int nfull = xs_floats >> 8;
-#pragma unroll
-      for (int ch = 0; ch < 10; ++ch) {
-        if (ch < nfull)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)ch * 1024u + 4u * lane4)),
-                                           (__attribute__((address_space(3))) void*)(xs + ch * 256), 16, 0, 0);
-      }
-      if ((unsigned)nfull * 256u + lane4 < (unsigned)xs_floats)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)nfull * 1024u + 4u * lane4)),
-                                         (__attribute__((address_space(3))) void*)(xs + nfull * 256), 16, 0, 0);
-    } else {
+    stage_span_wave<10, kGeoXs>(w, (int64_t)f0 * shift - npad_left, xs, xs_floats, cd.num_samples, lane4, [&](int64_t j0) {
       if (!kKaldiOnly && (p.flags & F_CENTER))  // torch.stft / librosa "reflect" padding (the edge sample is not repeated)
-        for (int i = (int)(lane4 >> 2); i < xs_floats; i += 64) xs[i] = load_sample_center(w, j0 + i, cd.num_samples);
+        span_fill(xs, xs_floats, lane4, j0, [&](int64_t j) { return load_sample_center(w, j, cd.num_samples); });
       else
-        for (int i = (int)(lane4 >> 2); i < xs_floats; i += 64) xs[i] = load_sample(w, j0 + i, cd.num_samples, cd.padded_len);
-    }
+        span_fill(xs, xs_floats, lane4, j0, [&](int64_t j) { return load_sample(w, j, cd.num_samples, cd.padded_len); });
+    });
   };
 
   const int first_frame = fb * p.frames_per_block + 4 * wv;  // the waves take the frame quads round-robin
   __syncthreads();  // the constant tables are in place (the only workgroup barrier of the kernel)
   if (kPrefetch && first_frame < cd.num_frames) stage_span(first_frame, (unsigned)lane * 4u);
 
-#ifdef HIPFEAT_PHASE_TIMERS
-  unsigned long long hfc_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hfc_last = __builtin_readcyclecounter();
-#endif
+  HFC_TIMERS();
   for (int r = 0; r < p.rounds; ++r) {
     const int f0 = first_frame + 4 * kWv * r;
     if (f0 >= cd.num_frames) break;
@@ -268,9 +247,7 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
       for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) *reinterpret_cast<v2*>(exf + rr * kWExRowStride + 2 * q) = a[16 * h + rr];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const float* src = exf + mul24(h == 0 ? q : ((16 - q) & 15), kWExRowStride);
 #pragma unroll
         for (int n2 = 0; n2 < 16; ++n2) {
@@ -278,8 +255,7 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
           else b1[n2] = *reinterpret_cast<const v2*>(src + 2 * n2);
           HFC_SEP();
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_release();
       }
       HFC_T(3);  // exchange
       fft16(b0, Za);
@@ -345,9 +321,7 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
     }
     HFC_T(4);  // pass 2, split step, power rows
     // the wave's four power rows are complete once its own (in-order) LDS queue has drained
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // the next round's span (requested at the start of this round) must have landed before this round's stores join the
     // same in-order vmcnt queue: waiting here instead of at the top of the next round never waits for the stores
@@ -398,16 +372,9 @@ __global__ __launch_bounds__(64 * (S0 != 0 ? kWWavesFixed : kWWaves), (S0 != 0 ?
       }
     }
     HFC_T(6);  // mel phase: operand reads, MFMAs, reduction, log, stores
-#ifdef HIPFEAT_PHASE_TIMERS
-    hfc_acc[7] += 1;
-#endif
+    HFC_ROUND();
   }
-#ifdef HIPFEAT_PHASE_TIMERS
-  if (lane == 0 && g_phase_buf) {
-    unsigned long long* o = g_phase_buf + ((size_t)blockIdx.x * kWv + wv) * 8;
-    for (int i = 0; i < 8; ++i) o[i] = hfc_acc[i];
-  }
-#endif
+  HFC_DUMP(lane, (size_t)blockIdx.x * kWv + wv);
 }
 
 }  // namespace hipfeat

@@ -20,7 +20,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
-#include "kernel_fft1024c.hpp"  // sel64; HFC_SEP, mul24, phase-timer macros via kernel_fft512c.hpp
+#include "wave_auto.hpp"
 
 namespace hipfeat {
 
@@ -94,13 +94,7 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
 
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const float* __restrict__ w = p.wave + cd.wave_off;
   // round 5, experiment 2: the fixed-schedule instances are the 80-filter Kaldi defaults at 44.1 kHz (ODD: 1102-sample frames, hop 441)
@@ -114,7 +108,8 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
 #endif
   const int N = kGeo ? (ODD ? 1102 : 1200) : p.N, shift = kGeo ? (ODD ? 441 : 480) : p.shift;
   const int npad_left = kGeo ? (ODD ? 330 : 360) : p.npad_left;
-  const int xs_floats = kGeo ? (((ODD ? 441 : 480) + 64 * NROWS + 3) & ~3) : p.xs_floats;
+  constexpr int kGeoXs = kGeo ? (((ODD ? 441 : 480) + 64 * NROWS + 3) & ~3) : 0;
+  const int xs_floats = kGeo ? kGeoXs : p.xs_floats;
   const int nwaves = kGeo ? (W12 ? kXWavesFixed : kXMaxWaves) : p.waves;
   const int M = kGeo ? 80 : p.M;
 
@@ -134,34 +129,19 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
   const float c = p.preemph;
 
   auto stage_span = [&](int f0, unsigned lane4) {
-    const int64_t j0 = (int64_t)f0 * shift - npad_left;
-    if (j0 >= 0 && j0 + xs_floats <= cd.num_samples) {
-      const char* src = reinterpret_cast<const char*>(w + j0);  // uniform
-      const int nfull = xs_floats >> 8;
-#pragma unroll
-      for (int ch = 0; ch < 10; ++ch) {
-        if (ch < nfull)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)ch * 1024u + 4u * lane4)),
-                                           (__attribute__((address_space(3))) void*)(xs + ch * 256), 16, 0, 0);
-      }
-      if ((unsigned)nfull * 256u + lane4 < (unsigned)xs_floats)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)nfull * 1024u + 4u * lane4)),
-                                         (__attribute__((address_space(3))) void*)(xs + nfull * 256), 16, 0, 0);
-    } else {
+    stage_span_wave<10, kGeoXs>(w, (int64_t)f0 * shift - npad_left, xs, xs_floats, cd.num_samples, lane4, [&](int64_t j0) {
       if (!kFixed && (p.flags & F_CENTER))  // torch.stft / librosa "reflect" padding (the edge sample is not repeated)
-        for (int i = (int)(lane4 >> 2); i < xs_floats; i += 64) xs[i] = load_sample_center(w, j0 + i, cd.num_samples);
+        span_fill(xs, xs_floats, lane4, j0, [&](int64_t j) { return load_sample_center(w, j, cd.num_samples); });
       else
-        for (int i = (int)(lane4 >> 2); i < xs_floats; i += 64) xs[i] = load_sample(w, j0 + i, cd.num_samples, cd.padded_len);
-    }
+        span_fill(xs, xs_floats, lane4, j0, [&](int64_t j) { return load_sample(w, j, cd.num_samples, cd.padded_len); });
+    });
   };
 
   const int first_frame = fb * p.frames_per_block + 2 * wv;  // the waves take the frame pairs round-robin
   __syncthreads();  // the constant tables are in place (the only workgroup barrier of the kernel)
   if (kPrefetch && first_frame < cd.num_frames) stage_span(first_frame, (unsigned)lane * 4u);
 
-#ifdef HIPFEAT_PHASE_TIMERS
-  unsigned long long hfc_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hfc_last = __builtin_readcyclecounter();
-#endif
+  HFC_TIMERS();
   for (int r = 0; r < p.rounds; ++r) {
     const int f0 = first_frame + 2 * nwaves * r;
     if (f0 >= cd.num_frames) break;
@@ -293,9 +273,7 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
       {
 #pragma unroll
         for (int rr = 0; rr < kXExRows; ++rr) *reinterpret_cast<v2*>(exf + rr * kXExRowStride + 2 * q) = a[rr];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const bool odd = q >= 17;
         const float* src = exf + mul24(odd ? 32 - q : q, kXExRowStride);
         v2 x32[32];
@@ -304,8 +282,7 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
           x32[n2] = *reinterpret_cast<const v2*>(src + 2 * n2);
           HFC_SEP();
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_release();
         const float sgn = odd ? -1.0f : 1.0f;
         half_fft32(x32, v2{sgn, sgn}, ctw32 + (odd ? 16 : 0), R0);
       }
@@ -314,9 +291,7 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) *reinterpret_cast<v2*>(exf + rr * kXExRowStride + 2 * q) = a[16 + rr];
         *reinterpret_cast<v2*>(exf + 16 * kXExRowStride + 2 * q) = a[0];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const bool odd = q <= 16;
         const int slot = q == 0 ? 16 : (q <= 16 ? 16 - q : q - 16);
         const float* src = exf + mul24(slot, kXExRowStride);
@@ -326,8 +301,7 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
           x32[n2] = *reinterpret_cast<const v2*>(src + 2 * n2);
           HFC_SEP();
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_release();
         const float sgn = odd ? -1.0f : 1.0f;
         half_fft32(x32, v2{sgn, sgn}, ctw32 + (odd ? 16 : 0), R1);
       }
@@ -395,9 +369,7 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
     }
     HFC_T(4);  // split step, power rows
     // the wave's two power rows are complete once its own (in-order) LDS queue has drained
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // the next round's span (requested at the start of this round) must have landed before this round's stores join the same
     // in-order vmcnt queue: waiting here instead of at the top of the next round never waits for the stores
@@ -454,16 +426,9 @@ __global__ __launch_bounds__(64 * (W12 ? kXWavesFixed : kXMaxWaves), (W12 ? 3 : 
       }
     }
     HFC_T(6);  // mel phase: operand reads, MFMAs, reduction, log, stores
-#ifdef HIPFEAT_PHASE_TIMERS
-    hfc_acc[7] += 1;
-#endif
+    HFC_ROUND();
   }
-#ifdef HIPFEAT_PHASE_TIMERS
-  if (lane == 0 && g_phase_buf) {
-    unsigned long long* o = g_phase_buf + ((size_t)blockIdx.x * kXMaxWaves + wv) * 8;
-    for (int i = 0; i < 8; ++i) o[i] = hfc_acc[i];
-  }
-#endif
+  HFC_DUMP(lane, (size_t)blockIdx.x * kXMaxWaves + wv);
 }
 
 }  // namespace hipfeat

@@ -16,8 +16,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
-#include "fft512_common.hpp"   // Fft512Params, WaveWork, kMaxGroups*, kMelARegs
-#include "kernel_fft512b.hpp"  // kBMelVec, kMaxDctGroups
+#include "fft512_common.hpp"  // Fft512Params, WaveWork, kMaxGroups*, kBMelVec, kMaxDctGroups
 
 namespace hipfeat {
 
@@ -26,20 +25,6 @@ constexpr int k256ExRowStride = 18;                          // dwords per excha
 constexpr int k256ExFrameStride = 8 * k256ExRowStride;       // 144 (== 16 mod 64): 8 rows per half
 constexpr int k256PRowStride = 132;                          // dwords per power row: 129 bins + pad (== 4 mod 64)
 constexpr int k256WaveRegion = 8 * k256ExFrameStride;        // 1152 dwords per wave (>= 8 * 132 power rows); 32.6 KB per workgroup at 8 kHz -> 5 per CU
-
-constexpr int DPP_ROW_ROR4 = 0x124, DPP_ROW_ROR8 = 0x128, DPP_ROW_SHR2 = 0x112;
-// frames interleaved in a 16-lane row (lane = 2 q + f): total over the 8 lanes of the same parity, in every one of them
-__device__ __forceinline__ float row8i_sum(float v) {
-  v += dpp_mov<DPP_QUAD(2, 3, 0, 1)>(v);  // q ^ 1
-  v += dpp_mov<DPP_ROW_ROR4>(v);          // q - 2
-  v += dpp_mov<DPP_ROW_ROR8>(v);          // q - 4
-  return v;
-}
-// lane (q, f) <- lane ((8 - q) % 8, f) of `v`; the q = 0 lanes (no source in the last move) keep `keep`
-__device__ __forceinline__ float row8i_negate_index(float keep, float v) {
-  const float m = dpp_mov<DPP_QUAD(1, 0, 3, 2)>(dpp_mov<DPP_ROW_MIRROR>(v));  // q -> 7 - q, same frame
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, keep), __builtin_bit_cast(int, m), DPP_ROW_SHR2, 0xF, 0xF, false));
-}
 
 // OUT = 0 fbank, 1 MFCC, 2 (log-)spectrogram -- see kernel_fft512b.hpp
 template <int NROWS, int OUT>
@@ -61,13 +46,7 @@ __global__ __launch_bounds__(256, (NROWS > 13 ? 4 : 5)) void fft256_kernel(const
 
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const float* __restrict__ w = p.wave + cd.wave_off;
   const int N = p.N, shift = p.shift;
@@ -85,15 +64,7 @@ __global__ __launch_bounds__(256, (NROWS > 13 ? 4 : 5)) void fft256_kernel(const
   const char* __restrict__ mel_base = reinterpret_cast<const char*>(p.mel_a) + (size_t)wv * kBMelVec * 64 * 16;
 
   auto stage_span = [&](int f0, unsigned lane16) {
-    const int64_t j0 = (int64_t)f0 * shift - p.npad_left;
-    if (j0 >= 0 && j0 + (int64_t)nchunks * 256 <= cd.num_samples) {
-      const char* src = reinterpret_cast<const char*>(w + j0);  // uniform
-      for (int ch = wv; ch < nchunks; ch += 4)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)ch * 1024u + lane16)),
-                                         (__attribute__((address_space(3))) void*)(xs + ch * 256), 16, 0, 0);
-    } else {
-      for (int i = tid; i < p.xs_floats; i += 256) xs[i] = load_sample(w, j0 + i, cd.num_samples, cd.padded_len);  // the whole buffer: rows past N are read (and masked or met by a zero window) too
-    }
+    stage_span_tile(w, (int64_t)f0 * shift - p.npad_left, xs, p.xs_floats, nchunks, cd, wv, tid, lane16);
   };
 
   const int first_tile = fb * p.tiles_per_block;
@@ -167,13 +138,10 @@ __global__ __launch_bounds__(256, (NROWS > 13 ? 4 : 5)) void fft256_kernel(const
       for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) *reinterpret_cast<v2*>(exf + r * k256ExRowStride + 2 * q) = a[8 * h + r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int n2 = 0; n2 < 8; ++n2) b[8 * h + n2] = *reinterpret_cast<const v2*>(exf + q * k256ExRowStride + 2 * n2);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_release();
       }
       v2 Z1[8], Z2[8];  // rows k1 = q and q + 8: bins q + 16 k2 and q + 8 + 16 k2
       fft8(b, Z1);

@@ -13,12 +13,14 @@
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
-#include "kernel_fft256.hpp"   // row8i_sum, row8i_negate_index, exchange strides
-#include "kernel_fft512c.hpp"  // Fft512cParams, HFC_SEP, mul24
+#include "kernel_fft512c.hpp"  // Fft512cParams
+#include "wave_auto.hpp"
 
 namespace hipfeat {
 
-constexpr int kDPRowStride = 144;                 // dwords per power row: 129 bins + pad (== 16 mod 64, as mel4_schedule.hpp assumes)
+constexpr int kDExRowStride = 18;                 // dwords per exchange row (8 complex + 2 pad)
+constexpr int kDExFrameStride = 8 * kDExRowStride;  // 144 (== 16 mod 64): 8 rows per half, as in kernel_fft256.hpp
+constexpr int kDPRowStride = 144;                // dwords per power row: 129 bins + pad (== 16 mod 64, as mel4_schedule.hpp assumes)
 constexpr int kDRegion = 8 * kDPRowStride;        // 1152 dwords per wave = 8 exchange blocks of 8 x 18 = 8 power rows
 constexpr int kDSets = 2, kDSteps = 8;            // accumulator sets x MFMA steps per set
 constexpr int kDWaves = 8;                        // waves per workgroup
@@ -40,13 +42,7 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
 
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const float* __restrict__ w = p.wave + cd.wave_off;
   const int N = p.N, shift = p.shift;
@@ -59,22 +55,9 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
   const float c = p.preemph;
 
   auto stage_span = [&](int f0, unsigned lane4) {
-    const int64_t j0 = (int64_t)f0 * shift - p.npad_left;
-    if (j0 >= 0 && j0 + p.xs_floats <= cd.num_samples) {
-      const char* src = reinterpret_cast<const char*>(w + j0);  // uniform
-      const int nfull = p.xs_floats >> 8;
-#pragma unroll
-      for (int ch = 0; ch < 6; ++ch) {
-        if (ch < nfull)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)ch * 1024u + 4u * lane4)),
-                                           (__attribute__((address_space(3))) void*)(xs + ch * 256), 16, 0, 0);
-      }
-      if ((unsigned)nfull * 256u + lane4 < (unsigned)p.xs_floats)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)nfull * 1024u + 4u * lane4)),
-                                         (__attribute__((address_space(3))) void*)(xs + nfull * 256), 16, 0, 0);
-    } else {
-      for (int i = (int)(lane4 >> 2); i < p.xs_floats; i += 64) xs[i] = load_sample(w, j0 + i, cd.num_samples, cd.padded_len);
-    }
+    stage_span_wave<6>(w, (int64_t)f0 * shift - p.npad_left, xs, p.xs_floats, cd.num_samples, lane4, [&](int64_t j0) {
+      span_fill(xs, p.xs_floats, lane4, j0, [&](int64_t j) { return load_sample(w, j, cd.num_samples, cd.padded_len); });
+    });
   };
 
   const int first_frame = fb * p.frames_per_block + 8 * wv;  // the waves take the frame octets round-robin
@@ -180,22 +163,19 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
           }
         }
         // exchange in two halves: rows k1 = 8h .. 8h+7 through an 8-row block per frame; lane q reads row q of each half
-        float* exf = myreg + mul24(g, k256ExFrameStride);
+        float* exf = myreg + mul24(g, kDExFrameStride);
         v2 b[16];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
-          for (int rr = 0; rr < 8; ++rr) *reinterpret_cast<v2*>(exf + rr * k256ExRowStride + 2 * q) = a[8 * h + rr];
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          for (int rr = 0; rr < 8; ++rr) *reinterpret_cast<v2*>(exf + rr * kDExRowStride + 2 * q) = a[8 * h + rr];
+          wave_lds_sync();
 #pragma unroll
           for (int n2 = 0; n2 < 8; ++n2) {
-            b[8 * h + n2] = *reinterpret_cast<const v2*>(exf + mul24(q, k256ExRowStride) + 2 * n2);
+            b[8 * h + n2] = *reinterpret_cast<const v2*>(exf + mul24(q, kDExRowStride) + 2 * n2);
             HFC_SEP();
           }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
+          wave_lds_release();
         }
         // the lane-table entries of this lane's filterbank slots, a phase early (no dependent LDS look-up in front of the operand reads)
 #pragma unroll
@@ -226,9 +206,7 @@ __global__ __launch_bounds__(64 * kDWaves, 4) void fft256c_kernel(const Fft512cP
       if (q == 0) prow[64] = 4.f * (Z1[4].x * Z1[4].x + Z1[4].y * Z1[4].y);
     }
     // the wave's eight power rows are complete once its own (in-order) LDS queue has drained
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // the next round's span (requested at the start of this round) must have landed before this round's stores join the same
     // in-order vmcnt queue: waiting here instead of at the top of the next round never waits for the stores

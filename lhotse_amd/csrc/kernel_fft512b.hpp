@@ -22,11 +22,6 @@ constexpr int kBExRowStride = 34;                        // dwords per exchange 
 constexpr int kBExParts = 2;
 constexpr int kBExFrameStride = 8 * kBExRowStride + 16;  // 288 (== 32 mod 64): 8 rows per half
 constexpr int kBWaveRegion = 4 * kBExFrameStride + 16;   // 1168 dwords per wave (== 16 mod 64)
-constexpr int kBMelVec = kMelARegs / 4;                  // 16-byte loads of filter weights per lane per tile
-
-
-constexpr int kMaxDctGroups = 10;
-#define HF_SEP() asm volatile("")  // keeps hipcc from merging two ds_read_b64 into one half-rate ds_read2_b64 (tools/ubench/lds_rate.hip)
 
 // OUT = 0: log-mel filterbank (Wav2LogFilterBank).  OUT = 1: MFCC -- the log-mel tile goes to LDS instead of
 // HBM and a second (dense, tiny) MFMA GEMM applies the DCT (layers.py:716), then the lifter (:717-718).
@@ -49,13 +44,7 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
 
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const float* __restrict__ w = p.wave + cd.wave_off;
   const int N = p.N, shift = p.shift;
@@ -79,15 +68,7 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
   // back at odd sample offsets run at the same rate and give identical results), so any packing works.
   // Tiles touching a cut edge (reflection / zero padding): scalar loads.
   auto stage_span = [&](int f0, unsigned lane16) {
-    const int64_t j0 = (int64_t)f0 * shift - p.npad_left;
-    if (j0 >= 0 && j0 + (int64_t)nchunks * 256 <= cd.num_samples) {
-      const char* src = reinterpret_cast<const char*>(w + j0);  // uniform
-      for (int ch = wv; ch < nchunks; ch += 4)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ((unsigned)ch * 1024u + lane16)),
-                                         (__attribute__((address_space(3))) void*)(xs + ch * 256), 16, 0, 0);
-    } else {
-      for (int i = tid; i < p.xs_floats; i += 256) xs[i] = load_sample(w, j0 + i, cd.num_samples, cd.padded_len);  // the whole buffer: rows past N are read (and masked) too
-    }
+    stage_span_tile(w, (int64_t)f0 * shift - p.npad_left, xs, p.xs_floats, nchunks, cd, wv, tid, lane16);
   };
 
   const int first_tile = fb * p.tiles_per_block;
@@ -135,9 +116,9 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
       v2 win[NROWS];
       v2 sum2 = {0.f, 0.f};
 #pragma unroll
-      for (int n1 = 0; n1 < NROWS; ++n1) { z[n1] = *reinterpret_cast<const v2*>(x + 32 * n1); HF_SEP(); }
+      for (int n1 = 0; n1 < NROWS; ++n1) { z[n1] = *reinterpret_cast<const v2*>(x + 32 * n1); HFC_SEP(); }
 #pragma unroll
-      for (int n1 = 0; n1 < NROWS; ++n1) { win[n1] = cwin[n1 * 16 + q]; HF_SEP(); }
+      for (int n1 = 0; n1 < NROWS; ++n1) { win[n1] = cwin[n1 * 16 + q]; HFC_SEP(); }
       // samples at or beyond N (the frame length) are not part of the frame: the template instance may carry up to three
       // rows more than ceil(N / 32), so every row is checked (uniform test per row, lane mask only in the boundary rows)
 #pragma unroll
@@ -176,7 +157,7 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
           for (int r = 0; r < 8; ++r) tw[r] = twpreg[8 * h + r];
         } else {
 #pragma unroll
-          for (int r = 0; r < 8; ++r) { tw[r] = ctwp[(8 * h + r) * 16 + q]; HF_SEP(); }
+          for (int r = 0; r < 8; ++r) { tw[r] = ctwp[(8 * h + r) * 16 + q]; HFC_SEP(); }
         }
 #pragma unroll
         for (int r = (h == 0 ? 1 : 0); r < 8; ++r) a[8 * h + r] = cmul2(a[8 * h + r], tw[r]);
@@ -191,15 +172,12 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
       for (int h = 0; h < kBExParts; ++h) {
 #pragma unroll
         for (int r = 0; r < RPP; ++r) *reinterpret_cast<v2*>(exf + r * kBExRowStride + 2 * q) = a[RPP * h + r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         if (h == 0 || q / RPP == h) {  // part 0: every lane reads (b is never undefined: nothing for hipcc to carry around the tile loop)
 #pragma unroll
-          for (int n2 = 0; n2 < 16; ++n2) { b[n2] = *reinterpret_cast<const v2*>(exf + (q % RPP) * kBExRowStride + 2 * n2); HF_SEP(); }
+          for (int n2 = 0; n2 < 16; ++n2) { b[n2] = *reinterpret_cast<const v2*>(exf + (q % RPP) * kBExRowStride + 2 * n2); HFC_SEP(); }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_release();
       }
       v2 Z[16];
       fft16(b, Z);
@@ -229,7 +207,7 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
           if (kRegTw) tw[r] = twsreg[4 * h + r];
           else {
             tw[r] = ctws[(4 * h + r) * 16 + q];
-            HF_SEP();
+            HFC_SEP();
           }
         }
 #pragma unroll
@@ -290,7 +268,7 @@ __global__ __launch_bounds__(256, 4) void fft512b_kernel(const Fft512Params p) {
       v2 pv[NCH][CH];
       auto load_chunk = [&](int ci) {
 #pragma unroll
-        for (int i = 0; i < CH; ++i) { pv[ci][i] = *reinterpret_cast<const v2*>(pb + min(ww.bin0 + 8 * (ci * CH + i), kPRowStride - 8)); HF_SEP(); }
+        for (int i = 0; i < CH; ++i) { pv[ci][i] = *reinterpret_cast<const v2*>(pb + min(ww.bin0 + 8 * (ci * CH + i), kPRowStride - 8)); HFC_SEP(); }
       };
       load_chunk(0);
       // gfx950 has ONE in-order counter for all vector-memory operations: take delivery of the weights

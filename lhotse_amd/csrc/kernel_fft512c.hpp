@@ -25,6 +25,7 @@
 #include "common.hpp"
 #include "fft512c_geom.hpp"  // kCExRowStride, kCExFrameStride, kCPRowStride, kCRegion, kCMaxSets, kCMaxSteps
 #include "fft_common.hpp"
+#include "wave_auto.hpp"
 
 namespace hipfeat {
 
@@ -54,15 +55,6 @@ struct Fft512cParams {
   int32_t C;
   int32_t total_quads;  // FLAT instances: frame quads (4 frames of one cut) of the whole batch; CutDesc::first_block then is a cut's first quad
 };
-
-#ifdef HIPFEAT_PHASE_TIMERS
-#define HFC_T(i) { const unsigned long long tt_ = __builtin_readcyclecounter(); hfc_acc[i] += tt_ - hfc_last; hfc_last = tt_; }
-#else
-#define HFC_T(i)
-#endif
-#define HFC_SEP() asm volatile("")
-// lane-index multiplies: v_mul_u32_u24 issues at the full VALU rate, v_mul_lo_u32 at a quarter of it
-__device__ __forceinline__ int mul24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
 
 // The LDS exchange between the two FFT passes of one wave, as ONE instruction sequence: the rows k1 = 0..7 (`lo`) go through the wave's
 // 8-row blocks and every lane reads "its" row q % 8 back, then the rows k1 = 8..15 (`hi`) go through the same blocks and the lanes with
@@ -197,12 +189,8 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
   if (FLAT) {
     cut = __builtin_amdgcn_readfirstlane(block_cut_map(p.cuts, p.num_cuts)[blk]);
     fb = 0;
-  } else if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
   } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
+    block_owner(p, blk, cut, fb);
   }
   CutDesc cd = FLAT ? load_cut_uniform(p.cuts + cut) : p.cuts[cut];  // (FLAT: the cut of the CURRENT round; it changes as the wave walks through the batch)
   const int N = p.N, shift = p.shift;
@@ -231,6 +219,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       typedef __attribute__((address_space(3))) float lds_float;
       span_pieces(src, (unsigned)(size_t)(lds_float*)xs, 4u * lane4, 4 * p.xs_floats);
 #else  // experiment build: a wave-uniform test per whole piece, as before (the same requests)
+      // (its own copy of wave_auto.hpp::span_request<6>: the shared form, which takes a piece's LDS address first, compiles to six lines more here)
       const int nfull = p.xs_floats >> 8;
 #pragma unroll
       for (int ch = 0; ch < 6; ++ch) {
@@ -308,9 +297,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
     for (int c4 = 0; c4 < DREG; ++c4) dw[c4] = *reinterpret_cast<const f32x4*>(p.dct_tab + (c4 * 64 + lane) * 4);
     lift = p.dct_tab[DCH * 256 + lane];
   }
-#ifdef HIPFEAT_PHASE_TIMERS
-  unsigned long long hfc_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hfc_last = __builtin_readcyclecounter();
-#endif
+  HFC_TIMERS();
   for (int r = 0; r < p.rounds; ++r) {
     const int f0 = FLAT ? f0_flat : first_frame + 4 * kCWaves * r;
     if (FLAT ? quad >= p.total_quads : f0 >= cd.num_frames) break;
@@ -504,9 +491,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
     }
     HFC_T(4);  // pass 2, split step, power rows
     // the wave's four power rows are complete once its own (in-order) LDS queue has drained
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // ---- mel filterbank on the matrix cores, 4 frames x 4 filters x 1 bin per block, 16 blocks per instruction ----
     // All operands of the phase are requested before the first MFMA (one LDS round trip; the FFT registers are dead):
@@ -613,9 +598,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
 #pragma unroll
         for (int i = 0; i < 4; ++i) lmrow[i * kCLmStride + col] = lm[i];
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       f32x4 al[DCH];  // A operand: lane (block b, frame i) = log-mel of frame i, four filters per read (the same for every block)
 #pragma unroll
       for (int c4 = 0; c4 < DCH; ++c4) al[c4] = *reinterpret_cast<const f32x4*>(lmrow + (lane_o & 3) * kCLmStride + 4 * c4);
@@ -638,9 +621,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       // the next round's exchange writes follow these reads in the wave's own LDS queue (in order)
     }
     HFC_T(6);  // MFMAs, reduction, log, stores
-#ifdef HIPFEAT_PHASE_TIMERS
-    hfc_acc[7] += 1;
-#endif
+    HFC_ROUND();
     // the next round's exchange writes follow this round's power-row reads in the wave's own LDS queue (in order)
     if (FLAT) {  // the staged round becomes the current one; locate the one after it
       quad = quad_n, cut = cut_n, cd = cd_n, next_first = next_first_n, f0_flat = f0_n;
@@ -649,12 +630,7 @@ __global__ __launch_bounds__(64 * kCWaves, 4) void fft512c_kernel(const Fft512cP
       f0_n = 4 * (quad_n - cd_n.first_block);
     }
   }
-#ifdef HIPFEAT_PHASE_TIMERS
-  if (lane == 0 && g_phase_buf) {
-    unsigned long long* o = g_phase_buf + ((size_t)blockIdx.x * kCWaves + wv) * 8;
-    for (int i = 0; i < 8; ++i) o[i] = hfc_acc[i];
-  }
-#endif
+  HFC_DUMP(lane, (size_t)blockIdx.x * kCWaves + wv);
 }
 
 }  // namespace hipfeat

@@ -43,13 +43,7 @@ __global__ __launch_bounds__(256) void generic_kernel(const GenericParams p) {
   constexpr int T = 256;
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const int f0 = fb * p.fpb;
   const int nf = min(p.fpb, cd.num_frames - f0);

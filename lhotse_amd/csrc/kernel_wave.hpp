@@ -43,12 +43,6 @@ __device__ __forceinline__ v2 twiddle_h(const float2* __restrict__ tw, int m, in
   return neg ? v2{-w.x, -w.y} : v2{w.x, w.y};
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ float wave_sum(float v) {  // every lane gets the total: 4 DPP adds inside the rows of 16, then the 4 row totals
   v = row16_sum(v);
   const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
@@ -164,13 +158,7 @@ struct CutSource {
   int fb;
   __device__ __forceinline__ CutSource(const WaveParams& p, const NoSourceArgs&, int blk) {
     int cut;
-    if (p.uniform_bpc > 0) {
-      cut = blk / p.uniform_bpc;
-      fb = blk - cut * p.uniform_bpc;
-    } else {
-      cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-      fb = blk - p.cuts[cut].first_block;
-    }
+    block_owner(p, blk, cut, fb);
     const CutDesc cd = p.cuts[cut];
     w = p.wave + cd.wave_off;
     out_row = cd.out_row;

@@ -61,13 +61,7 @@ __global__ __launch_bounds__(256, HIPFEAT_W2_OCC) void whisper2_kernel(const Whi
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const float* __restrict__ w = p.wave + cd.wave_off;
   const int S = cd.num_samples;
@@ -132,9 +126,7 @@ __global__ __launch_bounds__(256, HIPFEAT_W2_OCC) void whisper2_kernel(const Whi
     *reinterpret_cast<v2*>(tb + 2 * q) = Y[0];
 #pragma unroll
     for (int k = 1; k <= 12; ++k) *reinterpret_cast<v2*>(tb + k * kW2TStride + 2 * q) = cmul(Y[k], twl[k * 16 + q]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     v2 xin[16], X[16];
     {
       const float* src = tb + min(q, 12) * kW2TStride;

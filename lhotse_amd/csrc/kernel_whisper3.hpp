@@ -16,7 +16,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
-#include "kernel_fft512c.hpp"  // HFC_SEP, mul24
+#include "wave_auto.hpp"
 
 namespace hipfeat {
 
@@ -64,13 +64,7 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
 
   const int blk = blockIdx.x;
   int cut, fb;
-  if (p.uniform_bpc > 0) {
-    cut = blk / p.uniform_bpc;
-    fb = blk - cut * p.uniform_bpc;
-  } else {
-    cut = p.uniform_bpc < 0 ? block_cut_map(p.cuts, p.num_cuts)[blk] : find_cut(p.cuts, p.num_cuts, blk);
-    fb = blk - p.cuts[cut].first_block;
-  }
+  block_owner(p, blk, cut, fb);
   const CutDesc cd = p.cuts[cut];
   const float* __restrict__ w = p.wave + cd.wave_off;
   const int S = cd.num_samples;
@@ -83,6 +77,7 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
   // the tails of the power rows (floats 238..271) are never written by a round but may meet zero weights: make them finite once
   for (int i = lane; i < kW3Region; i += 64) myreg[i] = 0.f;
 
+  // (its own copy of wave_auto.hpp::stage_span_wave: with the constant span length the shared form compiles to three instructions less)
   auto stage_span = [&](int f0, unsigned lane4) {
     const int64_t j0 = (int64_t)f0 * kW3Shift - kW3N / 2;
     if (j0 >= 0 && j0 + kW3Span <= (int64_t)S) {
@@ -121,9 +116,7 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
   for (int s2 = 0; s2 < NSETS; ++s2) poffreg[s2] = __builtin_bit_cast(int, ltab[s2 * 256 + 4 * lane]);
   const bool fused = p.wg_stat != nullptr;
   float mx = -INFINITY, mn = INFINITY;
-#ifdef HIPFEAT_PHASE_TIMERS
-  unsigned long long hfc_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hfc_last = __builtin_readcyclecounter();
-#endif
+  HFC_TIMERS();
   for (int r = 0; r < p.rounds; ++r) {
     const int f0 = first_frame + 4 * kW3Waves * r;
     if (f0 >= cd.num_frames) break;
@@ -198,9 +191,7 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
 #pragma unroll
         for (int rr = 0; rr < 7; ++rr)
           if (7 * h + rr <= 12) *reinterpret_cast<v2*>(exf + rr * kW3TStride + 2 * q) = Y[7 * h + rr];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         // half 0: every lane reads (lanes 7.. get a row they do not need); half 1: lanes 7.. replace it -- xin is never undefined, which
         // keeps hipcc from carrying it around the round loop
         if (h == 0 || myrow >= 7) {
@@ -211,8 +202,7 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
             HFC_SEP();
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_release();
       }
     }
     HFC_T(2);  // twiddles, transpose
@@ -235,9 +225,7 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
     }
     HFC_T(3);  // fft16, power rows
     // the wave's four power rows are complete once its own (in-order) LDS queue has drained
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // the next round's span (requested at the start of this round) must have landed before this round's stores join the same
     // in-order vmcnt queue
@@ -291,16 +279,9 @@ __global__ __launch_bounds__(64 * kW3Waves, 4) void whisper3_kernel(const Whispe
       }
     }
     HFC_T(5);  // mel filterbank, log10, stores
-#ifdef HIPFEAT_PHASE_TIMERS
-    hfc_acc[7] += 1;
-#endif
+    HFC_ROUND();
   }
-#ifdef HIPFEAT_PHASE_TIMERS
-  if (lane == 0 && g_phase_buf) {
-    unsigned long long* o = g_phase_buf + ((size_t)blockIdx.x * kW3Waves + wv) * 8;
-    for (int i = 0; i < 8; ++i) o[i] = hfc_acc[i];
-  }
-#endif
+  HFC_DUMP(lane, (size_t)blockIdx.x * kW3Waves + wv);
 
   // ---- 6. per-cut normalisation, finished by the workgroup that completes the cut -----------------------------------------------------------
   // The rows above already hold y = (v + 4) / 4; what is missing is the clamp max(v, cut_max - 8), i.e. max(y, c) with
