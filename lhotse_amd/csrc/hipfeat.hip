@@ -14,6 +14,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <variant>
 #include <vector>
 
 #include "common.hpp"
@@ -202,12 +203,14 @@ enum class Route {
   Fft256c,   // fft256 wave-autonomous fbank
 };
 
+// The one argument of a plan's kernel: the Params struct of its family.  The setup that claims the plan fills every field that does not
+// depend on the call, straight from the tables it built; launch() copies it and binds the buffers and the layout.
+using KernelParams = std::variant<GenericParams, WaveParams, Whisper2Params, Whisper3Params, Fft512Params, Fft512cParams, Fft1024cParams, Fft2048cParams>;
+
 struct hipfeat_plan {
   hipfeat_config cfg{};
   int device = 0;
   int feature_dim = 0;
-  int K = 0, H = 0, log2H = 0;
-  bool pow2 = false;
   int npad_left = 0;
   std::string kernel_name = "generic";
   int blocks_per_cu = 0;  // hipOccupancyMaxActiveBlocksPerMultiprocessor for the selected kernel
@@ -219,49 +222,15 @@ struct hipfeat_plan {
   // kMel4WideMaxStride or more (the wide store's 32-bit lane offset holds three rows and a column only below it); nullptr: fn / fn_flat serve all
   const void* fn_far = nullptr;
   const void* fn_flat_far = nullptr;
-  int block = 0;                  // threads per workgroup
-  size_t lds = 0;                 // dynamic LDS bytes
-  // device constants
-  float* d_window = nullptr;
-  float2* d_tw = nullptr;
-  float* d_mel = nullptr;
-  int2* d_mel_range = nullptr;
-  float* d_dct = nullptr;
-  float* d_lifter = nullptr;
-  // generic kernel geometry
-  int fpb = 8;
-  int span = 0, off_z = 0, off_p = 0, off_tw = 0, off_stat = 0, off_mel = 0;
-  // fft512 / fft256 "b" kernels
-  float* d_mel_a4 = nullptr;
-  float* d_dct_consts = nullptr;
-  int lm_stride = 0, dct_groups = 0, dct_floats = 0;
-  int tiles_per_block = 4;
-  int xs_floats = 0;
-  int const_floats = 0;
-  float* d_lds_consts = nullptr;
-  float* d_mel_a = nullptr;  // fft512 "b": the operands before the reorder to d_mel_a4 (uploaded, read by no kernel)
-  WaveWork* d_work = nullptr;
-  // wave-autonomous kernels (fft512c, fft256c, fft1024c, fft2048c, whisper3)
-  float* d_c_shared = nullptr;  // LDS image: FFT constants | 4x4-block filterbank weights | lane tables
-  int c_shared_floats = 0, c_wtab_off = 0, c_ltab_off = 0, c_xs_floats = 0;
-  // wave-autonomous kernels: frames per workgroup = fpb_unit (frames of one round of all waves) x rounds, rounds chosen per LAYOUT between 2
+  int block = 0;        // threads per workgroup
+  size_t lds = 0;       // dynamic LDS bytes
+  KernelParams params;  // (the generic kernel's until a setup claims the plan)
+  std::vector<void*> uploads;  // the device tables `params` points to, in upload order: the plan's to free
+  // frames per workgroup.  Wave-autonomous kernels: fpb_unit (frames of one round of all waves) x rounds, rounds chosen per LAYOUT between 2
   // and c_rounds_max: long launches take many rounds per workgroup (the constant tables and the first, un-overlapped span are paid once per
   // workgroup: 16 instead of 8 rounds is + 4 % on the bench workload), short ones few (enough workgroups to fill the chip)
+  int fpb = 8;
   int fpb_unit = 0, c_rounds_max = 0;
-  // fft1024c / fft2048c / whisper3: accumulator sets of the filterbank schedule
-  int w_nsets = 0, w_steps[kWMaxSets] = {}, w_step0[kWMaxSets] = {};
-  // fft2048c
-  float* d_x_twp = nullptr;  // [32][32] v2 W_1024^(q k1)
-  int x_waves = 0, x_tws_off = 0, x_tw32_off = 0;
-  // wave-per-frame kernel
-  float* d_mel_t = nullptr;  // filterbank blob (descriptors + compact weights)
-  int wave_blob_floats = 0;
-  bool wave_dct_in_lds = false;
-  // whisper2 (whisper3 reads its d_wh2_cs)
-  float* d_wh2_cs = nullptr;
-  float* d_wh2_tw = nullptr;
-  float* d_wh2_mel = nullptr;
-  int32_t* d_wh2_sched = nullptr;
   // transient-layout staging ring (hipfeat_extract)
   mutable std::mutex mu;
   mutable SlotRing<4> ring;
@@ -346,37 +315,37 @@ static hipfeat_status upload(T** dst, const T* src, size_t n) {
   return HIPFEAT_OK;
 }
 
+// ... into a Params field of a handle that frees its tables as a whole: the allocation joins `owned` (a failed copy's too)
+template <typename T>
+static hipfeat_status upload(std::vector<void*>& owned, const T*& dst, const T* src, size_t n) {
+  T* d = nullptr;
+  const hipfeat_status st = upload(&d, src, n);
+  if (d) owned.push_back(d);
+  dst = d;
+  return st;
+}
+
+static void free_uploads(std::vector<void*>& owned) {
+  for (void* d : owned) (void)hipFree(d);
+  owned.clear();
+}
+
 static void plan_free(hipfeat_plan* p) {
   if (!p) return;
   DeviceGuard g(p->device);
-  (void)hipFree(p->d_window);
-  (void)hipFree(p->d_tw);
-  (void)hipFree(p->d_mel);
-  (void)hipFree(p->d_mel_range);
-  (void)hipFree(p->d_wh2_cs);
-  (void)hipFree(p->d_x_twp);
-  (void)hipFree(p->d_wh2_tw);
-  (void)hipFree(p->d_wh2_mel);
-  (void)hipFree(p->d_wh2_sched);
-  (void)hipFree(p->d_dct);
-  (void)hipFree(p->d_lifter);
+  free_uploads(p->uploads);
   (void)hipFree(p->d_scratch_wave);
   (void)hipFree(p->d_scratch_out);
-  (void)hipFree(p->d_lds_consts);
-  (void)hipFree(p->d_mel_a4);
-  (void)hipFree(p->d_dct_consts);
-  (void)hipFree(p->d_mel_a);
-  (void)hipFree(p->d_work);
-  (void)hipFree(p->d_mel_t);
-  (void)hipFree(p->d_c_shared);
   p->ring.free_all();  // (waits for the launches that used a slot)
   delete p;
 }
 
 // --------------------------------------------------------------------------------------
 // specialised kernels.  Every setup_* checks that the configuration and the routing switches admit its kernel family, has the family's
-// constant tables built (plan_tables.hpp: pure host code, tested on the CPU), tests the LDS budget, picks the kernel instance, uploads
-// the tables and claims the plan.  A setup that leaves the plan unclaimed has changed nothing the next one reads.
+// constant tables built (plan_tables.hpp: pure host code, tested on the CPU), tests the LDS budget, picks the kernel instance, fills
+// a Params of the family -- each table uploaded into the field that points to it, each constant written from the tables struct -- and
+// claims the plan with it.  The one place a family's kernel constants are wired is its setup: launch() adds only what a call brings.
+// A setup that leaves the plan unclaimed has changed nothing the next one reads.
 // --------------------------------------------------------------------------------------
 template <auto* F>
 static const void* entry() {
@@ -496,28 +465,12 @@ static int feature_dim(const hipfeat_config& c) {
   return (c.kind == HIPFEAT_WHISPER || c.kind == HIPFEAT_LIBROSA_FBANK) ? c.num_filters : c.fft_length / 2 + 1;
 }
 
-// What the wave-per-frame kernel (kernel_wave.hpp) reads besides the config: its tables on the device and its LDS bytes
-struct WaveFront {
-  float* d_window = nullptr;
-  float2* d_tw = nullptr;
-  float* d_mel_blob = nullptr;  // filterbank blob (descriptors + compact weights)
-  float* d_dct = nullptr;
-  float* d_lifter = nullptr;
-  int blob_floats = 0;
-  bool dct_in_lds = false;
-  size_t lds = 0;
-};
-
-// the WaveParams fields that do not depend on the call (its buffers, batch, frames per wave and npad_left do)
-static void fill_wave_front(WaveParams& wp, const hipfeat_config& c, const WaveFront& t) {
+// The WaveParams fields (kernel_wave.hpp) that come from the config and the tables' sizes; the creator uploads the tables into the
+// pointer fields and sets frames per wave and npad_left, the call brings its buffers and batch
+static void fill_wave_front(WaveParams& wp, const hipfeat_config& c, const WaveTables& t) {
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
-  wp.window = t.d_window;
-  wp.tw = t.d_tw;
-  wp.mel_blob = t.d_mel_blob;
-  wp.mel_blob_floats = t.blob_floats;
+  wp.mel_blob_floats = (int)t.blob.size();
   wp.dct_in_lds = t.dct_in_lds ? 1 : 0;
-  wp.dct = t.d_dct;
-  wp.lifter = t.d_lifter;
   wp.N = c.frame_length;
   wp.shift = c.frame_shift;
   wp.H = c.fft_length / 2;
@@ -601,8 +554,8 @@ static void fill_stft_front(StftParams& p, const StftFront& f) {
 }
 
 // The setup that accepts a configuration claims the plan with the instance it runs: the instance's dynamic-LDS limit is raised, its
-// occupancy read (blocks_per_cu, part of the kernel name) and the launch recorded for launch().
-static hipfeat_status claim(hipfeat_plan* p, Route route, const void* fn, int block, size_t lds) {
+// occupancy read (blocks_per_cu, part of the kernel name) and the launch recorded for launch(), `params` as the kernel's argument.
+static hipfeat_status claim(hipfeat_plan* p, Route route, const void* fn, int block, size_t lds, const KernelParams& params) {
   if (hipfeat_status bad = set_dynamic_lds(fn, lds)) return bad;
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, block, lds) == hipSuccess) p->blocks_per_cu = nb;
@@ -610,54 +563,89 @@ static hipfeat_status claim(hipfeat_plan* p, Route route, const void* fn, int bl
   p->fn = fn;
   p->block = block;
   p->lds = lds;
+  p->params = params;
   return HIPFEAT_OK;
 }
 
-// Wave-autonomous families: uploads the LDS image, stores what launch() passes on, claims the plan for `fn` and names it `head` + the
-// common trailer.  A wave takes `frames` frames per round; a workgroup runs 2 .. rounds_max rounds, chosen per layout (build_descs).
-static hipfeat_status claim_wave_auto(hipfeat_plan* p, Route route, const void* fn, const WaveAutoTables& t, int frames, int rounds, int rounds_max,
-                                      const std::string& head) {
-  hipfeat_status st;
-  if ((st = upload(&p->d_c_shared, t.image.data(), t.image.size())) != HIPFEAT_OK) return st;
-  if (!t.dct.empty() && (st = upload(&p->d_dct_consts, t.dct.data(), t.dct.size())) != HIPFEAT_OK) return st;
-  if (!t.twp.empty() && (st = upload(&p->d_x_twp, t.twp.data(), t.twp.size())) != HIPFEAT_OK) return st;
-  p->c_shared_floats = t.shared_floats;
-  p->c_wtab_off = t.wtab_off;
-  p->c_ltab_off = t.ltab_off;
-  p->c_xs_floats = t.xs_floats;
-  p->x_tws_off = t.tws_off;
-  p->x_tw32_off = t.tw32_off;
-  p->w_nsets = t.w_nsets;
-  std::copy(t.w_steps, t.w_steps + 4, p->w_steps);
-  std::copy(t.w_step0, t.w_step0 + 4, p->w_step0);
+// What the Params of the wave-autonomous families (fft512c / fft256c, fft1024c, fft2048c, whisper3) share: one LDS constants image,
+// uploaded here, the offsets of its tables, the filter count and floor.  The batch and the rounds of frames come with the launch.
+template <typename P>
+static hipfeat_status fill_wave_autonomous(P& q, hipfeat_plan* p, const WaveAutoTables& t) {
+  if (hipfeat_status bad = upload(p->uploads, q.shared_consts, t.image.data(), t.image.size())) return bad;
+  q.shared_floats = t.shared_floats;
+  q.wtab_off = t.wtab_off;
+  q.ltab_off = t.ltab_off;
+  q.M = p->cfg.num_filters;
+  q.mel_floor = p->cfg.mel_floor;
+  return HIPFEAT_OK;
+}
+
+// Frame geometry of the wave-autonomous FFT kernels (fft512c / fft256c plans have neither magnitudes nor centred framing: their
+// flags come down to F_REMOVE_DC).
+template <typename P>
+static void fill_frames(P& q, const hipfeat_plan* p, const WaveAutoTables& t) {
+  const hipfeat_config& c = p->cfg;
+  q.N = c.frame_length;
+  q.shift = c.frame_shift;
+  q.npad_left = p->npad_left;
+  q.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LIBROSA_FBANK ? (F_CENTER | F_LOG10) : 0);
+  q.preemph = c.preemph_coeff;
+  q.xs_floats = t.xs_floats;
+}
+
+// fft1024c / fft2048c: the accumulator sets the kernel walks, every entry of the tables' arrays
+template <typename P>
+static void fill_sets(P& q, const WaveAutoTables& t) {
+  static_assert(sizeof(q.steps) == sizeof(t.w_steps) && sizeof(q.step0) == sizeof(t.w_step0), "the kernel's set arrays and the tables' differ in length");
+  q.nsets = t.w_nsets;
+  std::copy(std::begin(t.w_steps), std::end(t.w_steps), q.steps);
+  std::copy(std::begin(t.w_step0), std::end(t.w_step0), q.step0);
+}
+static_assert(kWMaxSets == kXMaxSets, "fft1024c and fft2048c take their sets from one WaveAutoTables");
+
+// Wave-autonomous families: claims the plan for `fn` with the filled `params` and names it `head` + the common trailer.  A wave takes
+// `frames` frames per round; a workgroup runs 2 .. rounds_max rounds, chosen per layout (build_descs).
+static hipfeat_status claim_wave_auto(hipfeat_plan* p, Route route, const void* fn, const WaveAutoTables& t, const KernelParams& params, int frames, int rounds,
+                                      int rounds_max, const std::string& head) {
   p->fpb_unit = t.waves * frames;
   p->fpb = p->fpb_unit * rounds;
   p->c_rounds_max = rounds_max;
-  if ((st = claim(p, route, fn, 64 * t.waves, t.lds)) != HIPFEAT_OK) return st;
+  if (hipfeat_status bad = claim(p, route, fn, 64 * t.waves, t.lds, params)) return bad;
   p->kernel_name = head + strf(" lds=%zuB blocks/CU=%d mel4=%dx%d", t.lds, p->blocks_per_cu, t.sch_nsets, t.sch_steps);
   return HIPFEAT_OK;
 }
 
-// fft512 "b" / fft256 "b": uploads the tables, stores what launch() passes on, claims the plan for `fn`
+// fft512 "b" / fft256 "b": fills the Fft512Params, uploading the tables, and claims the plan for `fn`
 static hipfeat_status claim_tile(hipfeat_plan* p, Route route, const void* fn, const TileTables& t, int tile_frames, const char* kernel) {
   const hipfeat_config& c = p->cfg;
   const bool mfcc = c.kind == HIPFEAT_MFCC, spec = c.kind == HIPFEAT_SPECTROGRAM || c.kind == HIPFEAT_LOG_SPECTROGRAM;
+  Fft512Params q{};
+  const float* mel_a_plain = nullptr;  // fft512 "b": the operands before the reorder to mel_a (uploaded, read by no kernel)
   hipfeat_status st;
-  if ((st = upload(&p->d_lds_consts, t.consts.data(), t.consts.size())) != HIPFEAT_OK) return st;
-  if (route == Route::Fft512b && (st = upload(&p->d_mel_a, t.mel_a.data(), t.mel_a.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_work, t.work, 4)) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_mel_a4, t.mel_a4.data(), t.mel_a4.size())) != HIPFEAT_OK) return st;
-  if (mfcc && (st = upload(&p->d_dct_consts, t.dct.data(), t.dct.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.lds_consts, t.consts.data(), t.consts.size())) != HIPFEAT_OK) return st;
+  if (route == Route::Fft512b && (st = upload(p->uploads, mel_a_plain, t.mel_a.data(), t.mel_a.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.work, t.work, 4)) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.mel_a, t.mel_a4.data(), t.mel_a4.size())) != HIPFEAT_OK) return st;
+  if (mfcc && (st = upload(p->uploads, q.dct_consts, t.dct.data(), t.dct.size())) != HIPFEAT_OK) return st;
   // 16 tiles per workgroup: the constant-table load and the first, un-overlapped span fetch are paid once per workgroup (measured on
   // MI355X, cuts/s: fft512 4 -> 1.98 M, 8 -> 2.11 M, 16 -> 2.16 M; fft256 at 8 kHz fbank-80 8 -> 3.84 M, 16 -> 3.99 M, 32 -> 3.93 M)
-  p->tiles_per_block = 16;
-  p->fpb = tile_frames * p->tiles_per_block;
-  p->const_floats = (int)t.consts.size();
-  p->xs_floats = t.xs_floats;
-  p->lm_stride = t.lm_stride;
-  p->dct_groups = t.dct_groups;
-  p->dct_floats = (int)t.dct.size();
-  if ((st = claim(p, route, fn, 256, t.lds)) != HIPFEAT_OK) return st;
+  q.tiles_per_block = 16;
+  p->fpb = tile_frames * q.tiles_per_block;
+  q.N = c.frame_length;
+  q.shift = c.frame_shift;
+  q.npad_left = p->npad_left;
+  q.M = c.num_filters;
+  q.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LOG_SPECTROGRAM ? F_LOG_SPEC : 0);
+  q.log_offset = c.log_offset;
+  q.preemph = c.preemph_coeff;
+  q.mel_floor = c.mel_floor;
+  q.xs_floats = t.xs_floats;
+  q.const_floats = (int)t.consts.size();
+  q.C = c.num_ceps;
+  q.lm_stride = t.lm_stride;
+  q.dct_groups = t.dct_groups;
+  q.dct_floats = (int)t.dct.size();
+  if ((st = claim(p, route, fn, 256, t.lds, q)) != HIPFEAT_OK) return st;
   // same spelling as the device symbol rocprofv3 reports (modulo the space after the comma)
   p->kernel_name = strf("%s<%d,%d> %s lds=%zuB blocks/CU=%d", kernel, t.nrows, mfcc ? 1 : (spec ? 2 : 0), mfcc ? "mfcc" : (spec ? "spectrogram" : "fbank"), t.lds,
                         p->blocks_per_cu);
@@ -708,9 +696,15 @@ static hipfeat_status setup_fft512c(hipfeat_plan* p, const PlanInputs& in, int n
   const Fft512cMelSteps ts = (wide && t.mode == 0 && !route_env("HIPFEAT_NO_FIXED_SCHEDULE")) ? fft512c_mel_steps(t.sch_nsets, t.sch_set_steps) : padded;
   // the exchange rows are read 16 bytes at a time: every wave's region starts on a 16-byte boundary
   if (t.shared_floats % 4 != 0 || t.xs_floats % 4 != 0) return fail(HIPFEAT_ERR_INVALID, "fft512c: a wave's LDS region is not 16-byte aligned");
+  Fft512cParams q{};
+  hipfeat_status st = fill_wave_autonomous(q, p, t);
+  if (st == HIPFEAT_OK && !t.dct.empty()) st = upload(p->uploads, q.dct_tab, t.dct.data(), t.dct.size());
+  if (st != HIPFEAT_OK) return st;
+  fill_frames(q, p, t);
+  q.C = p->cfg.num_ceps;
   // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
-  hipfeat_status st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false, wide, ts), t, 4, 8, 16,
-                                      strf("fft512c_kernel<%d> %s", nrows, mfcc ? "mfcc" : "fbank"));
+  st = claim_wave_auto(p, Route::Fft512c, fft512c_dispatch(t.mode, nrows, in.N, false, wide, ts), t, q, 4, 8, 16,
+                       strf("fft512c_kernel<%d> %s", nrows, mfcc ? "mfcc" : "fbank"));
   if (st == HIPFEAT_OK && wide) p->kernel_name += " store=16B";
   const void** more[3] = {&p->fn_flat, &p->fn_far, &p->fn_flat_far};  // the same launch shape, chosen per layout (build_descs) / per launch
   for (int i = 0; st == HIPFEAT_OK && i < 3; ++i) {
@@ -785,7 +779,11 @@ static hipfeat_status setup_fft1024c(hipfeat_plan* p, const PlanInputs& in) {
                    : fixed == 3 ? entry<fft1024c_kernel<20, 24, 24, 8>>()
                    : fixed == 4 ? entry<fft1024c_kernel<32, 16, 16, 8, true>>()
                    : nrows == 20 ? entry<fft1024c_kernel<20>>() : (nrows == 26 ? entry<fft1024c_kernel<26>>() : entry<fft1024c_kernel<32>>());
-  return claim_wave_auto(p, Route::Fft1024c, fn, t, 4, 8, 32, strf("fft1024c_kernel<%d> fbank%s waves=%d", nrows, fixed ? " fixed-schedule" : "", t.waves));
+  Fft1024cParams q{};
+  if (hipfeat_status bad = fill_wave_autonomous(q, p, t)) return bad;
+  fill_frames(q, p, t);
+  fill_sets(q, t);
+  return claim_wave_auto(p, Route::Fft1024c, fn, t, q, 4, 8, 32, strf("fft1024c_kernel<%d> fbank%s waves=%d", nrows, fixed ? " fixed-schedule" : "", t.waves));
 }
 
 // --------------------------------------------------------------------------------------
@@ -797,8 +795,11 @@ static hipfeat_status setup_fft256c(hipfeat_plan* p, const PlanInputs& in, int n
   if (!t.fits || t.lds > 80 * 1024 || (t.xs_floats >> 8) > 6) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
   // 25 ms at 8 kHz (N = 200: 12 full rows of 16 samples + a partial one) gets the instance without length masks on the full rows
   const void* fn = nrows == 13 ? (in.N >= 192 ? entry<fft256c_kernel<13, 12>>() : entry<fft256c_kernel<13, 0>>()) : entry<fft256c_kernel<16, 0>>();
+  Fft512cParams q{};  // (without the MFCC and FLAT fields)
+  if (hipfeat_status bad = fill_wave_autonomous(q, p, t)) return bad;
+  fill_frames(q, p, t);
   // 8 waves x 4 rounds x 8 frames = 256 frames per workgroup
-  return claim_wave_auto(p, Route::Fft256c, fn, t, 8, 4, 16, strf("fft256c_kernel<%d> fbank", nrows));
+  return claim_wave_auto(p, Route::Fft256c, fn, t, q, 8, 4, 16, strf("fft256c_kernel<%d> fbank", nrows));
 }
 
 static hipfeat_status setup_fft256(hipfeat_plan* p, const PlanInputs& in) {
@@ -833,23 +834,26 @@ static hipfeat_status setup_fft256(hipfeat_plan* p, const PlanInputs& in) {
 static hipfeat_status setup_wave(hipfeat_plan* p, const PlanInputs& in) {
   const hipfeat_config& c = p->cfg;
   const bool librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
-  if (!p->pow2 || (c.kind > HIPFEAT_MFCC && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_KERNEL"))
-    return HIPFEAT_OK;
-  const int H = p->H;
+  if ((c.kind > HIPFEAT_MFCC && !librosa) || route_env("HIPFEAT_FORCE_GENERIC") || route_env("HIPFEAT_NO_WAVE_KERNEL")) return HIPFEAT_OK;
+  const int fft = c.fft_length, H = fft / 2;
   // H = 128 (fft 256) stays on the radix-2 kernel: measured 0.92 M vs 0.72 M cuts/s there; H = 256: 0.46 vs 0.48 M
-  if (!(H == 256 || H == 512 || H == 1024) || c.num_filters > 128) return HIPFEAT_OK;
+  if (!(fft == 512 || fft == 1024 || fft == 2048) || c.num_filters > 128) return HIPFEAT_OK;
   const WaveTables t = build_wave_tables(in, H);
+  const GenericParams& g = std::get<GenericParams>(p->params);  // the window, W_fft^k, DCT matrix and lifter are the generic kernel's
+  WaveParams q{};
+  q.window = g.window, q.tw = g.tw, q.dct = g.dct, q.lifter = g.lifter;
   hipfeat_status st;
-  if (in.M > 0 && (st = upload(&p->d_mel_t, t.blob.data(), t.blob.size())) != HIPFEAT_OK) return st;
-  p->wave_blob_floats = (int)t.blob.size();
-  p->wave_dct_in_lds = t.dct_in_lds;
+  if (in.M > 0 && (st = upload(p->uploads, q.mel_blob, t.blob.data(), t.blob.size())) != HIPFEAT_OK) return st;
+  fill_wave_front(q, c, t);
+  q.frames_per_wave = 8;  // 4 waves x 8 frames (the tables copied to LDS per workgroup are ~12 KB)
+  q.npad_left = p->npad_left;
   const void* fn = for_n1(H / 64, [](auto n) -> const void* {  // (no instance for n1 = 2: H = 128 was turned away above)
     if constexpr (decltype(n)::value > 2) return entry<wave_kernel<decltype(n)::value>>();
     return nullptr;
   });
-  if ((st = claim(p, Route::Wave, fn, 256, t.lds)) != HIPFEAT_OK) return st;
+  if ((st = claim(p, Route::Wave, fn, 256, t.lds, q)) != HIPFEAT_OK) return st;
   p->kernel_name = strf("wave_kernel<%d> fft=%d lds=%zuB blocks/CU=%d", H / 64, c.fft_length, t.lds, p->blocks_per_cu);
-  p->fpb = 32;  // 4 waves x 8 frames (the tables copied to LDS per workgroup are ~12 KB)
+  p->fpb = 4 * q.frames_per_wave;
   return HIPFEAT_OK;
 }
 
@@ -858,12 +862,15 @@ static hipfeat_status setup_wave(hipfeat_plan* p, const PlanInputs& in) {
 // when the filterbank schedule and the LDS budget allow, else whisper2 (kernel_whisper2.hpp: banded mel GEMM, normalisation in a
 // separate pass); whisper3 reads whisper2's DFT-25 table
 // --------------------------------------------------------------------------------------
-static hipfeat_status setup_whisper3(hipfeat_plan* p, const PlanInputs& in) {
+static hipfeat_status setup_whisper3(hipfeat_plan* p, const PlanInputs& in, const float* d_cs) {
   const WaveAutoTables t = build_whisper3_tables(in, {kW3PRowStride, kW3MaxSets, kW3Steps, kW3Waves, kW3Region}, kW3Span, kW3Tail);
   if (!t.fits || t.lds > 80 * 1024) return HIPFEAT_OK;  // two workgroups of 8 waves per CU or nothing
   const void* fn = t.w_nsets == 2 ? entry<whisper3_kernel<2>>() : entry<whisper3_kernel<3>>();
+  Whisper3Params q{};
+  if (hipfeat_status bad = fill_wave_autonomous(q, p, t)) return bad;
+  q.cs = d_cs;
   // 8 waves x 8 rounds x 4 frames = 256 frames per workgroup
-  return claim_wave_auto(p, Route::Whisper3, fn, t, 4, 8, 16, strf("whisper3_kernel<%d> fft400=16x25 fused-norm", t.w_nsets));
+  return claim_wave_auto(p, Route::Whisper3, fn, t, q, 4, 8, 16, strf("whisper3_kernel<%d> fft400=16x25 fused-norm", t.w_nsets));
 }
 
 static hipfeat_status setup_whisper(hipfeat_plan* p, const PlanInputs& in) {
@@ -872,17 +879,21 @@ static hipfeat_status setup_whisper(hipfeat_plan* p, const PlanInputs& in) {
       route_env("HIPFEAT_FORCE_GENERIC"))
     return HIPFEAT_OK;
   const Whisper2Tables t = build_whisper2_tables(in);
+  Whisper2Params q{};
   hipfeat_status st;
-  if ((st = upload(&p->d_wh2_cs, t.cs.data(), t.cs.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_wh2_tw, t.tw.data(), t.tw.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_wh2_mel, t.mel.data(), t.mel.size())) != HIPFEAT_OK) return st;
-  if ((st = upload(&p->d_wh2_sched, t.sched.data(), t.sched.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.cs, t.cs.data(), t.cs.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.tw, t.tw.data(), t.tw.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.mel_a, t.mel.data(), t.mel.size())) != HIPFEAT_OK) return st;
+  if ((st = upload(p->uploads, q.sched, t.sched.data(), t.sched.size())) != HIPFEAT_OK) return st;
   const char* v = route_env("HIPFEAT_WHISPER_VARIANT");
   if (!(v && v[0] == '2')) {  // HIPFEAT_WHISPER_VARIANT=2: whisper2 (tests compare the two)
-    if ((st = setup_whisper3(p, in)) != HIPFEAT_OK || p->route == Route::Whisper3) return st;
+    if ((st = setup_whisper3(p, in, q.cs)) != HIPFEAT_OK || p->route == Route::Whisper3) return st;
   }
+  q.window = std::get<GenericParams>(p->params).window;
+  q.M = c.num_filters;
+  q.mel_floor = c.mel_floor;
   p->fpb = 16 * kW2TilesPerBlock;
-  if ((st = claim(p, Route::Whisper2, entry<whisper2_kernel>(), 256, 0)) != HIPFEAT_OK) return st;
+  if ((st = claim(p, Route::Whisper2, entry<whisper2_kernel>(), 256, 0, q)) != HIPFEAT_OK) return st;
   p->kernel_name = strf("whisper_kernel2 fft400=16x25 mel_chunks=%d+%d+%d+%d blocks/CU=%d", t.load[0], t.load[1], t.load[2], t.load[3], p->blocks_per_cu);
   return HIPFEAT_OK;
 }
@@ -916,8 +927,16 @@ static hipfeat_status setup_fft2048c(hipfeat_plan* p, const PlanInputs& in) {
                                   : (t.w12 ? entry<fft2048c_kernel<19, false, 52, 28, 16, true>>() : entry<fft2048c_kernel<19, false, 52, 28, 16>>()))
                    : odd ? (nrows == 18 ? entry<fft2048c_kernel<18, true>>() : entry<fft2048c_kernel<32, true>>())
                          : (nrows == 19 ? entry<fft2048c_kernel<19, false>>() : entry<fft2048c_kernel<32, false>>());
-  p->x_waves = t.waves;
-  return claim_wave_auto(p, Route::Fft2048c, fn, t, 2, 8, 64,
+  Fft2048cParams q{};
+  hipfeat_status st = fill_wave_autonomous(q, p, t);
+  if (st == HIPFEAT_OK && !t.twp.empty()) st = upload(p->uploads, q.twp, t.twp.data(), t.twp.size());
+  if (st != HIPFEAT_OK) return st;
+  fill_frames(q, p, t);
+  fill_sets(q, t);
+  q.waves = t.waves;
+  q.tws_off = t.tws_off;
+  q.tw32_off = t.tw32_off;
+  return claim_wave_auto(p, Route::Fft2048c, fn, t, q, 2, 8, 64,
                          strf("fft2048c_kernel<%d,%d> fbank%s waves=%d", nrows, (int)odd, t.fixed ? " fixed-schedule" : "", t.waves));
 }
 
@@ -942,11 +961,9 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
   if (!p) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
   p->cfg = *cfg;
   p->device = device;
-  p->K = fft / 2 + 1;
-  p->pow2 = (fft & (fft - 1)) == 0 && fft >= 2;
-  p->H = p->pow2 ? fft / 2 : 0;
-  p->log2H = 0;
-  while (p->pow2 && (1 << p->log2H) < p->H) ++p->log2H;
+  const int K = fft / 2 + 1;
+  const bool pow2 = (fft & (fft - 1)) == 0 && fft >= 2;
+  const int H = pow2 ? fft / 2 : 0;
   p->npad_left = (whisper || librosa) ? N / 2 : (cfg->snip_edges ? 0 : (N - shift) / 2);
   const int M = need_mel ? cfg->num_filters : 0;
   const int C = cfg->kind == HIPFEAT_MFCC ? cfg->num_ceps : 0;
@@ -963,21 +980,23 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     return s;
   };
 
-  const std::vector<float2> tw = fft_twiddles(fft, p->pow2 ? p->H : fft);
-  if ((st = upload(&p->d_tw, tw.data(), tw.size())) != HIPFEAT_OK) return bail(st);
-  if ((st = upload(&p->d_window, h_window, (size_t)N)) != HIPFEAT_OK) return bail(st);
+  // the generic kernel's Params: they stay unless a specialised kernel claims the plan, and the setups read the tables they share from them
+  GenericParams& gp = std::get<GenericParams>(p->params);
+  const std::vector<float2> tw = fft_twiddles(fft, pow2 ? H : fft);
+  if ((st = upload(p->uploads, gp.tw, tw.data(), tw.size())) != HIPFEAT_OK) return bail(st);
+  if ((st = upload(p->uploads, gp.window, h_window, (size_t)N)) != HIPFEAT_OK) return bail(st);
   if (need_mel) {
-    if ((st = upload(&p->d_mel, h_mel, (size_t)p->K * M)) != HIPFEAT_OK) return bail(st);
+    if ((st = upload(p->uploads, gp.mel, h_mel, (size_t)K * M)) != HIPFEAT_OK) return bail(st);
     std::vector<int2> rng(M);  // band of each filter: [first non-zero bin, last non-zero bin + 1)
     for (int j = 0; j < M; ++j) {
-      const MelBand b = mel_band(h_mel, M, p->K, j, j + 1);
+      const MelBand b = mel_band(h_mel, M, K, j, j + 1);
       rng[j] = make_int2(b.lo, b.hi);
     }
-    if ((st = upload(&p->d_mel_range, rng.data(), rng.size())) != HIPFEAT_OK) return bail(st);
+    if ((st = upload(p->uploads, gp.mel_range, rng.data(), rng.size())) != HIPFEAT_OK) return bail(st);
   }
   if (C) {
-    if ((st = upload(&p->d_dct, h_dct, (size_t)M * C)) != HIPFEAT_OK) return bail(st);
-    if (cfg->apply_lifter && (st = upload(&p->d_lifter, h_lifter, (size_t)C)) != HIPFEAT_OK) return bail(st);
+    if ((st = upload(p->uploads, gp.dct, h_dct, (size_t)M * C)) != HIPFEAT_OK) return bail(st);
+    if (cfg->apply_lifter && (st = upload(p->uploads, gp.lifter, h_lifter, (size_t)C)) != HIPFEAT_OK) return bail(st);
   }
 
   // LDS carve-up of the generic kernel.  Frames per workgroup: the largest of 8/4/2 whose footprint stays <= 21 KB
@@ -987,13 +1006,13 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
   auto carve = [&](int fpb) {
     auto al = [](int v) { return (v + 3) & ~3; };
     p->fpb = fpb;
-    p->span = (fpb - 1) * shift + N;
-    p->off_z = al(p->span);
-    p->off_p = p->off_z + al(fpb * fft);
-    p->off_tw = p->off_p + al(fpb * p->K);
-    p->off_stat = p->off_tw + (p->pow2 ? al(2 * std::max(p->H, 1)) : 0);
-    p->off_mel = p->off_stat + al(2 * fpb);
-    const int end = p->off_mel + al(fpb * std::max(M, 1));
+    gp.span = (fpb - 1) * shift + N;
+    gp.off_z = al(gp.span);
+    gp.off_p = gp.off_z + al(fpb * fft);
+    gp.off_tw = gp.off_p + al(fpb * K);
+    gp.off_stat = gp.off_tw + (pow2 ? al(2 * std::max(H, 1)) : 0);
+    gp.off_mel = gp.off_stat + al(2 * fpb);
+    const int end = gp.off_mel + al(fpb * std::max(M, 1));
     p->lds = (size_t)end * sizeof(float);
     return p->lds;
   };
@@ -1006,7 +1025,23 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     if (carve(pick) > 160 * 1024) p->fpb = 0;
   }
   if (p->fpb < 1) return bail(fail(HIPFEAT_ERR_UNSUPPORTED, "configuration does not fit in LDS"));
-  // the generic kernel's launch: it stays unless a specialised kernel claims the plan
+  gp.N = N;
+  gp.shift = shift;
+  gp.fft = fft;
+  gp.H = H;
+  while (pow2 && (1 << gp.log2H) < H) ++gp.log2H;
+  gp.K = K;
+  gp.M = cfg->num_filters;
+  gp.C = cfg->num_ceps;
+  gp.kind = (whisper || librosa) ? (int)HIPFEAT_FBANK : cfg->kind;  // same epilogue with log10; Whisper: launch()'s post-pass finishes it
+  gp.flags = energy_flags(*cfg) | (pow2 ? F_POW2 : 0) | ((whisper || librosa) ? (F_CENTER | F_LOG10) : 0);
+  gp.fpb = p->fpb;
+  gp.npad_left = p->npad_left;
+  gp.preemph = cfg->preemph_coeff;
+  gp.log_energy_floor = log_energy_floor(cfg->energy_floor);
+  gp.mel_floor = cfg->mel_floor;
+  gp.log_offset = cfg->log_offset;
+  // ... and its launch
   p->fn = reinterpret_cast<const void*>(&generic_kernel);
   p->block = 256;
   if ((st = set_dynamic_lds(p->fn, p->lds)) != HIPFEAT_OK) return bail(st);
@@ -1017,7 +1052,7 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_plan_create(const hipfeat_config* 
     return st == HIPFEAT_OK && p->route == Route::Generic;
   };
   PlanInputs in;
-  in.N = N, in.shift = shift, in.K = p->K, in.M = M, in.C = C;
+  in.N = N, in.shift = shift, in.K = K, in.M = M, in.C = C;
   in.window = h_window, in.mel = h_mel, in.dct = h_dct, in.lifter = cfg->apply_lifter ? h_lifter : nullptr;
   if (unclaimed(setup_fft512(p, in)) && unclaimed(setup_whisper(p, in)) && unclaimed(setup_fft256(p, in)) && unclaimed(setup_fft1024c(p, in)) &&
       unclaimed(setup_fft2048c(p, in)))
@@ -1224,37 +1259,33 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_layout_num_frames(const hipfeat_la
 // --------------------------------------------------------------------------------------
 // launch
 // --------------------------------------------------------------------------------------
-// Fields of the wave-autonomous families (fft512c / fft256c, fft1024c, fft2048c, whisper3): the batch, one LDS constants image and
-// workgroups of `rounds` rounds of frames.
 template <typename P>
-static void fill_wave_autonomous(P& p, const hipfeat_plan* plan, const hipfeat_layout* lay, const float* d_wave, float* d_out) {
+constexpr bool kWaveAutonomous = std::is_same_v<P, Whisper3Params> || std::is_same_v<P, Fft512cParams> || std::is_same_v<P, Fft1024cParams> || std::is_same_v<P, Fft2048cParams>;
+
+// What a launch binds in its copy of the plan's Params: the buffers and the layout, in the fields the family has
+template <typename P>
+static void bind_launch(P& p, const hipfeat_plan* plan, const hipfeat_layout* lay, const float* d_wave, float* d_out) {
   p.wave = d_wave;
   p.out = d_out;
   p.cuts = lay->d_cuts;
-  p.shared_consts = plan->d_c_shared;
-  p.shared_floats = plan->c_shared_floats;
-  p.wtab_off = plan->c_wtab_off;
-  p.ltab_off = plan->c_ltab_off;
   p.out_stride = lay->out_row_stride;
   p.num_cuts = (int32_t)lay->batch;
   p.uniform_bpc = lay->uniform_bpc;
-  p.frames_per_block = lay->fpb;
-  p.rounds = lay->fpb / plan->fpb_unit;
-  p.M = plan->cfg.num_filters;
-  p.mel_floor = plan->cfg.mel_floor;
-}
-
-// Frame geometry of the wave-autonomous FFT kernels (fft512c / fft256c plans have neither magnitudes nor centred framing: their
-// flags come down to F_REMOVE_DC).
-template <typename P>
-static void fill_frames(P& p, const hipfeat_plan* plan) {
-  const hipfeat_config& c = plan->cfg;
-  p.N = c.frame_length;
-  p.shift = c.frame_shift;
-  p.npad_left = plan->npad_left;
-  p.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LIBROSA_FBANK ? (F_CENTER | F_LOG10) : 0);
-  p.preemph = c.preemph_coeff;
-  p.xs_floats = plan->c_xs_floats;
+  if constexpr (kWaveAutonomous<P>) {  // workgroups of the layout's rounds of frames
+    p.frames_per_block = lay->fpb;
+    p.rounds = lay->fpb / plan->fpb_unit;
+  }
+  if constexpr (std::is_same_v<P, Fft512cParams>) {
+    if (plan->route == Route::Fft512c) p.total_quads = (int32_t)lay->total_quads;
+  }
+  if constexpr (std::is_same_v<P, Whisper3Params>) {
+    p.total_blocks = (int32_t)lay->total_blocks;
+    if (lay->d_norm) {
+      unsigned char* slot = lay->d_norm + (size_t)(lay->norm_next.fetch_add(1u) % (unsigned)lay->norm_slots) * norm_slot_bytes(lay);
+      p.wg_stat = reinterpret_cast<float*>(slot);
+      p.cut_done = reinterpret_cast<uint32_t*>(slot + 2 * (size_t)lay->total_blocks * sizeof(float));
+    }
+  }
 }
 
 static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay, const float* d_wave, float* d_out,
@@ -1264,152 +1295,15 @@ static hipfeat_status launch(const hipfeat_plan* plan, const hipfeat_layout* lay
   if ((plan->fpb_unit > 0 ? (lay->fpb_unit != plan->fpb_unit || lay->fpb % plan->fpb_unit != 0) : lay->fpb != plan->fpb) || lay->device != plan->device)
     return fail(HIPFEAT_ERR_INVALID, "layout was created for a different plan");
   const hipfeat_config& c = plan->cfg;
-  const bool whisper = c.kind == HIPFEAT_WHISPER, librosa = c.kind == HIPFEAT_LIBROSA_FBANK;
-  // the kernel's one argument: the Params struct of the plan's family
-  GenericParams gp{};
-  WaveParams wp{};
-  Whisper2Params w2{};
-  Whisper3Params w3{};
-  Fft512Params bp{};
-  Fft512cParams cp{};
-  Fft1024cParams kp{};
-  Fft2048cParams xp{};
-  void* arg = nullptr;
-  switch (plan->route) {
-    case Route::Generic:
-      gp.wave = d_wave;
-      gp.out = d_out;
-      gp.cuts = lay->d_cuts;
-      gp.window = plan->d_window;
-      gp.tw = plan->d_tw;
-      gp.mel = plan->d_mel;
-      gp.mel_range = plan->d_mel_range;
-      gp.dct = plan->d_dct;
-      gp.lifter = plan->d_lifter;
-      gp.out_stride = lay->out_row_stride;
-      gp.num_cuts = (int32_t)lay->batch;
-      gp.uniform_bpc = lay->uniform_bpc;
-      gp.N = c.frame_length;
-      gp.shift = c.frame_shift;
-      gp.fft = c.fft_length;
-      gp.H = plan->H;
-      gp.log2H = plan->log2H;
-      gp.K = plan->K;
-      gp.M = c.num_filters;
-      gp.C = c.num_ceps;
-      gp.kind = (whisper || librosa) ? (int)HIPFEAT_FBANK : c.kind;  // same epilogue with log10; Whisper: the post-pass below finishes it
-      gp.flags = energy_flags(c) | (plan->pow2 ? F_POW2 : 0) | ((whisper || librosa) ? (F_CENTER | F_LOG10) : 0);
-      gp.fpb = plan->fpb;
-      gp.npad_left = plan->npad_left;
-      gp.preemph = c.preemph_coeff;
-      gp.log_energy_floor = log_energy_floor(c.energy_floor);
-      gp.mel_floor = c.mel_floor;
-      gp.log_offset = c.log_offset;
-      gp.span = plan->span;
-      gp.off_z = plan->off_z;
-      gp.off_p = plan->off_p;
-      gp.off_tw = plan->off_tw;
-      gp.off_stat = plan->off_stat;
-      gp.off_mel = plan->off_mel;
-      arg = &gp;
-      break;
-    case Route::Wave:
-      wp.wave = d_wave;
-      wp.out = d_out;
-      wp.cuts = lay->d_cuts;
-      fill_wave_front(wp, c, WaveFront{plan->d_window, plan->d_tw, plan->d_mel_t, plan->d_dct, plan->d_lifter, plan->wave_blob_floats, plan->wave_dct_in_lds, plan->lds});
-      wp.out_stride = lay->out_row_stride;
-      wp.num_cuts = (int32_t)lay->batch;
-      wp.uniform_bpc = lay->uniform_bpc;
-      wp.frames_per_wave = plan->fpb / 4;
-      wp.npad_left = plan->npad_left;
-      arg = &wp;
-      break;
-    case Route::Whisper2:
-      w2.wave = d_wave;
-      w2.out = d_out;
-      w2.cuts = lay->d_cuts;
-      w2.window = plan->d_window;
-      w2.cs = plan->d_wh2_cs;
-      w2.tw = plan->d_wh2_tw;
-      w2.mel_a = plan->d_wh2_mel;
-      w2.out_stride = lay->out_row_stride;
-      w2.num_cuts = (int32_t)lay->batch;
-      w2.uniform_bpc = lay->uniform_bpc;
-      w2.M = c.num_filters;
-      w2.mel_floor = c.mel_floor;
-      w2.sched = plan->d_wh2_sched;
-      arg = &w2;
-      break;
-    case Route::Whisper3:
-      fill_wave_autonomous(w3, plan, lay, d_wave, d_out);
-      w3.cs = plan->d_wh2_cs;
-      w3.total_blocks = (int32_t)lay->total_blocks;
-      if (lay->d_norm) {
-        unsigned char* slot = lay->d_norm + (size_t)(lay->norm_next.fetch_add(1u) % (unsigned)lay->norm_slots) * norm_slot_bytes(lay);
-        w3.wg_stat = reinterpret_cast<float*>(slot);
-        w3.cut_done = reinterpret_cast<uint32_t*>(slot + 2 * (size_t)lay->total_blocks * sizeof(float));
-      }
-      arg = &w3;
-      break;
-    case Route::Fft512c:
-      cp.dct_tab = plan->d_dct_consts;
-      cp.C = c.num_ceps;
-      cp.total_quads = (int32_t)lay->total_quads;
-      [[fallthrough]];
-    case Route::Fft256c:
-      fill_wave_autonomous(cp, plan, lay, d_wave, d_out);
-      fill_frames(cp, plan);
-      arg = &cp;
-      break;
-    case Route::Fft1024c:
-      fill_wave_autonomous(kp, plan, lay, d_wave, d_out);
-      fill_frames(kp, plan);
-      kp.nsets = plan->w_nsets;
-      for (int s2 = 0; s2 < kWMaxSets; ++s2) kp.steps[s2] = plan->w_steps[s2], kp.step0[s2] = plan->w_step0[s2];
-      arg = &kp;
-      break;
-    case Route::Fft2048c:
-      fill_wave_autonomous(xp, plan, lay, d_wave, d_out);
-      fill_frames(xp, plan);
-      xp.twp = plan->d_x_twp;
-      xp.waves = plan->x_waves;
-      xp.tws_off = plan->x_tws_off;
-      xp.tw32_off = plan->x_tw32_off;
-      xp.nsets = plan->w_nsets;
-      for (int s2 = 0; s2 < kXMaxSets; ++s2) xp.steps[s2] = plan->w_steps[s2], xp.step0[s2] = plan->w_step0[s2];
-      arg = &xp;
-      break;
-    case Route::Fft512b:
-    case Route::Fft256b:
-      bp.wave = d_wave;
-      bp.out = d_out;
-      bp.cuts = lay->d_cuts;
-      bp.lds_consts = plan->d_lds_consts;
-      bp.mel_a = plan->d_mel_a4;
-      bp.work = plan->d_work;
-      bp.out_stride = lay->out_row_stride;
-      bp.num_cuts = (int32_t)lay->batch;
-      bp.uniform_bpc = lay->uniform_bpc;
-      bp.tiles_per_block = plan->tiles_per_block;
-      bp.N = c.frame_length;
-      bp.shift = c.frame_shift;
-      bp.npad_left = plan->npad_left;
-      bp.M = c.num_filters;
-      bp.flags = (c.remove_dc_offset ? F_REMOVE_DC : 0) | (c.use_fft_mag ? F_FFT_MAG : 0) | (c.kind == HIPFEAT_LOG_SPECTROGRAM ? F_LOG_SPEC : 0);
-      bp.log_offset = c.log_offset;
-      bp.preemph = c.preemph_coeff;
-      bp.mel_floor = c.mel_floor;
-      bp.xs_floats = plan->xs_floats;
-      bp.const_floats = plan->const_floats;
-      bp.dct_consts = plan->d_dct_consts;
-      bp.C = c.num_ceps;
-      bp.lm_stride = plan->lm_stride;
-      bp.dct_groups = plan->dct_groups;
-      bp.dct_floats = plan->dct_floats;
-      arg = &bp;
-      break;
-  }
+  const bool whisper = c.kind == HIPFEAT_WHISPER;
+  // the kernel's one argument: a copy of the plan's Params with this call bound
+  KernelParams params = plan->params;
+  void* arg = std::visit(
+      [&](auto& p) -> void* {
+        bind_launch(p, plan, lay, d_wave, d_out);
+        return &p;
+      },
+      params);
   const bool far = plan->fn_far && lay->out_row_stride >= kMel4WideMaxStride;
   const void* fn = lay->flat && plan->fn_flat ? (far ? plan->fn_flat_far : plan->fn_flat) : (far ? plan->fn_far : plan->fn);
   void* args[] = {arg};
@@ -2980,19 +2874,17 @@ struct hipfeat_stream {
   const void* fn = nullptr;
   bool features = false;
   StftFront front;        // frames / spectrum: the STFT front end on the two-span source
-  hipfeat_config fcfg{};  // features: the wave kernel on tables of its own
-  WaveFront wave;
+  hipfeat_config fcfg{};  // features: the wave kernel on tables of its own (`uploads`), its Params complete but for the call's buffers
+  WaveParams wave{};
+  size_t wave_lds = 0;
+  std::vector<void*> uploads;
 };
 
 extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_destroy(hipfeat_stream* s) {
   if (!s) return HIPFEAT_OK;
   DeviceGuard g(s->device);
   stft_front_free(s->front);
-  (void)hipFree(s->wave.d_window);
-  (void)hipFree(s->wave.d_tw);
-  (void)hipFree(s->wave.d_mel_blob);
-  (void)hipFree(s->wave.d_dct);
-  (void)hipFree(s->wave.d_lifter);
+  free_uploads(s->uploads);
   delete s;
   return HIPFEAT_OK;
 }
@@ -3042,17 +2934,17 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_create_features(cons
   s->fcfg = *cfg;
   s->device = device;
   s->fn = for_n1(fft / 128, [](auto n) { return entry<wave_stream_kernel<decltype(n)::value>>(); });
-  WaveFront& w = s->wave;
-  w.blob_floats = (int)t.blob.size();
-  w.dct_in_lds = t.dct_in_lds;
-  w.lds = t.lds;
+  WaveParams& w = s->wave;
+  fill_wave_front(w, *cfg, t);
+  w.frames_per_wave = kStftFramesPerWave;  // (npad_left stays 0: V starts at its first frame)
+  s->wave_lds = t.lds;
   const std::vector<float2> tw = fft_twiddles(fft, fft / 2);
-  hipfeat_status st = upload(&w.d_window, h_window, (size_t)N);
-  if (st == HIPFEAT_OK) st = upload(&w.d_tw, tw.data(), tw.size());
-  if (st == HIPFEAT_OK && M > 0) st = upload(&w.d_mel_blob, t.blob.data(), t.blob.size());
-  if (st == HIPFEAT_OK && C > 0) st = upload(&w.d_dct, h_dct, (size_t)M * C);
-  if (st == HIPFEAT_OK && C > 0 && cfg->apply_lifter) st = upload(&w.d_lifter, h_lifter, (size_t)C);
-  if (st == HIPFEAT_OK) st = set_dynamic_lds(s->fn, w.lds);
+  hipfeat_status st = upload(s->uploads, w.window, h_window, (size_t)N);
+  if (st == HIPFEAT_OK) st = upload(s->uploads, w.tw, tw.data(), tw.size());
+  if (st == HIPFEAT_OK && M > 0) st = upload(s->uploads, w.mel_blob, t.blob.data(), t.blob.size());
+  if (st == HIPFEAT_OK && C > 0) st = upload(s->uploads, w.dct, h_dct, (size_t)M * C);
+  if (st == HIPFEAT_OK && C > 0 && cfg->apply_lifter) st = upload(s->uploads, w.lifter, h_lifter, (size_t)C);
+  if (st == HIPFEAT_OK) st = set_dynamic_lds(s->fn, s->wave_lds);
   if (st != HIPFEAT_OK) {
     hipfeat_stream_destroy(s);
     return st;
@@ -3127,14 +3019,12 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* 
   a.blocks_per_row = bpr;
   a.shift = shift;
   // the params of either kernel; npad_left stays 0: V starts at its first frame
-  WaveParams wp{};
+  WaveParams wp = s->wave;
   StftParams sp{};
   void* args[] = {nullptr, &a};
   if (s->features) {
-    fill_wave_front(wp, fc, s->wave);
     wp.out = d_out;
     wp.out_stride = width;
-    wp.frames_per_wave = kStftFramesPerWave;
     args[0] = &wp;
   } else {
     fill_stft_front(sp, s->front);
@@ -3144,7 +3034,7 @@ extern "C" HIPFEAT_STREAM_API hipfeat_status hipfeat_stream_run(hipfeat_stream* 
     sp.blocks_per_row = bpr;
     args[0] = &sp;
   }
-  const size_t lds = s->features ? s->wave.lds : s->front.lds;
+  const size_t lds = s->features ? s->wave_lds : s->front.lds;
   DeviceGuard g(s->device);
   set_lds_poison(lds);
   (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, lds, (hipStream_t)stream);
