@@ -42,7 +42,7 @@ extern "C" {
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
  * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES, _SINC_SIGNATURES,
- * _FEATMIX_SIGNATURES, _STATS_SIGNATURES and _STFT_SIGNATURES next to _SIGNATURES). */
+ * _FEATMIX_SIGNATURES, _STATS_SIGNATURES, _STFT_SIGNATURES and _CHANNELS_SIGNATURES next to _SIGNATURES). */
 #define HIPFEAT_COLLATE_API HIPFEAT_API
 #define HIPFEAT_FEATMIX_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
@@ -51,6 +51,7 @@ extern "C" {
 #define HIPFEAT_STFT_API HIPFEAT_API
 #define HIPFEAT_STREAM_API HIPFEAT_API
 #define HIPFEAT_GRAD_API HIPFEAT_API
+#define HIPFEAT_CHANNELS_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -473,6 +474,37 @@ HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_collate* collate
                                                         const int64_t* h_dst_offset, int64_t row_len, int32_t out_type, int64_t* h_info);
 HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collate* collate, int64_t ticket, const float* d_arena, int64_t arena_floats, void* d_out,
                                                        int64_t out_elements, void* stream);
+
+/* ---- collation of multi-channel cuts: (B, C, T) and the mono downmix (additive to ABI v8) --------------------------------------- */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_collate_plan_sources; as with hipfeat_level_* and hipfeat_collate_*, the
+ * version number did not change because nothing that existed changed.
+ *
+ * collate_audio (lhotse/dataset/collation.py:215-241) either downmixes a multi-channel cut to mono, audio.mean(dim=0) of its (C, T)
+ * samples, and collates (B, T), or collates (B, C, T) with all-zero rows for the channels a cut does not have.  Both are ONE launch of a
+ * second plan form of hipfeat_collate: output row r has k_r = h_first[r + 1] - h_first[r] >= 0 sources, each a run of h_src_len[r]
+ * float32 samples of the arena, source c at arena + h_src_offset[h_first[r] + c]; the row receives, from element h_dst_offset[r]
+ * (NULL = 0 for every row), per sample i
+ *   k = 0: nothing, the row is +0 everywhere;
+ *   k = 1: source 0, exactly the row of hipfeat_collate_plan (float32: a bit copy);
+ *   k >= 2: float32((0.0 + double(x_0[i]) + ... + double(x_{k-1}[i])) / double(k)): the sum in ascending source order in float64, one
+ *           float64 division, ONE rounding to nearest even (for sources whose float64 sum is exact, such as PCM samples, the correctly
+ *           rounded mean, which no float32 summation order is); binary16 / bfloat16 output converts that float32 value as it converts a
+ *           sample, so the result is .to(dtype) of the float32 mean.  NaN and Inf propagate by the IEEE rules.
+ * Every other element of the row is +0; what is written and what is not is as for hipfeat_collate_plan.  (B, T): one row per cut with
+ * its channels as sources.  (B, C, T): B * C rows of one source, or none.
+ *
+ * hipfeat_collate_plan_sources (host only).  h_first[num_rows + 1], h_src_offset[h_first[num_rows]], h_src_len[num_rows]; h_info[4] as
+ * hipfeat_collate_plan: {ticket, floats the arena must hold (the sources of rows with h_src_len == 0 do not count), elements `out` must
+ * hold (num_rows * row_len), work items}.  h_first that does not start at 0 or decreases, a negative offset or length, row_len < 0,
+ * num_rows < 0, h_dst_offset + h_src_len > row_len, num_rows * row_len or h_src_offset + h_src_len beyond INT64_MAX, an unknown
+ * out_type, a 17th plan while 16 are planned and not yet run: HIPFEAT_ERR_INVALID; a row of more than 32 sources:
+ * HIPFEAT_ERR_UNSUPPORTED; nothing is planned.  The tickets are those of hipfeat_collate_plan: hipfeat_collate_run runs a ticket of
+ * either form, with the same checks.
+ */
+HIPFEAT_CHANNELS_API hipfeat_status hipfeat_collate_plan_sources(hipfeat_collate* collate, int64_t num_rows, const int64_t* h_first,
+                                                                 const int64_t* h_src_offset, const int64_t* h_src_len, const int64_t* h_dst_offset,
+                                                                 int64_t row_len, int32_t out_type, int64_t* h_info);
 
 /* ---- sinc resampling without a filter bank: any rate pair, every row with its own (additive to ABI v8) ------------------------ */
 /*

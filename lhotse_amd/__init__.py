@@ -18,6 +18,7 @@ from .extractors import (  # noqa: F401
 from .augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_arena, reverb_tail_floats  # noqa: F401,E402
 from .augmentation import HipClipping, HipLevel, HipVolume, get_or_create_level, level_in_arena  # noqa: F401,E402
 from .augmentation import COLLATE_TILE, HipCollator, collate_in_arena, get_or_create_collator, left_pad_offsets  # noqa: F401,E402
+from .augmentation import COLLATE_MAX_SOURCES, collate_sources_in_arena, collate_sources_layout  # noqa: F401,E402
 from .augmentation import resample_in_arena, resample_layout, resampled_tail_floats  # noqa: F401,E402
 from .augmentation import HipSincResampler, get_or_create_sinc, sinc_in_arena  # noqa: F401,E402
 from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
@@ -94,6 +95,9 @@ __all__ = [
     "COLLATE_TILE",
     "HipCollator",
     "collate_in_arena",
+    "COLLATE_MAX_SOURCES",
+    "collate_sources_in_arena",
+    "collate_sources_layout",
     "get_or_create_collator",
     "left_pad_offsets",
     "FusedAudioBatch",

@@ -141,6 +141,13 @@ _COLLATE_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
     "hipfeat_collate_run": ("int", ["hipfeat_collate*", "int64_t", "const float*", "int64_t", "void*", "int64_t", "void*"]),
 }
+# Likewise (HIPFEAT_CHANNELS_API in the header): the sources form of the collate plan.
+_CHANNELS_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_collate_plan_sources": (
+        "int",
+        ["hipfeat_collate*", "int64_t", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "int64_t", "int32_t", "int64_t*"],
+    ),
+}
 # Likewise (HIPFEAT_SINC_API in the header).
 _SINC_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     "hipfeat_sinc_create": ("int", ["int32_t", "hipfeat_sinc**"]),
@@ -214,7 +221,7 @@ _GRAD_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     "hipfeat_grad_destroy": ("int", ["hipfeat_grad*"]),
 }
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
-                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES}
+                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -326,7 +333,7 @@ class _CffiBackend:
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
                         .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
-                        .replace("HIPFEAT_GRAD_API ", ""))
+                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

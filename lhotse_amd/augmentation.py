@@ -1108,6 +1108,21 @@ class HipCollator(_ArenaHandle):
                            _lib.addr(info))
         return int(info[0]), info
 
+    def plan_sources(self, first, src_offsets, src_lens, dst_offsets, row_len: int, dtype: torch.dtype = torch.float32):
+        """The sources form, host only: row ``r`` is the mean of the ``first[r + 1] - first[r]`` runs of ``src_lens[r]`` samples at
+        ``src_offsets[first[r] : first[r + 1]]`` -> (ticket, info) as ``plan``; ``run`` takes the ticket."""
+        if dtype not in _COLLATE_TYPES:
+            raise ValueError(f"collate: float32, float16 or bfloat16 output, got {dtype}")
+        fi, so, sl = _lib.i64(first), _lib.i64(src_offsets), _lib.i64(src_lens)
+        do = None if dst_offsets is None else _lib.i64(dst_offsets)
+        if len(fi) != len(sl) + 1 or (do is not None and len(do) != len(sl)) or int(fi[-1]) != len(so):
+            raise ValueError("collate tables: rows + 1 entries of `first` that end at the number of sources, one length per row")
+        info = np.zeros(4, dtype=np.int64)
+        with self._lock:
+            self.lib.check("hipfeat_collate_plan_sources", self.handle, len(sl), _lib.addr(fi), _lib.addr(so), _lib.addr(sl), _lib.addr(do),
+                           int(row_len), _COLLATE_TYPES[dtype], _lib.addr(info))
+        return int(info[0]), info
+
     def run(self, ticket: int, arena: torch.Tensor, out: torch.Tensor, stream: Optional[int] = None) -> None:
         assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1 and arena.device == self.device
         assert out.is_contiguous() and out.device == self.device
@@ -1156,6 +1171,76 @@ def collate_in_arena(arena: torch.Tensor, offsets, lengths, row_len: Optional[in
     if collator is None:
         collator = get_or_create_collator(arena.device)
     ticket, info = collator.plan(so, sl, None if dst_offsets is None else do, row_len, dtype)
+    collator.run(ticket, arena, res)
+    return res, sl
+
+
+COLLATE_MAX_SOURCES = 32  # sources of one row of the sources form (kCoMaxSources)
+
+
+def collate_sources_layout(arena_floats: int, first, src_offsets, lengths, row_len: Optional[int] = None, dst_offsets=None):
+    """The host arithmetic of ``collate_sources_in_arena`` -> ``(first, src_offsets, lengths, dst_offsets, row_len)`` as int64; raises
+    ``ValueError`` for what no launch could serve (``first`` that does not start at 0, decreases or does not end at the number of
+    sources, more than ``COLLATE_MAX_SOURCES`` sources in a row, tables of unequal length, negative entries, a row that does not fit
+    ``row_len`` or a source that does not fit the arena)."""
+    fi, so, sl = _lib.i64(first), _lib.i64(src_offsets), _lib.i64(lengths)
+    if fi.ndim != 1 or so.ndim != 1 or sl.ndim != 1 or len(fi) != len(sl) + 1:
+        raise ValueError("collate tables: one length per row and rows + 1 entries of `first`")
+    k = np.diff(fi)
+    if int(fi[0]) != 0 or (len(k) and int(k.min()) < 0) or int(fi[-1]) != len(so):
+        raise ValueError("collate tables: `first` starts at 0, does not decrease and ends at the number of sources")
+    if len(k) and int(k.max()) > COLLATE_MAX_SOURCES:
+        raise ValueError(f"a row of {int(k.max())} sources: a row takes at most {COLLATE_MAX_SOURCES}")
+    if row_len is None:
+        row_len = int(sl.max()) if len(sl) else 0
+    row_len = int(row_len)
+    do = np.zeros(len(sl), dtype=np.int64) if dst_offsets is None else _lib.i64(dst_offsets)
+    if do.shape != sl.shape:
+        raise ValueError("collate tables: one destination offset per row")
+    if row_len < 0 or (len(so) and int(so.min()) < 0) or (len(sl) and (int(sl.min()) < 0 or int(do.min()) < 0)):
+        raise ValueError("collate tables: negative offset, length or row length")
+    if len(sl) and int((do + sl).max()) > row_len:
+        raise ValueError(f"a row reaches to element {int((do + sl).max())} of a row of {row_len}")
+    ends = so + np.repeat(sl, k)
+    read = np.repeat(sl, k) > 0
+    need = int(ends[read].max()) if read.any() else 0
+    if need > int(arena_floats):
+        raise ValueError(f"arena too small: {int(arena_floats)} floats, the sources reach to {need}")
+    return fi, so, sl, do, row_len
+
+
+def collate_sources_in_arena(arena: torch.Tensor, first, src_offsets, lengths, row_len: Optional[int] = None, dst_offsets=None,
+                             dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
+                             collator: Optional[HipCollator] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """``collate_in_arena`` for rows of SEVERAL sources: the channel handling of ``collate_audio`` (lhotse/dataset/collation.py:215-241) in
+    ONE launch.  Row ``r`` has the ``k = first[r + 1] - first[r]`` sources ``src_offsets[first[r] : first[r + 1]]``, each ``lengths[r]``
+    samples of ``arena``: ``k = 0`` -- the row is +0; ``k = 1`` -- the row ``collate_in_arena`` writes, bit for bit; ``k >= 2`` -- per sample
+    ``float32((0.0 + float64(x_0) + ... + float64(x_{k-1})) / float64(k))``, the sum in ascending source order, one division, one rounding
+    (the mono downmix ``audio.mean(dim=0)``, correctly rounded wherever the float64 sum is exact, as it is for PCM samples), then
+    ``.to(dtype)`` of that value.  The mono downmix of a batch is one row per cut with its channels as sources; its ``(B, C, T)`` form is
+    ``B * C`` rows of one source or none -- reshape the result.  ``row_len``, ``dst_offsets``, ``dtype``, ``out`` and the result as for
+    ``collate_in_arena``.  One launch on the current stream, no memset, no device -> host copy."""
+    assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
+    if dtype not in _COLLATE_TYPES:
+        raise ValueError(f"collate: float32, float16 or bfloat16 output, got {dtype}")
+    fi, so, sl, do, row_len = collate_sources_layout(arena.numel(), first, src_offsets, lengths, row_len, dst_offsets)  # (before anything is planned)
+    rows = len(sl)
+    if out is not None:
+        if out.dtype != dtype or out.device != arena.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor on {arena.device}")
+        if out.numel() < rows * row_len:
+            raise ValueError(f"out too small: {out.numel()} elements, {rows} rows of {row_len} take {rows * row_len}")
+        a0, o0 = arena.data_ptr(), out.data_ptr()
+        if a0 < o0 + out.numel() * out.element_size() and o0 < a0 + arena.numel() * 4:  # (a plan that is never run would stay outstanding)
+            raise ValueError("out overlaps the arena")
+        res = out.view(-1)[: rows * row_len].view(rows, row_len)
+    else:
+        res = torch.empty((rows, row_len), dtype=dtype, device=arena.device)
+    if rows * row_len == 0:
+        return res, sl
+    if collator is None:
+        collator = get_or_create_collator(arena.device)
+    ticket, info = collator.plan_sources(fi, so, sl, None if dst_offsets is None else do, row_len, dtype)
     collator.run(ticket, arena, res)
     return res, sl
 

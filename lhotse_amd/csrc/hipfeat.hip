@@ -2444,6 +2444,25 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_plan(hipfeat_colla
   return HIPFEAT_OK;
 }
 
+// the sources form: a row is the mean of k >= 0 runs of the arena (collate_audio's mono_downmix, collation.py:215-241)
+extern "C" HIPFEAT_CHANNELS_API hipfeat_status hipfeat_collate_plan_sources(hipfeat_collate* c, int64_t num_rows, const int64_t* h_first,
+                                                                            const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                                           const int64_t* h_dst_offset, int64_t row_len, int32_t out_type,
+                                                                           int64_t* h_info) {
+  if (!c || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  CoPlan p = build_collate_sources_plan(num_rows, h_first, h_src_offset, h_src_len, h_dst_offset, row_len, out_type);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(c->mu);
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(c->tickets, "collations", &ticket)) return st;
+  const CoPlan& s = c->plans[ticket % kTicketSlots] = std::move(p);
+  h_info[0] = ticket;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.out_need;
+  h_info[3] = s.work_items;
+  return HIPFEAT_OK;
+}
+
 extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collate* c, int64_t ticket, const float* d_arena, int64_t arena_floats, void* d_out,
                                                                   int64_t out_elements, void* stream) {
   if (!c) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
@@ -2472,6 +2491,28 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
   DeviceGuard g(c->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = p.rows.size() * sizeof(CoRow);
+  // a flat 1-D grid over (row, tile); beyond 2^22 workgroups (2^34 elements) the workgroups stride
+  const unsigned grid = (unsigned)std::min<int64_t>(p.work_items, (int64_t)1 << 22);
+  if (p.sources) {  // the row table, and behind it the source offsets of all rows
+    const size_t src_bytes = p.srcs.size() * sizeof(int64_t);
+    HIP_TRY(stage(s, bytes + src_bytes, bytes + src_bytes, st, [&](unsigned char* h) {
+      std::memcpy(h, p.rows.data(), bytes);
+      if (src_bytes) std::memcpy(h + bytes, p.srcs.data(), src_bytes);
+    }));
+    CoMeanArgs m;
+    m.arena = reinterpret_cast<const uint32_t*>(d_arena);
+    m.out = d_out;
+    m.rows = static_cast<const CoRow*>(s.d);
+    m.srcs = reinterpret_cast<const int64_t*>(static_cast<const unsigned char*>(s.d) + bytes);
+    m.row_len = p.row_len;
+    m.tiles_per_row = p.tiles_per_row;
+    m.work_items = p.work_items;
+    if (p.out_type == kCoF32) hipLaunchKernelGGL(collate_mean_kernel<float>, dim3(grid), dim3(256), 0, st, m);
+    else if (p.out_type == kCoF16) hipLaunchKernelGGL(collate_mean_kernel<__half>, dim3(grid), dim3(256), 0, st, m);
+    else hipLaunchKernelGGL(collate_mean_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, m);
+    c->tickets.release(ticket);
+    return finish_launches(s, st, hipGetLastError(), "collate", kWaitedLaunch);
+  }
   HIP_TRY(stage(s, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, p.rows.data(), bytes); }));
   CoArgs a;
   a.arena = reinterpret_cast<const uint32_t*>(d_arena);
@@ -2480,8 +2521,6 @@ extern "C" HIPFEAT_COLLATE_API hipfeat_status hipfeat_collate_run(hipfeat_collat
   a.row_len = p.row_len;
   a.tiles_per_row = p.tiles_per_row;
   a.work_items = p.work_items;
-  // a flat 1-D grid over (row, tile); beyond 2^22 workgroups (2^34 elements) the workgroups stride
-  const unsigned grid = (unsigned)std::min<int64_t>(p.work_items, (int64_t)1 << 22);
   if (p.out_type == kCoF32) hipLaunchKernelGGL(collate_wave_kernel<float>, dim3(grid), dim3(256), 0, st, a);
   else if (p.out_type == kCoF16) hipLaunchKernelGGL(collate_wave_kernel<__half>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(collate_wave_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, a);

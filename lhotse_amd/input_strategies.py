@@ -68,6 +68,15 @@ Raw audio.  ``AudioSamples`` (lhotse/dataset/input_strategies.py:208-299) and ``
 place of the feature launch, ``HipAudioSamples`` the drop-in for ``AudioSamples``; ``return_audio_device=None`` (or a device) on
 ``HipOnTheFlyFeatures`` collates the audio of ``return_audio`` there too, instead of one blocking copy per cut and a host ``collate_vectors``.
 
+Multi-channel cuts.  ``collate_audio(..., mono_downmix=None | True | False)`` (lhotse/dataset/collation.py:215-241) downmixes a ``MultiCut`` with
+``audio.mean(dim=0)`` on the CPU or collates ``(B, C, T)``.  ``HipAudioSamples`` serves both (``gpu_channels``): every channel of a ``MultiCut``
+whose recording's transforms are ``[Resample]? [Speed]?`` (``pending_channel_chain``; padded to the right or to the left as well) is a row of its
+own in the arena and runs the chain like a mono cut, and ONE launch of the collate kernel's sources form
+(``lhotse_amd.augmentation.collate_sources_in_arena``) writes ``(B, Tmax)`` -- a row is the float64 sum of the cut's channels, divided once,
+rounded once -- or ``(B, Cmax, Tmax)`` with zero rows for the channels a cut does not have (``FusedAudioBatch.audio_of_channels``).  Mono cuts in
+such a batch keep their whole chain.  Other transforms on a multi-channel cut, a multi-channel track mixed with audio and more than 32 channels
+keep the reference's path for the batch.
+
 Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse works, constructing the classes does not.
 """
 from __future__ import annotations
@@ -134,6 +143,13 @@ def _collate_in_arena(arena, offsets, lengths, row_len, dtype):
     from .augmentation import collate_in_arena
 
     return collate_in_arena(arena, offsets, lengths, row_len=row_len, dtype=dtype)[0]
+
+
+def _collate_sources_in_arena(arena, first, src_offsets, lengths, row_len, dst_offsets, dtype):
+    """(indirection for the CPU stand-in of the tests) -> the dense (rows, row_len) tensor whose row r is the mean of its sources"""
+    from .augmentation import collate_sources_in_arena
+
+    return collate_sources_in_arena(arena, first, src_offsets, lengths, row_len=row_len, dst_offsets=dst_offsets, dtype=dtype)[0]
 
 
 def _is_plain(tracks) -> bool:
@@ -568,6 +584,63 @@ class FusedAudioBatch(_ArenaChain):
             arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sampling_rate)
             return self._collated(arena, cut_off, cut_len, wants)
 
+    def audio_of_channels(self, cuts_channels, factors: List[float], source_rates, wants: List[int], sampling_rate: int,
+                          mono_downmix: Optional[bool] = None, offsets=None, totals=None):
+        """Multi-channel cuts (``collate_audio(..., mono_downmix=...)``, lhotse/dataset/collation.py:215-241).  ``cuts_channels[i]``: the
+        channel rows of cut ``i`` -- 1-D float32, of equal length, read in front of the cut's pending transforms: ``factors[i]`` (a
+        ``Speed``, 1.0 = none) behind ``source_rates[i]`` (a ``Resample`` from that rate to ``sampling_rate``, None = none).  Every channel
+        row goes into the arena as a row of its own and runs through the chain of ``audio_of_tracks`` like a mono cut with that factor
+        and rate; then ONE collate launch (``lhotse_amd.augmentation.collate_sources_in_arena``) writes the batch:
+
+        ``mono_downmix=True`` -> ``(B, Tmax)``: a cut's row is the mean over its channels (float64 sum in channel order, one division, one
+        rounding; a cut of one channel is copied).  ``False`` -> ``(B, Cmax, Tmax)``, written as ``B * Cmax`` rows of the same launch: the
+        channels a cut does not have are zero rows, a mono cut sits in channel 0.  ``None``: the reference's rule -- downmix unless every
+        cut has more than one channel.  -> ``(audio, audio_lens)`` with ``wants`` truncating as in ``audio_of``.
+
+        An entry of ``cuts_channels`` may instead be the TRACK LIST of a mono cut as ``audio_of_tracks`` takes it (a list of tuples; its
+        factor and source rate are the tracks' own): that cut keeps its whole chain -- mix, reverb, level -- in the same arena and counts
+        as a cut of one channel.  ``offsets[i]`` / ``totals[i]`` (None: 0 / the cut's own length): a cut padded with silence -- its
+        samples start at element ``offsets[i]`` of its row(s) and its reported length is ``totals[i]``."""
+        B = len(cuts_channels)
+        if B == 0 or not (B == len(factors) == len(source_rates) == len(wants)):
+            raise ValueError("audio_of_channels: at least one cut, and one factor, one source rate and one wanted sample count per cut")
+        pseudo, pseudo_wants, first = [], [], [0]  # every channel row as a cut of one plain track; the rows of cut i are first[i] : first[i + 1]
+        for chans, f, rate, want in zip(cuts_channels, factors, source_rates, wants):
+            if len(chans) and isinstance(chans[0], tuple):  # the tracks of a mono cut
+                pseudo.append(list(chans)), pseudo_wants.append(int(want))
+            else:
+                if not len(chans):
+                    raise ValueError("audio_of_channels: a cut without channels")
+                if len({int(x.shape[-1]) for x in chans}) != 1 or any(x.ndim != 1 for x in chans):
+                    raise ValueError("audio_of_channels: the channel rows of a cut are 1-D and equally long")
+                for x in chans:
+                    pseudo.append([(x, float(f), 0, None, True, int(want), None, None if rate is None else int(rate))])
+                    pseudo_wants.append(int(want))
+            first.append(len(pseudo))
+        first = np.asarray(first, dtype=np.int64)
+        num_ch = np.diff(first)
+        if int(num_ch.max()) > 32:
+            raise ValueError(f"audio_of_channels: a cut of {int(num_ch.max())} channels, the collate launch takes at most 32 sources per row")
+        if mono_downmix is None:
+            mono_downmix = not bool((num_ch > 1).all())
+        with torch.no_grad():
+            arena, row_off, row_len = self._tracks_chain(pseudo, pseudo_wants, sampling_rate)
+            lens = np.minimum(row_len[first[:-1]], np.asarray(wants, dtype=np.int64))
+            dst = np.zeros(B, dtype=np.int64) if offsets is None else np.asarray([0 if o is None else int(o) for o in offsets], dtype=np.int64)
+            out_lens = lens.copy() if totals is None else np.asarray([int(n) if t is None else int(t) for n, t in zip(lens, totals)], dtype=np.int64)
+            if int((dst + lens - out_lens).max()) > 0:
+                raise ValueError("audio_of_channels: a cut's samples reach past its total length")
+            tmax = max(int(w) if totals is None or totals[i] is None else int(totals[i]) for i, w in enumerate(wants))
+            if mono_downmix:
+                audio = _collate_sources_in_arena(arena, first, row_off, lens, tmax, dst, self.dtype)
+            else:
+                cmax = int(num_ch.max())
+                k = (np.arange(cmax)[None, :] < num_ch[:, None]).astype(np.int64).reshape(-1)  # row (b, c) has one source, or none
+                srcs = np.concatenate([row_off[first[b] : first[b + 1]] for b in range(B)])
+                audio = _collate_sources_in_arena(arena, np.concatenate([[0], np.cumsum(k)]), srcs, np.repeat(lens, cmax), tmax,
+                                                  np.repeat(dst, cmax), self.dtype).view(B, cmax, tmax)
+            return audio, torch.from_numpy(out_lens)
+
 
 
 def _featmix_in_arena(arena_bytes, cuts_table, num_features, row_frames, layout=None):
@@ -753,6 +826,104 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
 
         rest = pending_transforms(fastcopy(cut, recording=fastcopy(cut.recording, transforms=tf[1:])), gpu_reverb)
         return None if rest is None else (src, rest[0], rest[1])
+
+    MAX_CHANNELS = 32  # channels of one cut = sources of one row of the collate launch (COLLATE_MAX_SOURCES)
+
+    def pending_channel_chain(cut, gpu_speed: bool = True, gpu_resample: bool = True):
+        """``pending_chain`` for a cut of SEVERAL channels: a ``MultiCut`` (no video, 1 ... 32 channels) over a recording whose transform
+        list is ``[Resample(a -> sr)]? [Speed]?`` -- the ``Resample`` under the conditions of ``pending_chain`` with ``bankless`` (first,
+        to the cut's rate, the ``default`` backend, a rate pair ``resample_route`` serves, ``gpu_resample`` on), a ``Speed`` with a factor
+        other than 1 only with ``gpu_speed`` -- or a ``MixedCut`` (no transforms of its own, no video) whose audible tracks are ONE such
+        ``MultiCut`` and ``PaddingCut``s, none with an SNR (``cut.pad``, to the right or to the left) -> ``(the MultiCut, a or None, factor
+        still to be applied (1.0 = none), the samples of padding in front of it, the cut's own num_samples or None when it is not
+        padded)``.  None = load it the reference's way: any other transform (``Volume``, ``Clipping``, a reverb, a ``Resample`` that is
+        not first or a bracket of two), more than 32 channels, a multi-channel track that is mixed with audio, a padded cut whose tracks
+        do not add up to its length (deferred_mix's rule)."""
+        if type(cut).__name__ == "MixedCut":
+            if not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
+                return None
+            from lhotse.audio.utils import get_audio_duration_mismatch_tolerance
+            from lhotse.cut.mixed import _get_audible_tracks
+
+            sr = cut.sampling_rate
+            tracks = _get_audible_tracks(cut)
+            data = [t for t in tracks if type(t.cut).__name__ != "PaddingCut"]
+            if len(data) != 1 or type(data[0].cut).__name__ != "MultiCut" or any(t.snr is not None or t.cut.sampling_rate != sr for t in tracks):
+                return None
+            inner = pending_channel_chain(data[0].cut, gpu_speed, gpu_resample)
+            if inner is None:
+                return None
+            off = compute_num_samples(data[0].offset, sr)
+            total = max(compute_num_samples(t.offset, sr) + compute_num_samples(t.cut.duration, sr) for t in tracks)
+            diff = total - cut.num_samples
+            if diff < 0 or diff >= max(1, compute_num_samples(get_audio_duration_mismatch_tolerance(), sampling_rate=sr)):
+                return None
+            return inner[0], inner[1], inner[2], off, int(cut.num_samples)
+        if type(cut).__name__ != "MultiCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
+            return None
+        channels = cut.channel if isinstance(cut.channel, (list, tuple)) else [cut.channel]
+        if not 1 <= len(channels) <= MAX_CHANNELS:
+            return None
+        tf = list(cut.recording.transforms or [])
+        src, factor = None, 1.0
+        if tf and _transform_name(tf[0]) == "Resample":
+            if not gpu_resample:
+                return None
+            src, dst = _resample_rates(tf.pop(0))
+            if dst != int(cut.sampling_rate) or src == dst or src <= 0:
+                return None
+            from lhotse.audio.resampling_backend import get_current_resampling_backend  # the reference's own switch is the contract
+
+            if get_current_resampling_backend() != "default" or resample_route(src, dst) is None:
+                return None
+        if tf and _transform_name(tf[0]) == "Speed":
+            t = tf.pop(0)
+            factor = float(t["kwargs"]["factor"] if isinstance(t, dict) else t.factor)
+            if factor != 1.0 and not gpu_speed:
+                return None
+        return None if tf else (cut, src, factor, 0, None)
+
+    def read_channels_before_chain(cut) -> np.ndarray:
+        """``read_before_chain`` for a ``MultiCut``: the ``(C, T)`` segment of the ORIGINAL audio that ``Recording.load_audio`` reads for
+        the cut's channels before it applies the recording's transforms (lhotse/audio/recording.py:412-467)."""
+        from lhotse.augmentation import AudioTransform  # the reference's own classes: their reverse_timestamps are the contract
+
+        rec = cut.recording
+        offset, duration = cut.start, cut.duration
+        if duration is not None and isclose(duration, rec.duration, abs_tol=1e-3):
+            duration = None  # (recording.py:415-417)
+        transforms = [t if isinstance(t, AudioTransform) else AudioTransform.from_dict(t) for t in rec.transforms or []]
+        for t in reversed(transforms):
+            offset, duration = t.reverse_timestamps(offset=offset, duration=duration, sampling_rate=rec.sampling_rate)
+        channels = frozenset(cut.channel if isinstance(cut.channel, (list, tuple)) else [cut.channel])
+        per_source = []
+        for source in rec.sources:
+            if not channels.intersection(source.channels):
+                continue
+            samples = source.load_audio(offset=offset, duration=duration, force_opus_sampling_rate=rec.sampling_rate)
+            drop = [i for i, cid in enumerate(source.channels) if cid not in channels]
+            if drop:
+                samples = np.delete(samples, drop, axis=0)
+            per_source.append(samples)
+        audio = rec._stack_audio_channels(per_source)
+        return np.ascontiguousarray(audio, dtype=np.float32)
+
+    def _read_channels(cut, chain, suppress_errors: bool):
+        """The entry of ``FusedAudioBatch.audio_of_channels`` for a cut ``pending_channel_chain`` serves (``chain`` = its answer):
+        ``(channel rows, factor, source rate, wanted samples, offset, total)``, read in front of the pending transforms -- or, when their
+        output would be shorter than the cut (it would need reflect-padding: the rule of ``_read_one``), the reference's own
+        ``load_audio`` of the ``MultiCut`` with nothing pending.  None when the read failed and errors are suppressed."""
+        with suppress_audio_loading_errors(enabled=suppress_errors):
+            data, src, factor, off, total = chain
+            sr = data.sampling_rate
+            want = compute_num_samples(data.duration, sr)
+            if src is not None or factor != 1.0:
+                raw = read_channels_before_chain(data)
+                if chain_num_samples(raw.shape[-1], src, factor, sr) >= want:
+                    return list(raw), factor, src, want, off, total
+            audio = data.load_audio()
+            return list(np.ascontiguousarray(audio, dtype=np.float32)), 1.0, None, int(audio.shape[-1]), off, total
+        return None
 
     LEVEL_NAMES = ("Volume", "Clipping")
     MAX_LEVEL_OPS = 4  # ops of one block = of one program of hipfeat_level_plan
@@ -1289,12 +1460,19 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         ``gpu_level`` with the meaning and defaults they have on ``HipOnTheFlyFeatures`` (there are no ``wave_transforms`` here: None = on).
         Returns ``(audio, audio_lens[, cuts])`` with the parent's int32 lengths and its ``fault_tolerant`` contract.
 
+        Multi-channel batches (``gpu_channels``; ``mono_downmix`` None / True / False as on the parent): a batch with ``MultiCut``s that
+        ``pending_channel_chain`` serves, and any batch with ``mono_downmix=False``, is collated by ONE launch as ``(B, T)`` -- a cut's row
+        is the correctly rounded mean over its channels -- or ``(B, C, T)`` (``FusedAudioBatch.audio_of_channels``); the mono cuts of
+        such a batch keep their whole device chain.  ``gpu_channels``: None = on where ``device`` is a GPU, False = the parent's path.
+
         The parent's own ``__call__`` runs, and its result is moved to ``return_device`` (None: ``device``), for ``recording_field``,
-        ``use_batch_loader``, ``mono_downmix=False`` and a batch in which any cut has more than one channel."""
+        ``use_batch_loader`` and a batch with a multi-channel cut that ``pending_channel_chain`` refuses (a transform other than
+        ``[Resample]? [Speed]?``, a multi-channel track mixed with audio, more than 32 channels)."""
 
         def __init__(self, *args, device: Union[str, torch.device, None] = None, return_device: Optional[Union[str, torch.device]] = None,
                      dtype: torch.dtype = torch.float32, gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None,
-                     gpu_reverb: Optional[bool] = None, gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, **kwargs) -> None:
+                     gpu_reverb: Optional[bool] = None, gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None,
+                     gpu_channels: Optional[bool] = None, **kwargs) -> None:
             super().__init__(*args, **kwargs)
             self.batch = FusedAudioBatch(device, dtype)
             self.device, self.dtype, self.return_device = self.batch.device, dtype, return_device
@@ -1304,15 +1482,62 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             # (only where the reference itself would run its sinc resampler, as on HipOnTheFlyFeatures)
             self.gpu_resample = _reference_resamples_with_sinc() if gpu_resample is None else bool(gpu_resample)
             self.gpu_level = True if gpu_level is None else bool(gpu_level)
+            # multi-channel cuts and the (B, C, T) form: None = on where the chain has a GPU to run on (a CPU `device` has no launch
+            # that could write the batch: the parent's path, as before), False = always the parent's path
+            self.gpu_channels = (self.device.type == "cuda") if gpu_channels is None else bool(gpu_channels)
 
         def _moved(self, result):
             dev = self.device if self.return_device is None else self.return_device
             return (result[0].to(dev),) + tuple(result[1:])
 
+        def _channel_chains(self, cuts):
+            """Per cut of a batch that needs the channel route: None for a cut of one channel (the mono route reads it), else the answer of
+            ``pending_channel_chain``; the whole result is None when the parent has to serve the batch."""
+            if not self.gpu_channels:
+                return None
+            chains = [None if _num_channels(c) == 1 else pending_channel_chain(c, self.gpu_speed_perturb, self.gpu_resample) for c in cuts]
+            return None if any(ch is None and _num_channels(c) != 1 for c, ch in zip(cuts, chains)) else chains
+
+        def _call_channels(self, cuts, chains):
+            """The batch through ``FusedAudioBatch.audio_of_channels``: multi-channel cuts as their channel rows, every other cut as the
+            tracks the mono route reads."""
+            from lhotse import CutSet
+
+            pool = _get_executor(self.num_workers, executor_type=self._executor_type)
+            map_fn = map if pool is None else pool.map
+
+            def read(pair):
+                cut, chain = pair
+                if chain is not None:
+                    return _read_channels(cut, chain, self.fault_tolerant)
+                res = _read_one(cut, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix,
+                                gpu_reverb=self.gpu_reverb, gpu_resample=self.gpu_resample, gpu_level=self.gpu_level)
+                if res is None:
+                    return None
+                a, f, want = res
+                return (a if isinstance(a, list) else [(a, f, 0, None, True)]), 1.0, None, want, None, None
+
+            entries, ok = [], []
+            for cut, res in zip(cuts, map_fn(read, list(zip(cuts, chains)))):
+                if res is not None:
+                    entries.append(res), ok.append(cut)
+            if not entries:
+                raise ValueError("HipAudioSamples: no cut of the mini-batch could be read")
+            rates = {c.sampling_rate for c in ok}
+            assert len(rates) == 1, f"one launch per batch needs a single sampling rate, got {sorted(rates)}"
+            chans, factors, srcs, wants, offs, totals = (list(x) for x in zip(*entries))
+            audio, lens = self.batch.audio_of_channels(chans, factors, srcs, wants, rates.pop(), self.mono_downmix, offs, totals)
+            result = self._moved((audio, lens.to(torch.int32)))  # (collation.py:242)
+            return result + (CutSet.from_cuts(ok),) if self.fault_tolerant else result
+
         def __call__(self, cuts, recording_field: Optional[str] = None):
-            if (recording_field is not None or self.use_batch_loader or self.mono_downmix is False
-                    or any(_num_channels(c) != 1 for c in cuts)):
+            if recording_field is not None or self.use_batch_loader:
                 return self._moved(super().__call__(cuts, recording_field=recording_field))
+            if self.mono_downmix is False or any(_num_channels(c) != 1 for c in cuts):
+                chains = self._channel_chains(list(cuts))
+                if chains is None:
+                    return self._moved(super().__call__(cuts, recording_field=recording_field))
+                return self._call_channels(list(cuts), chains)
             pool = _get_executor(self.num_workers, executor_type=self._executor_type)
             audios, factors, wants, ok = self._read(cuts, pool, None)
             if not len(audios):
