@@ -9,17 +9,27 @@ cut straight into its slot of the ``(B, Tmax, F)`` tensor and only the padding r
 (``hipfeat_extract_collated``); audio reading, wave transforms, ``return_audio`` / ``fault_tolerant`` outputs and the
 supervision helpers are inherited unchanged.
 
+The rule.  Which of a recording's pending transforms the device takes over is decided in ONE place, ``parse_chain``: one walk over the
+transform list of a mono cut, left to right, against the grammar ``[Resample]? [Speed]? L? [Reverb]? L?`` (L = a block of level ops), each
+element behind its switch (``gpu_resample`` / ``gpu_speed_perturb`` / ``gpu_level`` / ``gpu_reverb``) -> a ``Chain(source_rate, factor,
+pre, reverb, post)`` or None = the reference's ``cut.load_audio()``.  ``pending_channel_chain`` (a ``MultiCut``) and ``deferred_mix`` (the
+tracks of a ``MixedCut``: a ``PendingTrack(cut, offset, snr, is_ref, chain)`` each) ask the same walk.  A cut the rule serves is read ONCE
+in front of its whole chain (``read_before_chain``; a chain that keeps the length: ``load_audio()`` of the cut without its transforms)
+into a ``Track(samples, factor, offset, snr, is_ref, cap, reverb, source_rate, levels)``, what ``FusedMiniBatch.features_of_tracks``
+consumes; a chain whose output would be shorter than the cut (``chain_num_samples``: the reference reflect-pads it) goes back to
+``cut.load_audio()``.  The paragraphs below say what each element of the grammar is and what the device does with it.
+
 Speed perturbation.  ``PerturbSpeed`` (lhotse/dataset/cut_transforms/perturb_speed.py:8-47) turns a cut into one whose
 recording carries a ``Speed(factor)`` transform; the resampling itself then happens on the CPU inside
 ``Recording.load_audio`` (lhotse/audio/recording.py:431-490), one torch ``conv1d`` per cut, before the strategy ever
 sees the samples -- it is what an on-the-fly pipeline spends its time in once the features are on the GPU.  With
-``gpu_speed_perturb=True`` (default) a cut whose recording's ONLY transform is that ``Speed`` is read WITHOUT it -- the
+``gpu_speed_perturb=True`` (default) a cut with that ``Speed`` pending is read WITHOUT it -- the
 very segment of the original file ``load_audio`` would read, through the same ``reverse_timestamps`` /
 ``AudioSource.load_audio`` calls -- and the batch is perturbed on the device, mixed factors and all, in the arena the
 feature launch reads from (``lhotse_amd.augmentation.perturb_speed_in_arena``).  Sample counts follow
 ``assert_and_maybe_fix_num_samples`` (truncate; the rare cut that would need reflect-padding takes the reference's own
-path), values agree with the CPU ``Speed`` to the resampler's 1e-5.  Every other cut (other or several transforms,
-multi-channel) is loaded exactly as before.
+path), values agree with the CPU ``Speed`` to the resampler's 1e-5.  A mini-batch in which a ``Speed`` is all that is pending takes the route of
+``FusedMiniBatch.features_of`` (one launch for all factors).
 
 Mixed cuts.  ``CutMix`` / ``CutSet.mix`` / ``.pad`` turn a cut into a ``MixedCut`` whose samples come out of
 ``MixedCut.load_audio`` (lhotse/cut/mixed.py:1312-1409): every track is loaded (its ``Speed`` on the CPU), its energy is
@@ -37,7 +47,7 @@ mini-batch may combine device-mixed, plain, speed-only and fallback cuts freely.
 Reverberation.  ``ReverbWithImpulseResponse`` (lhotse/augmentation/rir.py:12-166; ``cut.reverb_rir``) appends itself to the recording's
 transforms and ``Recording.load_audio`` then convolves the loaded (and speed-perturbed) samples with the RIR through three full-length
 float32 FFTs on the CPU.  With ``gpu_reverb`` (default: on unless ``wave_transforms`` are given) a recording whose transforms are
-``[Reverb]`` or ``[Speed, Reverb]`` with a RECORDED RIR and one ``rir_channels`` entry is read in front of them, the RIR is loaded on the
+``[Reverb]`` or ``[Speed, Reverb]`` (with level blocks around the reverb, below) with a RECORDED RIR and one ``rir_channels`` entry is read in front of them, the RIR is loaded on the
 host with the reference's own calls, and the convolution runs on the device between the resampler and the mix
 (``lhotse_amd.augmentation.reverb_in_arena``: direct form, float32, within 2 x the reference's own distance from the exact float64
 convolution).  ``rir=None`` (the random generator), several ``rir_channels``, a reverb in front of a ``Speed`` and a ``MixedCut`` whose own
@@ -46,21 +56,21 @@ convolution).  ``rir=None`` (the random generator), several ``rir_channels``, a 
 Resampling.  ``cuts.resample(sr)`` puts a ``Resample(a -> sr)`` at the front of the recording's transforms (lhotse/audio/recording.py:905-935)
 and ``Recording.load_audio`` then runs the sinc resampler on the CPU (44.1 -> 16 kHz: 160 filters of 475 taps).  With ``gpu_resample``
 (default: on unless ``wave_transforms`` are given, and only where the reference itself runs its sinc resampler: torchaudio importable,
-backend ``default``) a mono recording whose transforms are ``[Resample]? [Speed]? [Reverb]?`` is read in front of ALL of them at the
+backend ``default``) a mono recording whose transforms are ``[Resample]? [Speed]? ...`` is read in front of ALL of them at the
 source rate (``read_before_chain``), and the chain runs on the device: the rate conversion first, one launch per distinct source rate
 (``lhotse_amd.augmentation.resample_in_arena``; the many-phase ratios on the matrix cores), then the ``Speed`` as a second pass over
-its output, then reverb and mix as before.  ``pending_chain`` says which cuts qualify; a ``Resample`` that is not first or not alone,
-the ``sox`` backend and a filter bank of more than 2^20 floats keep the reference's path.
+its output, then reverb and mix as before.  A ``Resample`` that is not first (other than the brackets of a level block, below),
+the ``sox`` backend and a pair of rates no kernel serves (``resample_route``) keep the reference's path.
 
 Level changes.  ``PerturbVolume`` appends a ``Volume`` to the recording's transforms, the ``Clipping`` cut transform / ``cut.clip_amplitude`` a
 ``Clipping`` -- with ``oversampling=k`` between ``Resample(sr -> k sr)`` and ``Resample(k sr -> sr)`` (lhotse/audio/recording.py:937-975).  With
 ``gpu_level`` (default: on unless ``wave_transforms`` are given) a mono recording whose transforms are ``[Resample]? [Speed]? L? [Reverb]? L?``, L =
 1 ... 4 such ops with at most one ``Clipping``, is read in front of all of them and scaled / clipped on the device, in place, behind the speed
 pass and on both sides of the reverb (``lhotse_amd.augmentation.level_in_arena``: ``Volume`` and hard ``Clipping`` bit for bit, soft ``Clipping`` as
-the float64 tanh rounded once); the oversampled form takes two more resample passes and needs the resampling route.  ``pending_level_chain`` says
-which cuts qualify -- a new rule: the older ones answer for such cuts what they always did --, ``deferred_mix(..., gpu_level=True)`` lets such
-tracks into a device mix.  A level op in front of the ``Speed``, more than 4 ops or two ``Clipping``s in a block and k outside 2 ... 8 keep the
-reference's path.
+the float64 tanh rounded once); the oversampled form takes two more resample passes and needs the resampling route, as does the band
+bracket ``Resample(sr -> m) Resample(m -> sr)`` of ``LowpassUsingResampling``, which counts as two ops of a block.
+``deferred_mix(..., gpu_level=True)`` lets such tracks into a device mix.  A level op in front of the ``Speed``, more than 4 ops or two
+``Clipping``s in a block, k outside 2 ... 8 and a recording of several channels keep the reference's path.
 
 Raw audio.  ``AudioSamples`` (lhotse/dataset/input_strategies.py:208-299) and ``return_audio=True`` want the cuts' SAMPLES as one zero-padded
 ``(B, Tmax)`` tensor (``collate_audio``, lhotse/dataset/collation.py:148-260).  The chain above leaves them ragged in the arena; one launch
@@ -82,7 +92,7 @@ Needs lhotse (it consumes ``CutSet``s); importing this module without lhotse wor
 from __future__ import annotations
 
 from math import gcd, isclose
-from typing import List, Optional, Tuple, Union
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -152,28 +162,114 @@ def _collate_sources_in_arena(arena, first, src_offsets, lengths, row_len, dst_o
     return collate_sources_in_arena(arena, first, src_offsets, lengths, row_len=row_len, dst_offsets=dst_offsets, dtype=dtype)[0]
 
 
+class Chain(NamedTuple):
+    """What the device takes over of a recording's transform list (``parse_chain``): the rate the samples are read at when a ``Resample``
+    leads the list, the factor of the pending ``Speed`` (1.0 = none), the level block in front of the reverb, the reverb's kwargs, the
+    level block behind it.  A block is None or a list of steps ``("level", [ops])`` / ``("up", k)`` / ``("down", k)`` /
+    ``("rate", src, dst)`` (``FusedMiniBatch.features_of_tracks``)."""
+
+    source_rate: Optional[int] = None
+    factor: float = 1.0
+    pre: Optional[list] = None
+    reverb: Optional[dict] = None
+    post: Optional[list] = None
+
+    @property
+    def pending(self) -> bool:
+        """Whether there is anything for the device to do."""
+        return self != Chain()
+
+    @property
+    def levels(self) -> Optional[tuple]:
+        return None if self.pre is None and self.post is None else (self.pre, self.post)
+
+    @property
+    def keeps_length(self) -> bool:
+        """No element that changes the sample count: no ``Resample``, no ``Speed``, no rate step in a level block."""
+        return self.source_rate is None and self.factor == 1.0 and all(st[0] == "level" for b in (self.pre, self.post) for st in b or ())
+
+
+class PendingTrack(NamedTuple):
+    """An audible track of a ``MixedCut`` the device mixes (``deferred_mix``), before it is read; ``chain`` None: a ``PaddingCut``."""
+
+    cut: object
+    offset: int
+    snr: Optional[float]
+    is_ref: bool
+    chain: Optional[Chain]
+
+
+class Track(NamedTuple):
+    """A track as ``FusedMiniBatch.features_of_tracks`` / ``FusedAudioBatch.audio_of_tracks`` consume it (a plain tuple of the first 5
+    to 9 values is taken as well): the samples in front of the pending chain -- or, for a ``PaddingCut`` track, their count --, the
+    ``Speed`` factor still to be applied, the first sample inside the cut, the SNR in dB or None, whether it is the cut's SNR reference
+    track, the sample count it is truncated to, ``(rir_samples, normalize_output)``, the rate the samples are at, the level blocks
+    ``(in front of the reverb, behind it)``."""
+
+    samples: object
+    factor: float
+    offset: int
+    snr: Optional[float]
+    is_ref: bool
+    cap: Optional[int] = None
+    reverb: Optional[tuple] = None
+    source_rate: Optional[int] = None
+    levels: Optional[tuple] = None
+
+
+class _Tracks(list):
+    """The cuts of a mini-batch as lists of ``Track``s, normalised (``_as_tracks``)."""
+
+
+def _as_tracks(cuts_tracks, sampling_rate: int) -> _Tracks:
+    """Every incoming track as a ``Track``, once; a source rate that is the mini-batch's own and a pair of empty level blocks are none.
+    (Plain loops: this runs per track of every mini-batch, in front of launches that take a fraction of a millisecond.)"""
+    if type(cuts_tracks) is _Tracks:
+        return cuts_tracks
+    sr = int(sampling_rate)
+    out = _Tracks()
+    for tracks in cuts_tracks:
+        row = []
+        for tr in tracks:
+            if type(tr) is not Track:
+                tr = Track(*tr)
+            if tr.source_rate is not None and int(tr.source_rate) == sr:
+                tr = tr._replace(source_rate=None)
+            if tr.levels is not None and not (tr.levels[0] or tr.levels[1]):
+                tr = tr._replace(levels=None)
+            row.append(tr)
+        out.append(row)
+    return out
+
+
+def _is_padding(track: Track) -> bool:
+    return isinstance(track.samples, (int, np.integer))
+
+
 def _is_plain(tracks) -> bool:
     """One track with samples that starts at 0 and is not scaled: the cut IS that track (a MonoCut, speed-perturbed or not; when the
     track carries a reverb, the cut is the reverb's output)."""
-    return len(tracks) == 1 and not isinstance(tracks[0][0], (int, np.integer)) and int(tracks[0][2]) == 0
+    return len(tracks) == 1 and int(tracks[0].offset) == 0 and not _is_padding(tracks[0])
 
 
-def _reverb_of(track):
-    """The optional 7th element of a track: ``(rir_samples, normalize_output)`` or None."""
-    return track[6] if len(track) > 6 and track[6] is not None else None
-
-
-def _source_rate_of(track, sampling_rate: int) -> Optional[int]:
-    """The optional 8th element of a track: the rate its samples are at, when that is not the mini-batch's (a pending ``Resample``)."""
-    rate = track[7] if len(track) > 7 else None
-    return None if rate is None or int(rate) == int(sampling_rate) else int(rate)
-
-
-def _level_of(track):
-    """The optional 9th element of a track: ``(block in front of the reverb, block behind it)`` or None.  A block is None or a list of
-    steps ``("level", [ops])`` / ``("up", k)`` / ``("down", k)`` / ``("rate", src, dst)`` (``pending_level_chain``)."""
-    lv = track[8] if len(track) > 8 else None
-    return None if lv is None or (not lv[0] and not lv[1]) else lv
+def _speed_only_batch(cuts_tracks: _Tracks):
+    """``(audios, factors)`` when every cut is one plain track with at most a ``Speed`` pending -- the mini-batch of ``features_of`` /
+    ``audio_of`` --, else None."""
+    audios, factors = [], []
+    for tracks in cuts_tracks:
+        if len(tracks) != 1:
+            return None
+        tr = tracks[0]  # (``_is_plain`` spelt out: one call less per cut)
+        if tr.reverb is not None or tr.source_rate is not None or tr.levels is not None or int(tr.offset) != 0:
+            return None
+        a = tr.samples
+        if not isinstance(a, torch.Tensor):
+            if _is_padding(tr):
+                return None
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        audios.append(a)
+        factors.append(float(tr.factor))
+    return audios, factors
 
 
 def _level_steps(arena, offs, lens, blocks, sr: int, tail: int):
@@ -222,17 +318,17 @@ class _ArenaChain:
         from .extractors import _as_1d_float
 
         self._chain_check_sr(sr)
+        cuts_tracks = _as_tracks(cuts_tracks, sr)
         items, factors, caps, ratios = [], [], [], []  # the tracks that have a source, in cut / track order; ratios: (source rate, sr) or None
         levels = []  # per such track: its two level blocks or None
         rirs, rir_of, rv_idx, rv_rir, rv_norm = [], {}, [], [], []  # distinct scaled RIRs (hs, shift); reverberated tracks -> their RIR
         for tracks in cuts_tracks:
             for tr in tracks:
-                if isinstance(tr[0], (int, np.integer)):
-                    if _reverb_of(tr) is not None:
+                if _is_padding(tr):
+                    if tr.reverb is not None:
                         raise ValueError("a padding track cannot carry a reverb")
                     continue
-                a = tr[0]
-                rv = _reverb_of(tr)
+                a, rv = tr.samples, tr.reverb
                 if rv is not None:
                     if id(rv[0]) not in rir_of:  # (the same array object, as the loader's RIR cache hands out: no look at its bytes)
                         h = np.ascontiguousarray(rv[0], dtype=np.float32).reshape(-1)
@@ -245,11 +341,10 @@ class _ArenaChain:
                         rir_of[id(rv[0])] = rir_of[key]
                     rv_idx.append(len(items)), rv_rir.append(rir_of[id(rv[0])]), rv_norm.append(int(bool(rv[1])))
                 items.append(_as_1d_float(a.squeeze() if a.ndim > 1 else a, "HipOnTheFlyFeatures"))
-                factors.append(float(tr[1]))
-                levels.append(_level_of(tr))
-                rate = _source_rate_of(tr, sr)
-                ratios.append(None if rate is None else (rate, int(sr)))
-                caps.append(-1 if len(tr) < 6 or tr[5] is None else int(tr[5]))
+                factors.append(float(tr.factor))
+                levels.append(tr.levels)
+                ratios.append(None if tr.source_rate is None else (int(tr.source_rate), int(sr)))
+                caps.append(-1 if tr.cap is None else int(tr.cap))
         caps = np.asarray(caps, dtype=np.int64)
         num_tracks = len(items)
         rir_items = [hs for hs, _ in rirs]  # the RIRs travel in the same pack, behind the tracks
@@ -267,23 +362,23 @@ class _ArenaChain:
         def tables(po, pl):
             """The mix tables over the tracks at po / pl (a sample or two of a resampled track truncated); plain cuts -> cut_off / cut_len."""
             pl = np.asarray(pl)[: len(caps)]  # (the RIRs behind the tracks are not tracks)
-            pl = np.where(caps >= 0, np.minimum(pl, caps), pl)
+            po, pl = np.asarray(po).tolist(), np.where(caps >= 0, np.minimum(pl, caps), pl).tolist()  # (plain ints: they are read one by one)
             first, so, sl, do, snrs, refs, cap, ids = [0], [], [], [], [], [], [], []
             k = 0
             for c, tracks in enumerate(cuts_tracks):
                 if _is_plain(tracks):
-                    cut_off[c], cut_len[c] = po[k], min(int(pl[k]), int(wants[c]))
+                    cut_off[c], cut_len[c] = po[k], min(pl[k], int(wants[c]))
                     k += 1
                     continue
                 ref = -1
                 for t, tr in enumerate(tracks):
-                    if isinstance(tr[0], (int, np.integer)):
-                        so.append(-1), sl.append(int(tr[0]))
+                    if _is_padding(tr):
+                        so.append(-1), sl.append(int(tr.samples))
                     else:
-                        so.append(int(po[k])), sl.append(int(pl[k]))
+                        so.append(po[k]), sl.append(pl[k])
                         k += 1
-                    do.append(int(tr[2])), snrs.append(tr[3])
-                    if tr[4] and ref < 0:
+                    do.append(int(tr.offset)), snrs.append(tr.snr)
+                    if tr.is_ref and ref < 0:
                         ref = t
                 first.append(len(so)), refs.append(ref), cap.append(int(wants[c])), ids.append(c)
             return first, so, sl, do, snrs, refs, cap, ids
@@ -392,7 +487,8 @@ class FusedMiniBatch(_ArenaChain):
 
     def features_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
         """``features_of`` for a mini-batch in which some cuts are ``MixedCut``s (``CutMix``, ``CutSet.mix`` / ``.pad``), without a lhotse
-        type: every cut is a list of tracks ``(samples, factor, offset_samples, snr, is_reference[, num_samples])`` -- ``samples`` as read
+        type: every cut is a list of tracks, each a ``Track`` or a plain tuple of its first 5 to 9 values (normalised once, on entry)
+        ``(samples, factor, offset_samples, snr, is_reference[, num_samples])`` -- ``samples`` as read
         from the file (in front of a pending ``Speed(factor)``; 1.0 = none) or, for a ``PaddingCut`` track, its sample COUNT as an int;
         the track's first sample inside the cut; its SNR in dB or None; whether it is the cut's SNR reference track
         (``_get_snr_reference_track``, lhotse/cut/mixed.py:1909-1918); optionally the samples the track must end up with after its
@@ -424,9 +520,10 @@ class FusedMiniBatch(_ArenaChain):
         audio_lens)``, the samples collated on the device out of the arena the feature launch read, with no per-cut copy."""
         if len(cuts_tracks) != len(wants):
             raise ValueError("features_of_tracks: one wanted sample count per cut")
-        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None and _level_of(t[0]) is None for t in cuts_tracks):
-            audios, factors = [t[0][0] for t in cuts_tracks], [float(t[0][1]) for t in cuts_tracks]
-            audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
+        cuts_tracks = _as_tracks(cuts_tracks, sampling_rate)
+        speed_only = _speed_only_batch(cuts_tracks)
+        if speed_only is not None:
+            audios, factors = speed_only
             if any(f != 1.0 for f in factors):
                 return self._perturb_and_extract(audios, factors, wants, sampling_rate)
             return self._plain_extract(audios, sampling_rate)
@@ -576,10 +673,10 @@ class FusedAudioBatch(_ArenaChain):
         -> ``(audio (B, Tmax) on the device, audio_lens)``: the same chain in the same arena, then the collate launch."""
         if len(cuts_tracks) != len(wants):
             raise ValueError("audio_of_tracks: one wanted sample count per cut")
-        if all(_is_plain(t) and _reverb_of(t[0]) is None and _source_rate_of(t[0], sampling_rate) is None and _level_of(t[0]) is None for t in cuts_tracks):
-            audios = [t[0][0] for t in cuts_tracks]
-            audios = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in audios]
-            return self.audio_of(audios, [float(t[0][1]) for t in cuts_tracks], wants, sampling_rate)
+        cuts_tracks = _as_tracks(cuts_tracks, sampling_rate)
+        speed_only = _speed_only_batch(cuts_tracks)
+        if speed_only is not None:
+            return self.audio_of(*speed_only, wants, sampling_rate)
         with torch.no_grad():
             arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sampling_rate)
             return self._collated(arena, cut_off, cut_len, wants)
@@ -614,7 +711,7 @@ class FusedAudioBatch(_ArenaChain):
                 if len({int(x.shape[-1]) for x in chans}) != 1 or any(x.ndim != 1 for x in chans):
                     raise ValueError("audio_of_channels: the channel rows of a cut are 1-D and equally long")
                 for x in chans:
-                    pseudo.append([(x, float(f), 0, None, True, int(want), None, None if rate is None else int(rate))])
+                    pseudo.append([Track(x, float(f), 0, None, True, int(want), source_rate=rate)])
                     pseudo_wants.append(int(want))
             first.append(len(pseudo))
         first = np.asarray(first, dtype=np.int64)
@@ -743,199 +840,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
     from lhotse.dataset.input_strategies import AudioSamples, OnTheFlyFeatures, PrecomputedFeatures, _get_executor  # type: ignore
     from lhotse.utils import compute_num_samples  # type: ignore
 
-    def deferred_speed_factor(cut) -> Optional[float]:
-        """The factor of the cut's ``Speed`` transform if that is all that stands between the file and the samples (a mono cut over
-        a recording whose transform list is exactly ``[Speed(factor)]``, no video); None = load it the reference's way."""
-        if type(cut).__name__ != "MonoCut" or not cut.has_recording:
-            return None
-        rec = cut.recording
-        tf = rec.transforms
-        if not tf or len(tf) != 1 or getattr(rec, "has_video", False):
-            return None
-        t = tf[0]
-        name = t.get("name") if isinstance(t, dict) else type(t).__name__
-        if name != "Speed":
-            return None
-        factor = t["kwargs"]["factor"] if isinstance(t, dict) else t.factor
-        return float(factor)
-
     def _transform_name(t) -> str:
         return t.get("name") if isinstance(t, dict) else type(t).__name__
-
-    def pending_transforms(cut, gpu_reverb: bool = True) -> Optional[Tuple[float, Optional[dict]]]:
-        """THE rule of what the device takes over: a mono cut (no video) over a recording whose transform list is ``[]``, ``[Speed]``,
-        ``[ReverbWithImpulseResponse]`` or ``[Speed, ReverbWithImpulseResponse]`` -> ``(factor still to be applied, 1.0 = none; the
-        reverb's kwargs or None)``.  The reverb must have a recorded ``rir`` and exactly one entry in ``rir_channels``.  None = load it
-        the reference's way: anything else, among it ``rir=None`` (the random generator), several ``rir_channels``, a reverb in front
-        of a ``Speed``, and any reverb when ``gpu_reverb`` is off."""
-        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
-            return None
-        tf = list(cut.recording.transforms or [])
-        factor, reverb = 1.0, None
-        if tf and _transform_name(tf[0]) == "Speed":
-            t = tf.pop(0)
-            factor = float(t["kwargs"]["factor"] if isinstance(t, dict) else t.factor)
-        if tf and _transform_name(tf[0]) == "ReverbWithImpulseResponse" and gpu_reverb:
-            t = tf.pop(0)
-            kw = dict(t["kwargs"]) if isinstance(t, dict) else {k: getattr(t, k) for k in ("rir", "normalize_output", "early_only", "rir_channels")}
-            if kw.get("rir") is None or len(kw.get("rir_channels") or [0]) != 1:
-                return None
-            reverb = {"rir": kw["rir"], "normalize_output": bool(kw.get("normalize_output", True)), "early_only": bool(kw.get("early_only", False)),
-                      "rir_channels": [int(c) for c in (kw.get("rir_channels") or [0])]}
-        return None if tf else (factor, reverb)
-
-    def deferred_reverb(cut, gpu_reverb: bool = True) -> Optional[Tuple[float, dict]]:
-        """``(pending speed factor, the reverb's kwargs)`` of a mono cut whose recording ends in a reverb the device serves
-        (``pending_transforms``), else None."""
-        p = pending_transforms(cut, gpu_reverb)
-        return None if p is None or p[1] is None else p
-
-    from .augmentation import MAX_RESAMPLE_BANK_FLOATS, _sinc_bank_floats, resample_route  # noqa: F401  (one rule for both sides)
-
-    def pending_chain(cut, gpu_reverb: bool = True, gpu_resample: bool = True, bankless: bool = False) -> Optional[Tuple[Optional[int], float, Optional[dict]]]:
-        """``pending_transforms`` with a ``Resample`` in front: a mono cut (no video) over a recording whose transform list is
-        ``[Resample(a -> sr)]? [Speed]? [ReverbWithImpulseResponse]?`` with ``sr == cut.sampling_rate`` and ``a != sr`` ->
-        ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None)``.  None = load it the reference's way:
-        whatever ``pending_transforms`` refuses behind the ``Resample``; a ``Resample`` that is not the first transform
-        (``[Speed, Resample]``) or not the only one (the two that ``LowpassUsingResampling`` adds are ``pending_level_chain``'s band bracket,
-        not this rule's); one to another rate than the cut's; the
-        ``sox`` resampling backend (``LHOTSE_RESAMPLING_BACKEND=sox``: another filter); a reduced filter bank of more than 2^20 floats
-        -- unless ``bankless`` is set, as the strategies set it: then any pair of rates that ``resample_in_arena`` routes is taken
-        (``resample_route``: 11127 -> 16000 goes to the kernel without a bank), and only what no kernel serves is refused --;
-        any ``Resample`` when ``gpu_resample`` is off."""
-        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
-            return None
-        tf = list(cut.recording.transforms or [])
-        if not tf or _transform_name(tf[0]) != "Resample":
-            p = pending_transforms(cut, gpu_reverb)
-            return None if p is None else (None, p[0], p[1])
-        if not gpu_resample:
-            return None
-        t = tf[0]
-        src = int(t["kwargs"]["source_sampling_rate"] if isinstance(t, dict) else t.source_sampling_rate)
-        dst = int(t["kwargs"]["target_sampling_rate"] if isinstance(t, dict) else t.target_sampling_rate)
-        if dst != int(cut.sampling_rate) or src == dst or src <= 0:
-            return None
-        from lhotse.audio.resampling_backend import get_current_resampling_backend  # the reference's own switch is the contract
-
-        if get_current_resampling_backend() != "default":
-            return None
-        if resample_route(src, dst) is None if bankless else _sinc_bank_floats(src, dst) > MAX_RESAMPLE_BANK_FLOATS:
-            return None
-        from lhotse.utils import fastcopy
-
-        rest = pending_transforms(fastcopy(cut, recording=fastcopy(cut.recording, transforms=tf[1:])), gpu_reverb)
-        return None if rest is None else (src, rest[0], rest[1])
-
-    MAX_CHANNELS = 32  # channels of one cut = sources of one row of the collate launch (COLLATE_MAX_SOURCES)
-
-    def pending_channel_chain(cut, gpu_speed: bool = True, gpu_resample: bool = True):
-        """``pending_chain`` for a cut of SEVERAL channels: a ``MultiCut`` (no video, 1 ... 32 channels) over a recording whose transform
-        list is ``[Resample(a -> sr)]? [Speed]?`` -- the ``Resample`` under the conditions of ``pending_chain`` with ``bankless`` (first,
-        to the cut's rate, the ``default`` backend, a rate pair ``resample_route`` serves, ``gpu_resample`` on), a ``Speed`` with a factor
-        other than 1 only with ``gpu_speed`` -- or a ``MixedCut`` (no transforms of its own, no video) whose audible tracks are ONE such
-        ``MultiCut`` and ``PaddingCut``s, none with an SNR (``cut.pad``, to the right or to the left) -> ``(the MultiCut, a or None, factor
-        still to be applied (1.0 = none), the samples of padding in front of it, the cut's own num_samples or None when it is not
-        padded)``.  None = load it the reference's way: any other transform (``Volume``, ``Clipping``, a reverb, a ``Resample`` that is
-        not first or a bracket of two), more than 32 channels, a multi-channel track that is mixed with audio, a padded cut whose tracks
-        do not add up to its length (deferred_mix's rule)."""
-        if type(cut).__name__ == "MixedCut":
-            if not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
-                return None
-            from lhotse.audio.utils import get_audio_duration_mismatch_tolerance
-            from lhotse.cut.mixed import _get_audible_tracks
-
-            sr = cut.sampling_rate
-            tracks = _get_audible_tracks(cut)
-            data = [t for t in tracks if type(t.cut).__name__ != "PaddingCut"]
-            if len(data) != 1 or type(data[0].cut).__name__ != "MultiCut" or any(t.snr is not None or t.cut.sampling_rate != sr for t in tracks):
-                return None
-            inner = pending_channel_chain(data[0].cut, gpu_speed, gpu_resample)
-            if inner is None:
-                return None
-            off = compute_num_samples(data[0].offset, sr)
-            total = max(compute_num_samples(t.offset, sr) + compute_num_samples(t.cut.duration, sr) for t in tracks)
-            diff = total - cut.num_samples
-            if diff < 0 or diff >= max(1, compute_num_samples(get_audio_duration_mismatch_tolerance(), sampling_rate=sr)):
-                return None
-            return inner[0], inner[1], inner[2], off, int(cut.num_samples)
-        if type(cut).__name__ != "MultiCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
-            return None
-        channels = cut.channel if isinstance(cut.channel, (list, tuple)) else [cut.channel]
-        if not 1 <= len(channels) <= MAX_CHANNELS:
-            return None
-        tf = list(cut.recording.transforms or [])
-        src, factor = None, 1.0
-        if tf and _transform_name(tf[0]) == "Resample":
-            if not gpu_resample:
-                return None
-            src, dst = _resample_rates(tf.pop(0))
-            if dst != int(cut.sampling_rate) or src == dst or src <= 0:
-                return None
-            from lhotse.audio.resampling_backend import get_current_resampling_backend  # the reference's own switch is the contract
-
-            if get_current_resampling_backend() != "default" or resample_route(src, dst) is None:
-                return None
-        if tf and _transform_name(tf[0]) == "Speed":
-            t = tf.pop(0)
-            factor = float(t["kwargs"]["factor"] if isinstance(t, dict) else t.factor)
-            if factor != 1.0 and not gpu_speed:
-                return None
-        return None if tf else (cut, src, factor, 0, None)
-
-    def read_channels_before_chain(cut) -> np.ndarray:
-        """``read_before_chain`` for a ``MultiCut``: the ``(C, T)`` segment of the ORIGINAL audio that ``Recording.load_audio`` reads for
-        the cut's channels before it applies the recording's transforms (lhotse/audio/recording.py:412-467)."""
-        from lhotse.augmentation import AudioTransform  # the reference's own classes: their reverse_timestamps are the contract
-
-        rec = cut.recording
-        offset, duration = cut.start, cut.duration
-        if duration is not None and isclose(duration, rec.duration, abs_tol=1e-3):
-            duration = None  # (recording.py:415-417)
-        transforms = [t if isinstance(t, AudioTransform) else AudioTransform.from_dict(t) for t in rec.transforms or []]
-        for t in reversed(transforms):
-            offset, duration = t.reverse_timestamps(offset=offset, duration=duration, sampling_rate=rec.sampling_rate)
-        channels = frozenset(cut.channel if isinstance(cut.channel, (list, tuple)) else [cut.channel])
-        per_source = []
-        for source in rec.sources:
-            if not channels.intersection(source.channels):
-                continue
-            samples = source.load_audio(offset=offset, duration=duration, force_opus_sampling_rate=rec.sampling_rate)
-            drop = [i for i, cid in enumerate(source.channels) if cid not in channels]
-            if drop:
-                samples = np.delete(samples, drop, axis=0)
-            per_source.append(samples)
-        audio = rec._stack_audio_channels(per_source)
-        return np.ascontiguousarray(audio, dtype=np.float32)
-
-    def _read_channels(cut, chain, suppress_errors: bool):
-        """The entry of ``FusedAudioBatch.audio_of_channels`` for a cut ``pending_channel_chain`` serves (``chain`` = its answer):
-        ``(channel rows, factor, source rate, wanted samples, offset, total)``, read in front of the pending transforms -- or, when their
-        output would be shorter than the cut (it would need reflect-padding: the rule of ``_read_one``), the reference's own
-        ``load_audio`` of the ``MultiCut`` with nothing pending.  None when the read failed and errors are suppressed."""
-        with suppress_audio_loading_errors(enabled=suppress_errors):
-            data, src, factor, off, total = chain
-            sr = data.sampling_rate
-            want = compute_num_samples(data.duration, sr)
-            if src is not None or factor != 1.0:
-                raw = read_channels_before_chain(data)
-                if chain_num_samples(raw.shape[-1], src, factor, sr) >= want:
-                    return list(raw), factor, src, want, off, total
-            audio = data.load_audio()
-            return list(np.ascontiguousarray(audio, dtype=np.float32)), 1.0, None, int(audio.shape[-1]), off, total
-        return None
-
-    LEVEL_NAMES = ("Volume", "Clipping")
-    MAX_LEVEL_OPS = 4  # ops of one block = of one program of hipfeat_level_plan
-
-    def _has_level_op(cut) -> bool:
-        """A ``Volume`` or ``Clipping`` in the list, or a ``Resample`` FROM the cut's rate: the opening of a bracket (a band bracket may
-        be a block's only element)."""
-        tf = cut.recording.transforms if type(cut).__name__ == "MonoCut" and cut.has_recording else None
-        if not tf:
-            return False
-        sr = int(cut.sampling_rate)
-        return any(_transform_name(t) in LEVEL_NAMES or (_transform_name(t) == "Resample" and _resample_rates(t)[0] == sr) for t in tf)
 
     def _kwargs_of(t, names) -> dict:
         return {k: t["kwargs"][k] for k in names if k in t["kwargs"]} if isinstance(t, dict) else {k: getattr(t, k) for k in names}
@@ -943,6 +849,19 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
     def _resample_rates(t) -> Tuple[int, int]:
         kw = _kwargs_of(t, ("source_sampling_rate", "target_sampling_rate"))
         return int(kw["source_sampling_rate"]), int(kw["target_sampling_rate"])
+
+    from .augmentation import MAX_RESAMPLE_BANK_FLOATS, _sinc_bank_floats, resample_route  # noqa: F401  (one rule for both sides)
+
+    MAX_CHANNELS = 32  # channels of one cut = sources of one row of the collate launch (COLLATE_MAX_SOURCES)
+    MAX_LEVEL_OPS = 4  # ops of one block = of one program of hipfeat_level_plan
+
+    def _reference_resamples_with_sinc() -> bool:
+        """Whether lhotse's ``Resample.__call__`` would run ``ResampleTensor`` (the sinc resampler the device implements): torchaudio
+        importable and the resampling backend ``default`` (lhotse/augmentation/torchaudio.py:108-139)."""
+        import lhotse.augmentation.torchaudio as ref  # (looked up on the module: the very name Resample.__call__ consults)
+        from lhotse.audio.resampling_backend import get_current_resampling_backend
+
+        return bool(ref.is_torchaudio_available()) and get_current_resampling_backend() == "default"
 
     def _level_block(tf: list, pos: int, sr: int):
         """The run of level elements of ``tf`` from ``pos`` on -- ``Volume`` | ``Clipping`` | ``Resample(sr -> k sr) Clipping
@@ -992,61 +911,118 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 return False, pos
         return (steps or None), pos
 
-    def pending_level_chain(cut, gpu_reverb: bool = True, gpu_resample: bool = True):
-        """The rule of the level route: a mono cut (no video) over a recording whose transform list is
+    def _parse_transforms(tf, sr: int, gpu_speed: bool, gpu_reverb: bool, gpu_resample: bool, gpu_level: bool, bankless: bool) -> Optional[Chain]:
+        """ONE walk over a recording's transform list, left to right, for ``parse_chain`` (a mono cut) and ``pending_channel_chain`` (a
+        ``MultiCut``: ``gpu_reverb`` and ``gpu_level`` off).  An element whose switch is off is not taken, and whatever is left over at the
+        end refuses the list."""
+        tf, pos = list(tf or []), 0
+        src, factor, pre, reverb, post = None, 1.0, None, None, None
+        if tf and _transform_name(tf[0]) == "Resample" and _resample_rates(tf[0])[0] != sr:  # cuts.resample(sr); one FROM sr opens a bracket
+            src, dst = _resample_rates(tf[0])
+            if not gpu_resample or dst != sr or src <= 0:
+                return None
+            from lhotse.audio.resampling_backend import get_current_resampling_backend  # the reference's own switch is the contract
+
+            if get_current_resampling_backend() != "default":
+                return None
+            if resample_route(src, dst) is None if bankless else _sinc_bank_floats(src, dst) > MAX_RESAMPLE_BANK_FLOATS:
+                return None
+            pos = 1
+        if pos < len(tf) and _transform_name(tf[pos]) == "Speed":
+            factor = float(_kwargs_of(tf[pos], ("factor",))["factor"])
+            if factor != 1.0 and not gpu_speed:
+                return None
+            pos += 1
+        if gpu_level:
+            pre, pos = _level_block(tf, pos, sr)
+            if pre is False:
+                return None
+        if gpu_reverb and pos < len(tf) and _transform_name(tf[pos]) == "ReverbWithImpulseResponse":
+            kw = _kwargs_of(tf[pos], ("rir", "normalize_output", "early_only", "rir_channels"))
+            if kw.get("rir") is None or len(kw.get("rir_channels") or [0]) != 1:
+                return None
+            reverb = {"rir": kw["rir"], "normalize_output": bool(kw.get("normalize_output", True)), "early_only": bool(kw.get("early_only", False)),
+                      "rir_channels": [int(c) for c in (kw.get("rir_channels") or [0])]}
+            pos += 1
+        if gpu_level:
+            post, pos = _level_block(tf, pos, sr)
+            if post is False:
+                return None
+        if pos != len(tf):
+            return None
+        if any(st[0] != "level" for st in (pre or []) + (post or [])) and not (gpu_resample and _reference_resamples_with_sinc()):
+            return None  # (a bracket runs the device's sinc resampler: only where the reference's Resample runs its own)
+        return Chain(src, factor, pre, reverb, post)
+
+    def parse_chain(cut, gpu_speed: bool = True, gpu_reverb: bool = True, gpu_resample: bool = True, gpu_level: bool = True,
+                    bankless: bool = False) -> Optional[Chain]:
+        """THE rule of what the device takes over: a mono cut (no video) over a recording whose transform list is
 
             [Resample(a -> sr)]? [Speed]? L? [ReverbWithImpulseResponse]? L?
             L = ( Volume | Clipping | Resample(sr -> k sr) Clipping Resample(k sr -> sr) | B ){1 ... 4 ops, at most one Clipping}
             B = Resample(sr -> m) Resample(m -> sr), m != sr: the band bracket of LowpassUsingResampling (m = 2 x cutoff); two ops
 
-        with at least one level op or bracket -> ``(a or None, factor still to be applied (1.0 = none), the reverb's kwargs or None, (the steps of
-        the L in front of the reverb or None, of the L behind it or None))``; the first three are ``pending_chain``'s answer for the
-        chain without its level ops.  The bracketed form is what ``clip_amplitude(oversampling=k)`` appends (recording.py:937-975), k an
-        integer 2 ... 8; it needs ``gpu_resample`` and a reference that resamples with its sinc module (``_reference_resamples_with_sinc``).  Steps: ``("level", [("volume", factor) | ("clip", hard, gain_db, normalize), ...])``,
-        ``("up", k)``, ``("down", k)``, and for a band bracket ``("rate", sr, m)``, ``("rate", m, sr)`` -- any rates: ``resample_in_arena`` routes each pair to its dense bank or to the bankless kernel; the preconditions are the oversampling bracket's -- (``FusedMiniBatch.features_of_tracks``).  None = not this rule's business -- a chain without a level
-        op, which the older rules decide -- or not served: anything but a ``MonoCut`` (a ``MultiCut``, a ``MixedCut`` as a whole), a recording
-        with more than one channel (also when the ``MonoCut`` selects one of them), a level op in front of the ``Speed`` or the leading ``Resample``, a block of
-        more than 4 ops or with two ``Clipping``s, k outside 2 ... 8, anything else in the list, and whatever ``pending_chain`` refuses
-        in the rest."""
-        if not _has_level_op(cut) or getattr(cut.recording, "has_video", False) or cut.recording.num_channels != 1:
-            return None  # (a MonoCut over one channel of a multi-channel recording is left to the reference too: level ops there are out of scope)
-        tf = list(cut.recording.transforms)
-        sr, pos = int(cut.sampling_rate), 0
-        if _transform_name(tf[pos]) == "Resample" and _resample_rates(tf[pos])[0] != sr:  # cuts.resample(sr); one FROM sr opens a bracket
-            pos += 1
-        if pos < len(tf) and _transform_name(tf[pos]) == "Speed":
-            pos += 1
-        rest = tf[:pos]
-        pre, pos = _level_block(tf, pos, sr)
-        if pre is False:
-            return None
-        if pos < len(tf) and _transform_name(tf[pos]) == "ReverbWithImpulseResponse":
-            rest.append(tf[pos])
-            pos += 1
-        post, pos = _level_block(tf, pos, sr)
-        if post is False or pos != len(tf) or (pre is None and post is None):
-            return None
-        if any(st[0] != "level" for st in (pre or []) + (post or [])) and not (gpu_resample and _reference_resamples_with_sinc()):
-            return None  # (the oversampling runs the device's sinc resampler: only where the reference's Resample runs its own)
-        from lhotse.utils import fastcopy
+        -> its ``Chain``; an empty list gives ``Chain()``, with nothing ``pending``.  None = load it the reference's way.  Every element
+        has its switch and its conditions:
 
-        chain = pending_chain(fastcopy(cut, recording=fastcopy(cut.recording, transforms=rest)), gpu_reverb, gpu_resample, bankless=True)
-        return None if chain is None else (chain[0], chain[1], chain[2], (pre, post))
+        * the leading ``Resample`` (``cuts.resample(sr)``): ``gpu_resample``; ``sr == cut.sampling_rate``, ``a != sr``; the reference's
+          ``default`` resampling backend (``sox``: another filter); a reduced filter bank of at most 2^20 floats -- or, with ``bankless``
+          as the strategies set it, any pair of rates that ``resample_in_arena`` routes (``resample_route``: 11127 -> 16000 goes to the
+          kernel without a bank);
+        * the ``Speed``: ``gpu_speed`` unless its factor is 1;
+        * the reverb: ``gpu_reverb``; a recorded ``rir`` (not the random generator) and exactly one entry in ``rir_channels``;
+        * the level blocks: ``gpu_level`` and a recording of ONE channel (a ``MonoCut`` that selects one channel of several is left to the
+          reference); k an integer 2 ... 8 (what ``clip_amplitude(oversampling=k)`` appends, recording.py:937-975); the rate steps of either
+          bracket need ``gpu_resample``, a route for each pair of rates and a reference that resamples with its sinc module
+          (``_reference_resamples_with_sinc``).
 
-    def _read_level_track(cut, lc, offset: int = 0, snr=None, is_ref: bool = True) -> Optional[tuple]:
-        """The 9-element track of ``FusedMiniBatch.features_of_tracks`` for a cut with level ops (``lc`` = ``pending_level_chain(cut)``),
-        or None when the chain's output would be shorter than the cut (it would need reflect-padding: the rule of ``_read_one``)."""
-        source_rate, factor, rv, blocks = lc
-        sr = cut.sampling_rate
-        raw = read_before_chain(cut)
-        want = compute_num_samples(cut.duration, sr)
-        if chain_num_samples(len(raw), source_rate, factor, sr, blocks) < want:
+        Refused with it: anything but a ``MonoCut`` (a ``MultiCut``: ``pending_channel_chain``; a ``MixedCut``: ``deferred_mix``), any other
+        transform, any other order (a ``Resample`` that is not first, a level op in front of the ``Speed``, a reverb in front of a
+        ``Speed``, two reverbs), a block of more than 4 ops or with two ``Clipping``s."""
+        if type(cut).__name__ != "MonoCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
             return None
-        return (raw, factor, offset, snr, is_ref, want, None if rv is None else (load_reverb_rir(rv), rv["normalize_output"]), source_rate, blocks)
+        return _parse_transforms(cut.recording.transforms, int(cut.sampling_rate), gpu_speed, gpu_reverb, gpu_resample,
+                                 gpu_level and cut.recording.num_channels == 1, bankless)
+
+    def pending_channel_chain(cut, gpu_speed: bool = True, gpu_resample: bool = True):
+        """``parse_chain`` for a cut of SEVERAL channels: a ``MultiCut`` (no video, 1 ... 32 channels) over a recording whose transform
+        list is ``[Resample(a -> sr)]? [Speed]?`` -- the same walk with ``bankless``, without a reverb and level blocks -- or a ``MixedCut``
+        (no transforms of its own, no video) whose audible tracks are ONE such ``MultiCut`` and ``PaddingCut``s, none with an SNR
+        (``cut.pad``, to the right or to the left) -> ``(the MultiCut, a or None, factor still to be applied (1.0 = none), the samples of
+        padding in front of it, the cut's own num_samples or None when it is not padded)``.  None = load it the reference's way: any other
+        transform (``Volume``, ``Clipping``, a reverb, a ``Resample`` that is not first or a bracket of two), more than 32 channels, a
+        multi-channel track that is mixed with audio, a padded cut whose tracks do not add up to its length (deferred_mix's rule)."""
+        if type(cut).__name__ == "MixedCut":
+            if not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
+                return None
+            from lhotse.audio.utils import get_audio_duration_mismatch_tolerance
+            from lhotse.cut.mixed import _get_audible_tracks
+
+            sr = cut.sampling_rate
+            tracks = _get_audible_tracks(cut)
+            data = [t for t in tracks if type(t.cut).__name__ != "PaddingCut"]
+            if len(data) != 1 or type(data[0].cut).__name__ != "MultiCut" or any(t.snr is not None or t.cut.sampling_rate != sr for t in tracks):
+                return None
+            inner = pending_channel_chain(data[0].cut, gpu_speed, gpu_resample)
+            if inner is None:
+                return None
+            off = compute_num_samples(data[0].offset, sr)
+            total = max(compute_num_samples(t.offset, sr) + compute_num_samples(t.cut.duration, sr) for t in tracks)
+            diff = total - cut.num_samples
+            if diff < 0 or diff >= max(1, compute_num_samples(get_audio_duration_mismatch_tolerance(), sampling_rate=sr)):
+                return None
+            return inner[0], inner[1], inner[2], off, int(cut.num_samples)
+        if type(cut).__name__ != "MultiCut" or not cut.has_recording or getattr(cut.recording, "has_video", False):
+            return None
+        channels = cut.channel if isinstance(cut.channel, (list, tuple)) else [cut.channel]
+        if not 1 <= len(channels) <= MAX_CHANNELS:
+            return None
+        chain = _parse_transforms(cut.recording.transforms, int(cut.sampling_rate), gpu_speed, False, gpu_resample, False, True)
+        return None if chain is None else (cut, chain.source_rate, chain.factor, 0, None)
 
     def chain_num_samples(num_samples: int, source_rate: Optional[int], factor: float, sampling_rate: int, blocks=None) -> int:
         """Samples that come out of ``[Resample(source_rate -> sr)]? [Speed(factor)]?`` and the rate steps of the level ``blocks`` behind
-        them (``pending_level_chain``: the two stages of a band bracket; an oversampling bracket gives back what it took; the level
+        them (``Chain.levels``: the two stages of a band bracket; an oversampling bracket gives back what it took; the level
         ops and the reverb keep the length) for ``num_samples`` going in: per stage ``ceil(new * n / orig)`` in float32 with the rates
         reduced by their gcd (resample.py:219-222, :309)."""
         sr = int(sampling_rate)
@@ -1063,9 +1039,9 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         return n
 
     def read_before_chain(cut) -> np.ndarray:
-        """``read_unperturbed`` for the whole pending chain: the segment of the ORIGINAL audio that ``Recording.load_audio`` reads for this
-        cut before it applies the recording's transforms (lhotse/audio/recording.py:412-467) -- the backward pass over ALL of them with
-        the reference's own objects (recording.py:436-444), then the same per-source reads."""
+        """The segment of the ORIGINAL audio that ``Recording.load_audio`` reads for this cut before it applies the recording's
+        transforms (lhotse/audio/recording.py:412-467) -- the backward pass over ALL of them with the reference's own objects
+        (recording.py:436-444), then the same per-source reads -> ``(T,)`` for a ``MonoCut``, ``(C, T)`` for a ``MultiCut``."""
         from lhotse.augmentation import AudioTransform  # the reference's own classes: their reverse_timestamps are the contract
 
         rec = cut.recording
@@ -1075,29 +1051,36 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         transforms = [t if isinstance(t, AudioTransform) else AudioTransform.from_dict(t) for t in rec.transforms or []]
         for t in reversed(transforms):
             offset, duration = t.reverse_timestamps(offset=offset, duration=duration, sampling_rate=rec.sampling_rate)
+        multi = isinstance(cut.channel, (list, tuple))
+        channels = frozenset(cut.channel if multi else [cut.channel])
         per_source = []
         for source in rec.sources:
-            if cut.channel not in source.channels:
+            if not channels.intersection(source.channels):
                 continue
             samples = source.load_audio(offset=offset, duration=duration, force_opus_sampling_rate=rec.sampling_rate)
-            drop = [i for i, cid in enumerate(source.channels) if cid != cut.channel]
+            drop = [i for i, cid in enumerate(source.channels) if cid not in channels]
             if drop:
                 samples = np.delete(samples, drop, axis=0)
             per_source.append(samples)
-        audio = rec._stack_audio_channels(per_source)
-        return np.ascontiguousarray(audio.reshape(-1), dtype=np.float32)
+        audio = np.ascontiguousarray(rec._stack_audio_channels(per_source), dtype=np.float32)
+        return audio if multi else audio.reshape(-1)
 
-    def _read_chain_track(cut, chain, offset: int = 0, snr=None, is_ref: bool = True) -> Optional[tuple]:
-        """The 8-element track of ``FusedMiniBatch.features_of_tracks`` for a cut with a pending ``Resample`` (``chain`` =
-        ``pending_chain(cut)``), or None when the chain's output would be shorter than the cut (it would need reflect-padding: the
-        rule of ``_read_one``)."""
-        source_rate, factor, rv = chain
-        sr = cut.sampling_rate
-        raw = read_before_chain(cut)
-        want = compute_num_samples(cut.duration, sr)
-        if chain_num_samples(len(raw), source_rate, factor, sr) < want:
-            return None
-        return (raw, factor, offset, snr, is_ref, want, None if rv is None else (load_reverb_rir(rv), rv["normalize_output"]), source_rate)
+    def _read_channels(cut, chain, suppress_errors: bool):
+        """The entry of ``FusedAudioBatch.audio_of_channels`` for a cut ``pending_channel_chain`` serves (``chain`` = its answer):
+        ``(channel rows, factor, source rate, wanted samples, offset, total)``, read in front of the pending transforms -- or, when their
+        output would be shorter than the cut (it would need reflect-padding: the rule of ``_read_one``), the reference's own
+        ``load_audio`` of the ``MultiCut`` with nothing pending.  None when the read failed and errors are suppressed."""
+        with suppress_audio_loading_errors(enabled=suppress_errors):
+            data, src, factor, off, total = chain
+            sr = data.sampling_rate
+            want = compute_num_samples(data.duration, sr)
+            if src is not None or factor != 1.0:
+                raw = read_before_chain(data)
+                if chain_num_samples(raw.shape[-1], src, factor, sr) >= want:
+                    return list(raw), factor, src, want, off, total
+            audio = data.load_audio()
+            return list(np.ascontiguousarray(audio, dtype=np.float32)), 1.0, None, int(audio.shape[-1]), off, total
+        return None
 
     _RIR_CACHE: dict = {}
 
@@ -1121,110 +1104,58 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             hit = _RIR_CACHE[key] = load_rir(rir, spec["rir_channels"], spec["early_only"])[0]
         return hit
 
-    def read_unperturbed(cut, factor: float) -> np.ndarray:
-        """The segment of the ORIGINAL audio that ``Recording.load_audio`` reads for this cut before it applies ``Speed(factor)``
-        (lhotse/audio/recording.py:412-467): same backward pass over the timestamps, same per-source reads."""
-        from lhotse.augmentation import Speed  # the reference's own class: its reverse_timestamps is the contract
-
-        rec = cut.recording
-        offset, duration = cut.start, cut.duration
-        if duration is not None and isclose(duration, rec.duration, abs_tol=1e-3):
-            duration = None  # (recording.py:415-417)
-        offset_aug, duration_aug = Speed(factor=factor).reverse_timestamps(offset=offset, duration=duration, sampling_rate=rec.sampling_rate)
-        per_source = []
-        for source in rec.sources:
-            if cut.channel not in source.channels:
-                continue
-            samples = source.load_audio(offset=offset_aug, duration=duration_aug, force_opus_sampling_rate=rec.sampling_rate)
-            drop = [i for i, cid in enumerate(source.channels) if cid != cut.channel]
-            if drop:
-                samples = np.delete(samples, drop, axis=0)
-            per_source.append(samples)
-        audio = rec._stack_audio_channels(per_source)
-        return np.ascontiguousarray(audio.reshape(-1), dtype=np.float32)
-
-    def _read_before_transforms(cut, factor: float) -> Optional[np.ndarray]:
-        """The samples in front of the cut's pending transforms: ``read_unperturbed`` in front of a ``Speed`` (None when the resampled
-        segment would need reflect-padding, the rule of ``_read_one``), the plain segment of the file otherwise."""
+    def _read_track(cut, chain: Chain, offset: int = 0, snr=None, is_ref: bool = True) -> Optional[Track]:
+        """The ``Track`` of a mono cut read in front of its ``chain``, or None when the chain's output would be shorter than the cut (it
+        would need reflect-padding: the reference's own path).  A chain that keeps the length is read through ``load_audio()`` of the
+        cut without its transforms, which fixes the sample count the way the reference does (``assert_and_maybe_fix_num_samples``)."""
         sr = cut.sampling_rate
-        if factor == 1.0:
+        want = compute_num_samples(cut.duration, sr)
+        if chain.keeps_length:
             from lhotse.utils import fastcopy
 
-            plain = fastcopy(cut, recording=fastcopy(cut.recording, transforms=None))
-            return np.ascontiguousarray(plain.load_audio().reshape(-1), dtype=np.float32)
-        raw = read_unperturbed(cut, factor)
-        src, dst = round(sr * factor), sr
-        g = gcd(src, dst)
-        if int(np.ceil(np.float32((dst // g) * len(raw) / (src // g)))) < compute_num_samples(cut.duration, sr):  # resample.py:309
-            return None
-        return raw
+            raw = np.ascontiguousarray(fastcopy(cut, recording=fastcopy(cut.recording, transforms=None)).load_audio().reshape(-1), dtype=np.float32)
+        else:
+            raw = read_before_chain(cut)
+            if chain_num_samples(len(raw), chain.source_rate, chain.factor, sr, chain.levels) < want:
+                return None
+        rv = chain.reverb
+        return Track(raw, chain.factor, offset, snr, is_ref, want, None if rv is None else (load_reverb_rir(rv), rv["normalize_output"]),
+                     chain.source_rate, chain.levels)
 
     def _read_one(cut, gpu_speed: bool, suppress_errors: bool, gpu_mix: bool = False, gpu_reverb: bool = False,
                   gpu_resample: bool = False, gpu_level: bool = False) -> Optional[Tuple[torch.Tensor, float, int]]:
         """(samples, factor still to be applied, samples the cut must end up with) or None when the read failed and errors are suppressed.
-        For a mixed cut the device will mix, and for a cut the device will reverberate, ``samples`` is the list of its loaded tracks
-        (``FusedMiniBatch.features_of_tracks``); a failed track drops the cut."""
+        For a mixed cut the device will mix, and for a cut with more than a ``Speed`` pending, ``samples`` is the list of its loaded tracks
+        (``FusedMiniBatch.features_of_tracks``); a failed track drops the cut.  Whatever the rule refuses, and whatever would come out
+        short of the cut (the reference reflect-pads it), is ``cut.load_audio()``."""
         with suppress_audio_loading_errors(enabled=suppress_errors):
-            tracks = deferred_mix(cut, gpu_reverb, gpu_resample=gpu_resample, gpu_level=gpu_level) if gpu_mix else None
-            if tracks is not None and (gpu_speed or all(t[1] in (None, 1.0) for t in tracks)):
-                res = _read_tracks(cut, tracks)
-                if res is not None:
-                    return res
-            lc = pending_level_chain(cut, gpu_reverb, gpu_resample) if gpu_level else None
-            if lc is not None and (gpu_speed or lc[1] == 1.0):  # level ops in the chain: the cut is one track
-                track = _read_level_track(cut, lc)
-                if track is not None:
-                    return [track], 1.0, track[5]
-            chain = pending_chain(cut, gpu_reverb, bankless=True) if gpu_resample else None
-            if chain is not None and chain[0] is not None and (gpu_speed or chain[1] == 1.0):  # a Resample in front: the cut is one track
-                track = _read_chain_track(cut, chain)
-                if track is not None:
-                    return [track], 1.0, track[5]
-            rv = deferred_reverb(cut, gpu_reverb)
-            if rv is not None and (gpu_speed or rv[0] == 1.0):
-                raw = _read_before_transforms(cut, rv[0])
-                if raw is not None:
-                    want = compute_num_samples(cut.duration, cut.sampling_rate)
-                    return [(raw, rv[0], 0, None, True, want, (load_reverb_rir(rv[1]), rv[1]["normalize_output"]))], 1.0, want
-            factor = deferred_speed_factor(cut) if gpu_speed else None
-            if factor is not None and factor != 1.0:
-                raw = read_unperturbed(cut, factor)
-                want = compute_num_samples(cut.duration, cut.sampling_rate)
-                src, dst = round(cut.sampling_rate * factor), cut.sampling_rate
-                g = gcd(src, dst)
-                got = int(np.ceil(np.float32((dst // g) * len(raw) / (src // g))))  # resample.py:309
-                if got >= want:  # the usual case: equal, or a sample or two to truncate (assert_and_maybe_fix_num_samples, recording.py:1032-1070)
-                    return torch.from_numpy(raw), factor, want
-                # (the cut would need reflect-padding: the reference's own path)
+            switches = dict(gpu_speed=gpu_speed, gpu_reverb=gpu_reverb, gpu_resample=gpu_resample, gpu_level=gpu_level)
+            tracks = deferred_mix(cut, **switches) if gpu_mix else None
+            res = None if tracks is None else _read_tracks(cut, tracks)
+            if res is not None:
+                return res
+            chain = parse_chain(cut, bankless=True, **switches)
+            track = _read_track(cut, chain) if chain is not None and chain.pending else None
+            if track is not None:
+                if chain == Chain(factor=chain.factor):  # a Speed and nothing else: the mini-batch may take the route of features_of
+                    return torch.from_numpy(track.samples), chain.factor, track.cap
+                return [track], 1.0, track.cap
             audio = cut.load_audio()
             if audio.shape[0] == 1:
                 audio = audio.squeeze(0)  # collapse channel dim if mono (collation.py:674-675)
             return torch.from_numpy(audio), 1.0, int(audio.shape[-1])
         return None
 
-    def _has_pending_resample(cut) -> bool:
-        tf = cut.recording.transforms if type(cut).__name__ == "MonoCut" and cut.has_recording else None
-        return bool(tf) and _transform_name(tf[0]) == "Resample"
-
-    def _pending_speed(cut, gpu_reverb: bool = True) -> Optional[float]:
-        """1.0 for a mono cut over a recording without a pending ``Speed``, the factor when one is pending in front of nothing else or
-        of a reverb the device serves, None otherwise (``pending_transforms``)."""
-        p = pending_transforms(cut, gpu_reverb)
-        return None if p is None else p[0]
-
-    def deferred_mix(cut, gpu_reverb: bool = True, gpu_resample: bool = False, gpu_level: bool = False) -> Optional[List[tuple]]:
-        """The tracks of a ``MixedCut`` the device can mix -- ``[(track cut, factor, offset_samples, snr, is_reference)]`` over its audible
-        tracks, ``factor`` = None for a ``PaddingCut`` track -- or None: load it the reference's way (``cut.load_audio()``).  Decided on
-        the host before anything is read.  Refused: anything but a ``MixedCut`` with audio and without video or ``transforms`` of its own;
-        a track that is not a ``PaddingCut`` or a mono cut whose recording's transforms are ``[]``, ``[Speed]``, ``[Reverb]`` or
-        ``[Speed, Reverb]`` (``pending_transforms``: multi-channel cuts, nested mixed cuts, other transforms, a reverb the device does
-        not serve); tracks at another sampling rate; no determinable, a muted or a padding SNR
+    def deferred_mix(cut, gpu_reverb: bool = True, gpu_resample: bool = False, gpu_level: bool = False, gpu_speed: bool = True) -> Optional[List[PendingTrack]]:
+        """The tracks of a ``MixedCut`` the device can mix -- a ``PendingTrack`` per audible track, ``chain`` = None for a ``PaddingCut``
+        track -- or None: load it the reference's way (``cut.load_audio()``).  Decided on the host before anything is read.  Refused:
+        anything but a ``MixedCut`` with audio and without video or ``transforms`` of its own; a track that is not a ``PaddingCut`` or a
+        mono cut that ``parse_chain`` serves under the same switches (with ``bankless``): multi-channel cuts, nested mixed cuts, other
+        transforms, a reverb the device does not serve; tracks at another sampling rate; no determinable, a muted or a padding SNR
         reference track; a first track with an SNR while the reference track is another one (the reference scales it through float64,
-        mixed.py:1346-1350); a mix that comes out shorter than ``cut.num_samples`` (reflect-
-        padded, mixed.py:1386-1387) or longer by lhotse's tolerance or more.  With ``gpu_resample`` a track may also carry a ``Resample`` in
-        front (``pending_chain``); such a track comes with two more elements, its reverb or None and its source rate.  (A perturbed track that would need reflect-padding is found when
-        it is read, as for a mono cut: ``_read_tracks`` returns None and the cut is loaded the reference's way.)  With ``gpu_level`` a track
-        may carry level ops (``pending_level_chain``); such a track has eight elements, the last one its level blocks."""
+        mixed.py:1346-1350); a mix that comes out shorter than ``cut.num_samples`` (reflect-padded, mixed.py:1386-1387) or longer by
+        lhotse's tolerance or more.  (A perturbed track that would need reflect-padding is found when it is read, as for a mono cut:
+        ``_read_tracks`` returns None and the cut is loaded the reference's way.)"""
         if type(cut).__name__ != "MixedCut" or not cut.has_recording or cut.transforms or getattr(cut, "has_video", False):
             return None
         from lhotse.audio.utils import get_audio_duration_mismatch_tolerance
@@ -1245,82 +1176,36 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             c = t.cut
             if c.sampling_rate != sr:
                 return None
-            if type(c).__name__ == "PaddingCut":
-                factor = None
-                chain = None
-            elif gpu_level and _has_level_op(c):
-                lc = pending_level_chain(c, gpu_reverb, gpu_resample)
-                if lc is None:
-                    return None
-                off = compute_num_samples(t.offset, sr)
-                total = max(total, off + compute_num_samples(c.duration, sr))
-                out.append((c, lc[1], off, t.snr, t is ref, lc[2], lc[0], lc[3]))  # (reverb or None, source rate or None, level blocks)
-                continue
-            elif gpu_resample and _has_pending_resample(c):
-                chain = pending_chain(c, gpu_reverb, bankless=True)
+            chain = None
+            if type(c).__name__ != "PaddingCut":
+                chain = parse_chain(c, gpu_speed, gpu_reverb, gpu_resample, gpu_level, bankless=True)
                 if chain is None:
-                    return None
-                factor = chain[1]
-            else:
-                chain = None
-                factor = _pending_speed(c, gpu_reverb)
-                if factor is None:
                     return None
             off = compute_num_samples(t.offset, sr)
             total = max(total, off + compute_num_samples(c.duration, sr))
-            if chain is not None:
-                out.append((c, factor, off, t.snr, t is ref, chain[2], chain[0]))  # (the track's reverb or None, its source rate)
-                continue
-            rv = None if factor is None else deferred_reverb(c, gpu_reverb)
-            out.append((c, factor, off, t.snr, t is ref) + (() if rv is None else (rv[1],)))  # (a 6th element: the track's reverb)
+            out.append(PendingTrack(c, off, t.snr, t is ref, chain))
         diff = total - cut.num_samples
         if diff < 0 or diff >= max(1, compute_num_samples(get_audio_duration_mismatch_tolerance(), sampling_rate=sr)):
             return None
         return out
 
-    def _read_tracks(cut, tracks) -> Optional[Tuple[list, float, int]]:
-        """The tracks of an eligible mixed cut, each loaded the way a mono cut is (``load_audio`` / ``read_unperturbed``); None when a
+    def _read_tracks(cut, tracks: List[PendingTrack]) -> Optional[Tuple[List[Track], float, int]]:
+        """The tracks of an eligible mixed cut, each loaded the way a mono cut is (``load_audio`` / ``_read_track``); None when a
         perturbed track would need reflect-padding (the rule of ``_read_one``)."""
         sr = cut.sampling_rate
         loaded = []
-        for tr in tracks:
-            c, factor, off, snr, is_ref = tr[:5]
+        for c, off, snr, is_ref, chain in tracks:
             n = compute_num_samples(c.duration, sr)
-            if factor is None:
-                loaded.append((n, 1.0, off, snr, is_ref, n))
-            elif len(tr) > 7:  # level ops somewhere in the chain
-                track = _read_level_track(c, (tr[6], factor, tr[5], tr[7]), off, snr, is_ref)
-                if track is None:
-                    return None
-                loaded.append(track)
-            elif len(tr) > 6:  # a Resample in front of the (possibly pending) Speed and reverb
-                track = _read_chain_track(c, (tr[6], factor, tr[5]), off, snr, is_ref)
-                if track is None:
-                    return None
-                loaded.append(track)
-            elif len(tr) > 5:  # a reverb behind the (possibly pending) Speed
-                raw = _read_before_transforms(c, factor)
-                if raw is None:
-                    return None
-                loaded.append((raw, factor, off, snr, is_ref, n, (load_reverb_rir(tr[5]), tr[5]["normalize_output"])))
-            elif factor != 1.0:
-                raw = read_unperturbed(c, factor)
-                src, dst = round(sr * factor), sr
-                g = gcd(src, dst)
-                if int(np.ceil(np.float32((dst // g) * len(raw) / (src // g)))) < n:  # resample.py:309
-                    return None
-                loaded.append((raw, factor, off, snr, is_ref, n))
+            if chain is None:
+                loaded.append(Track(n, 1.0, off, snr, is_ref, n))
+            elif not chain.pending:
+                loaded.append(Track(np.ascontiguousarray(c.load_audio().reshape(-1), dtype=np.float32), 1.0, off, snr, is_ref, n))
             else:
-                loaded.append((np.ascontiguousarray(c.load_audio().reshape(-1), dtype=np.float32), 1.0, off, snr, is_ref, n))
+                track = _read_track(c, chain, off, snr, is_ref)
+                if track is None:
+                    return None
+                loaded.append(track)
         return loaded, 1.0, int(cut.num_samples)
-
-    def _reference_resamples_with_sinc() -> bool:
-        """Whether lhotse's ``Resample.__call__`` would run ``ResampleTensor`` (the sinc resampler the device implements): torchaudio
-        importable and the resampling backend ``default`` (lhotse/augmentation/torchaudio.py:108-139)."""
-        import lhotse.augmentation.torchaudio as ref  # (looked up on the module: the very name Resample.__call__ consults)
-        from lhotse.audio.resampling_backend import get_current_resampling_backend
-
-        return bool(ref.is_torchaudio_available()) and get_current_resampling_backend() == "default"
 
     class _ChainReader:
         """The reading half of ``HipOnTheFlyFeatures`` and ``HipAudioSamples``: the cuts of a mini-batch as read in front of the transforms
@@ -1330,12 +1215,13 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         def _read(self, cuts, pool, recording_field):
             """read_audio_from_cuts (lhotse/dataset/collation.py:541-600) with the Speed of eligible cuts left for the device."""
             cuts = list(cuts)
-            on_device = recording_field is None and (
-                (self.gpu_speed_perturb and any(deferred_speed_factor(c) not in (None, 1.0) for c in cuts))
-                or (self.gpu_mix and any(type(c).__name__ == "MixedCut" for c in cuts))
-                or (self.gpu_reverb and any(deferred_reverb(c) is not None for c in cuts))
-                or (self.gpu_resample and any(_has_pending_resample(c) for c in cuts))
-                or (self.gpu_level and any(_has_level_op(c) for c in cuts)))
+            switches = dict(gpu_speed=self.gpu_speed_perturb, gpu_reverb=self.gpu_reverb, gpu_resample=self.gpu_resample, gpu_level=self.gpu_level)
+
+            def pending(cut) -> bool:
+                chain = parse_chain(cut, bankless=True, **switches)
+                return chain is not None and chain.pending
+
+            on_device = recording_field is None and any((self.gpu_mix and type(c).__name__ == "MixedCut") or pending(c) for c in cuts)
             if not on_device:
                 audios, ok = read_audio_from_cuts(cuts, executor=pool, suppress_errors=self.fault_tolerant, recording_field=recording_field)
                 return audios, [1.0] * len(audios), [int(a.shape[-1]) for a in audios], ok
@@ -1345,8 +1231,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
 
             map_fn = map if pool is None else pool.map
             audios, factors, wants, ok = [], [], [], []
-            read = partial(_read_one, gpu_speed=self.gpu_speed_perturb, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix,
-                           gpu_reverb=self.gpu_reverb, gpu_resample=self.gpu_resample, gpu_level=self.gpu_level)
+            read = partial(_read_one, suppress_errors=self.fault_tolerant, gpu_mix=self.gpu_mix, **switches)
             for cut, res in zip(cuts, map_fn(read, cuts)):
                 if res is None:
                     continue
@@ -1404,15 +1289,15 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             audios, factors, wants, cuts = self._read(cuts, pool, recording_field)
             mixed = any(isinstance(a, list) for a in audios)  # (the loaded tracks of the cuts the device mixes)
             for transform in self.wave_transforms:
-                if any(isinstance(a, list) and any(_level_of(t) is not None for t in a) for a in audios):
+                if any(isinstance(a, list) and any(t.levels is not None for t in a) for a in audios):
                     raise ValueError("gpu_level=True was requested together with wave_transforms: the transforms run on the scaled and clipped "
                                      "samples, before the device scales and clips them; leave gpu_level at its default (None: "
                                      "Recording.load_audio whenever wave_transforms are given) or pass False")
-                if any(isinstance(a, list) and any(len(t) > 7 and t[7] is not None for t in a) for a in audios):
+                if any(isinstance(a, list) and any(t.source_rate is not None for t in a) for a in audios):
                     raise ValueError("gpu_resample=True was requested together with wave_transforms: the transforms run on the resampled "
                                      "samples, before the device resamples them; leave gpu_resample at its default (None: "
                                      "Recording.load_audio whenever wave_transforms are given) or pass False")
-                if any(isinstance(a, list) and any(_reverb_of(t) is not None for t in a) for a in audios):
+                if any(isinstance(a, list) and any(t.reverb is not None for t in a) for a in audios):
                     raise ValueError("gpu_reverb=True was requested together with wave_transforms: the transforms run on the reverberated "
                                      "samples, before the device convolves them; leave gpu_reverb at its default (None: "
                                      "Recording.load_audio whenever wave_transforms are given) or pass False")
@@ -1429,7 +1314,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             assert len(rates) == 1, f"one launch per batch needs a single sampling rate, got {sorted(rates)}"
             sr = rates.pop()
             if mixed:  # (FusedMiniBatch.features_of_tracks: a plain cut is a cut of one track)
-                tracks = [a if isinstance(a, list) else [(a, f, 0, None, True)] for a, f in zip(audios, factors)]
+                tracks = [a if isinstance(a, list) else [Track(a, f, 0, None, True)] for a, f in zip(audios, factors)]
                 feats, feat_lens, *audio = self._mix_and_extract(tracks, wants, sr)
             elif any(f != 1.0 for f in factors):  # (FusedMiniBatch.features_of, with the perturbed samples kept for `return_audio`)
                 feats, feat_lens, *audio = self._perturb_and_extract(audios, factors, wants, sr)
@@ -1515,7 +1400,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
                 if res is None:
                     return None
                 a, f, want = res
-                return (a if isinstance(a, list) else [(a, f, 0, None, True)]), 1.0, None, want, None, None
+                return (a if isinstance(a, list) else [Track(a, f, 0, None, True)]), 1.0, None, want, None, None
 
             entries, ok = [], []
             for cut, res in zip(cuts, map_fn(read, list(zip(cuts, chains)))):
@@ -1546,7 +1431,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             assert len(rates) == 1, f"one launch per batch needs a single sampling rate, got {sorted(rates)}"
             sr = rates.pop()
             if any(isinstance(a, list) for a in audios):  # (the loaded tracks of the cuts the device mixes, reverberates, resamples, scales)
-                tracks = [a if isinstance(a, list) else [(a, f, 0, None, True)] for a, f in zip(audios, factors)]
+                tracks = [a if isinstance(a, list) else [Track(a, f, 0, None, True)] for a, f in zip(audios, factors)]
                 audio, lens = self.batch.audio_of_tracks(tracks, wants, sr)
             else:
                 audio, lens = self.batch.audio_of(audios, factors, wants, sr)

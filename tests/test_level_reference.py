@@ -3,8 +3,8 @@
   * ``_level_ref.model32`` -- the numpy statement of the device's arithmetic -- is ``array_equal`` to the reference for SCALE and hard CLIP;
   * the peak-propagation identity: max |fl(fl(x f1) f2)| == fl(fl(max|x| |f1|) |f2|), on random data;
   * the silence threshold is the reference's ``20 * np.log10(p) < -96`` on float32, restated as one float32 number;
-  * ``pending_level_chain`` accepts every form of its grammar and refuses what it must, and every older rule function still answers None
-    for those cuts with its default arguments;
+  * ``parse_chain`` accepts every form of the level grammar and refuses what it must, and answers None for those cuts with the level
+    route off;
   * ``HipOnTheFlyFeatures`` with CPU stand-ins for the device reproduces the reference's features (and, for Volume / hard Clipping, its
     audio bit for bit) over level cuts, plain cuts, a speed-only cut and a mixed cut, and leaves the cuts without a level op exactly as a
     mini-batch without the level cuts leaves them."""
@@ -126,6 +126,14 @@ def _with_transforms(cut, transforms):
     return fastcopy(cut, recording=fastcopy(cut.recording, transforms=[t if isinstance(t, dict) else t.to_dict() for t in transforms]))
 
 
+def _level_chain(IS, cut, **kw):
+    """The rule's answer for a cut with a level block in its chain, as ``(source rate, factor, reverb, (block in front of the reverb, block
+    behind it))``; None: refused, or no level block (what the reader asks with ``bankless``)."""
+    ch = IS.parse_chain(cut, bankless=True, **kw)
+    assert ch is None or isinstance(ch, IS.Chain)
+    return None if ch is None or ch.levels is None else (ch.source_rate, ch.factor, ch.reverb, ch.levels)
+
+
 def test_pending_level_chain_accepts_its_grammar_and_refuses_the_rest(env, tmp_path, monkeypatch):
     import lhotse.augmentation.torchaudio as ref_ta
     from lhotse.augmentation import Clipping, Resample, Speed, Volume
@@ -138,26 +146,26 @@ def test_pending_level_chain_accepts_its_grammar_and_refuses_the_rest(env, tmp_p
     lvl = lambda *ops: ("level", list(ops))  # noqa: E731
 
     # every form of the grammar
-    assert IS.pending_level_chain(c.perturb_volume(0.5)) == (None, 1.0, None, ([lvl(vol)], None))
-    assert IS.pending_level_chain(c.clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None)) == (None, 1.0, None, ([lvl(clip)], None))
-    assert IS.pending_level_chain(c.clip_amplitude()) == (None, 1.0, None, ([("up", 2), lvl(("clip", False, 0.0, True)), ("down", 2)], None))
+    assert _level_chain(IS, c.perturb_volume(0.5)) == (None, 1.0, None, ([lvl(vol)], None))
+    assert _level_chain(IS, c.clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None)) == (None, 1.0, None, ([lvl(clip)], None))
+    assert _level_chain(IS, c.clip_amplitude()) == (None, 1.0, None, ([("up", 2), lvl(("clip", False, 0.0, True)), ("down", 2)], None))
     for k in (2, 4, 8):
-        got = IS.pending_level_chain(c.clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=k))
+        got = _level_chain(IS, c.clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=k))
         assert got == (None, 1.0, None, ([("up", k), lvl(clip), ("down", k)], None))
-    got = IS.pending_level_chain(c.perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=4).perturb_volume(2.0))
+    got = _level_chain(IS, c.perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=4).perturb_volume(2.0))
     assert got == (None, 1.0, None, ([lvl(vol), ("up", 4), lvl(clip), ("down", 4), lvl(("volume", 2.0))], None))
-    assert IS.pending_level_chain(c.perturb_speed(1.1).perturb_volume(0.5))[:2] == (None, 1.1)
+    assert _level_chain(IS, c.perturb_speed(1.1).perturb_volume(0.5))[:2] == (None, 1.1)
     full = c.perturb_speed(0.9).perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None).reverb_rir(rir).perturb_volume(2.0)
-    src, factor, rv, blocks = IS.pending_level_chain(full)
+    src, factor, rv, blocks = _level_chain(IS, full)
     assert (src, factor) == (None, 0.9) and rv["normalize_output"] is True and blocks == ([lvl(vol, clip)], [lvl(("volume", 2.0))])
-    assert IS.pending_level_chain(c.reverb_rir(rir).perturb_volume(0.5))[3] == (None, [lvl(vol)])
-    assert IS.pending_level_chain(c.perturb_volume(0.5).reverb_rir(rir))[3] == ([lvl(vol)], None)
+    assert _level_chain(IS, c.reverb_rir(rir).perturb_volume(0.5))[3] == (None, [lvl(vol)])
+    assert _level_chain(IS, c.perturb_volume(0.5).reverb_rir(rir))[3] == ([lvl(vol)], None)
     res = _with_transforms(c, [Resample(44100, SR), Speed(1.1), Volume(0.5)])
-    assert IS.pending_level_chain(res) == (44100, 1.1, None, ([lvl(vol)], None))
+    assert _level_chain(IS, res) == (44100, 1.1, None, ([lvl(vol)], None))
     four = c.perturb_volume(0.5).perturb_volume(0.5).perturb_volume(0.5).perturb_volume(0.5)
-    assert IS.pending_level_chain(four)[3] == ([lvl(vol, vol, vol, vol)], None)
+    assert _level_chain(IS, four)[3] == ([lvl(vol, vol, vol, vol)], None)
     # serialised transforms (dicts, as a manifest carries them) and objects give the same answer
-    assert IS.pending_level_chain(_with_transforms(c, [Volume(0.5), Clipping(True, 6.0, False)])) == (None, 1.0, None, ([lvl(vol, clip)], None))
+    assert _level_chain(IS, _with_transforms(c, [Volume(0.5), Clipping(True, 6.0, False)])) == (None, 1.0, None, ([lvl(vol, clip)], None))
 
     # what keeps cut.load_audio()
     refused = {
@@ -177,24 +185,23 @@ def test_pending_level_chain_accepts_its_grammar_and_refuses_the_rest(env, tmp_p
         "the random RIR generator": c.perturb_volume(0.5).reverb_rir(),
     }
     for why, cut in refused.items():
-        assert IS.pending_level_chain(cut) is None, why
-    assert IS.pending_level_chain(c.pad(duration=1.0).perturb_volume(0.5)) is None  # a MixedCut as a whole
-    assert IS.pending_level_chain(full, gpu_reverb=False) is None
-    assert IS.pending_level_chain(res, gpu_resample=False) is None
-    assert IS.pending_level_chain(c.clip_amplitude(), gpu_resample=False) is None
-    assert IS.pending_level_chain(c.clip_amplitude(oversampling=None), gpu_reverb=False, gpu_resample=False) is not None
+        assert _level_chain(IS, cut) is None, why
+    assert _level_chain(IS, c.pad(duration=1.0).perturb_volume(0.5)) is None  # a MixedCut as a whole
+    assert _level_chain(IS, full, gpu_reverb=False) is None
+    assert _level_chain(IS, res, gpu_resample=False) is None
+    assert _level_chain(IS, c.clip_amplitude(), gpu_resample=False) is None
+    assert _level_chain(IS, c.clip_amplitude(oversampling=None), gpu_reverb=False, gpu_resample=False) is not None
     monkeypatch.setattr(ref_ta, "is_torchaudio_available", lambda: False)  # the reference would oversample with scipy's resample_poly
-    assert IS.pending_level_chain(c.clip_amplitude()) is None and IS.pending_level_chain(c.clip_amplitude(oversampling=None)) is not None
+    assert _level_chain(IS, c.clip_amplitude()) is None and _level_chain(IS, c.clip_amplitude(oversampling=None)) is not None
     monkeypatch.setattr(ref_ta, "is_torchaudio_available", lambda: True)
 
-    # the older rules keep their answers on every cut the new rule takes
+    # with the level route off every cut it takes is the reference's, whatever else is on
     for cut in (c.perturb_volume(0.5), c.clip_amplitude(), c.clip_amplitude(oversampling=None), full, res, four):
-        assert IS.deferred_speed_factor(cut) is None and IS.pending_transforms(cut) is None and IS.pending_chain(cut) is None
-        assert IS.deferred_reverb(cut) is None
+        assert IS.parse_chain(cut, gpu_level=False) is None and IS.parse_chain(cut, gpu_level=False, bankless=True) is None
         mixed = cut.pad(duration=cut.duration + 0.1)
         assert IS.deferred_mix(mixed) is None and IS.deferred_mix(mixed, gpu_resample=True) is None
         tracks = IS.deferred_mix(mixed, gpu_resample=True, gpu_level=True)
-        assert tracks is not None and len(tracks[0]) == 8 and tracks[0][7] == IS.pending_level_chain(cut)[3]
+        assert tracks is not None and tracks[0].chain.levels == _level_chain(IS, cut)[3] and tracks[0].chain[:2] + (tracks[0].chain.reverb,) == _level_chain(IS, cut)[:3]
     padded = c.pad(duration=c.duration + 0.1)
     assert IS.deferred_mix(padded.perturb_volume(0.5), gpu_level=True) is not None  # (MixedCut.perturb_volume perturbs the tracks)
     from lhotse.utils import fastcopy
@@ -342,10 +349,10 @@ def test_multi_channel_recordings_keep_the_reference_path(env, tmp_path, stand_i
     mono = level(MonoCut(id="mono-of-two", start=0, duration=n / SR, channel=0, recording=rec))
     for cut in (multi, mono):
         assert IS._transform_name(cut.recording.transforms[0]) == "Volume" and IS._transform_name(cut.recording.transforms[1]) == "Clipping"
-        assert IS.pending_level_chain(cut) is None and IS.pending_transforms(cut) is None and IS.pending_chain(cut) is None
+        assert IS.parse_chain(cut) is None and IS.parse_chain(cut, bankless=True) is None and IS.parse_chain(cut, gpu_level=False) is None
     assert IS.deferred_mix(mono.pad(duration=0.3), gpu_resample=True, gpu_level=True) is None  # ... and the mix around such a track goes back with it
     ok = level(env[0])
-    assert IS.pending_level_chain(ok) is not None
+    assert _level_chain(IS, ok) is not None
     batch = CutSet.from_cuts([mono, ok])
     want = OnTheFlyFeatures(Fbank(), return_audio=True)(batch)
     got = LA.HipOnTheFlyFeatures(LA.HipFbank(LA.HipFbankConfig(edge_rule="batch_zero_pad")), return_audio=True)(batch)

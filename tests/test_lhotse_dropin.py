@@ -538,8 +538,8 @@ def test_on_the_fly_features_with_speed_perturbed_cuts(cutset, cpu_device, monke
 
     monkeypatch.setattr(IS, "_perturb_in_arena", cpu_perturb)
     calls = {"raw": 0}
-    real_read = IS.read_unperturbed
-    monkeypatch.setattr(IS, "read_unperturbed", lambda cut, f: (calls.__setitem__("raw", calls["raw"] + 1), real_read(cut, f))[1])
+    real_read = IS.read_before_chain
+    monkeypatch.setattr(IS, "read_before_chain", lambda cut: (calls.__setitem__("raw", calls["raw"] + 1), real_read(cut))[1])
 
     mixed = CutSet.from_cuts(list(cutset.perturb_speed(1.1)) + list(cutset) + list(cutset.perturb_speed(0.9))
                              + [c.truncate(offset=0.13, duration=0.41) for c in cutset.perturb_speed(0.9)][:2])
@@ -561,9 +561,10 @@ def test_on_the_fly_features_with_speed_perturbed_cuts(cutset, cpu_device, monke
     with pytest.raises(ValueError, match="gpu_speed_perturb=True was requested together with wave_transforms"):  # only the explicit contradiction
         LA.HipOnTheFlyFeatures(LA.HipFbank(), wave_transforms=[lambda x: x], gpu_speed_perturb=True)(mixed)
     # cuts whose recording carries anything but exactly one Speed are not touched
-    assert IS.deferred_speed_factor(list(cutset)[0]) is None
-    assert IS.deferred_speed_factor(list(cutset.perturb_speed(1.1).perturb_volume(2.0))[0]) is None
-    assert IS.deferred_speed_factor(list(cutset.perturb_speed(1.1))[0]) == 1.1
+    speed_only = lambda cut: IS.parse_chain(cut, gpu_reverb=False, gpu_resample=False, gpu_level=False)  # noqa: E731  (the other routes off)
+    assert not speed_only(list(cutset)[0]).pending
+    assert speed_only(list(cutset.perturb_speed(1.1).perturb_volume(2.0))[0]) is None
+    assert speed_only(list(cutset.perturb_speed(1.1))[0]) == IS.Chain(factor=1.1)
 
 
 def _lines(path):

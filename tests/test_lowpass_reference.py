@@ -1,7 +1,7 @@
 """CPU, under the real lhotse (authoring container only): the band bracket ``Resample(sr -> m) Resample(m -> sr)`` that
 ``LowpassUsingResampling`` (lhotse/dataset/cut_transforms/lowpass.py) appends, taken by the level rule.
 
-  * ``pending_level_chain`` takes every lowpassed cut -- alone, behind a ``Speed``, with ``Volume`` / ``Clipping``, around a reverb, as the
+  * ``parse_chain`` takes every lowpassed cut -- alone, behind a ``Speed``, with ``Volume`` / ``Clipping``, around a reverb, as the
     track of a mix -- and gives the expected steps; it refuses the counter-examples, each by its own case;
   * ``read_before_chain`` / ``chain_num_samples`` give the sample counts the reference's own transforms produce;
   * ``HipOnTheFlyFeatures`` with CPU stand-ins for the device (``_sinc_ref``, the banded float64 truth rounded to float32, in place of the
@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import _sinc_ref as SRF
-from test_level_reference import _rir, _with_transforms, cpu_level
+from test_level_reference import _level_chain, _rir, _with_transforms, cpu_level
 from test_resample_chain_reference import cpu_perturb, cpu_reverb
 
 SR = 16000
@@ -61,8 +61,8 @@ def test_the_transform_itself_appends_the_bracket_and_the_rule_takes_it(env):
         names = [IS._transform_name(t) for t in cut.recording.transforms]
         (a, m), (m2, b) = (IS._resample_rates(t) for t in cut.recording.transforms)
         assert names == ["Resample", "Resample"] and a == b == SR == cut.sampling_rate and m == m2 and 7000 <= m < 16000 and m % 2 == 0
-        assert IS.pending_level_chain(cut) == (None, 1.0, None, ([("rate", SR, m), ("rate", m, SR)], None)), cut.id
-        assert IS.pending_chain(cut) is None and IS.pending_transforms(cut) is None and IS.deferred_speed_factor(cut) is None  # the older rules
+        assert _level_chain(IS, cut) == (None, 1.0, None, ([("rate", SR, m), ("rate", m, SR)], None)), cut.id
+        assert IS.parse_chain(cut, gpu_level=False) is None and IS.parse_chain(cut, gpu_level=False, bankless=True) is None  # the level route off
 
 
 def test_pending_level_chain_accepts_the_bracket_in_its_grammar_and_refuses_the_rest(env, tmp_path, monkeypatch):
@@ -80,21 +80,21 @@ def test_pending_level_chain_accepts_the_bracket_in_its_grammar_and_refuses_the_
     rir = _rir(tmp_path)
     lvl = lambda *ops: ("level", list(ops))  # noqa: E731
     for cutoff in CUTOFFS:
-        assert IS.pending_level_chain(lowpass(c, cutoff)) == (None, 1.0, None, (band(cutoff), None))
-    assert IS.pending_level_chain(lowpass(c.perturb_speed(1.1), 4673)) == (None, 1.1, None, (band(4673), None))
-    got = IS.pending_level_chain(lowpass(c, 3501).perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None))
+        assert _level_chain(IS, lowpass(c, cutoff)) == (None, 1.0, None, (band(cutoff), None))
+    assert _level_chain(IS, lowpass(c.perturb_speed(1.1), 4673)) == (None, 1.1, None, (band(4673), None))
+    got = _level_chain(IS, lowpass(c, 3501).perturb_volume(0.5).clip_amplitude(hard=True, gain_db=6.0, normalize=False, oversampling=None))
     assert got == (None, 1.0, None, (band(3501) + [lvl(("volume", 0.5), ("clip", True, 6.0, False))], None))
-    got = IS.pending_level_chain(lowpass(c.perturb_volume(0.5), 3501).perturb_volume(2.0))  # four ops: Volume, the bracket (two), Volume
+    got = _level_chain(IS, lowpass(c.perturb_volume(0.5), 3501).perturb_volume(2.0))  # four ops: Volume, the bracket (two), Volume
     assert got[3] == ([lvl(("volume", 0.5))] + band(3501) + [lvl(("volume", 2.0))], None)
-    assert IS.pending_level_chain(lowpass(lowpass(c, 4673), 3501))[3] == (band(4673) + band(3501), None)  # two brackets: four ops
-    src, factor, rv, blocks = IS.pending_level_chain(lowpass(c, 7999).reverb_rir(rir))
+    assert _level_chain(IS, lowpass(lowpass(c, 4673), 3501))[3] == (band(4673) + band(3501), None)  # two brackets: four ops
+    src, factor, rv, blocks = _level_chain(IS, lowpass(c, 7999).reverb_rir(rir))
     assert (src, factor) == (None, 1.0) and rv["normalize_output"] is True and blocks == (band(7999), None)
-    assert IS.pending_level_chain(lowpass(c.reverb_rir(rir), 7999))[3] == (None, band(7999))
+    assert _level_chain(IS, lowpass(c.reverb_rir(rir), 7999))[3] == (None, band(7999))
     res = _with_transforms(c, [Resample(44100, SR), Resample(SR, 9346), Resample(9346, SR)])
-    assert IS.pending_level_chain(res) == (44100, 1.0, None, (band(4673), None))
+    assert _level_chain(IS, res) == (44100, 1.0, None, (band(4673), None))
     mixed = lowpass(c, 4673).pad(duration=c.duration + 0.1)
     tracks = IS.deferred_mix(mixed, gpu_resample=True, gpu_level=True)
-    assert tracks is not None and len(tracks[0]) == 8 and tracks[0][7] == (band(4673), None)
+    assert tracks is not None and tracks[0].chain == IS.Chain(pre=band(4673))
     assert IS.deferred_mix(mixed, gpu_resample=True) is None and IS.deferred_mix(mixed) is None  # without gpu_level: the reference's path
 
     # what keeps cut.load_audio(), each by its own case
@@ -114,18 +114,18 @@ def test_pending_level_chain_accepts_the_bracket_in_its_grammar_and_refuses_the_
         "a bracket in front of the Speed": lowpass(c, 4673).perturb_speed(1.1),
     }
     for why, cut in refused.items():
-        assert IS.pending_level_chain(cut) is None, why
+        assert _level_chain(IS, cut) is None, why
     ok = lowpass(c, 4673)
-    assert IS.pending_level_chain(ok, gpu_resample=False) is None
+    assert _level_chain(IS, ok, gpu_resample=False) is None
     monkeypatch.setattr(RB, "CURRENT_RESAMPLING_BACKEND", "sox")
-    assert IS.pending_level_chain(ok) is None
+    assert _level_chain(IS, ok) is None
     monkeypatch.setattr(RB, "CURRENT_RESAMPLING_BACKEND", "default")
     monkeypatch.setattr(ref_ta, "is_torchaudio_available", lambda: False)  # the reference would resample with scipy's resample_poly
-    assert IS.pending_level_chain(ok) is None
+    assert _level_chain(IS, ok) is None
     monkeypatch.setattr(ref_ta, "is_torchaudio_available", lambda: True)
-    assert IS.pending_level_chain(ok) is not None
+    assert _level_chain(IS, ok) is not None
     # the small pair is served too (its two stages go to the dense bank), and Volume alone is what it was
-    assert IS.pending_level_chain(_with_transforms(c, [Volume(0.5)])) == (None, 1.0, None, ([lvl(("volume", 0.5))], None))
+    assert _level_chain(IS, _with_transforms(c, [Volume(0.5)])) == (None, 1.0, None, ([lvl(("volume", 0.5))], None))
 
 
 def test_sample_counts_are_the_reference_s(env):
@@ -137,7 +137,7 @@ def test_sample_counts_are_the_reference_s(env):
     for cut, cutoff, factor in ((env[0], 4673, 1.0), (env[2], 3501, 1.0), (env[1], 7999, 1.0), (env[3], 4000, 1.0), (env[2].truncate(offset=0.05, duration=0.3), 4673, 1.0),
                                 (env[4], 5000, 0.9), (env[4], 6811, 1.1)):
         lp = lowpass(cut if factor == 1.0 else cut.perturb_speed(factor), cutoff)
-        lc = IS.pending_level_chain(lp)
+        lc = _level_chain(IS, lp)
         raw = IS.read_before_chain(lp)
         # the reference's own transforms over what was read, with its own objects
         y = raw[None, :]
@@ -146,8 +146,8 @@ def test_sample_counts_are_the_reference_s(env):
         n = IS.chain_num_samples(len(raw), lc[0], lc[1], SR, lc[3])
         want = compute_num_samples(lp.duration, SR)
         assert n == y.shape[1] and n >= want and len(lp.load_audio()[0]) == want, (cut.id, cutoff, factor, n, y.shape, want)
-        track = IS._read_level_track(lp, lc)
-        assert track is not None and track[5] == want and np.array_equal(track[0], raw)
+        track = IS._read_track(lp, IS.parse_chain(lp, bankless=True))
+        assert track is not None and track.cap == want and np.array_equal(track.samples, raw) and track.levels == lc[3]
     assert IS.chain_num_samples(1000, None, 1.0, SR, (band(4673), None)) == int(np.ceil(np.float32(8000 * int(np.ceil(np.float32(4673 * 1000 / 8000))) / 4673)))
     assert IS.chain_num_samples(1000, None, 1.0, SR, ([("up", 2), ("level", []), ("down", 2)], None)) == 1000 == IS.chain_num_samples(1000, None, 1.0, SR)
 
@@ -253,8 +253,8 @@ def test_the_route_with_stand_ins_is_within_the_audio_bar_of_the_reference(env, 
 
 
 def test_a_leading_resample_over_the_threshold_is_taken_where_the_strategies_ask_for_it(env, tmp_path, stand_ins, monkeypatch):
-    """``cuts.resample(16000)`` over a recording at 11130 Hz: 1113 : 1600, a bank of 1.8 M floats.  ``pending_chain`` keeps refusing it with
-    its default arguments; with ``bankless=True`` -- what the level rule, the reader and ``deferred_mix`` pass -- it is taken, alone, in
+    """``cuts.resample(16000)`` over a recording at 11130 Hz: 1113 : 1600, a bank of 1.8 M floats.  ``parse_chain`` keeps refusing it with
+    its default arguments; with ``bankless=True`` -- what the reader and ``deferred_mix`` pass -- it is taken, alone, in
     front of a ``Speed`` and of a band bracket, and as the track of a mix; what no kernel serves stays refused."""
     from lhotse import CutSet, MonoCut, Recording
     from lhotse.audio import AudioSource
@@ -272,17 +272,18 @@ def test_a_leading_resample_over_the_threshold_is_taken_where_the_strategies_ask
                     duration=len(pcm) / 11130)
     odd = MonoCut(id="odd", start=0, duration=rec.duration, channel=0, recording=rec).resample(SR)
     assert IS._sinc_bank_floats(11130, SR) > IS.MAX_RESAMPLE_BANK_FLOATS
-    assert IS.pending_chain(odd) is None and IS.pending_chain(odd, bankless=True) == (11130, 1.0, None)
-    assert IS.pending_chain(odd, gpu_resample=False, bankless=True) is None
-    assert IS.pending_chain(odd.perturb_speed(1.1), bankless=True) == (11130, 1.1, None)
-    assert IS.pending_level_chain(lowpass(odd, 4673)) == (11130, 1.0, None, (band(4673), None))
-    assert IS.pending_level_chain(odd.perturb_volume(0.5))[:3] == (11130, 1.0, None)
+    assert IS.parse_chain(odd) is None and IS.parse_chain(odd, gpu_level=False) is None
+    assert IS.parse_chain(odd, bankless=True) == IS.parse_chain(odd, gpu_level=False, bankless=True) == IS.Chain(source_rate=11130)
+    assert IS.parse_chain(odd, gpu_resample=False, bankless=True) is None
+    assert IS.parse_chain(odd.perturb_speed(1.1), bankless=True) == IS.Chain(11130, 1.1)
+    assert _level_chain(IS, lowpass(odd, 4673)) == (11130, 1.0, None, (band(4673), None))
+    assert _level_chain(IS, odd.perturb_volume(0.5))[:3] == (11130, 1.0, None)
     tracks = IS.deferred_mix(odd.pad(duration=odd.duration + 0.1), gpu_resample=True)
-    assert tracks is not None and tracks[0][6] == 11130
+    assert tracks is not None and tracks[0].chain == IS.Chain(source_rate=11130)
     up = fastcopy(odd, recording=fastcopy(odd.recording, transforms=[{"name": "Resample", "kwargs": {"source_sampling_rate": 2001, "target_sampling_rate": SR}}]))
-    assert IS.pending_chain(up, bankless=True) == (2001, 1.0, None)  # 2001 -> 16000 is served (W = 16); the other direction is not (W = 100):
+    assert IS.parse_chain(up, bankless=True) == IS.Chain(source_rate=2001)  # 2001 -> 16000 is served (W = 16); the other direction is not (W = 100):
     down = fastcopy(odd, recording=fastcopy(odd.recording, sampling_rate=2001, transforms=[{"name": "Resample", "kwargs": {"source_sampling_rate": SR, "target_sampling_rate": 2001}}]))
-    assert IS.pending_chain(down, bankless=True) is None
+    assert IS.parse_chain(down, bankless=True) is None
     batch = CutSet.from_cuts([odd, env[1], lowpass(odd, 3501), odd.perturb_speed(0.9)])
     want_f, want_l, want_a, want_al = OnTheFlyFeatures(Fbank(), return_audio=True)(batch)
     loads = []

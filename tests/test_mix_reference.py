@@ -67,7 +67,7 @@ def _tracks_for_rule(cut, IS):
     tracks = IS.deferred_mix(cut)
     assert tracks is not None
     loaded, _, want = IS._read_tracks(cut, tracks)
-    return [(x, off, snr) for x, _, off, snr, _, _ in loaded], next((k for k, t in enumerate(loaded) if t[4]), -1), want
+    return [(t.samples, t.offset, t.snr) for t in loaded], next((k for k, t in enumerate(loaded) if t.is_ref), -1), want
 
 
 @pytest.mark.reference
@@ -96,14 +96,14 @@ def test_deferred_mix_accepts_and_refuses(env):
     s, n = list(speech)[0], list(noise)[1]
     ok = s.mix(n, snr=15)
     tr = IS.deferred_mix(ok)
-    assert [(t[1], t[2], t[3], t[4]) for t in tr] == [(1.0, 0, None, True), (1.0, 0, 15, False)]
-    assert [t[1] for t in IS.deferred_mix(s.pad(duration=1.5))] == [1.0, None]  # a PaddingCut track
-    assert [t[1] for t in IS.deferred_mix(s.perturb_speed(1.1).mix(n, snr=15))] == [1.1, 1.0]  # exactly one Speed
+    assert [(t.chain.factor, t.offset, t.snr, t.is_ref) for t in tr] == [(1.0, 0, None, True), (1.0, 0, 15, False)]
+    assert [t.chain and t.chain.factor for t in IS.deferred_mix(s.pad(duration=1.5))] == [1.0, None]  # a PaddingCut track
+    assert [t.chain.factor for t in IS.deferred_mix(s.perturb_speed(1.1).mix(n, snr=15))] == [1.1, 1.0]  # exactly one Speed
     assert IS.deferred_mix(s) is None  # not a mixed cut
     assert IS.deferred_mix(s.perturb_volume(2.0).mix(n, snr=15)) is None  # a transform other than Speed
     assert IS.deferred_mix(s.perturb_speed(1.1).perturb_volume(2.0).mix(n, snr=15)) is None  # several transforms
     assert IS.deferred_mix(ok.perturb_volume(2.0)) is None  # (the volume lands on the tracks' recordings)
-    assert IS.deferred_mix(s.mix(ok, snr=10)) is not None and all(type(t[0]).__name__ == "MonoCut" for t in IS.deferred_mix(s.mix(ok, snr=10)))  # mix() flattens
+    assert IS.deferred_mix(s.mix(ok, snr=10)) is not None and all(type(t.cut).__name__ == "MonoCut" for t in IS.deferred_mix(s.mix(ok, snr=10)))  # mix() flattens
     assert IS.deferred_mix(MixedCut(id="nest", tracks=[MixTrack(cut=s, type="MonoCut"), MixTrack(cut=ok, type="MixedCut", snr=10)])) is None  # a nested mixed cut
     assert IS.deferred_mix(fastcopy(ok, transforms=[{"name": "Volume", "kwargs": {"factor": 2.0}}])) is None  # transforms of its own
     multi = MultiCut(id="m", start=0, duration=s.duration, channel=[0], recording=s.recording)
@@ -139,7 +139,7 @@ def test_deferred_mix_accepts_and_refuses(env):
     # one sample LONGER (0.5 + 100.5 -> 1 + 101 against 101) is truncated on the device ...
     longer = MixedCut(id="long", tracks=[MixTrack(cut=fastcopy(s, duration=50 / sr), type="MonoCut"),
                                          MixTrack(cut=fastcopy(n, duration=100.5 / sr), type="MonoCut", offset=0.5 / sr, snr=10)])
-    assert longer.num_samples == 101 and [t[2] for t in IS.deferred_mix(longer)] == [0, 1]
+    assert longer.num_samples == 101 and [t.offset for t in IS.deferred_mix(longer)] == [0, 1]
     tracks, ref, want = _tracks_for_rule(longer, IS)
     assert want == 101 and np.array_equal(mix_tracks(tracks, ref, want, energy="float32"), longer.load_audio()[0])
     # ... unless that is lhotse's tolerance or more (the reference then refuses the cut itself)

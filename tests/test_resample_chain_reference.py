@@ -7,7 +7,7 @@ Anywhere (no lhotse):
   * ``resample_layout`` equals ``perturbed_layout`` bit for bit on speed ratios, and places ratio by ratio in ascending order;
   * ``FusedMiniBatch.features_of_tracks`` with CPU stand-ins for the device reproduces the reference's features over the tables.
 Under the real lhotse (authoring container):
-  * ``pending_chain`` accepts / refuses each case of the list; the older classifiers return what they returned;
+  * ``parse_chain`` accepts / refuses each case of the list, and nothing with a ``Resample`` when the resampling route is off;
   * ``read_before_chain`` reads the very file segments ``load_audio()`` reads (logging backend);
   * ``HipOnTheFlyFeatures`` with the stand-ins equals the reference's K2 batch, without one ``load_audio()`` of an eligible cut;
   * the default of ``gpu_resample`` with and without a pretended torchaudio."""
@@ -232,29 +232,34 @@ def test_pending_chain_accepts_and_refuses(env, monkeypatch):
     c44, c22, c8, c16 = cuts["s44a"], cuts["s22a"], cuts["n8a"], cuts["s16a"]
     rir = Recording(id="rir", sources=[AudioSource(type="file", channels=[0], source=c16.recording.sources[0].source)], sampling_rate=SR, num_samples=7000,
                     duration=7000 / SR)
+    def pending_chain(cut, **kw):  # the rule with the level route off: [Resample]? [Speed]? [Reverb]? is all it serves
+        ch = IS.parse_chain(cut, gpu_level=False, **kw)
+        assert ch is None or (isinstance(ch, IS.Chain) and ch.levels is None)
+        return None if ch is None else (ch.source_rate, ch.factor, ch.reverb)
+
     # accepted: [Resample]? [Speed]? [Reverb]?
-    assert IS.pending_chain(c16) == (None, 1.0, None) and IS.pending_chain(c16.perturb_speed(1.1)) == (None, 1.1, None)
-    assert IS.pending_chain(c44.resample(SR)) == (44100, 1.0, None)
-    assert IS.pending_chain(c22.resample(SR).perturb_speed(0.9)) == (22050, 0.9, None)
-    assert IS.pending_chain(c8.resample(SR)) == (8000, 1.0, None)
-    ch = IS.pending_chain(c44.resample(SR).perturb_speed(1.1).reverb_rir(rir))
+    assert pending_chain(c16) == (None, 1.0, None) and pending_chain(c16.perturb_speed(1.1)) == (None, 1.1, None)
+    assert pending_chain(c44.resample(SR)) == (44100, 1.0, None)
+    assert pending_chain(c22.resample(SR).perturb_speed(0.9)) == (22050, 0.9, None)
+    assert pending_chain(c8.resample(SR)) == (8000, 1.0, None)
+    ch = pending_chain(c44.resample(SR).perturb_speed(1.1).reverb_rir(rir))
     assert ch[:2] == (44100, 1.1) and ch[2]["normalize_output"] is True and ch[2]["rir_channels"] == [0]
-    assert IS.pending_chain(c44.resample(SR).reverb_rir(rir))[:2] == (44100, 1.0)
-    assert IS.pending_chain(c44.resample(24000)) == (44100, 1.0, None)
+    assert pending_chain(c44.resample(SR).reverb_rir(rir))[:2] == (44100, 1.0)
+    assert pending_chain(c44.resample(24000)) == (44100, 1.0, None)
     # refused
-    assert IS.pending_chain(c44.perturb_speed(1.1).resample(SR)) is None  # a Resample that is not first
-    assert IS.pending_chain(c44.resample(22050).resample(SR)) is None  # more than one
+    assert pending_chain(c44.perturb_speed(1.1).resample(SR)) is None  # a Resample that is not first
+    assert pending_chain(c44.resample(22050).resample(SR)) is None  # more than one
     low = fastcopy(c16, recording=fastcopy(c16.recording, transforms=[{"name": "Resample", "kwargs": {"source_sampling_rate": SR, "target_sampling_rate": 8000}},
                                                                       {"name": "Resample", "kwargs": {"source_sampling_rate": 8000, "target_sampling_rate": SR}}]))
-    assert IS.pending_chain(low) is None  # (what LowpassUsingResampling appends)
-    assert IS.pending_chain(c44.resample(SR).perturb_volume(2.0)) is None and IS.pending_chain(c44.resample(SR).reverb_rir()) is None
-    assert IS.pending_chain(c44.resample(SR), gpu_resample=False) is None
-    assert IS.pending_chain(c44.resample(SR).reverb_rir(rir), gpu_reverb=False) is None
-    assert IS.pending_chain(MultiCut(id="m", start=0, duration=c44.duration, channel=[0], recording=c44.resample(SR).recording)) is None
+    assert pending_chain(low) is None  # (what LowpassUsingResampling appends)
+    assert pending_chain(c44.resample(SR).perturb_volume(2.0)) is None and pending_chain(c44.resample(SR).reverb_rir()) is None
+    assert pending_chain(c44.resample(SR), gpu_resample=False) is None
+    assert pending_chain(c44.resample(SR).reverb_rir(rir), gpu_reverb=False) is None
+    assert pending_chain(MultiCut(id="m", start=0, duration=c44.duration, channel=[0], recording=c44.resample(SR).recording)) is None
     wrong = fastcopy(c44.resample(SR), recording=fastcopy(c44.resample(SR).recording, sampling_rate=22050))
-    assert IS.pending_chain(wrong) is None  # a Resample to another rate than the cut's
+    assert pending_chain(wrong) is None  # a Resample to another rate than the cut's
     monkeypatch.setattr(RB, "CURRENT_RESAMPLING_BACKEND", "sox")
-    assert IS.pending_chain(c44.resample(SR)) is None and IS.pending_chain(c16.perturb_speed(1.1)) == (None, 1.1, None)
+    assert pending_chain(c44.resample(SR)) is None and pending_chain(c16.perturb_speed(1.1)) == (None, 1.1, None)
     monkeypatch.setattr(RB, "CURRENT_RESAMPLING_BACKEND", "default")
     # the size of the reduced bank: every pair among the common rates -> 16 / 24 kHz is below 0.3 x 2^20 floats, the largest 441:640
     sizes = {(a, b): IS._sinc_bank_floats(a, b) for a in (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000) for b in (16000, 24000) if a != b}
@@ -263,15 +268,15 @@ def test_pending_chain_accepts_and_refuses(env, monkeypatch):
 
     assert sizes[(44100, 16000)] == sinc_resample_kernel(44100, 16000)[0].size == 76000
     big = fastcopy(c16, recording=fastcopy(c16.recording, sampling_rate=16001, transforms=[{"name": "Resample", "kwargs": {"source_sampling_rate": SR, "target_sampling_rate": 16001}}]))
-    assert IS._sinc_bank_floats(SR, 16001) > 2 ** 20 and IS.pending_chain(big) is None
-    # the older classifiers return what they returned: a Resample is nothing they know
+    assert IS._sinc_bank_floats(SR, 16001) > 2 ** 20 and pending_chain(big) is None
+    # with the resampling route off a Resample is nothing the rule knows, whatever follows it
     r = c44.resample(SR)
-    assert IS.pending_transforms(r) is None and IS.deferred_speed_factor(r) is None and IS.deferred_reverb(r.reverb_rir(rir)) is None
-    assert IS.pending_transforms(r.perturb_speed(1.1)) is None and IS.deferred_speed_factor(r.perturb_speed(1.1)) is None
+    assert pending_chain(r, gpu_resample=False) is None and pending_chain(r.reverb_rir(rir), gpu_resample=False) is None
+    assert pending_chain(r.perturb_speed(1.1), gpu_resample=False) is None
     mixed = c16.mix(c8.resample(SR), snr=10)
     assert IS.deferred_mix(mixed) is None and IS.deferred_mix(mixed, True) is None
     tr = IS.deferred_mix(mixed, gpu_resample=True)
-    assert [len(t) for t in tr] == [5, 7] and tr[1][1:] == (1.0, 0, 10, False, None, 8000)
+    assert tr[0].chain == IS.Chain() and tr[1][1:] == (0, 10, False, IS.Chain(source_rate=8000))
     assert IS.deferred_mix(c16.mix(c8.perturb_speed(0.9).resample(SR), snr=10), gpu_resample=True) is None
 
 
@@ -299,15 +304,17 @@ def test_the_reader_reads_the_file_segments_the_reference_reads(env, monkeypatch
         ref = cut.load_audio()[0]
         ref_reads = list(reads)
         del reads[:]
-        ch = IS.pending_chain(cut)
+        chain = IS.parse_chain(cut)
+        ch = (chain.source_rate, chain.factor)
+        assert chain == IS.Chain(*ch)
         raw = IS.read_before_chain(cut)
         assert reads == ref_reads and len(reads) == 1 and reads[0][2] == len(raw) and reads[0][3] == ch[0], cut
         want = int(cut.num_samples)
         assert IS.chain_num_samples(len(raw), ch[0], ch[1], SR) >= want
         model = RC.model_track(raw, ch[0], ch[1])[:want]
         assert len(model) == len(ref) and float(np.abs(model - ref).max()) <= 1e-5 * len(RC.stages(ch[0], ch[1]))
-        track = IS._read_chain_track(cut, ch)
-        assert np.array_equal(track[0], raw) and track[1:] == (ch[1], 0, None, True, want, None, ch[0])
+        track = IS._read_track(cut, chain)
+        assert np.array_equal(track.samples, raw) and track[1:] == (ch[1], 0, None, True, want, None, ch[0], None)
     # a chain whose output is shorter than the cut (its file is shorter than the manifest states) takes the reference's path
     import wave
 
@@ -320,7 +327,7 @@ def test_the_reader_reads_the_file_segments_the_reference_reads(env, monkeypatch
         fh.writeframes(((np.random.RandomState(3).rand(22050 - 40) - 0.5) * 32767).astype(np.int16).tobytes())
     rec = Recording(id="short44", sources=[AudioSource(type="file", channels=[0], source=str(path))], sampling_rate=44100, num_samples=22050, duration=0.5)
     short = MonoCut(id="short44", start=0, duration=0.5, channel=0, recording=rec).resample(SR)
-    assert IS.pending_chain(short) == (44100, 1.0, None) and IS._read_chain_track(short, IS.pending_chain(short)) is None
+    assert IS.parse_chain(short) == IS.Chain(source_rate=44100) and IS._read_track(short, IS.parse_chain(short)) is None
     assert IS._read_one(short, True, False, True, True, True)[1:] == (1.0, 8000)  # (load_audio reflect-pads it)
 
 

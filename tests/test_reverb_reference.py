@@ -3,7 +3,7 @@
   * tests/_reverb_ref.py (the contract of hipfeat_reverb_*) against the committed ``load_audio()`` goldens: its float64 form is the stored
     truth, the reference lies at its stored distance from it, the device's summation order keeps the audio bars and ONE serial float32
     chain does not;
-  * ``pending_transforms`` / ``deferred_mix`` accept the four transform lists and refuse the rest;
+  * ``parse_chain`` / ``deferred_mix`` accept the four transform lists and refuse the rest;
   * ``HipReverbWithImpulseResponse`` round-trips through the reference's dict form;
   * HipOnTheFlyFeatures with CPU stand-ins for the device (plan, resampler, reverb, mixer) returns what OnTheFlyFeatures(Fbank()) returns
     on a mini-batch of the three-transform recipe, WITHOUT a ReverbWithImpulseResponse call on the CPU for the eligible cuts."""
@@ -131,49 +131,55 @@ def test_classifier_accepts_the_four_transform_lists_and_refuses_the_rest(env):
 
     speech, noise, rirs = env
     s, n = list(speech)[0], list(noise)[1]
-    assert IS.pending_transforms(s) == (1.0, None)
-    assert IS.pending_transforms(s.perturb_speed(1.1)) == (1.1, None)
-    f, rv = IS.pending_transforms(s.reverb_rir(rirs[0]))
+    def speed_and_reverb(cut, **kw):  # the rule with the resampling and level routes off: [Speed]? [Reverb]? is all it serves
+        ch = IS.parse_chain(cut, gpu_resample=False, gpu_level=False, **kw)
+        assert ch is None or (ch.source_rate, ch.pre, ch.post) == (None, None, None)
+        return None if ch is None else (ch.factor, ch.reverb)
+
+    assert speed_and_reverb(s) == (1.0, None) and not IS.parse_chain(s).pending
+    assert speed_and_reverb(s.perturb_speed(1.1)) == (1.1, None)
+    f, rv = speed_and_reverb(s.reverb_rir(rirs[0]))
     assert f == 1.0 and rv["rir"].id == "rir0" and rv["normalize_output"] and not rv["early_only"] and rv["rir_channels"] == [0]
-    f, rv = IS.pending_transforms(s.perturb_speed(0.9).reverb_rir(rirs[1], normalize_output=False, early_only=True))
+    f, rv = speed_and_reverb(s.perturb_speed(0.9).reverb_rir(rirs[1], normalize_output=False, early_only=True))
     assert f == 0.9 and rv["rir"].id == "rir1" and not rv["normalize_output"] and rv["early_only"]
-    assert IS.deferred_reverb(s) is None and IS.deferred_reverb(s.perturb_speed(1.1)) is None
-    assert IS.deferred_reverb(s.reverb_rir(rirs[0]))[0] == 1.0
+    assert IS.parse_chain(s).reverb is None and IS.parse_chain(s.perturb_speed(1.1)).reverb is None
+    assert IS.parse_chain(s.reverb_rir(rirs[0])).factor == 1.0
     # ... the same after the manifest went through its dict form (a cut read back from disk)
     back = type(s).from_dict(s.perturb_speed(0.9).reverb_rir(rirs[2], rir_channels=[1]).to_dict())
-    f, rv = IS.pending_transforms(back)
+    f, rv = speed_and_reverb(back)
     assert f == 0.9 and rv["rir_channels"] == [1]
     ref_rir = rirs[2].to_cut().with_channels([1]).load_audio()[0]
     assert np.array_equal(IS.load_reverb_rir(rv), ref_rir) and IS.load_reverb_rir(rv).dtype == np.float32
     early = IS.load_reverb_rir({**rv, "early_only": True})
     assert len(early) == 800 and np.array_equal(early, ref_rir[:800])
-    # _pending_speed / deferred_speed_factor: a pending Speed in front of a reverb the device serves counts; deferred_speed_factor keeps
-    # its meaning (Speed is ALL that is pending)
-    assert IS._pending_speed(s.perturb_speed(1.1).reverb_rir(rirs[0])) == 1.1 and IS._pending_speed(s.reverb_rir(rirs[0])) == 1.0
-    assert IS.deferred_speed_factor(s.perturb_speed(1.1).reverb_rir(rirs[0])) is None
+    # a pending Speed in front of a reverb the device serves counts; with the reverb route off such a cut is the reference's
+    assert IS.parse_chain(s.perturb_speed(1.1).reverb_rir(rirs[0])).factor == 1.1 and IS.parse_chain(s.reverb_rir(rirs[0])).factor == 1.0
+    assert speed_and_reverb(s.perturb_speed(1.1).reverb_rir(rirs[0]), gpu_reverb=False) is None
     # refused: the random generator, several rir_channels, a reverb in front of a Speed, other transforms, gpu_reverb off
-    assert IS.pending_transforms(s.reverb_rir()) is None
+    assert speed_and_reverb(s.reverb_rir()) is None
     two = fastcopy(s, recording=s.recording.reverb_rir(rirs[2], rir_channels=[0, 1]))
-    assert IS.pending_transforms(two) is None
-    assert IS.pending_transforms(s.reverb_rir(rirs[0]).perturb_speed(1.1)) is None
-    assert IS.pending_transforms(s.reverb_rir(rirs[0]).perturb_volume(2.0)) is None
-    assert IS.pending_transforms(s.perturb_volume(2.0).reverb_rir(rirs[0])) is None
-    assert IS.pending_transforms(s.reverb_rir(rirs[0]).reverb_rir(rirs[1])) is None
-    assert IS.pending_transforms(s.reverb_rir(rirs[0]), gpu_reverb=False) is None and IS.pending_transforms(s.perturb_speed(1.1), gpu_reverb=False) == (1.1, None)
-    # mixed cuts: a reverberated track is accepted (a 6th element: its reverb), a reverb on the mixed cut itself (mix_first) is not
+    assert speed_and_reverb(two) is None
+    assert speed_and_reverb(s.reverb_rir(rirs[0]).perturb_speed(1.1)) is None
+    assert speed_and_reverb(s.reverb_rir(rirs[0]).perturb_volume(2.0)) is None
+    assert speed_and_reverb(s.perturb_volume(2.0).reverb_rir(rirs[0])) is None
+    assert speed_and_reverb(s.reverb_rir(rirs[0]).reverb_rir(rirs[1])) is None
+    assert speed_and_reverb(s.reverb_rir(rirs[0]), gpu_reverb=False) is None and speed_and_reverb(s.perturb_speed(1.1), gpu_reverb=False) == (1.1, None)
+    # mixed cuts: a reverberated track is accepted (its chain carries the reverb), a reverb on the mixed cut itself (mix_first) is not
     tr = IS.deferred_mix(s.perturb_speed(1.1).reverb_rir(rirs[1]).mix(n, snr=15))
-    assert [(t[1], len(t)) for t in tr] == [(1.1, 6), (1.0, 5)] and tr[0][5]["rir"].id == "rir1"
+    assert [(t.chain.factor, t.chain.reverb is not None) for t in tr] == [(1.1, True), (1.0, False)] and tr[0].chain.reverb["rir"].id == "rir1"
     assert IS.deferred_mix(s.perturb_speed(1.1).reverb_rir(rirs[1]).mix(n, snr=15), gpu_reverb=False) is None
     assert IS.deferred_mix(s.mix(n.reverb_rir(), snr=15)) is None
     own = s.mix(n, snr=15).reverb_rir(rirs[0], mix_first=True)
     assert type(own).__name__ == "MixedCut" and own.transforms and IS.deferred_mix(own) is None
-    # the loaded tracks: 7 elements where a reverb is pending, the samples in front of every transform
+    # the loaded tracks: a reverb where one is pending, the samples in front of every transform
     loaded, _, want = IS._read_tracks(s.reverb_rir(rirs[0]).mix(n, snr=15), IS.deferred_mix(s.reverb_rir(rirs[0]).mix(n, snr=15)))
-    assert [len(t) for t in loaded] == [7, 6] and np.array_equal(loaded[0][0], s.load_audio()[0]) and loaded[0][6][1] is True
-    assert np.array_equal(loaded[0][6][0], rirs[0].load_audio()[0])
+    assert [t.reverb is not None for t in loaded] == [True, False] and np.array_equal(loaded[0].samples, s.load_audio()[0]) and loaded[0].reverb[1] is True
+    assert all((t.cap, t.source_rate, t.levels) == (len(t.samples), None, None) for t in loaded)
+    assert np.array_equal(loaded[0].reverb[0], rirs[0].load_audio()[0])
     one = IS._read_one(s.perturb_speed(1.1).reverb_rir(rirs[0]), gpu_speed=True, suppress_errors=False, gpu_mix=True, gpu_reverb=True)
-    assert isinstance(one[0], list) and len(one[0][0]) == 7 and one[0][0][1] == 1.1 and one[2] == s.perturb_speed(1.1).num_samples
-    assert np.array_equal(one[0][0][0], IS.read_unperturbed(s.perturb_speed(1.1), 1.1))
+    assert isinstance(one[0], list) and one[0][0].reverb is not None and one[0][0].factor == 1.1 and one[2] == s.perturb_speed(1.1).num_samples
+    assert (one[0][0].source_rate, one[0][0].levels) == (None, None)
+    assert np.array_equal(one[0][0].samples, IS.read_before_chain(s.perturb_speed(1.1)))
     # gpu_speed off: a [Speed, Reverb] cut takes the reference's path, a [Reverb] cut still goes to the device
     off = IS._read_one(s.perturb_speed(1.1).reverb_rir(rirs[0]), gpu_speed=False, suppress_errors=False, gpu_mix=True, gpu_reverb=True)
     assert isinstance(off[0], torch.Tensor) and off[1] == 1.0

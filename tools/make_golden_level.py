@@ -18,7 +18,7 @@ Groups (fixed seeds), over the corpus of oracle/driver_corpus.py; ``lhotse.augme
   3 clip_soft                 clip_amplitude(hard=False)           7 k2                        one K2SpeechRecognitionDataset batch with [PerturbSpeed,
   4 clip_oversampled          oversampling = 2 and 4                                            PerturbVolume, ClippingTransform, Reverb, CutMix]
 Per cut: the track table as in reverb.json plus ``"level": [block in front of the reverb, block behind it]`` -- taken from the product's own
-classifier and reader (``pending_level_chain``, ``deferred_mix``, ``_read_tracks``) with the audio backend logging what each track read --, the
+classifier and reader (``parse_chain``, ``deferred_mix``, ``_read_tracks``) with the audio backend logging what each track read --, the
 wanted sample count and the reference's Fbank features.  Single-track cuts (all are short) keep ``load_audio()``; where the chain is more than
 Volume / hard Clipping also the float64 truth (its float32 difference from ``load_audio()``) and the reference's own max-abs and rel-L2
 distance from it.  The product's route is run over every table with the numpy statement of the device's arithmetic in place of the kernels:
@@ -137,13 +137,9 @@ def chain_groups(meta):
             tracks = IS.deferred_mix(cut, gpu_resample=True, gpu_level=True)
             assert tracks is not None, cut
         else:
-            lc = IS.pending_level_chain(cut)
-            if lc is not None:
-                tracks = [(cut, lc[1], 0, None, True, lc[2], lc[0], lc[3])]
-            else:
-                p = IS.pending_transforms(cut)
-                assert p is not None, cut
-                tracks = [(cut, p[0], 0, None, True) + (() if p[1] is None else (p[1],))]
+            chain = IS.parse_chain(cut)
+            assert chain is not None, cut
+            tracks = [IS.PendingTrack(cut, 0, None, True, chain)]
         rows = []
         for tr in tracks:
             del reads[:]
@@ -155,14 +151,14 @@ def chain_groups(meta):
             assert len(reads) == 1 and reads[0][2] == len(x), (reads, len(x))
             row = {"file": reads[0][0], "first": reads[0][1], "count": len(x), "factor": float(factor), "offset": int(off),
                    "snr": None if snr is None else float(snr), "ref": bool(is_ref), "num_samples": int(n)}
-            if len(t) > 6 and t[6] is not None:
-                spec = tr[5]
+            if t.reverb is not None:
+                spec = tr.chain.reverb
                 rid = spec["rir"]["id"] if isinstance(spec["rir"], dict) else spec["rir"].id
-                assert not spec["early_only"] and np.array_equal(t[6][0], rir_loaded[rid[len("rec-"):]])
-                row["reverb"] = {"rir": rid[len("rec-"):], "normalize": bool(t[6][1])}
-            if len(t) > 8:
-                assert t[7] is None
-                row["level"] = [t[8][0], t[8][1]]
+                assert not spec["early_only"] and np.array_equal(t.reverb[0], rir_loaded[rid[len("rec-"):]])
+                row["reverb"] = {"rir": rid[len("rec-"):], "normalize": bool(t.reverb[1])}
+            if t.levels is not None:
+                assert t.source_rate is None
+                row["level"] = [t.levels[0], t.levels[1]]
             rows.append(row)
         return rows
 

@@ -111,16 +111,9 @@ def chain_groups(meta):
             tracks = IS.deferred_mix(cut, gpu_resample=True, gpu_level=True)
             assert tracks is not None, cut
         else:
-            lc = IS.pending_level_chain(cut)
-            if lc is not None:
-                tracks = [(cut, lc[1], 0, None, True, lc[2], lc[0], lc[3])]
-            elif IS.pending_transforms(cut) is None:  # a leading Resample and no level op
-                ch = IS.pending_chain(cut, bankless=True)
-                assert ch is not None and ch[0] is not None, cut
-                tracks = [(cut, ch[1], 0, None, True, ch[2], ch[0])]
-            else:
-                p = IS.pending_transforms(cut)
-                tracks = [(cut, p[0], 0, None, True) + (() if p[1] is None else (p[1],))]
+            chain = IS.parse_chain(cut, bankless=True)
+            assert chain is not None, cut
+            tracks = [IS.PendingTrack(cut, 0, None, True, chain)]
         rows = []
         for tr in tracks:
             del reads[:]
@@ -132,15 +125,15 @@ def chain_groups(meta):
             assert len(reads) == 1 and reads[0][2] == len(x), (reads, len(x))
             row = {"file": reads[0][0], "first": reads[0][1], "count": len(x), "factor": float(factor), "offset": int(off),
                    "snr": None if snr is None else float(snr), "ref": bool(is_ref), "num_samples": int(n)}
-            if len(t) > 6 and t[6] is not None:
-                spec = tr[5]
+            if t.reverb is not None:
+                spec = tr.chain.reverb
                 rid = spec["rir"]["id"] if isinstance(spec["rir"], dict) else spec["rir"].id
-                assert not spec["early_only"] and np.array_equal(t[6][0], rir_loaded[rid[len("rec-"):]])
-                row["reverb"] = {"rir": rid[len("rec-"):], "normalize": bool(t[6][1])}
-            if len(t) > 7 and t[7] is not None:
-                row["source_rate"] = int(t[7])
-            if len(t) > 8:
-                row["level"] = [t[8][0], t[8][1]]
+                assert not spec["early_only"] and np.array_equal(t.reverb[0], rir_loaded[rid[len("rec-"):]])
+                row["reverb"] = {"rir": rid[len("rec-"):], "normalize": bool(t.reverb[1])}
+            if t.source_rate is not None:
+                row["source_rate"] = int(t.source_rate)
+            if t.levels is not None:
+                row["level"] = [t.levels[0], t.levels[1]]
             rows.append(row)
         return rows
 
@@ -231,7 +224,7 @@ def chain_groups(meta):
         odd_rec = Recording(id="rec-odd11130", sources=[AudioSource(type="file", channels=[0], source=str(td / "wav" / "odd11130.wav"))], sampling_rate=11130,
                             num_samples=len(odd_pcm), duration=len(odd_pcm) / 11130)
         odd = MonoCut(id="odd11130", start=0, duration=odd_rec.duration, channel=0, recording=odd_rec).resample(SAMPLING_RATE)
-        assert IS._sinc_bank_floats(11130, SAMPLING_RATE) > IS.MAX_RESAMPLE_BANK_FLOATS and IS.pending_chain(odd) is None
+        assert IS._sinc_bank_floats(11130, SAMPLING_RATE) > IS.MAX_RESAMPLE_BANK_FLOATS and IS.parse_chain(odd) is None
         record("lead", [odd, lowpass(odd, 4673)])
         low = LowpassUsingResampling(p=1.0, seed=5)
         record("band_cutmix", list(CutMix(noise, snr=(10, 20), p=1.0, pad_to_longest=True, random_mix_offset=True, seed=11)(low(CutSet.from_cuts([u6, u2])))))

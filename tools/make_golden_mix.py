@@ -93,14 +93,14 @@ def main():
             tracks = IS.deferred_mix(cut)
             assert tracks is not None, cut
         else:
-            f = IS.deferred_speed_factor(cut)
-            tracks = [(cut, 1.0 if f is None else f, 0, None, True)]
+            chain = IS.parse_chain(cut, gpu_reverb=False, gpu_resample=False, gpu_level=False)  # a Speed, or the cut as load_audio() gives it
+            tracks = [IS.PendingTrack(cut, 0, None, True, chain or IS.Chain())]
         rows, loaded = [], []
         for tr in tracks:
             del reads[:]
             res = IS._read_tracks(cut, [tr])
             assert res is not None
-            (x, factor, off, snr, is_ref, n), = res[0]
+            x, factor, off, snr, is_ref, n = res[0][0][:6]
             if isinstance(x, int):
                 assert not reads
                 rows.append({"file": None, "first": 0, "count": int(x), "factor": 1.0, "offset": int(off), "snr": None, "ref": False, "num_samples": int(n)})

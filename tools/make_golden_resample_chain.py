@@ -23,7 +23,7 @@ Groups (fixed seeds, cuts of at most 0.5 s):
 
 Per cut: the track table -- file id, first sample and sample count of the read (at the file's rate), source rate, factor, offset in
 samples, SNR, reference flag, samples the track ends up with[, the reverb] --, taken from the product's own classifier and reader
-(``pending_chain``, ``deferred_mix(gpu_resample=True)``, ``_read_tracks``) with the audio backend logging which samples of which file each
+(``parse_chain``, ``deferred_mix(gpu_resample=True)``, ``_read_tracks``) with the audio backend logging which samples of which file each
 track read; the wanted sample count; the reference's Fbank features.  Groups 1-3 also: ``load_audio()``; the exact float64 chain
 (``oracle.resample_ref.resample(..., dtype=np.float64)`` per stage, the float64 mix of tests/_resample_chain.py behind it) as its float32
 difference from ``load_audio()``; the reference's own max-abs distance from that chain.
@@ -115,9 +115,9 @@ def main():
             tracks = IS.deferred_mix(cut, gpu_resample=True)
             assert tracks is not None, cut
         else:
-            ch = IS.pending_chain(cut)
-            assert ch is not None, cut
-            tracks = [(cut, ch[1], 0, None, True, ch[2], ch[0])]
+            chain = IS.parse_chain(cut, gpu_level=False)
+            assert chain is not None, cut
+            tracks = [IS.PendingTrack(cut, 0, None, True, chain)]
         rows = []
         for tr in tracks:
             del reads[:]
@@ -131,11 +131,11 @@ def main():
                              "num_samples": int(n)})
                 continue
             assert len(reads) == 1 and reads[0][2] == len(x), (reads, len(x))
-            rows.append({"file": reads[0][0], "first": reads[0][1], "count": len(x), "source_rate": None if len(t) < 8 else t[7], "factor": float(factor),
+            rows.append({"file": reads[0][0], "first": reads[0][1], "count": len(x), "source_rate": t.source_rate, "factor": float(factor),
                          "offset": int(off), "snr": None if snr is None else float(snr), "ref": bool(is_ref), "num_samples": int(n)})
-            if len(t) > 6 and t[6] is not None:
-                rows[-1]["reverb"] = {"rir": RIR[0], "early_only": False, "normalize": bool(t[6][1])}
-                assert np.array_equal(t[6][0], rir_loaded)  # the product loaded what the reference loads
+            if t.reverb is not None:
+                rows[-1]["reverb"] = {"rir": RIR[0], "early_only": False, "normalize": bool(t.reverb[1])}
+                assert np.array_equal(t.reverb[0], rir_loaded)  # the product loaded what the reference loads
         return rows
 
     arrays, meta = {}, {"sampling_rate": SR, "groups": {}}

@@ -21,7 +21,7 @@ Groups (fixed seeds):
                     ReverbWithImpulseResponse(p=0.5), CutMix(p=0.5)]) batch: reverberated, speed-only, mixed and plain cuts share it
 
 Per cut: the track table as in mix.json, a reverberated track with ``"reverb": {"rir", "early_only", "normalize"}`` -- taken from the
-product's own classifier and reader (``deferred_mix``, ``pending_transforms``, ``_read_tracks``) with the audio backend logging which
+product's own classifier and reader (``deferred_mix``, ``parse_chain``, ``_read_tracks``) with the audio backend logging which
 samples of which file each track read --, the wanted sample count and the reference's Fbank features.  For the single-track cuts of groups
 1, 2 and 4 up to AUDIO_MAX samples, over RIRs of 800 taps or more: ``load_audio()``; the exact float64 convolution (tests/_reverb_ref.py) of
 the float32 samples the reference had in front of the reverb, scaled by the float64 gain, stored as its float32 difference from
@@ -118,9 +118,9 @@ def main():
             tracks = IS.deferred_mix(cut)
             assert tracks is not None, cut
         else:
-            p = IS.pending_transforms(cut)
-            assert p is not None, cut
-            tracks = [(cut, p[0], 0, None, True) + (() if p[1] is None else (p[1],))]
+            chain = IS.parse_chain(cut, gpu_resample=False, gpu_level=False)
+            assert chain is not None, cut
+            tracks = [IS.PendingTrack(cut, 0, None, True, chain)]
         rows, loaded = [], []
         for tr in tracks:
             del reads[:]
@@ -135,11 +135,11 @@ def main():
                 assert len(reads) == 1 and reads[0][2] == len(x), (reads, len(x))
                 rows.append({"file": reads[0][0], "first": reads[0][1], "count": len(x), "factor": float(factor), "offset": int(off),
                              "snr": None if snr is None else float(snr), "ref": bool(is_ref), "num_samples": int(n)})
-                if len(t) > 6:
-                    spec = tr[5]
-                    rows[-1]["reverb"] = {"rir": rir_name(spec), "early_only": bool(spec["early_only"]), "normalize": bool(t[6][1])}
+                if t.reverb is not None:
+                    spec = tr.chain.reverb
+                    rows[-1]["reverb"] = {"rir": rir_name(spec), "early_only": bool(spec["early_only"]), "normalize": bool(t.reverb[1])}
                     want_rir = rir_loaded[(rows[-1]["reverb"]["rir"], rows[-1]["reverb"]["early_only"])]
-                    assert np.array_equal(t[6][0], want_rir)  # the product loaded what the reference loads
+                    assert np.array_equal(t.reverb[0], want_rir)  # the product loaded what the reference loads
             loaded.append(x)
         return rows, loaded
 
