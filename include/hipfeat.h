@@ -42,7 +42,7 @@ extern "C" {
 #endif
 /* Entry points added to an ABI version WITHOUT a bump carry their own export macro, so that the set the version number stands for can
  * still be told from what was added to it (lhotse_amd/_lib.py: _LEVEL_SIGNATURES, _COLLATE_SIGNATURES, _SINC_SIGNATURES,
- * _FEATMIX_SIGNATURES, _STATS_SIGNATURES, _STFT_SIGNATURES and _CHANNELS_SIGNATURES next to _SIGNATURES). */
+ * _FEATMIX_SIGNATURES, _STATS_SIGNATURES, _STFT_SIGNATURES, _CHANNELS_SIGNATURES and _REVERB_FFT_SIGNATURES next to _SIGNATURES). */
 #define HIPFEAT_COLLATE_API HIPFEAT_API
 #define HIPFEAT_FEATMIX_API HIPFEAT_API
 #define HIPFEAT_LEVEL_API HIPFEAT_API
@@ -52,6 +52,7 @@ extern "C" {
 #define HIPFEAT_STREAM_API HIPFEAT_API
 #define HIPFEAT_GRAD_API HIPFEAT_API
 #define HIPFEAT_CHANNELS_API HIPFEAT_API
+#define HIPFEAT_REVERB_FFT_API HIPFEAT_API
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -394,6 +395,38 @@ HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* reverb, int64_t n
                                                const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
                                                const int32_t* h_normalize, int64_t tail_start, int64_t* h_out_offsets, int64_t* h_info);
 HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* reverb, int64_t ticket, float* d_arena, int64_t arena_floats, void* stream);
+
+/* ---- the reverberation by partitioned FFT convolution, opt-in per plan (additive to ABI v8) ----------------------- */
+/*
+ * The same rule (ReverbWithImpulseResponse.__call__, lhotse/augmentation/rir.py:78-153; its convolve1d, lhotse/augmentation/utils.py:49-75,
+ * is three float32 FFTs) with the convolution taken as the reference takes it, through FFTs, but block by block: uniformly partitioned
+ * overlap-save (kernel_reverb_fft.hpp, reverb_fft_tables.hpp).
+ *   Partition geometry: block B = 1024 samples, transform size 2 B = 2048 (one wave per transform).  An item with N samples, L taps and
+ *   shift s has P = ceil(L / 1024) partitions h_p = hs[1024 p, 1024 p + 1024) zero-padded to 2048 (spectra H_p), the input blocks
+ *   x[1024 (i - 1), 1024 (i + 1)) with zeros outside [0, N), i = 0 ... nx - 1, nx = min(j1, floor((N - 1) / 1024) + 1) + 1 (spectra X_i), and
+ *   the output blocks j = floor(s / 1024) ... j1 = floor((s + N - 1) / 1024).
+ *   Precision: the spectra and their accumulation are float32; the spectra of the impulse responses and the inverse transform are
+ *   computed in float64 and rounded once (the input blocks are transformed in float32).
+ *   Summation orders, float32: Y_j = sum_p H_p X_{j-p} over the p with 0 <= p < P and 0 <= j - p < nx, p ASCENDING, per bin
+ *   re = fmaf(-h.im, x.im, fmaf(h.re, x.re, re)), im = fmaf(h.im, x.re, fmaf(h.re, x.im, im)); the inverse transform of Y_j (float64), times 2^-11, rounded; its
+ *   upper 1024 samples are the full convolution at [1024 j, 1024 j + 1024), of which the part inside [s, s + N) is stored.  Sx = the sum over i
+ *   ascending of the float64 sums of squares of x[1024 i, 1024 i + 1024); Sy = the sum over j ascending of the float64 sums of squares of
+ *   what block j stored; the gain and its conditions are those of the direct form.  Results are bit-identical from run to run and do
+ *   not depend on the other items of the batch.
+ *   Workspace formula: a spectrum is 2048 floats (1024 complex bins, the real bin 1024 beside the real bin 0).  The spectra lie in the
+ *   caller's arena behind the outputs: 2048 x (sum of P over the DISTINCT (h_rir_offset, h_rir_len) pairs of the ticket's FFT items + sum
+ *   of nx over its FFT items) floats; each distinct impulse response is transformed once, however many items share it.
+ * hipfeat_reverb_plan_method = hipfeat_reverb_plan with a route per item.  method: 0 direct (exactly hipfeat_reverb_plan), 1 FFT, 2 auto:
+ * an item takes the FFT route when its h_rir_len >= min_fft_taps; one ticket may hold items of both routes.  h_info[8] = {ticket, floats
+ * the arena must hold INCLUDING the spectra workspace, direct-form work items, partial sums of both routes, transforms of the spectra
+ * launch, output blocks of the accumulate-and-invert launch, work items of the FFT items' gain launch, distinct impulse-response spectra}.
+ * A method outside 0 ... 2 or a negative min_fft_taps returns HIPFEAT_ERR_INVALID and plans nothing, as every refusal of
+ * hipfeat_reverb_plan.  hipfeat_reverb_run runs the ticket on the routes it was planned with; nothing is allocated per call.
+ */
+HIPFEAT_REVERB_FFT_API hipfeat_status hipfeat_reverb_plan_method(hipfeat_reverb* reverb, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                      const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
+                                                      const int32_t* h_normalize, int64_t tail_start, int32_t method, int64_t min_fft_taps,
+                                                      int64_t* h_out_offsets, int64_t* h_info);
 
 /* ---- level changes of cuts on the device (additive to ABI v8) ------------------------------------------------------ */
 /*

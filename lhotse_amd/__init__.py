@@ -16,6 +16,7 @@ from .extractors import (  # noqa: F401
 )
 
 from .augmentation import HipReverb, HipReverbWithImpulseResponse, reverb_in_arena, reverb_tail_floats  # noqa: F401,E402
+from .augmentation import REVERB_AUTO_MIN_TAPS, reverb_fft_tail_floats  # noqa: F401,E402
 from .augmentation import HipClipping, HipLevel, HipVolume, get_or_create_level, level_in_arena  # noqa: F401,E402
 from .augmentation import COLLATE_TILE, HipCollator, collate_in_arena, get_or_create_collator, left_pad_offsets  # noqa: F401,E402
 from .augmentation import COLLATE_MAX_SOURCES, collate_sources_in_arena, collate_sources_layout  # noqa: F401,E402
@@ -87,6 +88,8 @@ __all__ = [
     "HipReverbWithImpulseResponse",
     "reverb_in_arena",
     "reverb_tail_floats",
+    "reverb_fft_tail_floats",
+    "REVERB_AUTO_MIN_TAPS",
     "HipLevel",
     "HipVolume",
     "HipClipping",

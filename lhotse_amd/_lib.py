@@ -220,8 +220,16 @@ _GRAD_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
     ),
     "hipfeat_grad_destroy": ("int", ["hipfeat_grad*"]),
 }
+# Likewise (HIPFEAT_REVERB_FFT_API in the header): the reverb plan with a route per item (direct form | partitioned FFT convolution).
+_REVERB_FFT_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_reverb_plan_method": (
+        "int",
+        ["hipfeat_reverb*", "int64_t", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "const int64_t*", "const int32_t*",
+         "int64_t", "int32_t", "int64_t", "int64_t*", "int64_t*"],
+    ),
+}
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
-                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES}
+                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -333,7 +341,7 @@ class _CffiBackend:
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
                         .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
-                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", ""))
+                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

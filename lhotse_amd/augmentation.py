@@ -753,6 +753,54 @@ def reverb_tail_floats(src_lens) -> int:
     return int(((_lib.i64(src_lens) + 3) & ~3).sum()) + 3
 
 
+REVERB_METHODS = {"direct": 0, "fft": 1, "auto": 2}  # hipfeat_reverb_plan_method's `method`
+REVERB_FFT_BLOCK = 1024        # kRfBlock: new samples per 2048-point transform
+REVERB_FFT_SPEC_FLOATS = 2048  # kRfSpecFloats: floats of one spectrum in the workspace
+# The crossover of "auto": the smallest tap count of the grid of tools/bench_reverb_fft.py (256 ... 32768) from which the FFT route is
+# faster than the direct form at every larger tap count -- profiles/reverb_fft_bench.json, "auto_min_taps" (24 x 200 000 samples: 0.139
+# against 0.206 ms at 1024 taps, 0.453 against 5.06 ms at 32768; at 512 taps 0.143 against 0.142 ms, at 256 0.146 against 0.109: the
+# direct form) and "auto_min_taps_one_item_30s" (0.063 against 0.066 ms at 1024; 0.063 against 0.055 at 512): both 1024.
+REVERB_AUTO_MIN_TAPS = 1024
+
+
+def reverb_method_code(method: str) -> int:
+    if method not in REVERB_METHODS:
+        raise ValueError(f"reverb method {method!r}: expected one of {sorted(REVERB_METHODS)}")
+    return REVERB_METHODS[method]
+
+
+def reverb_fft_tail_floats(src_lens, rir_lens, shifts, rir_offsets=None) -> int:
+    """Floats the channels of a mini-batch reverberated on the FFT route need behind ``tail_start``: the outputs
+    (``reverb_tail_floats``) and behind them the spectra workspace of include/hipfeat.h's formula, 2048 floats per spectrum --
+    ``ceil(L / 1024)`` per impulse response and ``min(j1, (N - 1) // 1024 + 1) + 1`` per item, ``j1 = (shift + N - 1) // 1024``.  With
+    ``rir_offsets`` an impulse response that several items share (same offset and length) is counted once, as the plan does; without,
+    every item counts its own (an upper bound)."""
+    n, taps, s = _lib.i64(src_lens), _lib.i64(rir_lens), _lib.i64(shifts)
+    if not (len(n) == len(taps) == len(s)):
+        raise ValueError("reverb tables: one entry per item in every table")
+    parts = (taps + REVERB_FFT_BLOCK - 1) // REVERB_FFT_BLOCK
+    if rir_offsets is not None:
+        first = {}
+        for k, key in enumerate(zip(_lib.i64(rir_offsets).tolist(), taps.tolist())):
+            first.setdefault(key, k)
+        parts = parts[sorted(first.values())]
+    nx = np.minimum((s + n - 1) // REVERB_FFT_BLOCK, (n - 1) // REVERB_FFT_BLOCK + 1) + 1
+    return reverb_tail_floats(n) + REVERB_FFT_SPEC_FLOATS * int(parts.sum() + nx.sum())
+
+
+def reverb_workspace_floats(src_lens, rir_lens, shifts, rir_offsets=None, method: str = "direct", min_fft_taps: Optional[int] = None) -> int:
+    """The spectra workspace alone (``reverb_fft_tail_floats`` minus the outputs) of the items that ``method`` sends down the FFT route:
+    none with ``"direct"``, all with ``"fft"``, those of at least ``min_fft_taps`` (None: ``REVERB_AUTO_MIN_TAPS``) taps with ``"auto"``."""
+    code = reverb_method_code(method)
+    n, taps, s = _lib.i64(src_lens), _lib.i64(rir_lens), _lib.i64(shifts)
+    keep = np.zeros(len(n), dtype=bool) if code == 0 else np.ones(len(n), dtype=bool) if code == 1 else \
+        taps >= int(REVERB_AUTO_MIN_TAPS if min_fft_taps is None else min_fft_taps)
+    if not keep.any():
+        return 0
+    ro = None if rir_offsets is None else _lib.i64(rir_offsets)[keep]
+    return reverb_fft_tail_floats(n[keep], taps[keep], s[keep], ro) - reverb_tail_floats(n[keep])
+
+
 def scaled_rir(rir: np.ndarray) -> Tuple[np.ndarray, int]:
     """One channel of a loaded RIR -> (``hs = rir * 2^-15`` in float32 -- exact --, ``shift`` = first index of ``max(hs)``)
     (lhotse/augmentation/rir.py:139, 145)."""
@@ -763,12 +811,21 @@ def scaled_rir(rir: np.ndarray) -> Tuple[np.ndarray, int]:
 class HipReverb(_ArenaHandle):
     """The device half of ``ReverbWithImpulseResponse.__call__`` (lhotse/augmentation/rir.py:78-153) for a packed mini-batch:
     ``hipfeat_reverb`` (include/hipfeat.h) owns the workspace of the two launches -- direct-form float32 convolution with float64 sums
-    of squares, then the power-preserving gain.  One object per device (``get_or_create_reverb``); it may be shared by threads."""
+    of squares, then the power-preserving gain; with ``plan(..., method="fft" | "auto")`` the partitioned FFT convolution of
+    kernel_reverb_fft.hpp in four launches, its spectra in the arena behind the outputs.  One object per device
+    (``get_or_create_reverb``); it may be shared by threads."""
 
     _KIND = "reverb"  # hipfeat_reverb_create / _destroy
 
-    def plan(self, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0):
-        """Host only -> (ticket, out_offsets, info = [ticket, arena floats needed, convolution work items, partial sums])."""
+    def plan(self, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0, method: str = "direct",
+             min_fft_taps: Optional[int] = None):
+        """Host only -> (ticket, out_offsets, info = [ticket, arena floats needed, convolution work items, partial sums]).
+
+        ``method``: ``"direct"`` (the default: ``hipfeat_reverb_plan``, the direct form), ``"fft"`` (partitioned FFT convolution,
+        kernel_reverb_fft.hpp) or ``"auto"`` (per item: FFT when ``rir_len >= min_fft_taps``, None = ``REVERB_AUTO_MIN_TAPS``).  With
+        ``"fft"`` / ``"auto"`` the plan is ``hipfeat_reverb_plan_method``'s and ``info`` has its 8 fields: the arena floats include the
+        spectra workspace (``reverb_fft_tail_floats``), then [4:8] = transforms of the spectra launch, output blocks, gain work items of
+        the FFT items, distinct impulse-response spectra."""
         so, sl, ro, rl, sh = (_lib.i64(a) for a in (src_offsets, src_lens, rir_offsets, rir_lens, shifts))
         n = len(so)
         if np.ndim(normalize) == 0:
@@ -776,10 +833,17 @@ class HipReverb(_ArenaHandle):
         nm = np.ascontiguousarray(normalize, dtype=np.int32)
         if not (len(sl) == len(ro) == len(rl) == len(sh) == len(nm) == n):
             raise ValueError("reverb tables: one entry per item in every table")
-        out_offs, info = np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        code = reverb_method_code(method)
+        if code == 0:
+            out_offs, info = np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+            with self._lock:
+                self.lib.check("hipfeat_reverb_plan", self.handle, n, _lib.addr(so), _lib.addr(sl), _lib.addr(ro), _lib.addr(rl), _lib.addr(sh), _lib.addr(nm),
+                               int(tail_start), _lib.addr(out_offs), _lib.addr(info))
+            return int(info[0]), out_offs, info
+        out_offs, info = np.zeros(n, dtype=np.int64), np.zeros(8, dtype=np.int64)
         with self._lock:
-            self.lib.check("hipfeat_reverb_plan", self.handle, n, _lib.addr(so), _lib.addr(sl), _lib.addr(ro), _lib.addr(rl), _lib.addr(sh), _lib.addr(nm),
-                           int(tail_start), _lib.addr(out_offs), _lib.addr(info))
+            self.lib.check("hipfeat_reverb_plan_method", self.handle, n, _lib.addr(so), _lib.addr(sl), _lib.addr(ro), _lib.addr(rl), _lib.addr(sh), _lib.addr(nm),
+                           int(tail_start), code, int(REVERB_AUTO_MIN_TAPS if min_fft_taps is None else min_fft_taps), _lib.addr(out_offs), _lib.addr(info))
         return int(info[0]), out_offs, info
 
     def run(self, ticket: int, arena: torch.Tensor, stream: Optional[int] = None) -> None:
@@ -796,7 +860,7 @@ def get_or_create_reverb(device: Union[str, torch.device, None] = None) -> HipRe
 
 
 def reverb_in_arena(arena: torch.Tensor, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize=None, tail_start: int = 0,
-                    reverb: Optional[HipReverb] = None) -> np.ndarray:
+                    reverb: Optional[HipReverb] = None, method: str = "direct", min_fft_taps: Optional[int] = None) -> np.ndarray:
     """Reverberate the channels of a device-resident packed mini-batch (``ReverbWithImpulseResponse.__call__``,
     lhotse/augmentation/rir.py:78-153); the counterpart of ``perturb_speed_in_arena`` / ``mix_in_arena``, run between the two when a
     track carries ``[Speed, Reverb]``.
@@ -805,13 +869,18 @@ def reverb_in_arena(arena: torch.Tensor, src_offsets, src_lens, rir_offsets, rir
     space behind it (``reverb_tail_floats``).  Item ``i`` convolves the ``src_lens[i]`` samples at ``src_offsets[i]`` with the
     ``rir_lens[i]`` taps at ``rir_offsets[i]``, keeps the samples from ``shifts[i]`` on and, where ``normalize[i]``, scales them to the
     input's power.  Returns the arena offsets of the outputs (``src_lens[i]`` samples each).  Two launches on the current stream, no
-    device -> host copy, bit-identical from run to run."""
+    device -> host copy, bit-identical from run to run.
+
+    ``method="fft"`` (or ``"auto"``: per item, from ``min_fft_taps`` / ``REVERB_AUTO_MIN_TAPS`` taps on) takes the partitioned FFT
+    convolution instead of the direct form -- four launches, and the free space must also hold the spectra workspace behind the outputs
+    (``reverb_fft_tail_floats``)."""
     assert arena.dtype == torch.float32 and arena.is_contiguous() and arena.ndim == 1
     if reverb is None:
         reverb = get_or_create_reverb(arena.device)
-    ticket, offs, info = reverb.plan(src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start)
+    ticket, offs, info = reverb.plan(src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start, method, min_fft_taps)
     if int(info[1]) > arena.numel():
-        raise ValueError(f"arena too small: {arena.numel()} floats, the reverberated cuts need {int(info[1])} (see reverb_tail_floats)")
+        hint = "reverb_tail_floats" if method == "direct" else "reverb_fft_tail_floats"
+        raise ValueError(f"arena too small: {arena.numel()} floats, the reverberated cuts need {int(info[1])} (see {hint})")
     reverb.run(ticket, arena)
     return offs
 
@@ -854,8 +923,10 @@ class HipReverbWithImpulseResponse(AudioTransform):
     rir_channels: List[int] = None  # type: ignore[assignment]
     rir_generator: Optional[Union[dict, object]] = None
     device: str = "cuda"
+    method: str = "direct"  # "direct" | "fft" | "auto" (reverb_in_arena); not a field of the reference: to_dict omits it when "direct"
 
     def __post_init__(self):
+        reverb_method_code(self.method)
         if self.rir_channels is None:
             self.rir_channels = [0]
         self.rir_channels = [int(c) for c in self.rir_channels]
@@ -877,9 +948,11 @@ class HipReverbWithImpulseResponse(AudioTransform):
     def to_dict(self) -> dict:
         rir = self.rir.to_dict() if hasattr(self.rir, "to_dict") else self.rir
         gen = self.rir_generator if self.rir_generator is None or isinstance(self.rir_generator, dict) else self.rir_generator.to_dict()
-        return {"name": type(self).__name__,
-                "kwargs": {"rir": rir, "normalize_output": self.normalize_output, "early_only": self.early_only,
-                           "rir_channels": list(self.rir_channels), "rir_generator": gen, "device": self.device}}
+        kwargs = {"rir": rir, "normalize_output": self.normalize_output, "early_only": self.early_only,
+                  "rir_channels": list(self.rir_channels), "rir_generator": gen, "device": self.device}
+        if self.method != "direct":
+            kwargs["method"] = self.method
+        return {"name": type(self).__name__, "kwargs": kwargs}
 
     def __call__(self, samples: Union[np.ndarray, torch.Tensor], sampling_rate: int) -> Union[np.ndarray, torch.Tensor]:
         is_tensor = isinstance(samples, torch.Tensor)
@@ -901,11 +974,13 @@ class HipReverbWithImpulseResponse(AudioTransform):
         host = np.zeros(front, dtype=np.float32)
         for c, (hs, _) in enumerate(scaled):
             host[d_in * n4 + c * l4 : d_in * n4 + c * l4 + taps] = hs
-        arena = torch.empty(front + reverb_tail_floats([n] * len(items)), dtype=torch.float32, device=dev)
+        rir_offs, shifts = [d_in * n4 + b * l4 for _, b in items], [scaled[b][1] for _, b in items]
+        tail = reverb_tail_floats([n] * len(items)) if self.method == "direct" else reverb_fft_tail_floats([n] * len(items), [taps] * len(items), shifts, rir_offs)
+        arena = torch.empty(front + tail, dtype=torch.float32, device=dev)
         arena[:front].copy_(torch.from_numpy(host))
         arena[: d_in * n4].view(d_in, n4)[:, :n].copy_(x)
-        offs = reverb_in_arena(arena, [a * n4 for a, _ in items], [n] * len(items), [d_in * n4 + b * l4 for _, b in items], [taps] * len(items),
-                               [scaled[b][1] for _, b in items], [int(bool(self.normalize_output))] * len(items), front)
+        offs = reverb_in_arena(arena, [a * n4 for a, _ in items], [n] * len(items), rir_offs, [taps] * len(items), shifts,
+                               [int(bool(self.normalize_output))] * len(items), front, method=self.method)
         out = torch.stack([arena[int(o) : int(o) + n] for o in offs])
         return out.to(samples.device) if is_tensor else out.cpu().numpy()
 

@@ -30,6 +30,7 @@
 #include "kernel_minibatch.hpp"
 #include "kernel_mix.hpp"
 #include "kernel_reverb.hpp"
+#include "kernel_reverb_fft.hpp"
 #include "kernel_collate.hpp"
 #include "kernel_featmix.hpp"
 #include "kernel_stats.hpp"
@@ -1850,7 +1851,10 @@ struct TicketedHandle {
   StagedSlot slots[kTicketSlots];
 };
 struct hipfeat_mixer : TicketedHandle<MixPlan> {};
-struct hipfeat_reverb : TicketedHandle<RvPlan> {};
+struct hipfeat_reverb : TicketedHandle<RvMethodPlan> {
+  float2* d_tw = nullptr;  // W_2048^k, k < 1024: uploaded by the first run of a ticket with FFT items
+  double2* d_tw64 = nullptr;
+};
 struct hipfeat_level : TicketedHandle<LvPlan> {};
 struct hipfeat_collate : TicketedHandle<CoPlan> {};
 struct hipfeat_sinc : TicketedHandle<SincPlan> {};
@@ -2292,25 +2296,112 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_mix_run(hipfeat_mixer* mixer, int6
 // the table: reverb_tables.hpp)
 // --------------------------------------------------------------------------------------
 extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_create(int32_t device, hipfeat_reverb** out) { return handle_create(device, out, "reverb"); }
-extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_destroy(hipfeat_reverb* r) { return handle_destroy(r); }
+extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_destroy(hipfeat_reverb* r) {
+  if (r && (r->d_tw || r->d_tw64)) {
+    DeviceGuard g(r->device);
+    for (auto& s : r->slots) (void)s.wait();  // the launches that read the twiddles are done
+    if (r->d_tw) (void)hipFree(r->d_tw);
+    if (r->d_tw64) (void)hipFree(r->d_tw64);
+  }
+  return handle_destroy(r);
+}
+
+// a validated plan of either entry point into the handle's ring: the ticket, the output offsets and the info fields
+static hipfeat_status reverb_keep_plan(hipfeat_reverb* rv, RvMethodPlan&& p, int64_t num_items, int64_t* h_out_offsets, int64_t* h_info, bool method_info) {
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  std::lock_guard<std::mutex> lk(rv->mu);
+  int64_t ticket;
+  if (hipfeat_status st = take_ticket(rv->tickets, "reverberations", &ticket)) return st;
+  const RvMethodPlan& s = rv->plans[ticket % kTicketSlots] = std::move(p);
+  if (h_out_offsets)
+    for (int64_t i = 0; i < num_items; ++i) h_out_offsets[i] = s.out_offsets[(size_t)i];
+  h_info[0] = ticket;
+  h_info[1] = s.arena_need;
+  h_info[2] = s.work_items;
+  h_info[3] = 2 * s.work_items + s.fft_partials();
+  if (method_info) {
+    h_info[4] = s.fft.a_work;
+    h_info[5] = s.fft.b_work;
+    h_info[6] = s.fft.g_work;
+    h_info[7] = (int64_t)s.fft.rirs.size();
+  }
+  return HIPFEAT_OK;
+}
 
 extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_plan(hipfeat_reverb* rv, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
                                                           const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
                                                           const int32_t* h_normalize, int64_t tail_start, int64_t* h_out_offsets, int64_t* h_info) {
   if (!rv || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
   // (validated into a local first: a refused table leaves the outstanding plans as they were)
-  RvPlan p = build_reverb_plan(num_items, h_src_offset, h_src_len, h_rir_offset, h_rir_len, h_shift, h_normalize, tail_start);
-  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
-  std::lock_guard<std::mutex> lk(rv->mu);
-  int64_t ticket;
-  if (hipfeat_status st = take_ticket(rv->tickets, "reverberations", &ticket)) return st;
-  const RvPlan& s = rv->plans[ticket % kTicketSlots] = std::move(p);
-  if (h_out_offsets)
-    for (int64_t i = 0; i < num_items; ++i) h_out_offsets[i] = s.items[(size_t)i].out_off;
-  h_info[0] = ticket;
-  h_info[1] = s.arena_need;
-  h_info[2] = s.work_items;
-  h_info[3] = 2 * s.work_items;
+  return reverb_keep_plan(rv, build_reverb_plan_method(num_items, h_src_offset, h_src_len, h_rir_offset, h_rir_len, h_shift, h_normalize, tail_start, kRvDirect, 0),
+                          num_items, h_out_offsets, h_info, false);
+}
+
+extern "C" HIPFEAT_REVERB_FFT_API hipfeat_status hipfeat_reverb_plan_method(hipfeat_reverb* rv, int64_t num_items, const int64_t* h_src_offset, const int64_t* h_src_len,
+                                                                 const int64_t* h_rir_offset, const int64_t* h_rir_len, const int64_t* h_shift,
+                                                                 const int32_t* h_normalize, int64_t tail_start, int32_t method, int64_t min_fft_taps,
+                                                                 int64_t* h_out_offsets, int64_t* h_info) {
+  if (!rv || !h_info) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  return reverb_keep_plan(rv, build_reverb_plan_method(num_items, h_src_offset, h_src_len, h_rir_offset, h_rir_len, h_shift, h_normalize, tail_start, method,
+                                                       min_fft_taps),
+                          num_items, h_out_offsets, h_info, true);
+}
+
+// the FFT items of a ticket: spectra, accumulate and invert, gain (kernel_reverb_fft.hpp); their table and partial sums lie in the
+// ticket's slot from byte `foff` on (reserved by the caller)
+static size_t rf_table_bytes(const RfPlan& f) { return f.items.size() * sizeof(RfItem) + f.rirs.size() * sizeof(RfRir); }
+
+static hipfeat_status reverb_run_fft(hipfeat_reverb* rv, const RfPlan& f, StagedSlot& s, size_t foff, float* d_arena, hipStream_t st) {
+  const size_t fbytes = rf_table_bytes(f);
+  const TableRoute fr = table_route(rv->allow_inline, fbytes);
+  if (!rv->d_tw) {  // once per handle
+    const std::vector<float2> tw = fft_twiddles(2 * kRfBlock, kRfBlock);
+    std::vector<double2> tw64((size_t)kRfBlock);  // W_2048^k in float64: the RIR spectra and the inverse transform run in it
+    for (int k = 0; k < kRfBlock; ++k) {
+      const double a = -2.0 * M_PI * (double)k / (double)(2 * kRfBlock);
+      tw64[(size_t)k] = make_double2(std::cos(a), std::sin(a));
+    }
+    if (!rv->d_tw64)
+      if (hipfeat_status bad = upload(&rv->d_tw64, tw64.data(), tw64.size())) return bad;
+    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(rf_spectra_kernel), kRfMaxTableLds));
+    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(rf_rir_inline_kernel), kRfLds64));
+    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(rf_output_inline_kernel), kRfLds64));
+    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(rf_rir_kernel), kRfLds64 + kRfMaxTableLds));
+    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(rf_output_kernel), kRfLds64 + kRfMaxTableLds));
+    if (hipfeat_status bad = upload(&rv->d_tw, tw.data(), tw.size())) return bad;  // (last: d_tw says that all of this is done)
+  }
+  RfInlineArgs fa;  // (only the used part of the blob is written)
+  RfHeader& fh = fa.h;
+  fh.arena = d_arena;
+  fh.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(s.d) + foff + fbytes);
+  fh.tw = rv->d_tw;
+  fh.tw64 = rv->d_tw64;
+  fh.num_items = (int32_t)f.items.size();
+  fh.num_rirs = (int32_t)f.rirs.size();
+  fh.table_bytes = (int32_t)fbytes;
+  fh.rir_work = (int32_t)f.rir_work;
+  fh.a_work = (int32_t)f.a_work;
+  fh.b_work = (int32_t)f.b_work;
+  fh.g_work = (int32_t)f.g_work;
+  fh.x_total = (int32_t)f.x_total;
+  fh.tables = fr.inl ? nullptr : static_cast<const unsigned char*>(s.d) + foff;
+  unsigned char* dst = fr.inl ? fa.blob : static_cast<unsigned char*>(s.h) + foff;
+  std::memcpy(dst, f.items.data(), f.items.size() * sizeof(RfItem));
+  std::memcpy(dst + f.items.size() * sizeof(RfItem), f.rirs.data(), f.rirs.size() * sizeof(RfRir));
+  if (!fr.inl) HIP_TRY(hipMemcpyAsync(static_cast<unsigned char*>(s.d) + foff, dst, fbytes, hipMemcpyHostToDevice, st));
+  const dim3 wg(256), gr(items_grid((f.rir_work + kRfWaves - 1) / kRfWaves, kRfGridSlots)), ga(items_grid((f.x_total + kRfWaves - 1) / kRfWaves, kRfGridSlots)),
+      gb(items_grid((f.b_work + kRfWaves - 1) / kRfWaves, kRfGridSlots)), gg(items_grid(f.g_work));
+  if (fr.inl) {
+    hipLaunchKernelGGL(rf_rir_inline_kernel, gr, wg, kRfLds64, st, fa);
+    hipLaunchKernelGGL(rf_spectra_inline_kernel, ga, wg, 0, st, fa);
+    hipLaunchKernelGGL(rf_output_inline_kernel, gb, wg, kRfLds64, st, fa);
+    hipLaunchKernelGGL(rf_gain_inline_kernel, gg, wg, 0, st, fa);
+  } else {
+    hipLaunchKernelGGL(rf_rir_kernel, gr, wg, kRfLds64 + fr.dyn, st, fh);
+    hipLaunchKernelGGL(rf_spectra_kernel, ga, wg, fr.dyn, st, fh);
+    hipLaunchKernelGGL(rf_output_kernel, gb, wg, kRfLds64 + fr.dyn, st, fh);
+    hipLaunchKernelGGL(rf_gain_kernel, gg, wg, fr.dyn, st, fh);
+  }
   return HIPFEAT_OK;
 }
 
@@ -2319,8 +2410,8 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int
   std::lock_guard<std::mutex> lk(rv->mu);
   const int slot = find_ticket(rv->tickets, ticket, "reverberation");
   if (slot < 0) return HIPFEAT_ERR_INVALID;
-  const RvPlan& p = rv->plans[slot];
-  StagedSlot& s = rv->slots[slot];  // device: the staged table, then the partial sums of squares
+  const RvMethodPlan& p = rv->plans[slot];
+  StagedSlot& s = rv->slots[slot];  // device: the staged table, then the partial sums of squares; behind them the same of the FFT items
   if (arena_floats < p.arena_need)
     return fail(HIPFEAT_ERR_INVALID, "arena holds %lld floats, the reverberated cuts need %lld", (long long)arena_floats, (long long)p.arena_need);
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return fail(HIPFEAT_ERR_INVALID, "the arena must start on a 16-byte boundary");
@@ -2329,8 +2420,10 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int
   const size_t bytes = p.items.size() * sizeof(RvItem);  // (a multiple of 16)
   const size_t part_bytes = (size_t)p.work_items * 2 * sizeof(double);
   const TableRoute r = table_route(rv->allow_inline, bytes);
+  const RfPlan& f = p.fft;
+  const size_t fbytes = rf_table_bytes(f), foff = bytes + part_bytes;  // (multiples of 16)
   HIP_TRY(s.wait());
-  HIP_TRY(s.reserve(bytes + part_bytes));
+  HIP_TRY(s.reserve(foff + fbytes + (size_t)p.fft_partials() * sizeof(double)));
   RvInlineArgs args;  // (header + 3.3 KB; only the used part of the blob is written)
   RvHeader& h = args.h;
   h.arena = d_arena;
@@ -2341,13 +2434,17 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_reverb_run(hipfeat_reverb* rv, int
   h.pad = 0;
   HIP_TRY(place_tables(args, r, s, bytes, st, [&](unsigned char* dst) { std::memcpy(dst, p.items.data(), bytes); }));
   const dim3 grid(items_grid(p.work_items)), wg(256);
-  if (r.inl) {
+  if (p.items.empty()) {
+    // (every item of the ticket takes the FFT route)
+  } else if (r.inl) {
     hipLaunchKernelGGL(reverb_conv_inline_kernel, grid, wg, 0, st, args);
     hipLaunchKernelGGL(reverb_gain_inline_kernel, grid, wg, 0, st, args);
   } else {
     hipLaunchKernelGGL(reverb_conv_kernel, grid, wg, r.dyn, st, h);
     hipLaunchKernelGGL(reverb_gain_kernel, grid, wg, r.dyn, st, h);
   }
+  if (!f.items.empty())
+    if (hipfeat_status bad = reverb_run_fft(rv, f, s, foff, d_arena, st)) return bad;
   rv->tickets.release(ticket);
   return finish_launches(s, st, hipGetLastError(), "reverb", kWaitedLaunches);
 }

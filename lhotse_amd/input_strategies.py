@@ -134,11 +134,18 @@ def _mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, 
     return mix_in_arena(arena, track_first, src_offsets, src_lens, dst_offsets, snrs, ref_tracks, max_samples, tail_start)
 
 
-def _reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start):
-    """(indirection for the CPU stand-in of the tests)"""
+def _reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start, method="direct"):
+    """(indirection for the CPU stand-in of the tests; with the direct form it is called without ``method``, as before there was one)"""
     from .augmentation import reverb_in_arena
 
-    return reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start)
+    return reverb_in_arena(arena, src_offsets, src_lens, rir_offsets, rir_lens, shifts, normalize, tail_start, method=method)
+
+
+def _checked_reverb_method(method: str) -> str:
+    from .augmentation import reverb_method_code
+
+    reverb_method_code(method)  # (ValueError for an unknown one)
+    return method
 
 
 def _level_in_arena(arena, src_offsets, src_lens, programs):
@@ -311,10 +318,11 @@ class _ArenaChain:
     def _chain_check_sr(self, sr: int) -> None:
         pass
 
-    def _tracks_chain(self, cuts_tracks, wants: List[int], sr: int):
+    def _tracks_chain(self, cuts_tracks, wants: List[int], sr: int, reverb_method: str = "direct"):
         """Pack every track (and every distinct RIR), resample the tracks with a pending factor into the tail, reverberate those with a RIR
-        behind them, mix the mixed cuts behind that -> (arena, cut_off, cut_len).  (Runs under the caller's ``torch.no_grad()``.)"""
-        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout, resample_layout, scaled_rir
+        behind them, mix the mixed cuts behind that -> (arena, cut_off, cut_len).  (Runs under the caller's ``torch.no_grad()``.)
+        ``reverb_method``: the route of the reverb (``reverb_in_arena``); this is the one place it is planned."""
+        from .augmentation import mixed_num_samples, mixed_tail_floats, perturbed_layout, resample_layout, reverb_workspace_floats, scaled_rir
         from .extractors import _as_1d_float
 
         self._chain_check_sr(sr)
@@ -395,6 +403,8 @@ class _ArenaChain:
             ll = np.array(ll, dtype=np.int64)
             _, ll[:num_tracks], lv_floats[0] = _level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[0], int(sr), 0)
         rv_floats = int(((ll[rv_idx] + 3) & ~3).sum())  # the reverb's outputs: as long as the (untruncated) tracks that reach it
+        # ... and, on the FFT route, its spectra behind them (what the chain writes there later is stream-ordered behind the reverb)
+        rv_ws_floats = reverb_workspace_floats(ll[rv_idx], [len(rirs[r][0]) for r in rv_rir], [rirs[r][1] for r in rv_rir], rv_rir, reverb_method)
         if has_level:
             _, ll[:num_tracks], lv_floats[1] = _level_steps(None, np.zeros(num_tracks, dtype=np.int64), ll[:num_tracks], blocks[1], int(sr), 0)
         first, _, sl, do, _, _, cap, mixed_ids = tables(np.zeros(len(items), dtype=np.int64), ll)
@@ -403,7 +413,7 @@ class _ArenaChain:
             if short.any():
                 raise ValueError(f"mixed cut {mixed_ids[int(np.nonzero(short)[0][0])]} is shorter than its wanted sample count: the reference "
                                  "reflect-pads such a mix (lhotse/cut/mixed.py:1386-1387); load it with cut.load_audio()")
-        headroom = 3 + rs_floats + res_floats + rv_floats + sum(lv_floats) + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
+        headroom = 3 + rs_floats + res_floats + rv_floats + rv_ws_floats + sum(lv_floats) + (mixed_tail_floats(first, sl, do, cap) if mixed_ids else 0)
         arena, offs, lens = self._chain_pack(items, headroom=headroom)
         front = int(offs[-1] + lens[-1])
         if two_pass:  # the tracks at another rate come to sr behind the pack; the speed pass reads them there
@@ -423,7 +433,7 @@ class _ArenaChain:
             # the reverb sees the whole resampled track and takes its powers over that length; the sample or two that
             # assert_and_maybe_fix_num_samples removes come off afterwards (recording.py:1032-1070): `tables` applies the caps
             ro = _reverb_in_arena(arena, po[rv_idx], pl[rv_idx], [int(po[num_tracks + r]) for r in rv_rir], [len(rirs[r][0]) for r in rv_rir],
-                                  [rirs[r][1] for r in rv_rir], rv_norm, mix_start)
+                                  [rirs[r][1] for r in rv_rir], rv_norm, mix_start, *(() if reverb_method == "direct" else (reverb_method,)))
             po = np.array(po, dtype=np.int64)
             po[rv_idx] = ro
             mix_start += rv_floats
@@ -485,7 +495,7 @@ class FusedMiniBatch(_ArenaChain):
             return self._perturb_and_extract(audios, factors, wants, sampling_rate)[:2]
         return self.extractor.extract_collated(audios, sampling_rate=sampling_rate, padding_value=LOG_EPSILON)
 
-    def features_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
+    def features_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int, reverb_method: str = "direct"):
         """``features_of`` for a mini-batch in which some cuts are ``MixedCut``s (``CutMix``, ``CutSet.mix`` / ``.pad``), without a lhotse
         type: every cut is a list of tracks, each a ``Track`` or a plain tuple of its first 5 to 9 values (normalised once, on entry)
         ``(samples, factor, offset_samples, snr, is_reference[, num_samples])`` -- ``samples`` as read
@@ -517,7 +527,10 @@ class FusedMiniBatch(_ArenaChain):
         device -> host copy in between.  Without a mixed cut this IS ``features_of``.
         -> ``(feats (B, Tmax, F), feat_lens, audio)``, ``audio`` = the cuts' samples (host tensors) with ``return_audio``, else None.  With
         ``return_audio`` and an ``audio_device`` other than ``"cpu"`` (None: the extractor's device): ``(feats, feat_lens, audio (B, Tmax),
-        audio_lens)``, the samples collated on the device out of the arena the feature launch read, with no per-cut copy."""
+        audio_lens)``, the samples collated on the device out of the arena the feature launch read, with no per-cut copy.
+        ``reverb_method``: ``"direct"`` (default), ``"fft"`` or ``"auto"``, the route of the reverberated tracks' convolution
+        (``reverb_in_arena``); the arena then also has room for the spectra."""
+        _checked_reverb_method(reverb_method)
         if len(cuts_tracks) != len(wants):
             raise ValueError("features_of_tracks: one wanted sample count per cut")
         cuts_tracks = _as_tracks(cuts_tracks, sampling_rate)
@@ -527,13 +540,13 @@ class FusedMiniBatch(_ArenaChain):
             if any(f != 1.0 for f in factors):
                 return self._perturb_and_extract(audios, factors, wants, sampling_rate)
             return self._plain_extract(audios, sampling_rate)
-        return self._mix_and_extract(cuts_tracks, wants, sampling_rate)
+        return self._mix_and_extract(cuts_tracks, wants, sampling_rate, reverb_method)
 
-    def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int):
+    def _mix_and_extract(self, cuts_tracks, wants: List[int], sr: int, reverb_method: str = "direct"):
         """The chain (``_tracks_chain``), then the feature launch over the cuts where it left them."""
         ex = self.extractor
         with torch.no_grad():
-            arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sr)
+            arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sr, reverb_method)
             zero_pad = getattr(ex.config, "edge_rule", "reflect") == "batch_zero_pad"  # as extract_collated
             padded = np.full(len(cut_len), int(cut_len.max()), dtype=np.int64) if zero_pad else None
             feats, frames = ex.plan.run_collated(arena, cut_off, cut_len, padded, float(LOG_EPSILON))
@@ -668,9 +681,11 @@ class FusedAudioBatch(_ArenaChain):
                 arena, po, pl = self._chain_pack([_as_1d_float(a.squeeze() if a.ndim > 1 else a, "FusedAudioBatch") for a in audios])
             return self._collated(arena, po, pl, wants)
 
-    def audio_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int):
-        """The arguments of ``FusedMiniBatch.features_of_tracks`` (tracks with their pending speed, reverb, source rate and level blocks)
-        -> ``(audio (B, Tmax) on the device, audio_lens)``: the same chain in the same arena, then the collate launch."""
+    def audio_of_tracks(self, cuts_tracks, wants: List[int], sampling_rate: int, reverb_method: str = "direct"):
+        """The arguments of ``FusedMiniBatch.features_of_tracks`` (tracks with their pending speed, reverb, source rate and level blocks,
+        and the reverb's route) -> ``(audio (B, Tmax) on the device, audio_lens)``: the same chain in the same arena, then the collate
+        launch."""
+        _checked_reverb_method(reverb_method)
         if len(cuts_tracks) != len(wants):
             raise ValueError("audio_of_tracks: one wanted sample count per cut")
         cuts_tracks = _as_tracks(cuts_tracks, sampling_rate)
@@ -678,7 +693,7 @@ class FusedAudioBatch(_ArenaChain):
         if speed_only is not None:
             return self.audio_of(*speed_only, wants, sampling_rate)
         with torch.no_grad():
-            arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sampling_rate)
+            arena, cut_off, cut_len = self._tracks_chain(cuts_tracks, wants, sampling_rate, reverb_method)
             return self._collated(arena, cut_off, cut_len, wants)
 
     def audio_of_channels(self, cuts_channels, factors: List[float], source_rates, wants: List[int], sampling_rate: int,
@@ -1247,7 +1262,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
 
         def __init__(self, extractor, *args, return_device: Optional[Union[str, torch.device]] = None,
                      return_audio_device: Optional[Union[str, torch.device]] = "cpu", gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None, gpu_reverb: Optional[bool] = None,
-                     gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, **kwargs) -> None:
+                     gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None, reverb_method: str = "direct", **kwargs) -> None:
             if not hasattr(extractor, "extract_collated"):
                 raise TypeError("HipOnTheFlyFeatures needs a Hip* extractor (with extract_collated)")
             super().__init__(extractor, *args, **kwargs)
@@ -1279,6 +1294,8 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             # oversampled clip (clip_amplitude(oversampling=k)) and a leading Resample in such a chain also need the resampling route, and
             # that only where the reference itself would run its sinc resampler
             self.gpu_level = (not self.wave_transforms) if gpu_level is None else bool(gpu_level)
+            # the route of the device reverb: "direct" (the default), "fft" or "auto" (lhotse_amd.augmentation.reverb_in_arena)
+            self.reverb_method = _checked_reverb_method(reverb_method)
 
         def __call__(self, cuts, recording_field: Optional[str] = None):
             """Only the middle of the parent's pipeline differs: ``extract_batch`` + ``collate_matrices`` become ONE fused launch, and
@@ -1315,7 +1332,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             sr = rates.pop()
             if mixed:  # (FusedMiniBatch.features_of_tracks: a plain cut is a cut of one track)
                 tracks = [a if isinstance(a, list) else [Track(a, f, 0, None, True)] for a, f in zip(audios, factors)]
-                feats, feat_lens, *audio = self._mix_and_extract(tracks, wants, sr)
+                feats, feat_lens, *audio = self._mix_and_extract(tracks, wants, sr, *(() if self.reverb_method == "direct" else (self.reverb_method,)))
             elif any(f != 1.0 for f in factors):  # (FusedMiniBatch.features_of, with the perturbed samples kept for `return_audio`)
                 feats, feat_lens, *audio = self._perturb_and_extract(audios, factors, wants, sr)
             else:
@@ -1357,9 +1374,10 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
         def __init__(self, *args, device: Union[str, torch.device, None] = None, return_device: Optional[Union[str, torch.device]] = None,
                      dtype: torch.dtype = torch.float32, gpu_speed_perturb: Optional[bool] = None, gpu_mix: Optional[bool] = None,
                      gpu_reverb: Optional[bool] = None, gpu_resample: Optional[bool] = None, gpu_level: Optional[bool] = None,
-                     gpu_channels: Optional[bool] = None, **kwargs) -> None:
+                     gpu_channels: Optional[bool] = None, reverb_method: str = "direct", **kwargs) -> None:
             super().__init__(*args, **kwargs)
             self.batch = FusedAudioBatch(device, dtype)
+            self.reverb_method = _checked_reverb_method(reverb_method)  # the route of the device reverb (reverb_in_arena), mono cuts
             self.device, self.dtype, self.return_device = self.batch.device, dtype, return_device
             self.gpu_speed_perturb = True if gpu_speed_perturb is None else bool(gpu_speed_perturb)
             self.gpu_mix = True if gpu_mix is None else bool(gpu_mix)
@@ -1432,7 +1450,7 @@ if HAVE_LHOTSE:  # pragma: no cover - authoring container only
             sr = rates.pop()
             if any(isinstance(a, list) for a in audios):  # (the loaded tracks of the cuts the device mixes, reverberates, resamples, scales)
                 tracks = [a if isinstance(a, list) else [Track(a, f, 0, None, True)] for a, f in zip(audios, factors)]
-                audio, lens = self.batch.audio_of_tracks(tracks, wants, sr)
+                audio, lens = self.batch.audio_of_tracks(tracks, wants, sr, *(() if self.reverb_method == "direct" else (self.reverb_method,)))
             else:
                 audio, lens = self.batch.audio_of(audios, factors, wants, sr)
             result = self._moved((audio, lens.to(torch.int32)))  # (collation.py:242)
