@@ -53,6 +53,7 @@ extern "C" {
 #define HIPFEAT_GRAD_API HIPFEAT_API
 #define HIPFEAT_CHANNELS_API HIPFEAT_API
 #define HIPFEAT_REVERB_FFT_API HIPFEAT_API
+#define HIPFEAT_RAGGED_API HIPFEAT_API /* the per-row-length forms inside the stft and grad blocks (_RAGGED_SIGNATURES) */
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -740,6 +741,21 @@ HIPFEAT_STFT_API hipfeat_status hipfeat_stft_create(const hipfeat_stft_config* c
 HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* stft);
 HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* stft, const float* d_wave, int64_t batch, int64_t num_samples, int64_t row_stride,
                                                  float* d_out, int64_t out_floats, float* d_log_energy, void* stream);
+/*
+ * hipfeat_stft_run_ragged (additive to ABI v8, HIPFEAT_RAGGED_API): the same launch for a zero-padded (batch, max_samples) batch whose row b
+ * holds h_lengths[b] <= max_samples samples.  It replaces the reference layer applied to x[b, :len_b] row by row (layers.py:59-333) plus
+ * collate_matrices: row b is framed as x[b, :len_b] alone -- T_b = hipfeat_num_frames(len_b, ...) frames, the flip-reflection at both of
+ * ITS ends, no sample from len_b on is read -- into a (batch, Tmax, row) output, Tmax = max_b T_b, whose rows T_b ... Tmax - 1 hold
+ * padding_value (the spectrum: (padding_value, 0) per bin), as do the log-energies there.  The one launch writes every element; there is no
+ * memset and no fill launch.  h_lengths is a HOST array of `batch` int64: it is checked here (negative or > max_samples:
+ * HIPFEAT_ERR_INVALID; without snip_edges a row too short for its reflection, a row of no samples included: HIPFEAT_ERR_TOO_SHORT; both
+ * name the row) and then staged to the device through a slot of the handle (the kernel reads only lengths this call has checked).  With
+ * snip_edges a row shorter than a frame has no frames and is legal; Tmax == 0 launches nothing.  Everything else as hipfeat_stft_run,
+ * with max_samples in the place of num_samples; every refusal comes before any device call.
+ */
+HIPFEAT_RAGGED_API hipfeat_status hipfeat_stft_run_ragged(hipfeat_stft* stft, const float* d_wave, int64_t batch, int64_t max_samples, int64_t row_stride,
+                                                          const int64_t* h_lengths, float padding_value, float* d_out, int64_t out_floats,
+                                                          float* d_log_energy, void* stream);
 
 /* ---- streaming layers: online_inference of the six Kaldi layers (additive to ABI v8) ------------------------------------- */
 /*
@@ -850,6 +866,23 @@ HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_run(hipfeat_grad* grad, const float
                                                  const float* d_grad_out, int64_t grad_out_floats, const float* d_grad_log_energy, float* d_grad_wave,
                                                  int64_t grad_wave_stride, float* d_workspace, int64_t workspace_floats, void* stream);
 HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_destroy(hipfeat_grad* grad);
+/*
+ * hipfeat_grad_workspace_ragged / hipfeat_grad_run_ragged (additive to ABI v8, HIPFEAT_RAGGED_API): the gradient of
+ * hipfeat_stft_run_ragged's batch (and of the four feature kinds on the same rows).  They replace the autograd of the reference layer
+ * applied to x[b, :len_b] row by row (layers.py:59-333) plus collate_matrices.  d_grad_out is the (batch, Tmax, row) cotangent and
+ * d_grad_log_energy the (batch, Tmax) one, Tmax = max_b T_b; their rows from T_b on are NEVER read.  Row b of d_grad_wave gets the gradient
+ * of x[b, :len_b] alone in its first len_b samples -- gathered over the row's own index map (S = len_b) in the fixed order of step 4 --
+ * and +0.0 in every sample from len_b to max_samples.  The workspace stays dense, (rows, Tmax, Nr): hipfeat_grad_workspace_ragged is the
+ * arithmetic of hipfeat_grad_workspace at T = Tmax.  h_lengths is a host array, checked and staged as for hipfeat_stft_run_ragged.  No
+ * atomics, no memset: a row's gradient has the same bits alone, in any batch and under any piece size.  Statuses as for the uniform
+ * twins, with max_samples in the place of num_samples; every refusal comes before any device call.
+ */
+HIPFEAT_RAGGED_API hipfeat_status hipfeat_grad_workspace_ragged(const hipfeat_grad* grad, int64_t batch, int64_t max_samples, const int64_t* h_lengths,
+                                                                int64_t budget_bytes, int64_t* rows_per_piece, int64_t* floats);
+HIPFEAT_RAGGED_API hipfeat_status hipfeat_grad_run_ragged(hipfeat_grad* grad, const float* d_wave, int64_t batch, int64_t max_samples, int64_t row_stride,
+                                                          const int64_t* h_lengths, const float* d_grad_out, int64_t grad_out_floats,
+                                                          const float* d_grad_log_energy, float* d_grad_wave, int64_t grad_wave_stride,
+                                                          float* d_workspace, int64_t workspace_floats, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

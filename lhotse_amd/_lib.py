@@ -228,8 +228,21 @@ _REVERB_FFT_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
          "int64_t", "int32_t", "int64_t", "int64_t*", "int64_t*"],
     ),
 }
+# Likewise (HIPFEAT_RAGGED_API in the header): the per-row-length forms of hipfeat_stft_run, hipfeat_grad_workspace and hipfeat_grad_run.
+_RAGGED_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_stft_run_ragged": (
+        "int",
+        ["hipfeat_stft*", "const float*", "int64_t", "int64_t", "int64_t", "const int64_t*", "float", "float*", "int64_t", "float*", "void*"],
+    ),
+    "hipfeat_grad_workspace_ragged": ("int", ["const hipfeat_grad*", "int64_t", "int64_t", "const int64_t*", "int64_t", "int64_t*", "int64_t*"]),
+    "hipfeat_grad_run_ragged": (
+        "int",
+        ["hipfeat_grad*", "const float*", "int64_t", "int64_t", "int64_t", "const int64_t*", "const float*", "int64_t", "const float*", "float*", "int64_t",
+         "float*", "int64_t", "void*"],
+    ),
+}
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
-                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES}
+                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES, **_RAGGED_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -341,7 +354,7 @@ class _CffiBackend:
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
                         .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
-                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", ""))
+                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", "").replace("HIPFEAT_RAGGED_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

@@ -2932,11 +2932,36 @@ struct hipfeat_stft {
   StftFront front;
   int device = 0;
   const void* fn = nullptr;
+  const void* fn_ragged = nullptr;  // the same body on RaggedRowSource
+  std::mutex mu;                    // hipfeat_stft_run_ragged: the ring of its length tables
+  SlotRing<4> ring;
 };
+
+// The length table of a ragged call (kernel_stft.hpp, RaggedArgs): rows x {S_b, T_b}.  Checks the lengths against max_samples and the
+// reflection, names the offending row, and yields Tmax; touches no device.
+static hipfeat_status ragged_table(const int64_t* h_lengths, int64_t batch, int64_t max_samples, int N, int shift, bool snip, std::vector<int64_t>& table,
+                                   int64_t* tmax) {
+  table.resize((size_t)batch * 2);
+  *tmax = 0;
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t S = h_lengths[b];
+    if (S < 0 || S > max_samples)
+      return fail(HIPFEAT_ERR_INVALID, "row %lld: length %lld is outside [0, max_samples = %lld]", (long long)b, (long long)S, (long long)max_samples);
+    if (hipfeat_status bad = hipfeat_check_length(S, N, shift, snip)) {
+      const std::string why = g_err;
+      return fail(bad, "row %lld: %s", (long long)b, why.c_str());
+    }
+    const int64_t T = hipfeat_num_frames(S, N, shift, snip);
+    table[(size_t)(2 * b)] = S, table[(size_t)(2 * b + 1)] = T;
+    *tmax = std::max(*tmax, T);
+  }
+  return HIPFEAT_OK;
+}
 
 extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_destroy(hipfeat_stft* s) {
   if (!s) return HIPFEAT_OK;
   DeviceGuard g(s->device);
+  s->ring.free_all();  // (waits for the launches that used a slot)
   stft_front_free(s->front);
   delete s;
   return HIPFEAT_OK;
@@ -2953,8 +2978,11 @@ extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_create(const hipfeat_stf
   s->device = device;
   const bool spectrum = cfg->output == HIPFEAT_STFT_SPECTRUM;
   s->fn = for_n1(n1, [&](auto n) { return spectrum ? entry<stft_kernel<decltype(n)::value, 1>>() : entry<stft_kernel<decltype(n)::value, 0>>(); });
+  s->fn_ragged = for_n1(n1, [&](auto n) { return spectrum ? entry<stft_ragged_kernel<decltype(n)::value, 1>>() : entry<stft_ragged_kernel<decltype(n)::value, 0>>(); });
   DeviceGuard g(device);
-  if (hipfeat_status bad = stft_front_create(s->front, *cfg, n1, h_window, s->fn)) {
+  hipfeat_status bad = stft_front_create(s->front, *cfg, n1, h_window, s->fn);
+  if (bad == HIPFEAT_OK) bad = set_dynamic_lds(s->fn_ragged, s->front.lds);
+  if (bad != HIPFEAT_OK) {
     hipfeat_stft_destroy(s);
     return bad;
   }
@@ -2999,6 +3027,53 @@ extern "C" HIPFEAT_STFT_API hipfeat_status hipfeat_stft_run(hipfeat_stft* s, con
   (void)hipLaunchKernel(s->fn, dim3((unsigned)(batch * bpr)), dim3(256), args, s->front.lds, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return HIPFEAT_OK;
+}
+
+// ... of a zero-padded batch whose row b holds h_lengths[b] samples: the same body on RaggedRowSource, the padding rows of the
+// (batch, Tmax, width) output written by the same launch; the length table travels through a slot of the handle's ring
+extern "C" HIPFEAT_RAGGED_API hipfeat_status hipfeat_stft_run_ragged(hipfeat_stft* s, const float* d_wave, int64_t batch, int64_t max_samples, int64_t row_stride,
+                                                                   const int64_t* h_lengths, float padding_value, float* d_out, int64_t out_floats,
+                                                                   float* d_log_energy, void* stream) {
+  if (!s) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  const hipfeat_stft_config& c = s->front.cfg;
+  if (batch < 0 || max_samples < 0 || out_floats < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  if (batch > 0 && !h_lengths) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (batch > 1 && row_stride < max_samples) return fail(HIPFEAT_ERR_INVALID, "row_stride = %lld < max_samples = %lld", (long long)row_stride, (long long)max_samples);
+  std::vector<int64_t> table;
+  int64_t T = 0;  // Tmax
+  if (hipfeat_status bad = ragged_table(h_lengths, batch, max_samples, c.frame_length, c.frame_shift, c.snip_edges != 0, table, &T)) return bad;
+  if (batch == 0 || T == 0) return HIPFEAT_OK;  // (no frame, no padding row: nothing to write)
+  const int64_t width = s->front.width();
+  if (batch > INT64_MAX / T || batch * T > INT64_MAX / width) return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
+  if (out_floats < batch * T * width)
+    return fail(HIPFEAT_ERR_INVALID, "output of %lld floats, %lld x %lld x %lld needed", (long long)out_floats, (long long)batch, (long long)T, (long long)width);
+  if (!d_wave || !d_out) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
+  const int align = s->front.spectrum() ? 8 : 4;
+  if (reinterpret_cast<uintptr_t>(d_wave) % 4 || reinterpret_cast<uintptr_t>(d_out) % align || reinterpret_cast<uintptr_t>(d_log_energy) % 4)
+    return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples and log-energies: 4 bytes, output: %d)", align);
+  const int64_t fpb = 4 * kStftFramesPerWave, bpr = (T + fpb - 1) / fpb;
+  if (bpr > INT32_MAX / batch) return fail(HIPFEAT_ERR_UNSUPPORTED, "%lld workgroups in one launch", (long long)batch * (long long)bpr);
+  StftParams p{};
+  fill_stft_front(p, s->front);
+  p.wave = d_wave;
+  p.out = d_out;
+  p.log_energy = c.want_energy ? d_log_energy : nullptr;
+  p.row_stride = row_stride;
+  p.num_samples = max_samples;
+  p.frames_per_row = T;
+  p.blocks_per_row = bpr;
+  p.npad_left = c.snip_edges ? 0 : (c.frame_length - c.frame_shift) / 2;
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)stream;
+  StagedSlot& slot = s->ring.take();
+  const size_t bytes = table.size() * sizeof(int64_t);
+  HIP_TRY(stage(slot, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, table.data(), bytes); }));
+  RaggedArgs a{static_cast<const int64_t*>(slot.d), padding_value};
+  void* args[] = {&p, &a};
+  set_lds_poison(s->front.lds);
+  (void)hipLaunchKernel(s->fn_ragged, dim3((unsigned)(batch * bpr)), dim3(256), args, s->front.lds, st);
+  return finish_launches(slot, st, hipGetLastError(), "ragged stft", kWaitedLaunch);
 }
 
 // --------------------------------------------------------------------------------------
@@ -3191,11 +3266,15 @@ struct hipfeat_grad {
   size_t lds = 0, off_tw = 0, off_tw64 = 0, off_blob = 0;  // bytes into the slot
   int blob_floats = 0, off_fwd = 0, off_bwd = 0, off_dct = 0, off_lifter = 0;
   StagedSlot slot;  // device: [window | W_fft^k | W_fft^k in float64 | filterbank blob], staged once at creation
+  const void* fn_ragged = nullptr;  // the same body on RaggedRowSource
+  std::mutex mu;                    // hipfeat_grad_run_ragged: the ring of its length tables
+  SlotRing<4> ring;
 };
 
 extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_destroy(hipfeat_grad* g) {
   if (!g) return HIPFEAT_OK;
   DeviceGuard guard(g->device);
+  g->ring.free_all();  // (waits for the launches that used a slot)
   g->slot.free_all();
   delete g;
   return HIPFEAT_OK;
@@ -3206,6 +3285,7 @@ static hipfeat_status grad_finish_create(hipfeat_grad* g, int32_t device, const 
   const bool spectral = g->mode != GRAD_FRAMES;
   g->device = device;
   g->fn = for_n1(g->n1, [](auto n) { return entry<grad_frames_kernel<decltype(n)::value>>(); });
+  g->fn_ragged = for_n1(g->n1, [](auto n) { return entry<grad_frames_ragged_kernel<decltype(n)::value>>(); });
   g->blob_floats = (int)t.blob.size();
   g->off_fwd = t.off_fwd, g->off_bwd = t.off_bwd, g->off_dct = t.off_dct, g->off_lifter = t.off_lifter;
   g->blob_in_lds = g->blob_floats > 0 && grad_blob_fits_lds(g->n1, g->N, t.blob.size());
@@ -3233,6 +3313,7 @@ static hipfeat_status grad_finish_create(hipfeat_grad* g, int32_t device, const 
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   hipfeat_status st = e == hipSuccess ? HIPFEAT_OK : fail(HIPFEAT_ERR_HIP, "staging the gradient tables failed: %s", hipGetErrorName(e));
   if (st == HIPFEAT_OK) st = set_dynamic_lds(g->fn, g->lds);
+  if (st == HIPFEAT_OK) st = set_dynamic_lds(g->fn_ragged, g->lds);
   if (st != HIPFEAT_OK) {
     hipfeat_grad_destroy(g);
     return st;
@@ -3292,6 +3373,27 @@ extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_create_stft(const hipfea
   return grad_finish_create(g, device, h_window, GradTables(), out);
 }
 
+// The arguments of the two launches of a piece but for the piece's own pointers and row count, for rows of `num_samples` samples and T
+// frames (a ragged batch: Smax and Tmax), common to hipfeat_grad_run and hipfeat_grad_run_ragged
+static void fill_grad_params(const hipfeat_grad* g, const GradPieces& pc, int64_t num_samples, int64_t T, int64_t row_stride, int64_t grad_wave_stride,
+                             float* d_workspace, int64_t bpr, int64_t gpr, GradParams& p, GradOlaParams& o) {
+  const unsigned char* tables = static_cast<const unsigned char*>(g->slot.d);
+  p.window = reinterpret_cast<const float*>(tables);
+  p.tw = g->mode == GRAD_FRAMES ? nullptr : reinterpret_cast<const float2*>(tables + g->off_tw);
+  p.tw64 = g->mode <= GRAD_MFCC ? reinterpret_cast<const double2*>(tables + g->off_tw64) : nullptr;
+  p.blob = g->blob_floats ? reinterpret_cast<const float*>(tables + g->off_blob) : nullptr;
+  p.ws = d_workspace;
+  p.row_stride = row_stride, p.num_samples = num_samples, p.frames_per_row = T, p.blocks_per_row = bpr, p.width = g->width;
+  p.N = g->N, p.Nr = (int32_t)pc.Nr, p.shift = g->shift, p.npad_left = g->snip ? 0 : (g->N - g->shift) / 2;
+  p.frames_per_wave = kStftFramesPerWave, p.flags = g->flags, p.mode = g->mode;
+  p.M = g->M, p.C = g->C, p.blob_floats = g->blob_floats, p.blob_in_lds = g->blob_in_lds ? 1 : 0;
+  p.off_fwd = g->off_fwd, p.off_bwd = g->off_bwd, p.off_dct = g->off_dct, p.off_lifter = g->off_lifter;
+  p.preemph = g->preemph, p.log_energy_floor = g->log_floor, p.mel_floor = g->mel_floor, p.log_offset = g->log_offset;
+  o.ws = d_workspace;
+  o.S = num_samples, o.T = T, o.groups_per_row = gpr, o.stride = grad_wave_stride;
+  o.N = g->N, o.Nr = (int32_t)pc.Nr, o.shift = g->shift, o.npad_left = p.npad_left;
+}
+
 extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_workspace(const hipfeat_grad* g, int64_t batch, int64_t num_samples, int64_t budget_bytes,
                                                                   int64_t* rows_per_piece, int64_t* floats) {
   if (!g || !rows_per_piece || !floats) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
@@ -3336,22 +3438,8 @@ extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_run(hipfeat_grad* g, con
   int64_t rpp = T > 0 ? workspace_floats / pc.row_floats : batch;
   rpp = std::min({rpp, batch, T > 0 ? INT32_MAX / bpr : batch, (int64_t)INT32_MAX * 128 / gpr});
   GradParams p{};
-  const unsigned char* tables = static_cast<const unsigned char*>(g->slot.d);
-  p.window = reinterpret_cast<const float*>(tables);
-  p.tw = frames_mode ? nullptr : reinterpret_cast<const float2*>(tables + g->off_tw);
-  p.tw64 = g->mode <= GRAD_MFCC ? reinterpret_cast<const double2*>(tables + g->off_tw64) : nullptr;
-  p.blob = g->blob_floats ? reinterpret_cast<const float*>(tables + g->off_blob) : nullptr;
-  p.ws = d_workspace;
-  p.row_stride = row_stride, p.num_samples = num_samples, p.frames_per_row = T, p.blocks_per_row = bpr, p.width = g->width;
-  p.N = g->N, p.Nr = (int32_t)pc.Nr, p.shift = g->shift, p.npad_left = g->snip ? 0 : (g->N - g->shift) / 2;
-  p.frames_per_wave = kStftFramesPerWave, p.flags = g->flags, p.mode = g->mode;
-  p.M = g->M, p.C = g->C, p.blob_floats = g->blob_floats, p.blob_in_lds = g->blob_in_lds ? 1 : 0;
-  p.off_fwd = g->off_fwd, p.off_bwd = g->off_bwd, p.off_dct = g->off_dct, p.off_lifter = g->off_lifter;
-  p.preemph = g->preemph, p.log_energy_floor = g->log_floor, p.mel_floor = g->mel_floor, p.log_offset = g->log_offset;
   GradOlaParams o{};
-  o.ws = d_workspace;
-  o.S = num_samples, o.T = T, o.groups_per_row = gpr, o.stride = grad_wave_stride;
-  o.N = g->N, o.Nr = (int32_t)pc.Nr, o.shift = g->shift, o.npad_left = p.npad_left;
+  fill_grad_params(g, pc, num_samples, T, row_stride, grad_wave_stride, d_workspace, bpr, gpr, p, o);
   DeviceGuard guard(g->device);
   set_lds_poison(g->lds);
   for (int64_t r0 = 0; r0 < batch; r0 += rpp) {
@@ -3368,6 +3456,83 @@ extern "C" HIPFEAT_GRAD_API hipfeat_status hipfeat_grad_run(hipfeat_grad* g, con
     HIP_TRY(hipGetLastError());
   }
   return HIPFEAT_OK;
+}
+
+// ... of a zero-padded batch whose row b holds h_lengths[b] samples: the piece arithmetic at Tmax = max_b T_b (the workspace stays dense)
+extern "C" HIPFEAT_RAGGED_API hipfeat_status hipfeat_grad_workspace_ragged(const hipfeat_grad* g, int64_t batch, int64_t max_samples, const int64_t* h_lengths,
+                                                                         int64_t budget_bytes, int64_t* rows_per_piece, int64_t* floats) {
+  if (!g || !rows_per_piece || !floats || (batch > 0 && !h_lengths)) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  *rows_per_piece = *floats = 0;
+  if (batch < 0 || max_samples < 0 || budget_bytes < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  std::vector<int64_t> table;
+  int64_t T = 0;
+  if (hipfeat_status bad = ragged_table(h_lengths, batch, max_samples, g->N, g->shift, g->snip, table, &T)) return bad;
+  GradPieces pc;
+  if (!grad_pieces(batch, T, g->N, budget_bytes, &pc)) return fail(HIPFEAT_ERR_INVALID, "%lld rows of %lld samples overflow", (long long)batch, (long long)max_samples);
+  *rows_per_piece = pc.rows_per_piece;
+  *floats = pc.floats;
+  return HIPFEAT_OK;
+}
+
+// ... the two launches per piece on RaggedRowSource and the row's own index map; the cotangent (batch, Tmax, row) and the gradient
+// (batch, max_samples) are those of the ragged forward, the length table travels through a slot of the handle's ring
+extern "C" HIPFEAT_RAGGED_API hipfeat_status hipfeat_grad_run_ragged(hipfeat_grad* g, const float* d_wave, int64_t batch, int64_t max_samples, int64_t row_stride,
+                                                                   const int64_t* h_lengths, const float* d_grad_out, int64_t grad_out_floats,
+                                                                   const float* d_grad_log_energy, float* d_grad_wave, int64_t grad_wave_stride,
+                                                                   float* d_workspace, int64_t workspace_floats, void* stream) {
+  if (!g) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (batch < 0 || max_samples < 0 || grad_out_floats < 0 || workspace_floats < 0) return fail(HIPFEAT_ERR_INVALID, "negative size");
+  if (batch > 0 && !h_lengths) return fail(HIPFEAT_ERR_INVALID, "NULL argument");
+  if (batch > 1 && (row_stride < max_samples || grad_wave_stride < max_samples))
+    return fail(HIPFEAT_ERR_INVALID, "a row stride is shorter than its row (waveform %lld, gradient %lld, max_samples = %lld)", (long long)row_stride,
+                (long long)grad_wave_stride, (long long)max_samples);
+  std::vector<int64_t> table;
+  int64_t T = 0;  // Tmax
+  if (hipfeat_status bad = ragged_table(h_lengths, batch, max_samples, g->N, g->shift, g->snip, table, &T)) return bad;
+  if (batch == 0 || max_samples == 0) return HIPFEAT_OK;
+  GradPieces pc;
+  if (!grad_pieces(batch, T, g->N, 0, &pc) || (T > 0 && batch > INT64_MAX / T / g->width))
+    return fail(HIPFEAT_ERR_INVALID, "%lld x %lld frames overflow", (long long)batch, (long long)T);
+  const bool frames_mode = g->mode == GRAD_FRAMES;
+  if (!d_grad_out && !frames_mode) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer (only a frames handle takes a NULL output cotangent)");
+  if (d_grad_out && grad_out_floats < batch * T * g->width)
+    return fail(HIPFEAT_ERR_INVALID, "output cotangent of %lld floats, %lld x %lld x %lld needed", (long long)grad_out_floats, (long long)batch, (long long)T,
+                (long long)g->width);
+  if (!d_wave || !d_grad_wave) return fail(HIPFEAT_ERR_INVALID, "NULL device pointer");
+  if (T > 0 && (!d_workspace || workspace_floats < pc.row_floats))
+    return fail(HIPFEAT_ERR_INVALID, "workspace of %lld floats, one row of %lld frames needs %lld", (long long)workspace_floats, (long long)T, (long long)pc.row_floats);
+  if (reinterpret_cast<uintptr_t>(d_wave) % 4 || reinterpret_cast<uintptr_t>(d_grad_out) % 4 || reinterpret_cast<uintptr_t>(d_grad_log_energy) % 4 ||
+      reinterpret_cast<uintptr_t>(d_grad_wave) % 4 || reinterpret_cast<uintptr_t>(d_workspace) % 16)
+    return fail(HIPFEAT_ERR_INVALID, "misaligned device pointer (samples, cotangents and gradient: 4 bytes, workspace: 16)");
+  const int64_t fpb = 4 * kStftFramesPerWave, bpr = (T + fpb - 1) / fpb, gpr = (max_samples + 3) / 4 + 1;
+  if (bpr > INT32_MAX || gpr > (int64_t)INT32_MAX * 128) return fail(HIPFEAT_ERR_UNSUPPORTED, "a row of %lld samples is too long for one launch", (long long)max_samples);
+  int64_t rpp = T > 0 ? workspace_floats / pc.row_floats : batch;
+  rpp = std::min({rpp, batch, T > 0 ? INT32_MAX / bpr : batch, (int64_t)INT32_MAX * 128 / gpr});
+  GradParams p{};
+  GradOlaParams o{};
+  fill_grad_params(g, pc, max_samples, T, row_stride, grad_wave_stride, d_workspace, bpr, gpr, p, o);
+  std::lock_guard<std::mutex> lk(g->mu);
+  DeviceGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  StagedSlot& slot = g->ring.take();
+  const size_t bytes = table.size() * sizeof(int64_t);
+  HIP_TRY(stage(slot, bytes, bytes, st, [&](unsigned char* h) { std::memcpy(h, table.data(), bytes); }));
+  set_lds_poison(g->lds);
+  for (int64_t r0 = 0; r0 < batch; r0 += rpp) {
+    const int64_t rows = std::min(rpp, batch - r0);
+    p.wave = d_wave + r0 * row_stride;
+    p.gout = d_grad_out ? d_grad_out + r0 * T * g->width : nullptr;
+    p.glog_e = (g->energy_rows && d_grad_log_energy) ? d_grad_log_energy + r0 * T : nullptr;
+    o.gwave = d_grad_wave + r0 * grad_wave_stride;
+    o.rows = rows;
+    RaggedArgs a{static_cast<const int64_t*>(slot.d) + 2 * r0, 0.f};
+    const int64_t* ola_table = a.table;
+    void* pa[] = {&p, &a};
+    void* oa[] = {&o, &ola_table};
+    if (T > 0) (void)hipLaunchKernel(g->fn_ragged, dim3((unsigned)(rows * bpr)), dim3(256), pa, g->lds, st);
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(grad_overlap_add_ragged_kernel), dim3((unsigned)((rows * gpr + 255) / 256)), dim3(256), oa, 0, st);
+  }
+  return finish_launches(slot, st, hipGetLastError(), "ragged gradient", kWaitedLaunches);
 }
 
 // ---- bulk save path: per-batch host work of the offline driver (host_bulk.hpp) -------------------------------------------------

@@ -26,6 +26,10 @@
 //
 // No atomics anywhere: the gradient of a row has the same bits alone or in any batch, from run to run and under any piece size.  All
 // element indexing is 64-bit.
+//
+// Both kernels have a ragged instance (rows with a length of their own, kernel_stft.hpp's RaggedRowSource and length table): the frames
+// kernel leaves at a row's own frame count, the gather runs over the row's own index map and writes +0.0 from its length on; the
+// cotangent, the workspace and the gradient keep the launch's dense (rows, Tmax, .) / (rows, Smax) shapes.
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
@@ -159,8 +163,8 @@ __device__ __forceinline__ void fft3_frame_f64(cd* zf, const double2* __restrict
   wave_lds_sync();
 }
 
-template <int N1>
-__device__ __forceinline__ void grad_frames_body(const GradParams& p) {
+template <int N1, class Src>
+__device__ __forceinline__ void grad_frames_body(const GradParams& p, const typename Src::Args& sa) {
   constexpr int H = 64 * N1, BUF = grad_buf_floats(N1);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   HF_POISON_LDS(smem);
@@ -192,15 +196,16 @@ __device__ __forceinline__ void grad_frames_body(const GradParams& p) {
   StftParams sp{};
   sp.wave = p.wave, sp.row_stride = p.row_stride, sp.num_samples = p.num_samples;
   sp.frames_per_row = p.frames_per_row, sp.blocks_per_row = p.blocks_per_row;
-  const RowSource src(sp, NoSourceArgs{}, (int64_t)blockIdx.x);
-  const int64_t row = src.row, T = src.T;
+  const Src src(sp, sa, (int64_t)blockIdx.x);
+  const int64_t row = src.row;
+  const int64_t T = Src::kPads ? p.frames_per_row : src.T;  // frames of a cotangent / workspace row: dense at Tmax for a ragged batch
   const bool want_e = (p.flags & F_USE_ENERGY) != 0, raw_e = (p.flags & F_RAW_ENERGY) != 0, mag = (p.flags & F_FFT_MAG) != 0;
   const int M = p.M;
   const int64_t fbase = src.fb * 4 * p.frames_per_wave;
 #pragma unroll 1
   for (int it = 0; it < p.frames_per_wave; ++it) {
     const int64_t f = fbase + 4 * it + wv;
-    if (f >= T) break;
+    if (f >= src.T) break;  // (a ragged row: its cotangent rows from T_b on are never read, their workspace rows never written)
     const int64_t j0 = f * p.shift - p.npad_left;
     const int64_t frame = row * T + f;
     const float* __restrict__ grow = p.gout ? p.gout + frame * p.width : nullptr;
@@ -504,7 +509,13 @@ __device__ __forceinline__ void grad_frames_body(const GradParams& p) {
 
 template <int N1>
 __global__ __launch_bounds__(256, (N1 == 16 ? 1 : 2)) void grad_frames_kernel(const GradParams p) {
-  grad_frames_body<N1>(p);
+  grad_frames_body<N1, RowSource>(p, NoSourceArgs{});
+}
+
+// ... on RaggedRowSource (kernel_stft.hpp): row b has S_b samples and T_b frames of its own
+template <int N1>
+__global__ __launch_bounds__(256, (N1 == 16 ? 1 : 2)) void grad_frames_ragged_kernel(const GradParams p, const RaggedArgs a) {
+  grad_frames_body<N1, RaggedRowSource>(p, a);
 }
 
 struct GradOlaParams {
@@ -547,7 +558,9 @@ __device__ __forceinline__ float grad_sample(const GradOlaParams& p, const float
   return acc;
 }
 
-__global__ __launch_bounds__(256) void grad_overlap_add_kernel(const GradOlaParams p) {
+// `table` (a ragged batch, else NULL): rows x {S_b, T_b}.  The output row and the workspace row keep the launch's p.S = Smax samples and
+// p.T = Tmax frames; row b gathers its own T_b frames over the index map of S_b samples, and every sample from S_b on gets +0.0.
+__device__ __forceinline__ void grad_overlap_add_body(const GradOlaParams& p, const int64_t* __restrict__ table) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = gid / p.groups_per_row, g = gid - row * p.groups_per_row;
   if (row >= p.rows) return;
@@ -556,11 +569,13 @@ __global__ __launch_bounds__(256) void grad_overlap_add_kernel(const GradOlaPara
   const int head = (int)((reinterpret_cast<uintptr_t>(orow) / sizeof(float)) & 3);
   const int64_t row_end = (int64_t)head + p.S, pp = 4 * g;  // the row is [head, row_end), counted from the 16-byte boundary below it
   if (pp >= row_end) return;
+  GradOlaParams q = p;  // the row's own index map
+  if (table != nullptr) q.S = table[2 * row], q.T = table[2 * row + 1];
   float e[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t j = pp + i - head;
-    e[i] = (j >= 0 && j < p.S) ? grad_sample(p, ws_row, j) : 0.f;
+    e[i] = (j >= 0 && j < q.S) ? grad_sample(q, ws_row, j) : 0.f;
   }
   if (pp >= head && pp + 4 <= row_end) {
     *reinterpret_cast<f32x4*>(orow + (pp - head)) = f32x4{e[0], e[1], e[2], e[3]};
@@ -570,5 +585,9 @@ __global__ __launch_bounds__(256) void grad_overlap_add_kernel(const GradOlaPara
       if (pp + i >= head && pp + i < row_end) orow[pp + i - head] = e[i];
   }
 }
+
+__global__ __launch_bounds__(256) void grad_overlap_add_kernel(const GradOlaParams p) { grad_overlap_add_body(p, nullptr); }
+
+__global__ __launch_bounds__(256) void grad_overlap_add_ragged_kernel(const GradOlaParams p, const int64_t* table) { grad_overlap_add_body(p, table); }
 
 }  // namespace hipfeat

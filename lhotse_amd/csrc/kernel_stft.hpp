@@ -20,7 +20,9 @@
 // All arguments are scalars (the batch is uniform: no device table).  All element indexing is 64-bit.  No scratch, no atomics.
 //
 // The kernel's text is stft_body, parametrised by the source policy of kernel_wave.hpp: stft_kernel is the body on RowSource (the row
-// with its reflections, as described above), kernel_stream.hpp runs it on the two-span source of the streaming layers.
+// with its reflections, as described above), kernel_stream.hpp runs it on the two-span source of the streaming layers, and
+// stft_ragged_kernel is the body on RaggedRowSource: rows with a length of their own (the one device table of this file), whose padding
+// rows in the (B, Tmax, width) output the same launch writes.
 #pragma once
 #include "common.hpp"
 #include "fft_common.hpp"
@@ -76,6 +78,7 @@ inline size_t stft_lds_bytes(int N1, int OUT, int N) {
 // num_samples samples with the flip-reflection at both ends.
 struct RowSource {
   using Args = NoSourceArgs;
+  static constexpr bool kPads = false;
   const float* __restrict__ w;
   int64_t row, fb, T, S;
   __device__ __forceinline__ RowSource(const StftParams& p, const NoSourceArgs&, int64_t blk) {
@@ -91,6 +94,61 @@ struct RowSource {
     return v;
   }
 };
+
+// RaggedRowSource: the rows of a zero-padded (B, Smax) batch, each with a length of its own.  The grid is that of RowSource with
+// frames_per_row = Tmax = max_b T_b; a workgroup takes S_b and T_b of its row from the length table (rows x {S_b, T_b}, which the host
+// has checked against Smax before it staged it) and reflects at S_b, so row b is framed exactly as x[b, :S_b] alone and nothing from
+// S_b on is read.  kPads: the frames T_b <= f < Tmax of the (B, Tmax, width) output are the padding rows, which the same launch writes.
+struct RaggedArgs {
+  const int64_t* table;  // [rows][2]: S_b, T_b
+  float padding;         // what the padding rows hold
+};
+
+struct RaggedRowSource {
+  using Args = RaggedArgs;
+  static constexpr bool kPads = true;
+  const float* __restrict__ w;
+  int64_t row, fb, T, S;
+  float padding;
+  template <class Params>
+  __device__ __forceinline__ RaggedRowSource(const Params& p, const RaggedArgs& a, int64_t blk) {
+    row = blk / p.blocks_per_row, fb = blk - row * p.blocks_per_row;
+    S = a.table[2 * row], T = a.table[2 * row + 1];
+    padding = a.padding;
+    w = p.wave + row * p.row_stride;
+  }
+  __device__ __forceinline__ bool inside(int64_t j0, int span) const { return j0 >= 0 && j0 + span <= S; }
+  __device__ __forceinline__ const float* base(int64_t j0) const { return w + j0; }
+  __device__ __forceinline__ v2 slow_pair(int64_t j, bool second) const {
+    v2 v = {stft_sample(w, j, S), 0.f};
+    if (second) v.y = stft_sample(w, j + 1, S);
+    return v;
+  }
+};
+
+// One padding row of the output, by one wave, with the stores of a computed row: OUT 0 the 16-byte groups counted from the boundary at or
+// below the row's start with the scalar head and tail, OUT 1 one 8-byte (padding, 0) store per bin; and the row's padded log-energy.
+template <int OUT>
+__device__ __forceinline__ void stft_pad_row(const StftParams& p, float padding, int64_t orow_index, int lane) {
+  if (p.log_energy != nullptr && lane == 0) p.log_energy[orow_index] = padding;
+  if constexpr (OUT == 0) {
+    float* __restrict__ orow = p.out + orow_index * (int64_t)p.pad;
+    const int head = (int)((reinterpret_cast<uintptr_t>(orow) / sizeof(float)) & 3);
+    const int64_t row_end = (int64_t)head + p.pad;
+    for (int64_t pp = 4 * lane; pp < row_end; pp += 256) {
+      if (pp >= head && pp + 4 <= row_end) {
+        *reinterpret_cast<f32x4*>(orow + (pp - head)) = f32x4{padding, padding, padding, padding};
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (pp + j >= head && pp + j < row_end) orow[pp + j - head] = padding;
+      }
+    }
+  } else {
+    float* __restrict__ orow = p.out + orow_index * (int64_t)(p.pad + 2);
+    for (int k = lane; k <= p.pad / 2; k += 64) *reinterpret_cast<v2*>(orow + 2 * k) = v2{padding, 0.f};
+  }
+}
 
 template <int N1, int OUT, class Src>
 __device__ __forceinline__ void stft_body(const StftParams& p, const typename Src::Args& sa) {
@@ -115,12 +173,20 @@ __device__ __forceinline__ void stft_body(const StftParams& p, const typename Sr
 
   const Src src(p, sa, (int64_t)blockIdx.x);
   const int64_t row = src.row, fb = src.fb, T = src.T;
+  int64_t Tout = T;  // frames of an output row: the padding rows of a ragged batch included
+  if constexpr (Src::kPads) Tout = p.frames_per_row;
   const bool want_e = (p.flags & F_USE_ENERGY) != 0;
   const int64_t fbase = fb * 4 * p.frames_per_wave;
 #pragma unroll 1
   for (int i = 0; i < p.frames_per_wave; ++i) {
     const int64_t f = fbase + 4 * i + wv;
-    if (f >= T) break;
+    if (f >= Tout) break;
+    if constexpr (Src::kPads) {
+      if (f >= T) {  // wave-uniform: a wave owns the whole frame
+        stft_pad_row<OUT>(p, sa.padding, row * Tout + f, lane);
+        continue;
+      }
+    }
     const int64_t j0 = f * p.shift - p.npad_left;
 
     // ---- samples, DC mean, raw log-energy (layers.py:155-162): lane l holds (x[2n], x[2n+1]) for n = l + 64 q ----------------------
@@ -180,7 +246,7 @@ __device__ __forceinline__ void stft_body(const StftParams& p, const typename Sr
       }
       if (want_e && !(p.flags & F_RAW_ENERGY)) log_e = fmaxf(logf(wave_sum(e) + 1e-15f), p.log_energy_floor);  // layers.py:183-185
     }
-    const int64_t orow_index = row * T + f;
+    const int64_t orow_index = row * Tout + f;
     if (p.log_energy != nullptr && lane == 0) p.log_energy[orow_index] = log_e;
     wave_lds_sync();  // the previous frame's readers of this wave's buffer are done
 
@@ -237,6 +303,11 @@ __device__ __forceinline__ void stft_body(const StftParams& p, const typename Sr
 template <int N1, int OUT>
 __global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_kernel(const StftParams p) {
   stft_body<N1, OUT, RowSource>(p, NoSourceArgs{});
+}
+
+template <int N1, int OUT>
+__global__ __launch_bounds__(256, (N1 == 16 ? 2 : HIPFEAT_WAVE_OCC)) void stft_ragged_kernel(const StftParams p, const RaggedArgs a) {
+  stft_body<N1, OUT, RaggedRowSource>(p, a);
 }
 
 }  // namespace hipfeat

@@ -33,6 +33,7 @@ struct StreamArgs {
 
 struct StreamSource {
   using Args = StreamArgs;
+  static constexpr bool kPads = false;
   const float* __restrict__ ctx;
   const float* __restrict__ chunk;
   int64_t R, S, row, fb, T, out_row;

@@ -18,6 +18,13 @@ exactly as before, and ``online_inference`` always does.
 frames, ``(B, num_frames, pad_length)`` with the optional ``(B, num_frames)`` log-energies, and their complex STFT,
 ``(B, num_frames, fft_length / 2 + 1)`` ``complex64`` -- one launch of ``hipfeat_stft_run`` each, under the same restrictions.
 
+All six also take a ragged batch, ``forward(x, lengths, padding_value=0.0)``: ``x`` is the zero-padded ``(B, Smax)`` tensor and row ``b``
+is the waveform ``x[b, :lengths[b]]`` and nothing else -- framed as that cut alone, nothing behind its length read -- and the call returns
+``(out, out_lens)`` with ``out`` collated to ``(B, max T_b, F)`` and ``padding_value`` behind each row's ``T_b`` frames, every element
+written by the launch itself (``hipfeat_stft_run_ragged``; the four feature kinds through the plan's collated launch).  It combines with
+``differentiable_()``: ``hipfeat_grad_run_ragged`` gives each row the gradient of the row alone and ``+0.0`` behind its length.
+``_HipLayer.forward`` states the contract.
+
 All six have the reference's second public method, ``online_inference(x, context=None)`` (:199-224, :326-333, :775-856): the chunked,
 stateless streaming call that frames ``[context | x]``, returns what ``forward`` computes for the complete frames and hands back the
 samples they did not consume.  One launch of ``hipfeat_stream_run`` per chunk (csrc/kernel_stream.hpp: the wave-per-frame kernels on a
@@ -152,16 +159,39 @@ class _Grad(_E._DeviceHandle):
                            None if cots[1] is None else cots[1].data_ptr(), grad.data_ptr(), S, workspace.data_ptr(), workspace.numel(), int(stream))
         return grad
 
+    def run_ragged(self, x: torch.Tensor, lens: np.ndarray, tmax: int, grad_out: Optional[torch.Tensor], grad_log_e: Optional[torch.Tensor]) -> torch.Tensor:
+        """``run`` for rows of ``lens[b]`` samples: the cotangents are (B, tmax, width) / (B, tmax) and their rows from a row's frame count on
+        are never read; row ``b`` of the (B, S) gradient is that of ``x[b, :lens[b]]`` alone, followed by +0.0.  ``hipfeat_grad_run_ragged``."""
+        x, stride = _rows_in_place(x)
+        B, S = x.shape
+        with torch.cuda.device(self.device):
+            grad = torch.empty((B, S), dtype=torch.float32, device=self.device)
+            if B == 0 or S == 0:
+                return grad
+            z = self._sizes
+            self.lib.check("hipfeat_grad_workspace_ragged", self.handle, B, S, _lib.addr(lens), int(_GRAD_WORKSPACE_BYTES), z.ctypes.data, z.ctypes.data + 8)
+            workspace = torch.empty(max(int(z[1]), 4), dtype=torch.float32, device=self.device)
+            cots = [None if g is None else g.to(torch.float32).contiguous() for g in (grad_out, grad_log_e)]
+            assert cots[0] is None or cots[0].shape[:2] == (B, tmax), (tuple(cots[0].shape), B, tmax)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.lib.check("hipfeat_grad_run_ragged", self.handle, x.data_ptr(), B, S, stride, _lib.addr(lens),
+                           None if cots[0] is None else (cots[0].data_ptr() or workspace.data_ptr()), 0 if cots[0] is None else cots[0].numel(),
+                           None if cots[1] is None else (cots[1].data_ptr() or workspace.data_ptr()), grad.data_ptr(), S, workspace.data_ptr(),
+                           workspace.numel(), int(stream))
+        return grad
+
 
 class _WaveGrad(torch.autograd.Function):
     """``forward``: the launch the plain path makes (``run(x) -> (out, log-energies or None)``); saves only the waveform.  ``backward``:
-    ``hipfeat_grad_run`` on the cotangents, either of which may be None."""
+    ``hipfeat_grad_run`` on the cotangents, either of which may be None.  With ``ragged`` (a ``_Lengths``) the host lengths are kept next
+    to the waveform and the backward is ``hipfeat_grad_run_ragged``."""
 
     @staticmethod
-    def forward(ctx, x, run, grad: _Grad):
+    def forward(ctx, x, run, grad: _Grad, ragged=None):
         out, log_e = run(x.detach())
         ctx.save_for_backward(x)
         ctx.grad = grad
+        ctx.ragged = ragged
         ctx.set_materialize_grads(False)
         if log_e is None:
             return out
@@ -171,9 +201,12 @@ class _WaveGrad(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out, grad_log_e=None):
         if grad_out is None and grad_log_e is None:
-            return None, None, None
+            return None, None, None, None
         (x,) = ctx.saved_tensors
-        return ctx.grad.run(x, grad_out, grad_log_e), None, None
+        r = ctx.ragged
+        if r is not None:
+            return ctx.grad.run_ragged(x, r.lens, r.tmax, grad_out, grad_log_e), None, None, None
+        return ctx.grad.run(x, grad_out, grad_log_e), None, None, None
 
 
 def _wants_grad(layer, x) -> bool:
@@ -220,6 +253,57 @@ def _check_waveforms(layer, x, method: str = "forward") -> Tuple[torch.Tensor, b
         x = x.unsqueeze(0)
     assert x.ndim == 2, f"expected a (B, T) batch of waveforms, got shape {tuple(x.shape)}"
     return x.detach(), squeeze
+
+
+# --------------------------------------------------------------------------------------
+# forward(x, lengths): a zero-padded (B, Smax) batch whose row b is the waveform x[b, :lengths[b]] and nothing else
+# --------------------------------------------------------------------------------------
+class _Lengths:
+    """The checked row lengths of one ragged call, on the host (int64): ``lens``, the frame counts ``frames`` and their maximum ``tmax``.
+    ``out_lens()`` gives the frame counts back as the caller gave the lengths: a tensor of their dtype on their device, else int64 on the
+    CPU."""
+
+    def __init__(self, layer, x: torch.Tensor, lengths, n: int, shift: int, snip_edges: bool):
+        name = type(layer).__name__
+        self._like = lengths if isinstance(lengths, torch.Tensor) else None
+        if isinstance(lengths, torch.Tensor):
+            if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+                raise TypeError(f"{name}: lengths must be integers, got {lengths.dtype}")
+            lens = lengths.detach().cpu().numpy()  # (a device tensor: one copy to the host, which waits for the device)
+        else:
+            lens = np.asarray(lengths)
+            if lens.dtype.kind not in "iu":
+                raise TypeError(f"{name}: lengths must be integers, got {lens.dtype}")
+        B, S = x.shape
+        if lens.ndim != 1 or lens.shape[0] != B:
+            raise ValueError(f"{name}: {B} rows but lengths of shape {tuple(lens.shape)}")
+        lens = np.ascontiguousarray(lens, dtype=np.int64)
+        bad = np.flatnonzero((lens < 0) | (lens > S))
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"{name}: row {b}: length {int(lens[b])} is outside [0, {S}], the rows of x")
+        if snip_edges:
+            frames = np.where(lens < n, 0, 1 + (lens - n) // shift).astype(np.int64)
+        else:
+            frames = (lens + shift // 2) // shift
+            lib = _lib.load()
+            for s in np.unique(lens):  # the uniform call's HIPFEAT_ERR_TOO_SHORT, before anything is launched
+                if lib.raw("hipfeat_check_length", int(s), n, shift, 0) != 0:
+                    raise ValueError(f"{name}: row {int(np.flatnonzero(lens == s)[0])}: {lib.last_error()}")
+        self.lens, self.frames, self.tmax = lens, frames, int(frames.max(initial=0))
+
+    def out_lens(self) -> torch.Tensor:
+        if self._like is None:
+            return torch.from_numpy(self.frames.copy())
+        return torch.as_tensor(self.frames, dtype=self._like.dtype, device=self._like.device)
+
+
+def _rows_in_place(x: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """``x`` (B, S) as the kernels read it in place -- unit column stride, rows that do not overlap -- or its contiguous copy, and the row
+    stride in elements."""
+    x = _Stream._rows(x)
+    B, S = x.shape
+    return x, (int(x.stride(0)) if B > 1 else S)
 
 
 def _check_stream_input(layer, x, context) -> Tuple[torch.Tensor, Optional[torch.Tensor], bool]:
@@ -304,8 +388,36 @@ class _HipLayer(_Differentiable, torch.nn.Module):
         dither = self._opts["dither"]
         if dither != 0.0:  # layers.py:191-193
             x = x + dither * torch.randn(x.shape, device=x.device)
-        out = _WaveGrad.apply(x, lambda w: (self._run_plan(plan, w), None), grad)
+        out = _WaveGrad.apply(x, lambda w: (self._run_plan(plan, w), None), grad, None)
         return out[0] if squeeze else out
+
+    def _run_plan_ragged(self, plan, x: torch.Tensor, r: _Lengths, padding_value: float) -> torch.Tensor:
+        """(B, Smax) float32 on the plan's device, row ``b`` of ``r.lens[b]`` samples -> (B, Tmax, F) with ``padding_value`` in the rows from
+        ``r.frames[b]`` on: the plan's collated launch, the rows read in place as cuts at the offsets ``b * row stride``."""
+        B, S = x.shape
+        if B == 0 or r.tmax == 0:
+            return torch.empty((B, 0, plan.feature_dim), dtype=torch.float32, device=x.device)
+        if plan.dither != 0.0:
+            x = x.contiguous()  # the plan draws its noise for the tensor it is given: the whole (B, Smax) batch, as the uniform call
+        x, stride = _rows_in_place(x)
+        wave = torch.as_strided(x, ((B - 1) * stride + S,), (1,))  # the rows and the gaps between them as one 1-D buffer: no copy
+        out, frames = plan.run_collated(wave, np.arange(B, dtype=np.int64) * stride, r.lens, None, float(padding_value))
+        assert np.array_equal(frames, r.frames) and out.shape == (B, r.tmax, plan.feature_dim)
+        return out
+
+    def _forward_ragged(self, x: torch.Tensor, lengths, padding_value: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        wants = _wants_grad(self, x)
+        x, _ = _check_grad_input(self, x) if wants else _check_waveforms(self, x)
+        r = _Lengths(self, x, lengths, self._n, self._shift, self._opts["snip_edges"])
+        if not wants:
+            return self._run_plan_ragged(self._plan_for(x.device), x, r, padding_value), r.out_lens()
+        grad = self._grad_for(x.device)
+        plan = self._plan_for(x.device, no_dither=True)
+        dither = self._opts["dither"]
+        if dither != 0.0:  # layers.py:191-193, for the whole tensor; only each row's first lengths[b] samples of it are read
+            x = x + dither * torch.randn(x.shape, device=x.device)
+        out = _WaveGrad.apply(x, lambda w: (self._run_plan_ragged(plan, w, r, padding_value), None), grad, r)
+        return out, r.out_lens()
 
     def _stream_for(self, device: torch.device) -> _Stream:
         key = (device.type, device.index)
@@ -334,7 +446,24 @@ class _HipLayer(_Differentiable, torch.nn.Module):
         out, _, remainder = s.run(x, context)
         return (out[0] if squeeze else out), remainder
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths=None, padding_value: float = 0.0):
+        """``forward(x)``: a ``(B, T)`` or ``(T,)`` batch of equally long waveforms -> ``(B, num_frames, F)``.
+
+        ``forward(x, lengths, padding_value=0.0)``: the ragged batch.  ``x`` is a zero-padded ``(B, Smax)`` batch read in place (any row
+        stride) and row ``b`` is the waveform ``x[b, :lengths[b]]`` and nothing else: its ``T_b`` frames are those of that cut alone, with
+        its own reflection at both ends, and ``x[b, lengths[b]:]`` is never read.  Returns ``(out, out_lens)``: ``out`` is
+        ``(B, max T_b, F)`` with ``padding_value`` in ``out[b, T_b:]`` (written by the same launch), ``out_lens`` holds the ``T_b`` --
+        a tensor of the dtype and on the device of ``lengths`` if that was a tensor, else int64 on the CPU.  ``lengths``: ``B``
+        non-negative integers ``<= Smax`` as a sequence, a numpy array or an integer tensor; a DEVICE tensor is copied to the host once,
+        which synchronises with the device (the host validates the lengths and computes ``out_lens``).  With ``snip_edges=True`` a row
+        shorter than a frame has zero frames; with ``snip_edges=False`` a row too short for its reflection raises the ``ValueError`` of the
+        uniform call, naming the row, before anything is launched.  ``dither != 0`` draws ``torch.randn`` for the whole ``(B, Smax)``
+        tensor, as the uniform call does; only each row's first ``lengths[b]`` samples of it are read.  A 1-D ``x`` with a one-element
+        ``lengths`` is the batch of one row: the outputs keep their leading dimension of 1.  With ``differentiable_()``,
+        ``grad[b, :lengths[b]]`` is the gradient of the row alone, ``grad[b, lengths[b]:]`` is ``+0.0`` and the cotangent's padding rows
+        are never read."""
+        if lengths is not None:
+            return self._forward_ragged(x, lengths, padding_value)
         if _wants_grad(self, x):
             return self._forward_differentiable(x)
         x, squeeze = _check_waveforms(self, x)
@@ -452,6 +581,20 @@ class _Stft(_E._DeviceHandle):
                            None if log_e is None else log_e.data_ptr(), int(stream))
         return out, log_e
 
+    def run_ragged(self, x: torch.Tensor, r: _Lengths, padding_value: float) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``run`` for rows of ``r.lens[b]`` samples, read in place: ((B, Tmax, width), (B, Tmax) or None), every element written by the one
+        launch of ``hipfeat_stft_run_ragged`` -- ``padding_value`` from a row's frame count on."""
+        x, stride = _rows_in_place(x)
+        B, S = x.shape
+        with torch.cuda.device(self.device):
+            out = torch.empty((B, r.tmax, self.width), dtype=torch.float32, device=self.device)
+            log_e = torch.empty((B, r.tmax), dtype=torch.float32, device=self.device) if self.energy_rows else None
+            if out.numel():
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                self.lib.check("hipfeat_stft_run_ragged", self.handle, x.data_ptr(), B, S, stride, _lib.addr(r.lens), float(padding_value), out.data_ptr(),
+                               out.numel(), None if log_e is None else log_e.data_ptr(), int(stream))
+        return out, log_e
+
 
 class HipWav2Win(_Differentiable, torch.nn.Module):
     """Kaldi preprocessing (DC offset, pre-emphasis, window, zero padding to ``pad_length``) of overlapping frames: the reference's
@@ -541,7 +684,7 @@ class HipWav2Win(_Differentiable, torch.nn.Module):
             handle = self._handle_for(x.device, output)
             if self.dither != 0.0:  # layers.py:191-193
                 x = x + self.dither * torch.randn(x.shape, device=x.device)
-            res = _WaveGrad.apply(x, lambda w: self._launch(handle, w), grad)
+            res = _WaveGrad.apply(x, lambda w: self._launch(handle, w), grad, None)
             out, log_e = res if isinstance(res, tuple) else (res, None)
             return out, log_e, squeeze
         x, squeeze = _check_waveforms(layer, x)
@@ -551,7 +694,34 @@ class HipWav2Win(_Differentiable, torch.nn.Module):
         out, log_e = self._launch(handle, x)
         return out, log_e, squeeze
 
-    def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    def _run_ragged(self, x: torch.Tensor, lengths, padding_value: float, output: int,
+                    layer=None) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+        """``_run`` for the rows ``x[b, :lengths[b]]`` (``_HipLayer.forward`` states the contract): (out (B, Tmax, width), log-energies
+        (B, Tmax) or None, out_lens)."""
+        layer = self if layer is None else layer
+        wants = _wants_grad(layer, x)
+        x, _ = _check_grad_input(layer, x) if wants else _check_waveforms(layer, x)
+        r = _Lengths(layer, x, lengths, self._length, self._shift, self.snip_edges)
+        grad = self._grad_for(x.device, output, layer) if wants else None  # (refused before anything runs)
+        handle = self._handle_for(x.device, output)
+        if self.dither != 0.0:  # layers.py:191-193, for the whole tensor; only each row's first lengths[b] samples of it are read
+            x = x + self.dither * torch.randn(x.shape, device=x.device)
+        if not wants:
+            out, log_e = handle.run_ragged(x, r, padding_value)
+            return out, log_e, r.out_lens()
+        res = _WaveGrad.apply(x, lambda w: handle.run_ragged(w, r, padding_value), grad, r)
+        out, log_e = res if isinstance(res, tuple) else (res, None)
+        return out, log_e, r.out_lens()
+
+    def forward(self, x: torch.Tensor, lengths=None, padding_value: float = 0.0):
+        """``forward(x)``: ``(frames, log_energy or None)`` of equally long rows.  ``forward(x, lengths, padding_value=0.0)``: the ragged
+        batch of ``_HipLayer.forward`` -- ``((frames, log_energy or None), out_lens)``, the shape of ``online_inference``'s pair, with
+        ``frames[b, T_b:]`` and ``log_energy[b, T_b:]`` equal to ``padding_value``; a device ``lengths`` tensor is copied to the host once
+        (a synchronisation); ``dither`` is drawn for the whole ``(B, Smax)`` tensor and only each row's first ``lengths[b]`` samples of it
+        are read."""
+        if lengths is not None:
+            out, log_e, out_lens = self._run_ragged(x, lengths, padding_value, self._output)
+            return (out, log_e), out_lens
         out, log_e, squeeze = self._run(x, self._output)
         if squeeze:
             return out[0], (None if log_e is None else log_e[0])
@@ -637,7 +807,14 @@ class HipWav2FFT(_Differentiable, torch.nn.Module):
         spec = torch.view_as_complex(out.view(out.shape[0], out.shape[1], self.fft_length // 2 + 1, 2))
         return spec[0] if squeeze else spec
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths=None, padding_value: float = 0.0):
+        """``forward(x)``: the ``complex64`` STFT of equally long rows.  ``forward(x, lengths, padding_value=0.0)``: the ragged batch of
+        ``_HipLayer.forward`` -- ``(spectrum, out_lens)`` with ``spectrum[b, T_b:]`` equal to ``padding_value + 0j``; a device ``lengths``
+        tensor is copied to the host once (a synchronisation); ``dither`` is drawn for the whole ``(B, Smax)`` tensor and only each row's
+        first ``lengths[b]`` samples of it are read."""
+        if lengths is not None:
+            out, _, out_lens = self.wav2win._run_ragged(x, lengths, padding_value, _lib.STFT_SPECTRUM, self)
+            return self._complex(out, False), out_lens
         out, _, squeeze = self.wav2win._run(x, _lib.STFT_SPECTRUM, self)  # (refusals name this layer)
         return self._complex(out, squeeze)
 
