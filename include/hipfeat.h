@@ -663,7 +663,8 @@ HIPFEAT_FEATMIX_API hipfeat_status hipfeat_featmix_run(hipfeat_featmix* featmix,
  * hipfeat_stats_create / _destroy: the object that owns the state, the slab of block partials (grows on demand) and 16 staging slots on
  * `device`, for feature_dim = 1 ... 65535 bins; calls are serialised inside; destroy waits for the work it enqueued; destroying NULL is OK.
  * hipfeat_stats_update validates on the host, stages the table and enqueues the two launches on `stream` without waiting (a 17th update
- * waits for the first one's launches).  1 ... 65535 cuts; h_first_row == NULL: the cuts are packed back to back from row 0.  Negative
+ * waits for the first one's launches; an update that needs a larger slab than every one before it -- never the first -- waits for the
+ * launches of all earlier updates before the old slab is freed).  1 ... 65535 cuts; h_first_row == NULL: the cuts are packed back to back from row 0.  Negative
  * rows or frames, row_stride < feature_dim, a cut whose last element lies beyond feats_elems, a dtype other than 0 or 1, a base pointer
  * that is not a multiple of the element size (the stride counts elements and cannot break it), counts out of range:
  * HIPFEAT_ERR_INVALID; more than 2^24 blocks in one update: HIPFEAT_ERR_UNSUPPORTED; nothing is enqueued and the state is unchanged.

@@ -2849,10 +2849,13 @@ extern "C" HIPFEAT_STATS_API hipfeat_status hipfeat_stats_update(hipfeat_stats* 
   DeviceGuard g(s->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t F = (size_t)s->feature_dim, slab_bytes = (size_t)p.total_blocks * 2 * F * sizeof(double);
-  if (s->slab_cap < slab_bytes) {  // the launches that read the old slab are waited for before it goes
-    for (auto& slot : s->ring.slots) HIP_TRY(slot.wait());
-    HIP_TRY(hipStreamSynchronize(st));
-    if (s->d_slab) (void)hipFree(s->d_slab);
+  if (s->slab_cap < slab_bytes) {
+    // the launches that read the old slab are waited for before it goes: every update records its slot's event behind them (a failed
+    // record has waited for its stream, StagedSlot::record).  The first update has no old slab and waits for nothing.
+    if (s->d_slab) {
+      for (auto& slot : s->ring.slots) HIP_TRY(slot.wait());
+      (void)hipFree(s->d_slab);
+    }
     s->d_slab = nullptr;
     s->slab_cap = 0;
     const size_t grown = std::max<size_t>(slab_bytes * 2, 1 << 20);

@@ -12,7 +12,14 @@ The entry points without tickets take their slots round-robin from a ring (DESIG
 handle gets ring-size small calls and then one whose table is LARGER than any first allocation such a ring has ever made (64 KiB once,
 16384 bytes now), all on one stream with no host synchronisation in between; every call writes a NaN-filled buffer of its own.  After
 ONE final synchronise the first call, the last small one and the big one are bit-equal to the same call made alone, with a synchronise
-behind it, on a second private handle (the accumulator: its state to that of a second one fed update by update)."""
+behind it, on a second private handle (the accumulator: its state to that of a second one fed update by update).
+
+The first use is PROVABLY in flight when the second comes: every run is issued on a side stream behind a stall (tests/_stalled_stream.py)
+of 10 times the host time that the same small runs took on a rehearsal handle.  After tickets 0 ... 15 (the ring's small calls) are
+issued the stall must still be there -- none of them has started -- and after run 16 it must be gone: the host can only have got past
+``StagedSlot::wait`` by waiting for run 0, which sits behind the stall."""
+import time
+
 import numpy as np
 import pytest
 import torch
@@ -25,6 +32,7 @@ import test_gpu_reverb
 import test_gpu_sinc
 from _collate_ref import bits_of, collate_ref
 from _hip import make_hip
+from _stalled_stream import Stall, side_streams, stall_ms_for
 
 from lhotse_amd import _lib
 from lhotse_amd.augmentation import (HipCollator, HipLevel, HipMixer, HipResampleTensor, HipReverb, HipSincResampler, mixed_tail_floats, reverb_tail_floats,
@@ -48,15 +56,35 @@ def _lengths(rng, n):
     return [int(v) for v in rng.integers(8, 65, size=n)]
 
 
-def _drive(handle, cases):
-    """cases: 17 of (issue(handle) -> ticket, check(), bytes of the table), their device buffers already filled"""
-    assert len(cases) == SLOTS + 1
+def _stall_behind(what, rehearse):
+    """A stall on a side stream, 10 times the host time of ``rehearse()`` (the small runs on a handle of their own) -> (stream, stall)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rehearse()
+    enqueue_ms = (time.perf_counter() - t0) * 1e3
+    torch.cuda.synchronize()
+    side = side_streams()[0]
+    stall = Stall(side, stall_ms_for(enqueue_ms))
+    print(f"slot reuse, {what}: small runs enqueued in {enqueue_ms:.3f} ms, stall {stall.ms:.0f} ms")
+    return side, stall
+
+
+def _drive(handle, cases, rehearsal):
+    """cases: 17 of (issue(handle) -> ticket, check(), bytes of the table), their device buffers already filled; rehearsal: the 16 small
+    ones once more, for a second handle that only times their enqueue"""
+    assert len(cases) == SLOTS + 1 and len(rehearsal) == SLOTS
     small, big = [c[2] for c in cases[:SLOTS]], cases[SLOTS][2]
     assert max(small) <= test_gpu_mix.INLINE_BYTES and 2 * max(small) <= FIRST_ALLOCATION < big
-    torch.cuda.synchronize()  # the uploads; from here on nothing waits until every run is enqueued
-    tickets = [issue(handle) for issue, _, _ in cases]
+    twin = type(handle)("cuda:0")
+    side, stall = _stall_behind(type(handle).__name__, lambda: [issue(twin) for issue, _, _ in rehearsal])
+    with torch.cuda.stream(side):  # the uploads are done (_stall_behind); from here on nothing waits until run 16 needs the slot of run 0
+        tickets = [issue(handle) for issue, _, _ in cases[:SLOTS]]
+        assert stall.still_stalled(), "tickets 0 ... 15 were not all issued while the stream was stalled"
+        tickets.append(cases[SLOTS][0](handle))
+    assert not stall.still_stalled(), "run 16 took the slot of run 0 without waiting for it"
     assert tickets == list(range(SLOTS + 1)) and tickets[SLOTS] % SLOTS == 0  # run 16 reuses the slot of run 0
     torch.cuda.synchronize()
+    twin.close()
     for k in CHECKED:
         cases[k][1]()
     handle.close()
@@ -97,7 +125,7 @@ def _mix_case(seed, entries):
 def test_mix():
     cases = [_mix_case(100 + k, n) for k, n in enumerate(RUNS)] + [_mix_case(116, 300)]
     assert cases[SLOTS][2] == 600 * test_gpu_mix.DESCRIPTOR_BYTES  # 300 cuts + 300 tracks
-    _drive(HipMixer("cuda:0"), cases)
+    _drive(HipMixer("cuda:0"), cases, [_mix_case(100 + k, n) for k, n in enumerate(RUNS)])
 
 
 def _reverb_case(seed, entries):
@@ -138,7 +166,7 @@ def _reverb_case(seed, entries):
 
 def test_reverb():
     cases = [_reverb_case(200 + k, n) for k, n in enumerate(RUNS)] + [_reverb_case(216, 342)]
-    _drive(HipReverb("cuda:0"), cases)
+    _drive(HipReverb("cuda:0"), cases, [_reverb_case(200 + k, n) for k, n in enumerate(RUNS)])
 
 
 def _level_case(seed, entries):
@@ -171,7 +199,7 @@ def _level_case(seed, entries):
 
 def test_level():
     cases = [_level_case(300 + k, n) for k, n in enumerate(RUNS)] + [_level_case(316, 257)]
-    _drive(HipLevel("cuda:0"), cases)
+    _drive(HipLevel("cuda:0"), cases, [_level_case(300 + k, n) for k, n in enumerate(RUNS)])
 
 
 def _collate_case(seed, entries):
@@ -200,7 +228,7 @@ def _collate_case(seed, entries):
 
 def test_collate():
     cases = [_collate_case(400 + k, n) for k, n in enumerate(RUNS)] + [_collate_case(416, 513)]
-    _drive(HipCollator("cuda:0"), cases)
+    _drive(HipCollator("cuda:0"), cases, [_collate_case(400 + k, n) for k, n in enumerate(RUNS)])
 
 
 def _sinc_case(seed, entries):
@@ -238,7 +266,7 @@ def _sinc_case(seed, entries):
 
 def test_sinc():
     cases = [_sinc_case(500 + k, n) for k, n in enumerate(RUNS)] + [_sinc_case(516, 257)]
-    _drive(HipSincResampler("cuda:0"), cases)
+    _drive(HipSincResampler("cuda:0"), cases, [_sinc_case(500 + k, n) for k, n in enumerate(RUNS)])
 
 
 # ---- the rings of the entry points without tickets --------------------------------------------------------------------------------
@@ -252,9 +280,13 @@ def _drive_ring(make_handle, close, calls):
     alone = {k: torch.full(calls[k][1], float("nan"), dtype=torch.float32, device="cuda") for k in checked}
     stream = torch.cuda.current_stream().cuda_stream
     handle, second = make_handle(), make_handle()
-    torch.cuda.synchronize()  # the uploads and fills; from here on nothing waits until every call is enqueued
-    for (issue, _, _), out in zip(calls, outs):  # call RING lands on the slot of call 0
-        issue(handle, out, stream)
+    rehearsal = [torch.empty_like(out) for out in outs[:RING]]
+    side, stall = _stall_behind("ring", lambda: [issue(second, out, stream) for (issue, _, _), out in zip(calls, rehearsal)])
+    for (issue, _, _), out in zip(calls[:RING], outs):  # (the uploads and fills are done: _stall_behind)
+        issue(handle, out, side.cuda_stream)
+    assert stall.still_stalled(), "the ring's small calls were not all issued while the stream was stalled"
+    calls[RING][0](handle, outs[RING], side.cuda_stream)  # call RING lands on the slot of call 0
+    assert not stall.still_stalled(), "call RING took the slot of call 0 without waiting for it"
     torch.cuda.synchronize()
     for k in checked:
         calls[k][0](second, alone[k], stream)
@@ -313,11 +345,16 @@ def test_stats():
         updates.append((torch.from_numpy(rng.standard_normal((int(frames.sum()), F)).astype(np.float32)).cuda(), frames))
     small, big = max(len(f) for _, f in updates[:SLOTS]) * ST_CUT_BYTES, len(updates[SLOTS][1]) * ST_CUT_BYTES
     assert 2 * small <= FIRST_ALLOCATION < big
-    acc, one_by_one = HipStatsAccumulator(F, "cuda:0"), HipStatsAccumulator(F, "cuda:0")
-    torch.cuda.synchronize()  # the uploads; from here on nothing waits until every update is enqueued
-    for feats, frames in updates:  # update 16 lands on the slot of update 0
-        acc.update(feats, frames)
+    acc, one_by_one, twin = HipStatsAccumulator(F, "cuda:0"), HipStatsAccumulator(F, "cuda:0"), HipStatsAccumulator(F, "cuda:0")
+    side, stall = _stall_behind("stats", lambda: [twin.update(feats, frames) for feats, frames in updates[:SLOTS]])
+    with torch.cuda.stream(side):  # (the uploads are done: _stall_behind)
+        for feats, frames in updates[:SLOTS]:
+            acc.update(feats, frames)
+        assert stall.still_stalled(), "updates 0 ... 15 were not all issued while the stream was stalled"
+        acc.update(*updates[SLOTS])  # update 16 lands on the slot of update 0
+    assert not stall.still_stalled(), "update 16 took the slot of update 0 without waiting for it"
     torch.cuda.synchronize()
+    twin.close()
     for feats, frames in updates:
         one_by_one.update(feats, frames)
         torch.cuda.synchronize()
