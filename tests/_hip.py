@@ -16,6 +16,35 @@ _TABLE = {
 }
 
 
+_HOST_REGISTER = None
+
+
+def host_register_supported() -> bool:
+    """Can GPU 0's runtime page-lock memory the caller already has (hipHostRegister behind hipfeat_host_register)?  Asked once, with one
+    anonymous page.  Some machines (virtual ones among them) cannot: there the ring's slots stay on the staging route, as after any other
+    refused registration.  Only the RUNTIME's refusal counts as "unsupported": any other failure of the call is raised."""
+    global _HOST_REGISTER
+    if _HOST_REGISTER is None:
+        import mmap
+
+        from lhotse_amd import _lib
+
+        lib = _lib.load()
+        m = mmap.mmap(-1, mmap.PAGESIZE)
+        page = np.frombuffer(m, dtype=np.uint8)
+        try:
+            lib.check("hipfeat_host_register", 0, page.ctypes.data, page.shape[0])
+            lib.check("hipfeat_host_unregister", page.ctypes.data)
+            _HOST_REGISTER = True
+        except _lib.HipFeatError as e:
+            if "hipHostRegister(" not in str(e):
+                raise
+            _HOST_REGISTER = False
+        del page
+        m.close()
+    return _HOST_REGISTER
+
+
 def make_hip(kind: str, cfg: dict, **extra):
     cls, ccls = _TABLE[kind]
     with warnings.catch_warnings():

@@ -9,10 +9,13 @@ import pytest
 import torch
 
 import lhotse_amd as LA
+from _hip import host_register_supported
 from lhotse_amd import _lib
 from lhotse_amd.ring_loader import RingLoader, SlotWriter
 
 pytestmark = pytest.mark.gpu
+
+NO_HOST_REGISTER = "hipHostRegister is not supported here"  # (the subject of the tests that skip with it: memory of the caller, page-locked)
 
 
 def _page_aligned(nbytes):
@@ -26,6 +29,8 @@ def _direct(ex):
 
 @pytest.mark.parametrize("pcm16,half", [(False, False), (True, False), (False, True), (True, True)])
 def test_batches_in_registered_memory_are_uploaded_from_there_and_give_the_same_bits(pcm16, half):
+    if not host_register_supported():
+        pytest.skip(NO_HOST_REGISTER)
     rng = np.random.RandomState(7)
     ex = LA.HipFbank(LA.HipFbankConfig(device="cuda:0"))
     lens = [16000, 12345, 48000, 8001, 160000, 4000]
@@ -99,6 +104,8 @@ class _Noise:
 def test_ring_loader_with_page_locked_slots_feeds_the_host_pipeline():
     """Worker processes fill the slots; the slots are page-locked as they come into use; from its second use on a slot's batch is uploaded
     straight out of the ring.  Every batch equals the extractor's own per-cut result bit for bit, whichever route it took."""
+    if not host_register_supported():
+        pytest.skip(NO_HOST_REGISTER)
     specs = [(s, [16000 + 160 * s, 32000, 8000 + s]) for s in range(40)]
     ex = LA.HipFbank(LA.HipFbankConfig(device="cuda:0"))
     with RingLoader(_Noise(), num_workers=2, slot_bytes=1 << 19, num_slots=4, start_method="forkserver") as rl:

@@ -310,8 +310,8 @@ class _Accounting:
         if self.c0 and c1:
             out["container_cpus_busy"] = round((c1["usage_usec"] - self.c0["usage_usec"]) * 1e-6 / dt, 2)
             out["container_cpus_busy_user_system"] = [round((c1[k] - self.c0[k]) * 1e-6 / dt, 2) for k in ("user_usec", "system_usec")]
-            out["container_cpu_quota"] = cpu_quota()
             out["quota_periods_throttled"] = [c1["nr_throttled"] - self.c0["nr_throttled"], c1["nr_periods"] - self.c0["nr_periods"]]
+        out["container_cpu_quota"] = cpu_quota()  # (its own file: a container may show cpu.max and no cpu.stat)
         if p1:
             q0 = self.p0 or {"busy_s": 0.0, "pack_s": 0.0, "device_backpressure_s": 0.0}
             out["pipeline_thread_busy_share"] = round((p1["busy_s"] - q0["busy_s"]) / dt, 3)
