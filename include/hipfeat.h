@@ -54,6 +54,7 @@ extern "C" {
 #define HIPFEAT_CHANNELS_API HIPFEAT_API
 #define HIPFEAT_REVERB_FFT_API HIPFEAT_API
 #define HIPFEAT_RAGGED_API HIPFEAT_API /* the per-row-length forms inside the stft and grad blocks (_RAGGED_SIGNATURES) */
+#define HIPFEAT_WPE_API HIPFEAT_API    /* hipfeat_wpe_run (_WPE_SIGNATURES) */
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -884,6 +885,40 @@ HIPFEAT_RAGGED_API hipfeat_status hipfeat_grad_run_ragged(hipfeat_grad* grad, co
                                                           const int64_t* h_lengths, const float* d_grad_out, int64_t grad_out_floats,
                                                           const float* d_grad_log_energy, float* d_grad_wave, int64_t grad_wave_stride,
                                                           float* d_workspace, int64_t workspace_floats, void* stream);
+
+/* ---- WPE dereverberation of a batch of STFTs (additive to ABI v8) ------------------------------------------------ */
+/*
+ * v8 libraries built from this commit on also carry hipfeat_wpe_run; the version number did not change because nothing that existed
+ * changed.
+ *
+ * What DereverbWPE (lhotse/dataset/signal_transforms.py:404-447) does per example through dereverb_wpe_torch
+ * (lhotse/augmentation/wpe.py:87-130) between its torch.stft and torch.istft: nara_wpe's wpe_v6 with psd_context = 0, for the whole batch
+ * in one launch, one workgroup per (cut, bin).  For one cut and one bin, Y[d, t] complex64, D = channels, K = taps * D:
+ *   Yt[tau * D + d, t] = Y[d, t - delay - tau], tau = 0 ... taps - 1, zero where the frame index is negative;
+ *   X = Y; `iterations` times:  p_t = mean_d |X[d, t]|^2,  eps = 1e-10 * max_t p_t,  lambda_t = 1 / max(p_t, eps),
+ *     R = sum_{t in S} lambda_t Yt_t Yt_t^H,  P = sum_{t in S} lambda_t Yt_t Y_t^H,  G = R^-1 P,  X = Y - G^H Yt;
+ *   S = every frame (statistics_mode 0, "full") or t >= delay + taps - 1 (1, "valid"); p_t and its maximum always cover every frame.
+ * X, R, P, the Cholesky factor of R and G are float64 (the float32 input converts exactly); the weights are kept in float32, scaled by
+ * max_t p_t (G does not depend on a common factor of the weights; p_t passes through float32 on its way, so |Y| of a bin must lie within
+ * about 1e-19 ... 1e19); the output is rounded once to complex64.
+ * DELIBERATE DIFFERENCE: where R has no Cholesky factor (a pivot that is not a positive finite number) the bin returns X = Y, bit for
+ * bit: a silent bin, a silent cut, "valid" with no frame in S.  nara_wpe falls back to lstsq there, or returns NaN.
+ * The result of a (cut, bin) depends on nothing but its own Y: the same bits from run to run and for any batch composition.
+ *
+ * d_in / d_out: complex64 (re, im pairs of float32) on the CURRENT device, viewed as (batch * channels, bins, frames) with the three
+ * strides given in complex ELEMENTS (any sign, products beyond 2^31 are fine) -- what torch.stft returns for (batch * channels, samples)
+ * input is read in place, and what torch.istft takes is written in place.  The two buffers must not overlap.  Nothing is staged and
+ * nothing synchronises: one launch on `stream`.  A size of zero is a no-op.
+ * HIPFEAT_ERR_INVALID: channels < 1, a negative size, taps < 1, delay < 0, iterations < 1, another statistics_mode, a NULL or
+ * misaligned buffer.  HIPFEAT_ERR_UNSUPPORTED: taps * channels > 64; more than 2^31 - 1 (cut, bin) pairs; a working set beyond the
+ * 160 KiB of on-chip memory of a workgroup -- 16 bytes per entry of R's lower triangle and of P, 4 bytes per frame, and a tile of
+ * 8 bytes * channels * (32 + delay + taps - 1) at the least (30 s at a hop of 128 samples and 16 kHz, 3751 frames, fit for every
+ * taps * channels <= 64 with the default delay).
+ */
+HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins, int64_t frames,
+                                               int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride, int64_t out_row_stride,
+                                               int64_t out_bin_stride, int64_t out_frame_stride, int32_t taps, int32_t delay, int32_t iterations,
+                                               int32_t statistics_mode, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

@@ -241,8 +241,16 @@ _RAGGED_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
          "float*", "int64_t", "void*"],
     ),
 }
+# Likewise (HIPFEAT_WPE_API in the header): WPE dereverberation of a batch of STFTs, one launch.
+_WPE_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_wpe_run": (
+        "int",
+        ["const float*", "float*", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int32_t",
+         "int32_t", "int32_t", "int32_t", "void*"],
+    ),
+}
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
-                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES, **_RAGGED_SIGNATURES}
+                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES, **_RAGGED_SIGNATURES, **_WPE_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -354,7 +362,8 @@ class _CffiBackend:
                 continue
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
                         .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
-                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", "").replace("HIPFEAT_RAGGED_API ", ""))
+                        .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", "").replace("HIPFEAT_RAGGED_API ", "")
+                        .replace("HIPFEAT_WPE_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

@@ -50,6 +50,7 @@
 #include "kernel_grad.hpp"
 #include "grad_tables.hpp"
 #include "host_bulk.hpp"
+#include "kernel_wpe.hpp"
 
 using namespace hipfeat;
 
@@ -3617,6 +3618,50 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_manifest_lines(const char* h_heads
     return fail(HIPFEAT_ERR_INVALID, "%s (cut %lld: %lld vs %lld)", err.what, (long long)err.index, (long long)err.a, (long long)err.b);
   }
   *h_out_bytes = n;
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// WPE dereverberation (kernel_wpe.hpp): all arguments are scalars, nothing is staged, one launch on the caller's stream
+// --------------------------------------------------------------------------------------
+extern "C" HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins, int64_t frames,
+                                                          int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride,
+                                                          int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride, int32_t taps,
+                                                          int32_t delay, int32_t iterations, int32_t statistics_mode, void* stream) {
+  if (batch < 0 || channels < 1 || bins < 0 || frames < 0) return fail(HIPFEAT_ERR_INVALID, "wpe: negative size or no channel");
+  if (taps < 1 || delay < 0 || iterations < 1) return fail(HIPFEAT_ERR_INVALID, "wpe: taps >= 1, delay >= 0 and iterations >= 1 are required (got %d, %d, %d)", taps, delay, iterations);
+  if (statistics_mode != 0 && statistics_mode != 1) return fail(HIPFEAT_ERR_INVALID, "wpe: statistics_mode is 0 (full) or 1 (valid), got %d", statistics_mode);
+  if ((int64_t)taps * channels > kWpeMaxK)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe: taps * channels = %lld exceeds the kernel's limit of %d", (long long)taps * (long long)channels, kWpeMaxK);
+  if (batch == 0 || bins == 0 || frames == 0) return HIPFEAT_OK;
+  if (!d_in || !d_out) return fail(HIPFEAT_ERR_INVALID, "wpe: NULL buffer");
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(HIPFEAT_ERR_INVALID, "wpe: complex64 buffers must lie on 8-byte boundaries");
+  if (batch * bins > INT32_MAX) return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe: more than 2^31 - 1 (cut, bin) pairs in one call");
+  WpeParams p{};
+  p.in = reinterpret_cast<const float2*>(d_in);
+  p.out = reinterpret_cast<float2*>(d_out);
+  p.in_row = in_row_stride, p.in_bin = in_bin_stride, p.in_frame = in_frame_stride;
+  p.out_row = out_row_stride, p.out_bin = out_bin_stride, p.out_frame = out_frame_stride;
+  p.D = (int32_t)channels, p.F = (int32_t)bins, p.taps = taps, p.delay = delay, p.iterations = iterations, p.valid = statistics_mode;
+  const int64_t tile_cap = kWpeLdsBytes / 8;  // no tile of so many frames fits: keeps the 32-bit arithmetic of the plan exact
+  if (frames > tile_cap || delay > tile_cap) {
+    p.lds_bytes = INT32_MAX;
+  } else {
+    p.T = (int32_t)frames;
+  }
+  if (p.lds_bytes == INT32_MAX || !wpe_plan(p))
+    return fail(HIPFEAT_ERR_UNSUPPORTED,
+                "wpe: %lld frames with %lld channels, %d taps and delay %d need more than the %d bytes of on-chip memory a workgroup has (weights: 4 bytes per "
+                "frame; R, P: 16 bytes per entry; tile: 8 bytes per channel and frame of 32 + delay + taps - 1)",
+                (long long)frames, (long long)channels, taps, delay, kWpeLdsBytes);
+  // routing switch (both routes meet the parity bar): HIPFEAT_WPE_UPDATE = fma | mfma picks the rank-T update of pass 2 for every K
+  const char* upd = route_env("HIPFEAT_WPE_UPDATE");
+  const bool mfma = upd ? !std::strcmp(upd, "mfma") : p.K > kWpeFmaMaxK;
+  const void* fn = mfma ? entry<wpe_kernel<4, true>>() : (p.bs == 2 ? entry<wpe_kernel<2, false>>() : entry<wpe_kernel<4, false>>());
+  if (hipfeat_status bad = set_dynamic_lds(fn, (size_t)p.lds_bytes)) return bad;
+  void* args[] = {&p};
+  hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(batch * bins)), dim3(kWpeThreads), args, (size_t)p.lds_bytes, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "wpe launch failed: %s", hipGetErrorName(e));
   return HIPFEAT_OK;
 }
 

@@ -10,7 +10,11 @@ Post-feature transforms on the collated ``(B, T, F)`` batch, on the HIP path (SU
   kernels (time warp + clone + per-sequence sums; mean fill of the masked regions) instead of ~15 small torch kernels
   per sequence.
 
-Both need the batch on the GPU (there is no CPU fallback) and return a new tensor on the same device.
+* ``HipDereverbWPE``  -- drop-in for ``DereverbWPE`` (:404-447), which works on the raw waveforms: ``torch.stft`` of the whole batch,
+  ONE launch of the fused WPE kernel (``wpe_on_device``: one workgroup per cut and frequency bin, float64 on chip), ``torch.istft``
+  -- instead of a Python loop over the examples with dozens of complex64 launches each.
+
+All need the batch on the GPU (there is no CPU fallback) and return a new tensor on the same device.
 """
 from __future__ import annotations
 
@@ -23,7 +27,11 @@ import torch
 
 from . import _lib
 
-__all__ = ["HipGlobalMVN", "HipSpecAugment"]
+__all__ = ["HipGlobalMVN", "HipSpecAugment", "HipDereverbWPE", "wpe_on_device"]
+
+WPE_MAX_TAPS_TIMES_CHANNELS = 64  # kWpeMaxK of csrc/kernel_wpe.hpp
+WPE_TILE_FRAMES = 256  # kWpeMaxTile: frames per time tile of the kernel (it halves, down to 32, only where 256 frames of every channel do not fit)
+_WPE_MODES = {"full": 0, "valid": 1}
 
 
 def _require_cuda(features: torch.Tensor, who: str) -> torch.Tensor:
@@ -280,3 +288,78 @@ def apply_specaug(x: torch.Tensor, seg_rounds: List[np.ndarray], masks: np.ndarr
                       _lib.addr(m) if len(m) else None, len(m), stream)
             x = out
     return x
+
+
+def wpe_on_device(Y: torch.Tensor, taps: int = 10, delay: int = 3, iterations: int = 3, statistics_mode: str = "full", *,
+                  channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """WPE dereverberation (nara_wpe's ``wpe_v6`` with ``psd_context=0``; the algorithm is stated in csrc/kernel_wpe.hpp) of a batch of
+    STFTs in one launch.  ``Y``: complex64 on the device, ``(B, D, F, T)``, or ``(B * D, F, T)`` with ``channels=D`` (what
+    ``torch.stft`` returns for ``(B * D, samples)`` input; read in place whatever its strides).  The D channels of a cut are
+    dereverberated jointly.  Returns a tensor of Y's shape (``out``, if given: any strides, no overlap with Y).  A bin whose
+    correlation matrix has no Cholesky factor (a silent bin, "valid" statistics without a frame) comes back unchanged."""
+    if not isinstance(Y, torch.Tensor) or Y.device.type != "cuda":
+        raise _lib.HipFeatError(_lib.ERR_INVALID, "wpe_on_device runs on an AMD GPU: pass a complex64 tensor on a 'cuda' device (there is no CPU fallback)")
+    if Y.dtype != torch.complex64:
+        raise TypeError(f"wpe_on_device: expected a complex64 STFT, got {Y.dtype}")
+    if statistics_mode not in _WPE_MODES:
+        raise ValueError(f"wpe_on_device: statistics_mode is 'full' or 'valid', got {statistics_mode!r}")
+    if Y.ndim == 4 and channels is None:
+        shape, D = Y.shape, Y.shape[1]
+        rows = Y.reshape(-1, *Y.shape[2:])  # a view wherever the two leading strides allow one
+    elif Y.ndim == 3 and channels is not None and channels >= 1 and Y.shape[0] % channels == 0:
+        shape, D, rows = Y.shape, int(channels), Y
+    else:
+        raise ValueError("wpe_on_device: pass (B, D, F, T), or (B * D, F, T) with channels=D")
+    taps, delay, iterations = int(taps), int(delay), int(iterations)
+    if taps < 1 or delay < 0 or iterations < 1:
+        raise ValueError(f"wpe_on_device: taps >= 1, delay >= 0 and iterations >= 1 are required, got {taps}, {delay}, {iterations}")
+    if taps * D > WPE_MAX_TAPS_TIMES_CHANNELS:
+        raise NotImplementedError(f"wpe_on_device: taps * channels = {taps * D} exceeds the kernel's limit of {WPE_MAX_TAPS_TIMES_CHANNELS}")
+    if out is None:
+        out = torch.empty(rows.shape, dtype=torch.complex64, device=Y.device)
+    elif out.shape != shape or out.dtype != torch.complex64 or out.device != Y.device:
+        raise ValueError("wpe_on_device: `out` must have Y's shape, dtype and device")
+    out_rows = out if out.ndim == 3 else out.view(-1, *out.shape[2:])
+
+    def span(t):  # [first, last] byte address a strided tensor touches
+        lo = t.data_ptr() + 8 * sum(min(0, (n - 1) * st) for n, st in zip(t.shape, t.stride()))
+        return lo, lo + 8 * sum(abs((n - 1) * st) for n, st in zip(t.shape, t.stride())) + 7
+
+    if rows.numel() and span(rows)[0] <= span(out_rows)[1] and span(out_rows)[0] <= span(rows)[1]:
+        raise ValueError("wpe_on_device: `out` must not overlap Y in memory (the kernel re-reads Y after it has written earlier frames)")
+    N, F, T = rows.shape
+    with torch.cuda.device(Y.device):
+        try:
+            _lib.load().check("hipfeat_wpe_run", rows.data_ptr(), out_rows.data_ptr(), N // D, D, F, T, *rows.stride(), *out_rows.stride(), taps, delay,
+                              iterations, _WPE_MODES[statistics_mode], int(torch.cuda.current_stream(Y.device).cuda_stream))
+        except _lib.HipFeatError as e:
+            if e.status == _lib.ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from e
+            raise
+    return out.view(shape)
+
+
+class HipDereverbWPE(torch.nn.Module):
+    """Dereverberation with Weighted Prediction Error (DereverbWPE, signal_transforms.py:404-447): ``(B, T)`` audio is a batch of mono
+    rows, each dereverberated on its own; ``(B, D, T)`` is a batch of D-channel examples, the channels of one example jointly.  The
+    keyword-only extras are the arguments the reference leaves at nara_wpe's defaults."""
+
+    def __init__(self, n_fft: int = 512, hop_length: int = 128, *, taps: int = 10, delay: int = 3, iterations: int = 3, statistics_mode: str = "full"):
+        super().__init__()
+        self.n_fft = n_fft
+        self.hop_length = hop_length
+        self.taps, self.delay, self.iterations, self.statistics_mode = taps, delay, iterations, statistics_mode
+
+    def forward(self, audio: torch.Tensor, *args, **kwargs) -> torch.Tensor:
+        if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda":
+            raise _lib.HipFeatError(_lib.ERR_INVALID, "HipDereverbWPE runs on an AMD GPU: pass a float32 tensor on a 'cuda' device (there is no CPU fallback)")
+        if audio.dtype != torch.float32:
+            raise TypeError(f"HipDereverbWPE: expected float32 audio, got {audio.dtype}")
+        assert audio.ndim in (2, 3), "HipDereverbWPE expects (B, T) or (B, D, T) audio"
+        D = 1 if audio.ndim == 2 else audio.shape[1]
+        # dereverb_wpe_torch (lhotse/augmentation/wpe.py:111-129): periodic Blackman window, centred frames
+        window = torch.blackman_window(self.n_fft, device=audio.device)
+        Y = torch.stft(audio.reshape(-1, audio.shape[-1]), n_fft=self.n_fft, hop_length=self.hop_length, return_complex=True, window=window)
+        Z = wpe_on_device(Y, self.taps, self.delay, self.iterations, self.statistics_mode, channels=D)
+        z = torch.istft(Z, n_fft=self.n_fft, hop_length=self.hop_length, window=window)
+        return z.reshape(*audio.shape[:-1], z.shape[-1])
