@@ -55,6 +55,7 @@ extern "C" {
 #define HIPFEAT_REVERB_FFT_API HIPFEAT_API
 #define HIPFEAT_RAGGED_API HIPFEAT_API /* the per-row-length forms inside the stft and grad blocks (_RAGGED_SIGNATURES) */
 #define HIPFEAT_WPE_API HIPFEAT_API    /* hipfeat_wpe_run (_WPE_SIGNATURES) */
+#define HIPFEAT_WPESTFT_API HIPFEAT_API /* the ragged WPE chain: stft, per-example frame counts, istft (_WPESTFT_SIGNATURES) */
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -919,6 +920,46 @@ HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, float* d_out, 
                                                int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride, int64_t out_row_stride,
                                                int64_t out_bin_stride, int64_t out_frame_stride, int32_t taps, int32_t delay, int32_t iterations,
                                                int32_t statistics_mode, void* stream);
+
+/* ---- ragged WPE: centred STFT, per-example frame counts, inverse STFT (additive to ABI v8) ----------------------- */
+/*
+ * DereverbWPE for a padded batch with a length per example, samples to samples on the device: example b is its first lengths[b] samples
+ * and nothing else (nothing behind them is read; NaN there is legal).  Three launches on `stream`; no handle, nothing staged, nothing
+ * synchronises.  n_fft is 256, 512, 1024 or 2048 and hop n_fft / 4 or n_fft / 2 (anything else: HIPFEAT_ERR_UNSUPPORTED).  d_window:
+ * n_fft float32 on the device (the reference's is torch.blackman_window(n_fft), periodic).  The transforms run in float64 and round
+ * once to float32.  A result depends on nothing but the example's own data: the same bits alone and in any batch.
+ *
+ * hipfeat_wpe_stft_run: what torch.stft(center=True, pad_mode="reflect", window) gives for each example alone.  d_audio is float32
+ *   (batch, channels, num_samples) through the two element strides, unit stride along samples; d_lengths int32 per example (the
+ *   channels of an example share it), clamped to 0 ... num_samples.  Example b has 1 + lengths[b] / hop frames, frame t over samples
+ *   [t hop - n_fft / 2, t hop + n_fft / 2) reflected at the example's own two ends; they are written (complex64) to d_out viewed as
+ *   (batch * channels, n_fft / 2 + 1, frames_max) through three element strides, frames at and behind the example's count as 0, and the
+ *   counts to d_frames (int32 per example; may be NULL).  An example of n_fft / 2 samples or fewer cannot be reflected: the caller
+ *   refuses it (the kernel gives it no frame).  HIPFEAT_ERR_INVALID: frames_max > 1 + num_samples / hop.
+ * hipfeat_wpe_run_ragged: hipfeat_wpe_run with d_frames, int32 per example on the device (the frame table was chosen over lengths and
+ *   a hop: the STFT writes it and the inverse reads it).  Only the first frames[b] (clamped to 0 ... frames) frames of example b exist:
+ *   the statistics, the taps and the output cover them alone, and the output frames behind them are 0.  An example whose count equals
+ *   `frames` gets the bits of hipfeat_wpe_run.
+ * hipfeat_wpe_istft_run: what torch.istft(n_fft, hop, window) gives for the first frames[b] frames of each example: per frame an inverse
+ *   real transform (the imaginary parts of bin 0 and of the Nyquist bin are ignored) times the window; per sample the frames that cover
+ *   it added in ascending order, divided by the sum of their squared window values; the first n_fft / 2 samples trimmed.  Example b has
+ *   hop * (frames[b] - 1) samples; d_out, float32 (batch, channels, out_samples) through two element strides, is +0.0 behind them,
+ *   written by the same launch.  The window envelope must not vanish inside an example (torch raises there; here the sample is not finite).
+ * All three -- HIPFEAT_ERR_INVALID: channels < 1, a negative size, a NULL or misaligned buffer.  HIPFEAT_ERR_UNSUPPORTED: more than
+ * 2^24 - 1 workgroups (stft: rows * ceil(frames_max / 32); istft: rows * ceil(out_samples / (8 hop))).
+ */
+HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_stft_run(const float* d_audio, int64_t batch, int64_t channels, int64_t row_stride, int64_t channel_stride,
+                                                        int64_t num_samples, const int32_t* d_lengths, const float* d_window, int32_t n_fft, int32_t hop,
+                                                        float* d_out, int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride,
+                                                        int64_t frames_max, int32_t* d_frames, void* stream);
+HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_run_ragged(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins, int64_t frames,
+                                                          int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride, int64_t out_row_stride,
+                                                          int64_t out_bin_stride, int64_t out_frame_stride, int32_t taps, int32_t delay,
+                                                          int32_t iterations, int32_t statistics_mode, const int32_t* d_frames, void* stream);
+HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_istft_run(const float* d_in, int64_t batch, int64_t channels, int64_t in_row_stride, int64_t in_bin_stride,
+                                                         int64_t in_frame_stride, int64_t frames_max, const int32_t* d_frames, const float* d_window,
+                                                         int32_t n_fft, int32_t hop, float* d_out, int64_t out_row_stride, int64_t out_channel_stride,
+                                                         int64_t out_samples, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

@@ -249,8 +249,27 @@ _WPE_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
          "int32_t", "int32_t", "int32_t", "void*"],
     ),
 }
+# Likewise (HIPFEAT_WPESTFT_API in the header): the ragged WPE chain -- centred STFT, WPE with a frame count per example, inverse STFT.
+_WPESTFT_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_wpe_stft_run": (
+        "int",
+        ["const float*", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "const int32_t*", "const float*", "int32_t", "int32_t", "float*", "int64_t",
+         "int64_t", "int64_t", "int64_t", "int32_t*", "void*"],
+    ),
+    "hipfeat_wpe_run_ragged": (
+        "int",
+        ["const float*", "float*", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int32_t",
+         "int32_t", "int32_t", "int32_t", "const int32_t*", "void*"],
+    ),
+    "hipfeat_wpe_istft_run": (
+        "int",
+        ["const float*", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "int64_t", "const int32_t*", "const float*", "int32_t", "int32_t", "float*",
+         "int64_t", "int64_t", "int64_t", "void*"],
+    ),
+}
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
-                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES, **_RAGGED_SIGNATURES, **_WPE_SIGNATURES}
+                     **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES, **_RAGGED_SIGNATURES, **_WPE_SIGNATURES,
+                     **_WPESTFT_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -363,7 +382,7 @@ class _CffiBackend:
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
                         .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
                         .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", "").replace("HIPFEAT_RAGGED_API ", "")
-                        .replace("HIPFEAT_WPE_API ", ""))
+                        .replace("HIPFEAT_WPE_API ", "").replace("HIPFEAT_WPESTFT_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

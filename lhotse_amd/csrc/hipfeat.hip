@@ -51,6 +51,7 @@
 #include "grad_tables.hpp"
 #include "host_bulk.hpp"
 #include "kernel_wpe.hpp"
+#include "kernel_wpe_stft.hpp"
 
 using namespace hipfeat;
 
@@ -3624,10 +3625,9 @@ extern "C" HIPFEAT_API hipfeat_status hipfeat_manifest_lines(const char* h_heads
 // --------------------------------------------------------------------------------------
 // WPE dereverberation (kernel_wpe.hpp): all arguments are scalars, nothing is staged, one launch on the caller's stream
 // --------------------------------------------------------------------------------------
-extern "C" HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins, int64_t frames,
-                                                          int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride,
-                                                          int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride, int32_t taps,
-                                                          int32_t delay, int32_t iterations, int32_t statistics_mode, void* stream) {
+static hipfeat_status wpe_launch(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins, int64_t frames, int64_t in_row_stride,
+                                 int64_t in_bin_stride, int64_t in_frame_stride, int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride,
+                                 int32_t taps, int32_t delay, int32_t iterations, int32_t statistics_mode, const int32_t* d_frames, void* stream) {
   if (batch < 0 || channels < 1 || bins < 0 || frames < 0) return fail(HIPFEAT_ERR_INVALID, "wpe: negative size or no channel");
   if (taps < 1 || delay < 0 || iterations < 1) return fail(HIPFEAT_ERR_INVALID, "wpe: taps >= 1, delay >= 0 and iterations >= 1 are required (got %d, %d, %d)", taps, delay, iterations);
   if (statistics_mode != 0 && statistics_mode != 1) return fail(HIPFEAT_ERR_INVALID, "wpe: statistics_mode is 0 (full) or 1 (valid), got %d", statistics_mode);
@@ -3640,6 +3640,7 @@ extern "C" HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, flo
   WpeParams p{};
   p.in = reinterpret_cast<const float2*>(d_in);
   p.out = reinterpret_cast<float2*>(d_out);
+  p.frames = d_frames;
   p.in_row = in_row_stride, p.in_bin = in_bin_stride, p.in_frame = in_frame_stride;
   p.out_row = out_row_stride, p.out_bin = out_bin_stride, p.out_frame = out_frame_stride;
   p.D = (int32_t)channels, p.F = (int32_t)bins, p.taps = taps, p.delay = delay, p.iterations = iterations, p.valid = statistics_mode;
@@ -3663,6 +3664,96 @@ extern "C" HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, flo
   hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(batch * bins)), dim3(kWpeThreads), args, (size_t)p.lds_bytes, (hipStream_t)stream);
   if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "wpe launch failed: %s", hipGetErrorName(e));
   return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_WPE_API hipfeat_status hipfeat_wpe_run(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins, int64_t frames,
+                                                          int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride,
+                                                          int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride, int32_t taps,
+                                                          int32_t delay, int32_t iterations, int32_t statistics_mode, void* stream) {
+  return wpe_launch(d_in, d_out, batch, channels, bins, frames, in_row_stride, in_bin_stride, in_frame_stride, out_row_stride, out_bin_stride,
+                    out_frame_stride, taps, delay, iterations, statistics_mode, nullptr, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// Ragged WPE (kernel_wpe_stft.hpp): the centred STFT in front of the WPE kernel, that kernel with a frame count per example, and the
+// inverse STFT behind it.  Scalars and pointers only, nothing staged, one launch each on the caller's stream
+// --------------------------------------------------------------------------------------
+extern "C" HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_run_ragged(const float* d_in, float* d_out, int64_t batch, int64_t channels, int64_t bins,
+                                                                     int64_t frames, int64_t in_row_stride, int64_t in_bin_stride, int64_t in_frame_stride,
+                                                                     int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride,
+                                                                     int32_t taps, int32_t delay, int32_t iterations, int32_t statistics_mode,
+                                                                     const int32_t* d_frames, void* stream) {
+  if (batch > 0 && bins > 0 && frames > 0 && (!d_frames || ((uintptr_t)d_frames & 3)))
+    return fail(HIPFEAT_ERR_INVALID, "wpe: the ragged form needs a frame count per example (int32, on the device)");
+  return wpe_launch(d_in, d_out, batch, channels, bins, frames, in_row_stride, in_bin_stride, in_frame_stride, out_row_stride, out_bin_stride,
+                    out_frame_stride, taps, delay, iterations, statistics_mode, d_frames, stream);
+}
+
+// log2(n_fft) of a supported transform (256 ... 2048 points, a hop of a quarter or half of it), or 0
+static int wpe_stft_log2(int32_t n_fft, int32_t hop) {
+  for (int l = 8; l <= 11; ++l)
+    if (n_fft == (1 << l) && (hop == n_fft / 4 || hop == n_fft / 2)) return l;
+  return 0;
+}
+
+template <class Params>
+static hipfeat_status wpe_stft_launch(const void* fn, Params& p, int64_t rows, int64_t tiles, const char* what, void* stream) {
+  if (rows * tiles > (int64_t)(UINT32_MAX / kWpeStftThreads)) return fail(HIPFEAT_ERR_UNSUPPORTED, "%s: more than %u workgroups in one call", what, UINT32_MAX / kWpeStftThreads);
+  p.tiles = (int32_t)tiles;
+  if (hipfeat_status bad = set_dynamic_lds(fn, (size_t)p.lds_bytes)) return bad;
+  void* args[] = {&p};
+  hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(rows * tiles)), dim3(kWpeStftThreads), args, (size_t)p.lds_bytes, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "%s launch failed: %s", what, hipGetErrorName(e));
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_stft_run(const float* d_audio, int64_t batch, int64_t channels, int64_t row_stride,
+                                                                   int64_t channel_stride, int64_t num_samples, const int32_t* d_lengths,
+                                                                   const float* d_window, int32_t n_fft, int32_t hop, float* d_out,
+                                                                   int64_t out_row_stride, int64_t out_bin_stride, int64_t out_frame_stride,
+                                                                   int64_t frames_max, int32_t* d_frames, void* stream) {
+  if (batch < 0 || channels < 1 || num_samples < 0 || frames_max < 0) return fail(HIPFEAT_ERR_INVALID, "wpe stft: negative size or no channel");
+  const int log2n = wpe_stft_log2(n_fft, hop);
+  if (!log2n)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe stft: n_fft is 256, 512, 1024 or 2048 and hop_length a quarter or half of it (got %d, %d)", n_fft, hop);
+  if (frames_max > 1 + num_samples / hop)
+    return fail(HIPFEAT_ERR_INVALID, "wpe stft: %lld frames asked of rows of %lld samples at a hop of %d", (long long)frames_max, (long long)num_samples, hop);
+  if (batch == 0 || frames_max == 0) return HIPFEAT_OK;
+  if (!d_audio || !d_lengths || !d_window || !d_out) return fail(HIPFEAT_ERR_INVALID, "wpe stft: NULL buffer");
+  if ((((uintptr_t)d_audio | (uintptr_t)d_lengths | (uintptr_t)d_window | (uintptr_t)d_frames) & 3) || ((uintptr_t)d_out & 7))
+    return fail(HIPFEAT_ERR_INVALID, "wpe stft: float32 / int32 buffers must lie on 4-byte boundaries, the complex64 output on an 8-byte one");
+  if (frames_max > INT32_MAX) return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe stft: more than 2^31 - 1 frames in a row");
+  WpeStftParams p{};
+  p.audio = d_audio, p.lengths = d_lengths, p.window = d_window, p.out = reinterpret_cast<float2*>(d_out), p.frames_out = d_frames;
+  p.a_row = row_stride, p.a_chan = channel_stride, p.o_row = out_row_stride, p.o_bin = out_bin_stride, p.o_frame = out_frame_stride;
+  p.num_samples = num_samples, p.D = (int32_t)std::min<int64_t>(channels, INT32_MAX), p.N = n_fft, p.log2n = log2n, p.hop = hop, p.frames_max = (int32_t)frames_max;
+  int32_t off_acc;
+  wpe_stft_lds_map(n_fft, 0, p.off_win, p.off_work, off_acc, p.lds_bytes);
+  if (batch > INT32_MAX / channels) return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe stft: more than 2^31 - 1 rows");
+  return wpe_stft_launch(entry<wpe_stft_kernel>(), p, batch * channels, (frames_max + kWpeStftTileFrames - 1) / kWpeStftTileFrames, "wpe stft", stream);
+}
+
+extern "C" HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_istft_run(const float* d_in, int64_t batch, int64_t channels, int64_t in_row_stride,
+                                                                    int64_t in_bin_stride, int64_t in_frame_stride, int64_t frames_max,
+                                                                    const int32_t* d_frames, const float* d_window, int32_t n_fft, int32_t hop,
+                                                                    float* d_out, int64_t out_row_stride, int64_t out_channel_stride,
+                                                                    int64_t out_samples, void* stream) {
+  if (batch < 0 || channels < 1 || frames_max < 0 || out_samples < 0) return fail(HIPFEAT_ERR_INVALID, "wpe istft: negative size or no channel");
+  const int log2n = wpe_stft_log2(n_fft, hop);
+  if (!log2n)
+    return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe istft: n_fft is 256, 512, 1024 or 2048 and hop_length a quarter or half of it (got %d, %d)", n_fft, hop);
+  if (batch == 0 || out_samples == 0) return HIPFEAT_OK;
+  if (!d_in || !d_frames || !d_window || !d_out) return fail(HIPFEAT_ERR_INVALID, "wpe istft: NULL buffer");
+  if ((((uintptr_t)d_out | (uintptr_t)d_frames | (uintptr_t)d_window) & 3) || ((uintptr_t)d_in & 7))
+    return fail(HIPFEAT_ERR_INVALID, "wpe istft: float32 / int32 buffers must lie on 4-byte boundaries, the complex64 input on an 8-byte one");
+  if (frames_max > INT32_MAX || batch > INT32_MAX / channels) return fail(HIPFEAT_ERR_UNSUPPORTED, "wpe istft: more than 2^31 - 1 frames or rows");
+  WpeIstftParams p{};
+  p.in = reinterpret_cast<const float2*>(d_in), p.frames = d_frames, p.window = d_window, p.out = d_out;
+  p.i_row = in_row_stride, p.i_bin = in_bin_stride, p.i_frame = in_frame_stride, p.o_row = out_row_stride, p.o_chan = out_channel_stride;
+  p.out_samples = out_samples, p.D = (int32_t)channels, p.N = n_fft, p.log2n = log2n, p.hop = hop, p.frames_max = (int32_t)frames_max;
+  const int64_t span = (int64_t)kWpeIstftTileHops * hop;
+  wpe_stft_lds_map(n_fft, span, p.off_win, p.off_work, p.off_acc, p.lds_bytes);
+  return wpe_stft_launch(entry<wpe_istft_kernel>(), p, batch * channels, (out_samples + span - 1) / span, "wpe istft", stream);
 }
 
 #include "host_pipeline.hpp"

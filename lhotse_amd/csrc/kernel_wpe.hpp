@@ -16,6 +16,9 @@
 // itself passes through the float32 array on its way, so |Y| of a bin must lie within about 1e-19 ... 1e19; the output is rounded once to complex64.  X is never stored between iterations:
 // a pass that needs X_t recomputes it from the Y tile and the current G.
 //
+// Ragged batches: with a frame table (WpeParams::frames) the T of a workgroup is its cut's own count; the frames behind it are not read and
+// are written as zeros.  Everything below runs on that T, so a cut's bits are those of the cut alone (given the same time tile).
+//
 // Order of summation: a thread owns a BS x BS block of R or P and one of `slices` residues of the frame index; it adds its frames in
 // ascending order, and the slices are folded by a butterfly over the lanes (K <= 16).  Above, a wave owns 16 x 16 blocks on the float64
 // matrix instruction, four frames per step in ascending order (mono blocks split over two waves by alternate steps, folded in order).  No atomics, no workspace: same bits from run to run and
@@ -35,6 +38,7 @@ constexpr int kWpeLdsBytes = 160 * 1024;   // LDS of a gfx950 compute unit
 struct WpeParams {
   const float2* in;
   float2* out;
+  const int32_t* frames;                // per cut: only its first frames[cut] frames exist (clamped to 0 ... T); null: all T of every cut
   int64_t in_row, in_bin, in_frame;     // element (complex64) strides of the (B * D, F, T) input ...
   int64_t out_row, out_bin, out_frame;  // ... and output
   int32_t D, F, T, taps, delay, iterations, valid;
@@ -119,7 +123,7 @@ __global__ __launch_bounds__(kWpeThreads) void wpe_kernel(const WpeParams p) {
   const int64_t cut = blockIdx.x / p.F, bin = blockIdx.x - cut * p.F;
   const float2* __restrict__ yin = p.in + cut * p.D * p.in_row + bin * p.in_bin;
   float2* __restrict__ zout = p.out + cut * p.D * p.out_row + bin * p.out_bin;
-  const int K = p.K, D = p.D, T = p.T;
+  const int K = p.K, D = p.D, T = p.frames ? min(max(p.frames[cut], 0), p.T) : p.T;  // workgroup-uniform
 
   auto load_tile = [&](int t0) {  // frames t0 - halo ... t0 + tile - 1 of every channel, zero outside 0 ... T - 1
     __syncthreads();
@@ -401,6 +405,11 @@ __global__ __launch_bounds__(kWpeThreads) void wpe_kernel(const WpeParams p) {
           if (dc + r < D) zout[(int64_t)(dc + r) * p.out_row + (int64_t)t * p.out_frame] = make_float2((float)X[r].x, (float)X[r].y);
       }
     }
+  }
+  const int rest = p.T - T;  // frames behind a shorter cut's own: zero
+  for (int e = tid; e < D * rest; e += kWpeThreads) {
+    const int d = e / rest, t = T + (e - d * rest);
+    zout[(int64_t)d * p.out_row + (int64_t)t * p.out_frame] = make_float2(0.0f, 0.0f);
   }
 }
 

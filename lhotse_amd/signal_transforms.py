@@ -12,7 +12,9 @@ Post-feature transforms on the collated ``(B, T, F)`` batch, on the HIP path (SU
 
 * ``HipDereverbWPE``  -- drop-in for ``DereverbWPE`` (:404-447), which works on the raw waveforms: ``torch.stft`` of the whole batch,
   ONE launch of the fused WPE kernel (``wpe_on_device``: one workgroup per cut and frequency bin, float64 on chip), ``torch.istft``
-  -- instead of a Python loop over the examples with dozens of complex64 launches each.
+  -- instead of a Python loop over the examples with dozens of complex64 launches each.  With ``lengths=`` (a padded batch and its
+  ``audio_lens``) the transforms run on the device too (``wpe_stft_on_device``, ``wpe_istft_on_device``: csrc/kernel_wpe_stft.hpp), each
+  row reflected, dereverberated and resynthesised within its own length.
 
 All need the batch on the GPU (there is no CPU fallback) and return a new tensor on the same device.
 """
@@ -27,10 +29,12 @@ import torch
 
 from . import _lib
 
-__all__ = ["HipGlobalMVN", "HipSpecAugment", "HipDereverbWPE", "wpe_on_device"]
+__all__ = ["HipGlobalMVN", "HipSpecAugment", "HipDereverbWPE", "wpe_on_device", "wpe_stft_on_device", "wpe_istft_on_device"]
 
 WPE_MAX_TAPS_TIMES_CHANNELS = 64  # kWpeMaxK of csrc/kernel_wpe.hpp
 WPE_TILE_FRAMES = 256  # kWpeMaxTile: frames per time tile of the kernel (it halves, down to 32, only where 256 frames of every channel do not fit)
+WPE_STFT_SIZES = (256, 512, 1024, 2048)  # n_fft of csrc/kernel_wpe_stft.hpp; the hop is a quarter or half of it
+WPE_ISTFT_TILE_HOPS = 8  # kWpeIstftTileHops: output hops per workgroup of the inverse STFT
 _WPE_MODES = {"full": 0, "valid": 1}
 
 
@@ -291,12 +295,16 @@ def apply_specaug(x: torch.Tensor, seg_rounds: List[np.ndarray], masks: np.ndarr
 
 
 def wpe_on_device(Y: torch.Tensor, taps: int = 10, delay: int = 3, iterations: int = 3, statistics_mode: str = "full", *,
-                  channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  channels: Optional[int] = None, out: Optional[torch.Tensor] = None, frames: Optional[torch.Tensor] = None) -> torch.Tensor:
     """WPE dereverberation (nara_wpe's ``wpe_v6`` with ``psd_context=0``; the algorithm is stated in csrc/kernel_wpe.hpp) of a batch of
     STFTs in one launch.  ``Y``: complex64 on the device, ``(B, D, F, T)``, or ``(B * D, F, T)`` with ``channels=D`` (what
     ``torch.stft`` returns for ``(B * D, samples)`` input; read in place whatever its strides).  The D channels of a cut are
     dereverberated jointly.  Returns a tensor of Y's shape (``out``, if given: any strides, no overlap with Y).  A bin whose
-    correlation matrix has no Cholesky factor (a silent bin, "valid" statistics without a frame) comes back unchanged."""
+    correlation matrix has no Cholesky factor (a silent bin, "valid" statistics without a frame) comes back unchanged.
+    ``frames``: integer ``(B,)``, CPU or device -- only the first ``frames[b]`` frames of example b exist: its result is what the example
+    gives alone, bit for bit (as long as both calls run the same time tile, ``WPE_TILE_FRAMES`` unless the longest row's working set
+    forces a smaller one), and the output frames behind them are 0.  A table on the CPU is checked against ``0 ... T``; one on the
+    device is not read back, the kernel clamps it."""
     if not isinstance(Y, torch.Tensor) or Y.device.type != "cuda":
         raise _lib.HipFeatError(_lib.ERR_INVALID, "wpe_on_device runs on an AMD GPU: pass a complex64 tensor on a 'cuda' device (there is no CPU fallback)")
     if Y.dtype != torch.complex64:
@@ -328,15 +336,126 @@ def wpe_on_device(Y: torch.Tensor, taps: int = 10, delay: int = 3, iterations: i
     if rows.numel() and span(rows)[0] <= span(out_rows)[1] and span(out_rows)[0] <= span(rows)[1]:
         raise ValueError("wpe_on_device: `out` must not overlap Y in memory (the kernel re-reads Y after it has written earlier frames)")
     N, F, T = rows.shape
-    with torch.cuda.device(Y.device):
+    args = (rows.data_ptr(), out_rows.data_ptr(), N // D, D, F, T, *rows.stride(), *out_rows.stride(), taps, delay, iterations, _WPE_MODES[statistics_mode])
+    if frames is None:
+        _wpe_call(Y.device, "hipfeat_wpe_run", *args)
+    else:
+        counts = _wpe_counts("wpe_on_device", "frames", frames, N // D, 0, T, Y.device, need_host=False)[1]
+        _wpe_call(Y.device, "hipfeat_wpe_run_ragged", *args, counts.data_ptr())
+    return out.view(shape)
+
+
+def _wpe_call(device, name: str, *args) -> None:
+    with torch.cuda.device(device):
         try:
-            _lib.load().check("hipfeat_wpe_run", rows.data_ptr(), out_rows.data_ptr(), N // D, D, F, T, *rows.stride(), *out_rows.stride(), taps, delay,
-                              iterations, _WPE_MODES[statistics_mode], int(torch.cuda.current_stream(Y.device).cuda_stream))
+            _lib.load().check(name, *args, int(torch.cuda.current_stream(device).cuda_stream))
         except _lib.HipFeatError as e:
             if e.status == _lib.ERR_UNSUPPORTED:
                 raise NotImplementedError(str(e)) from e
             raise
-    return out.view(shape)
+
+
+def _wpe_sizes(who: str, n_fft: int, hop_length: int) -> Tuple[int, int]:
+    n_fft, hop = int(n_fft), int(hop_length)
+    if n_fft not in WPE_STFT_SIZES or hop not in (n_fft // 4, n_fft // 2):
+        raise NotImplementedError(f"{who}: n_fft is one of {WPE_STFT_SIZES} and hop_length a quarter or half of it, got {n_fft} and {hop}")
+    return n_fft, hop
+
+
+def _wpe_counts(who: str, what: str, counts: torch.Tensor, batch: int, low: int, high: int, device, need_host: bool = True):
+    """A per-example table of lengths or frame counts -> (its values on the host, itself as int32 on the device).  The values are checked
+    against ``low ... high`` here, before anything is launched.  ``need_host=False``: a table on the device is taken as it is (no
+    synchronisation; the kernel clamps it to the buffer) and the host values are None."""
+    if not isinstance(counts, torch.Tensor) or counts.is_floating_point() or counts.is_complex() or counts.dtype == torch.bool or counts.shape != (batch,):
+        raise ValueError(f"{who}: `{what}` is an integer tensor of shape ({batch},), one entry per example")
+    host = None
+    if need_host or counts.device.type == "cpu":
+        host = counts.tolist()
+        for b, n in enumerate(host):
+            if not low <= n <= high:
+                raise ValueError(f"{who}: {what}[{b}] = {n} lies outside {low} ... {high}" + (
+                    " (a row must be longer than n_fft // 2 samples to be reflected, and no longer than the tensor)" if what == "lengths" else ""))
+    return host, counts.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _wpe_stft(audio: torch.Tensor, lengths: torch.Tensor, frames_max: int, n_fft: int, hop: int, window: torch.Tensor, bin_major: bool = True):
+    """(B, D, T) float32 with unit sample stride, int32 lengths on the device -> (Y (B * D, F, frames_max), frames).  ``bin_major``: Y is
+    (F, frames)-contiguous per row; otherwise (frames, F)-contiguous, torch.stft's own layout."""
+    B, D, T = audio.shape
+    F = n_fft // 2 + 1
+    if bin_major:
+        Y = torch.empty((B * D, F, frames_max), dtype=torch.complex64, device=audio.device)
+    else:
+        Y = torch.empty((B * D, frames_max, F), dtype=torch.complex64, device=audio.device).transpose(1, 2)
+    frames = torch.empty(B, dtype=torch.int32, device=audio.device)
+    _wpe_call(audio.device, "hipfeat_wpe_stft_run", audio.data_ptr(), B, D, audio.stride(0), audio.stride(1), T, lengths.data_ptr(), window.data_ptr(), n_fft,
+              hop, Y.data_ptr(), *Y.stride(), frames_max, frames.data_ptr())
+    return Y, frames
+
+
+def _wpe_istft(Z: torch.Tensor, frames: torch.Tensor, D: int, n_fft: int, hop: int, window: torch.Tensor, out_samples: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B * D, F, T) complex64 of any strides, int32 frame counts on the device -> (B * D, out_samples) float32, +0.0 behind each row's end
+    (``out``: a float32 tensor of that shape, unit sample stride, row stride uniform across examples)."""
+    N, _, T = Z.shape
+    z = torch.empty((N, out_samples), dtype=torch.float32, device=Z.device) if out is None else out
+    _wpe_call(Z.device, "hipfeat_wpe_istft_run", Z.data_ptr(), N // D, D, *Z.stride(), T, frames.data_ptr(), window.data_ptr(), n_fft, hop, z.data_ptr(),
+              D * z.stride(0), z.stride(0), out_samples)
+    return z
+
+
+def _wpe_audio(who: str, audio: torch.Tensor) -> torch.Tensor:
+    if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda":
+        raise _lib.HipFeatError(_lib.ERR_INVALID, f"{who} runs on an AMD GPU: pass a float32 tensor on a 'cuda' device (there is no CPU fallback)")
+    if audio.dtype != torch.float32:
+        raise TypeError(f"{who}: expected float32 audio, got {audio.dtype}")
+    if audio.ndim not in (2, 3):
+        raise ValueError(f"{who} expects (B, T) or (B, D, T) audio")
+    audio = audio if audio.ndim == 3 else audio[:, None]
+    return audio if audio.stride(-1) == 1 else audio.contiguous()
+
+
+def wpe_stft_on_device(audio: torch.Tensor, lengths: torch.Tensor, n_fft: int = 512, hop_length: int = 128) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Centred STFT of a padded batch with a length per row, for the WPE kernel: row ``b`` is ``audio[b, ..., :lengths[b]]`` and nothing
+    behind it is read.  ``audio``: float32 ``(B, T)`` or ``(B, D, T)`` on the device (any row and channel stride); ``lengths``: integer
+    ``(B,)``, CPU or device.  Returns ``(Y, frames)``: ``frames[b] = 1 + lengths[b] // hop_length`` (int32, on the device) and ``Y``,
+    complex64 ``(B * D, n_fft // 2 + 1, max frames)``, what ``torch.stft(row, n_fft, hop_length, window=blackman_window(n_fft),
+    return_complex=True)`` gives for each row alone, with zeros at and behind ``frames[b]``.  Memory layout: contiguous, each bin's
+    frames side by side -- what the WPE kernel, one workgroup per bin, reads along time.  ``n_fft`` is 256, 512, 1024 or 2048 and
+    ``hop_length`` a quarter or half of it; anything else raises NotImplementedError.  A row with ``lengths[b] <= n_fft // 2`` (torch's
+    reflect padding refuses it too) or ``> T`` raises ValueError before anything is launched."""
+    a3 = _wpe_audio("wpe_stft_on_device", audio)
+    n_fft, hop = _wpe_sizes("wpe_stft_on_device", n_fft, hop_length)
+    host, lens = _wpe_counts("wpe_stft_on_device", "lengths", lengths, a3.shape[0], n_fft // 2 + 1, a3.shape[-1], a3.device)
+    return _wpe_stft(a3, lens, 1 + max(host, default=-hop) // hop, n_fft, hop, torch.blackman_window(n_fft, device=a3.device))
+
+
+def wpe_istft_on_device(Z: torch.Tensor, frames: torch.Tensor, n_fft: int = 512, hop_length: int = 128, *,
+                        channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of ``wpe_stft_on_device``: ``Z`` complex64 on the device, ``(B, D, F, T)``, or ``(B * D, F, T)`` with ``channels=D``
+    (default 1), read in place whatever its strides; ``frames``: integer ``(B,)``, only the first ``frames[b]`` frames of example b
+    exist.  Returns ``(z, z_lens)``: ``z`` float32 ``(B, D, n)`` or ``(B * D, n)``, ``n = max z_lens``, row b what ``torch.istft`` gives
+    for its own frames (periodic Blackman window) and +0.0 behind ``z_lens[b] = hop_length * (frames[b] - 1)``, all written by the one
+    launch (into ``out``, if given: float32 of z's shape, unit sample stride); ``z_lens`` is int64 where ``frames`` lives.  Same sizes as ``wpe_stft_on_device``, NotImplementedError otherwise."""
+    if not isinstance(Z, torch.Tensor) or Z.device.type != "cuda":
+        raise _lib.HipFeatError(_lib.ERR_INVALID, "wpe_istft_on_device runs on an AMD GPU: pass a complex64 tensor on a 'cuda' device (there is no CPU fallback)")
+    n_fft, hop = _wpe_sizes("wpe_istft_on_device", n_fft, hop_length)
+    D = Z.shape[1] if Z.ndim == 4 and channels is None else int(channels or 1)
+    if Z.dtype != torch.complex64 or Z.ndim not in (3, 4) or Z.shape[-2] != n_fft // 2 + 1 or (Z.ndim == 3 and (D < 1 or Z.shape[0] % D)):
+        raise ValueError(f"wpe_istft_on_device: pass complex64 (B, D, {n_fft // 2 + 1}, T), or (B * D, {n_fft // 2 + 1}, T) with channels=D")
+    rows = Z if Z.ndim == 3 else Z.reshape(-1, *Z.shape[2:])
+    host, counts = _wpe_counts("wpe_istft_on_device", "frames", frames, rows.shape[0] // D, 0, Z.shape[-1], Z.device)
+    z_lens = [hop * max(n - 1, 0) for n in host]
+    n = max(z_lens, default=0)
+    if out is not None:
+        flat = out if out.ndim == 2 else out.flatten(0, 1)
+        if (out.shape != (*Z.shape[:-2], n) or out.dtype != torch.float32 or out.device != Z.device or (n > 1 and out.stride(-1) != 1)
+                or flat.data_ptr() != out.data_ptr()):
+            raise ValueError(f"wpe_istft_on_device: `out` is float32 {(*Z.shape[:-2], n)} on Z's device with unit sample stride and one row stride")
+        _wpe_istft(rows, counts, D, n_fft, hop, torch.blackman_window(n_fft, device=Z.device), n, flat)
+        return out, torch.tensor(z_lens, dtype=torch.int64, device=frames.device)
+    z = _wpe_istft(rows, counts, D, n_fft, hop, torch.blackman_window(n_fft, device=Z.device), n)
+    return (z if Z.ndim == 3 else z.view(*Z.shape[:2], -1)), torch.tensor(z_lens, dtype=torch.int64, device=frames.device)
 
 
 class HipDereverbWPE(torch.nn.Module):
@@ -350,7 +469,22 @@ class HipDereverbWPE(torch.nn.Module):
         self.hop_length = hop_length
         self.taps, self.delay, self.iterations, self.statistics_mode = taps, delay, iterations, statistics_mode
 
-    def forward(self, audio: torch.Tensor, *args, **kwargs) -> torch.Tensor:
+    def forward(self, audio: torch.Tensor, *args, lengths: Optional[torch.Tensor] = None, **kwargs):
+        """``lengths=None``: the whole ``(B, [D,] T)`` tensor is dereverberated, padding included, as the reference does; returns ``z``.
+        ``lengths``: integer ``(B,)``, CPU or device -- row b is ``audio[b, ..., :lengths[b]]`` and nothing behind it is read; returns
+        ``(z, z_lens)``, row b what the module gives for that cut alone, ``z_lens[b] = hop_length * (lengths[b] // hop_length)`` samples
+        (an integer tensor where ``lengths`` lives) and +0.0 behind them.  Three launches (``wpe_stft_on_device``, ``wpe_on_device``,
+        ``wpe_istft_on_device``; their sizes and refusals apply), no torch.stft / torch.istft."""
+        if lengths is not None:
+            a3 = _wpe_audio("HipDereverbWPE", audio)
+            n_fft, hop = _wpe_sizes("HipDereverbWPE", self.n_fft, self.hop_length)
+            host, lens = _wpe_counts("HipDereverbWPE", "lengths", lengths, a3.shape[0], n_fft // 2 + 1, a3.shape[-1], a3.device)
+            frames_max = 1 + max(host, default=-hop) // hop
+            window = torch.blackman_window(n_fft, device=a3.device)
+            Y, frames = _wpe_stft(a3, lens, frames_max, n_fft, hop, window)
+            Z = wpe_on_device(Y, self.taps, self.delay, self.iterations, self.statistics_mode, channels=a3.shape[1], frames=frames)
+            z = _wpe_istft(Z, frames, a3.shape[1], n_fft, hop, window, hop * max(frames_max - 1, 0))
+            return z.view(*audio.shape[:-1], -1), (lengths // hop) * hop
         if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda":
             raise _lib.HipFeatError(_lib.ERR_INVALID, "HipDereverbWPE runs on an AMD GPU: pass a float32 tensor on a 'cuda' device (there is no CPU fallback)")
         if audio.dtype != torch.float32:

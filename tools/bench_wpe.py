@@ -7,7 +7,9 @@ collation does, and 48 six-channel cuts of 12.5 s (600 s of six-channel audio). 
 `repeats` calls after 3 warm-up calls, and around the kernel launch alone with pass 2 on float64 FMAs and on the float64 matrix
 instruction (HIPFEAT_WPE_UPDATE = fma | mfma; without it the library picks by K).  The baseline is what DereverbWPE runs per example -- the
 algorithm of csrc/kernel_wpe.hpp as torch complex64 operations (matmul, linalg.solve), one example after the other -- on the same
-device.  Needs a GPU; there is no fallback."""
+device.  The ragged leg (`ragged_leg`) times HipDereverbWPE(audio, lengths=) -- three HIP launches, samples to samples -- against a loop
+of per-cut calls and against the padded call, its three launches one by one, and both memory layouts of the spectra; its legs alternate.
+Needs a GPU; there is no fallback."""
 import argparse
 import json
 import os
@@ -62,6 +64,52 @@ def timed(fn, repeats):
     return {"median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "repeats": repeats}
 
 
+def timed_alternating(legs, repeats):
+    """legs: name -> callable.  One call of each in turn per repeat, after 3 warm-up turns: the legs see the same machine state."""
+    times = {name: [] for name in legs}
+    for i in range(3 + repeats):
+        for name, fn in legs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= 3:
+                times[name].append(a.elapsed_time(b))
+    return {name: {"median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t), "repeats": repeats} for name, t in times.items()}
+
+
+def ragged_leg(module, audio, lengths, repeats):
+    """HipDereverbWPE(audio, lengths=) against the two things a user could do before it: a loop of per-cut calls (correct) and the padded
+    call (wrong at the row ends; the speed floor).  Then the three launches of the ragged call one by one, with the spectra laid out bin-major
+    ((F, frames)-contiguous per row: what is kept) and frame-major (torch.stft's layout)."""
+    S = LA.signal_transforms
+    a3 = audio if audio.ndim == 3 else audio[:, None]
+    D, lens, window = a3.shape[1], torch.tensor(lengths), torch.blackman_window(512, device="cuda")
+    lens_dev, frames_max = lens.to("cuda", torch.int32), 1 + max(lengths) // 128
+    legs = {
+        "ragged_call": lambda: module(audio, lengths=lens),
+        "per_cut_loop": lambda: [module(audio[b : b + 1, ..., :n]) for b, n in enumerate(lengths)],
+        "padded_call": lambda: module(audio),
+    }
+    for tag, bin_major in (("", True), ("_frame_major", False)):
+        Y, fr = S._wpe_stft(a3, lens_dev, frames_max, 512, 128, window, bin_major)
+        Z = torch.empty_strided(Y.shape, Y.stride(), dtype=Y.dtype, device="cuda")
+        legs["stft" + tag] = lambda bin_major=bin_major: S._wpe_stft(a3, lens_dev, frames_max, 512, 128, window, bin_major)
+        legs["core" + tag] = lambda Y=Y, Z=Z, fr=fr: LA.wpe_on_device(Y, channels=D, frames=fr, out=Z)
+        legs["istft" + tag] = lambda Z=Z, fr=fr: S._wpe_istft(Z, fr, D, 512, 128, window, 128 * (frames_max - 1))
+    r = timed_alternating(legs, repeats)
+    z, z_lens = module(audio, lengths=lens)
+    worst = 0.0
+    for b in range(0, len(lengths), 12):  # the ragged rows against the per-cut calls (which run torch.stft / torch.istft)
+        want = module(audio[b : b + 1, ..., : lengths[b]])[0]
+        worst = max(worst, float((z[b, ..., : z_lens[b]] - want).norm() / want.norm()))
+    r["rel_l2_ragged_vs_per_cut_worst_of_4_rows"] = worst
+    r["speedup_ragged_vs_per_cut_loop"] = r["per_cut_loop"]["median_ms"] / r["ragged_call"]["median_ms"]
+    r["ragged_over_padded_call"] = r["ragged_call"]["median_ms"] / r["padded_call"]["median_ms"]
+    return r
+
+
 def batch(shape, lengths, seed):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(shape, generator=g)
@@ -101,6 +149,7 @@ def main():
             r["kernel_launch_only_" + update] = timed(lambda: LA.wpe_on_device(Y, channels=D), args.repeats)
         del os.environ["HIPFEAT_WPE_UPDATE"]
         r["speedup_module_vs_reference_sequence"] = r["reference_sequence_complex64"]["median_ms"] / r["module"]["median_ms"]
+        r["ragged"] = ragged_leg(module, audio, mono_len if audio.ndim == 2 else [audio.shape[-1]] * audio.shape[0], args.repeats)
         print(name, json.dumps(r))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
