@@ -56,6 +56,7 @@ extern "C" {
 #define HIPFEAT_RAGGED_API HIPFEAT_API /* the per-row-length forms inside the stft and grad blocks (_RAGGED_SIGNATURES) */
 #define HIPFEAT_WPE_API HIPFEAT_API    /* hipfeat_wpe_run (_WPE_SIGNATURES) */
 #define HIPFEAT_WPESTFT_API HIPFEAT_API /* the ragged WPE chain: stft, per-example frame counts, istft (_WPESTFT_SIGNATURES) */
+#define HIPFEAT_NOISE_API HIPFEAT_API   /* hipfeat_noise_run (_NOISE_SIGNATURES) */
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -960,6 +961,33 @@ HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_istft_run(const float* d_in, int6
                                                          int64_t in_frame_stride, int64_t frames_max, const int32_t* d_frames, const float* d_window,
                                                          int32_t n_fft, int32_t hop, float* d_out, int64_t out_row_stride, int64_t out_channel_stride,
                                                          int64_t out_samples, void* stream);
+
+/* ---- Gaussian noise on a waveform batch: RandomizedSmoothing in one launch (additive to ABI v8) -------------------- */
+/*
+ * RandomizedSmoothing (lhotse/dataset/signal_transforms.py:63-118) for a batch of `rows` rows of `cols` samples:
+ *     out[b, t] = clip( x[b, t] + a[b, t] * n(seed, key_b, t) ),    a[b, t] = sigma[b] if t < lengths[b] else 0
+ * THE CONTRACT.  n is a pure function of (seed, key_b, t): Philox4x32-10 as published (multipliers 0xD2511F53 and 0xCD9E8D57, key
+ * increments 0x9E3779B9 and 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and counter (q & 0xffffffff, q >> 32,
+ * key_b & 0xffffffff, key_b >> 32), q = t / 4 counted from the row's first sample.  Its four output words r0 ... r3 are the normals of
+ * samples 4 q ... 4 q + 3 by two Box-Muller pairs, (r0, r1) then (r2, r3), on exactly representable uniforms:
+ *     u1 = ((r >> 8) + 1) * 2^-24,  u2 = (r' >> 8) * 2^-24,  n_even = sqrt(-2 ln u1) cos(2 pi u2),  n_odd = sqrt(-2 ln u1) sin(2 pi u2).
+ * Normals and sum are float32 (float16 / bfloat16 samples convert exactly), product and sum are one fmaf(a, n, x), the result is
+ * rounded once, to nearest even; the clip passes NaN on as torch.clip does; a sample with a == 0 -- a row with sigma 0, the padding
+ * behind lengths[b] -- is clip(x) bit for bit.  The bits of a sample do not depend on the batch around it, on the row strides or on
+ * where a row starts in memory.
+ *
+ * d_in / d_out: `dtype` samples on the CURRENT device, (rows, cols) through the two row strides in ELEMENTS, unit sample stride; any
+ * alignment of the element type.  d_out may be d_in itself (same strides); otherwise the two must not overlap.  d_sigma: float32 per
+ * row.  d_row_keys: int64 per row, or NULL for key_b = b.  d_lengths: int64 per row (clamped to 0 ... cols), or NULL for cols.
+ * seed: 64 bits (the int64 is read as its bit pattern).  clip_lo <= clip_hi; -INFINITY, +INFINITY disable the clip.  Nothing behind
+ * `cols` of a row is read or written.  No handle, nothing staged, nothing synchronises: one launch on `stream`.  A size of zero is a no-op.
+ * HIPFEAT_ERR_INVALID: a negative size, an unknown dtype, a row stride smaller than cols, clip_lo > clip_hi (or a NaN bound), a NULL or
+ * misaligned buffer.  HIPFEAT_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups of 1024 16-byte groups (2^45 bytes).
+ */
+typedef enum hipfeat_noise_dtype { HIPFEAT_NOISE_FLOAT32 = 0, HIPFEAT_NOISE_FLOAT16 = 1, HIPFEAT_NOISE_BFLOAT16 = 2 } hipfeat_noise_dtype;
+HIPFEAT_NOISE_API hipfeat_status hipfeat_noise_run(const void* d_in, void* d_out, int64_t rows, int64_t cols, int64_t in_row_stride,
+                                                   int64_t out_row_stride, int32_t dtype, const float* d_sigma, const int64_t* d_row_keys,
+                                                   const int64_t* d_lengths, int64_t seed, float clip_lo, float clip_hi, void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

@@ -41,6 +41,7 @@ from .whisper import HipWhisperFbank, HipWhisperFbankConfig  # noqa: F401,E402
 from .librosa_fbank import HipLibrosaFbank, HipLibrosaFbankConfig  # noqa: F401,E402
 
 from .signal_transforms import HipDereverbWPE, HipGlobalMVN, HipSpecAugment, wpe_istft_on_device, wpe_on_device, wpe_stft_on_device  # noqa: F401,E402
+from .signal_transforms import HipRandomizedSmoothing, noise_on_device  # noqa: F401,E402
 
 from .stats import GlobalStatsPass, HipStatsAccumulator, compute_global_feature_stats, get_or_create_stats  # noqa: F401,E402
 
@@ -74,6 +75,8 @@ __all__ = [
     "wpe_on_device",
     "wpe_stft_on_device",
     "wpe_istft_on_device",
+    "HipRandomizedSmoothing",
+    "noise_on_device",
     "HipLibrosaFbankConfig",
     "HipWhisperFbankConfig",
     "HipOnTheFlyFeatures",

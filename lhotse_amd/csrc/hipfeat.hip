@@ -52,6 +52,7 @@
 #include "host_bulk.hpp"
 #include "kernel_wpe.hpp"
 #include "kernel_wpe_stft.hpp"
+#include "kernel_noise.hpp"
 
 using namespace hipfeat;
 
@@ -3754,6 +3755,40 @@ extern "C" HIPFEAT_WPESTFT_API hipfeat_status hipfeat_wpe_istft_run(const float*
   const int64_t span = (int64_t)kWpeIstftTileHops * hop;
   wpe_stft_lds_map(n_fft, span, p.off_win, p.off_work, p.off_acc, p.lds_bytes);
   return wpe_stft_launch(entry<wpe_istft_kernel>(), p, batch * channels, (out_samples + span - 1) / span, "wpe istft", stream);
+}
+
+// --------------------------------------------------------------------------------------
+// Gaussian noise on a waveform batch (kernel_noise.hpp): scalars and pointers only, nothing staged, one launch on the caller's stream
+// --------------------------------------------------------------------------------------
+extern "C" HIPFEAT_NOISE_API hipfeat_status hipfeat_noise_run(const void* d_in, void* d_out, int64_t rows, int64_t cols, int64_t in_row_stride,
+                                                              int64_t out_row_stride, int32_t dtype, const float* d_sigma, const int64_t* d_row_keys,
+                                                              const int64_t* d_lengths, int64_t seed, float clip_lo, float clip_hi, void* stream) {
+  if (rows < 0 || cols < 0) return fail(HIPFEAT_ERR_INVALID, "noise: negative size");
+  if (dtype != HIPFEAT_NOISE_FLOAT32 && dtype != HIPFEAT_NOISE_FLOAT16 && dtype != HIPFEAT_NOISE_BFLOAT16)
+    return fail(HIPFEAT_ERR_INVALID, "noise: dtype is 0 (float32), 1 (float16) or 2 (bfloat16), got %d", dtype);
+  if (in_row_stride < cols || out_row_stride < cols)
+    return fail(HIPFEAT_ERR_INVALID, "noise: row strides of %lld and %lld elements for rows of %lld", (long long)in_row_stride, (long long)out_row_stride, (long long)cols);
+  if (!(clip_lo <= clip_hi)) return fail(HIPFEAT_ERR_INVALID, "noise: the clip interval needs clip_lo <= clip_hi (-inf, +inf: no clip)");
+  if (rows == 0 || cols == 0) return HIPFEAT_OK;
+  if (!d_in || !d_out || !d_sigma) return fail(HIPFEAT_ERR_INVALID, "noise: NULL buffer");
+  const uintptr_t elem = dtype == HIPFEAT_NOISE_FLOAT32 ? 4 : 2;
+  if ((((uintptr_t)d_in | (uintptr_t)d_out) & (elem - 1)) || ((uintptr_t)d_sigma & 3) || (((uintptr_t)d_row_keys | (uintptr_t)d_lengths) & 7))
+    return fail(HIPFEAT_ERR_INVALID, "noise: samples must lie on boundaries of their own size, sigma on a 4-byte and the int64 tables on 8-byte ones");
+  NoiseParams p{};
+  p.in = d_in, p.out = d_out, p.sigma = d_sigma, p.keys = d_row_keys, p.lengths = d_lengths;
+  p.rows = rows, p.cols = cols, p.in_row = in_row_stride, p.out_row = out_row_stride;
+  p.slots = (uint64_t)cols / (16 / elem) + 2;
+  p.seed_lo = (uint32_t)(uint64_t)seed, p.seed_hi = (uint32_t)((uint64_t)seed >> 32);
+  p.lo = clip_lo, p.hi = clip_hi;
+  if ((uint64_t)rows > (UINT64_MAX - kNoiseSpan) / p.slots) return fail(HIPFEAT_ERR_UNSUPPORTED, "noise: rows * groups per row beyond 2^64");
+  const uint64_t blocks = ((uint64_t)rows * p.slots + kNoiseSpan - 1) / kNoiseSpan;
+  if (blocks > (uint64_t)INT32_MAX) return fail(HIPFEAT_ERR_UNSUPPORTED, "noise: more than 2^31 - 1 workgroups (of %d 16-byte groups each) in one call", kNoiseSpan);
+  const void* fn = dtype == HIPFEAT_NOISE_FLOAT32 ? entry<noise_kernel<float>>()
+                   : dtype == HIPFEAT_NOISE_FLOAT16 ? entry<noise_kernel<_Float16>>() : entry<noise_kernel<__bf16>>();
+  void* args[] = {&p};
+  hipError_t e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(kNoiseThreads), args, 0, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "noise launch failed: %s", hipGetErrorName(e));
+  return HIPFEAT_OK;
 }
 
 #include "host_pipeline.hpp"

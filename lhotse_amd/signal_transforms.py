@@ -16,10 +16,18 @@ Post-feature transforms on the collated ``(B, T, F)`` batch, on the HIP path (SU
   ``audio_lens``) the transforms run on the device too (``wpe_stft_on_device``, ``wpe_istft_on_device``: csrc/kernel_wpe_stft.hpp), each
   row reflected, dereverberated and resynthesised within its own length.
 
+* ``HipRandomizedSmoothing`` -- device twin of ``RandomizedSmoothing`` (:63-118), the one transform that works on the waveform batch
+  itself: per-row sigma and mask are drawn on the host (B numbers each) and ONE launch adds the noise and clips (``noise_on_device``:
+  csrc/kernel_noise.hpp, Philox4x32-10 and Box-Muller inside the kernel) -- instead of ``randn_like`` and four elementwise passes.
+  DIFFERENCE TO THE REFERENCE: the noise is a pure function of ``(seed, row key, sample index)`` and not a draw from torch's generator,
+  so under ``torch.manual_seed`` neither the noise nor the per-row sigma and mask repeat the reference's numbers (the reference draws
+  B * T normals between its two host draws); the distributions are the same.
+
 All need the batch on the GPU (there is no CPU fallback) and return a new tensor on the same device.
 """
 from __future__ import annotations
 
+import bisect
 import math
 import random
 from typing import Any, Dict, List, Optional, Tuple
@@ -29,7 +37,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["HipGlobalMVN", "HipSpecAugment", "HipDereverbWPE", "wpe_on_device", "wpe_stft_on_device", "wpe_istft_on_device"]
+__all__ = ["HipGlobalMVN", "HipSpecAugment", "HipDereverbWPE", "wpe_on_device", "wpe_stft_on_device", "wpe_istft_on_device",
+           "HipRandomizedSmoothing", "noise_on_device"]
 
 WPE_MAX_TAPS_TIMES_CHANNELS = 64  # kWpeMaxK of csrc/kernel_wpe.hpp
 WPE_TILE_FRAMES = 256  # kWpeMaxTile: frames per time tile of the kernel (it halves, down to 32, only where 256 frames of every channel do not fit)
@@ -497,3 +506,121 @@ class HipDereverbWPE(torch.nn.Module):
         Z = wpe_on_device(Y, self.taps, self.delay, self.iterations, self.statistics_mode, channels=D)
         z = torch.istft(Z, n_fft=self.n_fft, hop_length=self.hop_length, window=window)
         return z.reshape(*audio.shape[:-1], z.shape[-1])
+
+
+_NOISE_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # hipfeat_noise_dtype
+
+
+def _noise_table(what: str, values, rows: int, dtype: torch.dtype, device) -> torch.Tensor:
+    """A float, or one entry per row as a sequence or tensor -> a contiguous ``(rows,)`` table on the device (one small copy at the most)."""
+    t = torch.as_tensor(values)
+    if t.ndim == 0:
+        t = t.expand(rows)
+    if t.shape != (rows,) or (not dtype.is_floating_point and (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)):
+        raise ValueError(f"noise_on_device: `{what}` has one {'number' if dtype.is_floating_point else 'integer'} per row, shape ({rows},)")
+    return t.to(device=device, dtype=dtype).contiguous()
+
+
+def noise_on_device(x: torch.Tensor, sigma, *, seed: int, row_keys=None, lengths=None, clip: Optional[Tuple[float, float]] = (-1.0, 1.0),
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[b, t] = clip(x[b, t] + a[b, t] * n(seed, key_b, t))`` with ``a[b, t] = sigma[b]`` in front of ``lengths[b]`` and 0 behind, in one
+    launch (the generator and the map to normals are stated in csrc/kernel_noise.hpp and include/hipfeat.h).  ``x``: ``(B, T)`` or
+    ``(T,)`` on the device, float32, float16 or bfloat16, any row stride, unit sample stride.  ``sigma``: a float, or one per row
+    (sequence or tensor).  ``seed``: an integer, its low 64 bits count.  ``row_keys``: one int64 per row (default: the row index) -- a
+    row's noise depends on its key and not on its place in the batch, so a cut keyed by a hash of its id gets the same noise wherever
+    it lands.  ``lengths``: integers, one per row, CPU or device; the samples at and behind them are only clipped.  ``clip=None``: no
+    clip.  Returns a new tensor, or ``out`` (x's shape and dtype, unit sample stride; ``out=x`` works in place, any other overlap
+    with x is an error of the caller).  A sample with amplitude 0 is ``clip(x)`` bit for bit."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise _lib.HipFeatError(_lib.ERR_INVALID, "noise_on_device runs on an AMD GPU: pass a float32, float16 or bfloat16 tensor on a 'cuda' device (there is no CPU fallback)")
+    if x.dtype not in _NOISE_DTYPES:
+        raise TypeError(f"noise_on_device: expected float32, float16 or bfloat16 samples, got {x.dtype}")
+    if x.ndim not in (1, 2):
+        raise ValueError("noise_on_device expects (B, T) or (T,) samples")
+    lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
+    if not lo <= hi:
+        raise ValueError(f"noise_on_device: clip=(lo, hi) needs lo <= hi, got {clip}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError("noise_on_device: `out` must have x's shape, dtype and device")
+    B, T = (1, x.shape[0]) if x.ndim == 1 else x.shape
+
+    def row_stride(t: torch.Tensor, who: str) -> int:
+        if T > 1 and t.stride(-1) != 1:
+            raise ValueError(f"noise_on_device: {who} needs unit stride along the samples")
+        stride = T if B == 1 or t.ndim == 1 else t.stride(0)
+        if stride < T:
+            raise ValueError(f"noise_on_device: the rows of {who} overlap (row stride {stride} < {T} samples)")
+        return stride
+
+    if x is not out and x.ndim == 2 and B > 1 and 0 <= x.stride(0) < T and (T == 1 or x.stride(1) == 1):
+        x = x.contiguous()  # rows that repeat or overlap (an expanded row) are legal to read
+    strides = row_stride(x, "x"), row_stride(out, "`out`")
+    table = _noise_table("sigma", sigma, B, torch.float32, x.device)
+    keys = None if row_keys is None else _noise_table("row_keys", row_keys, B, torch.int64, x.device)
+    lens = None if lengths is None else _noise_table("lengths", lengths, B, torch.int64, x.device)
+    seed = int(seed) & (2**64 - 1)
+    _wpe_call(x.device, "hipfeat_noise_run", x.data_ptr(), out.data_ptr(), B, T, *strides, _NOISE_DTYPES[x.dtype], table.data_ptr(),
+              None if keys is None else keys.data_ptr(), None if lens is None else lens.data_ptr(), seed - 2**64 if seed >= 2**63 else seed, lo, hi)
+    return out
+
+
+def schedule_value_for_step(schedule, step: int):
+    """The value of a ``[(first step, value), ...]`` schedule at ``step`` (signal_transforms.py:374-382)."""
+    milestones, values = zip(*schedule)
+    assert milestones[0] <= step, f"Cannot determine the scheduled value for step {step} with schedule: {schedule}. Did you forget to add the first part of the schedule for steps below {milestones[0]}?"
+    return values[bisect.bisect_right(milestones, step) - 1]
+
+
+def _mix64(a: int, b: int) -> int:
+    """splitmix64's finaliser over a + b * golden ratio: the launch seed of call b of a module seeded with a."""
+    z = (a + (b + 1) * 0x9E3779B97F4A7C15) & (2**64 - 1)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2**64 - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2**64 - 1)
+    return z ^ (z >> 31)
+
+
+class HipRandomizedSmoothing(torch.nn.Module):
+    """Randomized smoothing (RandomizedSmoothing, signal_transforms.py:63-118): Gaussian noise added to a batch of waveforms, the sum
+    clipped to [-1, 1].  ``sigma`` (a float, or a ``[(step, value)]`` schedule read at ``step``, which advances per call as the
+    reference's does: under a schedule only), ``sample_sigma`` (a factor ``2 u - 1`` per row) and ``p`` (the probability that a row gets
+    noise at all) are the reference's; the two per-row draws come from torch's generator on the host, B numbers each, and fold into one
+    sigma table: a masked row gets 0.  The table goes up in one small copy and ``noise_on_device`` does the rest in one launch.
+    ``seed``: the noise itself is Philox's (see the module docstring for the difference to the reference); call i of a module uses a
+    launch seed mixed from ``seed`` and i, so successive calls differ and a module built again with the same seed replays them;
+    ``seed=None`` draws one from torch's generator per call.  ``row_keys`` / ``lengths``: as for ``noise_on_device``.  Audio is
+    ``(B, T)`` or ``(B, C, T)`` (the channels of an example share its sigma, its mask and its length; their noise differs)."""
+
+    def __init__(self, sigma=0.1, sample_sigma: bool = True, p: float = 0.3, seed: Optional[int] = None):
+        super().__init__()
+        self.sigma = sigma
+        self.sample_sigma = sample_sigma
+        self.p = p
+        self.seed = seed
+        self.step = 0
+        self.calls = 0
+
+    def forward(self, audio: torch.Tensor, *args, lengths=None, row_keys=None, **kwargs) -> torch.Tensor:
+        if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda":
+            raise _lib.HipFeatError(_lib.ERR_INVALID, "HipRandomizedSmoothing runs on an AMD GPU: pass a float32, float16 or bfloat16 tensor on a 'cuda' device (there is no CPU fallback)")
+        if audio.ndim not in (2, 3):
+            raise ValueError("HipRandomizedSmoothing expects (B, T) or (B, C, T) audio")
+        if isinstance(self.sigma, (int, float)):
+            sigma = self.sigma
+        else:
+            sigma = schedule_value_for_step(self.sigma, self.step)
+            self.step += 1
+        B = audio.shape[0]
+        table = torch.full((B,), float(sigma))
+        if self.sample_sigma:
+            table = table * (2 * torch.rand(B) - 1)
+        table = table * (torch.rand(B) > 1.0 - self.p)  # random_mask_along_batch_axis(p=1 - self.p): a row keeps its noise with probability p
+        seed = int(torch.randint(0, 2**62, ()).item()) if self.seed is None else int(self.seed)
+        seed, self.calls = _mix64(seed, self.calls), self.calls + 1
+        if audio.ndim == 2:
+            return noise_on_device(audio, table, seed=seed, row_keys=row_keys, lengths=lengths)
+        C = audio.shape[1]
+        per_row = lambda t: None if t is None else torch.as_tensor(t).repeat_interleave(C)  # noqa: E731
+        keys = torch.as_tensor(row_keys).repeat_interleave(C) * C + torch.arange(C).repeat(B) if row_keys is not None else None
+        return noise_on_device(audio.flatten(0, 1), per_row(table), seed=seed, row_keys=keys, lengths=per_row(lengths)).view(audio.shape)
