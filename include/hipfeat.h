@@ -57,6 +57,7 @@ extern "C" {
 #define HIPFEAT_WPE_API HIPFEAT_API    /* hipfeat_wpe_run (_WPE_SIGNATURES) */
 #define HIPFEAT_WPESTFT_API HIPFEAT_API /* the ragged WPE chain: stft, per-example frame counts, istft (_WPESTFT_SIGNATURES) */
 #define HIPFEAT_NOISE_API HIPFEAT_API   /* hipfeat_noise_run (_NOISE_SIGNATURES) */
+#define HIPFEAT_NARROWBAND_API HIPFEAT_API /* hipfeat_narrowband_* (_NARROWBAND_SIGNATURES) */
 
 typedef enum hipfeat_status {
   HIPFEAT_OK = 0,
@@ -988,6 +989,44 @@ typedef enum hipfeat_noise_dtype { HIPFEAT_NOISE_FLOAT32 = 0, HIPFEAT_NOISE_FLOA
 HIPFEAT_NOISE_API hipfeat_status hipfeat_noise_run(const void* d_in, void* d_out, int64_t rows, int64_t cols, int64_t in_row_stride,
                                                    int64_t out_row_stride, int32_t dtype, const float* d_sigma, const int64_t* d_row_keys,
                                                    const int64_t* d_lengths, int64_t seed, float clip_lo, float clip_hi, void* stream);
+
+/* ---- Narrowband (mu-law telephone channel) on a waveform batch, one fused launch (additive to ABI v8) ---------------- */
+/*
+ * Narrowband(codec="mulaw", source_sampling_rate=rate, restore_orig_sr=restore) (lhotse/augmentation/torchaudio.py:337-378) for `rows`
+ * rows of `cols` samples.  THE RULE, per row x of n = lengths[b] samples taken alone, zeros outside [0, n):
+ *   1. d = x if rate == 8000, else ResampleTensor(rate -> 8000)(x) (resample.py:186-315): L8 = hipfeat_resampled_length(n, rate, 8000) samples.
+ *   2. MuLawEncoding(256) then MuLawDecoding(256) in float32, mu = 255:
+ *        u = (sign(d) * log1p(mu |d|) / log1p(mu) + 1) / 2 * mu + 0.5;  c = trunc(u), a cast toward zero and NO clamp (|d| > 1 gives
+ *        codes outside 0 ... 255);  v = c / mu * 2 - 1;  q = sign(v) * (exp(|v| * log1p(mu)) - 1) / mu.
+ *      q exists on [0, L8) only: outside, the second resampler sees 0.0, not the decoded silence q(0) = 8.6e-5.
+ *   3. restore != 0 and rate != 8000: z = ResampleTensor(8000 -> rate)(q) cut to n samples (it is never shorter).  Otherwise the result
+ *      is q, L8 samples.
+ * Every FIR sample is the chain of hipfeat_sinc_run: an accumulator that starts at 0 and one fmaf per tap, taps ascending over the
+ * window of 2 width + 2 taps.  The 8 kHz signal never reaches device memory.  codec="lpc10" (spandsp) is not served.
+ *
+ * hipfeat_narrowband_tables / _geometry: pure host, no device.  h_dims[8] = {orig, new, width, W} of rate -> 8000, then of 8000 -> rate
+ * (rates reduced by their gcd; all 0 for rate == 8000); h_down_w[new][W] / h_down_first[new] and h_up_w / h_up_first as
+ * hipfeat_sinc_weights lays them out, each may be NULL.  h_geometry[4] = {M: 8 kHz samples of a tile, the samples in front of and behind
+ * a tile that its output windows reach, dynamic LDS bytes of the launch}.
+ * hipfeat_narrowband_create: the handle of one source rate on the CURRENT device, its tables staged once.  rate <= 0:
+ * HIPFEAT_ERR_INVALID; HIPFEAT_ERR_UNSUPPORTED, with the rate in the message: a rate below 8000, a window beyond 96 taps, tables and a tile
+ * of 256 samples beyond 160 KB of LDS (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100 and 48000 are served).
+ * hipfeat_narrowband_run: d_x (rows, cols) and d_out (rows, out_cols) float32 through their row strides in samples, unit sample stride,
+ * any 4-byte alignment, not overlapping; out_cols = cols when restore != 0 and rate != 8000 (and when rate == 8000), else
+ * hipfeat_resampled_length(cols, rate, 8000).  d_lengths: int64 per row on the device, clamped to 0 ... cols by the kernel and never
+ * read back, or NULL for cols.  Output behind a row's own length is +0.0 up to out_cols; input behind lengths[b] is never used.  One
+ * launch on `stream`, nothing synchronises.  A size of zero is a no-op.  HIPFEAT_ERR_INVALID, before any device call: a NULL handle or
+ * buffer, a negative size, cols > 2^30, a row stride smaller than its row, a misaligned pointer.
+ */
+typedef struct hipfeat_narrowband hipfeat_narrowband;
+HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_create(int32_t source_rate, hipfeat_narrowband** out);
+HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_destroy(hipfeat_narrowband* narrowband);
+HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_tables(int32_t source_rate, int32_t* h_dims, float* h_down_w, int32_t* h_down_first,
+                                                                float* h_up_w, int32_t* h_up_first);
+HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_geometry(int32_t source_rate, int32_t* h_geometry);
+HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_run(hipfeat_narrowband* narrowband, const float* d_x, float* d_out, int64_t rows, int64_t cols,
+                                                             int64_t in_row_stride, int64_t out_row_stride, const int64_t* d_lengths, int32_t restore,
+                                                             void* stream);
 
 /* ---- bulk save path: the per-batch host work of the offline driver ------------------------------- */
 /*

@@ -22,6 +22,7 @@ from .augmentation import COLLATE_TILE, HipCollator, collate_in_arena, get_or_cr
 from .augmentation import COLLATE_MAX_SOURCES, collate_sources_in_arena, collate_sources_layout  # noqa: F401,E402
 from .augmentation import resample_in_arena, resample_layout, resampled_tail_floats  # noqa: F401,E402
 from .augmentation import HipSincResampler, get_or_create_sinc, sinc_in_arena  # noqa: F401,E402
+from .augmentation import HipNarrowband, narrowband_geometry, narrowband_on_device  # noqa: F401,E402
 from .augmentation import HipMixer, HipResample, HipResampleTensor, HipSpeed, HipSpeedBank, get_or_create_resampler, mix_in_arena, mixed_tail_floats  # noqa: F401,E402
 
 from .kaldifeat import (  # noqa: F401,E402
@@ -124,6 +125,9 @@ __all__ = [
     "HipSincResampler",
     "get_or_create_sinc",
     "sinc_in_arena",
+    "HipNarrowband",
+    "narrowband_on_device",
+    "narrowband_geometry",
     "resample_layout",
     "resampled_tail_floats",
     "HipResample",

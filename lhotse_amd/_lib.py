@@ -275,9 +275,20 @@ _NOISE_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
          "float", "void*"],
     ),
 }
+# Likewise (HIPFEAT_NARROWBAND_API in the header): Narrowband(codec="mulaw") on a waveform batch, one fused launch per call.
+_NARROWBAND_SIGNATURES: Dict[str, Tuple[str, List[str]]] = {
+    "hipfeat_narrowband_create": ("int", ["int32_t", "hipfeat_narrowband**"]),
+    "hipfeat_narrowband_destroy": ("int", ["hipfeat_narrowband*"]),
+    "hipfeat_narrowband_tables": ("int", ["int32_t", "int32_t*", "float*", "int32_t*", "float*", "int32_t*"]),
+    "hipfeat_narrowband_geometry": ("int", ["int32_t", "int32_t*"]),
+    "hipfeat_narrowband_run": (
+        "int",
+        ["hipfeat_narrowband*", "const float*", "float*", "int64_t", "int64_t", "int64_t", "int64_t", "const int64_t*", "int32_t", "void*"],
+    ),
+}
 _ADDED_SIGNATURES = {**_LEVEL_SIGNATURES, **_COLLATE_SIGNATURES, **_SINC_SIGNATURES, **_FEATMIX_SIGNATURES, **_STATS_SIGNATURES, **_STFT_SIGNATURES,
                      **_STREAM_SIGNATURES, **_GRAD_SIGNATURES, **_CHANNELS_SIGNATURES, **_REVERB_FFT_SIGNATURES, **_RAGGED_SIGNATURES, **_WPE_SIGNATURES,
-                     **_WPESTFT_SIGNATURES, **_NOISE_SIGNATURES}
+                     **_WPESTFT_SIGNATURES, **_NOISE_SIGNATURES, **_NARROWBAND_SIGNATURES}
 
 
 def _signature(name: str) -> Tuple[str, List[str]]:
@@ -390,7 +401,7 @@ class _CffiBackend:
             decl.append(line.replace("HIPFEAT_API ", "").replace("HIPFEAT_LEVEL_API ", "").replace("HIPFEAT_COLLATE_API ", "").replace("HIPFEAT_SINC_API ", "")
                         .replace("HIPFEAT_FEATMIX_API ", "").replace("HIPFEAT_STATS_API ", "").replace("HIPFEAT_STFT_API ", "").replace("HIPFEAT_STREAM_API ", "")
                         .replace("HIPFEAT_GRAD_API ", "").replace("HIPFEAT_CHANNELS_API ", "").replace("HIPFEAT_REVERB_FFT_API ", "").replace("HIPFEAT_RAGGED_API ", "")
-                        .replace("HIPFEAT_WPE_API ", "").replace("HIPFEAT_WPESTFT_API ", "").replace("HIPFEAT_NOISE_API ", ""))
+                        .replace("HIPFEAT_WPE_API ", "").replace("HIPFEAT_WPESTFT_API ", "").replace("HIPFEAT_NOISE_API ", "").replace("HIPFEAT_NARROWBAND_API ", ""))
         self.ffi.cdef("\n".join(decl))
         self.dll = self.ffi.dlopen(path)
         self.fns = {name: getattr(self.dll, name) for name in _SIGNATURES}

@@ -1505,3 +1505,111 @@ def featmix_in_arena(arena_bytes: torch.Tensor, cuts_table: Sequence[FeatCut], F
     ticket, _ = mixer.plan(lay)
     mixer.run(ticket, arena_bytes, res)
     return res, lens
+
+
+# ---- Narrowband: the mu-law telephone channel (down to 8 kHz, codec, back up) in one fused launch ---------------------------------
+class _NarrowbandPlan:
+    """The library's handle of one source rate on one device (``hipfeat_narrowband``, csrc/kernel_narrowband.hpp), its tables staged once."""
+
+    def __init__(self, rate: int, device: torch.device):
+        self.lib = _lib.load()
+        self.rate, self.device, self.handle = int(rate), device, 0
+        out = np.zeros(1, dtype=np.uint64)
+        with torch.cuda.device(device):
+            try:
+                self.lib.check("hipfeat_narrowband_create", self.rate, _lib.addr(out))
+            except _lib.HipFeatError as e:
+                if e.status == _lib.ERR_UNSUPPORTED:
+                    raise NotImplementedError(str(e)) from e
+                raise
+        self.handle = int(out[0])
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.raw("hipfeat_narrowband_destroy", self.handle)
+        except Exception:
+            pass
+
+
+_narrowbands: Dict[Tuple[int, int], _NarrowbandPlan] = {}
+_narrowband_lock = threading.Lock()
+
+
+def narrowband_geometry(source_sampling_rate: int) -> dict:
+    """The launch geometry of a source rate as the library reports it (host only): the 8 kHz samples of a tile, the samples in front
+    of and behind a tile that its output windows reach, and the dynamic LDS bytes."""
+    g = np.zeros(4, dtype=np.int32)
+    _lib.load().check("hipfeat_narrowband_geometry", int(source_sampling_rate), _lib.addr(g))
+    return {"tile": int(g[0]), "halo_front": int(g[1]), "halo_back": int(g[2]), "lds_bytes": int(g[3])}
+
+
+def narrowband_on_device(x: torch.Tensor, source_sampling_rate: int, *, restore_orig_sr: bool = True, lengths=None, out: Optional[torch.Tensor] = None):
+    """``Narrowband(codec="mulaw", source_sampling_rate, restore_orig_sr)`` (lhotse/augmentation/torchaudio.py:337-378) of every row of
+    ``x`` in one launch: resampled to 8 kHz, through ``MuLawEncoding(256)`` / ``MuLawDecoding(256)``, resampled back; the 8 kHz signal
+    stays in LDS (the rule: include/hipfeat.h).  ``x``: float32 ``(B, T)`` or ``(T,)`` on the device, any row stride, unit sample
+    stride.  ``lengths``: one integer per row, CPU or device: a row is taken alone up to its length, what lies behind is never used and
+    comes out as +0.0.  Returns the tensor -- ``x``'s shape with ``restore_orig_sr`` (or at 8 kHz), else ``ceil(8000 T / rate)`` samples
+    per row -- or, with ``restore_orig_sr=False`` and ``lengths``, ``(tensor, out_lengths)`` with ``out_lengths`` where ``lengths``
+    lives.  ``out``: a float32 tensor of the result's shape, unit sample stride, that does not overlap ``x``."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise _lib.HipFeatError(_lib.ERR_INVALID, "narrowband_on_device runs on an AMD GPU: pass a float32 tensor on a 'cuda' device (there is no CPU fallback)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"narrowband_on_device: expected float32 samples, got {x.dtype}")
+    if x.ndim not in (1, 2):
+        raise ValueError("narrowband_on_device expects (B, T) or (T,) samples")
+    rate = int(source_sampling_rate)
+    B, T = (1, x.shape[0]) if x.ndim == 1 else x.shape
+    if T > 1 and x.stride(-1) != 1 or (x.ndim == 2 and B > 1 and x.stride(0) < T):
+        x = x.contiguous()
+    lib = _lib.load()
+    index = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with _narrowband_lock:
+        plan = _narrowbands.get((rate, index))
+        if plan is None:
+            plan = _narrowbands[(rate, index)] = _NarrowbandPlan(rate, torch.device("cuda", index))
+    up = bool(restore_orig_sr) or rate == 8000
+    g = np.gcd(rate, 8000)
+    T_out = T if up else int(lib.raw("hipfeat_resampled_length", T, rate // g, 8000 // g))
+    shape = (T_out,) if x.ndim == 1 else (B, T_out)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device or (T_out > 1 and out.stride(-1) != 1):
+        raise ValueError(f"narrowband_on_device: `out` must be a float32 tensor of shape {shape} on x's device with unit sample stride")
+    lens = out_lengths = None
+    if lengths is not None:
+        given = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths))
+        if given.ndim != 1 or given.numel() != B or given.dtype.is_floating_point:
+            raise ValueError(f"narrowband_on_device: lengths must be {B} integers")
+        lens = given.to(device=x.device, dtype=torch.int64).contiguous()
+        if not restore_orig_sr:  # resample.py:309 in the arithmetic of hipfeat_resampled_length, where the lengths live
+            n = given.to(torch.int64).clamp(0, T)
+            out_lengths = n if rate == 8000 else (n.double() * (8000 // g) / (rate // g)).float().ceil().to(torch.int64)
+    strides = [T if B == 1 or t.ndim == 1 else t.stride(0) for t in (x, out)]
+    with torch.cuda.device(x.device):
+        lib.check("hipfeat_narrowband_run", plan.handle, x.data_ptr(), out.data_ptr(), B, T, strides[0] if B > 1 else T, strides[1] if B > 1 else T_out,
+                  None if lens is None else lens.data_ptr(), 1 if restore_orig_sr else 0, int(_raw_stream(x.device)))
+    return (out, out_lengths) if out_lengths is not None else out
+
+
+@dataclass
+class HipNarrowband(AudioTransform):
+    """The narrowband (telephone channel) effect on the GPU; the twin of ``lhotse.augmentation.Narrowband`` (torchaudio.py:337-391) for
+    ``codec="mulaw"``.  ``codec="lpc10"`` is spandsp's code and is not served."""
+
+    codec: str
+    source_sampling_rate: int
+    restore_orig_sr: bool
+
+    def __post_init__(self):
+        if self.codec == "lpc10":
+            raise NotImplementedError("HipNarrowband: codec='lpc10' is not served on the device (only 'mulaw' is)")
+        if self.codec != "mulaw":
+            raise ValueError(f"unsupported codec: {self.codec}")
+
+    def __call__(self, samples: torch.Tensor, sampling_rate: Optional[int] = None, *, lengths=None):
+        return narrowband_on_device(samples, self.source_sampling_rate, restore_orig_sr=self.restore_orig_sr, lengths=lengths)
+
+    def reverse_timestamps(self, offset: Seconds, duration: Optional[Seconds], sampling_rate: Optional[int]) -> Tuple[Seconds, Optional[Seconds]]:
+        """The narrowband effect changes no timing (torchaudio.py:380-391)."""
+        return offset, duration

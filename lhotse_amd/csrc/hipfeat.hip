@@ -52,6 +52,7 @@
 #include "host_bulk.hpp"
 #include "kernel_wpe.hpp"
 #include "kernel_wpe_stft.hpp"
+#include "kernel_narrowband.hpp"
 #include "kernel_noise.hpp"
 
 using namespace hipfeat;
@@ -3788,6 +3789,118 @@ extern "C" HIPFEAT_NOISE_API hipfeat_status hipfeat_noise_run(const void* d_in, 
   void* args[] = {&p};
   hipError_t e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(kNoiseThreads), args, 0, (hipStream_t)stream);
   if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "noise launch failed: %s", hipGetErrorName(e));
+  return HIPFEAT_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Narrowband(codec="mulaw") on a waveform batch (kernel_narrowband.hpp; the tables: narrowband_tables.hpp): a handle per source rate
+// with its blob staged once, one launch per call on the caller's stream
+// --------------------------------------------------------------------------------------
+struct hipfeat_narrowband {
+  int device = 0;
+  NbPlan plan;      // (weights and first taps are dropped once the blob is staged)
+  StagedSlot slot;  // device: the blob
+};
+
+extern "C" HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_destroy(hipfeat_narrowband* h) {
+  if (!h) return HIPFEAT_OK;
+  DeviceGuard guard(h->device);
+  h->slot.free_all();
+  delete h;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_geometry(int32_t source_rate, int32_t* h_geometry) {
+  if (!h_geometry) return fail(HIPFEAT_ERR_INVALID, "narrowband: NULL geometry");
+  const NbPlan p = build_nb_plan(source_rate, false, nullptr);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  h_geometry[0] = p.M, h_geometry[1] = p.halo_lo, h_geometry[2] = p.halo_hi, h_geometry[3] = (int32_t)p.lds_bytes;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_tables(int32_t source_rate, int32_t* h_dims, float* h_down_w, int32_t* h_down_first,
+                                                                           float* h_up_w, int32_t* h_up_first) {
+  if (!h_dims) return fail(HIPFEAT_ERR_INVALID, "narrowband: NULL dims");
+  const bool want = h_down_w || h_down_first || h_up_w || h_up_first;
+  const NbPlan p = build_nb_plan(source_rate, want, nullptr);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  const NbFilter* fs[2] = {&p.down, &p.up};
+  float* ws[2] = {h_down_w, h_up_w};
+  int32_t* firsts[2] = {h_down_first, h_up_first};
+  for (int k = 0; k < 2; ++k) {  // (rate == 8000: no filter, all zero)
+    h_dims[4 * k] = fs[k]->orig, h_dims[4 * k + 1] = fs[k]->nw, h_dims[4 * k + 2] = fs[k]->width, h_dims[4 * k + 3] = fs[k]->W;
+    if (ws[k] && !fs[k]->w.empty()) std::memcpy(ws[k], fs[k]->w.data(), sizeof(float) * fs[k]->w.size());
+    if (firsts[k] && !fs[k]->first.empty()) std::memcpy(firsts[k], fs[k]->first.data(), sizeof(int32_t) * fs[k]->first.size());
+  }
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_create(int32_t source_rate, hipfeat_narrowband** out) {
+  if (!out) return fail(HIPFEAT_ERR_INVALID, "narrowband pointer is NULL");
+  *out = nullptr;
+  std::vector<float> blob;
+  NbPlan p = build_nb_plan(source_rate, true, &blob);
+  if (p.status != 0) return fail((hipfeat_status)p.status, "%s", p.message.c_str());
+  int device = 0;
+  HIP_TRY(hipGetDevice(&device));
+  if (hipfeat_status bad = require_gfx950(device)) return bad;
+  hipfeat_narrowband* h = new (std::nothrow) hipfeat_narrowband();
+  if (!h) return fail(HIPFEAT_ERR_INVALID, "out of host memory");
+  h->device = device;
+  h->plan = std::move(p);
+  h->plan.down.w = std::vector<float>(), h->plan.up.w = std::vector<float>();
+  hipfeat_status st = HIPFEAT_OK;
+  if (!blob.empty()) {
+    const size_t bytes = sizeof(float) * blob.size();
+    hipError_t e = stage(h->slot, bytes, bytes, nullptr, [&](unsigned char* dst) { std::memcpy(dst, blob.data(), bytes); });
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) st = fail(HIPFEAT_ERR_HIP, "staging the narrowband tables failed: %s", hipGetErrorName(e));
+  }
+  if (st == HIPFEAT_OK) st = set_dynamic_lds(entry<narrowband_kernel>(), (size_t)h->plan.lds_bytes);
+  if (st != HIPFEAT_OK) {
+    hipfeat_narrowband_destroy(h);
+    return st;
+  }
+  *out = h;
+  return HIPFEAT_OK;
+}
+
+extern "C" HIPFEAT_NARROWBAND_API hipfeat_status hipfeat_narrowband_run(hipfeat_narrowband* h, const float* d_x, float* d_out, int64_t rows, int64_t cols,
+                                                                        int64_t in_row_stride, int64_t out_row_stride, const int64_t* d_lengths,
+                                                                        int32_t restore, void* stream) {
+  if (!h) return fail(HIPFEAT_ERR_INVALID, "narrowband: NULL handle");
+  if (rows < 0 || cols < 0) return fail(HIPFEAT_ERR_INVALID, "narrowband: negative size");
+  if (cols > kNbMaxCols) return fail(HIPFEAT_ERR_INVALID, "narrowband: rows of %lld samples, at most 2^30", (long long)cols);
+  if (in_row_stride < cols || out_row_stride < 0)
+    return fail(HIPFEAT_ERR_INVALID, "narrowband: row strides of %lld and %lld samples for rows of %lld", (long long)in_row_stride, (long long)out_row_stride, (long long)cols);
+  if (rows == 0 || cols == 0) return HIPFEAT_OK;
+  if (!d_x || !d_out) return fail(HIPFEAT_ERR_INVALID, "narrowband: NULL buffer");
+  if ((((uintptr_t)d_x | (uintptr_t)d_out) & 3) || ((uintptr_t)d_lengths & 7))
+    return fail(HIPFEAT_ERR_INVALID, "narrowband: samples must lie on 4-byte boundaries, lengths on an 8-byte one");
+  const NbPlan& p = h->plan;  // (the handle is followed from here on)
+  const bool up = restore != 0 && !p.passthrough;
+  const int64_t l8 = p.passthrough ? cols : sinc_out_len(cols, p.down.orig, p.down.nw), out_cols = up ? cols : l8;
+  if (out_row_stride < out_cols)
+    return fail(HIPFEAT_ERR_INVALID, "narrowband: an output row stride of %lld samples for rows of %lld", (long long)out_row_stride, (long long)out_cols);
+  NbArgs a{};
+  a.x = d_x, a.out = d_out, a.lengths = d_lengths, a.tables = static_cast<const float*>(h->slot.d);
+  a.cols = cols, a.out_cols = out_cols, a.in_row = in_row_stride, a.out_row = out_row_stride;
+  a.restore = up ? 1 : 0, a.passthrough = p.passthrough ? 1 : 0;
+  a.orig_d = p.down.orig, a.new_d = p.down.nw, a.W_d = p.down.W, a.np_d = p.down.np, a.orig_u = p.up.orig, a.new_u = p.up.nw, a.np_u = p.up.np;
+  a.M = p.M, a.halo_lo = p.halo_lo, a.halo_hi = p.halo_hi, a.span_cap = p.span_cap;
+  a.off_wd = p.off_wd, a.off_wu = p.off_wu, a.off_sd = p.off_sd, a.off_su = p.off_su, a.off_x = p.off_x, a.off_q = p.off_q, a.table_floats = p.table_floats;
+  a.tiles = (int32_t)((l8 + p.M - 1) / p.M);
+  // tiles of a workgroup: the tables are copied into LDS once per workgroup, so long rows take up to 8 per workgroup while the launch
+  // keeps about kNbFillWorkgroups workgroups
+  constexpr int64_t kNbFillWorkgroups = 2048;
+  a.tiles_per_wg = (int32_t)std::min<int64_t>(8, std::max<int64_t>(1, rows * a.tiles / kNbFillWorkgroups));
+  a.wgs_per_row = (a.tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
+  if (rows > INT32_MAX / a.wgs_per_row) return fail(HIPFEAT_ERR_UNSUPPORTED, "narrowband: more than 2^31 - 1 workgroups in one call");
+  void* args[] = {&a};
+  DeviceGuard guard(h->device);
+  set_lds_poison((size_t)p.lds_bytes);
+  const hipError_t e = hipLaunchKernel(entry<narrowband_kernel>(), dim3((unsigned)(rows * a.wgs_per_row)), dim3(kNbThreads), args, (size_t)p.lds_bytes, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(HIPFEAT_ERR_HIP, "narrowband launch failed: %s", hipGetErrorName(e));
   return HIPFEAT_OK;
 }
 
